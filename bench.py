@@ -2,7 +2,12 @@
 """bench.py -- the headline measurement (BASELINE.json): PrimalCR++ pairwise-comparisons/sec
 + NDCG@10 on ml1m-shaped synthetic ratings, rank 100, lambda 5000, on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs the W warm-up steps, times the K steps (no HIP-event pairs in the timed region) and prints the
+line: metric, value, unit, ms_per_step, dtype, config and what the timed steps give for free (objective, inner counts).
+--dump-outputs DIR writes what the timed steps computed (U, V, the objective of each timed step) as DIR/<name>.npy.
+--full adds everything else below (the timed region then carries the sampled event pairs the roofline is built from).
 
 N > 1 without a launcher: the N ranks are started as direct CHILD processes (RANK / WORLD_SIZE / MASTER_* in
 their environment, 127.0.0.1 rendezvous) before this process imports torch or touches a GPU, and rank 0's
@@ -23,7 +28,7 @@ product are all-reduced over RCCL.
   --shape netflix  configs[3]: 480 189 x 17 770, 100 M ratings, nnz-balanced user ranges (strong scaling)
   --shape yahoo    configs[4]: 1.8 M x 136 k, 700 M ratings, k = 200: the first 225 000 N users (N = 8: all of them)
 
-The JSON line also carries
+With --full the JSON line also carries (and the full record goes to bench_full.json)
   roofline      the kernel slot with the most GPU time: algorithmic bytes per launch / its average duration
                 from HIP events on its launch stream, against the 8 TB/s HBM3E peak -- and `binding`: the level of the
                 memory hierarchy that actually serves its row gathers (l2-gather / mall-gather / hbm-gather by the size of
@@ -494,9 +499,11 @@ def make_shard(shape, job, users=None, nnz=None):
     return R, u0, total, "strong", int(index[-1])
 
 
-def timed_run(job, ds, shard, d2, r, lam, prec, steps, warmup, profile, shm_name, count_rows=False, cold_start=True):
+def timed_run(job, ds, shard, d2, r, lam, prec, steps, warmup, profile, shm_name, count_rows=False, cold_start=True, quality=True,
+              keep_factors=False):
     """One solver, `warmup` untimed + exactly `steps` timed outer iterations (barrier + synchronize on both sides, MAX over
-    ranks), then the quality after warmup + steps iterations."""
+    ranks), then (quality) the quality after warmup + steps iterations; keep_factors: this rank's factors as the timed steps
+    left them."""
     import primalcr_amd as pcr
     args, torch, dist, rank, N = job.args, job.torch, job.dist, job.rank, job.N
     first, total = shard
@@ -573,13 +580,16 @@ def timed_run(job, ds, shard, d2, r, lam, prec, steps, warmup, profile, shm_name
             inner[key] += rec[key]
     barrier()
     secs = job.allmax(time.perf_counter() - t0)
+    factors = s.get_factors_local() if keep_factors else None
     prof = s.profile_all() if profile else {}
     launches = {name: s.profile_launches(name) for name in prof}
     scope = {name: s.profile_scope(name) for name in prof}
     s.profile(False)
     rows_by_class = s.class_row_gathers() if count_rows else {}
-    te_err, te_ndcg = s.evaluate(1, 10)           # the quality after warmup + steps iterations (before the replay below)
-    tr_err, tr_ndcg = s.evaluate(0, 10)
+    te_err, te_ndcg, tr_err, tr_ndcg = None, None, None, None
+    if quality:                                   # the quality after warmup + steps iterations (before the replay below)
+        te_err, te_ndcg = s.evaluate(1, 10)
+        tr_err, tr_ndcg = s.evaluate(0, 10)
     comm_n, shard_now = s.comm_nranks(), (s.first_user, s.n_users, s.nnz_local)
     # what the event pairs cost the timed region: the same K steps once more, straight after, without them (same clock)
     noev = None
@@ -621,9 +631,38 @@ def timed_run(job, ds, shard, d2, r, lam, prec, steps, warmup, profile, shm_name
             hb = dict(busy_percent=bp, samples=ns, steps=n_rep, secs=dt, source=src)
     out = dict(secs=secs, secs_noevents=noev, create_s=t_create, objs=objs, inner=inner, prof=prof, launches=launches, scope=scope, prof_period=prof_period, cold=cold, hbm=hb,
                u_rows=s.counter("ustep_row_gathers") - rows0, rows_by_class=rows_by_class, steps=steps,
-               te=(te_err, te_ndcg), tr=(tr_err, tr_ndcg), comm_nranks=comm_n, shard=shard_now, comm_used=comm_used)
+               te=(te_err, te_ndcg), tr=(tr_err, tr_ndcg), comm_nranks=comm_n, shard=shard_now, comm_used=comm_used, factors=factors)
     s.close()
     return out
+
+
+DUMP_CAP = 64 << 20     # bytes: everything --dump-outputs writes, all ranks together
+
+
+def dump_outputs(path, run, rank, N):
+    """--dump-outputs: what the timed steps computed, as a caller of the training path receives it -- this rank's rows of U and V
+    as the last timed step left them (float64, pcr_solver_get_factors_local) and the objective after each timed step -- as
+    path/<name>.npy.  Factors beyond the rank's share of DUMP_CAP are cut to a fixed, seeded sample of their rows (the same
+    rows from run to run), whose indices go to path/<name>_rows.npy.  N > 1: every rank writes its own U_rank<q>.npy; rank 0
+    writes V and the objective."""
+    os.makedirs(path, exist_ok=True)
+    U, V = run["factors"]
+    mats = {("U" if N == 1 else f"U_rank{rank}"): U}
+    if rank == 0:
+        mats["V"] = V
+        objs = run["objs"]
+        np.save(os.path.join(path, "objective.npy"), np.asarray(objs[len(objs) - run["steps"]:], np.float64))
+    budget = (DUMP_CAP - (1 << 20)) // N                                   # (1 MiB for the objective and the file headers)
+    total = sum(a.nbytes for a in mats.values())
+    sampled = sum(a.nbytes + 8 * a.shape[0] for a in mats.values())         # (a sample also writes its row indices)
+    for name, a in mats.items():
+        a = np.ascontiguousarray(a, np.float64)
+        if total > budget and a.shape[0] > 1:
+            m = max(1, int(a.shape[0] * budget / sampled * 0.95))
+            rows = np.sort(np.random.default_rng(20261004).choice(a.shape[0], m, replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def analyse(run, rows_run, wl, prec_name, N, traffic_key, verbose=False, live=None, live_iters=0):
@@ -833,8 +872,10 @@ def analyse(run, rows_run, wl, prec_name, N, traffic_key, verbose=False, live=No
 
 
 def measure(job, shape, r, lam, steps, warmup, users=None, nnz=None, precisions=("f32", "f64"), profile=True, cpu=True,
-            cpu_sample=2_000_000, cpu_single=True, verbose=False, cli=None):
-    """Generate this rank's shard of `shape`, run the timed legs, return rank 0's record (None on the other ranks)."""
+            cpu_sample=2_000_000, cpu_single=True, verbose=False, cli=None, full=True, dump=None):
+    """Generate this rank's shard of `shape`, run the timed legs, return rank 0's record (None on the other ranks).
+    full=False: the headline's timed run alone (no quality evaluation, no roofline analysis).  dump: the directory the first
+    precision's outputs go to (dump_outputs)."""
     import primalcr_amd as pcr
     from primalcr_amd import synth
     args, rank, N = job.args, job.rank, job.N
@@ -856,7 +897,11 @@ def measure(job, shape, r, lam, steps, warmup, users=None, nnz=None, precisions=
     runs = {}
     for pn in precisions:
         prec = pcr.PCR_F32 if pn == "f32" else pcr.PCR_F64
-        runs[pn] = timed_run(job, ds, shard, R.d2, r, lam, prec, steps, warmup, profile, shm)
+        first_leg = pn == precisions[0]
+        runs[pn] = timed_run(job, ds, shard, R.d2, r, lam, prec, steps, warmup, profile, shm, quality=full,
+                             keep_factors=first_leg and dump is not None)
+        if first_leg and dump is not None:
+            dump_outputs(dump, runs[pn], rank, N)
         # diagnostic replay of the same iterations with the U-step kernels counting the rows of V they gather (an extra atomic
         # per user, so it is kept out of the timed run): the rating-weighted pass count of the U step, per length class
         runs[pn]["rows"] = None
@@ -876,6 +921,14 @@ def measure(job, shape, r, lam, steps, warmup, users=None, nnz=None, precisions=
     main_p = precisions[0]
     run = runs[main_p]
     secs, objs, inner = run["secs"], run["objs"], run["inner"]
+    value = n_pairs * steps / secs
+    workload = f"{note}; {total} users x {R.d2} items, {nnz_job} ratings, {n_pairs} ordered pairs; 1 step = 1 outer iteration (V step + U step)"
+    if not full:
+        return {"value": value, "unit": "pairs/s", "ms_per_step": 1e3 * secs / steps, "steps": steps, "warmup": warmup,
+                "solver_create_s": run.get("create_s"), "dtype": main_p, "scaling": scaling, "workload": workload,
+                "objective": objs[-1], "inner_per_step": {k: v / steps for k, v in inner.items()},
+                "comm_nranks": run["comm_nranks"], "comm_used": run.get("comm_used"), "shards": bounds,
+                "ms_per_step_first5": run["cold"]["ms_per_step"] if run["cold"] and run["cold"]["iterations"] == 5 else None}
     whole_yahoo = shape == "yahoo" and users == synth.SHAPES["yahoo"][0] and nnz is None          # configs[4] itself on one GPU
     tkey = (f"{shape}{'-whole' if whole_yahoo else ''}:{main_p}"
             if ((users is None or whole_yahoo) and nnz is None and N == 1 and r == (200 if shape == "yahoo" else 100)) else None)
@@ -886,7 +939,6 @@ def measure(job, shape, r, lam, steps, warmup, users=None, nnz=None, precisions=
                                               users=users if whole_yahoo else None)
         log("[traffic] live rocprofv3 --pmc pass: " + (f"{took:.0f} s, {live_iters} iterations replayed" if live else f"not available ({took}): stored passes used"))
     an = analyse(run, run["rows"], wl, main_p, N, tkey, verbose, live, live_iters)
-    value = n_pairs * steps / secs
     rec = {
         "value": value, "unit": "pairs/s", "ms_per_step": 1e3 * secs / steps, "s_per_iter": secs / steps, "steps": steps, "warmup": warmup,
         # the timed region carries the HIP-event pairs the roofline's durations come from; the same K steps straight after, without them:
@@ -894,8 +946,7 @@ def measure(job, shape, r, lam, steps, warmup, users=None, nnz=None, precisions=
         "profile_overhead_pct": None if not run.get("secs_noevents") else 100.0 * (secs / run["secs_noevents"] - 1.0),
         "solver_create_s": run.get("create_s"),          # rank 0's pcr_solver_create: off the timed region (the reference's convert(), util.cpp:219-274)
         "dtype": main_p, "scaling": scaling,
-        "workload": f"{note}; {total} users x {R.d2} items, {nnz_job} ratings, {n_pairs} ordered pairs; 1 step = 1 outer "
-                    f"iteration (V step + U step)",
+        "workload": workload,
         "ndcg10_test": run["te"][1], "pairwise_error_test": run["te"][0], "ndcg10_train": run["tr"][1], "pairwise_error_train": run["tr"][0],
         "outer_iterations_run": warmup + steps, "objective": objs[-1],
         "inner_per_step": {k: v / steps for k, v in inner.items()},
@@ -1128,6 +1179,18 @@ def compact_line(full, full_record_path=None):
     return line
 
 
+def plain_line(rec):
+    """The stdout line of a run without --full: the contract's header and the few figures the timed steps give for free."""
+    line = {k: rec.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                                    "vs_baseline", "dtype", "data", "config")}
+    line.update(objective=_r(rec.get("objective"), 9), inner_per_step=rec.get("inner_per_step"),
+                ms_per_step_first5=_r(rec.get("ms_per_step_first5"), 5), solver_create_s=_r(rec.get("solver_create_s"), 3),
+                comm_nranks=rec.get("comm_nranks"))
+    if rec.get("shards"):
+        line["shards"] = rec["shards"] if len(rec["shards"]) <= 8 else None
+    return line
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -1321,6 +1384,12 @@ def main():
     ap.add_argument("--rendezvous", choices=["nccl", "gloo"], default="nccl", help="torch.distributed backend of the barriers and the id broadcast")
     ap.add_argument("--tune", action="append", default=[], help="key=value launch knob (pcr_tune), repeatable -- for A/B runs")
     ap.add_argument("--lib", default=None, help="A/B: load this libprimalcr.so instead of primalcr_amd/lib/libprimalcr.so")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what they computed (U, V, the objective of each timed step) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel event timing, roofline and traffic passes, quality, the fp64 leg, "
+                         "the row-counting replay, the HBM replay, cpu_baseline, the CLI leg, the Netflix-shaped leg and the full "
+                         "record file (the --no-* options below switch parts of it off).  Without it: the timed steps and the line")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-f64", action="store_true", help="skip the second timed run in the reference's arithmetic type")
     ap.add_argument("--no-netflix", action="store_true", help="skip the Netflix-shaped sub-record (the default N = 1 run; every N > 1 run of the ml1m shape)")
@@ -1364,11 +1433,24 @@ def main():
             os._exit(int(f[2]))
         os.kill(os.getpid(), int(f[1]))
         time.sleep(30)
+    import signal
+
+    # A launcher that sees one rank fail sends SIGTERM to the others, maybe while they are still importing torch: until this rank
+    # holds its GPU it says so rather than vanish without a word.  (Afterwards the default action stands: SIGTERM must also end a
+    # rank that waits in a collective whose peer is gone.)
+    def stopped_early(sig, _frame):
+        log(f"[rank {rank}] stopped by SIGTERM before it held its GPU: the launcher is ending the job")
+        if rank == 0:
+            error_line("rank 0 stopped by SIGTERM before it held its GPU", rank=0)
+        sys.stdout.flush(); sys.stderr.flush()
+        os._exit(128 + sig)
+    signal.signal(signal.SIGTERM, stopped_early)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: no GPU visible (there is no CPU fallback for the training path)")
     device = int(args.devices.split(",")[local_rank]) if args.devices else local_rank
     torch.cuda.set_device(device)
+    signal.signal(signal.SIGTERM, signal.SIG_DFL)
     dist = None
     if N > 1:
         import torch.distributed as dist
@@ -1399,10 +1481,15 @@ def main():
     if N > 1 and not args.all_legs:
         args.no_f64 = True
         args.no_rows = True
+    if not args.full:
+        # the plain run: the headline's timed steps and nothing else -- no HIP-event pairs in the timed region, no other leg
+        args.no_f64 = args.no_rows = args.no_cpu = args.no_cli = args.no_netflix = args.no_profile = True
+        args.live_traffic = args.hbm = False
     precisions = (args.precision,) if (args.no_f64 or args.precision == "f64") else ("f32", "f64")
     default_run = (N == 1 and args.shape == "ml1m" and args.users is None and args.nnz is None and args.rank_k is None and args.precision == "f32")
     rec = measure(job, args.shape, r, lam, args.steps, args.warmup, args.users, args.nnz, precisions, not args.no_profile,
-                  not args.no_cpu, verbose=args.verbose, cli={} if (default_run and not args.no_cli) else None)
+                  not args.no_cpu, verbose=args.verbose, cli={} if (default_run and not args.no_cli) else None, full=args.full,
+                  dump=args.dump_outputs)
     # configs[3] in the driver's line: the default N = 1 run also times a few steps of the Netflix-shaped set (north star "Target")
     nf = None
     if (N == 1 and args.shape == "ml1m" and not args.no_netflix and args.users is None and args.nnz is None and args.rank_k is None
@@ -1425,6 +1512,9 @@ def main():
         """Rank 0: the full record to its file, the ONE compact line to stdout."""
         if netflix:
             out["netflix"] = netflix
+        if not args.full:
+            print(json.dumps(out if args.full_line else plain_line(out), separators=(",", ":")), flush=True)
+            return
         # The driver reads the LAST stdout line and keeps only a few KB of it: the line is the compact summary (< 5 KB, every
         # field the contract names + roofline + cpu_baseline), the full record (per-kernel tables, phases, notes) goes to a file.
         full_path = args.full_record or os.path.join(ROOT, "bench_full.json")

@@ -90,7 +90,7 @@ def test_a_rank_that_dies_is_named_and_takes_the_job_down(n, fault, want):
 def test_two_ranks_on_one_gpu_equal_one_rank():
     users, nnz, r, steps, warmup = 2000, 250000, 100, 2, 1
     p = run_bench("--gpus", "2", "--comm", "p2p", "--devices", "0,0", "--rendezvous", "gloo", "--steps", str(steps), "--warmup",
-                  str(warmup), "--users", str(users), "--nnz", str(nnz), "--no-cpu", "--no-f64", "--all-legs",   # (--all-legs: with the row-counting replay)
+                  str(warmup), "--users", str(users), "--nnz", str(nnz), "--full", "--no-cpu", "--no-f64", "--all-legs",   # (--all-legs: with the row-counting replay)
                   "--netflix-users", "6000", "--netflix-nnz", "600000")
     assert p.returncode == 0, p.stderr[-3000:]
     assert len([l for l in p.stdout.strip().split("\n") if l.startswith("{")]) == 1          # ONE line per run, whatever the legs
@@ -159,7 +159,7 @@ def test_a_failing_netflix_leg_never_costs_the_headline():
     import time
     t0 = time.time()
     p = run_bench("--gpus", "2", "--comm", "p2p", "--devices", "0,0", "--rendezvous", "gloo", "--steps", "2", "--warmup", "1", "--users", "800",
-                  "--nnz", "100000", "--no-cpu", "--no-f64", "--no-rows", "--netflix-users", "3000", "--netflix-nnz", "200000", "--fault-netflix", "1")
+                  "--nnz", "100000", "--full", "--no-cpu", "--no-f64", "--no-rows", "--netflix-users", "3000", "--netflix-nnz", "200000", "--fault-netflix", "1")
     assert p.returncode == 0 and time.time() - t0 < 300, p.stderr[-3000:]
     lines = [l for l in p.stdout.strip().split("\n") if l.startswith("{")]
     assert len(lines) == 1
@@ -178,7 +178,7 @@ def test_five_ranks_on_one_gpu_through_the_bench_launcher():
     one ONE solver reaches on the same 5 x 500 users."""
     n, users, nnz, steps, warmup = 5, 500, 60000, 2, 1
     p = run_bench("--gpus", str(n), "--comm", "p2p", "--devices", ",".join(["0"] * n), "--rendezvous", "gloo", "--steps", str(steps),
-                  "--warmup", str(warmup), "--users", str(users), "--nnz", str(nnz), "--no-cpu", "--no-f64", "--no-rows", "--no-netflix")
+                  "--warmup", str(warmup), "--users", str(users), "--nnz", str(nnz), "--full", "--no-cpu", "--no-f64", "--no-rows", "--no-netflix")
     assert p.returncode == 0, p.stderr[-3000:]
     assert f"starting {n} ranks (direct children" in p.stderr
     line = json.loads(p.stdout.strip().split("\n")[-1])
@@ -228,7 +228,7 @@ def test_two_ranks_under_the_drivers_launcher():
     scaling curve: bench.py is one of the ranks (RANK / WORLD_SIZE from the launcher), rank 0 prints the one line.  Two ranks on the
     one GPU through the peer-to-peer exchange; the line equals the one bench.py's own launcher gives for the same job."""
     common = ("--comm", "p2p", "--devices", "0,0", "--rendezvous", "gloo", "--steps", "2", "--warmup", "1", "--users", "800", "--nnz", "100000",
-              "--no-cpu", "--no-f64", "--no-rows", "--netflix-users", "3000", "--netflix-nnz", "200000")
+              "--full", "--no-cpu", "--no-f64", "--no-rows", "--netflix-users", "3000", "--netflix-nnz", "200000")
     a = run_bench_under_torchrun(2, *common)
     assert a.returncode == 0, a.stderr[-3000:]
     assert "starting 2 ranks" not in a.stderr
@@ -259,7 +259,7 @@ def test_two_physical_gpus_equal_one_rank(comm, chunks):
     """RCCL with more than one rank, the peer-to-peer exchange across xGMI and the item-range overlap have only ever run
     where a second GPU exists: when there is one, hold them to the one-rank trajectory."""
     users, nnz, steps, warmup = 2000, 250000, 2, 1
-    common = ["--steps", str(steps), "--warmup", str(warmup), "--users", str(users), "--nnz", str(nnz), "--no-cpu", "--no-f64", "--precision", "f64",
+    common = ["--steps", str(steps), "--warmup", str(warmup), "--users", str(users), "--nnz", str(nnz), "--full", "--no-cpu", "--no-f64", "--precision", "f64",
               "--no-profile", "--no-netflix"]
     two = run_bench("--gpus", "2", "--comm", comm, "--tune", f"allreduce_chunks={chunks}", *common)
     assert two.returncode == 0, two.stderr[-3000:]
@@ -499,3 +499,66 @@ def test_second_leg_guard_always_lets_the_held_record_out(mode, tmp_path):
     else:
         want = {"raise": "rank 1: RuntimeError: boom in the second leg", "deadline": "time budget", "sigterm": "SIGTERM"}[mode]
         assert want in line["netflix"]["error"], line
+
+
+def test_dumped_outputs_are_whole_or_a_fixed_sample_within_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs without a GPU: the factors and the timed steps' objectives as float64 .npy files; factors beyond the cap
+    are cut to the same seeded sample of rows on every call, with the row indices beside them, and everything stays within it."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    steps = 4
+    run = {"factors": (rng.standard_normal((20000, 20)), rng.standard_normal((5000, 20))), "objs": list(range(10)), "steps": steps}
+    small = {"factors": (run["factors"][0][:300], run["factors"][1][:200]), "objs": run["objs"], "steps": steps}
+    bench.dump_outputs(str(tmp_path / "small"), small, 0, 1)
+    assert sorted(os.listdir(tmp_path / "small")) == ["U.npy", "V.npy", "objective.npy"]
+    assert np.array_equal(np.load(tmp_path / "small" / "U.npy"), small["factors"][0])
+    assert np.array_equal(np.load(tmp_path / "small" / "V.npy"), small["factors"][1])
+    obj = np.load(tmp_path / "small" / "objective.npy")
+    assert obj.dtype == np.float64 and obj.tolist() == [6.0, 7.0, 8.0, 9.0]               # the timed steps only
+    monkeypatch.setattr(bench, "DUMP_CAP", 3 << 20)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), run, 0, 1)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["U.npy", "U_rows.npy", "V.npy", "V_rows.npy", "objective.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 3 << 20
+    for name, full in (("U", run["factors"][0]), ("V", run["factors"][1])):
+        rows = np.load(tmp_path / "a" / f"{name}_rows.npy")
+        assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0) and 0 < len(rows) < len(full)
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), full[rows.astype(np.int64)])
+        for f in (name, name + "_rows"):
+            assert np.array_equal(np.load(tmp_path / "a" / f"{f}.npy"), np.load(tmp_path / "b" / f"{f}.npy"))
+    bench.dump_outputs(str(tmp_path / "r1"), run, 1, 2)                    # N > 1: a rank other than 0 writes its own rows of U
+    assert os.listdir(tmp_path / "r1") == ["U_rank1.npy"] or sorted(os.listdir(tmp_path / "r1")) == ["U_rank1.npy", "U_rank1_rows.npy"]
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_plain_run_times_its_steps_and_dumps_what_they_computed(tmp_path):
+    """bench.py without --full: the timed steps and the line, no other leg and no full record; --dump-outputs writes the factors
+    and objectives the timed steps left -- those of one solver run for warmup + steps iterations from the same start."""
+    users, nnz, r, steps, warmup = 2000, 250000, 100, 3, 2
+    out = tmp_path / "out"
+    p = run_bench("--precision", "f64", "--steps", str(steps), "--warmup", str(warmup), "--users", str(users), "--nnz", str(nnz),
+                  "--dump-outputs", str(out))
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.strip().split("\n") if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["metric"] == "pairwise-comparisons/sec" and line["unit"] == "pairs/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f64" and line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0
+    assert not {"roofline", "cpu_baseline", "f64", "netflix", "cli", "full_record", "ndcg10_test", "kernels"} & set(line)
+    assert "[traffic]" not in p.stderr and "[cpu_baseline]" not in p.stderr and "[cli]" not in p.stderr
+    R = synth.generate("ml1m", seed=synth.SEED, d1=users, nnz=nnz)
+    ds = pcr.Dataset.from_ratings(R)
+    assert ds.count_pairs() / (line["ms_per_step"] * 1e-3) == pytest.approx(line["value"], rel=1e-9)
+    U, V, obj = (np.load(out / f) for f in ("U.npy", "V.npy", "objective.npy"))
+    assert U.shape == (users, r) and V.shape == (R.d2, r) and obj.shape == (steps,) and U.dtype == V.dtype == obj.dtype == np.float64
+    assert obj[-1] == pytest.approx(line["objective"], rel=1e-8)
+    s = pcr.Solver(ds, pcr.Parameter(k=r, precision=pcr.PCR_F64, do_predict=0, **{"lambda": 5000.0}))
+    s.set_factors(pcr.initial(users, r), pcr.initial(R.d2, r))
+    recs = s.iterate(warmup + steps)
+    Us, Vs = s.get_factors()
+    s.close()
+    assert np.allclose(obj, [x["obj"] for x in recs[warmup:]], rtol=1e-10, atol=0)
+    assert np.abs(U - Us).max() <= 1e-8 * np.abs(Us).max() and np.abs(V - Vs).max() <= 1e-8 * np.abs(Vs).max()

@@ -20,8 +20,8 @@ PREDICT = os.path.join(BIN_DIR, "omp-pmf-predict")
 NUM = r"[-+]?(?:\d+\.?\d*|\.\d+)(?:e[-+]?\d+)?"
 
 
-def run(cmd, cwd):
-    return subprocess.run(cmd, cwd=cwd, capture_output=True, text=True)
+def run(cmd, cwd, env=None):
+    return subprocess.run(cmd, cwd=cwd, capture_output=True, text=True, env=env)
 
 
 def test_usage_and_exit_codes(tmp_path):
@@ -395,6 +395,10 @@ def test_gpus_option_three_ranks_default_precision(n, tmp_path):
 
 
 STUB = os.path.join(ROOT, "oracle", "_ref", "omp-pmf-train-mi355x")
+# oracle/_ref is built where the reference lies and may reach this tree as a prebuilt copy: the stub is bound to THIS tree's
+# libprimalcr.so explicitly, whatever run path it was linked with
+STUB_ENV = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(
+    p for p in (os.path.join(ROOT, "primalcr_amd", "lib"), os.environ.get("LD_LIBRARY_PATH")) if p))
 
 
 def test_integration_stub_links_against_the_reference_objects(tmp_path):
@@ -404,14 +408,14 @@ def test_integration_stub_links_against_the_reference_objects(tmp_path):
     import torch
     if not os.path.exists(STUB):
         pytest.skip("oracle/_ref/omp-pmf-train-mi355x not built (no /root/reference in this container)")
-    ldd = subprocess.run(["ldd", STUB], capture_output=True, text=True).stdout
+    ldd = subprocess.run(["ldd", STUB], capture_output=True, text=True, env=STUB_ENV).stdout
     assert "libprimalcr.so" in ldd and "not found" not in ldd
     d = synth.write_dir(synth.generate("tiny"), str(tmp_path / "data"))
-    r = run([STUB, "-k", "4", d], tmp_path)
+    r = run([STUB, "-k", "4", d], tmp_path, STUB_ENV)
     assert r.returncode == 1 and "usage:" in r.stderr
     if torch.cuda.is_available():
         pytest.skip("GPU present: the no-GPU failure path needs a machine without one")
-    r = run([STUB, "-k", "4", "-t", "1", d, "m.model"], tmp_path)
+    r = run([STUB, "-k", "4", "-t", "1", d, "m.model"], tmp_path, STUB_ENV)
     assert r.returncode == 1 and "no HIP device" in r.stderr
     assert "the number of rows is 60 and the number of cols is 40" in r.stdout      # the reference's loader ran
 
@@ -424,7 +428,7 @@ def test_integration_stub_reproduces_the_reference_run(solver, tmp_path):
     if not os.path.exists(STUB):
         pytest.skip("oracle/_ref/omp-pmf-train-mi355x not built")
     g, meta, d = golden_dir("mid5", tmp_path)
-    out = run([STUB, "-s", str(solver), "-k", str(int(g["r"])), "-l", repr(float(g["lam"])), "-t", str(meta["iters"]), "--f64", d, "stub.model"], tmp_path)
+    out = run([STUB, "-s", str(solver), "-k", str(int(g["r"])), "-l", repr(float(g["lam"])), "-t", str(meta["iters"]), "--f64", d, "stub.model"], tmp_path, STUB_ENV)
     assert out.returncode == 0, out.stderr
     strip = lambda text: [l for l in text.split("\n") if l.startswith(("Iter", "(T"))]
     ours, theirs = strip(out.stdout), strip(meta["stdout_s%d" % solver])
