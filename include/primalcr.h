@@ -42,6 +42,7 @@ extern "C" {
 #define PCR_ERR_UNSUPPORTED -7
 
 /* solver ids: pmf.h:6  enum {CCDR1, PCR, PCRPP} */
+#define PCR_SOLVER_CCDR1  0   /* CCD++ rank-one, squared loss (ccd-r1.cpp:97-212); one rank only */
 #define PCR_SOLVER_PCR    1
 #define PCR_SOLVER_PCRPP  2
 
@@ -76,6 +77,15 @@ typedef struct pcr_params {
 /* pmf.h:27-48 parameter::parameter() */
 void pcr_params_default(pcr_params *p);                                   /* [host] */
 
+/* The CCDR1 solver's own settings (pcr_params stays as it is, so that callers built against it keep working).
+ * Set with pcr_solver_set_ccd_params before pcr_train / pcr_iterate. */
+typedef struct pcr_ccd_params {
+    int maxinneriter;  /* pmf.h:36  default 5     (-T)                                  */
+    double eps;        /* pmf.h:39  default 1e-3  (-e): inner stop at fundec < fundec_max * eps */
+    int do_nmf;        /* pmf.h:47  default 0     (-N): non-negative factors            */
+} pcr_ccd_params;
+void pcr_ccd_params_default(pcr_ccd_params *p);                           /* [host] */
+
 const char *pcr_last_error(void);                                         /* [host] */
 const char *pcr_version(void);                                            /* [host] */
 
@@ -92,6 +102,11 @@ int pcr_initial(double *X, int64_t n, int64_t k);                         /* [ho
  * depends on how many tries were accepted before it, so the tries before row0 are still evaluated (in parallel, without
  * their sqrt / log) -- for a rank that holds only its own users' rows of a large U. */
 int pcr_initial_rows(double *X, int64_t n, int64_t k, int64_t row0, int64_t nrows);   /* [host] */
+/* util.cpp:95-101 initial_col(): the row-major n x k values 0.1 * drand48(), drawn in order, bit for bit, from glibc's
+ * UNSEEDED drand48 stream (state 0: a = 0x5DEECE66D, c = 0xB, m = 2^48, value = X / 2^48).  The generator is the library's own
+ * (libc's drand48 state is global to the process and is never touched); above 2 M values several host threads draw ranges
+ * that start at states computed by jump-ahead. */
+int pcr_initial_col(double *X, int64_t n, int64_t k);                     /* [host] */
 
 typedef struct pcr_dataset pcr_dataset;   /* training CSR + test CSR, host memory */
 
@@ -274,6 +289,10 @@ int pcr_solver_setup_phase(const pcr_solver *s, int i, const char **name, double
  * process verify the sharding of N ranks on a single GPU. */
 int pcr_solver_set_local_only(pcr_solver *s, int on);
 
+/* CCDR1 (solver type 0) only: maxinneriter, eps, do_nmf, taken as given like the reference's -T / -e / -N (maxinneriter <= 0: no
+ * inner iteration, every rank only re-forms its residual); PCR_ERR_STATE on another solver */
+int pcr_solver_set_ccd_params(pcr_solver *s, const pcr_ccd_params *p);
+
 /* first local user and number of local users of this rank's shard */
 int pcr_solver_shard(const pcr_solver *s, int64_t *first_user, int64_t *n_users, int64_t *nnz_local);
 
@@ -315,9 +334,19 @@ typedef struct pcr_iter_stats {
     double seconds;                 /* cumulative, clock scope of pcrpp.cpp:874-881 */
     int64_t cg_v, ls_v, cg_u, ls_u; /* executed inner-iteration counts              */
 } pcr_iter_stats;
+/* On a CCDR1 solver one record per OUTER iteration (record 0 of pcr_train is zero): obj = the objective after its last rank,
+ * test_err / test_ndcg = the last evaluation (pcr_train with do_predict), seconds = device time of the CCDR1 kernels since the
+ * start of training, carried across pcr_iterate calls (the reference's Htime + Wtime + Rtime, ccd-r1.cpp:200), cg_v = inner iterations executed, cg_u = ranks executed
+ * (both cumulative since the start of training); train_err, train_ndcg, ls_v, ls_u = 0. */
 
 typedef void (*pcr_log_fn)(void *ctx, const char *line);
 
+/* CCDR1 (solver type 0): pcr_train = ccd-r1.cpp:97-212 ccdr1() from the current U, with V zeroed as the reference does; one
+ * line per rank (ccd-r1.cpp:196-206) when verbose, evaluated on the test set when do_predict.  pcr_iterate runs n more outer
+ * iterations without evaluation (starting a training run first if none is under way; pcr_solver_set_factors ends it).  The
+ * PrimalCR-only entry points (comp_m, objective, obtain_g, compute_Ha, solve_delta, update_V, update_U) return PCR_ERR_STATE.
+ * pcr_solver_counter(s, "ccd_residual_mismatch") counts the positions where the residual's user-major and item-major copies
+ * differ (always 0).  Profile slots: ccd/init, ccd/begin, ccd/vsweep, ccd/usweep, ccd/decide, ccd/resid, ccd/final. */
 /* pcrpp.cpp:841-901 pcrpp() / pcr.cpp:616-704 pcr(): the whole training loop
  * from the current device factors.  Emits the reference's log lines through
  * `log` (NULL = stdout, rank 0 only; a callback is invoked on EVERY rank of a multi-rank job with the

@@ -6,7 +6,7 @@ import os
 
 import numpy as np
 
-PCR_SOLVER_PCR, PCR_SOLVER_PCRPP = 1, 2
+PCR_SOLVER_CCDR1, PCR_SOLVER_PCR, PCR_SOLVER_PCRPP = 0, 1, 2
 PCR_F32, PCR_F64 = 0, 1
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -48,6 +48,19 @@ class Parameter(C.Structure):
             setattr(self, k, v)
 
 
+class CcdParameter(C.Structure):
+    """pcr_ccd_params: CCDR1's own settings (pmf.h:36,39,47: maxinneriter -T, eps -e, do_nmf -N)."""
+    _fields_ = [("maxinneriter", C.c_int), ("eps", C.c_double), ("do_nmf", C.c_int)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().pcr_ccd_params_default(C.byref(self))
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise AttributeError(k)
+            setattr(self, k, v)
+
+
 class IterStats(C.Structure):
     _fields_ = [("obj", C.c_double), ("train_err", C.c_double), ("train_ndcg", C.c_double), ("test_err", C.c_double),
                 ("test_ndcg", C.c_double), ("seconds", C.c_double), ("cg_v", C.c_int64), ("ls_v", C.c_int64),
@@ -77,6 +90,10 @@ def lib():
     L.pcr_params_default.argtypes = [C.POINTER(Parameter)]
     L.pcr_initial.argtypes = [_dp, i64, i64]
     L.pcr_initial_rows.argtypes = [_dp, i64, i64, i64, i64]
+    L.pcr_initial_col.argtypes = [_dp, i64, i64]
+    L.pcr_ccd_params_default.argtypes = [C.POINTER(CcdParameter)]
+    L.pcr_ccd_params_default.restype = None
+    L.pcr_solver_set_ccd_params.argtypes = [vp, C.POINTER(CcdParameter)]
     L.pcr_dataset_load.argtypes = [C.c_char_p, C.POINTER(vp)]
     L.pcr_dataset_load_mt.argtypes = [C.c_char_p, ci, C.POINTER(vp)]
     L.pcr_dataset_load_cached.argtypes = [C.c_char_p, ci, C.c_char_p, C.POINTER(vp)]
@@ -162,6 +179,13 @@ def initial(n, k):
     """util.cpp:80-93 initial()."""
     X = np.empty((n, k), np.float64)
     _chk(lib().pcr_initial(X, n, k))
+    return X
+
+
+def initial_col(n, k):
+    """util.cpp:95-101 initial_col(): n x k values 0.1 * drand48() of glibc's unseeded stream, drawn row by row."""
+    X = np.empty((n, k), np.float64)
+    _chk(lib().pcr_initial_col(X, n, k))
     return X
 
 
@@ -310,6 +334,11 @@ class Solver:
         _chk(lib().pcr_solver_shard(h, a, b, c))
         self.first_user, self.n_users, self.nnz_local = a.value, b.value, c.value
 
+    def set_ccd_params(self, params=None, **kw):
+        """CCDR1 (solver type 0): a CcdParameter, or its fields as keywords (maxinneriter, eps, do_nmf)."""
+        p = params if params is not None else CcdParameter(**kw)
+        _chk(lib().pcr_solver_set_ccd_params(self._h, C.byref(p)))
+
     def comm_init(self, uid: bytes):
         buf = C.create_string_buffer(uid, 128)
         _chk(lib().pcr_solver_comm_init(self._h, buf))
@@ -414,7 +443,7 @@ class Solver:
         return e.value, n.value
 
     def train(self, log=None):
-        """pcrpp()/pcr(): returns (per-iteration records, log lines)."""
+        """pcrpp()/pcr()/ccdr1(): returns (per-iteration records, log lines)."""
         hist = (IterStats * (self.param.maxiter + 1))()
         lines = []
 
@@ -428,7 +457,8 @@ class Solver:
         return recs, lines
 
     def iterate(self, n):
-        """n outer iterations (V step + U step, no evaluation) with one host round trip each; returns their records."""
+        """n outer iterations (V step + U step; for CCDR1 all k ranks), no evaluation, one host round trip each; returns their
+        records."""
         hist = (IterStats * max(n, 1))()
         _chk(lib().pcr_iterate(self._h, n, hist))
         return [{k: getattr(h, k) for k, _ in IterStats._fields_} for h in hist[:n]]

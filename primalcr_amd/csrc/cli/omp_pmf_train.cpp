@@ -49,12 +49,16 @@ static void exit_with_help() {
         "Usage: omp-pmf-train [options] data_dir [model_filename]\n"
         "options:\n"
         "    -s type : set type of solver (default 2)\n"
+        "    	 0 -- CCDR1 (squared loss)\n"
         "    	 1 -- PirmalCR\n"
         "    	 2 -- PrimalCR++\n"
         "    -k rank : set the rank (default 10)\n"
         "    -n threads : set the number of threads (default 4)\n"
         "    -l lambda : set the regularization parameter lambda (default 5000)\n"
         "    -t max_iter: set the number of iterations (default 10)\n"
+        "    -T max_iter: set the number of inner iterations used in CCDR1 (default 5)\n"
+        "    -e epsilon : set inner termination criterion epsilon of CCDR1 (default 1e-3)\n"
+        "    -N do_nmf: non-negative factors in CCDR1 (default 0)\n"
         "    -p do_predict: compute training/testing error & NDCG at each iteration or not (default 1)\n"
         "    --f64 : keep U, V in fp64 on the GPU (default fp32 storage, fp64 accumulation)\n"
         "    --device id : GPU to use (default 0)\n"
@@ -343,6 +347,40 @@ static int train_multi(const pcr_dataset* ds, const pcr_params& param, int gpus,
     return 0;
 }
 
+// pmf-train.cpp:138-172 run_ccdr1(): "starts!", the per-rank lines of ccdr1(), "Wall-time: %lg secs", the model; no side files
+static int run_ccdr1(pcr_dataset* ds, pcr_params param, const pcr_ccd_params& ccd, const std::vector<int>& devices, const std::string& model,
+                     std::vector<double>& U, std::vector<double>& V, int64_t d1, int64_t d2, bool timing, double load_s, double init_s,
+                     std::chrono::steady_clock::time_point t_main) {
+    auto t_lap = std::chrono::steady_clock::now();
+    auto lap = [&]() { const auto n = std::chrono::steady_clock::now(); const double d = std::chrono::duration<double>(n - t_lap).count(); t_lap = n; return d; };
+    struct Holder { pcr_solver* s; ~Holder() { if (s) pcr_solver_destroy(s); } } hold{nullptr};      // (the caller owns ds)
+    auto fail = [](const char* what) { fprintf(stderr, "%s: %s\n", what, pcr_last_error()); return 1; };
+    std::cout << "starts!" << std::endl;
+    const auto t0 = std::chrono::steady_clock::now();
+    join_warm();
+    if (!devices.empty()) param.device = devices[0];
+    pcr_solver* s = nullptr;
+    if (pcr_solver_create(ds, &param, 0, 1, &s) != PCR_OK) return fail("solver");
+    hold.s = s;
+    if (pcr_solver_set_ccd_params(s, &ccd) != PCR_OK) return fail("solver");
+    if (pcr_solver_set_factors(s, U.data(), nullptr) != PCR_OK) return fail("set_factors");
+    const double create_s = lap();
+    std::vector<pcr_iter_stats> hist((size_t)std::max(0, param.maxiter) + 1);
+    if (pcr_train(s, nullptr, nullptr, hist.data()) != PCR_OK) return fail("train");
+    const double train_s = lap();
+    if (pcr_solver_get_factors(s, U.data(), V.data()) != PCR_OK) return fail("get_factors");
+    printf("Wall-time: %lg secs\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    fflush(stdout);
+    if (pcr_model_save(model.c_str(), U.data(), d1, V.data(), d2, param.k) != PCR_OK) return fail("model");
+    const double write_s = lap();
+    if (timing) {
+        const double iter_s = hist.back().seconds;
+        fprintf(stderr, "[timing] load_s=%.4f init_s=%.4f create_s=%.4f train_s=%.4f iter_s=%.4f eval_s=%.4f write_s=%.4f wall_s=%.4f\n", load_s, init_s,
+                create_s, train_s, iter_s, std::max(0.0, train_s - iter_s), write_s, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main).count());
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const auto t_main = std::chrono::steady_clock::now();
     auto t_lap = t_main;
@@ -351,6 +389,8 @@ int main(int argc, char** argv) {
     double load_s = 0, init_s = 0, create_s = 0, train_s = 0, iter_s = 0, write_s = 0;
     pcr_params param;
     pcr_params_default(&param);
+    pcr_ccd_params ccd;
+    pcr_ccd_params_default(&ccd);
     std::string init_model, cache, comm_kind = "rccl";
     std::vector<int> devices;
     int snapshot_every = 0, gpus = 1;
@@ -390,8 +430,11 @@ int main(int argc, char** argv) {
             case 't': param.maxiter = atoi(argv[i]); break;
             case 'p': param.do_predict = atoi(argv[i]); break;
             case 'q': param.verbose = atoi(argv[i]); break;
-            // parsed-but-unused by the PCR/PCR++ path in the reference (pmf-train.cpp:59-102)
-            case 'r': case 'T': case 'e': case 'B': case 'm': case 'u': case 'd': case 'N': break;
+            case 'T': ccd.maxinneriter = atoi(argv[i]); break;                   // pmf-train.cpp:59-102: read by CCDR1 only
+            case 'e': ccd.eps = atof(argv[i]); break;
+            case 'N': ccd.do_nmf = atoi(argv[i]) == 1 ? 1 : 0; break;
+            // parsed-but-unused by every solver of the reference (pmf-train.cpp:59-102)
+            case 'r': case 'B': case 'm': case 'u': case 'd': break;
             default:
                 fprintf(stderr, "unknown option: -%c\n", argv[i - 1][1]);
                 exit_with_help();
@@ -407,9 +450,15 @@ int main(int argc, char** argv) {
         size_t p = d.rfind('/');
         model = (p == std::string::npos ? d : d.substr(p + 1)) + ".model";
     }
-    if (param.solver_type != PCR_SOLVER_PCR && param.solver_type != PCR_SOLVER_PCRPP) {
+    if (param.solver_type != PCR_SOLVER_CCDR1 && param.solver_type != PCR_SOLVER_PCR && param.solver_type != PCR_SOLVER_PCRPP) {
         fprintf(stderr, "Error: wrong solver type (%d)!\n", param.solver_type);   // pmf-train.cpp:331-333
         return 0;
+    }
+    if (param.solver_type == PCR_SOLVER_CCDR1) {                     // options CCDR1 does not have: refused, never ignored
+        const char* bad = gpus != 1 ? "--gpus" : devices.size() > 1 ? "--devices with more than one device" : !init_model.empty() ? "--init-model"
+                        : snapshot_every != 0 ? "--snapshot-every" : nullptr;
+        if (bad) { fprintf(stderr, "omp-pmf-train: %s is not supported with -s 0 (CCDR1 runs on one GPU from initial_col)\n", bad); return 1; }
+        if (comm_kind != "rccl" && comm_kind != "p2p") { fprintf(stderr, "--comm must be rccl or p2p\n"); return 1; }
     }
     // the reference opens the model file BEFORE training (pmf-train.cpp:252-259)
     FILE* fp = fopen(model.c_str(), "wb");
@@ -433,6 +482,10 @@ int main(int argc, char** argv) {
     pcr_dataset_dims(ds, &d1, &d2, &nnz, &tnnz);
     const int k = param.k;
     std::vector<double> U((size_t)d1 * k), V((size_t)d2 * k);
+    if (param.solver_type == PCR_SOLVER_CCDR1) {
+        pcr_initial_col(U.data(), d1, k);              // pmf-train.cpp:156-158 (H is zeroed by ccdr1 itself, ccd-r1.cpp:116)
+        return run_ccdr1(ds, param, ccd, devices, model, U, V, d1, d2, timing, load_s, lap() , t_main);
+    }
     pcr_initial(U.data(), d1, k);                      // pmf-train.cpp:264-266
     pcr_initial(V.data(), d2, k);
     if (!init_model.empty()) {                         // warm start

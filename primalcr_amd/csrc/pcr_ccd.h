@@ -1,0 +1,655 @@
+// pcr_ccd.h -- CCDR1 (CCD++ rank-one squared-loss matrix factorisation, solver type 0) on the device: ccd-r1.cpp:97-212.
+//
+// Included by pcr_solver.hip after Solver<T>: a CcdSolver<T> holds a Solver<T> for what the two solvers share -- the factor
+// storage (U d1 x ld, V d2 x ld, row-major, the storage type T), the test-set evaluator (k_eval / k_eval2, util.cpp:434-542)
+// and the stream -- and keeps its own state next to it:
+//   * the residual over the training ratings twice, in user-major (CSR) order and in item-major (CSC) order, so that both
+//     sweeps read it sequentially.  The two copies are updated by the same expression (an explicit fma with the same operands)
+//     on both sides and stay bitwise identical (pcr_solver_counter "ccd_residual_mismatch" checks it);
+//   * the test residuals behind the printed rmse (util.cpp:206-215);
+//   * fp64 work vectors u (d1), v (d2) and their values at the start of the rank, oldu / oldv (ccd-r1.cpp:120-125);
+//   * a control block (CcdCtl): the stopping state of ccd-r1.cpp:126-172 lives on the device, so that no inner iteration
+//     needs a host round trip.
+// Kernels per rank: k_ccd_begin, then per inner iteration k_ccd_sweep over the CSC (v), k_ccd_sweep over the
+// CSR (u) and k_ccd_decide, then k_ccd_resid and k_ccd_final: 3 T + 3 launches.  Every sum is accumulated in fp64 and reduced in
+// a fixed order (per-block partials summed by one block): results do not depend on timing and repeat bit for bit.
+#pragma once
+
+struct CcdCtl {
+    // stopping state (ccd-r1.cpp:126-129, :165-172)
+    double fundec_max, rankfundec;
+    int early_stop, broken, skip, pad0;
+    // objective bookkeeping (ccd-r1.cpp:110-118, :181-199)
+    double reg, loss, obj, oldobj, rmse;
+    // counters: inner iterations executed, ranks executed (cumulative since the start of training)
+    long long inner_iters, ranks_done;
+    // the record of the last rank: 1 if it ran (a skipped rank prints nothing)
+    int printed, pad1;
+};
+
+namespace ccd {
+constexpr int BLOCK = 256;          // 4 waves
+constexpr int LONG = 4096;          // columns with more ratings than this get a whole workgroup (Netflix-shaped long tails)
+constexpr int PART_MAX = 1024;      // blocks of the element-wise segments (fixed by the shape, never by the device)
+
+__device__ inline long long bits(double x) { return __double_as_longlong(x); }
+__device__ inline long long bits(float x) { return __float_as_int(x); }
+__device__ inline double wave_sum(double x) {
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+// fixed-order sum of a[0..n) by one block: thread j sums j, j + B, ... in order, then a tree over the threads
+__device__ inline double block_sum_fixed(const double* a, int n, double* lds) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += BLOCK) s += a[i];
+    lds[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = BLOCK / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) lds[threadIdx.x] += lds[threadIdx.x + w];
+        __syncthreads();
+    }
+    const double r = lds[0];
+    __syncthreads();
+    return r;
+}
+__device__ inline double block_reduce(double s, double* lds) {
+    lds[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = BLOCK / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) lds[threadIdx.x] += lds[threadIdx.x + w];
+        __syncthreads();
+    }
+    const double r = lds[0];
+    __syncthreads();
+    return r;
+}
+// RankOneUpdate's closing arithmetic (ccd-r1.cpp:7-30) for a non-empty column; *fundec receives the column's term
+__device__ inline double rank_one_new(double g, double h, double vj, int do_nmf, double* fundec) {
+    const double newvj = g / h;
+    if (do_nmf > 0 && newvj < 0) {
+        // ccd-r1.cpp:19: `fundec = -2*g*vj; + h*vj*vj;` -- the stray semicolon drops the h term; reproduced
+        *fundec = -2 * g * vj;
+        return 0.0;
+    }
+    const double delta = vj - newvj;
+    *fundec = h * delta * delta;
+    return newvj;
+}
+}  // namespace ccd
+
+// Start of rank t (ccd-r1.cpp:113-125): u = oldu = U[:, t]; v = V[:, t], oldv = 0 in outer iteration 1 (:124), else v.
+// Rank 1 of an outer iteration resets fundec_max and early_stop (:126-129); a rank after five first-iteration breaks is
+// skipped (:131) -- every later kernel of the rank exits at entry.
+template <typename T>
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_begin(CcdCtl* ctl, const T* U, const T* V, int ld, int t, int oiter, int64_t d1, int64_t d2,
+                                                          double* u, double* oldu, double* v, double* oldv) {
+    const bool skip = t > 0 && ctl->early_stop >= 5;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (t == 0) { ctl->fundec_max = 0.0; ctl->rankfundec = 0.0; ctl->early_stop = 0; }
+        ctl->broken = 0;
+        ctl->skip = skip ? 1 : 0;
+    }
+    if (skip) return;
+    const int64_t n = d1 > d2 ? d1 : d2;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (i < d1) { const double x = (double)U[i * ld + t]; u[i] = x; oldu[i] = x; }
+        if (i < d2) { const double x = (double)V[i * ld + t]; v[i] = x; oldv[i] = oiter == 1 ? 0.0 : x; }
+    }
+}
+
+// One half of an inner iteration (ccd-r1.cpp:146-160): for every column c of the given orientation (items over the CSC for v,
+// users over the CSR for u) y[c] = g / h with g = sum x_i r_ic, h = lambda * n_c + sum x_i^2 (:151,157: the regulariser is
+// lambda times the column's rating count), 0 for an empty column.  Short columns: one wave each, four per workgroup; long ones:
+// a workgroup each.  With `addback` (inner iteration 1 of an outer iteration > 1) the rank's old term is added back into this
+// orientation's residual copy on the way (ccd-r1.cpp:127-130: r += oldu_i oldv_j), stored, and used.
+// part[block] = the block's fundec, its columns in order.
+template <typename RT>
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_sweep(const CcdCtl* ctl, const int64_t* ptr, const int32_t* idx, RT* res, const double* x,
+                                                          const double* oldx, const double* oldy, double* y, const int32_t* longs, int nlong,
+                                                          const int32_t* shorts, int nshort, double lambda, int do_nmf, int addback, double* part) {
+    if (ctl->skip || ctl->broken) return;
+    __shared__ double sg[ccd::BLOCK / 64], sh[ccd::BLOCK / 64], sf[ccd::BLOCK / 64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if ((int)blockIdx.x < nlong) {
+        const int c = longs[blockIdx.x];
+        const int64_t z0 = ptr[c], z1 = ptr[c + 1];
+        const double oy = oldy[c];
+        double g = 0.0, h = 0.0;
+        for (int64_t z = z0 + threadIdx.x; z < z1; z += ccd::BLOCK) {
+            const int i = idx[z];
+            double r = (double)res[z];
+            if (addback) { const RT rn = (RT)fma(oldx[i], oy, r); res[z] = rn; r = (double)rn; }
+            const double xi = x[i];
+            g += xi * r; h += xi * xi;
+        }
+        g = ccd::wave_sum(g); h = ccd::wave_sum(h);
+        if (lane == 0) { sg[wv] = g; sh[wv] = h; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double G = 0.0, H = 0.0;
+            for (int w = 0; w < ccd::BLOCK / 64; ++w) { G += sg[w]; H += sh[w]; }
+            double f = 0.0;
+            y[c] = ccd::rank_one_new(G, lambda * (double)(z1 - z0) + H, y[c], do_nmf, &f);
+            part[blockIdx.x] = f;
+        }
+        return;
+    }
+    const int64_t s = (int64_t)(blockIdx.x - nlong) * (ccd::BLOCK / 64) + wv;
+    double f = 0.0;
+    if (s < nshort) {
+        const int c = shorts[s];
+        const int64_t z0 = ptr[c], z1 = ptr[c + 1];
+        const double oy = oldy[c];
+        double g = 0.0, h = 0.0;
+        for (int64_t z = z0 + lane; z < z1; z += 64) {
+            const int i = idx[z];
+            double r = (double)res[z];
+            if (addback) { const RT rn = (RT)fma(oldx[i], oy, r); res[z] = rn; r = (double)rn; }
+            const double xi = x[i];
+            g += xi * r; h += xi * xi;
+        }
+        g = ccd::wave_sum(g); h = ccd::wave_sum(h);
+        if (lane == 0) {
+            if (z1 > z0) y[c] = ccd::rank_one_new(g, lambda * (double)(z1 - z0) + h, y[c], do_nmf, &f);
+            else y[c] = 0.0;                                             // ccd-r1.cpp:9: an empty column returns 0, no fundec
+        }
+    }
+    if (lane == 0) sf[wv] = f;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double F = 0.0;
+        for (int w = 0; w < ccd::BLOCK / 64; ++w) F += sf[w];
+        part[blockIdx.x] = F;
+    }
+}
+
+// The stopping test after both sweeps of inner iteration `iter` (ccd-r1.cpp:161-172): innerfundec_cur = v-side + u-side sums;
+// below fundec_max * eps the rank breaks (its later sweeps exit at entry; a break at iteration 1 counts towards early_stop);
+// else fundec_max takes it, except at (outer 1, rank 1, inner 1) (:170-172).  The updated u and v are kept either way.
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_decide(CcdCtl* ctl, const double* vpart, int nv, const double* upart, int nu, double eps,
+                                                           int oiter, int t, int iter) {
+    if (ctl->skip || ctl->broken) return;
+    __shared__ double lds[ccd::BLOCK];
+    const double cur = ccd::block_sum_fixed(vpart, nv, lds) + ccd::block_sum_fixed(upart, nu, lds);
+    if (threadIdx.x != 0) return;
+    ctl->inner_iters += 1;
+    if (cur < ctl->fundec_max * eps) {
+        if (iter == 1) ctl->early_stop += 1;
+        ctl->broken = 1;
+        return;
+    }
+    ctl->rankfundec += cur;
+    if (!(oiter == 1 && t == 0 && iter == 1)) ctl->fundec_max = fmax(ctl->fundec_max, cur);
+}
+
+// End of the rank (ccd-r1.cpp:175-199), element-wise segments of one launch, each with per-block partials:
+//   blocks [0, B):        CSR copy  r -= u_i v_j, loss partials (the reference's loss is the sum over its CSR-ordered copy, :182)
+//   blocks [B, 2B):       CSC copy  r -= u_i v_j (same expression, same operands: the copies stay bitwise identical)
+//   blocks [2B, 2B + Bu): users: U[:, t] = u (rounded to the storage type: every later use, here included, sees the stored value),
+//                         reg partials nnz_i (u_i^2 - oldu_i^2) (:187-194)
+//   blocks [.., + Bv):    items: V[:, t] = v, reg partials
+//   blocks [.., + Bt):    test residuals tv -= u_i v_j - oldu_i oldv_j and their squares (util.cpp:206-215)
+template <typename T, typename RT>
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_resid(const CcdCtl* ctl, int B, int Bu, int Bv, int Bt, int64_t nnz, int64_t d1, int64_t d2, int64_t tn,
+                                                          RT* res_r, const int32_t* row_r, const int32_t* col_r,
+                                                          RT* res_c, const int32_t* row_c, const int32_t* col_c,
+                                                          const int64_t* uptr, const int64_t* cptr, const double* u, const double* oldu,
+                                                          const double* v, const double* oldv, T* U, T* V, int ld, int t,
+                                                          const int32_t* tu, const int32_t* ti, double* tres,
+                                                          double* p_loss, double* p_regu, double* p_regv, double* p_rmse, int addback) {
+    if (ctl->skip) return;
+    __shared__ double lds[ccd::BLOCK];
+    int b = blockIdx.x;
+    double s = 0.0;
+    double* out = nullptr;
+    if (b < 2 * B) {
+        const bool csr = b < B;
+        if (!csr) b -= B;
+        RT* res = csr ? res_r : res_c;
+        const int32_t* rr = csr ? row_r : row_c;       // user of every entry
+        const int32_t* cc = csr ? col_r : col_c;       // item of every entry
+        for (int64_t z = (int64_t)b * ccd::BLOCK + threadIdx.x; z < nnz; z += (int64_t)B * ccd::BLOCK) {
+            const double ui = (double)(T)u[rr[z]], vj = (double)(T)v[cc[z]];
+            RT r0 = res[z];
+            if (addback) r0 = (RT)fma(oldu[rr[z]], oldv[cc[z]], (double)r0);   // no inner iteration ran (-T 0): the add-back is here
+            const RT rn = (RT)fma(-ui, vj, (double)r0);
+            res[z] = rn;
+            const double r = (double)rn;
+            s += r * r;
+        }
+        if (!csr) return;
+        out = p_loss;
+    } else if ((b -= 2 * B) < Bu) {
+        for (int64_t i = (int64_t)b * ccd::BLOCK + threadIdx.x; i < d1; i += (int64_t)Bu * ccd::BLOCK) {
+            const T x = (T)u[i];
+            U[i * ld + t] = x;
+            const double n = (double)(uptr[i + 1] - uptr[i]), xd = (double)x;
+            s += n * (xd * xd) - n * (oldu[i] * oldu[i]);
+        }
+        out = p_regu;
+    } else if ((b -= Bu) < Bv) {
+        for (int64_t j = (int64_t)b * ccd::BLOCK + threadIdx.x; j < d2; j += (int64_t)Bv * ccd::BLOCK) {
+            const T x = (T)v[j];
+            V[j * ld + t] = x;
+            const double n = (double)(cptr[j + 1] - cptr[j]), xd = (double)x;
+            s += n * xd * xd - n * oldv[j] * oldv[j];
+        }
+        out = p_regv;
+    } else {
+        b -= Bv;
+        for (int64_t z = (int64_t)b * ccd::BLOCK + threadIdx.x; z < tn; z += (int64_t)Bt * ccd::BLOCK) {
+            const int i = tu[z], j = ti[z];
+            if (i < 0) { s += tres[z] * tres[z]; continue; }            // (a user id past d1: see CcdSolver::init)
+            const double r = tres[z] - ((double)(T)u[i] * (double)(T)v[j] - oldu[i] * oldv[j]);
+            tres[z] = r;
+            s += r * r;
+        }
+        out = p_rmse;
+    }
+    s = ccd::block_reduce(s, lds);
+    if (threadIdx.x == 0) out[b] = s;
+}
+
+// The rank's record (ccd-r1.cpp:180-199): reg += the item side then the user side, obj = loss + lambda reg, rmse over the test
+// entries; oldobj carries over to the next rank
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_final(CcdCtl* ctl, const double* p_loss, int B, const double* p_regu, int Bu, const double* p_regv,
+                                                          int Bv, const double* p_rmse, int Bt, int64_t tn, double lambda) {
+    __shared__ double lds[ccd::BLOCK];
+    if (ctl->skip) {
+        if (threadIdx.x == 0) ctl->printed = 0;
+        return;
+    }
+    const double loss = ccd::block_sum_fixed(p_loss, B, lds);
+    const double rv = ccd::block_sum_fixed(p_regv, Bv, lds);
+    const double ru = ccd::block_sum_fixed(p_regu, Bu, lds);
+    const double se = ccd::block_sum_fixed(p_rmse, Bt, lds);
+    if (threadIdx.x != 0) return;
+    ctl->reg += rv;
+    ctl->reg += ru;
+    ctl->loss = loss;
+    ctl->oldobj = ctl->obj;
+    ctl->obj = loss + ctl->reg * lambda;
+    ctl->rmse = tn > 0 ? sqrt(se / (double)tn) : 0.0;
+    ctl->ranks_done += 1;
+    ctl->printed = 1;
+}
+
+// Start of training (ccd-r1.cpp:107-118): V = 0 (the reference zeroes H), residuals = ratings, test residuals = test ratings
+// (uploaded by the host), reg partials = sum_i nnz_i sum_t U_it^2
+template <typename T>
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_init(T* V, int64_t nV, const T* U, int k, int ld, const int64_t* uptr, int64_t d1, double* p_reg) {
+    __shared__ double lds[ccd::BLOCK];
+    for (int64_t i = (int64_t)blockIdx.x * ccd::BLOCK + threadIdx.x; i < nV; i += (int64_t)gridDim.x * ccd::BLOCK) V[i] = (T)0;
+    double s = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * ccd::BLOCK + threadIdx.x; i < d1; i += (int64_t)gridDim.x * ccd::BLOCK) {
+        const double n = (double)(uptr[i + 1] - uptr[i]);
+        for (int t = 0; t < k; ++t) { const double x = (double)U[i * ld + t]; s += x * x * n; }
+    }
+    s = ccd::block_reduce(s, lds);
+    if (threadIdx.x == 0) p_reg[blockIdx.x] = s;
+}
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_init_fin(CcdCtl* ctl, const double* p_reg, int n) {
+    __shared__ double lds[ccd::BLOCK];
+    const double reg = ccd::block_sum_fixed(p_reg, n, lds);
+    if (threadIdx.x != 0) return;
+    ctl->fundec_max = 0.0; ctl->rankfundec = 0.0;
+    ctl->early_stop = 0; ctl->broken = 0; ctl->skip = 0;
+    ctl->reg = reg; ctl->loss = 0.0; ctl->obj = 0.0; ctl->oldobj = 0.0; ctl->rmse = 0.0;
+    ctl->inner_iters = 0; ctl->ranks_done = 0; ctl->printed = 0;
+}
+
+// the "ccd_residual_mismatch" diagnostic: positions where the CSC copy differs from the CSR copy, bit for bit
+template <typename RT>
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_mismatch(const RT* res_r, const RT* res_c, const int32_t* c2r, int64_t nnz, double* part) {
+    __shared__ double lds[ccd::BLOCK];
+    double s = 0.0;
+    for (int64_t z = (int64_t)blockIdx.x * ccd::BLOCK + threadIdx.x; z < nnz; z += (int64_t)gridDim.x * ccd::BLOCK) {
+        s += ccd::bits(res_c[z]) != ccd::bits(res_r[c2r[z]]) ? 1.0 : 0.0;
+    }
+    s = ccd::block_reduce(s, lds);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// host side
+template <typename T>
+struct CcdSolver final : pcr_solver {
+    typedef T RT;                                     // storage type of the residuals
+    std::unique_ptr<Solver<T>> base;                  // factors, evaluator, stream
+    pcr_params prm;
+    pcr_ccd_params cp;
+    int64_t d1 = 0, d2 = 0, nnz = 0, tn = 0, tnnz_file = 0;
+    int k = 1, ld = 4;
+    hipStream_t st = nullptr;
+    // CSR (user-major) and CSC (item-major) structure; row_* / col_* = user / item of every entry
+    DBuf<int64_t> d_cptr;
+    DBuf<int32_t> d_row_r, d_row_c, d_col_c, d_c2r, d_ilong, d_ishort, d_ulong, d_ushort, d_tu, d_ti;
+    DBuf<RT> d_res_r, d_res_c;
+    DBuf<double> d_u, d_oldu, d_v, d_oldv, d_tres;
+    DBuf<double> d_vpart, d_upart, d_ploss, d_pregu, d_pregv, d_prmse, d_pmis;
+    DBuf<CcdCtl> d_ctl;
+    CcdCtl* h_ctl = nullptr;                          // pinned
+    std::vector<RT> h_val_r, h_val_c;                 // the ratings in both orders (a training run starts from them)
+    std::vector<double> h_tval;
+    int nvb = 0, nub = 0, nilong = 0, nishort = 0, nulong = 0, nushort = 0;
+    int B = 1, Bu = 1, Bv = 1, Bt = 1, Bi = 1;
+    bool begun = false;
+    int oiter = 0;                                    // outer iterations run since the start of training
+    double secs = 0.0;                                // device seconds of the CCDR1 kernels since the start of training
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    std::vector<hipEvent_t> ev_pool;
+
+    ~CcdSolver() override {
+        if (st) (void)hipStreamSynchronize(st);
+        prof_resolve();
+        for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
+        if (ev_a) (void)hipEventDestroy(ev_a);
+        if (ev_b) (void)hipEventDestroy(ev_b);
+        if (h_ctl) (void)hipHostFree(h_ctl);
+    }
+
+    static int parts(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(ccd::PART_MAX, (n + ccd::BLOCK * 4 - 1) / (ccd::BLOCK * 4))); }
+
+    int init(const pcr_dataset* ds, const pcr_params* p) {
+        prm = *p;
+        pcr_ccd_params_default(&cp);
+        if (prm.k < 1) { pcr_set_error("rank k must be >= 1"); return PCR_ERR_ARG; }
+        pcr_params bp = *p;
+        bp.solver_type = PCR_SOLVER_PCRPP;             // the shared machinery: factor storage, evaluator, stream
+        base.reset(new Solver<T>());
+        RC(base->init(ds, &bp, 0, 1));
+        const auto t0 = std::chrono::steady_clock::now();
+        st = base->st;
+        d1 = base->d1; d2 = base->d2; nnz = base->nnz_local; tnnz_file = ds->tnnz_file;
+        k = prm.k; ld = base->geo.ld;
+        first_user = 0; n_users = d1; nnz_local = nnz;
+        const PcrCsr& X = ds->train;
+        // CSC by a counting sort over the CSR (entries of one item in user order)
+        std::vector<int64_t> cptr((size_t)d2 + 1, 0);
+        for (int64_t z = 0; z < nnz; ++z) cptr[(size_t)X.item[(size_t)z] + 1]++;
+        for (int64_t j = 0; j < d2; ++j) cptr[(size_t)j + 1] += cptr[(size_t)j];
+        std::vector<int32_t> row_r((size_t)nnz), row_c((size_t)nnz), col_c((size_t)nnz), c2r((size_t)nnz);
+        h_val_r.resize((size_t)nnz); h_val_c.resize((size_t)nnz);
+        {
+            std::vector<int64_t> fill(cptr.begin(), cptr.end() - 1);
+            for (int64_t u = 0; u < d1; ++u)
+                for (int64_t z = X.index[(size_t)u]; z < X.index[(size_t)u + 1]; ++z) {
+                    const int32_t j = X.item[(size_t)z];
+                    const int64_t q = fill[(size_t)j]++;
+                    row_r[(size_t)z] = (int32_t)u;
+                    row_c[(size_t)q] = (int32_t)u; col_c[(size_t)q] = j; c2r[(size_t)q] = (int32_t)z;
+                    h_val_r[(size_t)z] = (RT)X.val[(size_t)z];
+                    h_val_c[(size_t)q] = (RT)X.val[(size_t)z];
+                }
+        }
+        // column classes of the two sweeps
+        auto classes = [](const std::vector<int64_t>& ptr, int64_t n, std::vector<int32_t>& lo, std::vector<int32_t>& hi) {
+            for (int64_t c = 0; c < n; ++c) (ptr[(size_t)c + 1] - ptr[(size_t)c] > ccd::LONG ? hi : lo).push_back((int32_t)c);
+        };
+        std::vector<int32_t> ishort, ilong, ushort, ulong;
+        classes(cptr, d2, ishort, ilong);
+        classes(X.index, d1, ushort, ulong);
+        nishort = (int)ishort.size(); nilong = (int)ilong.size(); nushort = (int)ushort.size(); nulong = (int)ulong.size();
+        nvb = std::max(1, nilong + cdiv(nishort, ccd::BLOCK / 64));
+        nub = std::max(1, nulong + cdiv(nushort, ccd::BLOCK / 64));
+        // the test entries: util.cpp:206-215 walks T, the file's triplets in file order -- the data set's raw triplets where it
+        // kept them (a test file that is not user-sorted), else the test CSR, which then is the file row by row
+        std::vector<int32_t> tu, ti;
+        if (!ds->traw_val.empty()) {
+            tn = (int64_t)ds->traw_val.size();
+            tu = ds->traw_user; ti = ds->traw_item; h_tval = ds->traw_val;
+            // a user id >= d1 makes the reference read past W (util.cpp:211, undefined); here its residual stays at its rating
+            for (int32_t& x : tu) if (x >= d1) x = -1;
+        } else {
+            const PcrCsr& TT = ds->test;
+            tn = TT.nnz();
+            tu.resize((size_t)tn);
+            for (int64_t u = 0; u < TT.d1; ++u)
+                for (int64_t z = TT.index[(size_t)u]; z < TT.index[(size_t)u + 1]; ++z) tu[(size_t)z] = (int32_t)u;
+            ti.assign(TT.item.begin(), TT.item.begin() + tn);
+            h_tval.assign(TT.val.begin(), TT.val.begin() + tn);
+        }
+        B = parts(nnz); Bu = parts(d1); Bv = parts(d2); Bt = parts(tn); Bi = parts(d1);
+        RC(d_cptr.upload(cptr, st));
+        RC(d_row_r.upload(row_r, st)); RC(d_row_c.upload(row_c, st)); RC(d_col_c.upload(col_c, st)); RC(d_c2r.upload(c2r, st));
+        RC(d_ilong.upload(ilong, st)); RC(d_ishort.upload(ishort, st)); RC(d_ulong.upload(ulong, st)); RC(d_ushort.upload(ushort, st));
+        RC(d_tu.upload(tu, st)); RC(d_ti.upload(ti, st));
+        RC(d_res_r.alloc((size_t)nnz)); RC(d_res_c.alloc((size_t)nnz)); RC(d_tres.alloc((size_t)tn));
+        RC(d_u.alloc((size_t)d1)); RC(d_oldu.alloc((size_t)d1)); RC(d_v.alloc((size_t)d2)); RC(d_oldv.alloc((size_t)d2));
+        RC(d_vpart.alloc((size_t)nvb)); RC(d_upart.alloc((size_t)nub));
+        RC(d_ploss.alloc((size_t)B)); RC(d_pregu.alloc((size_t)std::max(Bu, Bi))); RC(d_pregv.alloc((size_t)Bv)); RC(d_prmse.alloc((size_t)Bt));
+        RC(d_pmis.alloc((size_t)B));
+        RC(d_ctl.alloc(1));
+        HIPCHK(hipMemset(d_ctl.p, 0, sizeof(CcdCtl)));
+        HIPCHK(hipHostMalloc((void**)&h_ctl, sizeof(CcdCtl), hipHostMallocDefault));
+        memset(h_ctl, 0, sizeof(CcdCtl));
+        HIPCHK(hipEventCreate(&ev_a)); HIPCHK(hipEventCreate(&ev_b));
+        setup_ms = base->setup_ms;
+        setup_ms.emplace_back("CCDR1 CSC and residuals", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        return PCR_OK;
+    }
+
+    // ---- profiling (the same slots and sampling rules as Solver<T>)
+    hipEvent_t ev_get() {
+        if (!ev_pool.empty()) { hipEvent_t e = ev_pool.back(); ev_pool.pop_back(); return e; }
+        hipEvent_t e = nullptr;
+        (void)hipEventCreate(&e);
+        return e;
+    }
+    struct Prof {
+        CcdSolver* s; ProfSlot* slot = nullptr; hipEvent_t a = nullptr, b = nullptr;
+        Prof(CcdSolver* s_, const char* name) : s(s_) {
+            if (!s->prof_on) return;
+            ProfSlot* sl = &s->prof[name];
+            if ((sl->seen++ % s->prof_period) != 0) return;
+            slot = sl;
+            a = s->ev_get(); b = s->ev_get();
+            (void)hipEventRecord(a, s->st);
+        }
+        ~Prof() {
+            if (!slot) return;
+            (void)hipEventRecord(b, s->st);
+            slot->pending.emplace_back(a, b);
+            slot->n += 1;
+        }
+    };
+    void prof_prewarm(int n) override {
+        while ((int)ev_pool.size() < n) { hipEvent_t e = nullptr; if (hipEventCreate(&e) != hipSuccess) break; ev_pool.push_back(e); }
+    }
+    int prof_resolve() override {
+        for (auto& kv : prof) {
+            for (auto& pr : kv.second.pending) {
+                float ms = 0.f;
+                (void)hipEventSynchronize(pr.second);
+                if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) kv.second.ms += ms;
+                ev_pool.push_back(pr.first); ev_pool.push_back(pr.second);
+            }
+            kv.second.pending.clear();
+        }
+        return PCR_OK;
+    }
+
+    // ---- the training loop
+    // ccd-r1.cpp:107-118: V = 0, residuals = ratings, reg from U
+    int begin() {
+        HIPCHK(hipMemcpyAsync(d_res_r.p, h_val_r.data(), (size_t)nnz * sizeof(RT), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_res_c.p, h_val_c.data(), (size_t)nnz * sizeof(RT), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_tres.p, h_tval.data(), (size_t)tn * sizeof(double), hipMemcpyHostToDevice, st));
+        {
+            Prof ps(this, "ccd/init");
+            hipLaunchKernelGGL((k_ccd_init<T>), dim3(Bi), dim3(ccd::BLOCK), 0, st, base->d_V.p, d2 * ld, (const T*)base->d_U.p, k, ld,
+                               (const int64_t*)base->d_uptr.p, d1, d_pregu.p);
+            hipLaunchKernelGGL(k_ccd_init_fin, dim3(1), dim3(ccd::BLOCK), 0, st, d_ctl.p, (const double*)d_pregu.p, Bi);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+        begun = true;
+        oiter = 0;
+        secs = 0.0;
+        return PCR_OK;
+    }
+    // rank t of outer iteration `oi` (ccd-r1.cpp:130-199): 3 maxinneriter + 3 launches, no host round trip
+    int enqueue_rank(int oi, int t) {
+        const int T_in = cp.maxinneriter;
+        {
+            Prof ps(this, "ccd/begin");
+            const int g = std::max(1, std::min(4096, cdiv(std::max(d1, d2), ccd::BLOCK)));
+            hipLaunchKernelGGL((k_ccd_begin<T>), dim3(g), dim3(ccd::BLOCK), 0, st, d_ctl.p, (const T*)base->d_U.p, (const T*)base->d_V.p, ld, t, oi, d1, d2,
+                               d_u.p, d_oldu.p, d_v.p, d_oldv.p);
+        }
+        for (int iter = 1; iter <= T_in; ++iter) {
+            const int addback = (iter == 1 && oi > 1) ? 1 : 0;          // ccd-r1.cpp:127-130, fused into the first sweeps
+            {
+                Prof ps(this, "ccd/vsweep");
+                hipLaunchKernelGGL((k_ccd_sweep<RT>), dim3(nvb), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, (const int64_t*)d_cptr.p,
+                                   (const int32_t*)d_row_c.p, d_res_c.p, (const double*)d_u.p, (const double*)d_oldu.p, (const double*)d_oldv.p, d_v.p,
+                                   (const int32_t*)d_ilong.p, nilong, (const int32_t*)d_ishort.p, nishort, prm.lambda, cp.do_nmf, addback, d_vpart.p);
+            }
+            {
+                Prof ps(this, "ccd/usweep");
+                hipLaunchKernelGGL((k_ccd_sweep<RT>), dim3(nub), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, (const int64_t*)base->d_uptr.p,
+                                   (const int32_t*)base->d_item.p, d_res_r.p, (const double*)d_v.p, (const double*)d_oldv.p, (const double*)d_oldu.p, d_u.p,
+                                   (const int32_t*)d_ulong.p, nulong, (const int32_t*)d_ushort.p, nushort, prm.lambda, cp.do_nmf, addback, d_upart.p);
+            }
+            {
+                Prof ps(this, "ccd/decide");
+                hipLaunchKernelGGL(k_ccd_decide, dim3(1), dim3(ccd::BLOCK), 0, st, d_ctl.p, (const double*)d_vpart.p, nvb, (const double*)d_upart.p, nub,
+                                   cp.eps, oi, t, iter);
+            }
+        }
+        {
+            Prof ps(this, "ccd/resid");
+            hipLaunchKernelGGL((k_ccd_resid<T, RT>), dim3(2 * B + Bu + Bv + Bt), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, B, Bu, Bv, Bt, nnz,
+                               d1, d2, tn, d_res_r.p, (const int32_t*)d_row_r.p, (const int32_t*)base->d_item.p, d_res_c.p, (const int32_t*)d_row_c.p,
+                               (const int32_t*)d_col_c.p, (const int64_t*)base->d_uptr.p, (const int64_t*)d_cptr.p, (const double*)d_u.p,
+                               (const double*)d_oldu.p, (const double*)d_v.p, (const double*)d_oldv.p, base->d_U.p, base->d_V.p, ld, t,
+                               (const int32_t*)d_tu.p, (const int32_t*)d_ti.p, d_tres.p, d_ploss.p, d_pregu.p, d_pregv.p, d_prmse.p,
+                               (T_in < 1 && oi > 1) ? 1 : 0);
+        }
+        {
+            Prof ps(this, "ccd/final");
+            hipLaunchKernelGGL(k_ccd_final, dim3(1), dim3(ccd::BLOCK), 0, st, d_ctl.p, (const double*)d_ploss.p, B, (const double*)d_pregu.p, Bu,
+                               (const double*)d_pregv.p, Bv, (const double*)d_prmse.p, Bt, tn, prm.lambda);
+        }
+        HIPCHK(hipGetLastError());
+        return PCR_OK;
+    }
+    int read_ctl() {
+        HIPCHK(hipMemcpyAsync(h_ctl, d_ctl.p, sizeof(CcdCtl), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return PCR_OK;
+    }
+    double elapsed_s() {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ev_a, ev_b) != hipSuccess) return 0.0;
+        return ms / 1e3;
+    }
+
+    // ccd-r1.cpp:97-212 ccdr1(): from the current U (V is zeroed); with verbose one line per rank, evaluated after every printed
+    // rank when do_predict and the test set is not empty (:196-206).  hist[0] is zero (nothing is printed before the first rank);
+    // hist[o]: outer iteration o -- obj of its last rank, the last evaluation, cumulative device seconds of the CCDR1 kernels,
+    // cg_v = inner iterations executed, cg_u = ranks executed.
+    int train(pcr_log_fn log, void* ctx, pcr_iter_stats* hist) override {
+        auto emit = [&](const char* s) { if (log) log(ctx, s); else { fputs(s, stdout); fputc('\n', stdout); fflush(stdout); } };
+        RC(begin());
+        if (hist) {
+            memset(hist, 0, sizeof(pcr_iter_stats) * (size_t)(std::max(0, prm.maxiter) + 1));
+        }
+        double te = 0.0, tndcg = 0.0;
+        const bool logging = prm.verbose != 0;
+        const bool evalp = prm.do_predict != 0 && tnnz_file != 0;
+        char line[1024];
+        for (int oi = 1; oi <= prm.maxiter; ++oi) {
+            oiter = oi;
+            if (!logging) {
+                HIPCHK(hipEventRecord(ev_a, st));
+                for (int t = 0; t < k; ++t) RC(enqueue_rank(oi, t));
+                HIPCHK(hipEventRecord(ev_b, st));
+                RC(read_ctl());
+                secs += elapsed_s();
+            } else {
+                for (int t = 0; t < k; ++t) {
+                    HIPCHK(hipEventRecord(ev_a, st));
+                    RC(enqueue_rank(oi, t));
+                    HIPCHK(hipEventRecord(ev_b, st));
+                    RC(read_ctl());
+                    if (!h_ctl->printed) break;                   // ccd-r1.cpp:131: every later rank is skipped too
+                    secs += elapsed_s();
+                    int n = snprintf(line, sizeof line, "iter %d rank %d time %.10g loss %.10g obj %.10g diff %.10g gnorm %.6g reg %.7g ", oi,
+                                     t + 1, secs, h_ctl->loss, h_ctl->obj, h_ctl->oldobj - h_ctl->obj, 0.0, h_ctl->reg);
+                    if (evalp) {
+                        RC(base->evaluate(1, prm.ndcg_k, &te, &tndcg));
+                        n += snprintf(line + n, sizeof line - (size_t)n, "rmse %.10g", h_ctl->rmse);
+                        snprintf(line + n, sizeof line - (size_t)n, "(Testing) pairwise error %lf NDCG %lf", te, tndcg);
+                    }
+                    emit(line);
+                }
+            }
+            if (hist) {
+                pcr_iter_stats& r = hist[oi];
+                r.obj = h_ctl->obj; r.test_err = te; r.test_ndcg = tndcg; r.seconds = secs;
+                r.cg_v = h_ctl->inner_iters; r.cg_u = h_ctl->ranks_done;
+            }
+        }
+        return PCR_OK;
+    }
+    // n more outer iterations without evaluation, one host round trip each (a training run is started first if none is); seconds
+    // in the records carry on from pcr_train and earlier calls: cumulative since the start of training
+    int iterate_abi(int n, pcr_iter_stats* out) override {
+        if (n < 0) { pcr_set_error("n must be >= 0"); return PCR_ERR_ARG; }
+        if (!begun) RC(begin());
+        for (int q = 0; q < n; ++q) {
+            const int oi = ++oiter;
+            HIPCHK(hipEventRecord(ev_a, st));
+            for (int t = 0; t < k; ++t) RC(enqueue_rank(oi, t));
+            HIPCHK(hipEventRecord(ev_b, st));
+            RC(read_ctl());
+            secs += elapsed_s();
+            if (out) {
+                memset(&out[q], 0, sizeof(pcr_iter_stats));
+                out[q].obj = h_ctl->obj; out[q].seconds = secs;
+                out[q].cg_v = h_ctl->inner_iters; out[q].cg_u = h_ctl->ranks_done;
+            }
+        }
+        return PCR_OK;
+    }
+
+    int set_factors(const double* U, const double* V, bool local) override { begun = false; return base->set_factors(U, V, local); }
+    int get_factors(double* U, double* V, bool local) override { return base->get_factors(U, V, local); }
+    int evaluate(int which, int ndcg_k, double* err, double* ndcg) override { return base->evaluate(which, ndcg_k, err, ndcg); }
+    int residual_mismatch(double* value) override {
+        hipLaunchKernelGGL((k_ccd_mismatch<RT>), dim3(B), dim3(ccd::BLOCK), 0, st, (const RT*)d_res_r.p, (const RT*)d_res_c.p, (const int32_t*)d_c2r.p,
+                           nnz, d_pmis.p);
+        HIPCHK(hipGetLastError());
+        std::vector<double> h((size_t)B);
+        HIPCHK(hipMemcpyAsync(h.data(), d_pmis.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        double s = 0.0;
+        for (double x : h) s += x;
+        *value = s;
+        return PCR_OK;
+    }
+    // any values, as the reference takes them: maxinneriter <= 0 runs no inner iteration (each rank only re-forms its residual)
+    int set_ccd_params(const pcr_ccd_params* p) override {
+        cp = *p;
+        return PCR_OK;
+    }
+    static int not_ccd(const char* what) {
+        pcr_set_error(std::string(what) + ": a PrimalCR / PrimalCR++ entry point; this solver is CCDR1 (solver type 0)");
+        return PCR_ERR_STATE;
+    }
+    int comp_m(double*) override { return not_ccd("pcr_comp_m"); }
+    int objective(double*) override { return not_ccd("pcr_objective"); }
+    int obtain_g(double*) override { return not_ccd("pcr_obtain_g"); }
+    int compute_Ha(const double*, double*) override { return not_ccd("pcr_compute_Ha"); }
+    int solve_delta(const double*, double*, int*) override { return not_ccd("pcr_solve_delta"); }
+    int update_V(double*, int*) override { return not_ccd("pcr_update_V"); }
+    int update_U(double*, int64_t*) override { return not_ccd("pcr_update_U"); }
+    int comm_init(const void*) override { pcr_set_error("CCDR1 runs on one rank"); return PCR_ERR_UNSUPPORTED; }
+    int comm_init_p2p(const char*) override { pcr_set_error("CCDR1 runs on one rank"); return PCR_ERR_UNSUPPORTED; }
+    void comm_abort() override {}
+    int comm_nranks() override { return 1; }
+    int sync() override { HIPCHK(hipStreamSynchronize(st)); return PCR_OK; }
+    std::string ustep_classes() override { return ""; }
+    int class_rows(const std::string& slot, double*) override { pcr_set_error("no U-step class '" + slot + "' on a CCDR1 solver"); return PCR_ERR_ARG; }
+};

@@ -264,6 +264,16 @@ static void build_test_csr(int64_t d1, int64_t d2, int64_t nnz, const int32_t* u
     }
 }
 
+// pcr_dataset::traw_*: the file's test triplets, kept only when the test CSR cannot stand for them
+static void keep_raw_test(pcr_dataset& ds, int64_t d1, int64_t tnnz, const int32_t* tuser, const int32_t* titem, const double* tval) {
+    bool as_is = true;
+    for (int64_t z = 0; z < tnnz && as_is; ++z) as_is = tuser[z] < d1 && (z == 0 || tuser[z] >= tuser[z - 1]);
+    if (as_is) return;
+    ds.traw_user.assign(tuser, tuser + tnnz);
+    ds.traw_item.assign(titem, titem + tnnz);
+    ds.traw_val.assign(tval, tval + tnnz);
+}
+
 static int check_test_ids(int64_t d2, int64_t tnnz, const int32_t* tuser, const int32_t* titem, int threads) {
     const int T = pieces_for(tnnz, threads);
     std::vector<int64_t> bad((size_t)T, -1);
@@ -296,6 +306,7 @@ extern "C" int pcr_dataset_from_triplets(int64_t d1, int64_t d2, int64_t nnz, co
         if (rc != PCR_OK) return rc;
         rc = check_test_ids(d2, tnnz, tuser, titem, threads);
         if (rc != PCR_OK) return rc;
+        keep_raw_test(*ds, d1, tnnz, tuser, titem, tval);
         build_test_csr(d1, d2, tnnz, tuser, titem, tval, ds->test, threads, false);
         ds->tnnz_file = tnnz;
         *out = ds.release();
@@ -643,6 +654,7 @@ extern "C" int pcr_dataset_load_mt(const char* dir, int threads, pcr_dataset** o
             if (rc != PCR_OK) return rc;
             rc = check_test_ids(n, tnnz, tu.data(), ds->test.item.data(), threads);
             if (rc != PCR_OK) return rc;
+            keep_raw_test(*ds, m, tnnz, tu.data(), ds->test.item.data(), ds->test.val.data());
         } else {
             tnnz = 0;
         }
@@ -656,11 +668,12 @@ extern "C" int pcr_dataset_load_mt(const char* dir, int threads, pcr_dataset** o
 // ---- binary side-car cache of the converted data set
 namespace {
 struct CacheHeader {
-    char magic[8];                 // "PCRCACH1"
+    char magic[8];                 // "PCRCACH2"
     int64_t d1, d2, nnz, tnnz, tnnz_file;
+    int64_t traw;                  // raw test triplets kept (pcr_dataset::traw_*), 0 for a user-sorted test file
     int64_t stamp[6];              // size, mtime (ns) of meta, training file, test file at the time of the parse (0: not recorded)
 };
-const char kCacheMagic[8] = {'P', 'C', 'R', 'C', 'A', 'C', 'H', '1'};
+const char kCacheMagic[8] = {'P', 'C', 'R', 'C', 'A', 'C', 'H', '2'};
 
 bool file_stamp(const std::string& p, int64_t* size, int64_t* mtime) {
     struct stat sb;
@@ -701,7 +714,7 @@ bool par_io(int fd, off_t off, void* mem, size_t n, bool write, int threads) {
     return true;
 }
 
-// Layout: header | train.index | train.item | train.val | test.index | test.item | test.val.  Written and read by the host
+// Layout: header | train.index | train.item | train.val | test.index | test.item | test.val | traw_user | traw_item | traw_val.  Written and read by the host
 // threads in disjoint pieces (a 1.2 GB cache through one fread / fwrite was SLOWER than parsing the text it caches).
 int save_cache(const pcr_dataset* ds, const char* path, const int64_t stamp[6]) {
     if (!ds || !path) { pcr_set_error("pcr_dataset_save_cache: bad argument"); return PCR_ERR_ARG; }
@@ -711,6 +724,7 @@ int save_cache(const pcr_dataset* ds, const char* path, const int64_t stamp[6]) 
     CacheHeader h;
     memcpy(h.magic, kCacheMagic, 8);
     h.d1 = ds->train.d1; h.d2 = ds->train.d2; h.nnz = ds->train.nnz(); h.tnnz = ds->test.nnz(); h.tnnz_file = ds->tnnz_file;
+    h.traw = (int64_t)ds->traw_val.size();
     for (int i = 0; i < 6; ++i) h.stamp[i] = stamp ? stamp[i] : 0;
     const int threads = pcr_host_threads();
     off_t off = 0;
@@ -719,6 +733,7 @@ int save_cache(const pcr_dataset* ds, const char* path, const int64_t stamp[6]) 
     auto put = [&](const void* p, size_t bytes) { if (ok && bytes) ok = par_io(fd, off, const_cast<void*>(p), bytes, true, threads); off += (off_t)bytes; };
     put(ds->train.index.data(), ds->train.index.size() * 8); put(ds->train.item.data(), ds->train.item.size() * 4); put(ds->train.val.data(), ds->train.val.size() * 8);
     put(ds->test.index.data(), ds->test.index.size() * 8); put(ds->test.item.data(), ds->test.item.size() * 4); put(ds->test.val.data(), ds->test.val.size() * 8);
+    put(ds->traw_user.data(), ds->traw_user.size() * 4); put(ds->traw_item.data(), ds->traw_item.size() * 4); put(ds->traw_val.data(), ds->traw_val.size() * 8);
     ok = (::close(fd) == 0) && ok;
     if (!ok || rename(tmp.c_str(), path) != 0) { remove(tmp.c_str()); pcr_set_error(std::string("can't write ") + path); return PCR_ERR_IO; }
     return PCR_OK;
@@ -732,9 +747,9 @@ int load_cache(const char* path, const int64_t want[6], pcr_dataset** out) {
     struct stat sb;
     if (fstat(fd, &sb) != 0 || (size_t)sb.st_size < sizeof(h) || !par_io(fd, 0, &h, sizeof(h), false, 1) || memcmp(h.magic, kCacheMagic, 8) != 0)
         return fail("not a data set cache of this version");
-    if (h.d1 < 0 || h.d2 < 0 || h.nnz < 0 || h.tnnz < 0 || h.d1 > kMaxDim || h.d2 > kMaxDim) return fail("corrupt header");
+    if (h.d1 < 0 || h.d2 < 0 || h.nnz < 0 || h.tnnz < 0 || h.traw < 0 || h.d1 > kMaxDim || h.d2 > kMaxDim) return fail("corrupt header");
     {   // the header must describe exactly this file before anything is allocated from it
-        const __int128 want_bytes = (__int128)sizeof(h) + 2 * (__int128)(h.d1 + 1) * 8 + (__int128)(h.nnz + h.tnnz) * 12;
+        const __int128 want_bytes = (__int128)sizeof(h) + 2 * (__int128)(h.d1 + 1) * 8 + (__int128)(h.nnz + h.tnnz) * 12 + (__int128)h.traw * 16;
         if ((__int128)sb.st_size != want_bytes) return fail("truncated or corrupt (size does not match the header)");
     }
     if (want) for (int i = 0; i < 6; ++i) if (h.stamp[i] != want[i]) return fail("stale (the text files changed)");
@@ -748,7 +763,11 @@ int load_cache(const char* path, const int64_t want[6], pcr_dataset** out) {
     auto get = [&](void* p, size_t bytes) { if (ok && bytes) ok = par_io(fd, off, p, bytes, false, threads); off += (off_t)bytes; };
     get(ds->train.index.data(), ds->train.index.size() * 8); get(ds->train.item.data(), ds->train.item.size() * 4); get(ds->train.val.data(), ds->train.val.size() * 8);
     get(ds->test.index.data(), ds->test.index.size() * 8); get(ds->test.item.data(), ds->test.item.size() * 4); get(ds->test.val.data(), ds->test.val.size() * 8);
+    ds->traw_user.resize((size_t)h.traw); ds->traw_item.resize((size_t)h.traw); ds->traw_val.resize((size_t)h.traw);
+    get(ds->traw_user.data(), ds->traw_user.size() * 4); get(ds->traw_item.data(), ds->traw_item.size() * 4); get(ds->traw_val.data(), ds->traw_val.size() * 8);
     if (!ok) return fail("truncated");
+    for (int64_t z = 0; z < h.traw; ++z)
+        if (ds->traw_user[(size_t)z] < 0 || ds->traw_item[(size_t)z] < 0 || ds->traw_item[(size_t)z] >= h.d2) return fail("raw test id out of range");
     const std::vector<int64_t>&ti = ds->train.index, &xi = ds->test.index;
     if (ti.front() != 0 || ti.back() != h.nnz || xi.front() != 0 || xi.back() != h.tnnz) return fail("corrupt row pointers");
     // consistency of everything an index will be taken from, user ranges side by side: 0 = fine, else the first kind of damage

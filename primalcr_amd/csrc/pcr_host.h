@@ -35,6 +35,11 @@ struct PcrCsr {
 struct pcr_dataset {
     PcrCsr train, test;
     int64_t tnnz_file = 0;        // test entries read from the file (T.nnz, pcrpp.cpp:865)
+    // The test file's triplets in file order (the reference's testset_t T, util.h:360-371) when the test CSR does not hold them
+    // as they are -- a file that is not user-sorted or names a user id >= d1 (convert()'s scan moves or drops such entries);
+    // empty otherwise (the CSR, row by row, IS the file).  CCDR1's printed rmse walks T (util.cpp:206-215).
+    std::vector<int32_t> traw_user, traw_item;
+    std::vector<double> traw_val;
 };
 
 // dense rank of the rating bucket inside each user: lround(val) for PrimalCR++

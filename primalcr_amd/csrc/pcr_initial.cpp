@@ -122,3 +122,50 @@ extern "C" int pcr_initial_rows(double* X, int64_t n, int64_t k, int64_t row0, i
     return guarded("pcr_initial_rows", [&]() -> int { normal_stream(X, row0 * k, nrows * k); return PCR_OK; });
 }
 
+
+// util.cpp:95-101 initial_col(): X[i][j] = 0.1 * drand48() for i < n, j < k, drawn in that order, from glibc's unseeded stream.
+// glibc's drand48 without srand48 starts from state 0 (its static state is zero-initialised; the first call only sets a and c), so
+// the first value is 0.1 * 11 / 2^48.  erand48 places the 48 state bits in the mantissa of a double in [1, 2) and subtracts 1:
+// exactly X / 2^48.  The LCG x -> a x + c mod 2^48 composes in closed form, so a range that starts at draw d starts at the
+// state (a^d, c (a^d - 1) / (a - 1)) applied to 0 -- computed by squaring without any division.
+namespace {
+constexpr uint64_t kDrandA = 0x5DEECE66Dull, kDrandC = 0xBull, kDrandMask = (1ull << 48) - 1;
+// state of the unseeded stream after d draws
+uint64_t drand_state_after(uint64_t d) {
+    uint64_t A = 1, C = 0;                  // accumulated map x -> A x + C
+    uint64_t a = kDrandA, c = kDrandC;      // map of 2^bit draws
+    for (; d; d >>= 1) {
+        if (d & 1) { C = (a * C + c) & kDrandMask; A = (a * A) & kDrandMask; }
+        c = (a * c + c) & kDrandMask;
+        a = (a * a) & kDrandMask;
+    }
+    return C;                               // applied to the initial state 0
+}
+void drand_fill(double* X, uint64_t first, uint64_t count) {
+    uint64_t x = drand_state_after(first);
+    for (uint64_t i = 0; i < count; ++i) {
+        x = (kDrandA * x + kDrandC) & kDrandMask;
+        X[i] = 0.1 * ((double)x * 0x1p-48);
+    }
+}
+}  // namespace
+
+extern "C" int pcr_initial_col(double* X, int64_t n, int64_t k) {
+    if (!X || n < 0 || k < 0) { pcr_set_error("pcr_initial_col: bad argument"); return PCR_ERR_ARG; }
+    return guarded("pcr_initial_col", [&]() -> int {
+        const uint64_t total = (uint64_t)n * (uint64_t)k;
+        int T = pcr_host_threads();
+        if (total < ((uint64_t)1 << 21)) T = 1;                           // (a few ms of serial work)
+        if (T <= 1) { drand_fill(X, 0, total); return PCR_OK; }
+        pcr_parallel_ranges((int64_t)total, T, [&](int, int64_t lo, int64_t hi) { drand_fill(X + lo, (uint64_t)lo, (uint64_t)(hi - lo)); });
+        return PCR_OK;
+    });
+}
+
+// pmf.h:36,39,47
+extern "C" void pcr_ccd_params_default(pcr_ccd_params* p) {
+    if (!p) return;
+    p->maxinneriter = 5;
+    p->eps = 1e-3;
+    p->do_nmf = 0;
+}

@@ -146,6 +146,9 @@ struct pcr_solver {
     std::vector<std::pair<std::string, double>> setup_ms;   // wall time of the phases of pcr_solver_create, in order (pcr_solver_counter "setup_ms/<i>", pcr_solver_setup_phase)
     virtual int prof_resolve() = 0;
     virtual void prof_prewarm(int n) = 0;
+    // CCDR1 only (pcr_ccd.h): the "ccd_residual_mismatch" counter, pcr_solver_set_ccd_params
+    virtual int residual_mismatch(double*) { pcr_set_error("pcr_solver_counter: 'ccd_residual_mismatch' exists on a CCDR1 solver only"); return PCR_ERR_STATE; }
+    virtual int set_ccd_params(const pcr_ccd_params*) { pcr_set_error("pcr_solver_set_ccd_params: not a CCDR1 solver (solver type 0)"); return PCR_ERR_STATE; }
 };
 
 // launch knobs: pcr_tune() values read once when the solver is created (include/primalcr.h lists them)
@@ -2289,6 +2292,8 @@ struct Solver final : pcr_solver {
     int sync() override { RC(sync_checked()); return PCR_OK; }
 };
 
+#include "pcr_ccd.h"
+
 // ------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------
@@ -2307,11 +2312,26 @@ extern "C" {
 
 static int solver_create(const pcr_dataset* ds, const pcr_params* p, int rank, int nranks, int64_t shard_first, int64_t d1_total, pcr_solver** out) {
     if (!ds || !p || !out || nranks < 1 || rank < 0 || rank >= nranks) { pcr_set_error("pcr_solver_create: bad argument"); return PCR_ERR_ARG; }
-    if (p->solver_type != PCR_SOLVER_PCR && p->solver_type != PCR_SOLVER_PCRPP) {
-        pcr_set_error("wrong solver type (" + std::to_string(p->solver_type) + "): 1 = PrimalCR, 2 = PrimalCR++");
+    if (p->solver_type != PCR_SOLVER_CCDR1 && p->solver_type != PCR_SOLVER_PCR && p->solver_type != PCR_SOLVER_PCRPP) {
+        pcr_set_error("wrong solver type (" + std::to_string(p->solver_type) + "): 0 = CCDR1, 1 = PrimalCR, 2 = PrimalCR++");
         return PCR_ERR_ARG;
     }
     if (p->precision != PCR_F64 && p->precision != PCR_F32) { pcr_set_error("precision must be PCR_F32 or PCR_F64"); return PCR_ERR_ARG; }
+    if (p->solver_type == PCR_SOLVER_CCDR1) {
+        if (nranks != 1 || shard_first >= 0) { pcr_set_error("CCDR1 (solver type 0) runs on one rank"); return PCR_ERR_UNSUPPORTED; }
+        return abi_guard("pcr_solver_create", [&]() -> int {
+            if (p->precision == PCR_F64) {
+                std::unique_ptr<CcdSolver<double>> s(new CcdSolver<double>());
+                RC(s->init(ds, p));
+                *out = s.release();
+            } else {
+                std::unique_ptr<CcdSolver<float>> s(new CcdSolver<float>());
+                RC(s->init(ds, p));
+                *out = s.release();
+            }
+            return PCR_OK;
+        });
+    }
     return abi_guard("pcr_solver_create", [&]() -> int {
         if (p->precision == PCR_F64) {
             std::unique_ptr<Solver<double>> s(new Solver<double>());
@@ -2379,11 +2399,17 @@ int pcr_solver_counter(pcr_solver* s, const char* name, double* value) {
     if (!name || !value) { pcr_set_error("pcr_solver_counter: bad argument"); return PCR_ERR_ARG; }
     if (!strcmp(name, "ustep_row_gathers")) { *value = s->ustep_rows; return PCR_OK; }
     if (!strncmp(name, "ustep_row_gathers/", 18)) return s->class_rows(name + 18, value);
+    if (!strcmp(name, "ccd_residual_mismatch")) PCR_ABI("pcr_solver_counter", s->residual_mismatch(value));
     pcr_set_error(std::string("pcr_solver_counter: unknown counter '") + name + "'");
     return PCR_ERR_ARG;
 }
 // a failing rank tells its peers (p2p: shared error flag; RCCL: local abort) before it reports the error
 static int leave_on_error(pcr_solver* s, int rc) { if (rc != PCR_OK) s->comm_abort(); return rc; }
+int pcr_solver_set_ccd_params(pcr_solver* s, const pcr_ccd_params* p) {
+    S_OR_ARG;
+    if (!p) { pcr_set_error("pcr_solver_set_ccd_params: null parameters"); return PCR_ERR_ARG; }
+    return s->set_ccd_params(p);
+}
 int pcr_solver_set_local_only(pcr_solver* s, int on) { S_OR_ARG; s->local_only = on != 0; return PCR_OK; }
 int pcr_solver_shard(const pcr_solver* s, int64_t* first_user, int64_t* n_users, int64_t* nnz_local) {
     S_OR_ARG;

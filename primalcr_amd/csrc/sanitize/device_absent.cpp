@@ -34,6 +34,7 @@ NO_SOLVER(pcr_solver_comm_init, pcr_solver*, const void*)
 NO_SOLVER(pcr_solver_comm_init_p2p, pcr_solver*, const char*)
 int pcr_solver_comm_nranks(pcr_solver*) { return -1; }
 NO_SOLVER(pcr_solver_counter, pcr_solver*, const char*, double*)
+NO_SOLVER(pcr_solver_set_ccd_params, pcr_solver*, const pcr_ccd_params*)
 NO_SOLVER(pcr_solver_ustep_classes, pcr_solver*, char*, int64_t)
 NO_SOLVER(pcr_solver_setup_phase, const pcr_solver*, int, const char**, double*)
 NO_SOLVER(pcr_solver_set_local_only, pcr_solver*, int)
