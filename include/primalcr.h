@@ -215,6 +215,8 @@ int pcr_partition_users(const int64_t *index, int64_t d1, int nparts, int64_t *b
  *                   (a rehearsal): every rank publishes the queues its process holds; past the budget kernels of different processes
  *                   no longer run side by side (0.5 us -> 7-11 ms per dependent hand-off, tools/ubench/queue_budget_probe.hip), so
  *                   the device-driven exchange is switched off for the whole job (host-synchronised exchange, one line on stderr)
+ *   recommend_select  0 = pcr_recommend's kernel without its streaming selection (the GEMM and the sweep alone; the lists come back
+ *                   empty): tools/exp_recommend.py times the selection's share with it; default 1
  *   count_rows      1 = the U-step kernels count the rows of V they gather (pcr_solver_counter; a diagnostic that
  *                   costs the short-user classes 10-20 %, so off by default)
  *   debug           1 = print launch decisions to stderr
@@ -362,6 +364,42 @@ int pcr_iterate(pcr_solver *s, int n, pcr_iter_stats *out);
 int pcr_predict(const double *U, int64_t d1, const double *V, int64_t d2, int64_t k,
                 int64_t n, const int32_t *user, const int32_t *item, double *pred,
                 int device);                                               /* [device] */
+
+/* ------------------------------------------------------------------------- */
+/* top-K recommendation (no reference counterpart: pmf-predict.cpp scores     */
+/* known pairs only)                                                          */
+/* ------------------------------------------------------------------------- */
+/* For each requested user u: the K items j of highest score s(u, j) = U[u] . V[j], computed on the device.
+ *   Order       descending computed score; equal computed scores by ascending item id (in every code path, merges of
+ *               partial lists included), so results are exactly checkable.
+ *   Exclusion   with exclusion on, every item of u's TRAINING CSR row is left out (duplicated (user, item) pairs allowed);
+ *               test ratings are never excluded.
+ *   Padding     a user with fewer than K eligible items: the row ends with item -1 and score -INFINITY.
+ *   Precision   fp64 factors are scored in fp64; fp32 factors with f32 inputs and f32 accumulation (the score is a fixed,
+ *               k-ordered chain of f32 fmas).  Scores come back as double.
+ *   Determinism a score depends on (u, j) alone -- not on the other users of the call, their order or the launch grid; two
+ *               identical calls return bitwise-identical output.
+ *   Limit       1 <= K <= PCR_RECOMMEND_MAX_K; anything out of range is PCR_ERR_ARG before any device work.
+ * Output: items[n * K] (0-based ids, int32) and scores[n * K], row i for users[i].
+ * PCR_RECOMMEND_MAX_K = 1024: the selection stages a user's list in LDS next to 16 x 64 candidate slots per wave (24 KB per
+ * wave in fp64 at K = 1024, four waves per workgroup); larger K would leave one workgroup per CU. */
+#define PCR_RECOMMEND_MAX_K 1024
+#define PCR_REC_EXCLUDE_TRAIN 1   /* pcr_recommend flag: leave out the solver's own training ratings */
+
+/* Standalone, like pcr_predict: U (d1 x k) and V (d2 x k) are host fp64 factors in model-file layout.  index[d1 + 1] / item
+ * (the training CSR, 0-based, index[0] = 0, monotone) give the exclusion; index = item = NULL: none.  users[n] are 0-based
+ * ids (NULL: users 0 .. n-1, n <= d1).  dtype PCR_F32 rounds the factors to f32 and scores them in f32, PCR_F64 scores in
+ * fp64.  Arguments (ids inside the model, CSR shape) are checked on the host before any device is looked for. */
+int pcr_recommend_model(const double *U, int64_t d1, const double *V, int64_t d2, int64_t k,
+                        const int64_t *index, const int32_t *item,
+                        int64_t n, const int32_t *users, int topk, int dtype,
+                        int32_t *items, double *scores, int device);       /* [device] */
+/* The same on a live solver's device factors (any solver type), in its storage type, on its stream; training state is not
+ * touched (training that continues afterwards gives bitwise the same factors).  users[n] are GLOBAL 0-based ids of this
+ * rank's shard (NULL: all of the shard's users in order, n = its n_users); a user outside the shard is PCR_ERR_ARG.
+ * flags: PCR_REC_EXCLUDE_TRAIN.  Profile slots: recommend/score, recommend/merge. */
+int pcr_recommend(pcr_solver *s, int64_t n, const int32_t *users, int topk, int flags,
+                  int32_t *items, double *scores);                         /* [device] */
 
 /* per-kernel device timing (HIP events on the solver's stream, one pair per launch).
  * slot names: "<class>/<workgroup size>[.<length bound>][g][c][l][r][#n]" for the per-user kernels (classes

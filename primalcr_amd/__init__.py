@@ -2,15 +2,15 @@
 
 The product is ``primalcr_amd/lib/libprimalcr.so`` (hand-written HIP for gfx950 behind the C
 ABI of ``include/primalcr.h``) plus the drop-in CLIs ``primalcr_amd/bin/omp-pmf-train`` and
-``omp-pmf-predict``.  This package is the thin host-side mirror of the reference's solver
+``omp-pmf-predict`` and ``omp-pmf-recommend``.  This package is the thin host-side mirror of the reference's solver
 interface (``pmf.h``) over that C ABI via ctypes -- used by tests and ``bench.py``.
 
 There is no CPU fallback: importing works without a GPU (host-side helpers such as the loader
 and ``initial`` are usable), but every training entry point raises ``PcrError`` when the HIP
 library or a GPU is missing.
 """
-from .api import (PCR_F32, PCR_F64, PCR_SOLVER_CCDR1, PCR_SOLVER_PCR, PCR_SOLVER_PCRPP, CcdParameter, Dataset, Parameter, PcrError,
-                  Solver, comm_unique_id, initial, initial_col, initial_rows, lib, lib_path, use_library, model_load, model_save, partition_users, predict, tune, tuned)
+from .api import (PCR_F32, PCR_F64, PCR_REC_EXCLUDE_TRAIN, PCR_RECOMMEND_MAX_K, PCR_SOLVER_CCDR1, PCR_SOLVER_PCR, PCR_SOLVER_PCRPP, CcdParameter, Dataset, Parameter, PcrError,
+                  Solver, comm_unique_id, initial, initial_col, initial_rows, lib, lib_path, use_library, model_load, model_save, partition_users, predict, recommend, tune, tuned)
 
-__all__ = ["PCR_F32", "PCR_F64", "PCR_SOLVER_CCDR1", "PCR_SOLVER_PCR", "PCR_SOLVER_PCRPP", "CcdParameter", "Dataset", "Parameter", "PcrError",
-           "Solver", "comm_unique_id", "initial", "initial_col", "initial_rows", "lib", "lib_path", "use_library", "model_load", "model_save", "partition_users", "predict", "tune", "tuned"]
+__all__ = ["PCR_F32", "PCR_F64", "PCR_REC_EXCLUDE_TRAIN", "PCR_RECOMMEND_MAX_K", "PCR_SOLVER_CCDR1", "PCR_SOLVER_PCR", "PCR_SOLVER_PCRPP", "CcdParameter", "Dataset", "Parameter", "PcrError",
+           "Solver", "comm_unique_id", "initial", "initial_col", "initial_rows", "lib", "lib_path", "use_library", "model_load", "model_save", "partition_users", "predict", "recommend", "tune", "tuned"]

@@ -8,6 +8,8 @@ import numpy as np
 
 PCR_SOLVER_CCDR1, PCR_SOLVER_PCR, PCR_SOLVER_PCRPP = 0, 1, 2
 PCR_F32, PCR_F64 = 0, 1
+PCR_RECOMMEND_MAX_K = 1024
+PCR_REC_EXCLUDE_TRAIN = 1
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -137,6 +139,8 @@ def lib():
     L.pcr_train.argtypes = [vp, vp, vp, C.POINTER(IterStats)]
     L.pcr_iterate.argtypes = [vp, ci, C.POINTER(IterStats)]
     L.pcr_predict.argtypes = [_dp, i64, _dp, i64, i64, i64, _ip, _ip, _dp, ci]
+    L.pcr_recommend_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, vp, ci, ci, vp, vp, ci]
+    L.pcr_recommend.argtypes = [vp, i64, vp, ci, ci, vp, vp]
     L.pcr_profile_enable.argtypes = [vp, ci]
     L.pcr_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(cd), C.POINTER(i64)]
     L.pcr_profile_scope.argtypes = [vp, C.c_char_p, C.POINTER(i64), C.POINTER(i64)]
@@ -223,6 +227,31 @@ def predict(U, V, user, item, device=0):
     out = np.empty(user.shape[0], np.float64)
     _chk(lib().pcr_predict(U, U.shape[0], V, V.shape[0], U.shape[1], user.shape[0], user, item, out, device))
     return out
+
+
+def recommend(U, V, topk, exclude=None, users=None, dtype=PCR_F64, device=0):
+    """Top-K items per user on the GPU (pcr_recommend_model): descending score, equal scores by ascending item id, rows padded
+    with (-1, -inf).  exclude: a Dataset (its training CSR) or an (index, item) pair, or None; users: 0-based ids (None: all).
+    Returns (items int32 [n, topk], scores float64 [n, topk])."""
+    U = np.ascontiguousarray(U, np.float64); V = np.ascontiguousarray(V, np.float64)
+    d1, k = U.shape
+    idx = it = None
+    if exclude is not None:
+        if isinstance(exclude, Dataset):
+            idx, it, _ = exclude.csr(0)
+        else:
+            idx, it = exclude
+        idx = np.ascontiguousarray(idx, np.int64); it = np.ascontiguousarray(it, np.int32)
+        if idx.shape[0] != d1 + 1 or idx[-1] != it.shape[0]:
+            raise ValueError(f"exclude: index must have d1 + 1 = {d1 + 1} entries, the last equal to len(item) = {it.shape[0]}")
+    if users is not None:
+        users = np.ascontiguousarray(users, np.int32)
+    n = d1 if users is None else users.shape[0]
+    items = np.empty((n, max(int(topk), 1)), np.int32); scores = np.empty((n, max(int(topk), 1)), np.float64)
+    _chk(lib().pcr_recommend_model(U.ctypes.data, d1, V.ctypes.data, V.shape[0], k, None if idx is None else idx.ctypes.data,
+                                   None if it is None else it.ctypes.data, n, None if users is None else users.ctypes.data, int(topk),
+                                   int(dtype), items.ctypes.data, scores.ctypes.data, device))
+    return items, scores
 
 
 def comm_unique_id() -> bytes:
@@ -493,6 +522,17 @@ class Solver:
         _chk(lib().pcr_profile_list(self._h, buf, 4096))
         names = [n for n in buf.value.decode().split(",") if n]
         return {n: self.profile_get(n) for n in names}
+
+    def recommend(self, topk=10, users=None, exclude_train=True):
+        """Top-K items per user from the device factors (pcr_recommend), in the solver's storage type.  users: GLOBAL 0-based
+        ids of this rank's shard (None: all of them, in order).  Returns (items int32 [n, topk], scores float64 [n, topk])."""
+        if users is not None:
+            users = np.ascontiguousarray(users, np.int32)
+        n = self.n_users if users is None else users.shape[0]
+        items = np.empty((n, max(int(topk), 1)), np.int32); scores = np.empty((n, max(int(topk), 1)), np.float64)
+        _chk(lib().pcr_recommend(self._h, n, None if users is None else users.ctypes.data, int(topk),
+                                 PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, items.ctypes.data, scores.ctypes.data))
+        return items, scores
 
     def sync(self):
         _chk(lib().pcr_solver_sync(self._h))

@@ -617,6 +617,9 @@ struct CcdSolver final : pcr_solver {
     int set_factors(const double* U, const double* V, bool local) override { begun = false; return base->set_factors(U, V, local); }
     int get_factors(double* U, double* V, bool local) override { return base->get_factors(U, V, local); }
     int evaluate(int which, int ndcg_k, double* err, double* ndcg) override { return base->evaluate(which, ndcg_k, err, ndcg); }
+    int recommend(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores) override {
+        return base->recommend_with(n, local, K, flags, items, scores, [this](const char* name) { return Prof(this, name); });
+    }
     int residual_mismatch(double* value) override {
         hipLaunchKernelGGL((k_ccd_mismatch<RT>), dim3(B), dim3(ccd::BLOCK), 0, st, (const RT*)d_res_r.p, (const RT*)d_res_c.p, (const int32_t*)d_c2r.p,
                            nnz, d_pmis.p);

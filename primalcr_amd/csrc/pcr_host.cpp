@@ -362,7 +362,7 @@ extern "C" int pcr_dataset_from_csr(int64_t d1, int64_t d2, const int64_t* index
 static std::map<std::string, std::string>& tune_table() { static thread_local std::map<std::string, std::string> t; return t; }
 static const char* const TUNE_KEYS[] = {"ustep_mode", "cluster_k", "cluster_users", "ubins", "ustep_gram", "spmm_tiles", "spmm_chunk", "sddmm_csc",
                                         "lanes", "pipeline", "window_cache", "prepare_merged", "resort_window", "allreduce_chunks", "p2p_ll",
-                                        "p2p_timeout_ms", "p2p_queue_budget", "count_rows", "debug", "win16", "ustep_win_lds", "plan_key64", "ustep_newton", "vblock_users", "fault_cluster_member", "fault_p2p_skip", "fault_p2p_coarse", nullptr};
+                                        "p2p_timeout_ms", "p2p_queue_budget", "count_rows", "debug", "win16", "ustep_win_lds", "plan_key64", "ustep_newton", "vblock_users", "recommend_select", "fault_cluster_member", "fault_p2p_skip", "fault_p2p_coarse", nullptr};
 extern "C" int pcr_tune(const char* key, const char* value) {
     if (!key) { pcr_set_error("pcr_tune: null key"); return PCR_ERR_ARG; }
     bool known = false;
@@ -1046,5 +1046,45 @@ extern "C" int pcr_partition_users(const int64_t* index, int64_t d1, int nparts,
         bounds[p] = std::max(lo, bounds[p - 1]);
     }
     bounds[nparts] = d1;
+    return PCR_OK;
+}
+
+int pcr_recommend_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
+                              const int32_t* item, int64_t n, const int32_t* users, int topk, int dtype, const int32_t* items,
+                              const double* scores, bool* sorted) {
+    auto bad = [](const std::string& why) { pcr_set_error("pcr_recommend_model: " + why); return PCR_ERR_ARG; };
+    if (sorted) *sorted = true;
+    if (!U || !V || d1 < 1 || d2 < 1 || k < 1 || n < 0) return bad("bad argument");
+    if (d2 >= ((int64_t)1 << 31) - 64) return bad("more than 2^31 items");
+    if (topk < 1 || topk > PCR_RECOMMEND_MAX_K) return bad("K = " + std::to_string(topk) + " outside [1, " + std::to_string(PCR_RECOMMEND_MAX_K) + "]");
+    if (dtype != PCR_F32 && dtype != PCR_F64) return bad("dtype must be PCR_F32 or PCR_F64");
+    if (n > 0 && (!items || !scores)) return bad("null output");
+    if ((index == nullptr) != (item == nullptr)) return bad("index and item go together");
+    if (!users && n > d1) return bad("n > d1 without a user list");
+    const int nth = pcr_host_threads();
+    if (users) {
+        std::vector<int64_t> first((size_t)nth, -1);
+        pcr_parallel_ranges(n, nth, [&](int t, int64_t lo, int64_t hi) {
+            for (int64_t z = lo; z < hi; ++z)
+                if (users[z] < 0 || users[z] >= d1) { first[(size_t)t] = z; return; }
+        });
+        for (int64_t x : first) if (x >= 0) return bad("user " + std::to_string(users[x]) + " (entry " + std::to_string(x) + ") outside the model");
+    }
+    if (index) {
+        if (index[0] != 0) return bad("index[0] must be 0");
+        for (int64_t u = 0; u < d1; ++u) if (index[u + 1] < index[u]) return bad("index not monotone at user " + std::to_string(u));
+        std::vector<int> st((size_t)nth, 0);   // bit 0: an item outside [0, d2); bit 1: a row that is not item-ascending
+        pcr_parallel_ranges(d1, nth, [&](int t, int64_t lo, int64_t hi) {
+            for (int64_t u = lo; u < hi; ++u)
+                for (int64_t z = index[u]; z < index[u + 1]; ++z) {
+                    if (item[z] < 0 || item[z] >= d2) { st[(size_t)t] |= 1; return; }
+                    if (z > index[u] && item[z] < item[z - 1]) st[(size_t)t] |= 2;
+                }
+        });
+        int all = 0;
+        for (int x : st) all |= x;
+        if (all & 1) return bad("an item id of the exclusion CSR is outside [0, d2)");
+        if (sorted) *sorted = !(all & 2);
+    }
     return PCR_OK;
 }

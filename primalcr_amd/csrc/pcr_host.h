@@ -66,3 +66,10 @@ void pcr_set_error(const std::string& msg);
 // launch knobs set through pcr_tune() (include/primalcr.h): consulted by the solver when it is created
 bool pcr_tune_get(const char* key, std::string* out);
 int pcr_tune_int(const char* key, int dflt);
+
+// pcr_recommend_model's argument checks (the library and the sanitizer build's "no device" stub run the same ones): sizes, K,
+// user ids inside the model, the exclusion CSR's shape (index[0] = 0, monotone, items inside [0, d2)).  *sorted = every row of
+// `item` is non-decreasing (the kernel's exclusion cursor needs that; the caller sorts a copy otherwise).
+int pcr_recommend_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
+                              const int32_t* item, int64_t n, const int32_t* users, int topk, int dtype, const int32_t* items,
+                              const double* scores, bool* sorted);

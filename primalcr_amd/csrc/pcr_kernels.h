@@ -1,7 +1,8 @@
 // pcr_kernels.h -- hand-written HIP kernels for gfx950 (CDNA4, wave64) of the PrimalCR /
 // PrimalCR++ hot path.  Header-only templates, instantiated in pcr_solver.hip:
 //   pcr_prims.h (wave / team primitives, sorts, sweep coefficients, row primitives), pcr_vside.h (V step), pcr_ustep.h (U step),
-//   pcr_eval.h (evaluator, objective reductions, predict); pcr_gram.h (optional dual-form U step on MFMA).
+//   pcr_eval.h (evaluator, objective reductions, predict); pcr_gram.h (optional dual-form U step on MFMA); pcr_topk.h (top-K
+//   recommendation: MFMA scores with a fused streaming selection).
 //
 // Kernel map (reference site -> kernel); design and rooflines: DESIGN.md section 3:
 //   K1        comp_m_new, b = u.a in compute_Ha_new        -> k_sddmm     (rating-parallel)
@@ -12,6 +13,7 @@
 //   K8        update_u_new (pcrpp.cpp:779-815)             -> k_ustep     (per user, fused; K workgroups per long user)
 //   K10       compute_pairwise_error_ndcg (util.cpp:434)   -> k_eval2 (sorted) / k_eval (brute force)
 //             pmf-predict.cpp:56-64                        -> k_predict
+//             top-K unrated items per user (no reference)  -> k_rec_score + k_rec_merge
 //
 // Formulation (replaces the sequential two-pointer sweep with data-parallel primitives,
 // same result): a user's ratings are sorted by (level, m), so every rating level is one
@@ -29,3 +31,4 @@
 #include "pcr_vside.h"
 #include "pcr_ustep.h"
 #include "pcr_eval.h"
+#include "pcr_topk.h"

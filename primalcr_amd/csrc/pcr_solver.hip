@@ -82,6 +82,62 @@ struct DBuf {
     ~DBuf() { free(); }
 };
 
+// Top-K recommendation (pcr_topk.h) for the n users h_users[0..n) -- rows of U and of the exclusion CSR xptr / xitem (NULL:
+// none), or rows 0..n-1 when h_users is NULL -- into the host arrays items / scores (n x K).  Users go in batches whose
+// partial lists stay under REC_SCRATCH bytes; the item range is split across workgroups until the grid holds about
+// REC_TARGET_WG workgroups (ml1m's 6 040 users are 95 workgroups of 64).  scope(name) returns the profiler's RAII scope.
+// select = 0 only for tools/exp_recommend.py's GEMM-alone timing (lists come back empty).
+static const size_t REC_SCRATCH = (size_t)1 << 30;
+static const int REC_TARGET_WG = 1024, REC_MAX_SPLIT = 16, REC_MIN_SPLIT_ITEMS = 1024;
+template <typename T, class Scope>
+static int rec_run(hipStream_t st, const T* U, const T* V, int r, int ld, int64_t d2, const int64_t* xptr, const int32_t* xitem,
+                   int64_t n, const int32_t* h_users, int K, int32_t* items, double* scores, int select, Scope&& scope) {
+    if (n <= 0) return PCR_OK;
+    const size_t per_user = (size_t)K * (sizeof(T) + sizeof(int32_t)) + sizeof(int32_t);
+    const int64_t users_per_wg = (int64_t)rec::WAVES * rec::UW;
+    int64_t nb = std::min<int64_t>(n, std::max<int64_t>(users_per_wg, (int64_t)(REC_SCRATCH / (per_user * 2)) / users_per_wg * users_per_wg));
+    auto splits_for = [&](int64_t users) {
+        const int64_t wg = (users + users_per_wg - 1) / users_per_wg;
+        int64_t s = std::max<int64_t>(1, (REC_TARGET_WG + wg - 1) / wg);
+        s = std::min<int64_t>(s, std::max<int64_t>(1, d2 / REC_MIN_SPLIT_ITEMS));
+        return (int)std::min<int64_t>(s, REC_MAX_SPLIT);
+    };
+    while (nb > users_per_wg && (size_t)nb * (size_t)splits_for(nb) * per_user > REC_SCRATCH) nb = std::max<int64_t>(users_per_wg, nb / 2);
+    const int smax = splits_for(std::min(nb, n));
+    DBuf<T> ls; DBuf<int32_t> li, ln, du, oi; DBuf<double> os;
+    RC(ls.alloc((size_t)nb * smax * K)); RC(li.alloc((size_t)nb * smax * K)); RC(ln.alloc((size_t)nb * smax));
+    RC(du.alloc((size_t)nb)); RC(oi.alloc((size_t)nb * K)); RC(os.alloc((size_t)nb * K));
+    const size_t lds = rec_wave_lds<T>(K) * rec::WAVES;
+    HIPCHK(hipFuncSetAttribute((const void*)k_rec_score<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    std::vector<int32_t> seq;
+    for (int64_t b0 = 0; b0 < n; b0 += nb) {
+        const int64_t m = std::min(nb, n - b0);
+        const int32_t* hu = h_users ? h_users + b0 : nullptr;
+        if (!hu) { seq.resize((size_t)m); for (int64_t i = 0; i < m; ++i) seq[(size_t)i] = (int32_t)(b0 + i); hu = seq.data(); }
+        HIPCHK(hipMemcpyAsync(du.p, hu, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        const int ns = std::min(splits_for(m), smax);      // (a short last batch keeps the scratch of the first)
+        const int per = (int)(((d2 + ns - 1) / ns + rec::TILE - 1) / rec::TILE * rec::TILE);
+        const int nsp = (int)((d2 + per - 1) / per);
+        {
+            auto sc = scope("recommend/score");
+            (void)sc;
+            hipLaunchKernelGGL((k_rec_score<T>), dim3((unsigned)cdiv(m, users_per_wg), (unsigned)nsp), dim3(rec::WAVES * 64), lds, st, U, V, r, ld,
+                               (int)d2, du.p, m, xptr, xitem, K, per, ls.p, li.p, ln.p, select);
+            HIPCHK(hipGetLastError());
+        }
+        {
+            auto sc = scope("recommend/merge");
+            (void)sc;
+            hipLaunchKernelGGL((k_rec_merge<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), 0, st, ls.p, li.p, ln.p, nsp, m, K, oi.p, os.p);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(items + b0 * K, oi.p, (size_t)m * K * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(scores + b0 * K, os.p, (size_t)m * K * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return PCR_OK;
+}
+
 // users of one CSR grouped by length class; each class has its own workgroup size
 struct Bin {
     int block = 64;
@@ -149,13 +205,15 @@ struct pcr_solver {
     // CCDR1 only (pcr_ccd.h): the "ccd_residual_mismatch" counter, pcr_solver_set_ccd_params
     virtual int residual_mismatch(double*) { pcr_set_error("pcr_solver_counter: 'ccd_residual_mismatch' exists on a CCDR1 solver only"); return PCR_ERR_STATE; }
     virtual int set_ccd_params(const pcr_ccd_params*) { pcr_set_error("pcr_solver_set_ccd_params: not a CCDR1 solver (solver type 0)"); return PCR_ERR_STATE; }
+    // pcr_recommend: `local` = rows of this shard (checked by the caller)
+    virtual int recommend(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores) = 0;
 };
 
 // launch knobs: pcr_tune() values read once when the solver is created (include/primalcr.h lists them)
 struct Tune {
     int lanes = 0, spmm_chunk = 0, spmm_tiles = 0, sddmm_csc = -1, ustep_mode = 0, cluster_k = 4, cluster_users = 0, window_cache = 1,
         prepare_merged = -1, pipeline = 1, debug = 0, fault_cluster_member = 0, ustep_gram = -1, count_rows = 0, allreduce_chunks = 0,
-        resort_window = 8, p2p_ll = 16, p2p_timeout_ms = 20000, p2p_queue_budget = 0, fault_p2p_skip = 0, fault_p2p_coarse = 0, win16 = 1, ustep_win_lds = 1, plan_key64 = 0, ustep_newton = 0, vblock_users = 0;
+        resort_window = 8, p2p_ll = 16, p2p_timeout_ms = 20000, p2p_queue_budget = 0, fault_p2p_skip = 0, fault_p2p_coarse = 0, win16 = 1, ustep_win_lds = 1, plan_key64 = 0, ustep_newton = 0, vblock_users = 0, recommend_select = 1;
     std::string ubins;
     void read() {
         lanes = pcr_tune_int("lanes", 0); spmm_chunk = pcr_tune_int("spmm_chunk", 0); spmm_tiles = pcr_tune_int("spmm_tiles", 0);
@@ -169,6 +227,7 @@ struct Tune {
         p2p_timeout_ms = pcr_tune_int("p2p_timeout_ms", 20000); fault_p2p_skip = pcr_tune_int("fault_p2p_skip", 0);
         fault_p2p_coarse = pcr_tune_int("fault_p2p_coarse", 0); p2p_queue_budget = pcr_tune_int("p2p_queue_budget", 0);
         win16 = pcr_tune_int("win16", 1); ustep_win_lds = pcr_tune_int("ustep_win_lds", 1); plan_key64 = pcr_tune_int("plan_key64", 0); ustep_newton = pcr_tune_int("ustep_newton", 0); vblock_users = pcr_tune_int("vblock_users", 0);
+        recommend_select = pcr_tune_int("recommend_select", 1);
         ubins.clear(); pcr_tune_get("ubins", &ubins);
     }
 };
@@ -2290,6 +2349,18 @@ struct Solver final : pcr_solver {
         return n;
     }
     int sync() override { RC(sync_checked()); return PCR_OK; }
+
+    // top-K recommendation from the device factors (pcr_topk.h); reads U, V and the shard's CSR (item-ascending per user: the
+    // data set's CSR as uploaded, never permuted -- the (level, m) sorts write their own arrays), writes nothing of the solver
+    template <class Scope>
+    int recommend_with(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores, Scope&& scope) {
+        const bool ex = (flags & PCR_REC_EXCLUDE_TRAIN) != 0;
+        return rec_run<T>(st, d_U.p, d_V.p, geo.r, geo.ld, d2, ex ? d_uptr.p : nullptr, ex ? d_item.p : nullptr, n, local, K, items, scores,
+                          tune.recommend_select, scope);
+    }
+    int recommend(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores) override {
+        return recommend_with(n, local, K, flags, items, scores, [this](const char* name) { return ProfScope(this, name); });
+    }
 };
 
 #include "pcr_ccd.h"
@@ -2529,6 +2600,87 @@ int pcr_predict(const double* U, int64_t d1, const double* V, int64_t d2, int64_
         HIPCHK(hipMemcpy(pred, dP.p, n * sizeof(double), hipMemcpyDeviceToHost));
     }
     return PCR_OK;
+    });
+}
+
+int pcr_recommend_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                        int64_t n, const int32_t* users, int topk, int dtype, int32_t* items, double* scores, int device) {
+    return abi_guard("pcr_recommend_model", [&]() -> int {
+    bool sorted = true;
+    RC(pcr_recommend_model_check(U, d1, V, d2, k, index, item, n, users, topk, dtype, items, scores, &sorted));
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { pcr_set_error("no HIP device available"); return PCR_ERR_DEVICE; }
+    if (device < 0 || device >= ndev) { pcr_set_error("device ordinal out of range"); return PCR_ERR_ARG; }
+    HIPCHK(hipSetDevice(device));
+    if (n == 0) return PCR_OK;
+    // the exclusion rows must be item-ascending for the kernel's cursor: a CSR that is not gets a sorted copy
+    std::vector<int32_t> sitem;
+    const int64_t nnz = index ? index[d1] : 0;
+    if (index && !sorted) {
+        sitem.assign(item, item + nnz);
+        pcr_parallel_ranges(d1, pcr_host_threads(), [&](int, int64_t lo, int64_t hi) {
+            for (int64_t u = lo; u < hi; ++u) std::sort(sitem.begin() + index[u], sitem.begin() + index[u + 1]);
+        });
+    }
+    const int ld = ((int)k + 3) & ~3;
+    hipStream_t st = nullptr;
+    DBuf<int64_t> dx; DBuf<int32_t> di;
+    if (index) { RC(dx.upload_n(index, (size_t)d1 + 1)); RC(di.upload_n(sorted ? item : sitem.data(), (size_t)nnz)); }
+    auto up = [&](auto* D) -> int {     // both factors to the device in the requested type, rows padded to ld (slabs of 64 M values)
+        typedef std::remove_pointer_t<decltype(D)> T;
+        DBuf<double> stage;
+        const int64_t slab_rows = std::max<int64_t>(1, ((int64_t)64 << 20) / k);
+        RC(stage.alloc((size_t)std::min<int64_t>(std::max(d1, d2), slab_rows) * (size_t)k));
+        for (int w = 0; w < 2; ++w) {
+            const double* H = w == 0 ? U : V;
+            T* dst = D + (w == 0 ? 0 : (size_t)d1 * ld);
+            const int64_t rows = w == 0 ? d1 : d2;
+            for (int64_t r0 = 0; r0 < rows; r0 += slab_rows) {
+                const int64_t nr = std::min(slab_rows, rows - r0);
+                HIPCHK(hipMemcpyAsync(stage.p, H + r0 * k, (size_t)nr * k * sizeof(double), hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL((k_mat_in<T>), dim3((unsigned)std::min<int64_t>(1 << 16, cdiv(nr * ld, 256))), dim3(256), 0, st, stage.p, dst + r0 * ld, nr, (int)k, ld);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipStreamSynchronize(st));
+            }
+        }
+        return PCR_OK;
+    };
+    auto noscope = [](const char*) { return 0; };
+    const int select = pcr_tune_int("recommend_select", 1);
+    if (dtype == PCR_F64) {
+        DBuf<double> F;
+        RC(F.alloc((size_t)(d1 + d2) * ld));
+        RC(up(F.p));
+        return rec_run<double>(st, F.p, F.p + (size_t)d1 * ld, (int)k, ld, d2, dx.p, index ? di.p : nullptr, n, users, topk, items, scores, select, noscope);
+    }
+    DBuf<float> F;
+    RC(F.alloc((size_t)(d1 + d2) * ld));
+    RC(up(F.p));
+    return rec_run<float>(st, F.p, F.p + (size_t)d1 * ld, (int)k, ld, d2, dx.p, index ? di.p : nullptr, n, users, topk, items, scores, select, noscope);
+    });
+}
+
+int pcr_recommend(pcr_solver* s, int64_t n, const int32_t* users, int topk, int flags, int32_t* items, double* scores) {
+    S_OR_ARG;
+    if (topk < 1 || topk > PCR_RECOMMEND_MAX_K) { pcr_set_error("pcr_recommend: K = " + std::to_string(topk) + " outside [1, " + std::to_string(PCR_RECOMMEND_MAX_K) + "]"); return PCR_ERR_ARG; }
+    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_recommend: unknown flags"); return PCR_ERR_ARG; }
+    if (!users) n = s->n_users;
+    if (n < 0 || (n > 0 && (!items || !scores))) { pcr_set_error("pcr_recommend: bad argument"); return PCR_ERR_ARG; }
+    return abi_guard("pcr_recommend", [&]() -> int {
+        std::vector<int32_t> loc;
+        if (users) {
+            loc.resize((size_t)n);
+            for (int64_t i = 0; i < n; ++i) {
+                const int64_t x = (int64_t)users[i] - s->first_user;
+                if (x < 0 || x >= s->n_users) {
+                    pcr_set_error("pcr_recommend: user " + std::to_string(users[i]) + " is not in this shard [" + std::to_string(s->first_user) + ", " +
+                                  std::to_string(s->first_user + s->n_users) + ")");
+                    return PCR_ERR_ARG;
+                }
+                loc[(size_t)i] = (int32_t)x;
+            }
+        }
+        return s->recommend(n, users ? loc.data() : nullptr, topk, flags, items, scores);
     });
 }
 

@@ -1,0 +1,243 @@
+// pcr_topk.h -- top-K recommendation (pcr_recommend / pcr_recommend_model): for every requested user the K items of highest
+// score U[u] . V[j], without the items the user rated in training, in the order of include/primalcr.h (descending score, equal
+// scores by ascending item id).  DESIGN.md section 3.10 has the layout, the selection and the roofline.
+//
+// k_rec_score: a wave owns 16 users and sweeps the items [jb, je) of its split 64 at a time.  The scores of a step are four
+//   16 x 16 tiles on the matrix cores (v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64) with the items as the A operand's rows
+//   and the users as the B operand's columns, so every lane keeps ONE user (lane & 15) through the whole sweep: its threshold,
+//   its exclusion cursor and its list length live in registers.  Each lane group g = lane >> 4 loads 16 bytes of a row per
+//   k-step (k = c + KV g + e, e < KV) for both operands, so the k order of every score is fixed by the code alone.
+//   Selection: a score that beats the user's threshold -- the K-th entry of its list, or nothing while the list is short --
+//   goes into the user's candidate buffer in LDS (64 slots); when fewer than 16 slots are free the wave merges the buffer into
+//   the user's list (global scratch, staged through LDS) by rank counting and raises the threshold.  After the first few
+//   steps almost every score fails the threshold: one compare per score.
+//   Exclusion: training rows are item-ascending (duplicates allowed); each lane walks a cursor through its user's row and
+//   builds the 64-bit mask of the step's rated items -- O(nnz) in all.
+// k_rec_merge: one wave per user merges the partial lists of the item splits by rank counting (binary searches into the other
+//   lists), converts the scores to double and pads with (-1, -inf).
+// No atomic decides a result: the LDS slot counter only decides where a candidate sits in the buffer, and the merges rank by
+// the total order (score, id), so every list is the same whatever the order of arrival.
+#pragma once
+#include "pcr_prims.h"
+
+namespace rec {
+constexpr int WAVES = 4;      // waves per workgroup: the four sweep the same items, so three of them read V's rows from L1
+constexpr int UW = 16;        // users per wave (the columns of the MFMA tile)
+constexpr int NQ = 4;         // 16-item MFMA tiles per step
+constexpr int TILE = 16 * NQ; // items per step
+constexpr int CAP = 64;       // candidate slots per user; a merge is due when fewer than 16 are free
+}  // namespace rec
+
+template <typename T> struct RecMma;
+template <> struct RecMma<float> {
+    typedef float acc_t __attribute__((ext_vector_type(4)));
+    typedef float vec_t __attribute__((ext_vector_type(4)));
+    static constexpr int KV = 4;   // k values per 16-byte load
+    static __device__ __forceinline__ acc_t mma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+    // accumulator register j of lane l holds C[row][l & 15]
+    static __device__ __forceinline__ int crow(int j, int l) { return 4 * (l >> 4) + j; }
+};
+template <> struct RecMma<double> {
+    typedef double acc_t __attribute__((ext_vector_type(4)));
+    typedef double vec_t __attribute__((ext_vector_type(2)));
+    static constexpr int KV = 2;
+    static __device__ __forceinline__ acc_t mma(double a, double b, acc_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ int crow(int j, int l) { return (l >> 4) + 4 * j; }
+};
+
+// the order of a list: a before b
+template <typename T>
+__device__ __forceinline__ bool rec_better(T sa, int ia, T sb, int ib) { return sa > sb || (sa == sb && ia < ib); }
+
+// LDS of one wave of k_rec_score: candidate scores [UW * CAP], staged list scores [K], candidate ids, staged ids, fill counters
+template <typename T>
+__host__ __device__ inline size_t rec_wave_lds(int K) {
+    const size_t b = (size_t)(rec::UW * rec::CAP + K) * (sizeof(T) + sizeof(int)) + rec::UW * sizeof(int);
+    return (b + 15) & ~(size_t)15;
+}
+
+// partial lists: [split][n][K] scores and ids, [split][n] lengths
+template <typename T>
+__global__ __launch_bounds__(256) void k_rec_score(const T* __restrict__ U, const T* __restrict__ V, int r, int ld, int d2,
+                                                   const int32_t* __restrict__ users, int64_t n,
+                                                   const int64_t* __restrict__ xptr, const int32_t* __restrict__ xitem,
+                                                   int K, int per_split, T* __restrict__ lst_s, int32_t* __restrict__ lst_i,
+                                                   int32_t* __restrict__ lst_n, int select) {
+    typedef RecMma<T> M;
+    typedef typename M::acc_t acc_t;
+    typedef typename M::vec_t vec_t;
+    constexpr int KV = M::KV;
+    extern __shared__ __align__(16) char rec_lds[];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    char* wl = rec_lds + (size_t)w * rec_wave_lds<T>(K);
+    T* bs = (T*)wl;
+    T* ss = bs + rec::UW * rec::CAP;
+    int* bi = (int*)(ss + K);
+    int* si = bi + rec::UW * rec::CAP;
+    int* fill = si + K;
+
+    const int m = lane & 15, g = lane >> 4;
+    const int64_t idx = ((int64_t)blockIdx.x * rec::WAVES + w) * rec::UW + m;
+    const bool active = idx < n;
+    const int u = active ? users[idx] : 0;
+    const int jb = (int)blockIdx.y * per_split;
+    const int je = min(d2, jb + per_split);
+    const size_t lofs = active ? ((size_t)blockIdx.y * (size_t)n + (size_t)idx) * (size_t)K : 0;
+    int64_t cur = 0, cend = 0;
+    if (xptr && active) {
+        cur = xptr[u]; cend = xptr[u + 1];
+        int64_t hi = cend;
+        while (cur < hi) { const int64_t mid = (cur + hi) >> 1; if (xitem[mid] < jb) cur = mid + 1; else hi = mid; }
+    }
+    if (lane < rec::UW) fill[lane] = 0;
+    int len = 0;
+    T ts = -INFINITY;
+    int ti = INT_MAX;
+    wave_sync();
+
+    // merge user column mm's candidate buffer into its list; every lane of the wave takes part
+    auto merge = [&](int mm) {
+        const int B = fill[mm];
+        const int L = __shfl(len, mm);
+        const size_t lo = (size_t)__shfl((long long)lofs, mm);
+        T* gs = lst_s + lo;
+        int32_t* gi = lst_i + lo;
+        const T* cs = bs + mm * rec::CAP;
+        const int* ci = bi + mm * rec::CAP;
+        for (int p = lane; p < L; p += 64) { ss[p] = gs[p]; si[p] = gi[p]; }
+        wave_sync();
+        bool has = false;
+        T hs = -INFINITY;
+        int hi_ = INT_MAX;
+        if (lane < B) {
+            const T s = cs[lane];
+            const int j = ci[lane];
+            int rk = 0;
+            for (int e = 0; e < B; ++e) rk += rec_better(cs[e], ci[e], s, j) ? 1 : 0;
+            int a = 0, b = L;
+            while (a < b) { const int mid = (a + b) >> 1; if (rec_better(ss[mid], si[mid], s, j)) a = mid + 1; else b = mid; }
+            rk += a;
+            if (rk < K) { gs[rk] = s; gi[rk] = j; }
+            if (rk == K - 1) { has = true; hs = s; hi_ = j; }
+        }
+        for (int p = lane; p < L; p += 64) {
+            const T s = ss[p];
+            const int j = si[p];
+            int rk = p;
+            for (int e = 0; e < B; ++e) rk += rec_better(cs[e], ci[e], s, j) ? 1 : 0;
+            if (rk < K) { gs[rk] = s; gi[rk] = j; }
+            if (rk == K - 1) { has = true; hs = s; hi_ = j; }
+        }
+        const int nl = min(K, L + B);
+        const unsigned long long hb = __ballot(has);
+        if (hb) {
+            const int src = __ffsll((long long)hb) - 1;
+            hs = __shfl(hs, src);
+            hi_ = __shfl(hi_, src);
+        }
+        if (m == mm) {
+            len = nl;
+            if (nl == K) { ts = hs; ti = hi_; }
+        }
+        __threadfence_block();             // the next merge of this user reads the list back
+        wave_sync();
+        if (lane == 0) fill[mm] = 0;
+        wave_sync();
+    };
+
+    const T* Ur = U + (size_t)(unsigned)u * (unsigned)ld;
+    for (int j0 = jb; j0 < je; j0 += rec::TILE) {
+        acc_t acc[rec::NQ];
+#pragma unroll
+        for (int q = 0; q < rec::NQ; ++q) acc[q] = acc_t{};
+        for (int c = 0; c < ld; c += 4 * KV) {          // wave-uniform trip count: the MFMAs run with every lane
+            const int c0 = c + g * KV;
+            vec_t b = vec_t{};
+            if (active && c0 < ld) b = *(const vec_t*)(Ur + c0);
+#pragma unroll
+            for (int e = 0; e < KV; ++e) if (c0 + e >= r) b[e] = (T)0;
+#pragma unroll
+            for (int q = 0; q < rec::NQ; ++q) {
+                const int jr = j0 + 16 * q + m;
+                vec_t a = vec_t{};
+                if (jr < je && c0 < ld) a = *(const vec_t*)(V + (size_t)(unsigned)jr * (unsigned)ld + c0);
+#pragma unroll
+                for (int e = 0; e < KV; ++e) if (c0 + e >= r) a[e] = (T)0;
+#pragma unroll
+                for (int e = 0; e < KV; ++e) acc[q] = M::mma(a[e], b[e], acc[q]);
+            }
+        }
+        if (!select) {                                 // (tools/exp_recommend.py: the GEMM alone; the NaN test keeps it alive)
+            T t = (T)0;
+#pragma unroll
+            for (int q = 0; q < rec::NQ; ++q) t += acc[q][0] + acc[q][1] + acc[q][2] + acc[q][3];
+            if (t != t && active && g == 0) lst_n[(size_t)blockIdx.y * (size_t)n + (size_t)idx] = -1;
+            continue;
+        }
+        unsigned long long xm = 0;                     // this step's rated items of the lane's user
+        while (cur < cend) {
+            const int it = xitem[cur];
+            if (it >= j0 + rec::TILE) break;
+            xm |= 1ull << (it - j0);
+            ++cur;
+        }
+#pragma unroll
+        for (int q = 0; q < rec::NQ; ++q) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int jl = 16 * q + M::crow(j, lane);
+                const int item = j0 + jl;
+                const T s = acc[q][j];
+                if (active && item < je && !((xm >> jl) & 1ull) && rec_better(s, item, ts, ti)) {
+                    const int p = atomicAdd(&fill[m], 1);
+                    bs[m * rec::CAP + p] = s;
+                    bi[m * rec::CAP + p] = item;
+                }
+            }
+            wave_sync();
+            unsigned long long due = __ballot(lane < rec::UW && fill[lane] > rec::CAP - 16);
+            while (due) {
+                const int mm = __ffsll((long long)due) - 1;
+                due &= due - 1;
+                merge(mm);
+            }
+        }
+    }
+    unsigned long long due = __ballot(lane < rec::UW && fill[lane] > 0);
+    while (due) {
+        const int mm = __ffsll((long long)due) - 1;
+        due &= due - 1;
+        merge(mm);
+    }
+    if (active && g == 0) lst_n[(size_t)blockIdx.y * (size_t)n + (size_t)idx] = len;
+}
+
+// one wave per user: the nsplit partial lists -> items[idx * K ...], scores (double), padded with (-1, -inf)
+template <typename T>
+__global__ __launch_bounds__(256) void k_rec_merge(const T* __restrict__ lst_s, const int32_t* __restrict__ lst_i,
+                                                   const int32_t* __restrict__ lst_n, int nsplit, int64_t n, int K,
+                                                   int32_t* __restrict__ out_i, double* __restrict__ out_s) {
+    const int lane = threadIdx.x & 63;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (idx >= n) return;
+    int tot = 0;
+    for (int sp = 0; sp < nsplit; ++sp) {
+        const size_t o = ((size_t)sp * (size_t)n + (size_t)idx) * (size_t)K;
+        const int L = lst_n[(size_t)sp * (size_t)n + (size_t)idx];
+        tot += L;
+        for (int p = lane; p < L; p += 64) {
+            const T s = lst_s[o + p];
+            const int j = lst_i[o + p];
+            int rk = p;
+            for (int sq = 0; sq < nsplit; ++sq) {
+                if (sq == sp) continue;
+                const size_t o2 = ((size_t)sq * (size_t)n + (size_t)idx) * (size_t)K;
+                int a = 0, b = lst_n[(size_t)sq * (size_t)n + (size_t)idx];
+                while (a < b) { const int mid = (a + b) >> 1; if (rec_better(lst_s[o2 + mid], lst_i[o2 + mid], s, j)) a = mid + 1; else b = mid; }
+                rk += a;
+            }
+            if (rk < K) { out_i[(size_t)idx * K + rk] = j; out_s[(size_t)idx * K + rk] = (double)s; }
+        }
+    }
+    for (int p = min(tot, K) + lane; p < K; p += 64) { out_i[(size_t)idx * K + p] = -1; out_s[(size_t)idx * K + p] = -INFINITY; }
+}

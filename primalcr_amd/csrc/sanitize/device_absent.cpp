@@ -64,4 +64,10 @@ int pcr_predict(const double* U, int64_t, const double* V, int64_t, int64_t k, i
     if (!U || !V || k < 1 || n < 0 || (n > 0 && (!user || !item || !pred))) { pcr_set_error("pcr_predict: bad argument"); return PCR_ERR_ARG; }
     return absent();
 }
+int pcr_recommend_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                        int64_t n, const int32_t* users, int topk, int dtype, int32_t* items, double* scores, int) {
+    const int rc = pcr_recommend_model_check(U, d1, V, d2, k, index, item, n, users, topk, dtype, items, scores, nullptr);
+    return rc != PCR_OK ? rc : absent();
+}
+NO_SOLVER(pcr_recommend, pcr_solver*, int64_t, const int32_t*, int, int, int32_t*, double*)
 }
