@@ -401,6 +401,55 @@ int pcr_recommend_model(const double *U, int64_t d1, const double *V, int64_t d2
 int pcr_recommend(pcr_solver *s, int64_t n, const int32_t *users, int topk, int flags,
                   int32_t *items, double *scores);                         /* [device] */
 
+/* ------------------------------------------------------------------------- */
+/* full-catalogue top-N evaluation (no reference counterpart: util.cpp's       */
+/* evaluator ranks a user's own test items among themselves)                  */
+/* ------------------------------------------------------------------------- */
+/* Every user with held-out ratings is scored against the whole catalogue, its top K = cutoffs[ncut - 1] list is selected and
+ * the ranking metrics are reduced at each cutoff -- on the device; no list leaves it.  For a user u and a cutoff c:
+ *   Relevant set R_u   the DISTINCT items j with a test rating (u, j, v), v >= threshold; an item that occurs several times in
+ *                      u's test row counts once, with its largest rating.  threshold = -INFINITY: every test item; NaN is
+ *                      PCR_ERR_ARG.  Exclusion does not change R_u: a test item that also sits in u's training row stays in
+ *                      R_u with exclusion on, although it can never be listed.
+ *   Graded gain        g(j) = pow(2.0, v_max) - 1.0 (the existing evaluator's gain).
+ *   List L_u           exactly the list pcr_recommend / pcr_recommend_model returns with the same factors, dtype, K and
+ *                      exclusion; padding (-1) is never relevant.
+ *   Discount           d(i) = 1.0 / log2((double)(i + 2)) at position i = 0, 1, ...
+ *   Counted users      |R_u| >= 1; the others are not scored at all.
+ *   Per user           hits = |L_u[0..c) & R_u|, precision = hits / c, recall = hits / |R_u|,
+ *                      ap = (sum over i < c, L_u[i] in R_u, of hits_{<=i} / (i + 1)) / min(c, |R_u|),
+ *                      ndcg = sum_{i < c, L_u[i] in R_u} d(i) / sum_{i < min(c, |R_u|)} d(i),
+ *                      ndcg_graded = sum_{i < c, L_u[i] in R_u} g(L_u[i]) d(i) / sum_{i < min(c, |R_u|)} g_desc[i] d(i)
+ *                      (g_desc: R_u's gains in descending order), defined only when that ideal DCG is > 0.
+ *   Summary per cutoff means over counted users (users), hit_rate = share of them with hits > 0, hits summed; ndcg_graded is
+ *                      averaged over its own count (users_graded).  A denominator of 0 gives a mean of 0.
+ *   Determinism        per-user values depend on (u, its list, its test row) alone; sums run in a fixed order over users in
+ *                      ascending id; two identical calls are bitwise identical.
+ * cutoffs[ncut]: 1 <= ncut <= PCR_TOPN_MAX_CUTOFFS, strictly ascending, each in [1, PCR_RECOMMEND_MAX_K].
+ * per_user (optional, NULL: not written): [rows][ncut][6] = hits, precision, recall, ap, ndcg, ndcg_graded; uncounted users
+ * (all six) and an undefined ndcg_graded are NaN. */
+#define PCR_TOPN_MAX_CUTOFFS 8
+typedef struct pcr_topn_stats {
+    int     cutoff;
+    int64_t users, users_graded, hits;
+    double  precision, recall, hit_rate, map, ndcg, ndcg_graded;
+} pcr_topn_stats;
+/* Standalone: the factors, dtype and exclusion CSR as pcr_recommend_model; tindex[d1 + 1] / titem / tval the test CSR (0-based,
+ * tindex[0] = 0, monotone, items in any order within a row).  rows = d1.  Arguments are checked on the host before any device
+ * is looked for. */
+int pcr_evaluate_topn_model(const double *U, int64_t d1, const double *V, int64_t d2, int64_t k,
+                            const int64_t *index, const int32_t *item,
+                            const int64_t *tindex, const int32_t *titem, const double *tval,
+                            int ncut, const int *cutoffs, double threshold, int dtype,
+                            pcr_topn_stats *stats, double *per_user, int device);     /* [device] */
+/* On a live PCR, PCR++ or CCDR1 solver: its device factors and storage type, the test ratings it was created with, flags
+ * PCR_REC_EXCLUDE_TRAIN as pcr_recommend; training state is not touched.  rows = the shard's n_users (per_user row i = user
+ * first_user + i).  N ranks: stats are the totals over the communicator's ranks (every rank must call); local-only shards
+ * (no communicator) return their own partials.  The relevance tables are built once per (threshold, cutoffs) and kept.
+ * Profile slots: recommend/score, and recommend/metrics (the merge with the metrics fused in, and the reduction). */
+int pcr_evaluate_topn(pcr_solver *s, int ncut, const int *cutoffs, double threshold, int flags,
+                      pcr_topn_stats *stats, double *per_user);                        /* [device] */
+
 /* per-kernel device timing (HIP events on the solver's stream, one pair per launch).
  * slot names: "<class>/<workgroup size>[.<length bound>][g][c][l][r][#n]" for the per-user kernels (classes
  * prepare, vgrad, vhv, ustep; g = global-scratch variant, c = workgroup clusters, l = k_ustep's latency form (8 rows

@@ -10,6 +10,8 @@ PCR_SOLVER_CCDR1, PCR_SOLVER_PCR, PCR_SOLVER_PCRPP = 0, 1, 2
 PCR_F32, PCR_F64 = 0, 1
 PCR_RECOMMEND_MAX_K = 1024
 PCR_REC_EXCLUDE_TRAIN = 1
+PCR_TOPN_MAX_CUTOFFS = 8
+TOPN_FIELDS = ("hits", "precision", "recall", "ap", "ndcg", "ndcg_graded")   # per_user columns
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -67,6 +69,11 @@ class IterStats(C.Structure):
     _fields_ = [("obj", C.c_double), ("train_err", C.c_double), ("train_ndcg", C.c_double), ("test_err", C.c_double),
                 ("test_ndcg", C.c_double), ("seconds", C.c_double), ("cg_v", C.c_int64), ("ls_v", C.c_int64),
                 ("cg_u", C.c_int64), ("ls_u", C.c_int64)]
+
+
+class TopnStats(C.Structure):
+    _fields_ = [("cutoff", C.c_int), ("users", C.c_int64), ("users_graded", C.c_int64), ("hits", C.c_int64), ("precision", C.c_double),
+                ("recall", C.c_double), ("hit_rate", C.c_double), ("map", C.c_double), ("ndcg", C.c_double), ("ndcg_graded", C.c_double)]
 
 
 _LOG_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p)
@@ -141,6 +148,8 @@ def lib():
     L.pcr_predict.argtypes = [_dp, i64, _dp, i64, i64, i64, _ip, _ip, _dp, ci]
     L.pcr_recommend_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, vp, ci, ci, vp, vp, ci]
     L.pcr_recommend.argtypes = [vp, i64, vp, ci, ci, vp, vp]
+    L.pcr_evaluate_topn_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, ci, vp, cd, ci, vp, vp, ci]
+    L.pcr_evaluate_topn.argtypes = [vp, ci, vp, cd, ci, vp, vp]
     L.pcr_profile_enable.argtypes = [vp, ci]
     L.pcr_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(cd), C.POINTER(i64)]
     L.pcr_profile_scope.argtypes = [vp, C.c_char_p, C.POINTER(i64), C.POINTER(i64)]
@@ -252,6 +261,46 @@ def recommend(U, V, topk, exclude=None, users=None, dtype=PCR_F64, device=0):
                                    None if it is None else it.ctypes.data, n, None if users is None else users.ctypes.data, int(topk),
                                    int(dtype), items.ctypes.data, scores.ctypes.data, device))
     return items, scores
+
+
+def _topn_call(cutoffs, per_user, rows, fn):
+    """Shared by evaluate_topn() and Solver.evaluate_topn(): fn(ncut, cutoffs_ptr, stats_ptr, per_user_ptr) -> status."""
+    cuts = np.ascontiguousarray(np.atleast_1d(np.asarray(cutoffs)), np.int32)
+    ncut = int(cuts.shape[0])
+    stats = (TopnStats * max(ncut, 1))()
+    pu = np.empty((rows, max(ncut, 1), len(TOPN_FIELDS)), np.float64) if per_user else None
+    _chk(fn(ncut, cuts.ctypes.data, C.cast(stats, C.c_void_p), None if pu is None else pu.ctypes.data))
+    out = [{f: getattr(stats[c], f) for f, _ in TopnStats._fields_} for c in range(ncut)]
+    return (out, pu) if per_user else out
+
+
+def evaluate_topn(U, V, test, cutoffs=(10,), exclude=None, threshold=-np.inf, dtype=PCR_F64, device=0, per_user=False):
+    """Full-catalogue top-N evaluation on the GPU (pcr_evaluate_topn_model): every user with a relevant test rating (value >=
+    threshold) gets its top max(cutoffs) list, as recommend() returns it, scored against its test items.  test / exclude: a
+    Dataset (its test / training CSR) or an (index, item, val) / (index, item) tuple; exclude None: no exclusion.  Returns one
+    dict per cutoff (cutoff, users, users_graded, hits, precision, recall, hit_rate, map, ndcg, ndcg_graded) and, with
+    per_user, also the array [d1, ncut, 6] of TOPN_FIELDS (NaN for users not counted and for an undefined ndcg_graded)."""
+    U = np.ascontiguousarray(U, np.float64); V = np.ascontiguousarray(V, np.float64)
+    d1, k = U.shape
+    if isinstance(test, Dataset):
+        tidx, tit, tval = test.csr(1)
+    else:
+        tidx, tit, tval = test
+    tidx = np.ascontiguousarray(tidx, np.int64); tit = np.ascontiguousarray(tit, np.int32); tval = np.ascontiguousarray(tval, np.float64)
+    if tidx.shape[0] != d1 + 1 or tidx[-1] != tit.shape[0] or tit.shape[0] != tval.shape[0]:
+        raise ValueError(f"test: index must have d1 + 1 = {d1 + 1} entries, the last equal to len(item) = len(val)")
+    idx = it = None
+    if exclude is not None:
+        if isinstance(exclude, Dataset):
+            idx, it, _ = exclude.csr(0)
+        else:
+            idx, it = exclude[:2]
+        idx = np.ascontiguousarray(idx, np.int64); it = np.ascontiguousarray(it, np.int32)
+        if idx.shape[0] != d1 + 1 or idx[-1] != it.shape[0]:
+            raise ValueError(f"exclude: index must have d1 + 1 = {d1 + 1} entries, the last equal to len(item) = {it.shape[0]}")
+    return _topn_call(cutoffs, per_user, d1, lambda nc, cp, sp, pp: lib().pcr_evaluate_topn_model(
+        U.ctypes.data, d1, V.ctypes.data, V.shape[0], k, None if idx is None else idx.ctypes.data, None if it is None else it.ctypes.data,
+        tidx.ctypes.data, tit.ctypes.data, tval.ctypes.data, nc, cp, float(threshold), int(dtype), sp, pp, device))
 
 
 def comm_unique_id() -> bytes:
@@ -533,6 +582,13 @@ class Solver:
         _chk(lib().pcr_recommend(self._h, n, None if users is None else users.ctypes.data, int(topk),
                                  PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, items.ctypes.data, scores.ctypes.data))
         return items, scores
+
+    def evaluate_topn(self, cutoffs=(10,), threshold=-np.inf, exclude_train=True, per_user=False):
+        """Full-catalogue top-N evaluation of this shard's users against the solver's test ratings (pcr_evaluate_topn); the
+        result as evaluate_topn(), per_user rows for the shard's users.  N ranks with a communicator: the totals of all ranks
+        (every rank must call); local-only shards: their own partials."""
+        return _topn_call(cutoffs, per_user, self.n_users, lambda nc, cp, sp, pp: lib().pcr_evaluate_topn(
+            self._h, nc, cp, float(threshold), PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, sp, pp))
 
     def sync(self):
         _chk(lib().pcr_solver_sync(self._h))

@@ -1,16 +1,25 @@
-// omp-pmf-recommend -- top-K unrated items per user from a model file (pcr_recommend_model, include/primalcr.h).  The reference
-// has no counterpart: pmf-predict.cpp scores the pairs of a test file only.
+// omp-pmf-recommend -- top-K unrated items per user from a model file (pcr_recommend_model, include/primalcr.h), or, with
+// --eval, the full-catalogue top-N evaluation of those lists against a data directory's test ratings (pcr_evaluate_topn_model).
+// The reference has no counterpart: pmf-predict.cpp scores the pairs of a test file only.
 //   omp-pmf-recommend [-K topk] [-x data_dir] [-u users_file] [--f32] [--scores] model_file output_file
-//     -K topk       items per user (default 10, at most PCR_RECOMMEND_MAX_K)
-//     -x data_dir   leave out the training ratings of a data directory (its meta file; d1 / d2 must match the model)
-//     -u users_file one 1-based user id per line (default: every user of the model)
-//     --f32         score with f32 factors (default: fp64, as the model file holds them)
-//     --scores      write every item as item:score (score in "%lf", as omp-pmf-predict prints it)
+//   omp-pmf-recommend --eval data_dir [-c c1,c2,...] [--threshold v] [-K topk] [-x data_dir] [--f32] model_file [output_file]
+//     -K topk        items per user (default 10, at most PCR_RECOMMEND_MAX_K)
+//     -x data_dir    leave out the training ratings of a data directory (its meta file; d1 / d2 must match the model)
+//     -u users_file  one 1-based user id per line (default: every user of the model)
+//     --f32          score with f32 factors (default: fp64, as the model file holds them)
+//     --scores       write every item as item:score (score in "%lf", as omp-pmf-predict prints it)
+//     --eval dir     evaluate against the test file of a data directory (its meta file; d1 / d2 must match the model)
+//     -c cutoffs     comma-separated ascending cutoffs, at most PCR_TOPN_MAX_CUTOFFS (default: -K)
+//     --threshold v  a test rating is relevant when >= v (default: every test rating)
 // Output: one line per user, in input order: the 1-based user id, then the 1-based item ids (padding is left out).  Users go
 // to the device in batches, so host memory for the lists stays bounded on any catalogue.
+// With --eval: stdout gets one line per cutoff, "cutoff c users n users_graded n hits n precision x recall x hit_rate x map x
+// ndcg x ndcg_graded x" (values in %g); the output file, if given, one line per counted user at the largest cutoff: the 1-based
+// user id, then hits precision recall ap ndcg ndcg_graded (%g; nan where ndcg_graded is undefined).
 #include <algorithm>
 #include <cerrno>
 #include <charconv>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,11 +32,16 @@
 
 static const char* USAGE =
     "Usage: omp-pmf-recommend [-K topk] [-x data_dir] [-u users_file] [--f32] [--scores] model_file output_file\n"
-    "    -K topk       items per user (default 10, 1 .. 1024)\n"
-    "    -x data_dir   leave out the training ratings of this data directory (meta file)\n"
-    "    -u users_file one 1-based user id per line (default: every user)\n"
-    "    --f32         score in f32 (default fp64)\n"
-    "    --scores      write item:score instead of item\n";
+    "       omp-pmf-recommend --eval data_dir [-c c1,c2,...] [--threshold v] [-K topk] [-x data_dir] [--f32] model_file [output_file]\n"
+    "    -K topk        items per user (default 10, 1 .. 1024)\n"
+    "    -x data_dir    leave out the training ratings of this data directory (meta file)\n"
+    "    -u users_file  one 1-based user id per line (default: every user)\n"
+    "    --f32          score in f32 (default fp64)\n"
+    "    --scores       write item:score instead of item\n"
+    "    --eval dir     top-N metrics against the test ratings of this data directory (meta file)\n"
+    "    -c cutoffs     comma-separated ascending cutoffs, at most 8, each 1 .. 1024 (default: -K)\n"
+    "    --threshold v  a test rating is relevant when >= v (default: every test rating)\n"
+    "    output_file    with --eval optional: per counted user at the largest cutoff, hits precision recall ap ndcg ndcg_graded\n";
 
 static int usage() { printf("%s", USAGE); return 1; }
 
@@ -55,14 +69,104 @@ static bool read_users(const char* path, int64_t d1, std::vector<int32_t>& out) 
     return ok;
 }
 
+// "5,10,20": 1 .. PCR_TOPN_MAX_CUTOFFS integers in [1, PCR_RECOMMEND_MAX_K], strictly ascending
+static bool parse_cutoffs(const char* v, std::vector<int>& out) {
+    const char* p = v;
+    while (true) {
+        char* end = nullptr;
+        errno = 0;
+        const long x = strtol(p, &end, 10);
+        if (end == p || errno || x < 1 || x > PCR_RECOMMEND_MAX_K || (*end != ',' && *end != 0)) return false;
+        if (!out.empty() && x <= out.back()) return false;
+        out.push_back((int)x);
+        if ((int)out.size() > PCR_TOPN_MAX_CUTOFFS) return false;
+        if (*end == 0) return true;
+        p = end + 1;
+    }
+}
+
+// a data directory whose dims must match the model: its CSR `which` (0 training, 1 test); val may be NULL
+static bool load_csr(const char* dir, int which, int64_t d1, int64_t d2, std::vector<int64_t>& index, std::vector<int32_t>& item,
+                     std::vector<double>* val) {
+    pcr_dataset* ds = nullptr;
+    if (pcr_dataset_load_mt(dir, 0, &ds) != PCR_OK) { fprintf(stderr, "%s\n", pcr_last_error()); return false; }
+    int64_t xd1, xd2, nnz, tnnz;
+    pcr_dataset_dims(ds, &xd1, &xd2, &nnz, &tnnz);
+    if (xd1 != d1 || xd2 != d2) {
+        fprintf(stderr, "data set %s is %lld x %lld, the model %lld x %lld\n", dir, (long long)xd1, (long long)xd2, (long long)d1, (long long)d2);
+        pcr_dataset_free(ds);
+        return false;
+    }
+    const int64_t z = which == 0 ? nnz : tnnz;
+    index.resize((size_t)d1 + 1);
+    std::vector<int64_t> it64((size_t)z);
+    if (val) val->resize((size_t)z);
+    pcr_dataset_csr(ds, which, index.data(), it64.data(), val ? val->data() : nullptr);
+    pcr_dataset_free(ds);
+    item.assign(it64.begin(), it64.end());
+    return true;
+}
+
+// --eval: the metrics per cutoff to stdout, the per-user rows at the largest cutoff to out_path (if given)
+static int run_eval(const char* edir, const std::vector<double>& U, const std::vector<double>& V, int64_t d1, int64_t d2, int64_t k,
+                    const std::vector<int64_t>* xindex, const std::vector<int32_t>* xitem, const std::vector<int>& cuts, double threshold,
+                    bool f32, const char* out_path) {
+    std::vector<int64_t> tindex;
+    std::vector<int32_t> titem;
+    std::vector<double> tval;
+    if (!load_csr(edir, 1, d1, d2, tindex, titem, &tval)) return 1;
+    const int nc = (int)cuts.size();
+    std::vector<pcr_topn_stats> st((size_t)nc);
+    std::vector<double> per;
+    if (out_path) per.resize((size_t)d1 * nc * 6);
+    if (pcr_evaluate_topn_model(U.data(), d1, V.data(), d2, k, xindex ? xindex->data() : nullptr, xitem ? xitem->data() : nullptr, tindex.data(),
+                                titem.data(), tval.data(), nc, cuts.data(), threshold, f32 ? PCR_F32 : PCR_F64, st.data(),
+                                out_path ? per.data() : nullptr, 0) != PCR_OK) {
+        fprintf(stderr, "evaluate: %s\n", pcr_last_error());
+        return 1;
+    }
+    for (const pcr_topn_stats& s : st)
+        printf("cutoff %d users %lld users_graded %lld hits %lld precision %g recall %g hit_rate %g map %g ndcg %g ndcg_graded %g\n", s.cutoff,
+               (long long)s.users, (long long)s.users_graded, (long long)s.hits, s.precision, s.recall, s.hit_rate, s.map, s.ndcg, s.ndcg_graded);
+    if (!out_path) return 0;
+    FILE* fp = fopen(out_path, "wb");
+    if (!fp) { fprintf(stderr, "can't open output file %s\n", out_path); return 1; }
+    bool ok = true;
+    for (int64_t u = 0; u < d1 && ok; ++u) {
+        const double* r = per.data() + ((size_t)u * nc + (nc - 1)) * 6;
+        if (r[0] != r[0]) continue;                                   // not counted
+        ok = fprintf(fp, "%lld %g %g %g %g %g %g\n", (long long)u + 1, r[0], r[1], r[2], r[3], r[4], r[5]) > 0;
+    }
+    ok = (fclose(fp) == 0) && ok;
+    if (!ok) { fprintf(stderr, "short write to %s\n", out_path); return 1; }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     int K = 10;
     bool f32 = false, with_scores = false;
-    const char *xdir = nullptr, *ufile = nullptr;
+    const char *xdir = nullptr, *ufile = nullptr, *edir = nullptr;
+    std::vector<int> cuts;
+    double threshold = -INFINITY;
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
-        if (!strcmp(a, "-K") || !strcmp(a, "-x") || !strcmp(a, "-u")) {
+        if (!strcmp(a, "--eval") || !strcmp(a, "-c") || !strcmp(a, "--threshold")) {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
+            const char* v = argv[++i];
+            if (a[1] == 'c') {
+                cuts.clear();
+                if (!parse_cutoffs(v, cuts)) {
+                    fprintf(stderr, "-c %s: must be 1 .. %d strictly ascending integers in 1 .. %d, separated by commas\n", v, PCR_TOPN_MAX_CUTOFFS, PCR_RECOMMEND_MAX_K);
+                    return 1;
+                }
+            } else if (a[2] == 'e') edir = v;
+            else {
+                char* end = nullptr;
+                threshold = strtod(v, &end);
+                if (!*v || *end || threshold != threshold) { fprintf(stderr, "--threshold %s: must be a number\n", v); return 1; }
+            }
+        } else if (!strcmp(a, "-K") || !strcmp(a, "-x") || !strcmp(a, "-u")) {
             if (i + 1 >= argc) return usage();
             const char* v = argv[++i];
             if (a[1] == 'K') {
@@ -77,7 +181,9 @@ int main(int argc, char** argv) {
         else if (a[0] == '-' && a[1]) { fprintf(stderr, "unknown option %s\n", a); return usage(); }
         else pos.push_back(a);
     }
-    if (pos.size() != 2) return usage();
+    if (edir ? (pos.empty() || pos.size() > 2) : pos.size() != 2) return usage();
+    if (!edir && (!cuts.empty() || threshold != -INFINITY)) { fprintf(stderr, "-c and --threshold go with --eval\n"); return 1; }
+    if (edir && (ufile || with_scores)) { fprintf(stderr, "-u and --scores do not go with --eval\n"); return 1; }
     int64_t d1, d2, k;
     if (pcr_model_load(pos[0], &d1, &d2, &k, nullptr, nullptr) != PCR_OK) { fprintf(stderr, "can't open model file %s\n", pos[0]); return 1; }
     std::vector<double> U((size_t)d1 * k), V((size_t)d2 * k);
@@ -87,21 +193,14 @@ int main(int argc, char** argv) {
     else { users.resize((size_t)d1); for (int64_t u = 0; u < d1; ++u) users[(size_t)u] = (int32_t)u; }
     std::vector<int64_t> xindex;
     std::vector<int32_t> xitem;
-    if (xdir) {
-        pcr_dataset* ds = nullptr;
-        if (pcr_dataset_load_mt(xdir, 0, &ds) != PCR_OK) { fprintf(stderr, "%s\n", pcr_last_error()); return 1; }
-        int64_t xd1, xd2, nnz, tnnz;
-        pcr_dataset_dims(ds, &xd1, &xd2, &nnz, &tnnz);
-        if (xd1 != d1 || xd2 != d2) {
-            fprintf(stderr, "data set %s is %lld x %lld, the model %lld x %lld\n", xdir, (long long)xd1, (long long)xd2, (long long)d1, (long long)d2);
-            pcr_dataset_free(ds);
-            return 1;
-        }
-        xindex.resize((size_t)d1 + 1);
-        std::vector<int64_t> it64((size_t)nnz);
-        pcr_dataset_csr(ds, 0, xindex.data(), it64.data(), nullptr);
-        pcr_dataset_free(ds);
-        xitem.assign(it64.begin(), it64.end());
+    if (xdir && !load_csr(xdir, 0, d1, d2, xindex, xitem, nullptr)) return 1;
+    if (edir) {
+        if (cuts.empty()) cuts.push_back(K);
+        const int rc = run_eval(edir, U, V, d1, d2, k, xdir ? &xindex : nullptr, xdir ? &xitem : nullptr, cuts, threshold, f32,
+                                pos.size() == 2 ? pos[1] : nullptr);
+        if (rc) return rc;
+        fflush(stdout); fflush(stderr);
+        _exit(0);
     }
     FILE* out_fp = fopen(pos[1], "wb");
     if (!out_fp) { fprintf(stderr, "can't open output file %s\n", pos[1]); return 1; }

@@ -620,6 +620,9 @@ struct CcdSolver final : pcr_solver {
     int recommend(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores) override {
         return base->recommend_with(n, local, K, flags, items, scores, [this](const char* name) { return Prof(this, name); });
     }
+    int evaluate_topn(int ncut, const int* cuts, double thr, int flags, pcr_topn_stats* stats, double* per_user) override {
+        return base->evaluate_topn_with(ncut, cuts, thr, flags, stats, per_user, [this](const char* name) { return Prof(this, name); });
+    }
     int residual_mismatch(double* value) override {
         hipLaunchKernelGGL((k_ccd_mismatch<RT>), dim3(B), dim3(ccd::BLOCK), 0, st, (const RT*)d_res_r.p, (const RT*)d_res_c.p, (const int32_t*)d_c2r.p,
                            nnz, d_pmis.p);

@@ -1051,8 +1051,8 @@ extern "C" int pcr_partition_users(const int64_t* index, int64_t d1, int nparts,
 
 int pcr_recommend_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
                               const int32_t* item, int64_t n, const int32_t* users, int topk, int dtype, const int32_t* items,
-                              const double* scores, bool* sorted) {
-    auto bad = [](const std::string& why) { pcr_set_error("pcr_recommend_model: " + why); return PCR_ERR_ARG; };
+                              const double* scores, bool* sorted, const char* who) {
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
     if (sorted) *sorted = true;
     if (!U || !V || d1 < 1 || d2 < 1 || k < 1 || n < 0) return bad("bad argument");
     if (d2 >= ((int64_t)1 << 31) - 64) return bad("more than 2^31 items");
@@ -1087,4 +1087,106 @@ int pcr_recommend_model_check(const double* U, int64_t d1, const double* V, int6
         if (sorted) *sorted = !(all & 2);
     }
     return PCR_OK;
+}
+
+int pcr_topn_check(const char* who, int ncut, const int* cutoffs, double threshold, const pcr_topn_stats* stats) {
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
+    if (ncut < 1 || ncut > PCR_TOPN_MAX_CUTOFFS || !cutoffs)
+        return bad("ncut = " + std::to_string(ncut) + " outside [1, " + std::to_string(PCR_TOPN_MAX_CUTOFFS) + "] (or no cutoffs)");
+    for (int c = 0; c < ncut; ++c) {
+        if (cutoffs[c] < 1 || cutoffs[c] > PCR_RECOMMEND_MAX_K)
+            return bad("cutoff " + std::to_string(cutoffs[c]) + " outside [1, " + std::to_string(PCR_RECOMMEND_MAX_K) + "]");
+        if (c > 0 && cutoffs[c] <= cutoffs[c - 1]) return bad("cutoffs must be strictly ascending");
+    }
+    if (std::isnan(threshold)) return bad("threshold is NaN");
+    if (!stats) return bad("null stats");
+    return PCR_OK;
+}
+
+int pcr_evaluate_topn_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
+                                  const int32_t* item, const int64_t* tindex, const int32_t* titem, const double* tval, int ncut,
+                                  const int* cutoffs, double threshold, int dtype, const pcr_topn_stats* stats, bool* sorted) {
+    auto bad = [](const std::string& why) { pcr_set_error("pcr_evaluate_topn_model: " + why); return PCR_ERR_ARG; };
+    int rc = pcr_topn_check("pcr_evaluate_topn_model", ncut, cutoffs, threshold, stats);
+    if (rc != PCR_OK) return rc;
+    rc = pcr_recommend_model_check(U, d1, V, d2, k, index, item, 0, nullptr, cutoffs[ncut - 1], dtype, nullptr, nullptr, sorted,
+                                             "pcr_evaluate_topn_model");
+    if (rc != PCR_OK) return rc;
+    if (!tindex || !titem || !tval) return bad("null test CSR");
+    if (tindex[0] != 0) return bad("tindex[0] must be 0");
+    for (int64_t u = 0; u < d1; ++u) if (tindex[u + 1] < tindex[u]) return bad("tindex not monotone at user " + std::to_string(u));
+    const int nth = pcr_host_threads();
+    std::vector<char> out_of_range((size_t)nth, 0);
+    pcr_parallel_ranges(tindex[d1], nth, [&](int t, int64_t lo, int64_t hi) {
+        for (int64_t z = lo; z < hi; ++z) if (titem[z] < 0 || titem[z] >= d2) { out_of_range[(size_t)t] = 1; return; }
+    });
+    for (char x : out_of_range) if (x) return bad("an item id of the test CSR is outside [0, d2)");
+    return PCR_OK;
+}
+
+void pcr_topn_relevance(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, double threshold, int ncut,
+                        const int* cutoffs, PcrTopnRel& out) {
+    const int K = cutoffs[ncut - 1];
+    out.disc.resize((size_t)K);
+    for (int i = 0; i < K; ++i) out.disc[(size_t)i] = 1.0 / log2((double)(i + 2));
+    // contiguous user ranges per host thread, concatenated in order: the counted users stay ascending
+    const int nth = pcr_host_threads();
+    struct Part { std::vector<int32_t> users; std::vector<int64_t> len; std::vector<int32_t> item; std::vector<double> gain, idcg; };
+    std::vector<Part> parts((size_t)nth);
+    pcr_parallel_ranges(rows, nth, [&](int t, int64_t lo, int64_t hi) {
+        Part& P = parts[(size_t)t];
+        std::vector<std::pair<int32_t, double>> row;
+        std::vector<double> g;
+        for (int64_t u = lo; u < hi; ++u) {
+            row.clear();
+            for (int64_t z = tptr[u]; z < tptr[u + 1]; ++z) if (tval[z] >= threshold) row.emplace_back(titem[z], tval[z]);
+            if (row.empty()) continue;
+            std::sort(row.begin(), row.end());
+            g.clear();
+            for (size_t e = 0; e < row.size(); ++e) {
+                if (e + 1 < row.size() && row[e + 1].first == row[e].first) continue;      // the largest rating of a duplicated item
+                P.item.push_back(row[e].first);
+                g.push_back(pow(2.0, row[e].second) - 1.0);
+                P.gain.push_back(g.back());
+            }
+            P.users.push_back((int32_t)u);
+            P.len.push_back((int64_t)g.size());
+            std::sort(g.begin(), g.end(), [](double a, double b) { return a > b; });
+            const int64_t nr = (int64_t)g.size();
+            for (int c = 0; c < ncut; ++c) {
+                const int64_t m = std::min<int64_t>(cutoffs[c], nr);
+                double b = 0.0, w = 0.0;
+                for (int64_t i = 0; i < m; ++i) { b += out.disc[(size_t)i]; w += g[(size_t)i] * out.disc[(size_t)i]; }
+                P.idcg.push_back(b); P.idcg.push_back(w);
+            }
+        }
+    });
+    out.users.clear(); out.ritem.clear(); out.rgain.clear(); out.idcg.clear();
+    out.rptr.assign(1, 0);
+    for (const Part& P : parts) {
+        out.users.insert(out.users.end(), P.users.begin(), P.users.end());
+        for (int64_t l : P.len) out.rptr.push_back(out.rptr.back() + l);
+        out.ritem.insert(out.ritem.end(), P.item.begin(), P.item.end());
+        out.rgain.insert(out.rgain.end(), P.gain.begin(), P.gain.end());
+        out.idcg.insert(out.idcg.end(), P.idcg.begin(), P.idcg.end());
+    }
+}
+
+void pcr_topn_stats_from(const double* sums, int ncut, const int* cutoffs, pcr_topn_stats* stats) {
+    const double users = sums[8 * ncut];
+    auto mean = [](double s, double n) { return n > 0.0 ? s / n : 0.0; };
+    for (int c = 0; c < ncut; ++c) {
+        const double* x = sums + 8 * c;
+        pcr_topn_stats& o = stats[c];
+        o.cutoff = cutoffs[c];
+        o.users = (int64_t)users;
+        o.users_graded = (int64_t)x[7];
+        o.hits = (int64_t)x[0];
+        o.precision = mean(x[1], users);
+        o.recall = mean(x[2], users);
+        o.hit_rate = mean(x[3], users);
+        o.map = mean(x[4], users);
+        o.ndcg = mean(x[5], users);
+        o.ndcg_graded = mean(x[6], x[7]);
+    }
 }

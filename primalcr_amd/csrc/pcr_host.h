@@ -72,4 +72,30 @@ int pcr_tune_int(const char* key, int dflt);
 // `item` is non-decreasing (the kernel's exclusion cursor needs that; the caller sorts a copy otherwise).
 int pcr_recommend_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
                               const int32_t* item, int64_t n, const int32_t* users, int topk, int dtype, const int32_t* items,
-                              const double* scores, bool* sorted);
+                              const double* scores, bool* sorted, const char* who = "pcr_recommend_model");
+
+// the top-N evaluation's own arguments (both entries): 1 .. PCR_TOPN_MAX_CUTOFFS cutoffs, strictly ascending, inside
+// [1, PCR_RECOMMEND_MAX_K]; threshold not NaN; stats != NULL.  Errors are prefixed with `who`.
+int pcr_topn_check(const char* who, int ncut, const int* cutoffs, double threshold, const pcr_topn_stats* stats);
+// pcr_evaluate_topn_model's argument checks (shared with the sanitizer build's stub): the factor / exclusion checks of
+// pcr_recommend_model, pcr_topn_check and the test CSR's shape.  *sorted as pcr_recommend_model_check.
+int pcr_evaluate_topn_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
+                                  const int32_t* item, const int64_t* tindex, const int32_t* titem, const double* tval, int ncut,
+                                  const int* cutoffs, double threshold, int dtype, const pcr_topn_stats* stats, bool* sorted);
+
+// Top-N evaluation's relevance tables (include/primalcr.h, "full-catalogue top-N evaluation") of rows [0, rows) of a test CSR
+// (tptr[rows + 1] relative, items in any order): the counted users (|R_u| >= 1, ascending), their relevant rows (distinct items
+// ascending, each with its graded gain pow(2, v_max) - 1), the discounts d(i) for i < the largest cutoff and per counted user
+// and cutoff the ideal DCGs, binary then graded, each summed in position order.
+struct PcrTopnRel {
+    std::vector<int32_t> users;
+    std::vector<int64_t> rptr;       // users.size() + 1
+    std::vector<int32_t> ritem;
+    std::vector<double> rgain;
+    std::vector<double> disc;
+    std::vector<double> idcg;        // [users][ncut][2]
+};
+void pcr_topn_relevance(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, double threshold, int ncut,
+                        const int* cutoffs, PcrTopnRel& out);
+// stats[c] from the reduced sums (k_topn_fin's layout: [ncut][8], then the counted users)
+void pcr_topn_stats_from(const double* sums, int ncut, const int* cutoffs, pcr_topn_stats* stats);

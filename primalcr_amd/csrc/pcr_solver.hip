@@ -83,15 +83,16 @@ struct DBuf {
 };
 
 // Top-K recommendation (pcr_topk.h) for the n users h_users[0..n) -- rows of U and of the exclusion CSR xptr / xitem (NULL:
-// none), or rows 0..n-1 when h_users is NULL -- into the host arrays items / scores (n x K).  Users go in batches whose
-// partial lists stay under REC_SCRATCH bytes; the item range is split across workgroups until the grid holds about
-// REC_TARGET_WG workgroups (ml1m's 6 040 users are 95 workgroups of 64).  scope(name) returns the profiler's RAII scope.
-// select = 0 only for tools/exp_recommend.py's GEMM-alone timing (lists come back empty).
+// none), or rows 0..n-1 when h_users is NULL.  Users go in batches whose partial lists stay under REC_SCRATCH bytes; the item
+// range is split across workgroups until the grid holds about REC_TARGET_WG workgroups (ml1m's 6 040 users are 95 workgroups
+// of 64).  Each batch's partial lists go to the sink: sink.begin(nb) once with the largest batch, then sink.batch(b0, m, ...)
+// per batch, which merges them (RecCopy: into pcr_recommend's host arrays; RecTopn: into the top-N metrics).  scope(name)
+// returns the profiler's RAII scope.  select = 0 only for tools/exp_recommend.py's GEMM-alone timing (lists come back empty).
 static const size_t REC_SCRATCH = (size_t)1 << 30;
 static const int REC_TARGET_WG = 1024, REC_MAX_SPLIT = 16, REC_MIN_SPLIT_ITEMS = 1024;
-template <typename T, class Scope>
+template <typename T, class Scope, class Sink>
 static int rec_run(hipStream_t st, const T* U, const T* V, int r, int ld, int64_t d2, const int64_t* xptr, const int32_t* xitem,
-                   int64_t n, const int32_t* h_users, int K, int32_t* items, double* scores, int select, Scope&& scope) {
+                   int64_t n, const int32_t* h_users, int K, int select, Scope&& scope, Sink&& sink) {
     if (n <= 0) return PCR_OK;
     const size_t per_user = (size_t)K * (sizeof(T) + sizeof(int32_t)) + sizeof(int32_t);
     const int64_t users_per_wg = (int64_t)rec::WAVES * rec::UW;
@@ -104,9 +105,9 @@ static int rec_run(hipStream_t st, const T* U, const T* V, int r, int ld, int64_
     };
     while (nb > users_per_wg && (size_t)nb * (size_t)splits_for(nb) * per_user > REC_SCRATCH) nb = std::max<int64_t>(users_per_wg, nb / 2);
     const int smax = splits_for(std::min(nb, n));
-    DBuf<T> ls; DBuf<int32_t> li, ln, du, oi; DBuf<double> os;
+    DBuf<T> ls; DBuf<int32_t> li, ln, du;
     RC(ls.alloc((size_t)nb * smax * K)); RC(li.alloc((size_t)nb * smax * K)); RC(ln.alloc((size_t)nb * smax));
-    RC(du.alloc((size_t)nb)); RC(oi.alloc((size_t)nb * K)); RC(os.alloc((size_t)nb * K));
+    RC(du.alloc((size_t)nb)); RC(sink.begin(nb));
     const size_t lds = rec_wave_lds<T>(K) * rec::WAVES;
     HIPCHK(hipFuncSetAttribute((const void*)k_rec_score<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     std::vector<int32_t> seq;
@@ -125,18 +126,109 @@ static int rec_run(hipStream_t st, const T* U, const T* V, int r, int ld, int64_
                                (int)d2, du.p, m, xptr, xitem, K, per, ls.p, li.p, ln.p, select);
             HIPCHK(hipGetLastError());
         }
+        RC(sink.batch(b0, m, (const T*)ls.p, (const int32_t*)li.p, (const int32_t*)ln.p, nsp, scope));
+        HIPCHK(hipStreamSynchronize(st));                  // (the next batch's users overwrite du / seq)
+    }
+    return PCR_OK;
+}
+
+// rec_run's sink for pcr_recommend: merged lists to the host arrays items / scores (n x K)
+template <typename T>
+struct RecCopy {
+    hipStream_t st;
+    int K;
+    int32_t* items;
+    double* scores;
+    DBuf<int32_t> oi;
+    DBuf<double> os;
+    RecCopy(hipStream_t st_, int K_, int32_t* items_, double* scores_) : st(st_), K(K_), items(items_), scores(scores_) {}
+    int begin(int64_t nb) { RC(oi.alloc((size_t)nb * K)); RC(os.alloc((size_t)nb * K)); return PCR_OK; }
+    template <class Scope>
+    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp, Scope& scope) {
         {
             auto sc = scope("recommend/merge");
             (void)sc;
-            hipLaunchKernelGGL((k_rec_merge<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), 0, st, ls.p, li.p, ln.p, nsp, m, K, oi.p, os.p);
+            hipLaunchKernelGGL((k_rec_merge<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), 0, st, ls, li, ln, nsp, m, K, oi.p, os.p);
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipMemcpyAsync(items + b0 * K, oi.p, (size_t)m * K * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(scores + b0 * K, os.p, (size_t)m * K * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
+        return PCR_OK;
     }
-    return PCR_OK;
-}
+};
+
+// Top-N evaluation's device tables (PcrTopnRel of pcr_host.h, uploaded once per (threshold, cutoffs)) and its outputs: the
+// per-user metric rows met[n][ncut][6] of the counted users and the reduced sums [ncut][8] + the count (k_topn_fin)
+struct TopnDev {
+    PcrTopnRel rel;
+    int ncut = 0;
+    int cut[PCR_TOPN_MAX_CUTOFFS] = {};
+    double threshold = 0.0;
+    bool valid = false;
+    DBuf<int64_t> rptr;
+    DBuf<int32_t> ritem;
+    DBuf<double> rgain, idcg, disc, met, part, sums;
+    bool same(int nc, const int* cuts, double thr) const {
+        if (!valid || nc != ncut || !(thr == threshold)) return false;
+        for (int c = 0; c < nc; ++c) if (cuts[c] != cut[c]) return false;
+        return true;
+    }
+    // the relevance tables of rows [0, rows) of the test CSR, to the device
+    int build(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, int nc, const int* cuts, double thr) {
+        valid = false;
+        pcr_topn_relevance(rows, tptr, titem, tval, thr, nc, cuts, rel);
+        ncut = nc; threshold = thr;
+        for (int c = 0; c < nc; ++c) cut[c] = cuts[c];
+        RC(rptr.upload(rel.rptr, nullptr)); RC(ritem.upload(rel.ritem, nullptr)); RC(rgain.upload(rel.rgain, nullptr));
+        RC(idcg.upload(rel.idcg, nullptr)); RC(disc.upload(rel.disc, nullptr));
+        RC(met.alloc(rel.users.size() * (size_t)ncut * 6)); RC(sums.alloc((size_t)ncut * 8 + 1));
+        valid = true;
+        return PCR_OK;
+    }
+    // the fixed-order sums over the counted users into sums (k_sum4_stage1 / k_fin4's two stages, one block row per cutoff)
+    int reduce(hipStream_t st) {
+        const int64_t n = (int64_t)rel.users.size();
+        const int nb = (int)std::min<int64_t>(512, std::max<int64_t>(1, cdiv(n, 2048)));
+        const int per = cdiv(std::max<int64_t>(n, 1), nb);
+        if (part.n < (size_t)nb * ncut * 8) RC(part.alloc((size_t)nb * ncut * 8));
+        hipLaunchKernelGGL(k_topn_sum1, dim3(nb, ncut), dim3(PCR_EW_BLOCK), 0, st, (const double*)met.p, n, ncut, per, part.p);
+        hipLaunchKernelGGL(k_topn_fin, dim3(ncut), dim3(PCR_EW_BLOCK), 0, st, (const double*)part.p, nb, n, sums.p);
+        HIPCHK(hipGetLastError());
+        return PCR_OK;
+    }
+    // per_user[rows][ncut][6]: NaN, then the counted users' rows
+    int fetch_per_user(hipStream_t st, int64_t rows, double* per_user) {
+        const size_t w = (size_t)ncut * 6;
+        std::vector<double> h(rel.users.size() * w);
+        if (!h.empty()) HIPCHK(hipMemcpyAsync(h.data(), met.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        std::fill(per_user, per_user + (size_t)rows * w, (double)NAN);
+        for (size_t i = 0; i < rel.users.size(); ++i) std::copy(h.begin() + i * w, h.begin() + (i + 1) * w, per_user + (size_t)rel.users[i] * w);
+        return PCR_OK;
+    }
+};
+
+// rec_run's sink for the top-N evaluation: merge + metrics (k_rec_merge_topn) into d.met at the batch's rows
+template <typename T>
+struct RecTopn {
+    hipStream_t st;
+    int K;
+    TopnDev& d;
+    RecTopn(hipStream_t st_, int K_, TopnDev& d_) : st(st_), K(K_), d(d_) {}
+    int begin(int64_t) { return PCR_OK; }
+    template <class Scope>
+    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp, Scope& scope) {
+        TopnArgs ta;
+        ta.rptr = d.rptr.p + b0; ta.ritem = d.ritem.p; ta.rgain = d.rgain.p; ta.idcg = d.idcg.p + (size_t)b0 * d.ncut * 2;
+        ta.disc = d.disc.p; ta.out = d.met.p + (size_t)b0 * d.ncut * 6; ta.ncut = d.ncut;
+        for (int c = 0; c < PCR_TOPN_MAX_CUTOFFS; ++c) ta.cut[c] = c < d.ncut ? d.cut[c] : 0;
+        auto sc = scope("recommend/metrics");
+        (void)sc;
+        hipLaunchKernelGGL((k_rec_merge_topn<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), (size_t)4 * K * sizeof(int32_t), st, ls, li, ln, nsp, m, K, ta);
+        HIPCHK(hipGetLastError());
+        return PCR_OK;
+    }
+};
 
 // users of one CSR grouped by length class; each class has its own workgroup size
 struct Bin {
@@ -207,6 +299,8 @@ struct pcr_solver {
     virtual int set_ccd_params(const pcr_ccd_params*) { pcr_set_error("pcr_solver_set_ccd_params: not a CCDR1 solver (solver type 0)"); return PCR_ERR_STATE; }
     // pcr_recommend: `local` = rows of this shard (checked by the caller)
     virtual int recommend(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores) = 0;
+    // pcr_evaluate_topn (arguments checked by the caller)
+    virtual int evaluate_topn(int ncut, const int* cuts, double threshold, int flags, pcr_topn_stats* stats, double* per_user) = 0;
 };
 
 // launch knobs: pcr_tune() values read once when the solver is created (include/primalcr.h lists them)
@@ -334,6 +428,9 @@ struct Solver final : pcr_solver {
         int idcg_k = -1;
     } ev[2];
     DBuf<double> d_out4;
+    std::vector<int32_t> h_test_item;             // the test shard's ratings (rows: ev[1].h_uptr), for pcr_evaluate_topn
+    std::vector<double> h_test_val;
+    TopnDev topn;
     // ---- factors and CG vectors (d2 x ld, nu x ld)
     DBuf<T> d_U, d_V, d_Vnew, d_g, d_delta, d_rr, d_p, d_Hp;
     CGState* d_cgp = nullptr;                     // the CG scalars live in d_scal[32..43): they come back with the objective's read-back
@@ -1126,7 +1223,10 @@ struct Solver final : pcr_solver {
             es.nnz = b - a;
             es.h_uptr.resize(nu + 1);
             for (int64_t u = 0; u <= nu; ++u) es.h_uptr[u] = E.index[ds_u0 + u] - a;
-            if (w == 1) { RC(es.uptr.upload(es.h_uptr, st)); RC(es.item.upload_n(E.item.data() + a, (size_t)es.nnz)); }
+            if (w == 1) {
+                RC(es.uptr.upload(es.h_uptr, st)); RC(es.item.upload_n(E.item.data() + a, (size_t)es.nnz));
+                h_test_item.assign(E.item.begin() + a, E.item.begin() + b); h_test_val.assign(E.val.begin() + a, E.val.begin() + b);
+            }
             RC(es.idcg.alloc(nu));
             const bool same = w == 0 && (prm.solver_type == PCR_SOLVER_PCR || lv.integer_valued);
             PcrLevels rl_own;
@@ -2355,8 +2455,34 @@ struct Solver final : pcr_solver {
     template <class Scope>
     int recommend_with(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores, Scope&& scope) {
         const bool ex = (flags & PCR_REC_EXCLUDE_TRAIN) != 0;
-        return rec_run<T>(st, d_U.p, d_V.p, geo.r, geo.ld, d2, ex ? d_uptr.p : nullptr, ex ? d_item.p : nullptr, n, local, K, items, scores,
-                          tune.recommend_select, scope);
+        return rec_run<T>(st, d_U.p, d_V.p, geo.r, geo.ld, d2, ex ? d_uptr.p : nullptr, ex ? d_item.p : nullptr, n, local, K,
+                          tune.recommend_select, scope, RecCopy<T>(st, K, items, scores));
+    }
+    // full-catalogue top-N evaluation of the shard's users against its test ratings (h_test_*, kept at creation); the relevance
+    // tables are built on the first call for a (threshold, cutoffs) and kept in topn
+    template <class Scope>
+    int evaluate_topn_with(int ncut, const int* cuts, double thr, int flags, pcr_topn_stats* stats, double* per_user, Scope&& scope) {
+        if (!topn.same(ncut, cuts, thr))
+            RC(topn.build(n_users, ev[1].h_uptr.data(), h_test_item.data(), h_test_val.data(), ncut, cuts, thr));
+        const bool ex = (flags & PCR_REC_EXCLUDE_TRAIN) != 0;
+        const int K = cuts[ncut - 1];
+        RC(rec_run<T>(st, d_U.p, d_V.p, geo.r, geo.ld, d2, ex ? d_uptr.p : nullptr, ex ? d_item.p : nullptr, (int64_t)topn.rel.users.size(),
+                      topn.rel.users.data(), K, 1, scope, RecTopn<T>(st, K, topn)));
+        {
+            auto sc = scope("recommend/metrics");
+            (void)sc;
+            RC(topn.reduce(st));
+        }
+        RC(allreduce_f64(topn.sums.p, (size_t)ncut * 8 + 1));
+        std::vector<double> h((size_t)ncut * 8 + 1);
+        HIPCHK(hipMemcpyAsync(h.data(), topn.sums.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        RC(sync_checked());
+        pcr_topn_stats_from(h.data(), ncut, cuts, stats);
+        if (per_user) RC(topn.fetch_per_user(st, n_users, per_user));
+        return PCR_OK;
+    }
+    int evaluate_topn(int ncut, const int* cuts, double thr, int flags, pcr_topn_stats* stats, double* per_user) override {
+        return evaluate_topn_with(ncut, cuts, thr, flags, stats, per_user, [this](const char* name) { return ProfScope(this, name); });
     }
     int recommend(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores) override {
         return recommend_with(n, local, K, flags, items, scores, [this](const char* name) { return ProfScope(this, name); });
@@ -2378,6 +2504,58 @@ static int abi_guard(const char* what, F&& body) noexcept {
     catch (...) { return PCR_ERR_ARG; }
 }
 #define PCR_ABI(name, expr) return abi_guard(name, [&]() -> int { return (expr); })
+
+// pcr_recommend_model / pcr_evaluate_topn_model: the exclusion CSR (item-ascending rows: a CSR that is not gets a sorted copy,
+// for the kernel's cursor) and both host fp64 factors in the requested type, rows padded to ld (slabs of 64 M values)
+struct ModelDev {
+    DBuf<int64_t> dx;
+    DBuf<int32_t> di;
+    DBuf<float> F32;
+    DBuf<double> F64;
+    int ld = 0;
+    int upload_exclusion(int64_t d1, const int64_t* index, const int32_t* item, bool sorted) {
+        if (!index) return PCR_OK;
+        std::vector<int32_t> sitem;
+        const int64_t nnz = index[d1];
+        if (!sorted) {
+            sitem.assign(item, item + nnz);
+            pcr_parallel_ranges(d1, pcr_host_threads(), [&](int, int64_t lo, int64_t hi) {
+                for (int64_t u = lo; u < hi; ++u) std::sort(sitem.begin() + index[u], sitem.begin() + index[u + 1]);
+            });
+        }
+        RC(dx.upload_n(index, (size_t)d1 + 1)); RC(di.upload_n(sorted ? item : sitem.data(), (size_t)nnz));
+        return PCR_OK;
+    }
+    template <typename T>
+    int upload_factors(hipStream_t st, const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, DBuf<T>& F) {
+        ld = ((int)k + 3) & ~3;
+        RC(F.alloc((size_t)(d1 + d2) * ld));
+        DBuf<double> stage;
+        const int64_t slab_rows = std::max<int64_t>(1, ((int64_t)64 << 20) / k);
+        RC(stage.alloc((size_t)std::min<int64_t>(std::max(d1, d2), slab_rows) * (size_t)k));
+        for (int w = 0; w < 2; ++w) {
+            const double* H = w == 0 ? U : V;
+            T* dst = F.p + (w == 0 ? 0 : (size_t)d1 * ld);
+            const int64_t rows = w == 0 ? d1 : d2;
+            for (int64_t r0 = 0; r0 < rows; r0 += slab_rows) {
+                const int64_t nr = std::min(slab_rows, rows - r0);
+                HIPCHK(hipMemcpyAsync(stage.p, H + r0 * k, (size_t)nr * k * sizeof(double), hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL((k_mat_in<T>), dim3((unsigned)std::min<int64_t>(1 << 16, cdiv(nr * ld, 256))), dim3(256), 0, st, stage.p, dst + r0 * ld, nr, (int)k, ld);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipStreamSynchronize(st));
+            }
+        }
+        return PCR_OK;
+    }
+};
+
+static int model_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { pcr_set_error("no HIP device available"); return PCR_ERR_DEVICE; }
+    if (device < 0 || device >= ndev) { pcr_set_error("device ordinal out of range"); return PCR_ERR_ARG; }
+    HIPCHK(hipSetDevice(device));
+    return PCR_OK;
+}
 
 extern "C" {
 
@@ -2608,55 +2786,55 @@ int pcr_recommend_model(const double* U, int64_t d1, const double* V, int64_t d2
     return abi_guard("pcr_recommend_model", [&]() -> int {
     bool sorted = true;
     RC(pcr_recommend_model_check(U, d1, V, d2, k, index, item, n, users, topk, dtype, items, scores, &sorted));
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { pcr_set_error("no HIP device available"); return PCR_ERR_DEVICE; }
-    if (device < 0 || device >= ndev) { pcr_set_error("device ordinal out of range"); return PCR_ERR_ARG; }
-    HIPCHK(hipSetDevice(device));
+    RC(model_device(device));
     if (n == 0) return PCR_OK;
-    // the exclusion rows must be item-ascending for the kernel's cursor: a CSR that is not gets a sorted copy
-    std::vector<int32_t> sitem;
-    const int64_t nnz = index ? index[d1] : 0;
-    if (index && !sorted) {
-        sitem.assign(item, item + nnz);
-        pcr_parallel_ranges(d1, pcr_host_threads(), [&](int, int64_t lo, int64_t hi) {
-            for (int64_t u = lo; u < hi; ++u) std::sort(sitem.begin() + index[u], sitem.begin() + index[u + 1]);
-        });
-    }
-    const int ld = ((int)k + 3) & ~3;
     hipStream_t st = nullptr;
-    DBuf<int64_t> dx; DBuf<int32_t> di;
-    if (index) { RC(dx.upload_n(index, (size_t)d1 + 1)); RC(di.upload_n(sorted ? item : sitem.data(), (size_t)nnz)); }
-    auto up = [&](auto* D) -> int {     // both factors to the device in the requested type, rows padded to ld (slabs of 64 M values)
-        typedef std::remove_pointer_t<decltype(D)> T;
-        DBuf<double> stage;
-        const int64_t slab_rows = std::max<int64_t>(1, ((int64_t)64 << 20) / k);
-        RC(stage.alloc((size_t)std::min<int64_t>(std::max(d1, d2), slab_rows) * (size_t)k));
-        for (int w = 0; w < 2; ++w) {
-            const double* H = w == 0 ? U : V;
-            T* dst = D + (w == 0 ? 0 : (size_t)d1 * ld);
-            const int64_t rows = w == 0 ? d1 : d2;
-            for (int64_t r0 = 0; r0 < rows; r0 += slab_rows) {
-                const int64_t nr = std::min(slab_rows, rows - r0);
-                HIPCHK(hipMemcpyAsync(stage.p, H + r0 * k, (size_t)nr * k * sizeof(double), hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL((k_mat_in<T>), dim3((unsigned)std::min<int64_t>(1 << 16, cdiv(nr * ld, 256))), dim3(256), 0, st, stage.p, dst + r0 * ld, nr, (int)k, ld);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipStreamSynchronize(st));
-            }
-        }
-        return PCR_OK;
-    };
+    ModelDev M;
+    RC(M.upload_exclusion(d1, index, item, sorted));
     auto noscope = [](const char*) { return 0; };
     const int select = pcr_tune_int("recommend_select", 1);
     if (dtype == PCR_F64) {
-        DBuf<double> F;
-        RC(F.alloc((size_t)(d1 + d2) * ld));
-        RC(up(F.p));
-        return rec_run<double>(st, F.p, F.p + (size_t)d1 * ld, (int)k, ld, d2, dx.p, index ? di.p : nullptr, n, users, topk, items, scores, select, noscope);
+        RC(M.upload_factors(st, U, d1, V, d2, k, M.F64));
+        return rec_run<double>(st, M.F64.p, M.F64.p + (size_t)d1 * M.ld, (int)k, M.ld, d2, M.dx.p, M.di.p, n, users, topk, select, noscope,
+                               RecCopy<double>(st, topk, items, scores));
     }
-    DBuf<float> F;
-    RC(F.alloc((size_t)(d1 + d2) * ld));
-    RC(up(F.p));
-    return rec_run<float>(st, F.p, F.p + (size_t)d1 * ld, (int)k, ld, d2, dx.p, index ? di.p : nullptr, n, users, topk, items, scores, select, noscope);
+    RC(M.upload_factors(st, U, d1, V, d2, k, M.F32));
+    return rec_run<float>(st, M.F32.p, M.F32.p + (size_t)d1 * M.ld, (int)k, M.ld, d2, M.dx.p, M.di.p, n, users, topk, select, noscope,
+                          RecCopy<float>(st, topk, items, scores));
+    });
+}
+
+int pcr_evaluate_topn_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                            const int64_t* tindex, const int32_t* titem, const double* tval, int ncut, const int* cutoffs, double threshold,
+                            int dtype, pcr_topn_stats* stats, double* per_user, int device) {
+    return abi_guard("pcr_evaluate_topn_model", [&]() -> int {
+    bool sorted = true;
+    RC(pcr_evaluate_topn_model_check(U, d1, V, d2, k, index, item, tindex, titem, tval, ncut, cutoffs, threshold, dtype, stats, &sorted));
+    RC(model_device(device));
+    hipStream_t st = nullptr;
+    ModelDev M;
+    RC(M.upload_exclusion(d1, index, item, sorted));
+    TopnDev D;
+    RC(D.build(d1, tindex, titem, tval, ncut, cutoffs, threshold));
+    const int K = cutoffs[ncut - 1];
+    const int64_t n = (int64_t)D.rel.users.size();
+    auto noscope = [](const char*) { return 0; };
+    if (dtype == PCR_F64) {
+        RC(M.upload_factors(st, U, d1, V, d2, k, M.F64));
+        RC(rec_run<double>(st, M.F64.p, M.F64.p + (size_t)d1 * M.ld, (int)k, M.ld, d2, M.dx.p, M.di.p, n, D.rel.users.data(), K, 1, noscope,
+                           RecTopn<double>(st, K, D)));
+    } else {
+        RC(M.upload_factors(st, U, d1, V, d2, k, M.F32));
+        RC(rec_run<float>(st, M.F32.p, M.F32.p + (size_t)d1 * M.ld, (int)k, M.ld, d2, M.dx.p, M.di.p, n, D.rel.users.data(), K, 1, noscope,
+                          RecTopn<float>(st, K, D)));
+    }
+    RC(D.reduce(st));
+    std::vector<double> h((size_t)ncut * 8 + 1);
+    HIPCHK(hipMemcpyAsync(h.data(), D.sums.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    pcr_topn_stats_from(h.data(), ncut, cutoffs, stats);
+    if (per_user) RC(D.fetch_per_user(st, d1, per_user));
+    return PCR_OK;
     });
 }
 
@@ -2682,6 +2860,13 @@ int pcr_recommend(pcr_solver* s, int64_t n, const int32_t* users, int topk, int 
         }
         return s->recommend(n, users ? loc.data() : nullptr, topk, flags, items, scores);
     });
+}
+
+int pcr_evaluate_topn(pcr_solver* s, int ncut, const int* cutoffs, double threshold, int flags, pcr_topn_stats* stats, double* per_user) {
+    S_OR_ARG;
+    RC(pcr_topn_check("pcr_evaluate_topn", ncut, cutoffs, threshold, stats));
+    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_evaluate_topn: unknown flags"); return PCR_ERR_ARG; }
+    return abi_guard("pcr_evaluate_topn", [&]() -> int { return s->evaluate_topn(ncut, cutoffs, threshold, flags, stats, per_user); });
 }
 
 }  // extern "C"

@@ -15,10 +15,14 @@
 //   builds the 64-bit mask of the step's rated items -- O(nnz) in all.
 // k_rec_merge: one wave per user merges the partial lists of the item splits by rank counting (binary searches into the other
 //   lists), converts the scores to double and pads with (-1, -inf).
+// k_rec_merge_topn: the same merge for the full-catalogue top-N evaluation (pcr_evaluate_topn): the list
+//   stays in LDS and is scored against the user's relevant test items; k_topn_sum1 / k_topn_fin reduce the per-user metrics.
 // No atomic decides a result: the LDS slot counter only decides where a candidate sits in the buffer, and the merges rank by
 // the total order (score, id), so every list is the same whatever the order of arrival.
 #pragma once
+#include "primalcr.h"
 #include "pcr_prims.h"
+#include "pcr_vside.h"      // PCR_EW_BLOCK
 
 namespace rec {
 constexpr int WAVES = 4;      // waves per workgroup: the four sweep the same items, so three of them read V's rows from L1
@@ -212,14 +216,12 @@ __global__ __launch_bounds__(256) void k_rec_score(const T* __restrict__ U, cons
     if (active && g == 0) lst_n[(size_t)blockIdx.y * (size_t)n + (size_t)idx] = len;
 }
 
-// one wave per user: the nsplit partial lists -> items[idx * K ...], scores (double), padded with (-1, -inf)
-template <typename T>
-__global__ __launch_bounds__(256) void k_rec_merge(const T* __restrict__ lst_s, const int32_t* __restrict__ lst_i,
-                                                   const int32_t* __restrict__ lst_n, int nsplit, int64_t n, int K,
-                                                   int32_t* __restrict__ out_i, double* __restrict__ out_s) {
-    const int lane = threadIdx.x & 63;
-    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (idx >= n) return;
+// the rank of every entry of the nsplit partial lists of user idx in the merged list, by rank counting (binary searches into
+// the other lists); emit(rank, id, score) for ranks < K.  Returns the total length of the partial lists.
+template <typename T, class Emit>
+__device__ __forceinline__ int rec_merge_ranks(const T* __restrict__ lst_s, const int32_t* __restrict__ lst_i,
+                                               const int32_t* __restrict__ lst_n, int nsplit, int64_t n, int K, int64_t idx, int lane,
+                                               Emit&& emit) {
     int tot = 0;
     for (int sp = 0; sp < nsplit; ++sp) {
         const size_t o = ((size_t)sp * (size_t)n + (size_t)idx) * (size_t)K;
@@ -236,8 +238,136 @@ __global__ __launch_bounds__(256) void k_rec_merge(const T* __restrict__ lst_s, 
                 while (a < b) { const int mid = (a + b) >> 1; if (rec_better(lst_s[o2 + mid], lst_i[o2 + mid], s, j)) a = mid + 1; else b = mid; }
                 rk += a;
             }
-            if (rk < K) { out_i[(size_t)idx * K + rk] = j; out_s[(size_t)idx * K + rk] = (double)s; }
+            if (rk < K) emit(rk, j, s);
         }
     }
+    return tot;
+}
+
+// one wave per user: the nsplit partial lists -> items[idx * K ...], scores (double), padded with (-1, -inf)
+template <typename T>
+__global__ __launch_bounds__(256) void k_rec_merge(const T* __restrict__ lst_s, const int32_t* __restrict__ lst_i,
+                                                   const int32_t* __restrict__ lst_n, int nsplit, int64_t n, int K,
+                                                   int32_t* __restrict__ out_i, double* __restrict__ out_s) {
+    const int lane = threadIdx.x & 63;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (idx >= n) return;
+    const int tot = rec_merge_ranks(lst_s, lst_i, lst_n, nsplit, n, K, idx, lane, [&](int rk, int j, T s) {
+        out_i[(size_t)idx * K + rk] = j; out_s[(size_t)idx * K + rk] = (double)s;
+    });
     for (int p = min(tot, K) + lane; p < K; p += 64) { out_i[(size_t)idx * K + p] = -1; out_s[(size_t)idx * K + p] = -INFINITY; }
+}
+
+// Top-N evaluation (pcr_evaluate_topn): the relevance tables of the batch's users (offset to the batch), built on the host.
+struct TopnArgs {
+    const int64_t* rptr;   // [n + 1] relevant CSR: distinct items, item-ascending
+    const int32_t* ritem;
+    const double* rgain;   // graded gain of each relevant item
+    const double* idcg;    // [n][ncut][2] ideal DCG, binary then graded
+    const double* disc;    // [K] d(i) = 1 / log2(i + 2)
+    double* out;           // [n][ncut][6] hits, precision, recall, ap, ndcg, ndcg_graded
+    int ncut;
+    int cut[PCR_TOPN_MAX_CUTOFFS];
+};
+
+// k_rec_merge with the metrics fused into its tail, one wave per user: the merged list goes to the wave's LDS row (K ids; 4 K
+// ints of dynamic LDS per workgroup) and is never written out.  Lanes own contiguous position ranges; each list entry is
+// looked up in the user's relevant row by binary search (its slot replaces the id in LDS, -1 if not relevant); a wave
+// exclusive scan of the lanes' hit counts gives every hit its hits_{<=i}; the per-cutoff sums are reduced by wave_sum's fixed
+// butterfly.
+template <typename T>
+__global__ __launch_bounds__(256) void k_rec_merge_topn(const T* __restrict__ lst_s, const int32_t* __restrict__ lst_i,
+                                                        const int32_t* __restrict__ lst_n, int nsplit, int64_t n, int K, TopnArgs ta) {
+    extern __shared__ int32_t rec_lst[];
+    const int lane = threadIdx.x & 63;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (idx >= n) return;
+    int32_t* sl = rec_lst + (size_t)(threadIdx.x >> 6) * (size_t)K;
+    const int tot = rec_merge_ranks(lst_s, lst_i, lst_n, nsplit, n, K, idx, lane, [&](int rk, int j, T) { sl[rk] = j; });
+    for (int p = min(tot, K) + lane; p < K; p += 64) sl[p] = -1;
+    wave_sync();
+    const int64_t rb = ta.rptr[idx], nr = ta.rptr[idx + 1] - rb;
+    const int32_t* ri = ta.ritem + rb;
+    const int P = (K + 63) >> 6, p0 = min(K, lane * P), p1 = min(K, p0 + P);
+    int h = 0;
+    for (int i = p0; i < p1; ++i) {              // the list entry -> its slot in the relevant row, or -1
+        const int j = sl[i];
+        int f = -1;
+        if (j >= 0) {
+            int64_t a = 0, b = nr;
+            while (a < b) { const int64_t mid = (a + b) >> 1; if (ri[mid] < j) a = mid + 1; else b = mid; }
+            if (a < nr && ri[a] == j) f = (int)a;
+        }
+        sl[i] = f;
+        h += f >= 0 ? 1 : 0;
+    }
+    int ex = h;                                   // inclusive scan of the lanes' hit counts (integers: exact), then exclusive
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(ex, d); if (lane >= d) ex += t; }
+    ex -= h;
+    int hits[PCR_TOPN_MAX_CUTOFFS];
+    double ap[PCR_TOPN_MAX_CUTOFFS], dcg[PCR_TOPN_MAX_CUTOFFS], gdcg[PCR_TOPN_MAX_CUTOFFS];
+#pragma unroll
+    for (int c = 0; c < PCR_TOPN_MAX_CUTOFFS; ++c) { hits[c] = 0; ap[c] = 0.0; dcg[c] = 0.0; gdcg[c] = 0.0; }
+    int cum = ex;
+    for (int i = p0; i < p1; ++i) {
+        const int f = sl[i];
+        if (f < 0) continue;
+        ++cum;
+        const double pr = (double)cum / (double)(i + 1), d = ta.disc[i], gd = ta.rgain[rb + f] * d;
+#pragma unroll
+        for (int c = 0; c < PCR_TOPN_MAX_CUTOFFS; ++c)
+            if (c < ta.ncut && i < ta.cut[c]) { hits[c] += 1; ap[c] += pr; dcg[c] += d; gdcg[c] += gd; }
+    }
+    // lane l < 6 ncut writes field l % 6 of cutoff l / 6: one coalesced row per user
+    double v = 0.0;
+    const int myc = lane / 6, myf = lane - 6 * myc;
+#pragma unroll
+    for (int c = 0; c < PCR_TOPN_MAX_CUTOFFS; ++c) {
+        if (c >= ta.ncut) break;                  // (wave-uniform)
+        const double H = wave_sum((double)hits[c]);   // (an exact integer)
+        const double A = wave_sum(ap[c]), D = wave_sum(dcg[c]), G = wave_sum(gdcg[c]);
+        const double* id = ta.idcg + ((size_t)idx * ta.ncut + c) * 2;
+        const double c_ = (double)ta.cut[c], m = (double)(ta.cut[c] < nr ? (int64_t)ta.cut[c] : nr);
+        if (myc == c) {
+            v = myf == 0 ? H : myf == 1 ? H / c_ : myf == 2 ? H / (double)nr : myf == 3 ? A / m : myf == 4 ? D / id[0]
+              : (id[1] > 0.0 ? G / id[1] : (double)NAN);
+        }
+    }
+    if (lane < 6 * ta.ncut) ta.out[(size_t)idx * 6 * ta.ncut + lane] = v;
+}
+
+// Top-N evaluation's sums over users (fixed order, as k_sum4_stage1 / k_fin4): block x of cutoff y = blockIdx.y sums rows
+// [x per_block, ...) of the per-user table into part[y][x][8] = hits, precision, recall, users with a hit, ap, ndcg,
+// ndcg_graded (defined ones), users with ndcg_graded defined.
+__global__ __launch_bounds__(PCR_EW_BLOCK) void k_topn_sum1(const double* __restrict__ in, int64_t n, int ncut, int per_block,
+                                                            double* __restrict__ part) {
+    __shared__ double red[PCR_EW_BLOCK / PCR_WAVE + 1];
+    const int c = blockIdx.y;
+    const int64_t lo = (int64_t)blockIdx.x * per_block;
+    const int64_t hi = (lo + per_block < n) ? lo + per_block : n;
+    double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int64_t i = lo + threadIdx.x; i < hi; i += PCR_EW_BLOCK) {
+        const double* r = in + ((size_t)i * ncut + c) * 6;
+        a[0] += r[0]; a[1] += r[1]; a[2] += r[2]; a[3] += r[0] > 0.0 ? 1.0 : 0.0; a[4] += r[3]; a[5] += r[4];
+        if (r[5] == r[5]) { a[6] += r[5]; a[7] += 1.0; }
+    }
+#pragma unroll
+    for (int f = 0; f < 8; ++f) {
+        const double s = block_sum<PCR_EW_BLOCK>(a[f], red);
+        if (threadIdx.x == 0) part[((size_t)c * gridDim.x + blockIdx.x) * 8 + f] = s;
+    }
+}
+// one block per cutoff: out[c][8] = the sums of part[c][0..nblk)[8]; out[8 ncut] = n (the counted users of this shard)
+__global__ __launch_bounds__(PCR_EW_BLOCK) void k_topn_fin(const double* __restrict__ part, int nblk, int64_t n, double* __restrict__ out) {
+    __shared__ double red[PCR_EW_BLOCK / PCR_WAVE + 1];
+    const int c = blockIdx.x;
+#pragma unroll
+    for (int f = 0; f < 8; ++f) {
+        double x = 0.0;
+        for (int i = threadIdx.x; i < nblk; i += PCR_EW_BLOCK) x += part[((size_t)c * nblk + i) * 8 + f];
+        x = block_sum<PCR_EW_BLOCK>(x, red);
+        if (threadIdx.x == 0) out[c * 8 + f] = x;
+    }
+    if (c == 0 && threadIdx.x == 0) out[gridDim.x * 8] = (double)n;
 }

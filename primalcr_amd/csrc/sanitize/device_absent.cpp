@@ -70,4 +70,11 @@ int pcr_recommend_model(const double* U, int64_t d1, const double* V, int64_t d2
     return rc != PCR_OK ? rc : absent();
 }
 NO_SOLVER(pcr_recommend, pcr_solver*, int64_t, const int32_t*, int, int, int32_t*, double*)
+int pcr_evaluate_topn_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                            const int64_t* tindex, const int32_t* titem, const double* tval, int ncut, const int* cutoffs, double threshold,
+                            int dtype, pcr_topn_stats* stats, double*, int) {
+    const int rc = pcr_evaluate_topn_model_check(U, d1, V, d2, k, index, item, tindex, titem, tval, ncut, cutoffs, threshold, dtype, stats, nullptr);
+    return rc != PCR_OK ? rc : absent();
+}
+NO_SOLVER(pcr_evaluate_topn, pcr_solver*, int, const int*, double, int, pcr_topn_stats*, double*)
 }
