@@ -337,12 +337,9 @@ struct CcdSolver final : pcr_solver {
     int oiter = 0;                                    // outer iterations run since the start of training
     double secs = 0.0;                                // device seconds of the CCDR1 kernels since the start of training
     hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    std::vector<hipEvent_t> ev_pool;
 
     ~CcdSolver() override {
         if (st) (void)hipStreamSynchronize(st);
-        prof_resolve();
-        for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
         if (ev_a) (void)hipEventDestroy(ev_a);
         if (ev_b) (void)hipEventDestroy(ev_b);
         if (h_ctl) (void)hipHostFree(h_ctl);
@@ -429,54 +426,14 @@ struct CcdSolver final : pcr_solver {
         return PCR_OK;
     }
 
-    // ---- profiling (the same slots and sampling rules as Solver<T>)
-    hipEvent_t ev_get() {
-        if (!ev_pool.empty()) { hipEvent_t e = ev_pool.back(); ev_pool.pop_back(); return e; }
-        hipEvent_t e = nullptr;
-        (void)hipEventCreate(&e);
-        return e;
-    }
-    struct Prof {
-        CcdSolver* s; ProfSlot* slot = nullptr; hipEvent_t a = nullptr, b = nullptr;
-        Prof(CcdSolver* s_, const char* name) : s(s_) {
-            if (!s->prof_on) return;
-            ProfSlot* sl = &s->prof[name];
-            if ((sl->seen++ % s->prof_period) != 0) return;
-            slot = sl;
-            a = s->ev_get(); b = s->ev_get();
-            (void)hipEventRecord(a, s->st);
-        }
-        ~Prof() {
-            if (!slot) return;
-            (void)hipEventRecord(b, s->st);
-            slot->pending.emplace_back(a, b);
-            slot->n += 1;
-        }
-    };
-    void prof_prewarm(int n) override {
-        while ((int)ev_pool.size() < n) { hipEvent_t e = nullptr; if (hipEventCreate(&e) != hipSuccess) break; ev_pool.push_back(e); }
-    }
-    int prof_resolve() override {
-        for (auto& kv : prof) {
-            for (auto& pr : kv.second.pending) {
-                float ms = 0.f;
-                (void)hipEventSynchronize(pr.second);
-                if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) kv.second.ms += ms;
-                ev_pool.push_back(pr.first); ev_pool.push_back(pr.second);
-            }
-            kv.second.pending.clear();
-        }
-        return PCR_OK;
-    }
-
-    // ---- the training loop
+    // ---- the training loop (timed in this solver's own profiler, pcr_solver::prof: the "ccd/..." slots)
     // ccd-r1.cpp:107-118: V = 0, residuals = ratings, reg from U
     int begin() {
         HIPCHK(hipMemcpyAsync(d_res_r.p, h_val_r.data(), (size_t)nnz * sizeof(RT), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_res_c.p, h_val_c.data(), (size_t)nnz * sizeof(RT), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_tres.p, h_tval.data(), (size_t)tn * sizeof(double), hipMemcpyHostToDevice, st));
         {
-            Prof ps(this, "ccd/init");
+            ProfScope ps(&prof, "ccd/init", st);
             hipLaunchKernelGGL((k_ccd_init<T>), dim3(Bi), dim3(ccd::BLOCK), 0, st, base->d_V.p, d2 * ld, (const T*)base->d_U.p, k, ld,
                                (const int64_t*)base->d_uptr.p, d1, d_pregu.p);
             hipLaunchKernelGGL(k_ccd_init_fin, dim3(1), dim3(ccd::BLOCK), 0, st, d_ctl.p, (const double*)d_pregu.p, Bi);
@@ -492,7 +449,7 @@ struct CcdSolver final : pcr_solver {
     int enqueue_rank(int oi, int t) {
         const int T_in = cp.maxinneriter;
         {
-            Prof ps(this, "ccd/begin");
+            ProfScope ps(&prof, "ccd/begin", st);
             const int g = std::max(1, std::min(4096, cdiv(std::max(d1, d2), ccd::BLOCK)));
             hipLaunchKernelGGL((k_ccd_begin<T>), dim3(g), dim3(ccd::BLOCK), 0, st, d_ctl.p, (const T*)base->d_U.p, (const T*)base->d_V.p, ld, t, oi, d1, d2,
                                d_u.p, d_oldu.p, d_v.p, d_oldv.p);
@@ -500,25 +457,25 @@ struct CcdSolver final : pcr_solver {
         for (int iter = 1; iter <= T_in; ++iter) {
             const int addback = (iter == 1 && oi > 1) ? 1 : 0;          // ccd-r1.cpp:127-130, fused into the first sweeps
             {
-                Prof ps(this, "ccd/vsweep");
+                ProfScope ps(&prof, "ccd/vsweep", st);
                 hipLaunchKernelGGL((k_ccd_sweep<RT>), dim3(nvb), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, (const int64_t*)d_cptr.p,
                                    (const int32_t*)d_row_c.p, d_res_c.p, (const double*)d_u.p, (const double*)d_oldu.p, (const double*)d_oldv.p, d_v.p,
                                    (const int32_t*)d_ilong.p, nilong, (const int32_t*)d_ishort.p, nishort, prm.lambda, cp.do_nmf, addback, d_vpart.p);
             }
             {
-                Prof ps(this, "ccd/usweep");
+                ProfScope ps(&prof, "ccd/usweep", st);
                 hipLaunchKernelGGL((k_ccd_sweep<RT>), dim3(nub), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, (const int64_t*)base->d_uptr.p,
                                    (const int32_t*)base->d_item.p, d_res_r.p, (const double*)d_v.p, (const double*)d_oldv.p, (const double*)d_oldu.p, d_u.p,
                                    (const int32_t*)d_ulong.p, nulong, (const int32_t*)d_ushort.p, nushort, prm.lambda, cp.do_nmf, addback, d_upart.p);
             }
             {
-                Prof ps(this, "ccd/decide");
+                ProfScope ps(&prof, "ccd/decide", st);
                 hipLaunchKernelGGL(k_ccd_decide, dim3(1), dim3(ccd::BLOCK), 0, st, d_ctl.p, (const double*)d_vpart.p, nvb, (const double*)d_upart.p, nub,
                                    cp.eps, oi, t, iter);
             }
         }
         {
-            Prof ps(this, "ccd/resid");
+            ProfScope ps(&prof, "ccd/resid", st);
             hipLaunchKernelGGL((k_ccd_resid<T, RT>), dim3(2 * B + Bu + Bv + Bt), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, B, Bu, Bv, Bt, nnz,
                                d1, d2, tn, d_res_r.p, (const int32_t*)d_row_r.p, (const int32_t*)base->d_item.p, d_res_c.p, (const int32_t*)d_row_c.p,
                                (const int32_t*)d_col_c.p, (const int64_t*)base->d_uptr.p, (const int64_t*)d_cptr.p, (const double*)d_u.p,
@@ -527,7 +484,7 @@ struct CcdSolver final : pcr_solver {
                                (T_in < 1 && oi > 1) ? 1 : 0);
         }
         {
-            Prof ps(this, "ccd/final");
+            ProfScope ps(&prof, "ccd/final", st);
             hipLaunchKernelGGL(k_ccd_final, dim3(1), dim3(ccd::BLOCK), 0, st, d_ctl.p, (const double*)d_ploss.p, B, (const double*)d_pregu.p, Bu,
                                (const double*)d_pregv.p, Bv, (const double*)d_prmse.p, Bt, tn, prm.lambda);
         }
@@ -543,6 +500,15 @@ struct CcdSolver final : pcr_solver {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, ev_a, ev_b) != hipSuccess) return 0.0;
         return ms / 1e3;
+    }
+    // outer iteration oi in one go: its k ranks between the timing events, one host round trip; secs += its device time
+    int run_outer(int oi) {
+        HIPCHK(hipEventRecord(ev_a, st));
+        for (int t = 0; t < k; ++t) RC(enqueue_rank(oi, t));
+        HIPCHK(hipEventRecord(ev_b, st));
+        RC(read_ctl());
+        secs += elapsed_s();
+        return PCR_OK;
     }
 
     // ccd-r1.cpp:97-212 ccdr1(): from the current U (V is zeroed); with verbose one line per rank, evaluated after every printed
@@ -562,11 +528,7 @@ struct CcdSolver final : pcr_solver {
         for (int oi = 1; oi <= prm.maxiter; ++oi) {
             oiter = oi;
             if (!logging) {
-                HIPCHK(hipEventRecord(ev_a, st));
-                for (int t = 0; t < k; ++t) RC(enqueue_rank(oi, t));
-                HIPCHK(hipEventRecord(ev_b, st));
-                RC(read_ctl());
-                secs += elapsed_s();
+                RC(run_outer(oi));
             } else {
                 for (int t = 0; t < k; ++t) {
                     HIPCHK(hipEventRecord(ev_a, st));
@@ -599,12 +561,7 @@ struct CcdSolver final : pcr_solver {
         if (n < 0) { pcr_set_error("n must be >= 0"); return PCR_ERR_ARG; }
         if (!begun) RC(begin());
         for (int q = 0; q < n; ++q) {
-            const int oi = ++oiter;
-            HIPCHK(hipEventRecord(ev_a, st));
-            for (int t = 0; t < k; ++t) RC(enqueue_rank(oi, t));
-            HIPCHK(hipEventRecord(ev_b, st));
-            RC(read_ctl());
-            secs += elapsed_s();
+            RC(run_outer(++oiter));
             if (out) {
                 memset(&out[q], 0, sizeof(pcr_iter_stats));
                 out[q].obj = h_ctl->obj; out[q].seconds = secs;
@@ -618,10 +575,10 @@ struct CcdSolver final : pcr_solver {
     int get_factors(double* U, double* V, bool local) override { return base->get_factors(U, V, local); }
     int evaluate(int which, int ndcg_k, double* err, double* ndcg) override { return base->evaluate(which, ndcg_k, err, ndcg); }
     int recommend(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores) override {
-        return base->recommend_with(n, local, K, flags, items, scores, [this](const char* name) { return Prof(this, name); });
+        return base->recommend_with(n, local, K, flags, items, scores, &prof);
     }
     int evaluate_topn(int ncut, const int* cuts, double thr, int flags, pcr_topn_stats* stats, double* per_user) override {
-        return base->evaluate_topn_with(ncut, cuts, thr, flags, stats, per_user, [this](const char* name) { return Prof(this, name); });
+        return base->evaluate_topn_with(ncut, cuts, thr, flags, stats, per_user, &prof);
     }
     int residual_mismatch(double* value) override {
         hipLaunchKernelGGL((k_ccd_mismatch<RT>), dim3(B), dim3(ccd::BLOCK), 0, st, (const RT*)d_res_r.p, (const RT*)d_res_c.p, (const int32_t*)d_c2r.p,
@@ -640,17 +597,6 @@ struct CcdSolver final : pcr_solver {
         cp = *p;
         return PCR_OK;
     }
-    static int not_ccd(const char* what) {
-        pcr_set_error(std::string(what) + ": a PrimalCR / PrimalCR++ entry point; this solver is CCDR1 (solver type 0)");
-        return PCR_ERR_STATE;
-    }
-    int comp_m(double*) override { return not_ccd("pcr_comp_m"); }
-    int objective(double*) override { return not_ccd("pcr_objective"); }
-    int obtain_g(double*) override { return not_ccd("pcr_obtain_g"); }
-    int compute_Ha(const double*, double*) override { return not_ccd("pcr_compute_Ha"); }
-    int solve_delta(const double*, double*, int*) override { return not_ccd("pcr_solve_delta"); }
-    int update_V(double*, int*) override { return not_ccd("pcr_update_V"); }
-    int update_U(double*, int64_t*) override { return not_ccd("pcr_update_U"); }
     int comm_init(const void*) override { pcr_set_error("CCDR1 runs on one rank"); return PCR_ERR_UNSUPPORTED; }
     int comm_init_p2p(const char*) override { pcr_set_error("CCDR1 runs on one rank"); return PCR_ERR_UNSUPPORTED; }
     void comm_abort() override {}

@@ -15,9 +15,11 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <string>
+#include <string_view>
 #include <vector>
 
 #include "pcr_host.h"
@@ -82,17 +84,107 @@ struct DBuf {
     ~DBuf() { free(); }
 };
 
+// Factor matrices cross the boundary as the reference's fp64 row-major payload (mat_t), k values per row; the device keeps rows
+// padded to ld elements of T.  upload_rows converts each {host rows H, row count, device rows D} on the device (k_mat_in) in slabs
+// of at most 64 M values, staged straight from the caller's buffer through one device buffer sized for the longest matrix, and
+// synchronises st after every slab: no host-side staging copy, no serial conversion loop (48 M values at the Netflix shape).
+template <typename T>
+struct HostRows { const double* H; int64_t rows; T* D; };
+template <typename T>
+static int upload_rows(hipStream_t st, int k, int ld, std::initializer_list<HostRows<T>> mats) {
+    const int64_t slab_rows = std::max<int64_t>(1, ((int64_t)64 << 20) / k);
+    int64_t longest = 0;
+    for (const HostRows<T>& m : mats) longest = std::max(longest, m.rows);
+    DBuf<double> stage;
+    RC(stage.alloc((size_t)std::min(longest, slab_rows) * k));
+    for (const HostRows<T>& m : mats)
+        for (int64_t r0 = 0; r0 < m.rows; r0 += slab_rows) {
+            const int64_t nr = std::min(slab_rows, m.rows - r0);
+            HIPCHK(hipMemcpyAsync(stage.p, m.H + r0 * k, (size_t)nr * k * sizeof(double), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL((k_mat_in<T>), dim3((unsigned)std::min<int64_t>(1 << 16, cdiv(nr * ld, 256))), dim3(256), 0, st, stage.p, m.D + r0 * ld, nr, k, ld);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(st));
+        }
+    return PCR_OK;
+}
+
+// ------------------------------------------------------------------------------ profiling (pcr_profile_*)
+struct ProfSlot {
+    int64_t ratings = -1, users = -1;      // what one launch covers (-1: the whole shard)
+    int64_t seen = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+    double ms = 0.0;
+    int64_t n = 0;
+};
+// A solver's named timing slots and the HIP events behind them
+struct Profiler {
+    bool on = false;
+    int period = 1;                       // time every period-th launch of each slot
+    std::map<std::string, ProfSlot> slots;
+    std::vector<hipEvent_t> pool;         // timing events are recycled: creating one per launch costs more than the launch
+    ~Profiler() {
+        for (auto& kv : slots)
+            for (auto& pr : kv.second.pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
+        for (hipEvent_t e : pool) (void)hipEventDestroy(e);
+    }
+    hipEvent_t get() {
+        if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
+        hipEvent_t e = nullptr;
+        (void)hipEventCreate(&e);
+        return e;
+    }
+    void prewarm(int n) {
+        while ((int)pool.size() < n) { hipEvent_t e = nullptr; if (hipEventCreate(&e) != hipSuccess) break; pool.push_back(e); }
+    }
+    // waits for the recorded pairs, adds their times to the slots and returns their events to the pool
+    void resolve() {
+        for (auto& kv : slots) {
+            for (auto& pr : kv.second.pending) {
+                float ms = 0.f;
+                (void)hipEventSynchronize(pr.second);
+                if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) kv.second.ms += ms;
+                pool.push_back(pr.first); pool.push_back(pr.second);
+            }
+            kv.second.pending.clear();
+        }
+    }
+};
+// One launch (or group of launches) of slot `name` on stream q, timed by an event pair when it is sampled.  p NULL: not profiled.
+struct ProfScope {
+    Profiler* p; ProfSlot* slot = nullptr; hipEvent_t a = nullptr, b = nullptr; hipStream_t q;
+    ProfScope(Profiler* p_, std::string_view name, hipStream_t q_, int64_t ratings = -1, int64_t users = -1) : p(p_), q(q_) {
+        if (!p || !p->on) return;
+        ProfSlot* sl = &p->slots[std::string(name)];
+        sl->ratings = ratings; sl->users = users;
+        // sampled: an event pair costs ~3 us of queue time.  Slots launched once per outer iteration (the U-step classes,
+        // the prepares, the fork..join walls) are sampled at least every 4th launch, so that a 20-step run still
+        // averages five of them; the per-CG-iteration kernels every period-th
+        const bool rare = name.compare(0, 5, "ustep") == 0 || name.compare(0, 5, "wall:") == 0 || name.compare(0, 7, "prepare") == 0;
+        const int period = rare ? std::min(p->period, 4) : p->period;
+        if ((sl->seen++ % period) != 0) return;
+        slot = sl;
+        a = p->get(); b = p->get();
+        (void)hipEventRecord(a, q);
+    }
+    ~ProfScope() {
+        if (!slot) return;
+        (void)hipEventRecord(b, q);
+        slot->pending.emplace_back(a, b);
+        slot->n += 1;
+    }
+};
+
 // Top-K recommendation (pcr_topk.h) for the n users h_users[0..n) -- rows of U and of the exclusion CSR xptr / xitem (NULL:
 // none), or rows 0..n-1 when h_users is NULL.  Users go in batches whose partial lists stay under REC_SCRATCH bytes; the item
 // range is split across workgroups until the grid holds about REC_TARGET_WG workgroups (ml1m's 6 040 users are 95 workgroups
 // of 64).  Each batch's partial lists go to the sink: sink.begin(nb) once with the largest batch, then sink.batch(b0, m, ...)
-// per batch, which merges them (RecCopy: into pcr_recommend's host arrays; RecTopn: into the top-N metrics).  scope(name)
-// returns the profiler's RAII scope.  select = 0 only for tools/exp_recommend.py's GEMM-alone timing (lists come back empty).
+// per batch, which merges them (RecCopy: into pcr_recommend's host arrays; RecTopn: into the top-N metrics).  The launches
+// are timed in prof's "recommend/..." slots (NULL: not profiled).  select = 0 only for tools/exp_recommend.py's GEMM-alone timing (lists come back empty).
 static const size_t REC_SCRATCH = (size_t)1 << 30;
 static const int REC_TARGET_WG = 1024, REC_MAX_SPLIT = 16, REC_MIN_SPLIT_ITEMS = 1024;
-template <typename T, class Scope, class Sink>
+template <typename T, class Sink>
 static int rec_run(hipStream_t st, const T* U, const T* V, int r, int ld, int64_t d2, const int64_t* xptr, const int32_t* xitem,
-                   int64_t n, const int32_t* h_users, int K, int select, Scope&& scope, Sink&& sink) {
+                   int64_t n, const int32_t* h_users, int K, int select, Profiler* prof, Sink&& sink) {
     if (n <= 0) return PCR_OK;
     const size_t per_user = (size_t)K * (sizeof(T) + sizeof(int32_t)) + sizeof(int32_t);
     const int64_t users_per_wg = (int64_t)rec::WAVES * rec::UW;
@@ -120,13 +212,12 @@ static int rec_run(hipStream_t st, const T* U, const T* V, int r, int ld, int64_
         const int per = (int)(((d2 + ns - 1) / ns + rec::TILE - 1) / rec::TILE * rec::TILE);
         const int nsp = (int)((d2 + per - 1) / per);
         {
-            auto sc = scope("recommend/score");
-            (void)sc;
+            ProfScope ps(prof, "recommend/score", st);
             hipLaunchKernelGGL((k_rec_score<T>), dim3((unsigned)cdiv(m, users_per_wg), (unsigned)nsp), dim3(rec::WAVES * 64), lds, st, U, V, r, ld,
                                (int)d2, du.p, m, xptr, xitem, K, per, ls.p, li.p, ln.p, select);
             HIPCHK(hipGetLastError());
         }
-        RC(sink.batch(b0, m, (const T*)ls.p, (const int32_t*)li.p, (const int32_t*)ln.p, nsp, scope));
+        RC(sink.batch(b0, m, (const T*)ls.p, (const int32_t*)li.p, (const int32_t*)ln.p, nsp, prof));
         HIPCHK(hipStreamSynchronize(st));                  // (the next batch's users overwrite du / seq)
     }
     return PCR_OK;
@@ -143,11 +234,9 @@ struct RecCopy {
     DBuf<double> os;
     RecCopy(hipStream_t st_, int K_, int32_t* items_, double* scores_) : st(st_), K(K_), items(items_), scores(scores_) {}
     int begin(int64_t nb) { RC(oi.alloc((size_t)nb * K)); RC(os.alloc((size_t)nb * K)); return PCR_OK; }
-    template <class Scope>
-    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp, Scope& scope) {
+    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp, Profiler* prof) {
         {
-            auto sc = scope("recommend/merge");
-            (void)sc;
+            ProfScope ps(prof, "recommend/merge", st);
             hipLaunchKernelGGL((k_rec_merge<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), 0, st, ls, li, ln, nsp, m, K, oi.p, os.p);
             HIPCHK(hipGetLastError());
         }
@@ -185,19 +274,27 @@ struct TopnDev {
         valid = true;
         return PCR_OK;
     }
-    // the fixed-order sums over the counted users into sums (k_sum4_stage1 / k_fin4's two stages, one block row per cutoff)
-    int reduce(hipStream_t st) {
-        const int64_t n = (int64_t)rel.users.size();
-        const int nb = (int)std::min<int64_t>(512, std::max<int64_t>(1, cdiv(n, 2048)));
-        const int per = cdiv(std::max<int64_t>(n, 1), nb);
-        if (part.n < (size_t)nb * ncut * 8) RC(part.alloc((size_t)nb * ncut * 8));
-        hipLaunchKernelGGL(k_topn_sum1, dim3(nb, ncut), dim3(PCR_EW_BLOCK), 0, st, (const double*)met.p, n, ncut, per, part.p);
-        hipLaunchKernelGGL(k_topn_fin, dim3(ncut), dim3(PCR_EW_BLOCK), 0, st, (const double*)part.p, nb, n, sums.p);
-        HIPCHK(hipGetLastError());
-        return PCR_OK;
-    }
-    // per_user[rows][ncut][6]: NaN, then the counted users' rows
-    int fetch_per_user(hipStream_t st, int64_t rows, double* per_user) {
+    // The end of an evaluation, after rec_run: the fixed-order sums over the counted users into sums (k_sum4_stage1 / k_fin4's
+    // two stages, one block row per cutoff; timed in prof's "recommend/metrics"), combined across ranks by combine(sums, count),
+    // read back into stats once wait() has synchronised st; with per_user, per_user[rows][ncut][6]: NaN, then the counted users' rows
+    template <class Combine, class Wait>
+    int finish(hipStream_t st, Profiler* prof, Combine&& combine, Wait&& wait, pcr_topn_stats* stats, int64_t rows, double* per_user) {
+        {
+            ProfScope ps(prof, "recommend/metrics", st);
+            const int64_t n = (int64_t)rel.users.size();
+            const int nb = (int)std::min<int64_t>(512, std::max<int64_t>(1, cdiv(n, 2048)));
+            const int per = cdiv(std::max<int64_t>(n, 1), nb);
+            if (part.n < (size_t)nb * ncut * 8) RC(part.alloc((size_t)nb * ncut * 8));
+            hipLaunchKernelGGL(k_topn_sum1, dim3(nb, ncut), dim3(PCR_EW_BLOCK), 0, st, (const double*)met.p, n, ncut, per, part.p);
+            hipLaunchKernelGGL(k_topn_fin, dim3(ncut), dim3(PCR_EW_BLOCK), 0, st, (const double*)part.p, nb, n, sums.p);
+            HIPCHK(hipGetLastError());
+        }
+        RC(combine(sums.p, (size_t)ncut * 8 + 1));
+        std::vector<double> hs((size_t)ncut * 8 + 1);
+        HIPCHK(hipMemcpyAsync(hs.data(), sums.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        RC(wait());
+        pcr_topn_stats_from(hs.data(), ncut, cut, stats);
+        if (!per_user) return PCR_OK;
         const size_t w = (size_t)ncut * 6;
         std::vector<double> h(rel.users.size() * w);
         if (!h.empty()) HIPCHK(hipMemcpyAsync(h.data(), met.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -216,14 +313,12 @@ struct RecTopn {
     TopnDev& d;
     RecTopn(hipStream_t st_, int K_, TopnDev& d_) : st(st_), K(K_), d(d_) {}
     int begin(int64_t) { return PCR_OK; }
-    template <class Scope>
-    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp, Scope& scope) {
+    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp, Profiler* prof) {
         TopnArgs ta;
         ta.rptr = d.rptr.p + b0; ta.ritem = d.ritem.p; ta.rgain = d.rgain.p; ta.idcg = d.idcg.p + (size_t)b0 * d.ncut * 2;
         ta.disc = d.disc.p; ta.out = d.met.p + (size_t)b0 * d.ncut * 6; ta.ncut = d.ncut;
         for (int c = 0; c < PCR_TOPN_MAX_CUTOFFS; ++c) ta.cut[c] = c < d.ncut ? d.cut[c] : 0;
-        auto sc = scope("recommend/metrics");
-        (void)sc;
+        ProfScope ps(prof, "recommend/metrics", st);
         hipLaunchKernelGGL((k_rec_merge_topn<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), (size_t)4 * K * sizeof(int32_t), st, ls, li, ln, nsp, m, K, ta);
         HIPCHK(hipGetLastError());
         return PCR_OK;
@@ -256,25 +351,22 @@ static const int BIN_LIMIT[3] = {128, 512, 4096};
 static const int BIN_BLOCK[4] = {64, 256, 512, 512};
 static const int GRAM_DEFAULT_CAP = 0;       // default length bound of the dual-form U-step class (0: off; pcr_tune "ustep_gram")
 
-struct ProfSlot {
-    int64_t ratings = -1, users = -1;      // what one launch covers (-1: the whole shard)
-    int64_t seen = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-    double ms = 0.0;
-    int64_t n = 0;
-};
-
 struct pcr_solver {
     virtual ~pcr_solver() {}
     virtual int set_factors(const double* U, const double* V, bool local) = 0;
     virtual int get_factors(double* U, double* V, bool local) = 0;
-    virtual int comp_m(double* m_out) = 0;
-    virtual int objective(double* obj) = 0;
-    virtual int obtain_g(double* g) = 0;
-    virtual int compute_Ha(const double* a, double* Ha) = 0;
-    virtual int solve_delta(const double* g, double* delta, int* iters) = 0;
-    virtual int update_V(double* now_obj, int* info) = 0;
-    virtual int update_U(double* now_obj, int64_t* info) = 0;
+    // PrimalCR / PrimalCR++ only (Solver<T>)
+    static int pcr_only(const char* what) {
+        pcr_set_error(std::string(what) + ": a PrimalCR / PrimalCR++ entry point; this solver is CCDR1 (solver type 0)");
+        return PCR_ERR_STATE;
+    }
+    virtual int comp_m(double*) { return pcr_only("pcr_comp_m"); }
+    virtual int objective(double*) { return pcr_only("pcr_objective"); }
+    virtual int obtain_g(double*) { return pcr_only("pcr_obtain_g"); }
+    virtual int compute_Ha(const double*, double*) { return pcr_only("pcr_compute_Ha"); }
+    virtual int solve_delta(const double*, double*, int*) { return pcr_only("pcr_solve_delta"); }
+    virtual int update_V(double*, int*) { return pcr_only("pcr_update_V"); }
+    virtual int update_U(double*, int64_t*) { return pcr_only("pcr_update_U"); }
     virtual int evaluate(int which, int ndcg_k, double* err, double* ndcg) = 0;
     virtual int train(pcr_log_fn log, void* ctx, pcr_iter_stats* hist) = 0;
     virtual int iterate_abi(int n, pcr_iter_stats* out) = 0;
@@ -287,13 +379,9 @@ struct pcr_solver {
     virtual int class_rows(const std::string& slot, double* v) = 0; // rows of V that class has gathered so far (pcr_tune "count_rows")
     int64_t first_user = 0, n_users = 0, nnz_local = 0;
     double ustep_rows = 0.0;      // rows of V gathered by all U steps so far (all ranks); pcr_solver_counter("ustep_row_gathers")
-    bool prof_on = false;
     bool local_only = false;      // nranks > 1 without a communicator: entry points return this shard's partials
-    int prof_period = 1;          // time every prof_period-th launch of each slot
-    std::map<std::string, ProfSlot> prof;
+    Profiler prof;
     std::vector<std::pair<std::string, double>> setup_ms;   // wall time of the phases of pcr_solver_create, in order (pcr_solver_counter "setup_ms/<i>", pcr_solver_setup_phase)
-    virtual int prof_resolve() = 0;
-    virtual void prof_prewarm(int n) = 0;
     // CCDR1 only (pcr_ccd.h): the "ccd_residual_mismatch" counter, pcr_solver_set_ccd_params
     virtual int residual_mismatch(double*) { pcr_set_error("pcr_solver_counter: 'ccd_residual_mismatch' exists on a CCDR1 solver only"); return PCR_ERR_STATE; }
     virtual int set_ccd_params(const pcr_ccd_params*) { pcr_set_error("pcr_solver_set_ccd_params: not a CCDR1 solver (solver type 0)"); return PCR_ERR_STATE; }
@@ -481,8 +569,6 @@ struct Solver final : pcr_solver {
             }
         }
 #endif
-        prof_resolve();
-        for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
         if (ar_st) { (void)hipStreamSynchronize(ar_st); (void)hipStreamDestroy(ar_st); }
         for (hipEvent_t e : ev_rng) (void)hipEventDestroy(e);
         if (ev_ar) (void)hipEventDestroy(ev_ar);
@@ -498,54 +584,6 @@ struct Solver final : pcr_solver {
         for (hipStream_t x : hi_spare) (void)hipStreamDestroy(x);
         if (ev_hi) (void)hipEventDestroy(ev_hi);
         if (st) (void)hipStreamDestroy(st);
-    }
-
-    // ------------------------------------------------------------------------------ profiling
-    struct ProfScope {
-        Solver* s; ProfSlot* slot = nullptr; hipEvent_t a = nullptr, b = nullptr; hipStream_t q;
-        ProfScope(Solver* s_, const std::string& name, hipStream_t q_ = nullptr, int64_t ratings = -1, int64_t users = -1)
-            : s(s_), q(q_ ? q_ : s_->st) {
-            if (!s->prof_on) return;
-            ProfSlot* sl = &s->prof[name];
-            sl->ratings = ratings; sl->users = users;
-            // sampled: an event pair costs ~3 us of queue time.  Slots launched once per outer iteration (the U-step classes,
-            // the prepares, the fork..join walls) are sampled at least every 4th launch, so that a 20-step run still
-            // averages five of them; the per-CG-iteration kernels every prof_period-th
-            const bool rare = name.compare(0, 5, "ustep") == 0 || name.compare(0, 5, "wall:") == 0 || name.compare(0, 7, "prepare") == 0;
-            const int period = rare ? std::min(s->prof_period, 4) : s->prof_period;
-            if ((sl->seen++ % period) != 0) return;
-            slot = sl;
-            a = s->ev_get(); b = s->ev_get();
-            (void)hipEventRecord(a, q);
-        }
-        ~ProfScope() {
-            if (!slot) return;
-            (void)hipEventRecord(b, q);
-            slot->pending.emplace_back(a, b);
-            slot->n += 1;
-        }
-    };
-    std::vector<hipEvent_t> ev_pool;      // timing events are recycled: creating one per launch costs more than the launch
-    hipEvent_t ev_get() {
-        if (!ev_pool.empty()) { hipEvent_t e = ev_pool.back(); ev_pool.pop_back(); return e; }
-        hipEvent_t e = nullptr;
-        (void)hipEventCreate(&e);
-        return e;
-    }
-    void prof_prewarm(int n) override {
-        while ((int)ev_pool.size() < n) { hipEvent_t e = nullptr; if (hipEventCreate(&e) != hipSuccess) break; ev_pool.push_back(e); }
-    }
-    int prof_resolve() override {
-        for (auto& kv : prof) {
-            for (auto& pr : kv.second.pending) {
-                float ms = 0.f;
-                (void)hipEventSynchronize(pr.second);
-                if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) kv.second.ms += ms;
-                ev_pool.push_back(pr.first); ev_pool.push_back(pr.second);
-            }
-            kv.second.pending.clear();
-        }
-        return PCR_OK;
     }
 
     // does work on stream b wait for work on stream a (same hardware queue)?
@@ -568,7 +606,7 @@ struct Solver final : pcr_solver {
     // per kernel on a shared pipe, 14.9 -> 14.9 otherwise; in the solver's own layout the third side lane reads 14.9 -> 17.9.
     int shares_pipe(hipStream_t busy, hipStream_t other, long long spin_ticks, double* base_us, bool* out) {
         constexpr int N = 12;
-        hipEvent_t e0 = ev_get(), e1 = ev_get();
+        hipEvent_t e0 = prof.get(), e1 = prof.get();
         auto chain = [&](double* us) -> int {
             HIPCHK(hipEventRecord(e0, busy));
             for (int i = 0; i < N; ++i) hipLaunchKernelGGL(k_nop, dim3(65536), dim3(64), 0, busy);
@@ -588,7 +626,7 @@ struct Solver final : pcr_solver {
             HIPCHK(hipStreamSynchronize(other));
             with = std::min(with, w);
         }
-        ev_pool.push_back(e0); ev_pool.push_back(e1);
+        prof.pool.push_back(e0); prof.pool.push_back(e1);
         *out = with > 1.1 * *base_us;                              // (a queue on another pipe reproduces the base figure to 0.1 us)
         if (tune.debug) fprintf(stderr, "[pcr] pipe probe: %.1f us per kernel alone, %.1f with the other queue held -> %s\n", *base_us, with, *out ? "SAME pipe" : "separate pipes");
         return PCR_OK;
@@ -1376,7 +1414,7 @@ struct Solver final : pcr_solver {
         if (main_bin < 0) return PCR_OK;
         // wall time of the whole concurrent group on the solver's stream (fork .. join): the per-bin slots
         // overlap, so their sum overstates the group's share of the timed region
-        ProfScope wall(this, std::string("wall:") + cls, st);
+        ProfScope wall(&prof, std::string("wall:") + cls, st);
         bool forked = false;
         // longest users first: their workgroups are the critical path and must not queue behind the many
         // short-user workgroups
@@ -1391,10 +1429,10 @@ struct Solver final : pcr_solver {
             if (l > 0 && !forked) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipEventRecord(ev_fork, st)); forked = true; }
             if (l > 0 && !used[l]) HIPCHK(hipStreamWaitEvent(lane[l], ev_fork, 0));
             used[l] = true;
-            ProfScope ps(this, pname(cls, bs[i]), lane[l], bs[i].nnz, (int64_t)bs[i].users.size());
+            ProfScope ps(&prof, pname(cls, bs[i]), lane[l], bs[i].nnz, (int64_t)bs[i].users.size());
             launch(bs[i], lane[l]);
         }
-        { ProfScope ps(this, pname(cls, bs[main_bin]), st, bs[main_bin].nnz, (int64_t)bs[main_bin].users.size()); launch(bs[main_bin], st); }
+        { ProfScope ps(&prof, pname(cls, bs[main_bin]), st, bs[main_bin].nnz, (int64_t)bs[main_bin].users.size()); launch(bs[main_bin], st); }
         for (int l = 1; l < nlane; ++l)
             if (used[l]) { HIPCHK(hipEventRecord(ev_lane[l], lane[l])); RC(join(ev_lane[l])); }
         HIPCHK(hipGetLastError());
@@ -1452,7 +1490,7 @@ struct Solver final : pcr_solver {
         // running on a side stream once st has drained.  Anything that ever launches asynchronously on a lane without joining
         // it into st must record / wait ev_fork here unconditionally.
         const bool idle = hipStreamQuery(st) == hipSuccess;
-        ProfScope wall(this, "wall:ustep", st);
+        ProfScope wall(&prof, "wall:ustep", st);
         bool used[MAXLANE + 1] = {};
         if (!idle) HIPCHK(hipEventRecord(ev_fork, st));
         for (auto& pr : plan) {
@@ -1460,7 +1498,7 @@ struct Solver final : pcr_solver {
             hipStream_t q = pr.second == MAXLANE ? hi : lane[pr.second];
             if (!idle && q != st && !used[pr.second]) HIPCHK(hipStreamWaitEvent(q, ev_fork, 0));
             used[pr.second] = true;
-            ProfScope ps(this, pname("ustep", b), q, b.nnz, (int64_t)b.users.size());
+            ProfScope ps(&prof, pname("ustep", b), q, b.nnz, (int64_t)b.users.size());
             launch(b, q);
         }
         for (int l = 1; l < nlane; ++l)
@@ -1475,7 +1513,7 @@ struct Solver final : pcr_solver {
     int for_bins_seq(std::vector<Bin>& bs, const char* cls, F launch) {
         for (auto& b : bs) {
             if (b.users.empty()) continue;
-            ProfScope ps(this, pname(cls, b), st, b.nnz, (int64_t)b.users.size());
+            ProfScope ps(&prof, pname(cls, b), st, b.nnz, (int64_t)b.users.size());
             launch(b, st);
         }
         HIPCHK(hipGetLastError());
@@ -1518,7 +1556,7 @@ struct Solver final : pcr_solver {
     // out[z] = U[user(z)] . M[rows[z]] for all local ratings (rating-parallel, balanced)
     int launch_sddmm(const T* M, const int32_t* rows, T* out, const int* skip = nullptr) {
         if (nnz_local == 0) return PCR_OK;
-        ProfScope ps(this, "sddmm");
+        ProfScope ps(&prof, "sddmm", st);
         const T* Umat = d_U.p;
         // tile = consecutive ratings one lane group walks.  64 by default; a shard that needs between one and two rounds of
         // workgroups at 64 gets the smallest tile (a multiple of the 8-row batch) with which ONE round holds it all
@@ -1545,7 +1583,7 @@ struct Solver final : pcr_solver {
     bool sddmm_by_tiles() const { return sddmm_csc; }
     int launch_sddmm_csc(const T* A, T* out, const int* skip) {
         if (nnz_local == 0) return PCR_OK;
-        ProfScope ps(this, "sddmm");
+        ProfScope ps(&prof, "sddmm", st);
         const int span = (256 / geo.G) * spmm_chunk;
         hipLaunchKernelGGL((k_sddmm<T, 256>), dim3(spmm_blocks), dim3(256), (size_t)span * 8, st, A, d_U.p, d_crow.p, d_cuser.p, nnz_local, out, geo,
                            spmm_chunk, skip, d_c2r.p, d_blk_chunks.p, d_chunk_ptr.p);
@@ -1586,11 +1624,11 @@ struct Solver final : pcr_solver {
             const int wbs = 512, wpb = wbs / 64;
             const size_t lds = std::max(wb * wpb, small_common(wbs) + prepare_bytes<T>(bb.cap, cpb, rsb, 4));
             {
-                ProfScope ps(this, "prepare/all", st, ba.nnz + bb.nnz, (int64_t)(na + nb));
+                ProfScope ps(&prof, "prepare/all", st, ba.nnz + bb.nnz, (int64_t)(na + nb));
                 hipLaunchKernelGGL((k_prepare_all<T, 512>), dim3(nb + cdiv(na, wpb)), dim3(512), lds, st, shp, ba.d_users.p, na, ba.cap, cpa, rsa, wb,
                                    bb.d_users.p, nb, bb.cap, cpb, rsb, nb, d_mcsr.p, strict());
             }
-            if (!pbins[2].users.empty()) { ProfScope ps(this, pname("prepare", pbins[2]), st, pbins[2].nnz, (int64_t)pbins[2].users.size()); fn(pbins[2], st); }
+            if (!pbins[2].users.empty()) { ProfScope ps(&prof, pname("prepare", pbins[2]), st, pbins[2].nnz, (int64_t)pbins[2].users.size()); fn(pbins[2], st); }
             HIPCHK(hipGetLastError());
             have_sorted = true;
             sh.prev_valid = 1;
@@ -1607,7 +1645,7 @@ struct Solver final : pcr_solver {
         // the CSC walk (item tables beyond the L2s) leaves it in CSR order and the sweep picks it up through sidx
         if (hv) { if (sddmm_by_tiles()) RC(launch_sddmm_csc(A, d_b.p, skip)); else RC(launch_sddmm(A, d_sitem.p, d_b.p, skip)); }
         if (hv && vblock_nbp) {                                   // the block's share of b = U A^T on the matrix cores (pcr_vblock.h)
-            ProfScope ps(this, "vblock_b");
+            ProfScope ps(&prof, "vblock_b", st);
             const int64_t tiles = (int64_t)(vblock_nbp / GramMfma<T>::TS) * cdiv(d2, GramMfma<T>::TS);
 #ifndef PCR_NO_OPTIONAL_KERNELS
             hipLaunchKernelGGL((k_vblock_b<T>), dim3((unsigned)cdiv(tiles, 4)), dim3(256), 0, st, d_U.p, A, d_blk_user.p, vblock_nbp, d_cpos_dense.p, d2, geo, d_b.p, skip);
@@ -1647,7 +1685,7 @@ struct Solver final : pcr_solver {
             const size_t lds = std::max(wb * wpb, small_common(wbs) + vsweep_bytes<T>(bb.cap, rsb, two));
             const int grid = nb + cdiv(na, wpb);
             {
-                ProfScope ps(this, std::string(hv ? "vhv" : "vgrad") + "/all", st, ba.nnz + bb.nnz, (int64_t)(na + nb));
+                ProfScope ps(&prof, std::string(hv ? "vhv" : "vgrad") + "/all", st, ba.nnz + bb.nnz, (int64_t)(na + nb));
 #define LVA(HV, WBS, MW) hipLaunchKernelGGL((k_vsweep_all<T, HV, WBS, MW>), dim3(grid), dim3(WBS), lds, st, sh, ba.d_users.p, na, ba.cap, rsa, wb, \
                                         bb.d_users.p, nb, bb.cap, rsb, nb, d_b.p, d_c.p, strict(), skip, bc)
                 // (four workgroups per CU where the longest user's arrays fit a quarter of the LDS: the 64-VGPR symbol)
@@ -1655,7 +1693,7 @@ struct Solver final : pcr_solver {
                 if (hv) { if (dense) LVA(true, 512, 8); else LVA(true, 512, 1); } else { if (dense) LVA(false, 512, 8); else LVA(false, 512, 1); }
 #undef LVA
             }
-            if (!sbins[2].users.empty()) { ProfScope ps(this, pname(hv ? "vhv" : "vgrad", sbins[2]), st, sbins[2].nnz, (int64_t)sbins[2].users.size()); fn(sbins[2], st); }
+            if (!sbins[2].users.empty()) { ProfScope ps(&prof, pname(hv ? "vhv" : "vgrad", sbins[2]), st, sbins[2].nnz, (int64_t)sbins[2].users.size()); fn(sbins[2], st); }
             HIPCHK(hipGetLastError());
             return PCR_OK;
         }
@@ -1669,14 +1707,14 @@ struct Solver final : pcr_solver {
     // one item range of the SpMM: k_spmm over the range's workgroups, k_spmm_fin over its items
     int launch_spmm_range(int r, T* out, const T* base, double beta, const int* skip, const T* dots_rr) {
         if (nnz_local > 0 && rng_blk[r + 1] > rng_blk[r]) {
-            ProfScope ps(this, "spmm");
+            ProfScope ps(&prof, "spmm", st);
             hipLaunchKernelGGL((k_spmm<T, 256>), dim3(rng_blk[r + 1] - rng_blk[r]), dim3(256), 0, st, d_c.p, d_c2r.p, d_cuf.p,
                                d_chunk_ptr.p, d_slot_base.p, d_slot_id.p, d_blk_chunks.p + rng_blk[r], d_U.p, d_slab.p, geo, skip);
         }
         const int j0 = (int)rng_item[r], j1 = (int)rng_item[r + 1];
         if (j1 <= j0) return PCR_OK;
         const int grid = n_rng == 1 ? fin_blocks() : (int)std::min<int64_t>(1024, cdiv(j1 - j0, 256 / geo.G));
-        ProfScope ps2(this, "spmm_fin");
+        ProfScope ps2(&prof, "spmm_fin", st);
         if (dots_rr) hipLaunchKernelGGL((k_spmm_fin<T, 256, true>), dim3(grid), dim3(256), 0, st, d_slab.p, d_item_slot.p, base, beta, j1, out, geo, skip, dots_rr, d_partA.p, j0);
         else hipLaunchKernelGGL((k_spmm_fin<T, 256, false>), dim3(grid), dim3(256), 0, st, d_slab.p, d_item_slot.p, base, beta, j1, out, geo, skip, (const T*)nullptr, (double*)nullptr, j0);
         return PCR_OK;
@@ -1690,7 +1728,7 @@ struct Solver final : pcr_solver {
         if (n_rng == 1) {
             RC(launch_spmm_range(0, out, base, beta, skip, dots_rr));
             if (vblock_nbp) {                                     // + the block's share, C_B^T U_B on the matrix cores, before the exchange
-                ProfScope ps(this, "vblock_hp");
+                ProfScope ps(&prof, "vblock_hp", st);
                 const int64_t tiles = (int64_t)cdiv(d2, GramMfma<T>::TS) * cdiv(geo.ld, GramMfma<T>::TS);
 #ifndef PCR_NO_OPTIONAL_KERNELS
                 hipLaunchKernelGGL((k_vblock_hp<T>), dim3((unsigned)cdiv(tiles, 4)), dim3(256), 0, st, d_U.p, d_c.p, d_blk_user.p, vblock_nbp, d_cpos_dense.p, d2, geo, out, skip);
@@ -1722,7 +1760,7 @@ struct Solver final : pcr_solver {
         if (single()) return PCR_OK;
         if (!comm && !p2p) { pcr_set_error("nranks > 1 but neither pcr_solver_comm_init nor pcr_solver_comm_init_p2p was called"); return PCR_ERR_STATE; }
         if (!q) q = st;
-        ProfScope ps(this, "allreduce", q);
+        ProfScope ps(&prof, "allreduce", q);
         if (p2p) {
             if (!p2p->allreduce<T>(buf, count, q)) { pcr_set_error("p2p all-reduce: " + p2p->err); return PCR_ERR_COMM; }
             return PCR_OK;
@@ -1733,7 +1771,7 @@ struct Solver final : pcr_solver {
     int allreduce_f64(double* buf, size_t count) {
         if (single()) return PCR_OK;
         if (!comm && !p2p) { pcr_set_error("nranks > 1 but neither pcr_solver_comm_init nor pcr_solver_comm_init_p2p was called"); return PCR_ERR_STATE; }
-        ProfScope ps(this, "allreduce");
+        ProfScope ps(&prof, "allreduce", st);
         if (p2p) {
             if (!p2p->allreduce<double>(buf, count, st, true)) { pcr_set_error("p2p all-reduce: " + p2p->err); return PCR_ERR_COMM; }
             return PCR_OK;
@@ -1802,22 +1840,8 @@ struct Solver final : pcr_solver {
     }
 
     // ------------------------------------------------------------------------------ host <-> device
-    // Factor matrices cross the boundary as the reference's fp64 row-major payload (mat_t); the device keeps rows padded to ld
-    // elements of T.  The conversion runs on the device (k_mat_in / k_mat_out) on slabs of at most 64 M values, straight from / into
-    // the caller's buffer: no host-side staging copy, no serial conversion loop (48 M values at the Netflix shape).
-    int upload_mat(const double* H, int64_t rows, T* D) {
-        const int64_t slab_rows = std::max<int64_t>(1, ((int64_t)64 << 20) / std::max(1, geo.r));
-        DBuf<double> stage;
-        RC(stage.alloc((size_t)std::min(rows, slab_rows) * geo.r));
-        for (int64_t r0 = 0; r0 < rows; r0 += slab_rows) {
-            const int64_t nr = std::min(slab_rows, rows - r0);
-            HIPCHK(hipMemcpyAsync(stage.p, H + r0 * geo.r, (size_t)nr * geo.r * sizeof(double), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL((k_mat_in<T>), dim3((unsigned)std::min<int64_t>(1 << 16, cdiv(nr * geo.ld, 256))), dim3(256), 0, st, stage.p, D + r0 * geo.ld, nr, geo.r, geo.ld);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(st));
-        }
-        return PCR_OK;
-    }
+    // fp64 rows to and from the padded T rows (upload_rows; the way back mirrors it with k_mat_out)
+    int upload_mat(const double* H, int64_t rows, T* D) { return upload_rows<T>(st, geo.r, geo.ld, {{H, rows, D}}); }
     int download_mat(const T* D, int64_t rows, double* H) {
         const int64_t slab_rows = std::max<int64_t>(1, ((int64_t)64 << 20) / std::max(1, geo.r));
         DBuf<double> stage;
@@ -1988,7 +2012,7 @@ struct Solver final : pcr_solver {
     int device_cg(int* iters) {
         const int64_t n = (int64_t)d2 * geo.ld;
         {
-            ProfScope ps(this, "cg");
+            ProfScope ps(&prof, "cg", st);
             hipLaunchKernelGGL((k_cg_init<T>), dim3(ew_blocks), dim3(PCR_EW_BLOCK), 0, st, d_g.p, d_delta.p, d_rr.p, d_p.p, n, ew_per_block, d_partA.p);
             hipLaunchKernelGGL(k_cg_init_fin, dim3(1), dim3(PCR_EW_BLOCK), 0, st, d_partA.p, ew_blocks, d_cgp, prm.cg_tol);
         }
@@ -2002,7 +2026,7 @@ struct Solver final : pcr_solver {
         for (int k = 1; k <= prm.cg_max_iter; ++k) {
             RC(device_hv(d_p.p, d_Hp.p, skip, fused_dots ? d_rr.p : nullptr));
             {
-                ProfScope ps(this, "cg");
+                ProfScope ps(&prof, "cg", st);
                 if (!fused_dots) hipLaunchKernelGGL((k_cg_a<T>), dim3(ew_blocks), dim3(PCR_EW_BLOCK), 0, st, d_p.p, d_Hp.p, d_rr.p, n, ew_per_block, d_partA.p, d_cgp);
                 if (exact_rr) {
                     hipLaunchKernelGGL((k_cg_bc<T, true>), dim3(ew_blocks), dim3(PCR_EW_BLOCK), 0, st, d_p.p, d_Hp.p, d_rr.p, d_delta.p, n, ew_per_block, fused_dots ? fin_blocks() : ew_blocks, d_partA.p, d_cgp, k, d_partB.p);
@@ -2096,7 +2120,7 @@ struct Solver final : pcr_solver {
             HIPCHK(hipMemsetAsync(d_dir.p, 0xFF, d_dir.n * sizeof(double), st));          // all ones = NaN: "no direction"
             if (newton_n > 0) {
                 const int ldp = (geo.ld + 15) & ~15;
-                ProfScope ps(this, "unewton", st, -1, newton_n);
+                ProfScope ps(&prof, "unewton", st, -1, newton_n);
                 // (the window bounds ride along where the workgroup still fits half a CU's LDS: two workgroups per CU matter more)
                 const int wbcap = newton_bytes<T>(newton_cap, newton_rs, geo.ld, ldp, newton_cap) <= (size_t)80 * 1024 ? newton_cap : 0;
                 const size_t lds = newton_bytes<T>(newton_cap, newton_rs, geo.ld, ldp, wbcap);
@@ -2452,40 +2476,30 @@ struct Solver final : pcr_solver {
 
     // top-K recommendation from the device factors (pcr_topk.h); reads U, V and the shard's CSR (item-ascending per user: the
     // data set's CSR as uploaded, never permuted -- the (level, m) sorts write their own arrays), writes nothing of the solver
-    template <class Scope>
-    int recommend_with(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores, Scope&& scope) {
+    // The launches are timed in prof: this solver's own, or that of the CCDR1 solver that holds this one.
+    int recommend_with(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores, Profiler* prof) {
         const bool ex = (flags & PCR_REC_EXCLUDE_TRAIN) != 0;
         return rec_run<T>(st, d_U.p, d_V.p, geo.r, geo.ld, d2, ex ? d_uptr.p : nullptr, ex ? d_item.p : nullptr, n, local, K,
-                          tune.recommend_select, scope, RecCopy<T>(st, K, items, scores));
+                          tune.recommend_select, prof, RecCopy<T>(st, K, items, scores));
     }
     // full-catalogue top-N evaluation of the shard's users against its test ratings (h_test_*, kept at creation); the relevance
     // tables are built on the first call for a (threshold, cutoffs) and kept in topn
-    template <class Scope>
-    int evaluate_topn_with(int ncut, const int* cuts, double thr, int flags, pcr_topn_stats* stats, double* per_user, Scope&& scope) {
+    int evaluate_topn_with(int ncut, const int* cuts, double thr, int flags, pcr_topn_stats* stats, double* per_user, Profiler* prof) {
         if (!topn.same(ncut, cuts, thr))
             RC(topn.build(n_users, ev[1].h_uptr.data(), h_test_item.data(), h_test_val.data(), ncut, cuts, thr));
         const bool ex = (flags & PCR_REC_EXCLUDE_TRAIN) != 0;
         const int K = cuts[ncut - 1];
         RC(rec_run<T>(st, d_U.p, d_V.p, geo.r, geo.ld, d2, ex ? d_uptr.p : nullptr, ex ? d_item.p : nullptr, (int64_t)topn.rel.users.size(),
-                      topn.rel.users.data(), K, 1, scope, RecTopn<T>(st, K, topn)));
-        {
-            auto sc = scope("recommend/metrics");
-            (void)sc;
-            RC(topn.reduce(st));
-        }
-        RC(allreduce_f64(topn.sums.p, (size_t)ncut * 8 + 1));
-        std::vector<double> h((size_t)ncut * 8 + 1);
-        HIPCHK(hipMemcpyAsync(h.data(), topn.sums.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        RC(sync_checked());
-        pcr_topn_stats_from(h.data(), ncut, cuts, stats);
-        if (per_user) RC(topn.fetch_per_user(st, n_users, per_user));
-        return PCR_OK;
+                      topn.rel.users.data(), K, 1, prof, RecTopn<T>(st, K, topn)));
+        // (the read-back waits through sync_checked: a peer-to-peer exchange that missed its deadline is reported there)
+        return topn.finish(st, prof, [this](double* p, size_t n) { return allreduce_f64(p, n); }, [this] { return sync_checked(); }, stats,
+                           n_users, per_user);
     }
     int evaluate_topn(int ncut, const int* cuts, double thr, int flags, pcr_topn_stats* stats, double* per_user) override {
-        return evaluate_topn_with(ncut, cuts, thr, flags, stats, per_user, [this](const char* name) { return ProfScope(this, name); });
+        return evaluate_topn_with(ncut, cuts, thr, flags, stats, per_user, &prof);
     }
     int recommend(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores) override {
-        return recommend_with(n, local, K, flags, items, scores, [this](const char* name) { return ProfScope(this, name); });
+        return recommend_with(n, local, K, flags, items, scores, &prof);
     }
 };
 
@@ -2506,13 +2520,16 @@ static int abi_guard(const char* what, F&& body) noexcept {
 #define PCR_ABI(name, expr) return abi_guard(name, [&]() -> int { return (expr); })
 
 // pcr_recommend_model / pcr_evaluate_topn_model: the exclusion CSR (item-ascending rows: a CSR that is not gets a sorted copy,
-// for the kernel's cursor) and both host fp64 factors in the requested type, rows padded to ld (slabs of 64 M values)
+// for the kernel's cursor) and both host fp64 factors in the requested type T, rows padded to ld: U then V in one buffer
+template <typename T>
 struct ModelDev {
     DBuf<int64_t> dx;
     DBuf<int32_t> di;
-    DBuf<float> F32;
-    DBuf<double> F64;
+    DBuf<T> F;
+    int64_t d1 = 0;
     int ld = 0;
+    const T* U() const { return F.p; }
+    const T* V() const { return F.p + (size_t)d1 * ld; }
     int upload_exclusion(int64_t d1, const int64_t* index, const int32_t* item, bool sorted) {
         if (!index) return PCR_OK;
         std::vector<int32_t> sitem;
@@ -2526,26 +2543,11 @@ struct ModelDev {
         RC(dx.upload_n(index, (size_t)d1 + 1)); RC(di.upload_n(sorted ? item : sitem.data(), (size_t)nnz));
         return PCR_OK;
     }
-    template <typename T>
-    int upload_factors(hipStream_t st, const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, DBuf<T>& F) {
+    int upload_factors(hipStream_t st, const double* hU, int64_t rows_u, const double* hV, int64_t rows_v, int64_t k) {
+        d1 = rows_u;
         ld = ((int)k + 3) & ~3;
-        RC(F.alloc((size_t)(d1 + d2) * ld));
-        DBuf<double> stage;
-        const int64_t slab_rows = std::max<int64_t>(1, ((int64_t)64 << 20) / k);
-        RC(stage.alloc((size_t)std::min<int64_t>(std::max(d1, d2), slab_rows) * (size_t)k));
-        for (int w = 0; w < 2; ++w) {
-            const double* H = w == 0 ? U : V;
-            T* dst = F.p + (w == 0 ? 0 : (size_t)d1 * ld);
-            const int64_t rows = w == 0 ? d1 : d2;
-            for (int64_t r0 = 0; r0 < rows; r0 += slab_rows) {
-                const int64_t nr = std::min(slab_rows, rows - r0);
-                HIPCHK(hipMemcpyAsync(stage.p, H + r0 * k, (size_t)nr * k * sizeof(double), hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL((k_mat_in<T>), dim3((unsigned)std::min<int64_t>(1 << 16, cdiv(nr * ld, 256))), dim3(256), 0, st, stage.p, dst + r0 * ld, nr, (int)k, ld);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipStreamSynchronize(st));
-            }
-        }
-        return PCR_OK;
+        RC(F.alloc((size_t)(d1 + rows_v) * ld));
+        return upload_rows<T>(st, (int)k, ld, {{hU, d1, F.p}, {hV, rows_v, F.p + (size_t)d1 * ld}});
     }
 };
 
@@ -2683,11 +2685,11 @@ int pcr_train(pcr_solver* s, pcr_log_fn log, void* ctx, pcr_iter_stats* hist) { 
 int pcr_solver_sync(pcr_solver* s) { S_OR_ARG; return s->sync(); }
 int pcr_iterate(pcr_solver* s, int n, pcr_iter_stats* out) { S_OR_ARG; PCR_ABI("pcr_iterate", leave_on_error(s, s->iterate_abi(n, out))); }
 
-int pcr_profile_enable(pcr_solver* s, int on) { S_OR_ARG; s->prof_on = on != 0; s->prof_period = on > 1 ? on : 1; if (on) s->prof_prewarm(4096); return PCR_OK; }
+int pcr_profile_enable(pcr_solver* s, int on) { S_OR_ARG; s->prof.on = on != 0; s->prof.period = on > 1 ? on : 1; if (on) s->prof.prewarm(4096); return PCR_OK; }
 int pcr_profile_reset(pcr_solver* s) {
     S_OR_ARG;
-    s->sync(); s->prof_resolve();
-    for (auto& kv : s->prof) { kv.second.ms = 0.0; kv.second.n = 0; kv.second.seen = 0; }
+    s->sync(); s->prof.resolve();
+    for (auto& kv : s->prof.slots) { kv.second.ms = 0.0; kv.second.n = 0; kv.second.seen = 0; }
     return PCR_OK;
 }
 int pcr_solver_ustep_classes(pcr_solver* s, char* buf, int64_t cap) {
@@ -2700,31 +2702,31 @@ int pcr_solver_ustep_classes(pcr_solver* s, char* buf, int64_t cap) {
 int pcr_profile_list(pcr_solver* s, char* buf, int64_t cap) {
     S_OR_ARG;
     std::string all;
-    for (auto& kv : s->prof) { if (!all.empty()) all += ","; all += kv.first; }
+    for (auto& kv : s->prof.slots) { if (!all.empty()) all += ","; all += kv.first; }
     if (!buf || cap < (int64_t)all.size() + 1) { pcr_set_error("buffer too small"); return PCR_ERR_ARG; }
     memcpy(buf, all.c_str(), all.size() + 1);
     return PCR_OK;
 }
 int pcr_profile_get(pcr_solver* s, const char* name, double* total_ms, int64_t* launches) {
     S_OR_ARG;
-    s->sync(); s->prof_resolve();
-    auto it = s->prof.find(name ? name : "");
-    if (total_ms) *total_ms = it == s->prof.end() ? 0.0 : it->second.ms;
-    if (launches) *launches = it == s->prof.end() ? 0 : it->second.n;
+    s->sync(); s->prof.resolve();
+    auto it = s->prof.slots.find(name ? name : "");
+    if (total_ms) *total_ms = it == s->prof.slots.end() ? 0.0 : it->second.ms;
+    if (launches) *launches = it == s->prof.slots.end() ? 0 : it->second.n;
     return PCR_OK;
 }
 
 int pcr_profile_launches(pcr_solver* s, const char* name, int64_t* launches) {
     S_OR_ARG;
-    auto it = s->prof.find(name ? name : "");
-    if (launches) *launches = it == s->prof.end() ? 0 : it->second.seen;
+    auto it = s->prof.slots.find(name ? name : "");
+    if (launches) *launches = it == s->prof.slots.end() ? 0 : it->second.seen;
     return PCR_OK;
 }
 
 int pcr_profile_scope(pcr_solver* s, const char* name, int64_t* ratings, int64_t* users) {
     S_OR_ARG;
-    auto it = s->prof.find(name ? name : "");
-    const bool whole = it == s->prof.end() || it->second.ratings < 0;
+    auto it = s->prof.slots.find(name ? name : "");
+    const bool whole = it == s->prof.slots.end() || it->second.ratings < 0;
     if (ratings) *ratings = whole ? s->nnz_local : it->second.ratings;
     if (users) *users = whole ? s->n_users : it->second.users;
     return PCR_OK;
@@ -2752,24 +2754,11 @@ int pcr_predict(const double* U, int64_t d1, const double* V, int64_t d2, int64_
     geo.r = (int)k; geo.ld = ((int)k + 3) & ~3; geo.nchunk = geo.ld / 2; geo.G = std::min(64, host_pow2(geo.nchunk));
     // the model file holds fp64 factors: score in fp64 like pmf-predict.cpp:58-62.  The matrices go up as they are (slabs of 64 M
     // values) and are padded to ld on the device; the ids from the caller's arrays.
-    DBuf<double> dU, dV, dP, stage;
+    DBuf<double> dU, dV, dP;
     DBuf<int32_t> du, di;
     hipStream_t st = nullptr;
     RC(dU.alloc((size_t)d1 * geo.ld)); RC(dV.alloc((size_t)d2 * geo.ld)); RC(dP.alloc((size_t)n));
-    const int64_t slab_rows = std::max<int64_t>(1, ((int64_t)64 << 20) / std::max<int64_t>(1, k));
-    RC(stage.alloc((size_t)std::min<int64_t>(std::max(d1, d2), slab_rows) * (size_t)k));
-    for (int w = 0; w < 2; ++w) {
-        const double* H = w == 0 ? U : V;
-        double* D = w == 0 ? dU.p : dV.p;
-        const int64_t rows = w == 0 ? d1 : d2;
-        for (int64_t r0 = 0; r0 < rows; r0 += slab_rows) {
-            const int64_t nr = std::min(slab_rows, rows - r0);
-            HIPCHK(hipMemcpyAsync(stage.p, H + r0 * k, (size_t)nr * k * sizeof(double), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL((k_mat_in<double>), dim3((unsigned)std::min<int64_t>(1 << 16, cdiv(nr * geo.ld, 256))), dim3(256), 0, st, stage.p, D + r0 * geo.ld, nr, (int)k, geo.ld);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(st));
-        }
-    }
+    RC(upload_rows<double>(st, (int)k, geo.ld, {{U, d1, dU.p}, {V, d2, dV.p}}));
     RC(du.upload_n(user, (size_t)n)); RC(di.upload_n(item, (size_t)n));
     if (n > 0) {
         const int gpb = 256 / geo.G;
@@ -2788,19 +2777,16 @@ int pcr_recommend_model(const double* U, int64_t d1, const double* V, int64_t d2
     RC(pcr_recommend_model_check(U, d1, V, d2, k, index, item, n, users, topk, dtype, items, scores, &sorted));
     RC(model_device(device));
     if (n == 0) return PCR_OK;
-    hipStream_t st = nullptr;
-    ModelDev M;
-    RC(M.upload_exclusion(d1, index, item, sorted));
-    auto noscope = [](const char*) { return 0; };
     const int select = pcr_tune_int("recommend_select", 1);
-    if (dtype == PCR_F64) {
-        RC(M.upload_factors(st, U, d1, V, d2, k, M.F64));
-        return rec_run<double>(st, M.F64.p, M.F64.p + (size_t)d1 * M.ld, (int)k, M.ld, d2, M.dx.p, M.di.p, n, users, topk, select, noscope,
-                               RecCopy<double>(st, topk, items, scores));
-    }
-    RC(M.upload_factors(st, U, d1, V, d2, k, M.F32));
-    return rec_run<float>(st, M.F32.p, M.F32.p + (size_t)d1 * M.ld, (int)k, M.ld, d2, M.dx.p, M.di.p, n, users, topk, select, noscope,
-                          RecCopy<float>(st, topk, items, scores));
+    auto run = [&](auto zero) -> int {
+        using T = decltype(zero);
+        hipStream_t st = nullptr;
+        ModelDev<T> M;
+        RC(M.upload_exclusion(d1, index, item, sorted));
+        RC(M.upload_factors(st, U, d1, V, d2, k));
+        return rec_run<T>(st, M.U(), M.V(), (int)k, M.ld, d2, M.dx.p, M.di.p, n, users, topk, select, nullptr, RecCopy<T>(st, topk, items, scores));
+    };
+    return dtype == PCR_F64 ? run(0.0) : run(0.0f);
     });
 }
 
@@ -2811,30 +2797,21 @@ int pcr_evaluate_topn_model(const double* U, int64_t d1, const double* V, int64_
     bool sorted = true;
     RC(pcr_evaluate_topn_model_check(U, d1, V, d2, k, index, item, tindex, titem, tval, ncut, cutoffs, threshold, dtype, stats, &sorted));
     RC(model_device(device));
-    hipStream_t st = nullptr;
-    ModelDev M;
-    RC(M.upload_exclusion(d1, index, item, sorted));
-    TopnDev D;
-    RC(D.build(d1, tindex, titem, tval, ncut, cutoffs, threshold));
-    const int K = cutoffs[ncut - 1];
-    const int64_t n = (int64_t)D.rel.users.size();
-    auto noscope = [](const char*) { return 0; };
-    if (dtype == PCR_F64) {
-        RC(M.upload_factors(st, U, d1, V, d2, k, M.F64));
-        RC(rec_run<double>(st, M.F64.p, M.F64.p + (size_t)d1 * M.ld, (int)k, M.ld, d2, M.dx.p, M.di.p, n, D.rel.users.data(), K, 1, noscope,
-                           RecTopn<double>(st, K, D)));
-    } else {
-        RC(M.upload_factors(st, U, d1, V, d2, k, M.F32));
-        RC(rec_run<float>(st, M.F32.p, M.F32.p + (size_t)d1 * M.ld, (int)k, M.ld, d2, M.dx.p, M.di.p, n, D.rel.users.data(), K, 1, noscope,
-                          RecTopn<float>(st, K, D)));
-    }
-    RC(D.reduce(st));
-    std::vector<double> h((size_t)ncut * 8 + 1);
-    HIPCHK(hipMemcpyAsync(h.data(), D.sums.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    pcr_topn_stats_from(h.data(), ncut, cutoffs, stats);
-    if (per_user) RC(D.fetch_per_user(st, d1, per_user));
-    return PCR_OK;
+    auto run = [&](auto zero) -> int {
+        using T = decltype(zero);
+        hipStream_t st = nullptr;
+        ModelDev<T> M;
+        RC(M.upload_exclusion(d1, index, item, sorted));
+        TopnDev D;
+        RC(D.build(d1, tindex, titem, tval, ncut, cutoffs, threshold));
+        const int K = cutoffs[ncut - 1];
+        RC(M.upload_factors(st, U, d1, V, d2, k));
+        RC(rec_run<T>(st, M.U(), M.V(), (int)k, M.ld, d2, M.dx.p, M.di.p, (int64_t)D.rel.users.size(), D.rel.users.data(), K, 1, nullptr,
+                      RecTopn<T>(st, K, D)));
+        return D.finish(st, nullptr, [](double*, size_t) { return PCR_OK; }, [st] { HIPCHK(hipStreamSynchronize(st)); return PCR_OK; }, stats, d1,
+                        per_user);
+    };
+    return dtype == PCR_F64 ? run(0.0) : run(0.0f);
     });
 }
 

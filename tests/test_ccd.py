@@ -238,6 +238,12 @@ def test_profile_slots_and_iterate_without_a_host_round_trip_per_rank():
         assert slot in prof and prof[slot][1] > 0, prof
     assert prof["ccd/vsweep"][1] == prof["ccd/usweep"][1] == 6 * 5 and prof["ccd/resid"][1] == 6
     assert rec["cg_u"] == 6 and 6 <= rec["cg_v"] <= 30
+    # recommend() and evaluate_topn() are timed in this solver's own profile (not in the PrimalCR++ solver it holds)
+    s.recommend(10)
+    s.evaluate_topn((5, 10))
+    prof = s.profile_all()
+    for slot in ("recommend/score", "recommend/merge", "recommend/metrics"):
+        assert slot in prof and prof[slot][1] > 0, prof
     s.close()
 
 

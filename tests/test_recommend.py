@@ -258,6 +258,22 @@ def test_solver_entry_equals_model_entry():
 
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
+def test_recommend_and_evaluate_topn_profile_slots():
+    import primalcr_amd as pcr
+    R, ds = _train_data()
+    s = pcr.Solver(ds, pcr.Parameter(k=8, **{"lambda": 100.0}))
+    s.set_factors(pcr.initial(R.d1, 8), pcr.initial(R.d2, 8))
+    s.profile(True)
+    s.recommend(10)
+    s.evaluate_topn((5, 10))
+    prof = s.profile_all()
+    for slot in ("recommend/score", "recommend/merge", "recommend/metrics"):
+        assert slot in prof and prof[slot][1] > 0, prof
+    s.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
 def test_invariance_determinism_and_training_untouched():
     import primalcr_amd as pcr
     R, ds = _train_data(seed=4)
