@@ -217,6 +217,8 @@ int pcr_partition_users(const int64_t *index, int64_t d1, int nparts, int64_t *b
  *                   the device-driven exchange is switched off for the whole job (host-synchronised exchange, one line on stderr)
  *   recommend_select  0 = pcr_recommend's kernel without its streaming selection (the GEMM and the sweep alone; the lists come back
  *                   empty): tools/exp_recommend.py times the selection's share with it; default 1
+ *   ranks_batch_users  test hook: at most this many counted users per batch of pcr_evaluate_ranks (rounded up to whole
+ *                   workgroups of 64; 0 = the natural batch, which holds a million users and more); read at every call
  *   count_rows      1 = the U-step kernels count the rows of V they gather (pcr_solver_counter; a diagnostic that
  *                   costs the short-user classes 10-20 %, so off by default)
  *   debug           1 = print launch decisions to stderr
@@ -449,6 +451,57 @@ int pcr_evaluate_topn_model(const double *U, int64_t d1, const double *V, int64_
  * Profile slots: recommend/score, and recommend/metrics (the merge with the metrics fused in, and the reduction). */
 int pcr_evaluate_topn(pcr_solver *s, int ncut, const int *cutoffs, double threshold, int flags,
                       pcr_topn_stats *stats, double *per_user);                        /* [device] */
+
+/* ------------------------------------------------------------------------- */
+/* exact full-catalogue rank metrics: AUC, MRR, mean (percentile) rank (no    */
+/* reference counterpart)                                                     */
+/* ------------------------------------------------------------------------- */
+/* Where in the whole catalogue every held-out item lands -- what the top-N metrics cannot see below position K.  Every counted
+ * user is scored against the whole catalogue on the device; no score leaves it.  For a user u:
+ *   Score s(u, j)      exactly the score pcr_recommend computes for the same factors and dtype (bit for bit: the same fixed
+ *                      k-ordered chain).
+ *   Order              a BEFORE b when s(u, a) > s(u, b), or the scores are equal and a < b (the order of a recommended list).
+ *   Relevant set R_u   as in the top-N evaluation: the distinct items with a test rating >= threshold; counted users are those
+ *                      with |R_u| >= 1, in ascending order.  NaN threshold is PCR_ERR_ARG.
+ *   Non-relevant N_u   all items, minus R_u, minus (with exclusion on) the items of u's training row.
+ *   Rank               for j in R_u:  rank_u(j) = 1 + #{i in N_u : i before j} + #{j' in R_u : j' before j}   (an integer >= 1),
+ *                      the position of j when N_u and R_u together are sorted by the order.  A held-out item is always a
+ *                      candidate, also when it sits in u's training row too.  With train and test disjoint, rank_u(j) is the
+ *                      position of j in an unbounded pcr_recommend list, and rank_u(j) <= K exactly when j is in the top-K list.
+ *   Per user           first_rank = min_j rank_u(j);  rr = 1 / first_rank;  mean_rank = (sum_j rank_u(j)) / |R_u|;
+ *                      auc = #{(j, i) : j in R_u, i in N_u, j before i} / (|R_u| |N_u|), NaN when N_u is empty;
+ *                      mpr = (sum_j (rank_u(j) - 1)) / (|R_u| (|N_u| + |R_u| - 1)), the mean of the percentile ranks
+ *                      (rank_u(j) - 1) / (|N_u| + |R_u| - 1); 0 when that denominator is 0.
+ *                      Each is ONE fp64 division of two exactly represented integers (the sums and products are formed as
+ *                      integers first), so a caller can reproduce every value exactly from ranks[].
+ *   Summary            users, users_auc (users with a defined auc), relevant = sum |R_u|, and the means over the counted users
+ *                      mrr, mean_rank, mpr and (over users_auc) auc.  A denominator of 0 gives a mean of 0.  No order
+ *                      statistics over users (a median rank).
+ *   Determinism        as the top-N evaluation: per-user values depend on (u, its rows) alone, the sums over users run in a
+ *                      fixed order, two identical calls are bitwise identical.
+ * per_user (optional, NULL: not written): [rows][PCR_RANK_FIELDS] = first_rank, rr, mean_rank, auc, mpr; uncounted users (all
+ * five) and an undefined auc are NaN.
+ * ranks (optional, NULL: not written): [tnnz] in the order of the test CSR: rank_u(titem[z]) for every test rating with
+ * tval[z] >= threshold (every occurrence of a duplicated item gets the item's rank), 0 for the others. */
+#define PCR_RANK_FIELDS 5
+typedef struct pcr_rank_stats {
+    int64_t users, users_auc, relevant;
+    double  mrr, mean_rank, auc, mpr;
+} pcr_rank_stats;
+/* Standalone: arguments and host-side checks as pcr_evaluate_topn_model (rows = d1; tnnz = tindex[d1]); everything is checked
+ * on the host before any device is looked for. */
+int pcr_evaluate_ranks_model(const double *U, int64_t d1, const double *V, int64_t d2, int64_t k,
+                             const int64_t *index, const int32_t *item,
+                             const int64_t *tindex, const int32_t *titem, const double *tval,
+                             double threshold, int dtype,
+                             pcr_rank_stats *stats, double *per_user, int64_t *ranks, int device);   /* [device] */
+/* On a live PCR, PCR++ or CCDR1 solver, as pcr_evaluate_topn: its device factors, storage type and stream, the test ratings
+ * it was created with (ranks[]: the shard's test ratings in their CSR order), flags PCR_REC_EXCLUDE_TRAIN; training state is
+ * not touched.  rows = the shard's n_users.  N ranks: stats are the totals over the communicator's ranks (every rank must
+ * call); local-only shards return their own partials.  The relevance table is built once per threshold and kept.
+ * Profile slots: ranks/relscore (the relevant items' scores and their sort), ranks/count (the counting sweep), ranks/finish. */
+int pcr_evaluate_ranks(pcr_solver *s, double threshold, int flags,
+                       pcr_rank_stats *stats, double *per_user, int64_t *ranks);                   /* [device] */
 
 /* per-kernel device timing (HIP events on the solver's stream, one pair per launch).
  * slot names: "<class>/<workgroup size>[.<length bound>][g][c][l][r][#n]" for the per-user kernels (classes

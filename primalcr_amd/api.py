@@ -12,6 +12,7 @@ PCR_RECOMMEND_MAX_K = 1024
 PCR_REC_EXCLUDE_TRAIN = 1
 PCR_TOPN_MAX_CUTOFFS = 8
 TOPN_FIELDS = ("hits", "precision", "recall", "ap", "ndcg", "ndcg_graded")   # per_user columns
+RANK_FIELDS = ("first_rank", "rr", "mean_rank", "auc", "mpr")                   # evaluate_ranks' per_user columns (PCR_RANK_FIELDS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -74,6 +75,12 @@ class IterStats(C.Structure):
 class TopnStats(C.Structure):
     _fields_ = [("cutoff", C.c_int), ("users", C.c_int64), ("users_graded", C.c_int64), ("hits", C.c_int64), ("precision", C.c_double),
                 ("recall", C.c_double), ("hit_rate", C.c_double), ("map", C.c_double), ("ndcg", C.c_double), ("ndcg_graded", C.c_double)]
+
+
+class RankStats(C.Structure):
+    """pcr_rank_stats."""
+    _fields_ = [("users", C.c_int64), ("users_auc", C.c_int64), ("relevant", C.c_int64), ("mrr", C.c_double), ("mean_rank", C.c_double),
+                ("auc", C.c_double), ("mpr", C.c_double)]
 
 
 _LOG_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p)
@@ -150,6 +157,8 @@ def lib():
     L.pcr_recommend.argtypes = [vp, i64, vp, ci, ci, vp, vp]
     L.pcr_evaluate_topn_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, ci, vp, cd, ci, vp, vp, ci]
     L.pcr_evaluate_topn.argtypes = [vp, ci, vp, cd, ci, vp, vp]
+    L.pcr_evaluate_ranks_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, cd, ci, vp, vp, vp, ci]
+    L.pcr_evaluate_ranks.argtypes = [vp, cd, ci, vp, vp, vp]
     L.pcr_profile_enable.argtypes = [vp, ci]
     L.pcr_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(cd), C.POINTER(i64)]
     L.pcr_profile_scope.argtypes = [vp, C.c_char_p, C.POINTER(i64), C.POINTER(i64)]
@@ -301,6 +310,50 @@ def evaluate_topn(U, V, test, cutoffs=(10,), exclude=None, threshold=-np.inf, dt
     return _topn_call(cutoffs, per_user, d1, lambda nc, cp, sp, pp: lib().pcr_evaluate_topn_model(
         U.ctypes.data, d1, V.ctypes.data, V.shape[0], k, None if idx is None else idx.ctypes.data, None if it is None else it.ctypes.data,
         tidx.ctypes.data, tit.ctypes.data, tval.ctypes.data, nc, cp, float(threshold), int(dtype), sp, pp, device))
+
+
+def _ranks_call(per_user, ranks, rows, tnnz, fn):
+    """Shared by evaluate_ranks() and Solver.evaluate_ranks(): fn(stats_ptr, per_user_ptr, ranks_ptr) -> status.  Returns the
+    summary dict, then the per-user table and / or the ranks array when asked for."""
+    stats = RankStats()
+    pu = np.empty((rows, len(RANK_FIELDS)), np.float64) if per_user else None
+    rk = np.empty(max(int(tnnz), 1), np.int64) if ranks else None
+    _chk(fn(C.addressof(stats), None if pu is None else pu.ctypes.data, None if rk is None else rk.ctypes.data))
+    out = ({f: getattr(stats, f) for f, _ in RankStats._fields_},)
+    if per_user:
+        out += (pu,)
+    if ranks:
+        out += (rk[:int(tnnz)],)
+    return out[0] if len(out) == 1 else out
+
+
+def evaluate_ranks(U, V, test, exclude=None, threshold=-np.inf, dtype=PCR_F64, device=0, per_user=False, ranks=False):
+    """Exact full-catalogue rank metrics on the GPU (pcr_evaluate_ranks_model): the position of every relevant test item (value >=
+    threshold) among all items the user has not rated (exclude given) in the order of recommend().  test / exclude as
+    evaluate_topn().  Returns the summary dict (users, users_auc, relevant, mrr, mean_rank, auc, mpr); with per_user also the
+    array [d1, 5] of RANK_FIELDS (NaN for users not counted and for an undefined auc); with ranks also the int64 array [tnnz] of
+    1-based ranks in the order of the test CSR (0 for ratings below the threshold)."""
+    U = np.ascontiguousarray(U, np.float64); V = np.ascontiguousarray(V, np.float64)
+    d1, k = U.shape
+    if isinstance(test, Dataset):
+        tidx, tit, tval = test.csr(1)
+    else:
+        tidx, tit, tval = test
+    tidx = np.ascontiguousarray(tidx, np.int64); tit = np.ascontiguousarray(tit, np.int32); tval = np.ascontiguousarray(tval, np.float64)
+    if tidx.shape[0] != d1 + 1 or tidx[-1] != tit.shape[0] or tit.shape[0] != tval.shape[0]:
+        raise ValueError(f"test: index must have d1 + 1 = {d1 + 1} entries, the last equal to len(item) = len(val)")
+    idx = it = None
+    if exclude is not None:
+        if isinstance(exclude, Dataset):
+            idx, it, _ = exclude.csr(0)
+        else:
+            idx, it = exclude[:2]
+        idx = np.ascontiguousarray(idx, np.int64); it = np.ascontiguousarray(it, np.int32)
+        if idx.shape[0] != d1 + 1 or idx[-1] != it.shape[0]:
+            raise ValueError(f"exclude: index must have d1 + 1 = {d1 + 1} entries, the last equal to len(item) = {it.shape[0]}")
+    return _ranks_call(per_user, ranks, d1, tit.shape[0], lambda sp, pp, rp: lib().pcr_evaluate_ranks_model(
+        U.ctypes.data, d1, V.ctypes.data, V.shape[0], k, None if idx is None else idx.ctypes.data, None if it is None else it.ctypes.data,
+        tidx.ctypes.data, tit.ctypes.data, tval.ctypes.data, float(threshold), int(dtype), sp, pp, rp, device))
 
 
 def comm_unique_id() -> bytes:
@@ -589,6 +642,18 @@ class Solver:
         (every rank must call); local-only shards: their own partials."""
         return _topn_call(cutoffs, per_user, self.n_users, lambda nc, cp, sp, pp: lib().pcr_evaluate_topn(
             self._h, nc, cp, float(threshold), PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, sp, pp))
+
+    def evaluate_ranks(self, threshold=-np.inf, exclude_train=True, per_user=False, ranks=False):
+        """Exact full-catalogue rank metrics of this shard's users against the solver's test ratings (pcr_evaluate_ranks); the
+        result as evaluate_ranks(), per_user rows and ranks for the shard's users / test ratings.  N ranks with a communicator:
+        the totals of all ranks (every rank must call); local-only shards: their own partials."""
+        tnnz = 0
+        if ranks:
+            tidx = self.ds.csr(1)[0]                     # (a shard's own data set starts at its first user)
+            lo = 0 if tidx.shape[0] - 1 == self.n_users else self.first_user
+            tnnz = int(tidx[lo + self.n_users] - tidx[lo])
+        return _ranks_call(per_user, ranks, self.n_users, tnnz, lambda sp, pp, rp: lib().pcr_evaluate_ranks(
+            self._h, float(threshold), PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, sp, pp, rp))
 
     def sync(self):
         _chk(lib().pcr_solver_sync(self._h))

@@ -2,7 +2,7 @@
 // --eval, the full-catalogue top-N evaluation of those lists against a data directory's test ratings (pcr_evaluate_topn_model).
 // The reference has no counterpart: pmf-predict.cpp scores the pairs of a test file only.
 //   omp-pmf-recommend [-K topk] [-x data_dir] [-u users_file] [--f32] [--scores] model_file output_file
-//   omp-pmf-recommend --eval data_dir [-c c1,c2,...] [--threshold v] [-K topk] [-x data_dir] [--f32] model_file [output_file]
+//   omp-pmf-recommend --eval data_dir [-c c1,c2,...] [--threshold v] [--ranks] [-K topk] [-x data_dir] [--f32] model_file [output_file]
 //     -K topk        items per user (default 10, at most PCR_RECOMMEND_MAX_K)
 //     -x data_dir    leave out the training ratings of a data directory (its meta file; d1 / d2 must match the model)
 //     -u users_file  one 1-based user id per line (default: every user of the model)
@@ -11,11 +11,14 @@
 //     --eval dir     evaluate against the test file of a data directory (its meta file; d1 / d2 must match the model)
 //     -c cutoffs     comma-separated ascending cutoffs, at most PCR_TOPN_MAX_CUTOFFS (default: -K)
 //     --threshold v  a test rating is relevant when >= v (default: every test rating)
+//     --ranks        also the exact full-catalogue rank metrics (pcr_evaluate_ranks_model)
 // Output: one line per user, in input order: the 1-based user id, then the 1-based item ids (padding is left out).  Users go
 // to the device in batches, so host memory for the lists stays bounded on any catalogue.
 // With --eval: stdout gets one line per cutoff, "cutoff c users n users_graded n hits n precision x recall x hit_rate x map x
 // ndcg x ndcg_graded x" (values in %g); the output file, if given, one line per counted user at the largest cutoff: the 1-based
 // user id, then hits precision recall ap ndcg ndcg_graded (%g; nan where ndcg_graded is undefined).
+// With --eval --ranks: after the cutoff lines one line "ranks users n users_auc n relevant n mrr x mean_rank x auc x mpr x"; the
+// output file then holds, per counted user, the 1-based user id, then first_rank rr mean_rank auc mpr (%g) instead.
 #include <algorithm>
 #include <cerrno>
 #include <charconv>
@@ -32,7 +35,7 @@
 
 static const char* USAGE =
     "Usage: omp-pmf-recommend [-K topk] [-x data_dir] [-u users_file] [--f32] [--scores] model_file output_file\n"
-    "       omp-pmf-recommend --eval data_dir [-c c1,c2,...] [--threshold v] [-K topk] [-x data_dir] [--f32] model_file [output_file]\n"
+    "       omp-pmf-recommend --eval data_dir [-c c1,c2,...] [--threshold v] [--ranks] [-K topk] [-x data_dir] [--f32] model_file [output_file]\n"
     "    -K topk        items per user (default 10, 1 .. 1024)\n"
     "    -x data_dir    leave out the training ratings of this data directory (meta file)\n"
     "    -u users_file  one 1-based user id per line (default: every user)\n"
@@ -41,7 +44,9 @@ static const char* USAGE =
     "    --eval dir     top-N metrics against the test ratings of this data directory (meta file)\n"
     "    -c cutoffs     comma-separated ascending cutoffs, at most 8, each 1 .. 1024 (default: -K)\n"
     "    --threshold v  a test rating is relevant when >= v (default: every test rating)\n"
-    "    output_file    with --eval optional: per counted user at the largest cutoff, hits precision recall ap ndcg ndcg_graded\n";
+    "    --ranks        with --eval: also a line of exact full-catalogue rank metrics (mrr, mean_rank, auc, mpr)\n"
+    "    output_file    with --eval optional: per counted user at the largest cutoff, hits precision recall ap ndcg ndcg_graded;\n"
+    "                   with --ranks: per counted user first_rank rr mean_rank auc mpr\n";
 
 static int usage() { printf("%s", USAGE); return 1; }
 
@@ -110,7 +115,7 @@ static bool load_csr(const char* dir, int which, int64_t d1, int64_t d2, std::ve
 // --eval: the metrics per cutoff to stdout, the per-user rows at the largest cutoff to out_path (if given)
 static int run_eval(const char* edir, const std::vector<double>& U, const std::vector<double>& V, int64_t d1, int64_t d2, int64_t k,
                     const std::vector<int64_t>* xindex, const std::vector<int32_t>* xitem, const std::vector<int>& cuts, double threshold,
-                    bool f32, const char* out_path) {
+                    bool f32, bool with_ranks, const char* out_path) {
     std::vector<int64_t> tindex;
     std::vector<int32_t> titem;
     std::vector<double> tval;
@@ -118,21 +123,39 @@ static int run_eval(const char* edir, const std::vector<double>& U, const std::v
     const int nc = (int)cuts.size();
     std::vector<pcr_topn_stats> st((size_t)nc);
     std::vector<double> per;
-    if (out_path) per.resize((size_t)d1 * nc * 6);
+    const bool topn_rows = out_path && !with_ranks;
+    if (topn_rows) per.resize((size_t)d1 * nc * 6);
     if (pcr_evaluate_topn_model(U.data(), d1, V.data(), d2, k, xindex ? xindex->data() : nullptr, xitem ? xitem->data() : nullptr, tindex.data(),
                                 titem.data(), tval.data(), nc, cuts.data(), threshold, f32 ? PCR_F32 : PCR_F64, st.data(),
-                                out_path ? per.data() : nullptr, 0) != PCR_OK) {
+                                topn_rows ? per.data() : nullptr, 0) != PCR_OK) {
         fprintf(stderr, "evaluate: %s\n", pcr_last_error());
         return 1;
     }
     for (const pcr_topn_stats& s : st)
         printf("cutoff %d users %lld users_graded %lld hits %lld precision %g recall %g hit_rate %g map %g ndcg %g ndcg_graded %g\n", s.cutoff,
                (long long)s.users, (long long)s.users_graded, (long long)s.hits, s.precision, s.recall, s.hit_rate, s.map, s.ndcg, s.ndcg_graded);
+    if (with_ranks) {
+        pcr_rank_stats rs;
+        if (out_path) per.resize((size_t)d1 * PCR_RANK_FIELDS);
+        if (pcr_evaluate_ranks_model(U.data(), d1, V.data(), d2, k, xindex ? xindex->data() : nullptr, xitem ? xitem->data() : nullptr,
+                                     tindex.data(), titem.data(), tval.data(), threshold, f32 ? PCR_F32 : PCR_F64, &rs,
+                                     out_path ? per.data() : nullptr, nullptr, 0) != PCR_OK) {
+            fprintf(stderr, "evaluate: %s\n", pcr_last_error());
+            return 1;
+        }
+        printf("ranks users %lld users_auc %lld relevant %lld mrr %g mean_rank %g auc %g mpr %g\n", (long long)rs.users, (long long)rs.users_auc,
+               (long long)rs.relevant, rs.mrr, rs.mean_rank, rs.auc, rs.mpr);
+    }
     if (!out_path) return 0;
     FILE* fp = fopen(out_path, "wb");
     if (!fp) { fprintf(stderr, "can't open output file %s\n", out_path); return 1; }
     bool ok = true;
-    for (int64_t u = 0; u < d1 && ok; ++u) {
+    for (int64_t u = 0; u < d1 && ok && with_ranks; ++u) {
+        const double* r = per.data() + (size_t)u * PCR_RANK_FIELDS;
+        if (r[0] != r[0]) continue;                                   // not counted
+        ok = fprintf(fp, "%lld %g %g %g %g %g\n", (long long)u + 1, r[0], r[1], r[2], r[3], r[4]) > 0;
+    }
+    for (int64_t u = 0; u < d1 && ok && !with_ranks; ++u) {
         const double* r = per.data() + ((size_t)u * nc + (nc - 1)) * 6;
         if (r[0] != r[0]) continue;                                   // not counted
         ok = fprintf(fp, "%lld %g %g %g %g %g %g\n", (long long)u + 1, r[0], r[1], r[2], r[3], r[4], r[5]) > 0;
@@ -144,7 +167,7 @@ static int run_eval(const char* edir, const std::vector<double>& U, const std::v
 
 int main(int argc, char** argv) {
     int K = 10;
-    bool f32 = false, with_scores = false;
+    bool f32 = false, with_scores = false, with_ranks = false;
     const char *xdir = nullptr, *ufile = nullptr, *edir = nullptr;
     std::vector<int> cuts;
     double threshold = -INFINITY;
@@ -178,11 +201,13 @@ int main(int argc, char** argv) {
             else ufile = v;
         } else if (!strcmp(a, "--f32")) f32 = true;
         else if (!strcmp(a, "--scores")) with_scores = true;
+        else if (!strcmp(a, "--ranks")) with_ranks = true;
         else if (a[0] == '-' && a[1]) { fprintf(stderr, "unknown option %s\n", a); return usage(); }
         else pos.push_back(a);
     }
     if (edir ? (pos.empty() || pos.size() > 2) : pos.size() != 2) return usage();
     if (!edir && (!cuts.empty() || threshold != -INFINITY)) { fprintf(stderr, "-c and --threshold go with --eval\n"); return 1; }
+    if (!edir && with_ranks) { fprintf(stderr, "--ranks goes with --eval\n"); return 1; }
     if (edir && (ufile || with_scores)) { fprintf(stderr, "-u and --scores do not go with --eval\n"); return 1; }
     int64_t d1, d2, k;
     if (pcr_model_load(pos[0], &d1, &d2, &k, nullptr, nullptr) != PCR_OK) { fprintf(stderr, "can't open model file %s\n", pos[0]); return 1; }
@@ -197,7 +222,7 @@ int main(int argc, char** argv) {
     if (edir) {
         if (cuts.empty()) cuts.push_back(K);
         const int rc = run_eval(edir, U, V, d1, d2, k, xdir ? &xindex : nullptr, xdir ? &xitem : nullptr, cuts, threshold, f32,
-                                pos.size() == 2 ? pos[1] : nullptr);
+                                with_ranks, pos.size() == 2 ? pos[1] : nullptr);
         if (rc) return rc;
         fflush(stdout); fflush(stderr);
         _exit(0);

@@ -580,6 +580,9 @@ struct CcdSolver final : pcr_solver {
     int evaluate_topn(int ncut, const int* cuts, double thr, int flags, pcr_topn_stats* stats, double* per_user) override {
         return base->evaluate_topn_with(ncut, cuts, thr, flags, stats, per_user, &prof);
     }
+    int evaluate_ranks(double thr, int flags, pcr_rank_stats* stats, double* per_user, int64_t* ranks) override {
+        return base->evaluate_ranks_with(thr, flags, stats, per_user, ranks, &prof);
+    }
     int residual_mismatch(double* value) override {
         hipLaunchKernelGGL((k_ccd_mismatch<RT>), dim3(B), dim3(ccd::BLOCK), 0, st, (const RT*)d_res_r.p, (const RT*)d_res_c.p, (const int32_t*)d_c2r.p,
                            nnz, d_pmis.p);

@@ -362,7 +362,7 @@ extern "C" int pcr_dataset_from_csr(int64_t d1, int64_t d2, const int64_t* index
 static std::map<std::string, std::string>& tune_table() { static thread_local std::map<std::string, std::string> t; return t; }
 static const char* const TUNE_KEYS[] = {"ustep_mode", "cluster_k", "cluster_users", "ubins", "ustep_gram", "spmm_tiles", "spmm_chunk", "sddmm_csc",
                                         "lanes", "pipeline", "window_cache", "prepare_merged", "resort_window", "allreduce_chunks", "p2p_ll",
-                                        "p2p_timeout_ms", "p2p_queue_budget", "count_rows", "debug", "win16", "ustep_win_lds", "plan_key64", "ustep_newton", "vblock_users", "recommend_select", "fault_cluster_member", "fault_p2p_skip", "fault_p2p_coarse", nullptr};
+                                        "p2p_timeout_ms", "p2p_queue_budget", "count_rows", "debug", "win16", "ustep_win_lds", "plan_key64", "ustep_newton", "vblock_users", "recommend_select", "ranks_batch_users", "fault_cluster_member", "fault_p2p_skip", "fault_p2p_coarse", nullptr};
 extern "C" int pcr_tune(const char* key, const char* value) {
     if (!key) { pcr_set_error("pcr_tune: null key"); return PCR_ERR_ARG; }
     bool known = false;
@@ -1103,15 +1103,9 @@ int pcr_topn_check(const char* who, int ncut, const int* cutoffs, double thresho
     return PCR_OK;
 }
 
-int pcr_evaluate_topn_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
-                                  const int32_t* item, const int64_t* tindex, const int32_t* titem, const double* tval, int ncut,
-                                  const int* cutoffs, double threshold, int dtype, const pcr_topn_stats* stats, bool* sorted) {
-    auto bad = [](const std::string& why) { pcr_set_error("pcr_evaluate_topn_model: " + why); return PCR_ERR_ARG; };
-    int rc = pcr_topn_check("pcr_evaluate_topn_model", ncut, cutoffs, threshold, stats);
-    if (rc != PCR_OK) return rc;
-    rc = pcr_recommend_model_check(U, d1, V, d2, k, index, item, 0, nullptr, cutoffs[ncut - 1], dtype, nullptr, nullptr, sorted,
-                                             "pcr_evaluate_topn_model");
-    if (rc != PCR_OK) return rc;
+// the test CSR of a model entry: present, tindex[0] = 0, monotone, items inside [0, d2)
+static int test_csr_check(const char* who, int64_t d1, int64_t d2, const int64_t* tindex, const int32_t* titem, const double* tval) {
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
     if (!tindex || !titem || !tval) return bad("null test CSR");
     if (tindex[0] != 0) return bad("tindex[0] must be 0");
     for (int64_t u = 0; u < d1; ++u) if (tindex[u + 1] < tindex[u]) return bad("tindex not monotone at user " + std::to_string(u));
@@ -1122,6 +1116,29 @@ int pcr_evaluate_topn_model_check(const double* U, int64_t d1, const double* V, 
     });
     for (char x : out_of_range) if (x) return bad("an item id of the test CSR is outside [0, d2)");
     return PCR_OK;
+}
+
+int pcr_evaluate_topn_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
+                                  const int32_t* item, const int64_t* tindex, const int32_t* titem, const double* tval, int ncut,
+                                  const int* cutoffs, double threshold, int dtype, const pcr_topn_stats* stats, bool* sorted) {
+    int rc = pcr_topn_check("pcr_evaluate_topn_model", ncut, cutoffs, threshold, stats);
+    if (rc != PCR_OK) return rc;
+    rc = pcr_recommend_model_check(U, d1, V, d2, k, index, item, 0, nullptr, cutoffs[ncut - 1], dtype, nullptr, nullptr, sorted,
+                                             "pcr_evaluate_topn_model");
+    if (rc != PCR_OK) return rc;
+    return test_csr_check("pcr_evaluate_topn_model", d1, d2, tindex, titem, tval);
+}
+
+int pcr_evaluate_ranks_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
+                                   const int32_t* item, const int64_t* tindex, const int32_t* titem, const double* tval,
+                                   double threshold, int dtype, const pcr_rank_stats* stats, bool* sorted) {
+    auto bad = [](const std::string& why) { pcr_set_error("pcr_evaluate_ranks_model: " + why); return PCR_ERR_ARG; };
+    if (std::isnan(threshold)) return bad("threshold is NaN");
+    if (!stats) return bad("null stats");
+    const int rc = pcr_recommend_model_check(U, d1, V, d2, k, index, item, 0, nullptr, 1, dtype, nullptr, nullptr, sorted,
+                                             "pcr_evaluate_ranks_model");
+    if (rc != PCR_OK) return rc;
+    return test_csr_check("pcr_evaluate_ranks_model", d1, d2, tindex, titem, tval);
 }
 
 void pcr_topn_relevance(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, double threshold, int ncut,
@@ -1189,4 +1206,30 @@ void pcr_topn_stats_from(const double* sums, int ncut, const int* cutoffs, pcr_t
         o.ndcg = mean(x[5], users);
         o.ndcg_graded = mean(x[6], x[7]);
     }
+}
+
+void pcr_rank_stats_from(const double* sums, pcr_rank_stats* stats) {
+    const double users = sums[8];
+    auto mean = [](double s, double n) { return n > 0.0 ? s / n : 0.0; };
+    stats->users = (int64_t)users;
+    stats->users_auc = (int64_t)sums[7];
+    stats->relevant = (int64_t)sums[0];
+    stats->mrr = mean(sums[1], users);
+    stats->mean_rank = mean(sums[2], users);
+    stats->auc = mean(sums[6], sums[7]);
+    stats->mpr = mean(sums[4], users);
+}
+
+void pcr_rank_scatter(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, double threshold,
+                      const PcrTopnRel& rel, const int64_t* rrank, int64_t* ranks) {
+    std::fill(ranks, ranks + tptr[rows], (int64_t)0);
+    pcr_parallel_ranges((int64_t)rel.users.size(), pcr_host_threads(), [&](int, int64_t lo, int64_t hi) {
+        for (int64_t i = lo; i < hi; ++i) {
+            const int64_t u = rel.users[(size_t)i];
+            const int32_t* rb = rel.ritem.data() + rel.rptr[(size_t)i];
+            const int32_t* re = rel.ritem.data() + rel.rptr[(size_t)i + 1];
+            for (int64_t z = tptr[u]; z < tptr[u + 1]; ++z)
+                if (tval[z] >= threshold) ranks[z] = rrank[std::lower_bound(rb, re, titem[z]) - rel.ritem.data()];
+        }
+    });
 }

@@ -99,3 +99,17 @@ void pcr_topn_relevance(int64_t rows, const int64_t* tptr, const int32_t* titem,
                         const int* cutoffs, PcrTopnRel& out);
 // stats[c] from the reduced sums (k_topn_fin's layout: [ncut][8], then the counted users)
 void pcr_topn_stats_from(const double* sums, int ncut, const int* cutoffs, pcr_topn_stats* stats);
+
+// Exact rank metrics (include/primalcr.h, "exact full-catalogue rank metrics").
+// pcr_evaluate_ranks_model's argument checks (shared with the sanitizer build's stub): threshold not NaN, stats != NULL, the
+// factor / exclusion checks of pcr_recommend_model and the test CSR's shape.  *sorted as pcr_recommend_model_check.
+int pcr_evaluate_ranks_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
+                                   const int32_t* item, const int64_t* tindex, const int32_t* titem, const double* tval,
+                                   double threshold, int dtype, const pcr_rank_stats* stats, bool* sorted);
+// stats from the reduced sums of k_rank_finish's rows (k_topn_fin's layout with one cutoff: |R_u|, rr, mean_rank, users, mpr,
+// first_rank, auc, users_auc summed, then the counted users)
+void pcr_rank_stats_from(const double* sums, pcr_rank_stats* stats);
+// ranks[z] of rows [0, rows) of the test CSR from rrank (the ranks of rel.ritem, entry for entry): the rank of titem[z] where
+// tval[z] >= threshold, 0 elsewhere
+void pcr_rank_scatter(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, double threshold,
+                      const PcrTopnRel& rel, const int64_t* rrank, int64_t* ranks);

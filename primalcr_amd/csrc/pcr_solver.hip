@@ -182,21 +182,39 @@ struct ProfScope {
 // are timed in prof's "recommend/..." slots (NULL: not profiled).  select = 0 only for tools/exp_recommend.py's GEMM-alone timing (lists come back empty).
 static const size_t REC_SCRATCH = (size_t)1 << 30;
 static const int REC_TARGET_WG = 1024, REC_MAX_SPLIT = 16, REC_MIN_SPLIT_ITEMS = 1024;
+// The user batches and item splits of a sweep over n users whose scratch takes per_user bytes per user and split (rec_run and
+// rank_run share this arithmetic): nb users per batch, at most smax splits
+struct RecGeom {
+    int64_t d2, nb = 0;
+    int smax = 1;
+    static constexpr int64_t users_per_wg = (int64_t)rec::WAVES * rec::UW;
+    int splits_for(int64_t users) const {
+        const int64_t wg = (users + users_per_wg - 1) / users_per_wg;
+        int64_t s = std::max<int64_t>(1, (REC_TARGET_WG + wg - 1) / wg);
+        s = std::min<int64_t>(s, std::max<int64_t>(1, d2 / REC_MIN_SPLIT_ITEMS));
+        return (int)std::min<int64_t>(s, REC_MAX_SPLIT);
+    }
+    RecGeom(int64_t n, int64_t d2_, size_t per_user) : d2(d2_) {
+        nb = std::min<int64_t>(n, std::max<int64_t>(users_per_wg, (int64_t)(REC_SCRATCH / (per_user * 2)) / users_per_wg * users_per_wg));
+        while (nb > users_per_wg && (size_t)nb * (size_t)splits_for(nb) * per_user > REC_SCRATCH) nb = std::max<int64_t>(users_per_wg, nb / 2);
+        smax = splits_for(std::min(nb, n));
+    }
+    // a batch of m users: the items per split (whole steps) and the splits launched
+    void batch(int64_t m, int* per, int* nsp) const {
+        const int ns = std::min(splits_for(m), smax);      // (a short last batch keeps the scratch of the first)
+        *per = (int)(((d2 + ns - 1) / ns + rec::TILE - 1) / rec::TILE * rec::TILE);
+        *nsp = (int)((d2 + *per - 1) / *per);
+    }
+};
+
 template <typename T, class Sink>
 static int rec_run(hipStream_t st, const T* U, const T* V, int r, int ld, int64_t d2, const int64_t* xptr, const int32_t* xitem,
                    int64_t n, const int32_t* h_users, int K, int select, Profiler* prof, Sink&& sink) {
     if (n <= 0) return PCR_OK;
     const size_t per_user = (size_t)K * (sizeof(T) + sizeof(int32_t)) + sizeof(int32_t);
-    const int64_t users_per_wg = (int64_t)rec::WAVES * rec::UW;
-    int64_t nb = std::min<int64_t>(n, std::max<int64_t>(users_per_wg, (int64_t)(REC_SCRATCH / (per_user * 2)) / users_per_wg * users_per_wg));
-    auto splits_for = [&](int64_t users) {
-        const int64_t wg = (users + users_per_wg - 1) / users_per_wg;
-        int64_t s = std::max<int64_t>(1, (REC_TARGET_WG + wg - 1) / wg);
-        s = std::min<int64_t>(s, std::max<int64_t>(1, d2 / REC_MIN_SPLIT_ITEMS));
-        return (int)std::min<int64_t>(s, REC_MAX_SPLIT);
-    };
-    while (nb > users_per_wg && (size_t)nb * (size_t)splits_for(nb) * per_user > REC_SCRATCH) nb = std::max<int64_t>(users_per_wg, nb / 2);
-    const int smax = splits_for(std::min(nb, n));
+    const RecGeom geom(n, d2, per_user);
+    const int64_t users_per_wg = RecGeom::users_per_wg, nb = geom.nb;
+    const int smax = geom.smax;
     DBuf<T> ls; DBuf<int32_t> li, ln, du;
     RC(ls.alloc((size_t)nb * smax * K)); RC(li.alloc((size_t)nb * smax * K)); RC(ln.alloc((size_t)nb * smax));
     RC(du.alloc((size_t)nb)); RC(sink.begin(nb));
@@ -208,9 +226,8 @@ static int rec_run(hipStream_t st, const T* U, const T* V, int r, int ld, int64_
         const int32_t* hu = h_users ? h_users + b0 : nullptr;
         if (!hu) { seq.resize((size_t)m); for (int64_t i = 0; i < m; ++i) seq[(size_t)i] = (int32_t)(b0 + i); hu = seq.data(); }
         HIPCHK(hipMemcpyAsync(du.p, hu, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        const int ns = std::min(splits_for(m), smax);      // (a short last batch keeps the scratch of the first)
-        const int per = (int)(((d2 + ns - 1) / ns + rec::TILE - 1) / rec::TILE * rec::TILE);
-        const int nsp = (int)((d2 + per - 1) / per);
+        int per, nsp;
+        geom.batch(m, &per, &nsp);
         {
             ProfScope ps(prof, "recommend/score", st);
             hipLaunchKernelGGL((k_rec_score<T>), dim3((unsigned)cdiv(m, users_per_wg), (unsigned)nsp), dim3(rec::WAVES * 64), lds, st, U, V, r, ld,
@@ -325,6 +342,121 @@ struct RecTopn {
     }
 };
 
+// Exact rank metrics (pcr_evaluate_ranks, pcr_topk.h): the relevance table of a threshold on the device (PcrTopnRel's users,
+// rptr and ritem; uploaded once per threshold) and the outputs: rrank[nrel] the ranks of ritem entry for entry, met[n][6]
+// k_rank_finish's rows, the reduced sums [8] + the count
+struct RankDev {
+    PcrTopnRel rel;
+    double threshold = 0.0;
+    bool valid = false;
+    DBuf<int64_t> rptr, rrank;
+    DBuf<int32_t> ritem, rslot, users;
+    DBuf<double> met, part, sums;
+    bool same(double thr) const { return valid && thr == threshold; }
+    int build(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, double thr) {
+        valid = false;
+        const int one = 1;
+        pcr_topn_relevance(rows, tptr, titem, tval, thr, 1, &one, rel);
+        threshold = thr;
+        RC(rptr.upload(rel.rptr, nullptr)); RC(ritem.upload(rel.ritem, nullptr)); RC(users.upload(rel.users, nullptr));
+        RC(rslot.alloc(rel.ritem.size())); RC(rrank.alloc(rel.ritem.size()));
+        RC(met.alloc(rel.users.size() * 6)); RC(sums.alloc(9));
+        valid = true;
+        return PCR_OK;
+    }
+    // The end of an evaluation, after rank_run: TopnDev::finish's steps with one "cutoff" (the same two kernels sum met's
+    // columns), then per_user[rows][PCR_RANK_FIELDS] and ranks[] of the test CSR tptr / titem / tval (rows of this table's build)
+    template <class Combine, class Wait>
+    int finish(hipStream_t st, Profiler* prof, Combine&& combine, Wait&& wait, pcr_rank_stats* stats, int64_t rows, double* per_user,
+               const int64_t* tptr, const int32_t* titem, const double* tval, int64_t* ranks) {
+        const int64_t n = (int64_t)rel.users.size();
+        {
+            ProfScope ps(prof, "ranks/finish", st);
+            const int nb = (int)std::min<int64_t>(512, std::max<int64_t>(1, cdiv(n, 2048)));
+            const int per = cdiv(std::max<int64_t>(n, 1), nb);
+            if (part.n < (size_t)nb * 8) RC(part.alloc((size_t)nb * 8));
+            hipLaunchKernelGGL(k_topn_sum1, dim3(nb, 1), dim3(PCR_EW_BLOCK), 0, st, (const double*)met.p, n, 1, per, part.p);
+            hipLaunchKernelGGL(k_topn_fin, dim3(1), dim3(PCR_EW_BLOCK), 0, st, (const double*)part.p, nb, n, sums.p);
+            HIPCHK(hipGetLastError());
+        }
+        RC(combine(sums.p, (size_t)9));
+        double hs[9];
+        HIPCHK(hipMemcpyAsync(hs, sums.p, sizeof hs, hipMemcpyDeviceToHost, st));
+        RC(wait());
+        pcr_rank_stats_from(hs, stats);
+        if (per_user) {
+            std::vector<double> h((size_t)n * 6);
+            if (n) HIPCHK(hipMemcpyAsync(h.data(), met.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            std::fill(per_user, per_user + (size_t)rows * PCR_RANK_FIELDS, (double)NAN);
+            for (int64_t i = 0; i < n; ++i) {           // met: |R_u|, rr, mean_rank, mpr, first_rank, auc
+                const double* m = h.data() + (size_t)i * 6;
+                double* o = per_user + (size_t)rel.users[(size_t)i] * PCR_RANK_FIELDS;
+                o[0] = m[4]; o[1] = m[1]; o[2] = m[2]; o[3] = m[5]; o[4] = m[3];
+            }
+        }
+        if (ranks) {
+            std::vector<int64_t> h(rel.ritem.size());
+            if (!h.empty()) HIPCHK(hipMemcpyAsync(h.data(), rrank.p, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            pcr_rank_scatter(rows, tptr, titem, tval, threshold, rel, h.data(), ranks);
+        }
+        return PCR_OK;
+    }
+};
+
+// The rank metrics' sweep for the counted users of d (rows of U and of the exclusion CSR, as rec_run): the relevant items'
+// scores and their sort once for all users ("ranks/relscore"), then per user batch (RecGeom, the scratch being the splits'
+// histograms: |R_u| + 1 counters per user) the counting sweep ("ranks/count") and the scan ("ranks/finish") into d.rrank / d.met.
+template <typename T>
+static int rank_run(hipStream_t st, const T* U, const T* V, int r, int ld, int64_t d2, const int64_t* xptr, const int32_t* xitem,
+                    RankDev& d, Profiler* prof) {
+    const int64_t n = (int64_t)d.rel.users.size(), nrel = (int64_t)d.rel.ritem.size();
+    if (n <= 0) return PCR_OK;
+    DBuf<T> us, rs;
+    DBuf<int32_t> ri, hist;
+    RC(us.alloc((size_t)nrel)); RC(rs.alloc((size_t)nrel)); RC(ri.alloc((size_t)nrel));
+    {
+        ProfScope ps(prof, "ranks/relscore", st);
+        hipLaunchKernelGGL((k_rank_relscore<T>), dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, U, V, r, ld, (const int32_t*)d.users.p, n,
+                           (const int64_t*)d.rptr.p, (const int32_t*)d.ritem.p, us.p);
+        hipLaunchKernelGGL((k_rank_sort<T>), dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, n, (const int64_t*)d.rptr.p, (const int32_t*)d.ritem.p,
+                           (const T*)us.p, rs.p, ri.p, d.rslot.p);
+        HIPCHK(hipGetLastError());
+    }
+    RecGeom geom(n, d2, sizeof(int32_t) * (size_t)((nrel + n + n - 1) / n));
+    const int64_t cap = pcr_tune_int("ranks_batch_users", 0);
+    if (cap > 0) {
+        geom.nb = std::min(geom.nb, (cap + RecGeom::users_per_wg - 1) / RecGeom::users_per_wg * RecGeom::users_per_wg);
+        geom.smax = geom.splits_for(std::min(geom.nb, n));
+    }
+    const std::vector<int64_t>& rp = d.rel.rptr;
+    auto buckets = [&](int64_t b0, int64_t m) { return rp[(size_t)(b0 + m)] - rp[(size_t)b0] + m; };
+    size_t hmax = 0;
+    for (int64_t b0 = 0; b0 < n; b0 += geom.nb) hmax = std::max(hmax, (size_t)buckets(b0, std::min(geom.nb, n - b0)));
+    RC(hist.alloc(hmax * (size_t)geom.smax));
+    const size_t lds = rank_wave_lds<T>() * rec::WAVES;
+    for (int64_t b0 = 0; b0 < n; b0 += geom.nb) {
+        const int64_t m = std::min(geom.nb, n - b0), hsplit = buckets(b0, m);
+        int per, nsp;
+        geom.batch(m, &per, &nsp);
+        {
+            ProfScope ps(prof, "ranks/count", st);
+            HIPCHK(hipMemsetAsync(hist.p, 0, (size_t)nsp * (size_t)hsplit * sizeof(int32_t), st));
+            hipLaunchKernelGGL((k_rank_count<T>), dim3((unsigned)cdiv(m, RecGeom::users_per_wg), (unsigned)nsp), dim3(rec::WAVES * 64), lds, st, U, V,
+                               r, ld, (int)d2, (const int32_t*)d.users.p + b0, m, xptr, xitem, per, (const int64_t*)d.rptr.p + b0, (const T*)rs.p,
+                               (const int32_t*)ri.p, hist.p, hsplit);
+            HIPCHK(hipGetLastError());
+        }
+        ProfScope ps(prof, "ranks/finish", st);
+        hipLaunchKernelGGL(k_rank_finish, dim3((unsigned)cdiv(m, 4)), dim3(256), 0, st, (const int32_t*)hist.p, hsplit, nsp, m,
+                           (const int64_t*)d.rptr.p + b0, (const int32_t*)d.rslot.p, d.rrank.p, d.met.p + (size_t)b0 * 6);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(st));                      // (us / rs / ri / hist are freed on return)
+    return PCR_OK;
+}
+
 // users of one CSR grouped by length class; each class has its own workgroup size
 struct Bin {
     int block = 64;
@@ -389,6 +521,8 @@ struct pcr_solver {
     virtual int recommend(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores) = 0;
     // pcr_evaluate_topn (arguments checked by the caller)
     virtual int evaluate_topn(int ncut, const int* cuts, double threshold, int flags, pcr_topn_stats* stats, double* per_user) = 0;
+    // pcr_evaluate_ranks (arguments checked by the caller)
+    virtual int evaluate_ranks(double threshold, int flags, pcr_rank_stats* stats, double* per_user, int64_t* ranks) = 0;
 };
 
 // launch knobs: pcr_tune() values read once when the solver is created (include/primalcr.h lists them)
@@ -519,6 +653,7 @@ struct Solver final : pcr_solver {
     std::vector<int32_t> h_test_item;             // the test shard's ratings (rows: ev[1].h_uptr), for pcr_evaluate_topn
     std::vector<double> h_test_val;
     TopnDev topn;
+    RankDev rankd;
     // ---- factors and CG vectors (d2 x ld, nu x ld)
     DBuf<T> d_U, d_V, d_Vnew, d_g, d_delta, d_rr, d_p, d_Hp;
     CGState* d_cgp = nullptr;                     // the CG scalars live in d_scal[32..43): they come back with the objective's read-back
@@ -2498,6 +2633,18 @@ struct Solver final : pcr_solver {
     int evaluate_topn(int ncut, const int* cuts, double thr, int flags, pcr_topn_stats* stats, double* per_user) override {
         return evaluate_topn_with(ncut, cuts, thr, flags, stats, per_user, &prof);
     }
+    // exact rank metrics of the shard's users against its test ratings; the relevance table is built on the first call for a
+    // threshold and kept in rankd
+    int evaluate_ranks_with(double thr, int flags, pcr_rank_stats* stats, double* per_user, int64_t* ranks, Profiler* prof) {
+        if (!rankd.same(thr)) RC(rankd.build(n_users, ev[1].h_uptr.data(), h_test_item.data(), h_test_val.data(), thr));
+        const bool ex = (flags & PCR_REC_EXCLUDE_TRAIN) != 0;
+        RC(rank_run<T>(st, d_U.p, d_V.p, geo.r, geo.ld, d2, ex ? d_uptr.p : nullptr, ex ? d_item.p : nullptr, rankd, prof));
+        return rankd.finish(st, prof, [this](double* p, size_t n) { return allreduce_f64(p, n); }, [this] { return sync_checked(); }, stats,
+                            n_users, per_user, ev[1].h_uptr.data(), h_test_item.data(), h_test_val.data(), ranks);
+    }
+    int evaluate_ranks(double thr, int flags, pcr_rank_stats* stats, double* per_user, int64_t* ranks) override {
+        return evaluate_ranks_with(thr, flags, stats, per_user, ranks, &prof);
+    }
     int recommend(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores) override {
         return recommend_with(n, local, K, flags, items, scores, &prof);
     }
@@ -2815,6 +2962,29 @@ int pcr_evaluate_topn_model(const double* U, int64_t d1, const double* V, int64_
     });
 }
 
+int pcr_evaluate_ranks_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                             const int64_t* tindex, const int32_t* titem, const double* tval, double threshold, int dtype,
+                             pcr_rank_stats* stats, double* per_user, int64_t* ranks, int device) {
+    return abi_guard("pcr_evaluate_ranks_model", [&]() -> int {
+    bool sorted = true;
+    RC(pcr_evaluate_ranks_model_check(U, d1, V, d2, k, index, item, tindex, titem, tval, threshold, dtype, stats, &sorted));
+    RC(model_device(device));
+    auto run = [&](auto zero) -> int {
+        using T = decltype(zero);
+        hipStream_t st = nullptr;
+        ModelDev<T> M;
+        RC(M.upload_exclusion(d1, index, item, sorted));
+        RankDev D;
+        RC(D.build(d1, tindex, titem, tval, threshold));
+        RC(M.upload_factors(st, U, d1, V, d2, k));
+        RC(rank_run<T>(st, M.U(), M.V(), (int)k, M.ld, d2, M.dx.p, M.di.p, D, nullptr));
+        return D.finish(st, nullptr, [](double*, size_t) { return PCR_OK; }, [st] { HIPCHK(hipStreamSynchronize(st)); return PCR_OK; }, stats, d1,
+                        per_user, tindex, titem, tval, ranks);
+    };
+    return dtype == PCR_F64 ? run(0.0) : run(0.0f);
+    });
+}
+
 int pcr_recommend(pcr_solver* s, int64_t n, const int32_t* users, int topk, int flags, int32_t* items, double* scores) {
     S_OR_ARG;
     if (topk < 1 || topk > PCR_RECOMMEND_MAX_K) { pcr_set_error("pcr_recommend: K = " + std::to_string(topk) + " outside [1, " + std::to_string(PCR_RECOMMEND_MAX_K) + "]"); return PCR_ERR_ARG; }
@@ -2844,6 +3014,14 @@ int pcr_evaluate_topn(pcr_solver* s, int ncut, const int* cutoffs, double thresh
     RC(pcr_topn_check("pcr_evaluate_topn", ncut, cutoffs, threshold, stats));
     if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_evaluate_topn: unknown flags"); return PCR_ERR_ARG; }
     return abi_guard("pcr_evaluate_topn", [&]() -> int { return s->evaluate_topn(ncut, cutoffs, threshold, flags, stats, per_user); });
+}
+
+int pcr_evaluate_ranks(pcr_solver* s, double threshold, int flags, pcr_rank_stats* stats, double* per_user, int64_t* ranks) {
+    S_OR_ARG;
+    if (std::isnan(threshold)) { pcr_set_error("pcr_evaluate_ranks: threshold is NaN"); return PCR_ERR_ARG; }
+    if (!stats) { pcr_set_error("pcr_evaluate_ranks: null stats"); return PCR_ERR_ARG; }
+    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_evaluate_ranks: unknown flags"); return PCR_ERR_ARG; }
+    return abi_guard("pcr_evaluate_ranks", [&]() -> int { return s->evaluate_ranks(threshold, flags, stats, per_user, ranks); });
 }
 
 }  // extern "C"

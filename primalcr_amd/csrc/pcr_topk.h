@@ -17,6 +17,8 @@
 //   lists), converts the scores to double and pads with (-1, -inf).
 // k_rec_merge_topn: the same merge for the full-catalogue top-N evaluation (pcr_evaluate_topn): the list
 //   stays in LDS and is scored against the user's relevant test items; k_topn_sum1 / k_topn_fin reduce the per-user metrics.
+// k_rank_relscore / k_rank_sort / k_rank_count / k_rank_finish: the exact full-catalogue rank metrics (pcr_evaluate_ranks, DESIGN.md
+//   section 3.12): the same sweep with a counting tail in place of the selecting one, at the end of this file.
 // No atomic decides a result: the LDS slot counter only decides where a candidate sits in the buffer, and the merges rank by
 // the total order (score, id), so every list is the same whatever the order of arrival.
 #pragma once
@@ -30,6 +32,8 @@ constexpr int UW = 16;        // users per wave (the columns of the MFMA tile)
 constexpr int NQ = 4;         // 16-item MFMA tiles per step
 constexpr int TILE = 16 * NQ; // items per step
 constexpr int CAP = 64;       // candidate slots per user; a merge is due when fewer than 16 are free
+constexpr int RANK_STAGE = 32;            // k_rank_count: relevant rows up to this length are staged (and counted) in LDS
+constexpr int RANK_LD = RANK_STAGE + 1;   // their LDS row stride (scores, ids, histogram): odd, see rank_wave_lds
 }  // namespace rec
 
 template <typename T> struct RecMma;
@@ -60,6 +64,39 @@ __host__ __device__ inline size_t rec_wave_lds(int K) {
     return (b + 15) & ~(size_t)15;
 }
 
+// The scores of one step: acc[q] = the 16 x 16 tile of the rows row_of(q) of V (the A operand; row_of is asked by lane m = lane & 15
+// for its row of tile q, -1: none, a zero row) against the wave's 16 user columns (the B operand: lane m + 16 g holds its user's
+// row Ur, inactive columns are zero).  Lane group g loads 16 bytes of a row per k-step for both operands, so the k order of a
+// score is fixed by this code alone and depends on its (row of U, row of V) only: every caller that scores a pair through here
+// gets the same bits (k_rec_score, k_rank_count and k_rank_relscore rely on that).
+template <typename T, class RowOf>
+__device__ __forceinline__ void rec_score_tile(const T* __restrict__ Ur, bool active, const T* __restrict__ V, int r, int ld, int g,
+                                               RowOf&& row_of, typename RecMma<T>::acc_t (&acc)[rec::NQ]) {
+    typedef RecMma<T> M;
+    typedef typename M::acc_t acc_t;
+    typedef typename M::vec_t vec_t;
+    constexpr int KV = M::KV;
+#pragma unroll
+    for (int q = 0; q < rec::NQ; ++q) acc[q] = acc_t{};
+    for (int c = 0; c < ld; c += 4 * KV) {          // wave-uniform trip count: the MFMAs run with every lane
+        const int c0 = c + g * KV;
+        vec_t b = vec_t{};
+        if (active && c0 < ld) b = *(const vec_t*)(Ur + c0);
+#pragma unroll
+        for (int e = 0; e < KV; ++e) if (c0 + e >= r) b[e] = (T)0;
+#pragma unroll
+        for (int q = 0; q < rec::NQ; ++q) {
+            const int jr = row_of(q);
+            vec_t a = vec_t{};
+            if (jr >= 0 && c0 < ld) a = *(const vec_t*)(V + (size_t)(unsigned)jr * (unsigned)ld + c0);
+#pragma unroll
+            for (int e = 0; e < KV; ++e) if (c0 + e >= r) a[e] = (T)0;
+#pragma unroll
+            for (int e = 0; e < KV; ++e) acc[q] = M::mma(a[e], b[e], acc[q]);
+        }
+    }
+}
+
 // partial lists: [split][n][K] scores and ids, [split][n] lengths
 template <typename T>
 __global__ __launch_bounds__(256) void k_rec_score(const T* __restrict__ U, const T* __restrict__ V, int r, int ld, int d2,
@@ -69,8 +106,6 @@ __global__ __launch_bounds__(256) void k_rec_score(const T* __restrict__ U, cons
                                                    int32_t* __restrict__ lst_n, int select) {
     typedef RecMma<T> M;
     typedef typename M::acc_t acc_t;
-    typedef typename M::vec_t vec_t;
-    constexpr int KV = M::KV;
     extern __shared__ __align__(16) char rec_lds[];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     char* wl = rec_lds + (size_t)w * rec_wave_lds<T>(K);
@@ -152,25 +187,7 @@ __global__ __launch_bounds__(256) void k_rec_score(const T* __restrict__ U, cons
     const T* Ur = U + (size_t)(unsigned)u * (unsigned)ld;
     for (int j0 = jb; j0 < je; j0 += rec::TILE) {
         acc_t acc[rec::NQ];
-#pragma unroll
-        for (int q = 0; q < rec::NQ; ++q) acc[q] = acc_t{};
-        for (int c = 0; c < ld; c += 4 * KV) {          // wave-uniform trip count: the MFMAs run with every lane
-            const int c0 = c + g * KV;
-            vec_t b = vec_t{};
-            if (active && c0 < ld) b = *(const vec_t*)(Ur + c0);
-#pragma unroll
-            for (int e = 0; e < KV; ++e) if (c0 + e >= r) b[e] = (T)0;
-#pragma unroll
-            for (int q = 0; q < rec::NQ; ++q) {
-                const int jr = j0 + 16 * q + m;
-                vec_t a = vec_t{};
-                if (jr < je && c0 < ld) a = *(const vec_t*)(V + (size_t)(unsigned)jr * (unsigned)ld + c0);
-#pragma unroll
-                for (int e = 0; e < KV; ++e) if (c0 + e >= r) a[e] = (T)0;
-#pragma unroll
-                for (int e = 0; e < KV; ++e) acc[q] = M::mma(a[e], b[e], acc[q]);
-            }
-        }
+        rec_score_tile<T>(Ur, active, V, r, ld, g, [&](int q) { const int jr = j0 + 16 * q + m; return jr < je ? jr : -1; }, acc);
         if (!select) {                                 // (tools/exp_recommend.py: the GEMM alone; the NaN test keeps it alive)
             T t = (T)0;
 #pragma unroll
@@ -370,4 +387,218 @@ __global__ __launch_bounds__(PCR_EW_BLOCK) void k_topn_fin(const double* __restr
         if (threadIdx.x == 0) out[c * 8 + f] = x;
     }
     if (c == 0 && threadIdx.x == 0) out[gridDim.x * 8] = (double)n;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Exact full-catalogue rank metrics (pcr_evaluate_ranks, include/primalcr.h).  Per counted user a
+// histogram over |R_u| + 1 buckets: bucket b counts the eligible non-relevant items that have exactly b relevant items before
+// them.  The relevance tables are TopnArgs' (rptr / ritem: distinct items, item-ascending).
+
+// One wave per counted user: the scores of its relevant items, us[rptr[idx] + t] for ritem[rptr[idx] + t], 64 per step through
+// rec_score_tile -- the same chain as the sweep's, so that the sweep recognises a relevant item by its (score, id).  All 16
+// columns of the tile are this one user; column 0 is read.
+template <typename T>
+__global__ __launch_bounds__(256) void k_rank_relscore(const T* __restrict__ U, const T* __restrict__ V, int r, int ld,
+                                                       const int32_t* __restrict__ users, int64_t n, const int64_t* __restrict__ rptr,
+                                                       const int32_t* __restrict__ ritem, T* __restrict__ us) {
+    typedef RecMma<T> M;
+    typedef typename M::acc_t acc_t;
+    const int lane = threadIdx.x & 63;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (idx >= n) return;                               // (the whole wave)
+    const int m = lane & 15, g = lane >> 4;
+    const int64_t rb = rptr[idx], nr = rptr[idx + 1] - rb;
+    const T* Ur = U + (size_t)(unsigned)users[idx] * (unsigned)ld;
+    for (int64_t t0 = 0; t0 < nr; t0 += rec::TILE) {
+        acc_t acc[rec::NQ];
+        rec_score_tile<T>(Ur, true, V, r, ld, g, [&](int q) { const int64_t t = t0 + 16 * q + m; return t < nr ? (int)ritem[rb + t] : -1; }, acc);
+#pragma unroll
+        for (int q = 0; q < rec::NQ; ++q)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int64_t t = t0 + 16 * q + M::crow(j, lane);
+                if (m == 0 && t < nr) us[rb + t] = acc[q][j];
+            }
+    }
+}
+
+// One wave per counted user: its relevant row in the order of a list (rec_better) by rank counting, as the merges do: rs / ri
+// the sorted scores and ids, rslot[t] = the position in the item-ascending row of the t-th entry.  The ids of a row are
+// distinct, so the order is strict and every rank is taken once.
+template <typename T>
+__global__ __launch_bounds__(256) void k_rank_sort(int64_t n, const int64_t* __restrict__ rptr, const int32_t* __restrict__ ritem,
+                                                   const T* __restrict__ us, T* __restrict__ rs, int32_t* __restrict__ ri,
+                                                   int32_t* __restrict__ rslot) {
+    const int lane = threadIdx.x & 63;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (idx >= n) return;
+    const int64_t rb = rptr[idx];
+    const int nr = (int)(rptr[idx + 1] - rb);
+    for (int p = lane; p < nr; p += 64) {
+        const T s = us[rb + p];
+        const int j = ritem[rb + p];
+        int rk = 0;
+        for (int e = 0; e < nr; ++e) rk += rec_better(us[rb + e], ritem[rb + e], s, j) ? 1 : 0;
+        rs[rb + rk] = s; ri[rb + rk] = j; rslot[rb + rk] = p;
+    }
+}
+
+// LDS of one wave of k_rank_count: per user column a staged relevant row (RANK_LD scores, RANK_LD ids) and its histogram
+// (RANK_LD counters).  The odd stride puts entry t of the 16 users of a wave into 16 different banks (32 in fp64, two per
+// entry), so neither the probes of a binary search that run in step nor the adds to equal buckets share a bank.
+template <typename T>
+__host__ __device__ inline size_t rank_wave_lds() {
+    const size_t b = (size_t)rec::UW * rec::RANK_LD * (sizeof(T) + 2 * sizeof(int));
+    return (b + 15) & ~(size_t)15;
+}
+
+// b = the number of entries of the sorted row (s[t], id[t]), t < nr, that come before (sc, item); -1 when the item meets itself
+template <typename T, class S, class I>
+__device__ __forceinline__ int rank_bucket(const S s, const I id, int nr, T sc, int item) {
+    int a = 0, b = nr;
+    while (a < b) { const int mid = (a + b) >> 1; if (rec_better(s[mid], id[mid], sc, item)) a = mid + 1; else b = mid; }
+    return (a < nr && s[a] == sc && id[a] == item) ? -1 : a;
+}
+
+// The counting sweep: k_rec_score's layout (a wave owns 16 users, a lane keeps one user, 64 items per step, the same exclusion
+// cursor and item splits on blockIdx.y) with this tail: every eligible score is placed into the user's sorted relevant row.
+// The best and the worst relevant (score, id) sit in registers: an item before the best goes to bucket 0 and one after the
+// worst to bucket nr without a search, in per-lane register counters (most of the catalogue).  The others are searched: rows
+// of at most RANK_STAGE entries in LDS with an LDS integer add, longer ones in global memory (rs / ri, L2-resident) with a
+// global integer add.  An item that compares equal to a row entry (same score, same id) is a relevant item meeting itself and
+// is not counted.  Integer adds commute: the histogram is the same whatever the order of arrival.
+// hist: [split][hsplit] counters, zeroed by the caller; user idx's nr + 1 buckets start at (rptr[idx] - rptr[0]) + idx.
+template <typename T>
+__global__ __launch_bounds__(256) void k_rank_count(const T* __restrict__ U, const T* __restrict__ V, int r, int ld, int d2,
+                                                    const int32_t* __restrict__ users, int64_t n,
+                                                    const int64_t* __restrict__ xptr, const int32_t* __restrict__ xitem, int per_split,
+                                                    const int64_t* __restrict__ rptr, const T* __restrict__ rs, const int32_t* __restrict__ ri,
+                                                    int32_t* __restrict__ hist, int64_t hsplit) {
+    typedef RecMma<T> M;
+    typedef typename M::acc_t acc_t;
+    extern __shared__ __align__(16) char rec_lds[];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int m = lane & 15, g = lane >> 4;
+    char* wl = rec_lds + (size_t)w * rank_wave_lds<T>();
+    T* ls = (T*)wl + m * rec::RANK_LD;
+    int* li = (int*)((T*)wl + rec::UW * rec::RANK_LD) + m * rec::RANK_LD;
+    int* lh = li + rec::UW * rec::RANK_LD;
+
+    const int64_t idx = ((int64_t)blockIdx.x * rec::WAVES + w) * rec::UW + m;
+    const bool active = idx < n;
+    const int u = active ? users[idx] : 0;
+    const int jb = (int)blockIdx.y * per_split;
+    const int je = min(d2, jb + per_split);
+    int64_t cur = 0, cend = 0;
+    if (xptr && active) {
+        cur = xptr[u]; cend = xptr[u + 1];
+        int64_t hi = cend;
+        while (cur < hi) { const int64_t mid = (cur + hi) >> 1; if (xitem[mid] < jb) cur = mid + 1; else hi = mid; }
+    }
+    int nr = 0;
+    const T* gs = rs;
+    const int32_t* gi = ri;
+    int32_t* gh = hist;
+    T best_s = (T)0, worst_s = (T)0;
+    int best_i = 0, worst_i = 0;
+    if (active) {                                      // (a counted user: nr >= 1)
+        const int64_t rb = rptr[idx];
+        nr = (int)(rptr[idx + 1] - rb);
+        gs += rb; gi += rb;
+        gh += (size_t)blockIdx.y * (size_t)hsplit + (size_t)(rb - rptr[0]) + (size_t)idx;
+        best_s = gs[0]; best_i = gi[0]; worst_s = gs[nr - 1]; worst_i = gi[nr - 1];
+    }
+    const bool staged = active && nr <= rec::RANK_STAGE;
+    if (staged) {
+        for (int t = g; t < nr; t += 4) { ls[t] = gs[t]; li[t] = gi[t]; }
+        for (int t = g; t <= nr; t += 4) lh[t] = 0;
+    }
+    wave_sync();
+    int c_lo = 0, c_hi = 0;
+
+    const T* Ur = U + (size_t)(unsigned)u * (unsigned)ld;
+    for (int j0 = jb; j0 < je; j0 += rec::TILE) {
+        acc_t acc[rec::NQ];
+        rec_score_tile<T>(Ur, active, V, r, ld, g, [&](int q) { const int jr = j0 + 16 * q + m; return jr < je ? jr : -1; }, acc);
+        unsigned long long xm = 0;                     // this step's rated items of the lane's user
+        while (cur < cend) {
+            const int it = xitem[cur];
+            if (it >= j0 + rec::TILE) break;
+            xm |= 1ull << (it - j0);
+            ++cur;
+        }
+#pragma unroll
+        for (int q = 0; q < rec::NQ; ++q) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int jl = 16 * q + M::crow(j, lane);
+                const int item = j0 + jl;
+                const T s = acc[q][j];
+                if (!(active && item < je && !((xm >> jl) & 1ull))) continue;
+                if (rec_better(s, item, best_s, best_i)) ++c_lo;
+                else if (rec_better(worst_s, worst_i, s, item)) ++c_hi;
+                else if (staged) {
+                    const int b = rank_bucket<T>(ls, li, nr, s, item);
+                    if (b >= 0) atomicAdd(&lh[b], 1);
+                } else {
+                    const int b = rank_bucket<T>(gs, gi, nr, s, item);
+                    if (b >= 0) atomicAdd(&gh[b], 1);
+                }
+            }
+        }
+    }
+    // the four lanes of a user add up their end buckets; lane group 0 holds the sums
+    c_lo += __shfl_xor(c_lo, 16); c_lo += __shfl_xor(c_lo, 32);
+    c_hi += __shfl_xor(c_hi, 16); c_hi += __shfl_xor(c_hi, 32);
+    wave_sync();
+    if (staged) {
+        for (int t = g; t <= nr; t += 4) gh[t] = lh[t] + (t == 0 ? c_lo : 0) + (t == nr ? c_hi : 0);
+    } else if (active && g == 0) {
+        atomicAdd(&gh[0], c_lo);
+        atomicAdd(&gh[nr], c_hi);
+    }
+}
+
+// One wave per counted user: the splits' histograms summed and scanned.  With cum(t) = sum_{b <= t} hist[b], the t-th entry of
+// the sorted relevant row has rank 1 + t + cum(t) (t relevant and cum(t) non-relevant items before it), |N_u| = cum(nr) and
+// the (relevant, non-relevant) pairs in the right order number sum_t (|N_u| - cum(t)).  Writes rrank[rptr[idx] + rslot] (the
+// ranks in the item-ascending order of the relevance table) and the user's row met[idx][6] = |R_u|, rr, mean_rank, mpr,
+// first_rank, auc -- the column order k_topn_sum1 reduces (columns 0, 1, 2, 4 summed, column 0 > 0 counted, column 5 summed
+// and counted where it is not NaN).  Every quotient is one fp64 division of two exact integers.
+__global__ __launch_bounds__(256) void k_rank_finish(const int32_t* __restrict__ hist, int64_t hsplit, int nsplit, int64_t n,
+                                                     const int64_t* __restrict__ rptr, const int32_t* __restrict__ rslot,
+                                                     int64_t* __restrict__ rrank, double* __restrict__ met) {
+    const int lane = threadIdx.x & 63;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (idx >= n) return;
+    const int64_t rb = rptr[idx], nr = rptr[idx + 1] - rb;
+    const int32_t* h = hist + (size_t)(rb - rptr[0]) + (size_t)idx;
+    long long carry = 0, first = 0;
+    double sum_rank = 0.0, sum_cum = 0.0;               // (integers below 2^53: exact in any order)
+    for (int64_t t0 = 0; t0 <= nr; t0 += 64) {
+        const int64_t t = t0 + lane;
+        long long c = 0;
+        if (t <= nr) for (int sp = 0; sp < nsplit; ++sp) c += h[(size_t)sp * (size_t)hsplit + (size_t)t];
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const long long x = __shfl_up(c, d); if (lane >= d) c += x; }
+        c += carry;
+        if (t < nr) {
+            const long long rank = 1 + t + c;
+            rrank[rb + rslot[rb + t]] = rank;
+            sum_rank += (double)rank; sum_cum += (double)c;
+            if (t == 0) first = rank;
+        }
+        carry = __shfl(c, 63);
+    }
+    first = __shfl(first, 0);
+    sum_rank = wave_sum(sum_rank); sum_cum = wave_sum(sum_cum);
+    const double R = (double)nr, N = (double)carry;
+    const double pairs = R * N, span = R * (N + R - 1.0);
+    double v = R;
+    if (lane == 1) v = 1.0 / (double)first;
+    else if (lane == 2) v = sum_rank / R;
+    else if (lane == 3) v = span > 0.0 ? (sum_rank - R) / span : 0.0;
+    else if (lane == 4) v = (double)first;
+    else if (lane == 5) v = pairs > 0.0 ? (pairs - sum_cum) / pairs : (double)NAN;
+    if (lane < 6) met[(size_t)idx * 6 + lane] = v;
 }

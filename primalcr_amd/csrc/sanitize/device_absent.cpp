@@ -77,4 +77,11 @@ int pcr_evaluate_topn_model(const double* U, int64_t d1, const double* V, int64_
     return rc != PCR_OK ? rc : absent();
 }
 NO_SOLVER(pcr_evaluate_topn, pcr_solver*, int, const int*, double, int, pcr_topn_stats*, double*)
+int pcr_evaluate_ranks_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                             const int64_t* tindex, const int32_t* titem, const double* tval, double threshold, int dtype,
+                             pcr_rank_stats* stats, double*, int64_t*, int) {
+    const int rc = pcr_evaluate_ranks_model_check(U, d1, V, d2, k, index, item, tindex, titem, tval, threshold, dtype, stats, nullptr);
+    return rc != PCR_OK ? rc : absent();
+}
+NO_SOLVER(pcr_evaluate_ranks, pcr_solver*, double, int, pcr_rank_stats*, double*, int64_t*)
 }
