@@ -503,6 +503,63 @@ int pcr_evaluate_ranks_model(const double *U, int64_t d1, const double *V, int64
 int pcr_evaluate_ranks(pcr_solver *s, double threshold, int flags,
                        pcr_rank_stats *stats, double *per_user, int64_t *ranks);                   /* [device] */
 
+/* ------------------------------------------------------------------------- */
+/* beyond-accuracy top-N metrics: catalogue coverage, Gini index of item      */
+/* exposure, novelty, intra-list diversity (no reference counterpart)         */
+/* ------------------------------------------------------------------------- */
+/* What the recommended lists look like, whatever the held-out ratings say: whether every user gets the same popular items and
+ * how varied one user's list is.  The lists are selected, walked and reduced on the device; no list leaves it and no test set
+ * is involved.  For every requested user u and cutoff c (cutoffs as in the top-N evaluation):
+ *   List L_u           exactly the list pcr_recommend / pcr_recommend_model returns with the same factors, dtype and exclusion
+ *                      and K = cutoffs[ncut - 1]; len(u, c) = the number of non-padding entries among the first c.
+ *   Users              users[n] as in pcr_recommend (NULL: all users, in order); an id listed twice counts twice; every
+ *                      requested user is counted, also with len = 0.
+ *   Exposure           x_c[j] = the number of requested users with j in L_u[0..c): integers.
+ *   From exposure      recs_c = sum_j x_c[j];  items_covered_c = #{j : x_c[j] > 0};  coverage_c = items_covered_c / d2 (one
+ *                      fp64 division);  gini_c = (sum_{i = 1..d2} (2 i - d2 - 1) x_(i)) / (d2 recs_c) with x_(1) <= ... <= x_(d2)
+ *                      the exposure sorted ascending: numerator and denominator are formed as 128-bit integers, each is
+ *                      converted to double once, then one division; 0 when recs_c = 0.
+ *   Popularity         pop[j] = the number of training-CSR entries with item j over all d1 users (duplicated pairs counted);
+ *                      info[j] = log2((double)(d1 + 1) / (double)(pop[j] + 1)), built once on the host in fp64.
+ *   Novelty            novelty(u, c) = (sum_{i < len} info[L_u[i]]) / len; NaN when len = 0.
+ *   ILD                ild(u, c) = 1 - (sum_{a < b < len} cos(L_u[a], L_u[b])) / (len (len - 1) / 2), cos(a, b) = v^_a . v^_b,
+ *                      v^_j = V[j] / |V[j]| in fp64 from the factors as the dtype stores them (f32-rounded for PCR_F32); a
+ *                      row of norm 0 has v^_j = 0.  NaN when len < 2.  Always accumulated in fp64.
+ *   Summary per cutoff users (n), users_ild (users with a defined ild), recs, items_covered, coverage, gini, novelty (mean over
+ *                      the users with len >= 1), ild (mean over users_ild).  A denominator of 0 gives 0.
+ *   Determinism        as the top-N evaluation: per-user values depend on (u, its list, V) alone; exposure is built with
+ *                      integer adds, so it does not depend on their order; the sums over users run in a fixed order (the order
+ *                      of users[]); two identical calls are bitwise identical.
+ * per_user (optional, NULL: not written): [n][ncut][PCR_DIVERSITY_FIELDS] = len, novelty, ild; row i is for users[i].
+ * exposure (optional, NULL: not written): int64 [ncut][d2] = x_c[j]. */
+#define PCR_DIVERSITY_FIELDS 3
+typedef struct pcr_diversity_stats {
+    int     cutoff;
+    int64_t users, users_ild, recs, items_covered;
+    double  coverage, gini, novelty, ild;
+} pcr_diversity_stats;
+/* The closing arithmetic above for ONE cutoff's exposure row x[d2] (every entry >= 0): recs, items_covered, coverage, gini.
+ * Both device entries use it; a caller who sums the exposure rows of local-only shards finishes the job with it.
+ * PCR_ERR_ARG for a NULL row, d2 < 1, a negative entry or a row whose sum exceeds INT64_MAX (recs could not hold it). */
+int pcr_exposure_stats(const int64_t *exposure, int64_t d2, int64_t *recs, int64_t *items_covered,
+                       double *coverage, double *gini);                                             /* [host] */
+/* Standalone: the factors, dtype, users[n] and host-side checks as pcr_recommend_model, the cutoff checks of
+ * pcr_evaluate_topn_model; everything is checked on the host before any device is looked for.  index / item (the training
+ * CSR) give both the exclusion and the popularity; NULL: no exclusion and pop = 0. */
+int pcr_evaluate_diversity_model(const double *U, int64_t d1, const double *V, int64_t d2, int64_t k,
+                                 const int64_t *index, const int32_t *item,
+                                 int64_t n, const int32_t *users, int ncut, const int *cutoffs, int dtype,
+                                 pcr_diversity_stats *stats, double *per_user, int64_t *exposure, int device);   /* [device] */
+/* On a live PCR, PCR++ or CCDR1 solver: its device factors, storage type and stream; users[n] are GLOBAL ids of this rank's
+ * shard as in pcr_recommend (NULL: all of the shard's users, n = its n_users); flags PCR_REC_EXCLUDE_TRAIN.  Popularity comes
+ * from the solver's training ratings (whether or not they are excluded) with d1 = the job's total; training state is not
+ * touched.  N ranks with a communicator: pop, exposure and the per-user sums are all-reduced and every rank returns the totals
+ * (every rank must call; an RCCL communicator -- on a peer-to-peer communicator the entry is PCR_ERR_UNSUPPORTED, its fp64
+ * exchange being a 64-double slot); a local-only shard returns its own partials, with pop from its own ratings.
+ * Profile slots: recommend/score, and recommend/diversity (the row norms, the merge with the metrics fused in, the reductions). */
+int pcr_evaluate_diversity(pcr_solver *s, int64_t n, const int32_t *users, int ncut, const int *cutoffs, int flags,
+                           pcr_diversity_stats *stats, double *per_user, int64_t *exposure);                 /* [device] */
+
 /* per-kernel device timing (HIP events on the solver's stream, one pair per launch).
  * slot names: "<class>/<workgroup size>[.<length bound>][g][c][l][r][#n]" for the per-user kernels (classes
  * prepare, vgrad, vhv, ustep; g = global-scratch variant, c = workgroup clusters, l = k_ustep's latency form (8 rows

@@ -13,6 +13,7 @@ PCR_REC_EXCLUDE_TRAIN = 1
 PCR_TOPN_MAX_CUTOFFS = 8
 TOPN_FIELDS = ("hits", "precision", "recall", "ap", "ndcg", "ndcg_graded")   # per_user columns
 RANK_FIELDS = ("first_rank", "rr", "mean_rank", "auc", "mpr")                   # evaluate_ranks' per_user columns (PCR_RANK_FIELDS)
+DIVERSITY_FIELDS = ("len", "novelty", "ild")                                     # evaluate_diversity's per_user columns (PCR_DIVERSITY_FIELDS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -75,6 +76,12 @@ class IterStats(C.Structure):
 class TopnStats(C.Structure):
     _fields_ = [("cutoff", C.c_int), ("users", C.c_int64), ("users_graded", C.c_int64), ("hits", C.c_int64), ("precision", C.c_double),
                 ("recall", C.c_double), ("hit_rate", C.c_double), ("map", C.c_double), ("ndcg", C.c_double), ("ndcg_graded", C.c_double)]
+
+
+class DiversityStats(C.Structure):
+    """pcr_diversity_stats."""
+    _fields_ = [("cutoff", C.c_int), ("users", C.c_int64), ("users_ild", C.c_int64), ("recs", C.c_int64), ("items_covered", C.c_int64),
+                ("coverage", C.c_double), ("gini", C.c_double), ("novelty", C.c_double), ("ild", C.c_double)]
 
 
 class RankStats(C.Structure):
@@ -159,6 +166,9 @@ def lib():
     L.pcr_evaluate_topn.argtypes = [vp, ci, vp, cd, ci, vp, vp]
     L.pcr_evaluate_ranks_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, cd, ci, vp, vp, vp, ci]
     L.pcr_evaluate_ranks.argtypes = [vp, cd, ci, vp, vp, vp]
+    L.pcr_evaluate_diversity_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, vp, ci, vp, ci, vp, vp, vp, ci]
+    L.pcr_evaluate_diversity.argtypes = [vp, i64, vp, ci, vp, ci, vp, vp, vp]
+    L.pcr_exposure_stats.argtypes = [vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(cd), C.POINTER(cd)]
     L.pcr_profile_enable.argtypes = [vp, ci]
     L.pcr_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(cd), C.POINTER(i64)]
     L.pcr_profile_scope.argtypes = [vp, C.c_char_p, C.POINTER(i64), C.POINTER(i64)]
@@ -354,6 +364,59 @@ def evaluate_ranks(U, V, test, exclude=None, threshold=-np.inf, dtype=PCR_F64, d
     return _ranks_call(per_user, ranks, d1, tit.shape[0], lambda sp, pp, rp: lib().pcr_evaluate_ranks_model(
         U.ctypes.data, d1, V.ctypes.data, V.shape[0], k, None if idx is None else idx.ctypes.data, None if it is None else it.ctypes.data,
         tidx.ctypes.data, tit.ctypes.data, tval.ctypes.data, float(threshold), int(dtype), sp, pp, rp, device))
+
+
+def _diversity_call(cutoffs, per_user, exposure, n, d2, fn):
+    """Shared by evaluate_diversity() and Solver.evaluate_diversity(): fn(ncut, cutoffs_ptr, stats_ptr, per_user_ptr,
+    exposure_ptr) -> status.  Returns the list of per-cutoff dicts, then the per-user table and / or the exposure when asked for."""
+    cuts = np.ascontiguousarray(np.atleast_1d(np.asarray(cutoffs)), np.int32)
+    ncut = int(cuts.shape[0])
+    stats = (DiversityStats * max(ncut, 1))()
+    pu = np.empty((n, max(ncut, 1), len(DIVERSITY_FIELDS)), np.float64) if per_user else None
+    ex = np.empty((max(ncut, 1), d2), np.int64) if exposure else None
+    _chk(fn(ncut, cuts.ctypes.data, C.cast(stats, C.c_void_p), None if pu is None else pu.ctypes.data, None if ex is None else ex.ctypes.data))
+    out = ([{f: getattr(stats[c], f) for f, _ in DiversityStats._fields_} for c in range(ncut)],)
+    if per_user:
+        out += (pu,)
+    if exposure:
+        out += (ex,)
+    return out[0] if len(out) == 1 else out
+
+
+def evaluate_diversity(U, V, cutoffs=(10,), exclude=None, users=None, dtype=PCR_F64, device=0, per_user=False, exposure=False):
+    """Beyond-accuracy metrics of the top max(cutoffs) lists on the GPU (pcr_evaluate_diversity_model): catalogue coverage and the
+    Gini index of item exposure, novelty (mean self-information against the popularity of `exclude`'s ratings) and intra-list
+    diversity (1 - mean pairwise cosine of the listed rows of V).  exclude: a Dataset (its training CSR) or an (index, item)
+    pair -- exclusion and popularity -- or None; users: 0-based ids (None: all).  Returns one dict per cutoff (cutoff, users,
+    users_ild, recs, items_covered, coverage, gini, novelty, ild); with per_user also the array [n, ncut, 3] of DIVERSITY_FIELDS
+    (row i for users[i]; NaN novelty for an empty list, NaN ild below two items); with exposure also int64 [ncut, d2]."""
+    U = np.ascontiguousarray(U, np.float64); V = np.ascontiguousarray(V, np.float64)
+    d1, k = U.shape
+    idx = it = None
+    if exclude is not None:
+        if isinstance(exclude, Dataset):
+            idx, it, _ = exclude.csr(0)
+        else:
+            idx, it = exclude[:2]
+        idx = np.ascontiguousarray(idx, np.int64); it = np.ascontiguousarray(it, np.int32)
+        if idx.shape[0] != d1 + 1 or idx[-1] != it.shape[0]:
+            raise ValueError(f"exclude: index must have d1 + 1 = {d1 + 1} entries, the last equal to len(item) = {it.shape[0]}")
+    if users is not None:
+        users = np.ascontiguousarray(users, np.int32)
+    n = d1 if users is None else users.shape[0]
+    return _diversity_call(cutoffs, per_user, exposure, n, V.shape[0], lambda nc, cp, sp, pp, ep: lib().pcr_evaluate_diversity_model(
+        U.ctypes.data, d1, V.ctypes.data, V.shape[0], k, None if idx is None else idx.ctypes.data, None if it is None else it.ctypes.data,
+        n, None if users is None else users.ctypes.data, nc, cp, int(dtype), sp, pp, ep, device))
+
+
+def exposure_stats(x):
+    """The closing arithmetic of one exposure row (pcr_exposure_stats): dict(recs, items_covered, coverage, gini)."""
+    x = np.ascontiguousarray(x, np.int64)
+    if x.ndim != 1:
+        raise ValueError("exposure_stats: one exposure row (d2 counts)")
+    recs, cov, coverage, gini = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
+    _chk(lib().pcr_exposure_stats(x.ctypes.data, x.shape[0], recs, cov, coverage, gini))
+    return {"recs": recs.value, "items_covered": cov.value, "coverage": coverage.value, "gini": gini.value}
 
 
 def comm_unique_id() -> bytes:
@@ -654,6 +717,17 @@ class Solver:
             tnnz = int(tidx[lo + self.n_users] - tidx[lo])
         return _ranks_call(per_user, ranks, self.n_users, tnnz, lambda sp, pp, rp: lib().pcr_evaluate_ranks(
             self._h, float(threshold), PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, sp, pp, rp))
+
+    def evaluate_diversity(self, cutoffs=(10,), users=None, exclude_train=True, per_user=False, exposure=False):
+        """Beyond-accuracy metrics of this shard's users from the device factors (pcr_evaluate_diversity); the result as
+        evaluate_diversity(), popularity from the solver's training ratings.  users: GLOBAL 0-based ids of this rank's shard
+        (None: all of them, in order).  N ranks with a communicator: the totals of all ranks (every rank must call);
+        local-only shards: their own partials."""
+        if users is not None:
+            users = np.ascontiguousarray(users, np.int32)
+        n = self.n_users if users is None else users.shape[0]
+        return _diversity_call(cutoffs, per_user, exposure, n, self.d2, lambda nc, cp, sp, pp, ep: lib().pcr_evaluate_diversity(
+            self._h, n, None if users is None else users.ctypes.data, nc, cp, PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, sp, pp, ep))
 
     def sync(self):
         _chk(lib().pcr_solver_sync(self._h))

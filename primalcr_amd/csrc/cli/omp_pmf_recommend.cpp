@@ -12,11 +12,17 @@
 //     -c cutoffs     comma-separated ascending cutoffs, at most PCR_TOPN_MAX_CUTOFFS (default: -K)
 //     --threshold v  a test rating is relevant when >= v (default: every test rating)
 //     --ranks        also the exact full-catalogue rank metrics (pcr_evaluate_ranks_model)
+//   omp-pmf-recommend --diversity [-x data_dir] [-c c1,c2,...] [-u users_file] [-K topk] [--f32] model_file [output_file]
+//     --diversity    beyond-accuracy metrics of the lists (pcr_evaluate_diversity_model): coverage, Gini index of item exposure,
+//                    novelty (popularity from -x's training ratings) and intra-list diversity; not together with --eval
 // Output: one line per user, in input order: the 1-based user id, then the 1-based item ids (padding is left out).  Users go
 // to the device in batches, so host memory for the lists stays bounded on any catalogue.
 // With --eval: stdout gets one line per cutoff, "cutoff c users n users_graded n hits n precision x recall x hit_rate x map x
 // ndcg x ndcg_graded x" (values in %g); the output file, if given, one line per counted user at the largest cutoff: the 1-based
 // user id, then hits precision recall ap ndcg ndcg_graded (%g; nan where ndcg_graded is undefined).
+// With --diversity: stdout gets one line per cutoff, "diversity@c users n users_ild n recs n items_covered n coverage x gini x
+// novelty x ild x" (values in %g); the output file, if given, one line per requested user at the largest cutoff: the 1-based
+// user id, then len novelty ild (%g).
 // With --eval --ranks: after the cutoff lines one line "ranks users n users_auc n relevant n mrr x mean_rank x auc x mpr x"; the
 // output file then holds, per counted user, the 1-based user id, then first_rank rr mean_rank auc mpr (%g) instead.
 #include <algorithm>
@@ -45,6 +51,9 @@ static const char* USAGE =
     "    -c cutoffs     comma-separated ascending cutoffs, at most 8, each 1 .. 1024 (default: -K)\n"
     "    --threshold v  a test rating is relevant when >= v (default: every test rating)\n"
     "    --ranks        with --eval: also a line of exact full-catalogue rank metrics (mrr, mean_rank, auc, mpr)\n"
+    "       omp-pmf-recommend --diversity [-x data_dir] [-c c1,c2,...] [-u users_file] [-K topk] [--f32] model_file [output_file]\n"
+    "    --diversity    coverage, Gini index of item exposure, novelty (popularity from -x) and intra-list diversity of the lists;\n"
+    "                   output_file optional: per requested user at the largest cutoff, len novelty ild\n"
     "    output_file    with --eval optional: per counted user at the largest cutoff, hits precision recall ap ndcg ndcg_graded;\n"
     "                   with --ranks: per counted user first_rank rr mean_rank auc mpr\n";
 
@@ -165,9 +174,40 @@ static int run_eval(const char* edir, const std::vector<double>& U, const std::v
     return 0;
 }
 
+// --diversity: one line per cutoff to stdout, the per-user rows at the largest cutoff to out_path (if given)
+static int run_diversity(const std::vector<double>& U, const std::vector<double>& V, int64_t d1, int64_t d2, int64_t k,
+                         const std::vector<int64_t>* xindex, const std::vector<int32_t>* xitem, const std::vector<int32_t>& users,
+                         const std::vector<int>& cuts, bool f32, const char* out_path) {
+    const int nc = (int)cuts.size();
+    const int64_t n = (int64_t)users.size();
+    std::vector<pcr_diversity_stats> st((size_t)nc);
+    std::vector<double> per;
+    if (out_path) per.resize((size_t)n * nc * PCR_DIVERSITY_FIELDS);
+    if (pcr_evaluate_diversity_model(U.data(), d1, V.data(), d2, k, xindex ? xindex->data() : nullptr, xitem ? xitem->data() : nullptr, n,
+                                     users.data(), nc, cuts.data(), f32 ? PCR_F32 : PCR_F64, st.data(), out_path ? per.data() : nullptr, nullptr,
+                                     0) != PCR_OK) {
+        fprintf(stderr, "diversity: %s\n", pcr_last_error());
+        return 1;
+    }
+    for (const pcr_diversity_stats& s : st)
+        printf("diversity@%d users %lld users_ild %lld recs %lld items_covered %lld coverage %g gini %g novelty %g ild %g\n", s.cutoff,
+               (long long)s.users, (long long)s.users_ild, (long long)s.recs, (long long)s.items_covered, s.coverage, s.gini, s.novelty, s.ild);
+    if (!out_path) return 0;
+    FILE* fp = fopen(out_path, "wb");
+    if (!fp) { fprintf(stderr, "can't open output file %s\n", out_path); return 1; }
+    bool ok = true;
+    for (int64_t i = 0; i < n && ok; ++i) {
+        const double* r = per.data() + ((size_t)i * nc + (nc - 1)) * PCR_DIVERSITY_FIELDS;
+        ok = fprintf(fp, "%lld %g %g %g\n", (long long)users[(size_t)i] + 1, r[0], r[1], r[2]) > 0;
+    }
+    ok = (fclose(fp) == 0) && ok;
+    if (!ok) { fprintf(stderr, "short write to %s\n", out_path); return 1; }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     int K = 10;
-    bool f32 = false, with_scores = false, with_ranks = false;
+    bool f32 = false, with_scores = false, with_ranks = false, diversity = false;
     const char *xdir = nullptr, *ufile = nullptr, *edir = nullptr;
     std::vector<int> cuts;
     double threshold = -INFINITY;
@@ -202,11 +242,14 @@ int main(int argc, char** argv) {
         } else if (!strcmp(a, "--f32")) f32 = true;
         else if (!strcmp(a, "--scores")) with_scores = true;
         else if (!strcmp(a, "--ranks")) with_ranks = true;
+        else if (!strcmp(a, "--diversity")) diversity = true;
         else if (a[0] == '-' && a[1]) { fprintf(stderr, "unknown option %s\n", a); return usage(); }
         else pos.push_back(a);
     }
-    if (edir ? (pos.empty() || pos.size() > 2) : pos.size() != 2) return usage();
-    if (!edir && (!cuts.empty() || threshold != -INFINITY)) { fprintf(stderr, "-c and --threshold go with --eval\n"); return 1; }
+    if (diversity && edir) { fprintf(stderr, "--diversity does not go with --eval\n"); return 1; }
+    if ((edir || diversity) ? (pos.empty() || pos.size() > 2) : pos.size() != 2) return usage();
+    if (diversity && (with_scores || with_ranks || threshold != -INFINITY)) { fprintf(stderr, "--scores, --ranks and --threshold do not go with --diversity\n"); return 1; }
+    if (!edir && !diversity && (!cuts.empty() || threshold != -INFINITY)) { fprintf(stderr, "-c and --threshold go with --eval\n"); return 1; }
     if (!edir && with_ranks) { fprintf(stderr, "--ranks goes with --eval\n"); return 1; }
     if (edir && (ufile || with_scores)) { fprintf(stderr, "-u and --scores do not go with --eval\n"); return 1; }
     int64_t d1, d2, k;
@@ -219,6 +262,14 @@ int main(int argc, char** argv) {
     std::vector<int64_t> xindex;
     std::vector<int32_t> xitem;
     if (xdir && !load_csr(xdir, 0, d1, d2, xindex, xitem, nullptr)) return 1;
+    if (diversity) {
+        if (cuts.empty()) cuts.push_back(K);
+        const int rc = run_diversity(U, V, d1, d2, k, xdir ? &xindex : nullptr, xdir ? &xitem : nullptr, users, cuts, f32,
+                                     pos.size() == 2 ? pos[1] : nullptr);
+        if (rc) return rc;
+        fflush(stdout); fflush(stderr);
+        _exit(0);
+    }
     if (edir) {
         if (cuts.empty()) cuts.push_back(K);
         const int rc = run_eval(edir, U, V, d1, d2, k, xdir ? &xindex : nullptr, xdir ? &xitem : nullptr, cuts, threshold, f32,

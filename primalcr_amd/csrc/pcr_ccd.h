@@ -583,6 +583,10 @@ struct CcdSolver final : pcr_solver {
     int evaluate_ranks(double thr, int flags, pcr_rank_stats* stats, double* per_user, int64_t* ranks) override {
         return base->evaluate_ranks_with(thr, flags, stats, per_user, ranks, &prof);
     }
+    int evaluate_diversity(int64_t n, const int32_t* local, int ncut, const int* cuts, int flags, pcr_diversity_stats* stats, double* per_user,
+                           int64_t* exposure) override {
+        return base->evaluate_diversity_with(n, local, ncut, cuts, flags, stats, per_user, exposure, &prof);
+    }
     int residual_mismatch(double* value) override {
         hipLaunchKernelGGL((k_ccd_mismatch<RT>), dim3(B), dim3(ccd::BLOCK), 0, st, (const RT*)d_res_r.p, (const RT*)d_res_c.p, (const int32_t*)d_c2r.p,
                            nnz, d_pmis.p);

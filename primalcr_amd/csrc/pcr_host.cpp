@@ -1089,7 +1089,7 @@ int pcr_recommend_model_check(const double* U, int64_t d1, const double* V, int6
     return PCR_OK;
 }
 
-int pcr_topn_check(const char* who, int ncut, const int* cutoffs, double threshold, const pcr_topn_stats* stats) {
+int pcr_cutoffs_check(const char* who, int ncut, const int* cutoffs) {
     auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
     if (ncut < 1 || ncut > PCR_TOPN_MAX_CUTOFFS || !cutoffs)
         return bad("ncut = " + std::to_string(ncut) + " outside [1, " + std::to_string(PCR_TOPN_MAX_CUTOFFS) + "] (or no cutoffs)");
@@ -1098,6 +1098,13 @@ int pcr_topn_check(const char* who, int ncut, const int* cutoffs, double thresho
             return bad("cutoff " + std::to_string(cutoffs[c]) + " outside [1, " + std::to_string(PCR_RECOMMEND_MAX_K) + "]");
         if (c > 0 && cutoffs[c] <= cutoffs[c - 1]) return bad("cutoffs must be strictly ascending");
     }
+    return PCR_OK;
+}
+
+int pcr_topn_check(const char* who, int ncut, const int* cutoffs, double threshold, const pcr_topn_stats* stats) {
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
+    const int rc = pcr_cutoffs_check(who, ncut, cutoffs);
+    if (rc != PCR_OK) return rc;
     if (std::isnan(threshold)) return bad("threshold is NaN");
     if (!stats) return bad("null stats");
     return PCR_OK;
@@ -1232,4 +1239,62 @@ void pcr_rank_scatter(int64_t rows, const int64_t* tptr, const int32_t* titem, c
                 if (tval[z] >= threshold) ranks[z] = rrank[std::lower_bound(rb, re, titem[z]) - rel.ritem.data()];
         }
     });
+}
+
+// ------------------------------------------------------------------------------ beyond-accuracy metrics (include/primalcr.h)
+int pcr_evaluate_diversity_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
+                                       const int32_t* item, int64_t n, const int32_t* users, int ncut, const int* cutoffs, int dtype,
+                                       const pcr_diversity_stats* stats, bool* sorted) {
+    static const char* who = "pcr_evaluate_diversity_model";
+    const int rc = pcr_cutoffs_check(who, ncut, cutoffs);
+    if (rc != PCR_OK) return rc;
+    if (!stats) { pcr_set_error(std::string(who) + ": null stats"); return PCR_ERR_ARG; }
+    static const int32_t no_items = 0;         // (the lists stay on the device: nothing for the output check to find missing)
+    static const double no_scores = 0.0;
+    return pcr_recommend_model_check(U, d1, V, d2, k, index, item, n, users, cutoffs[ncut - 1], dtype, &no_items, &no_scores, sorted, who);
+}
+
+int pcr_exposure_stats(const int64_t* exposure, int64_t d2, int64_t* recs, int64_t* items_covered, double* coverage, double* gini) {
+    if (!exposure || d2 < 1) { pcr_set_error("pcr_exposure_stats: bad argument"); return PCR_ERR_ARG; }
+    std::vector<int64_t> x(exposure, exposure + d2);
+    for (int64_t v : x) if (v < 0) { pcr_set_error("pcr_exposure_stats: a negative exposure count"); return PCR_ERR_ARG; }
+    std::sort(x.begin(), x.end());
+    __int128 num = 0, tot = 0;
+    int64_t cov = 0;
+    for (int64_t i = 0; i < d2; ++i) {
+        num += (__int128)(2 * (i + 1) - d2 - 1) * (__int128)x[(size_t)i];
+        tot += x[(size_t)i];
+        cov += x[(size_t)i] > 0 ? 1 : 0;
+    }
+    if (tot > (__int128)INT64_MAX) { pcr_set_error("pcr_exposure_stats: the exposure counts sum to more than an int64 holds"); return PCR_ERR_ARG; }
+    const __int128 den = (__int128)d2 * tot;
+    if (recs) *recs = (int64_t)tot;
+    if (items_covered) *items_covered = cov;
+    if (coverage) *coverage = (double)cov / (double)d2;
+    if (gini) *gini = tot > 0 ? (double)num / (double)den : 0.0;
+    return PCR_OK;
+}
+
+void pcr_diversity_info(int64_t d1, const double* pop, int64_t d2, double* info) {
+    for (int64_t j = 0; j < d2; ++j) info[j] = log2((double)(d1 + 1) / (pop[j] + 1.0));
+}
+
+int pcr_diversity_stats_from(const double* sums, int ncut, const int* cutoffs, const double* expo, int64_t d2,
+                             pcr_diversity_stats* stats, int64_t* exposure) {
+    auto mean = [](double s, double n) { return n > 0.0 ? s / n : 0.0; };
+    std::vector<int64_t> row((size_t)d2);
+    for (int c = 0; c < ncut; ++c) {
+        const double* x = sums + 8 * c;
+        pcr_diversity_stats& o = stats[c];
+        for (int64_t j = 0; j < d2; ++j) row[(size_t)j] = (int64_t)expo[(size_t)c * d2 + j];
+        o.cutoff = cutoffs[c];
+        o.users = (int64_t)sums[8 * ncut];
+        o.users_ild = (int64_t)x[7];
+        const int rc = pcr_exposure_stats(row.data(), d2, &o.recs, &o.items_covered, &o.coverage, &o.gini);
+        if (rc != PCR_OK) return rc;
+        o.novelty = mean(x[1], x[3]);
+        o.ild = mean(x[6], x[7]);
+        if (exposure) std::copy(row.begin(), row.end(), exposure + (size_t)c * d2);
+    }
+    return PCR_OK;
 }

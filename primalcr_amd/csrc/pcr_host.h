@@ -100,6 +100,22 @@ void pcr_topn_relevance(int64_t rows, const int64_t* tptr, const int32_t* titem,
 // stats[c] from the reduced sums (k_topn_fin's layout: [ncut][8], then the counted users)
 void pcr_topn_stats_from(const double* sums, int ncut, const int* cutoffs, pcr_topn_stats* stats);
 
+// Beyond-accuracy metrics (include/primalcr.h, "beyond-accuracy top-N metrics").
+// the cutoff list of an evaluation entry: 1 .. PCR_TOPN_MAX_CUTOFFS values, strictly ascending, inside [1, PCR_RECOMMEND_MAX_K]
+int pcr_cutoffs_check(const char* who, int ncut, const int* cutoffs);
+// pcr_evaluate_diversity_model's argument checks (shared with the sanitizer build's stub): the cutoffs, stats != NULL, then the
+// factor / user / exclusion checks of pcr_recommend_model.  *sorted as pcr_recommend_model_check.
+int pcr_evaluate_diversity_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
+                                       const int32_t* item, int64_t n, const int32_t* users, int ncut, const int* cutoffs, int dtype,
+                                       const pcr_diversity_stats* stats, bool* sorted);
+// info[j] = log2((d1 + 1) / (pop[j] + 1)) for the d2 popularity counts pop (exact integers in fp64)
+void pcr_diversity_info(int64_t d1, const double* pop, int64_t d2, double* info);
+// stats[c] from the reduced sums (k_topn_fin's layout: [ncut][8] = sum len, sum novelty, -, users with len >= 1, -, -, sum ild,
+// users_ild; then the requested users) and the cumulative exposure rows expo[ncut][d2] (exact integers in fp64); exposure
+// (may be NULL) receives them as int64.  pcr_exposure_stats' return code.
+int pcr_diversity_stats_from(const double* sums, int ncut, const int* cutoffs, const double* expo, int64_t d2,
+                             pcr_diversity_stats* stats, int64_t* exposure);
+
 // Exact rank metrics (include/primalcr.h, "exact full-catalogue rank metrics").
 // pcr_evaluate_ranks_model's argument checks (shared with the sanitizer build's stub): threshold not NaN, stats != NULL, the
 // factor / exclusion checks of pcr_recommend_model and the test CSR's shape.  *sorted as pcr_recommend_model_check.

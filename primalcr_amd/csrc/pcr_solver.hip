@@ -342,6 +342,113 @@ struct RecTopn {
     }
 };
 
+// Beyond-accuracy metrics (pcr_evaluate_diversity, pcr_topk.h): the per-item tables and the outputs of one call -- the exposure
+// counters [ncut][d2] (they live across rec_run's user batches and are zeroed once per call), the per-user rows met[n][ncut][6]
+// in the column order k_topn_sum1 reduces, the reduced sums [ncut][8] + the count
+struct DivDev {
+    int ncut = 0;
+    int cut[PCR_TOPN_MAX_CUTOFFS] = {};
+    int64_t d2 = 0;
+    DBuf<double> inv, q, met, part, sums, expod;
+    DBuf<unsigned long long> expo;
+    const double* info = nullptr;
+};
+
+// rec_run's sink for the beyond-accuracy metrics: merge + exposure, novelty and ILD (k_rec_merge_div) into d.expo and d.met
+template <typename T>
+struct RecDiversity {
+    hipStream_t st;
+    int K;
+    const T* V;
+    int r, ld;
+    DivDev& d;
+    RecDiversity(hipStream_t st_, int K_, const T* V_, int r_, int ld_, DivDev& d_) : st(st_), K(K_), V(V_), r(r_), ld(ld_), d(d_) {}
+    int begin(int64_t) { return PCR_OK; }
+    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp, Profiler* prof) {
+        DivArgs da;
+        da.inv = d.inv.p; da.q = d.q.p; da.info = d.info; da.expo = d.expo.p; da.out = d.met.p + (size_t)b0 * d.ncut * 6;
+        da.d2 = d.d2; da.ncut = d.ncut;
+        for (int c = 0; c < PCR_TOPN_MAX_CUTOFFS; ++c) da.cut[c] = c < d.ncut ? d.cut[c] : 0;
+        ProfScope ps(prof, "recommend/diversity", st);
+        hipLaunchKernelGGL((k_rec_merge_div<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), (size_t)4 * K * sizeof(int32_t), st, ls, li, ln, nsp, m, K, V, r,
+                           ld, da);
+        HIPCHK(hipGetLastError());
+        return PCR_OK;
+    }
+};
+
+// info[] of the training ratings pitem[0, pnnz) on the device (NULL: pop = 0) into `info`: the counts by integer adds, combined
+// across ranks by combine(), the logarithms on the host (pcr_diversity_info), like the top-N discount table
+template <class Combine, class Wait>
+static int div_info_build(hipStream_t st, const int32_t* pitem, int64_t pnnz, int64_t d1, int64_t d2, Combine&& combine, Wait&& wait,
+                          DBuf<double>& info) {
+    DBuf<unsigned long long> cnt;
+    DBuf<double> pop;
+    RC(cnt.alloc((size_t)d2)); RC(pop.alloc((size_t)d2));
+    HIPCHK(hipMemsetAsync(cnt.p, 0, (size_t)d2 * sizeof(unsigned long long), st));
+    if (pitem && pnnz > 0)
+        hipLaunchKernelGGL(k_div_pop, dim3((unsigned)std::min<int64_t>(4096, cdiv(pnnz, 256))), dim3(256), 0, st, pitem, pnnz, cnt.p);
+    hipLaunchKernelGGL(k_div_pop_f64, dim3((unsigned)cdiv(d2, 256)), dim3(256), 0, st, (const unsigned long long*)cnt.p, d2, pop.p);
+    HIPCHK(hipGetLastError());
+    RC(combine(pop.p, (size_t)d2));
+    std::vector<double> h((size_t)d2), hi((size_t)d2);
+    HIPCHK(hipMemcpyAsync(h.data(), pop.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    RC(wait());
+    pcr_diversity_info(d1, h.data(), d2, hi.data());
+    RC(info.upload(hi, st));
+    return PCR_OK;
+}
+
+// The beyond-accuracy evaluation of the n users h_users (rows of U and of the exclusion CSR, as rec_run; NULL: rows 0..n-1)
+// with the self-information table info: the row norms, the sweep with RecDiversity, the fixed-order sums over the users
+// (k_topn_sum1 / k_topn_fin on met, unchanged) and the cumulative exposure; sums and exposure are combined across ranks by
+// combine() and read back once wait() has synchronised st.  "recommend/diversity" times everything but the score kernel.
+template <typename T, class Combine, class Wait>
+static int div_run(hipStream_t st, const T* U, const T* V, int r, int ld, int64_t d2, const int64_t* xptr, const int32_t* xitem,
+                   const double* info, int64_t n, const int32_t* h_users, int ncut, const int* cuts, Profiler* prof, Combine&& combine,
+                   Wait&& wait, pcr_diversity_stats* stats, double* per_user, int64_t* exposure) {
+    DivDev D;
+    D.ncut = ncut; D.d2 = d2; D.info = info;
+    for (int c = 0; c < ncut; ++c) D.cut[c] = cuts[c];
+    const int K = cuts[ncut - 1];
+    RC(D.inv.alloc((size_t)d2)); RC(D.q.alloc((size_t)d2)); RC(D.expo.alloc((size_t)ncut * d2)); RC(D.expod.alloc((size_t)ncut * d2));
+    RC(D.met.alloc((size_t)n * ncut * 6)); RC(D.sums.alloc((size_t)ncut * 8 + 1));
+    {
+        ProfScope ps(prof, "recommend/diversity", st);
+        HIPCHK(hipMemsetAsync(D.expo.p, 0, (size_t)ncut * d2 * sizeof(unsigned long long), st));
+        hipLaunchKernelGGL((k_div_prepare<T>), dim3((unsigned)cdiv(d2, 4)), dim3(256), 0, st, V, r, ld, d2, D.inv.p, D.q.p);
+        HIPCHK(hipGetLastError());
+    }
+    RC(rec_run<T>(st, U, V, r, ld, d2, xptr, xitem, n, h_users, K, 1, prof, RecDiversity<T>(st, K, V, r, ld, D)));
+    {
+        ProfScope ps(prof, "recommend/diversity", st);
+        const int nb = (int)std::min<int64_t>(512, std::max<int64_t>(1, cdiv(n, 2048)));
+        const int per = cdiv(std::max<int64_t>(n, 1), nb);
+        RC(D.part.alloc((size_t)nb * ncut * 8));
+        hipLaunchKernelGGL(k_topn_sum1, dim3(nb, ncut), dim3(PCR_EW_BLOCK), 0, st, (const double*)D.met.p, n, ncut, per, D.part.p);
+        hipLaunchKernelGGL(k_topn_fin, dim3(ncut), dim3(PCR_EW_BLOCK), 0, st, (const double*)D.part.p, nb, n, D.sums.p);
+        hipLaunchKernelGGL(k_div_expo_finish, dim3((unsigned)cdiv(d2, 256)), dim3(256), 0, st, (const unsigned long long*)D.expo.p, d2, ncut, D.expod.p);
+        HIPCHK(hipGetLastError());
+    }
+    RC(combine(D.sums.p, (size_t)ncut * 8 + 1));
+    RC(combine(D.expod.p, (size_t)ncut * d2));
+    std::vector<double> hs((size_t)ncut * 8 + 1), he((size_t)ncut * d2), hm;
+    HIPCHK(hipMemcpyAsync(hs.data(), D.sums.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(he.data(), D.expod.p, he.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (per_user && n > 0) {
+        hm.resize((size_t)n * ncut * 6);
+        HIPCHK(hipMemcpyAsync(hm.data(), D.met.p, hm.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    RC(wait());
+    RC(pcr_diversity_stats_from(hs.data(), ncut, cuts, he.data(), d2, stats, exposure));
+    for (size_t i = 0; i < hm.size() / 6; ++i) {           // met: len, novelty (0 when len = 0), -, -, -, ild
+        const double* m = hm.data() + i * 6;
+        double* o = per_user + i * PCR_DIVERSITY_FIELDS;
+        o[0] = m[0]; o[1] = m[0] > 0.0 ? m[1] : (double)NAN; o[2] = m[5];
+    }
+    return PCR_OK;
+}
+
 // Exact rank metrics (pcr_evaluate_ranks, pcr_topk.h): the relevance table of a threshold on the device (PcrTopnRel's users,
 // rptr and ritem; uploaded once per threshold) and the outputs: rrank[nrel] the ranks of ritem entry for entry, met[n][6]
 // k_rank_finish's rows, the reduced sums [8] + the count
@@ -523,6 +630,9 @@ struct pcr_solver {
     virtual int evaluate_topn(int ncut, const int* cuts, double threshold, int flags, pcr_topn_stats* stats, double* per_user) = 0;
     // pcr_evaluate_ranks (arguments checked by the caller)
     virtual int evaluate_ranks(double threshold, int flags, pcr_rank_stats* stats, double* per_user, int64_t* ranks) = 0;
+    // pcr_evaluate_diversity: `local` = rows of this shard (arguments checked by the caller)
+    virtual int evaluate_diversity(int64_t n, const int32_t* local, int ncut, const int* cuts, int flags, pcr_diversity_stats* stats,
+                                   double* per_user, int64_t* exposure) = 0;
 };
 
 // launch knobs: pcr_tune() values read once when the solver is created (include/primalcr.h lists them)
@@ -2648,6 +2758,30 @@ struct Solver final : pcr_solver {
     int recommend(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores) override {
         return recommend_with(n, local, K, flags, items, scores, &prof);
     }
+    // beyond-accuracy metrics of the shard's users from the device factors; the self-information table comes from the shard's
+    // training ratings (all-reduced with a communicator) and is kept: the ratings never change, the exchange mode can
+    int evaluate_diversity_with(int64_t n, const int32_t* local, int ncut, const int* cuts, int flags, pcr_diversity_stats* stats,
+                                double* per_user, int64_t* exposure, Profiler* prof) {
+        // (the peer-to-peer communicator's fp64 exchange is its 64-double scalar slot: the d2-sized tables do not fit it)
+        if (p2p && !single()) { pcr_set_error("pcr_evaluate_diversity: not available on a peer-to-peer communicator (use RCCL, or local-only shards and pcr_exposure_stats)"); return PCR_ERR_UNSUPPORTED; }
+        auto combine = [this](double* p, size_t cnt) { return allreduce_f64(p, cnt); };
+        auto wait = [this] { return sync_checked(); };
+        const int mode = single() ? 1 : 2;
+        if (div_info_mode != mode) {
+            div_info_mode = 0;
+            RC(div_info_build(st, d_item.p, nnz_local, d1, d2, combine, wait, div_info));
+            div_info_mode = mode;
+        }
+        const bool ex = (flags & PCR_REC_EXCLUDE_TRAIN) != 0;
+        return div_run<T>(st, d_U.p, d_V.p, geo.r, geo.ld, d2, ex ? d_uptr.p : nullptr, ex ? d_item.p : nullptr, div_info.p, n, local, ncut, cuts,
+                          prof, combine, wait, stats, per_user, exposure);
+    }
+    int evaluate_diversity(int64_t n, const int32_t* local, int ncut, const int* cuts, int flags, pcr_diversity_stats* stats, double* per_user,
+                           int64_t* exposure) override {
+        return evaluate_diversity_with(n, local, ncut, cuts, flags, stats, per_user, exposure, &prof);
+    }
+    DBuf<double> div_info;        // info[d2] of pcr_evaluate_diversity
+    int div_info_mode = 0;        // 0: not built, 1: from this shard's ratings alone, 2: all-reduced
 };
 
 #include "pcr_ccd.h"
@@ -2985,6 +3119,60 @@ int pcr_evaluate_ranks_model(const double* U, int64_t d1, const double* V, int64
     });
 }
 
+int pcr_evaluate_diversity_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                                 int64_t n, const int32_t* users, int ncut, const int* cutoffs, int dtype, pcr_diversity_stats* stats,
+                                 double* per_user, int64_t* exposure, int device) {
+    return abi_guard("pcr_evaluate_diversity_model", [&]() -> int {
+    bool sorted = true;
+    RC(pcr_evaluate_diversity_model_check(U, d1, V, d2, k, index, item, n, users, ncut, cutoffs, dtype, stats, &sorted));
+    RC(model_device(device));
+    auto run = [&](auto zero) -> int {
+        using T = decltype(zero);
+        hipStream_t st = nullptr;
+        ModelDev<T> M;
+        RC(M.upload_exclusion(d1, index, item, sorted));
+        RC(M.upload_factors(st, U, d1, V, d2, k));
+        auto combine = [](double*, size_t) { return PCR_OK; };
+        auto wait = [st] { HIPCHK(hipStreamSynchronize(st)); return PCR_OK; };
+        DBuf<double> info;
+        RC(div_info_build(st, (const int32_t*)M.di.p, index ? index[d1] : 0, d1, d2, combine, wait, info));
+        return div_run<T>(st, M.U(), M.V(), (int)k, M.ld, d2, M.dx.p, M.di.p, info.p, n, users, ncut, cutoffs, nullptr, combine, wait, stats,
+                          per_user, exposure);
+    };
+    return dtype == PCR_F64 ? run(0.0) : run(0.0f);
+    });
+}
+
+// users[n] (global ids, NULL: the whole shard) as rows of s's shard in loc (left empty for NULL); *n the count
+static int shard_rows(const char* who, const pcr_solver* s, int64_t* n, const int32_t* users, std::vector<int32_t>& loc) {
+    if (!users) { *n = s->n_users; return PCR_OK; }
+    loc.resize((size_t)*n);
+    for (int64_t i = 0; i < *n; ++i) {
+        const int64_t x = (int64_t)users[i] - s->first_user;
+        if (x < 0 || x >= s->n_users) {
+            pcr_set_error(std::string(who) + ": user " + std::to_string(users[i]) + " is not in this shard [" + std::to_string(s->first_user) + ", " +
+                          std::to_string(s->first_user + s->n_users) + ")");
+            return PCR_ERR_ARG;
+        }
+        loc[(size_t)i] = (int32_t)x;
+    }
+    return PCR_OK;
+}
+
+int pcr_evaluate_diversity(pcr_solver* s, int64_t n, const int32_t* users, int ncut, const int* cutoffs, int flags, pcr_diversity_stats* stats,
+                           double* per_user, int64_t* exposure) {
+    S_OR_ARG;
+    RC(pcr_cutoffs_check("pcr_evaluate_diversity", ncut, cutoffs));
+    if (!stats) { pcr_set_error("pcr_evaluate_diversity: null stats"); return PCR_ERR_ARG; }
+    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_evaluate_diversity: unknown flags"); return PCR_ERR_ARG; }
+    if (users && n < 0) { pcr_set_error("pcr_evaluate_diversity: bad argument"); return PCR_ERR_ARG; }
+    return abi_guard("pcr_evaluate_diversity", [&]() -> int {
+        std::vector<int32_t> loc;
+        RC(shard_rows("pcr_evaluate_diversity", s, &n, users, loc));
+        return s->evaluate_diversity(n, users ? loc.data() : nullptr, ncut, cutoffs, flags, stats, per_user, exposure);
+    });
+}
+
 int pcr_recommend(pcr_solver* s, int64_t n, const int32_t* users, int topk, int flags, int32_t* items, double* scores) {
     S_OR_ARG;
     if (topk < 1 || topk > PCR_RECOMMEND_MAX_K) { pcr_set_error("pcr_recommend: K = " + std::to_string(topk) + " outside [1, " + std::to_string(PCR_RECOMMEND_MAX_K) + "]"); return PCR_ERR_ARG; }
@@ -2993,18 +3181,7 @@ int pcr_recommend(pcr_solver* s, int64_t n, const int32_t* users, int topk, int 
     if (n < 0 || (n > 0 && (!items || !scores))) { pcr_set_error("pcr_recommend: bad argument"); return PCR_ERR_ARG; }
     return abi_guard("pcr_recommend", [&]() -> int {
         std::vector<int32_t> loc;
-        if (users) {
-            loc.resize((size_t)n);
-            for (int64_t i = 0; i < n; ++i) {
-                const int64_t x = (int64_t)users[i] - s->first_user;
-                if (x < 0 || x >= s->n_users) {
-                    pcr_set_error("pcr_recommend: user " + std::to_string(users[i]) + " is not in this shard [" + std::to_string(s->first_user) + ", " +
-                                  std::to_string(s->first_user + s->n_users) + ")");
-                    return PCR_ERR_ARG;
-                }
-                loc[(size_t)i] = (int32_t)x;
-            }
-        }
+        RC(shard_rows("pcr_recommend", s, &n, users, loc));
         return s->recommend(n, users ? loc.data() : nullptr, topk, flags, items, scores);
     });
 }

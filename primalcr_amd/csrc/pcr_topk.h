@@ -602,3 +602,150 @@ __global__ __launch_bounds__(256) void k_rank_finish(const int32_t* __restrict__
     else if (lane == 5) v = pairs > 0.0 ? (pairs - sum_cum) / pairs : (double)NAN;
     if (lane < 6) met[(size_t)idx * 6 + lane] = v;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Beyond-accuracy metrics (pcr_evaluate_diversity, include/primalcr.h): item exposure, novelty and
+// intra-list diversity of the merged lists.  The tables are per item: inv[j] = 1 / |V[j]| (0 for a zero row), q[j] = |v^_j|^2
+// (k_div_prepare), info[j] the self-information (built on the host).
+namespace rec {
+constexpr int DIV_ROWS = 8;   // rows of V in flight per wave in k_rec_merge_div's walk (the gathers are latency-bound, as k_ustep's)
+constexpr int DIV_CH = 2;     // components per lane and pass: a pass covers 64 DIV_CH components of the rows
+}  // namespace rec
+
+struct DivArgs {
+    const double* inv;            // [d2]
+    const double* q;              // [d2]
+    const double* info;           // [d2]
+    unsigned long long* expo;     // [ncut][d2]: row c counts the list positions in [cut[c - 1], cut[c]); made cumulative by k_div_expo_finish
+    double* out;                  // [n][ncut][6]: len, novelty (0 when len = 0), 0, 0, 0, ild -- the columns k_topn_sum1 reduces
+    int64_t d2;
+    int ncut;
+    int cut[PCR_TOPN_MAX_CUTOFFS];
+};
+
+// one wave per item: the fixed-order sum of squares of its row (lane-strided partial sums, wave_sum's butterfly), then the same
+// sum over the normalised components
+template <typename T>
+__global__ __launch_bounds__(256) void k_div_prepare(const T* __restrict__ V, int r, int ld, int64_t d2, double* __restrict__ inv,
+                                                     double* __restrict__ q) {
+    const int lane = threadIdx.x & 63;
+    const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= d2) return;
+    const T* row = V + (size_t)j * (size_t)ld;
+    double s = 0.0;
+    for (int c = lane; c < r; c += 64) { const double x = (double)row[c]; s += x * x; }
+    s = wave_sum(s);
+    const double iv = s > 0.0 ? 1.0 / sqrt(s) : 0.0;
+    double t = 0.0;
+    for (int c = lane; c < r; c += 64) { const double x = (double)row[c] * iv; t += x * x; }
+    t = wave_sum(t);
+    if (lane == 0) { inv[j] = iv; q[j] = t; }
+}
+
+// popularity: cnt[item[z]] += 1 over the training ratings (64-bit integer adds, as the exposure: no count an int64 nnz can
+// reach wraps), then the counts as doubles for the all-reduce
+__global__ __launch_bounds__(256) void k_div_pop(const int32_t* __restrict__ item, int64_t nnz, unsigned long long* __restrict__ cnt) {
+    for (int64_t z = (int64_t)blockIdx.x * 256 + threadIdx.x; z < nnz; z += (int64_t)gridDim.x * 256) atomicAdd(&cnt[item[z]], 1ull);
+}
+__global__ __launch_bounds__(256) void k_div_pop_f64(const unsigned long long* __restrict__ cnt, int64_t d2, double* __restrict__ pop) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < d2) pop[j] = (double)cnt[j];
+}
+
+// exposure rows per cutoff band -> cumulative over the cutoffs, as doubles (exact below 2^53)
+__global__ __launch_bounds__(256) void k_div_expo_finish(const unsigned long long* __restrict__ expo, int64_t d2, int ncut,
+                                                         double* __restrict__ out) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= d2) return;
+    unsigned long long c = 0;
+    for (int k = 0; k < ncut; ++k) { c += expo[(size_t)k * d2 + j]; out[(size_t)k * d2 + j] = (double)c; }
+}
+
+// k_rec_merge with the beyond-accuracy metrics fused into its tail, one wave per user: the merged list goes to the wave's LDS
+// row as in k_rec_merge_topn and is never written out.  Then
+//   exposure   every list position p does one integer add into the row of the first cutoff that contains p;
+//   novelty    lanes own the positions p = lane, lane + 64, ...: info[] and q[] lookups, per-cutoff sums by wave_sum;
+//   ILD        sum_{a<b} v^_a . v^_b = (|sum_a v^_a|^2 - sum_a q_a) / 2: the wave walks the list in position order, gathers each
+//              listed row of V coalesced (lane = component, DIV_CH components per lane), scales it by inv[id] in fp64 and adds
+//              it to a running vector sum in registers; at every cutoff boundary wave_sum of the squared components.  DIV_ROWS
+//              rows are loaded before the first is used.  Ranks wider than 64 DIV_CH re-walk the list per component chunk (the
+//              squared norm is a sum over components).  Lane c keeps cutoff c's |S|^2.
+// Every value of a user depends on its list and on V alone.
+template <typename T>
+__global__ __launch_bounds__(256) void k_rec_merge_div(const T* __restrict__ lst_s, const int32_t* __restrict__ lst_i,
+                                                       const int32_t* __restrict__ lst_n, int nsplit, int64_t n, int K,
+                                                       const T* __restrict__ V, int r, int ld, DivArgs da) {
+    extern __shared__ int32_t rec_lst[];
+    const int lane = threadIdx.x & 63;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (idx >= n) return;
+    int32_t* sl = rec_lst + (size_t)(threadIdx.x >> 6) * (size_t)K;
+    const int tot = rec_merge_ranks(lst_s, lst_i, lst_n, nsplit, n, K, idx, lane, [&](int rk, int j, T) { sl[rk] = j; });
+    const int L = __builtin_amdgcn_readfirstlane(min(tot, K));      // the list is sl[0, L): no padding inside
+    wave_sync();
+    double nov[PCR_TOPN_MAX_CUTOFFS], qs[PCR_TOPN_MAX_CUTOFFS];
+#pragma unroll
+    for (int c = 0; c < PCR_TOPN_MAX_CUTOFFS; ++c) { nov[c] = 0.0; qs[c] = 0.0; }
+    for (int p = lane; p < L; p += 64) {
+        const int j = sl[p];
+        const double nv = da.info[j], qq = da.q[j];
+        int c0 = 0;                                                  // the first cutoff that contains p (p < L <= the last cutoff)
+#pragma unroll
+        for (int c = 0; c < PCR_TOPN_MAX_CUTOFFS; ++c)
+            if (c < da.ncut) { if (p < da.cut[c]) { nov[c] += nv; qs[c] += qq; } else c0 = c + 1; }
+        atomicAdd(&da.expo[(size_t)c0 * (size_t)da.d2 + (size_t)j], 1ull);
+    }
+    double myn = 0.0;                                                // lane c: |sum_{a < len(c)} v^_a|^2
+    for (int cb = 0; cb < r; cb += 64 * rec::DIV_CH) {
+        double S[rec::DIV_CH];
+#pragma unroll
+        for (int t = 0; t < rec::DIV_CH; ++t) S[t] = 0.0;
+        for (int i0 = 0; i0 < L; i0 += rec::DIV_ROWS) {
+            T x[rec::DIV_ROWS][rec::DIV_CH];
+            double iv[rec::DIV_ROWS];
+#pragma unroll
+            for (int e = 0; e < rec::DIV_ROWS; ++e) {
+                const int j = __builtin_amdgcn_readfirstlane(i0 + e < L ? sl[i0 + e] : -1);
+                iv[e] = j >= 0 ? da.inv[j] : 0.0;
+#pragma unroll
+                for (int t = 0; t < rec::DIV_CH; ++t) {
+                    const int c = cb + 64 * t + lane;
+                    x[e][t] = (j >= 0 && c < r) ? V[(size_t)(unsigned)j * (unsigned)ld + c] : (T)0;
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < rec::DIV_ROWS; ++e) {
+                const int cnt = i0 + e + 1;                          // entries summed after this one
+                if (cnt > L) break;                                  // (wave-uniform)
+#pragma unroll
+                for (int t = 0; t < rec::DIV_CH; ++t) S[t] += (double)x[e][t] * iv[e];
+                unsigned hit = 0;                                    // the cutoffs whose list ends here
+#pragma unroll
+                for (int c = 0; c < PCR_TOPN_MAX_CUTOFFS; ++c) if (c < da.ncut && cnt == min(da.cut[c], L)) hit |= 1u << c;
+                if (hit) {
+                    double ss = 0.0;
+#pragma unroll
+                    for (int t = 0; t < rec::DIV_CH; ++t) ss += S[t] * S[t];
+                    ss = wave_sum(ss);
+                    if (lane < PCR_TOPN_MAX_CUTOFFS && ((hit >> lane) & 1u)) myn += ss;
+                }
+            }
+        }
+    }
+    double mynov = 0.0, myq = 0.0;
+    int mycut = 0;
+#pragma unroll
+    for (int c = 0; c < PCR_TOPN_MAX_CUTOFFS; ++c) {
+        if (c >= da.ncut) break;                                     // (wave-uniform)
+        const double N = wave_sum(nov[c]), Q = wave_sum(qs[c]);
+        if (lane == c) { mynov = N; myq = Q; mycut = da.cut[c]; }
+    }
+    const int len = min(mycut, L);
+    const double dl = (double)len, pairs = 0.5 * dl * (dl - 1.0);
+    const double ild = len >= 2 ? 1.0 - (0.5 * (myn - myq)) / pairs : (double)NAN;
+    const double novelty = len >= 1 ? mynov / dl : 0.0;
+    // lane l < 6 ncut writes field l % 6 of cutoff l / 6: one coalesced row per user
+    const int myc = lane / 6, myf = lane - 6 * myc;
+    const double f0 = __shfl(dl, myc), f1 = __shfl(novelty, myc), f5 = __shfl(ild, myc);
+    if (lane < 6 * da.ncut) da.out[(size_t)idx * 6 * da.ncut + lane] = myf == 0 ? f0 : myf == 1 ? f1 : myf == 5 ? f5 : 0.0;
+}

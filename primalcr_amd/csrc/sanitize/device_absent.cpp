@@ -84,4 +84,11 @@ int pcr_evaluate_ranks_model(const double* U, int64_t d1, const double* V, int64
     return rc != PCR_OK ? rc : absent();
 }
 NO_SOLVER(pcr_evaluate_ranks, pcr_solver*, double, int, pcr_rank_stats*, double*, int64_t*)
+int pcr_evaluate_diversity_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                                 int64_t n, const int32_t* users, int ncut, const int* cutoffs, int dtype, pcr_diversity_stats* stats, double*,
+                                 int64_t*, int) {
+    const int rc = pcr_evaluate_diversity_model_check(U, d1, V, d2, k, index, item, n, users, ncut, cutoffs, dtype, stats, nullptr);
+    return rc != PCR_OK ? rc : absent();
+}
+NO_SOLVER(pcr_evaluate_diversity, pcr_solver*, int64_t, const int32_t*, int, const int*, int, pcr_diversity_stats*, double*, int64_t*)
 }
