@@ -219,6 +219,10 @@ int pcr_partition_users(const int64_t *index, int64_t d1, int nparts, int64_t *b
  *                   empty): tools/exp_recommend.py times the selection's share with it; default 1
  *   ranks_batch_users  test hook: at most this many counted users per batch of pcr_evaluate_ranks (rounded up to whole
  *                   workgroups of 64; 0 = the natural batch, which holds a million users and more); read at every call
+ *   rerank_lds      the form of pcr_recommend_diverse's selection kernel: 0 (default) = the streaming form (the pool's rows of V
+ *                   are re-read from L2 every round; the faster one at every shape measured), 1 = the LDS form (the pool's rows
+ *                   staged once per user) whenever one wave's image fits a workgroup's 160 KiB; both forms implement the same
+ *                   contract, the tests hold them to each other; read at every call
  *   count_rows      1 = the U-step kernels count the rows of V they gather (pcr_solver_counter; a diagnostic that
  *                   costs the short-user classes 10-20 %, so off by default)
  *   debug           1 = print launch decisions to stderr
@@ -559,6 +563,47 @@ int pcr_evaluate_diversity_model(const double *U, int64_t d1, const double *V, i
  * Profile slots: recommend/score, and recommend/diversity (the row norms, the merge with the metrics fused in, the reductions). */
 int pcr_evaluate_diversity(pcr_solver *s, int64_t n, const int32_t *users, int ncut, const int *cutoffs, int flags,
                            pcr_diversity_stats *stats, double *per_user, int64_t *exposure);                 /* [device] */
+
+/* ------------------------------------------------------------------------- */
+/* MMR diversity re-ranking of the top-K lists (no reference counterpart)      */
+/* ------------------------------------------------------------------------- */
+/* Greedy re-ranking by Maximal Marginal Relevance (Carbonell and Goldstein): topk items are taken one by one from a pool of the
+ * user's `pool` best items, each time the one that is relevant and unlike what the list already holds.  Selected on the device;
+ * only the re-ranked lists leave it.  For each requested user u, with 1 <= topk <= pool <= PCR_RECOMMEND_MAX_K and
+ * 0 <= theta <= 1:
+ *   Pool P_u           exactly the list pcr_recommend / pcr_recommend_model returns for the same factors, dtype, exclusion and
+ *                      K = pool, without its padding: len entries (j_i, s_i), i = 0 .. len - 1, in the recommendation order,
+ *                      the scores the same bits.
+ *   Arithmetic         everything below is fp64; s_i is the computed score converted to double (exact, from f32 as well).
+ *   Range              smin = min_i s_i, R = max_i s_i - smin, and R = 1 when that difference is 0.
+ *   Cosine             cos(a, b) = v^_a . v^_b with v^_j = V[j] inv[j]; inv[j] = 1 / |V[j]| is taken from the factors as the dtype
+ *                      stores them and is 0 for a zero row (the ILD's inv above, the same kernel).  Neither the order of the
+ *                      k-term sum nor the place of the two factors inv[a] inv[b] (inside or outside the sum) is part of the
+ *                      contract; the error is bounded as the ILD's, about (k + 2) 2^-52.
+ *   Greedy rule        S starts empty.  At step t = 0 .. min(topk, len) - 1, for every pool entry i not yet taken:
+ *                      m_i = (1 - theta) (s_i - smin) - (theta R) c_i with c_i = max_{a in S} cos(j_i, j_a), and c_i = 0 while S
+ *                      is empty.  The entry with the largest m_i is taken; equal m_i go to the smaller pool position i.  (The
+ *                      usual (1 - theta) rel - theta max sim with min-max-normalised relevance, multiplied through by R: the
+ *                      order does not depend on the scale of the scores and no division is involved.)
+ *   Output             items[n * topk] and scores[n * topk] in the order taken; the scores are the items' original s_i; a row
+ *                      shorter than topk ends with (-1, -INFINITY).
+ *   Consequences       theta = 0 returns bit for bit pcr_recommend's top-topk list, for any pool >= topk; the first entry is
+ *                      always pool position 0; pool == topk returns a permutation of pcr_recommend's list.
+ *   Determinism        a row depends on (u, its pool, V) alone -- not on the other users, the order of users[], batches or
+ *                      splits; two identical calls are bitwise identical; no floating-point atomics.
+ *   Errors             a NaN theta, theta outside [0, 1], topk < 1, pool < topk, pool > PCR_RECOMMEND_MAX_K and every argument
+ *                      error of pcr_recommend_model are PCR_ERR_ARG, reported before any device is looked for; the message
+ *                      names the entry. */
+int pcr_recommend_diverse_model(const double *U, int64_t d1, const double *V, int64_t d2, int64_t k,
+                                const int64_t *index, const int32_t *item, int64_t n, const int32_t *users,
+                                int topk, int pool, double theta, int dtype,
+                                int32_t *items, double *scores, int device);                          /* [device] */
+/* On a live PCR, PCR++ or CCDR1 solver, as pcr_recommend: its device factors, storage type and stream; users[n] are GLOBAL ids
+ * of this rank's shard (NULL: all of them); flags PCR_REC_EXCLUDE_TRAIN; training state is not touched.  Per user, nothing is
+ * exchanged: it works on every communicator and on local-only shards.
+ * Profile slots: recommend/score, and recommend/rerank (the row norms, the merge with the selection fused in). */
+int pcr_recommend_diverse(pcr_solver *s, int64_t n, const int32_t *users, int topk, int pool, double theta,
+                          int flags, int32_t *items, double *scores);                                 /* [device] */
 
 /* per-kernel device timing (HIP events on the solver's stream, one pair per launch).
  * slot names: "<class>/<workgroup size>[.<length bound>][g][c][l][r][#n]" for the per-user kernels (classes

@@ -162,6 +162,8 @@ def lib():
     L.pcr_predict.argtypes = [_dp, i64, _dp, i64, i64, i64, _ip, _ip, _dp, ci]
     L.pcr_recommend_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, vp, ci, ci, vp, vp, ci]
     L.pcr_recommend.argtypes = [vp, i64, vp, ci, ci, vp, vp]
+    L.pcr_recommend_diverse_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, vp, ci, ci, cd, ci, vp, vp, ci]
+    L.pcr_recommend_diverse.argtypes = [vp, i64, vp, ci, ci, cd, ci, vp, vp]
     L.pcr_evaluate_topn_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, ci, vp, cd, ci, vp, vp, ci]
     L.pcr_evaluate_topn.argtypes = [vp, ci, vp, cd, ci, vp, vp]
     L.pcr_evaluate_ranks_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, cd, ci, vp, vp, vp, ci]
@@ -279,6 +281,48 @@ def recommend(U, V, topk, exclude=None, users=None, dtype=PCR_F64, device=0):
     _chk(lib().pcr_recommend_model(U.ctypes.data, d1, V.ctypes.data, V.shape[0], k, None if idx is None else idx.ctypes.data,
                                    None if it is None else it.ctypes.data, n, None if users is None else users.ctypes.data, int(topk),
                                    int(dtype), items.ctypes.data, scores.ctypes.data, device))
+    return items, scores
+
+
+def _rerank_args(topk, pool, theta):
+    """Shared by recommend_diverse() and Solver.recommend_diverse(): (topk, pool, theta) checked as the library checks them;
+    pool None = min(PCR_RECOMMEND_MAX_K, max(topk, 10 * topk))."""
+    topk = int(topk)
+    if topk < 1:
+        raise ValueError(f"topk = {topk} must be at least 1")
+    pool = min(PCR_RECOMMEND_MAX_K, max(topk, 10 * topk)) if pool is None else int(pool)
+    if pool < topk or pool > PCR_RECOMMEND_MAX_K:
+        raise ValueError(f"pool = {pool} must be in [topk = {topk}, {PCR_RECOMMEND_MAX_K}]")
+    theta = float(theta)
+    if not 0.0 <= theta <= 1.0:
+        raise ValueError(f"theta = {theta} must be in [0, 1]")
+    return topk, pool, theta
+
+
+def recommend_diverse(U, V, topk, pool=None, theta=0.5, exclude=None, users=None, dtype=PCR_F64, device=0):
+    """Top-K lists re-ranked by Maximal Marginal Relevance on the GPU (pcr_recommend_diverse_model): topk items taken greedily
+    from the `pool` best of recommend(), each time the largest (1 - theta) (s - smin) - theta R max cos to the items already
+    taken (cosine of rows of V; theta = 0 is recommend()'s list).  pool None: min(1024, 10 topk).  exclude / users / dtype as
+    recommend().  Returns (items int32 [n, topk], scores float64 [n, topk]) in the order taken, rows padded with (-1, -inf)."""
+    topk, pool, theta = _rerank_args(topk, pool, theta)
+    U = np.ascontiguousarray(U, np.float64); V = np.ascontiguousarray(V, np.float64)
+    d1, k = U.shape
+    idx = it = None
+    if exclude is not None:
+        if isinstance(exclude, Dataset):
+            idx, it, _ = exclude.csr(0)
+        else:
+            idx, it = exclude[:2]
+        idx = np.ascontiguousarray(idx, np.int64); it = np.ascontiguousarray(it, np.int32)
+        if idx.shape[0] != d1 + 1 or idx[-1] != it.shape[0]:
+            raise ValueError(f"exclude: index must have d1 + 1 = {d1 + 1} entries, the last equal to len(item) = {it.shape[0]}")
+    if users is not None:
+        users = np.ascontiguousarray(users, np.int32)
+    n = d1 if users is None else users.shape[0]
+    items = np.empty((n, topk), np.int32); scores = np.empty((n, topk), np.float64)
+    _chk(lib().pcr_recommend_diverse_model(U.ctypes.data, d1, V.ctypes.data, V.shape[0], k, None if idx is None else idx.ctypes.data,
+                                           None if it is None else it.ctypes.data, n, None if users is None else users.ctypes.data,
+                                           topk, pool, theta, int(dtype), items.ctypes.data, scores.ctypes.data, device))
     return items, scores
 
 
@@ -697,6 +741,18 @@ class Solver:
         items = np.empty((n, max(int(topk), 1)), np.int32); scores = np.empty((n, max(int(topk), 1)), np.float64)
         _chk(lib().pcr_recommend(self._h, n, None if users is None else users.ctypes.data, int(topk),
                                  PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, items.ctypes.data, scores.ctypes.data))
+        return items, scores
+
+    def recommend_diverse(self, topk=10, pool=None, theta=0.5, users=None, exclude_train=True):
+        """MMR re-ranked top-K lists from the device factors (pcr_recommend_diverse), in the solver's storage type; arguments
+        and result as recommend_diverse(), users as Solver.recommend()."""
+        topk, pool, theta = _rerank_args(topk, pool, theta)
+        if users is not None:
+            users = np.ascontiguousarray(users, np.int32)
+        n = self.n_users if users is None else users.shape[0]
+        items = np.empty((n, topk), np.int32); scores = np.empty((n, topk), np.float64)
+        _chk(lib().pcr_recommend_diverse(self._h, n, None if users is None else users.ctypes.data, topk, pool, theta,
+                                         PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, items.ctypes.data, scores.ctypes.data))
         return items, scores
 
     def evaluate_topn(self, cutoffs=(10,), threshold=-np.inf, exclude_train=True, per_user=False):

@@ -15,6 +15,11 @@
 //   omp-pmf-recommend --diversity [-x data_dir] [-c c1,c2,...] [-u users_file] [-K topk] [--f32] model_file [output_file]
 //     --diversity    beyond-accuracy metrics of the lists (pcr_evaluate_diversity_model): coverage, Gini index of item exposure,
 //                    novelty (popularity from -x's training ratings) and intra-list diversity; not together with --eval
+//   omp-pmf-recommend --mmr theta [--pool P] [-K topk] [-x data_dir] [-u users_file] [--f32] [--scores] model_file output_file
+//     --mmr theta    re-rank every list by Maximal Marginal Relevance (pcr_recommend_diverse_model): the -K items are taken
+//                    greedily from the user's P best, theta in [0, 1] weighing likeness (cosine of rows of V) against score;
+//                    the output format is that of the plain list; not together with --eval or --diversity
+//     --pool P       the pool of --mmr (default min(1024, 10 K)); refused without --mmr
 // Output: one line per user, in input order: the 1-based user id, then the 1-based item ids (padding is left out).  Users go
 // to the device in batches, so host memory for the lists stays bounded on any catalogue.
 // With --eval: stdout gets one line per cutoff, "cutoff c users n users_graded n hits n precision x recall x hit_rate x map x
@@ -54,6 +59,10 @@ static const char* USAGE =
     "       omp-pmf-recommend --diversity [-x data_dir] [-c c1,c2,...] [-u users_file] [-K topk] [--f32] model_file [output_file]\n"
     "    --diversity    coverage, Gini index of item exposure, novelty (popularity from -x) and intra-list diversity of the lists;\n"
     "                   output_file optional: per requested user at the largest cutoff, len novelty ild\n"
+    "       omp-pmf-recommend --mmr theta [--pool P] [-K topk] [-x data_dir] [-u users_file] [--f32] [--scores] model_file output_file\n"
+    "    --mmr theta    re-rank the lists by Maximal Marginal Relevance: -K items taken greedily from the user's P best,\n"
+    "                   theta in 0 .. 1 (0: the plain list); output as the plain list; not with --eval or --diversity\n"
+    "    --pool P       the pool of --mmr, topk .. 1024 (default min(1024, 10 topk)); only with --mmr\n"
     "    output_file    with --eval optional: per counted user at the largest cutoff, hits precision recall ap ndcg ndcg_graded;\n"
     "                   with --ranks: per counted user first_rank rr mean_rank auc mpr\n";
 
@@ -210,7 +219,9 @@ int main(int argc, char** argv) {
     bool f32 = false, with_scores = false, with_ranks = false, diversity = false;
     const char *xdir = nullptr, *ufile = nullptr, *edir = nullptr;
     std::vector<int> cuts;
-    double threshold = -INFINITY;
+    double threshold = -INFINITY, theta = 0.0;
+    bool mmr = false;
+    int pool = 0;
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -229,6 +240,20 @@ int main(int argc, char** argv) {
                 threshold = strtod(v, &end);
                 if (!*v || *end || threshold != threshold) { fprintf(stderr, "--threshold %s: must be a number\n", v); return 1; }
             }
+        } else if (!strcmp(a, "--mmr")) {
+            if (i + 1 >= argc) { fprintf(stderr, "--mmr needs a value\n"); return usage(); }
+            const char* v = argv[++i];
+            char* end = nullptr;
+            theta = strtod(v, &end);
+            if (!*v || *end || !(theta >= 0.0 && theta <= 1.0)) { fprintf(stderr, "--mmr %s: must be a number in 0 .. 1\n", v); return 1; }
+            mmr = true;
+        } else if (!strcmp(a, "--pool")) {
+            if (i + 1 >= argc) { fprintf(stderr, "--pool needs a value\n"); return usage(); }
+            const char* v = argv[++i];
+            char* end = nullptr;
+            const long x = strtol(v, &end, 10);
+            if (!*v || *end || x < 1 || x > PCR_RECOMMEND_MAX_K) { fprintf(stderr, "--pool %s: must be an integer in 1 .. %d\n", v, PCR_RECOMMEND_MAX_K); return 1; }
+            pool = (int)x;
         } else if (!strcmp(a, "-K") || !strcmp(a, "-x") || !strcmp(a, "-u")) {
             if (i + 1 >= argc) return usage();
             const char* v = argv[++i];
@@ -247,10 +272,16 @@ int main(int argc, char** argv) {
         else pos.push_back(a);
     }
     if (diversity && edir) { fprintf(stderr, "--diversity does not go with --eval\n"); return 1; }
+    if (mmr && (edir || diversity)) { fprintf(stderr, "--mmr does not go with --eval or --diversity\n"); return 1; }
+    if (pool && !mmr) { fprintf(stderr, "--pool goes with --mmr\n"); return 1; }
     if ((edir || diversity) ? (pos.empty() || pos.size() > 2) : pos.size() != 2) return usage();
     if (diversity && (with_scores || with_ranks || threshold != -INFINITY)) { fprintf(stderr, "--scores, --ranks and --threshold do not go with --diversity\n"); return 1; }
     if (!edir && !diversity && (!cuts.empty() || threshold != -INFINITY)) { fprintf(stderr, "-c and --threshold go with --eval\n"); return 1; }
     if (!edir && with_ranks) { fprintf(stderr, "--ranks goes with --eval\n"); return 1; }
+    if (mmr) {
+        if (!pool) pool = std::min(PCR_RECOMMEND_MAX_K, 10 * K);
+        if (pool < K) { fprintf(stderr, "--pool %d: below -K %d\n", pool, K); return 1; }
+    }
     if (edir && (ufile || with_scores)) { fprintf(stderr, "-u and --scores do not go with --eval\n"); return 1; }
     int64_t d1, d2, k;
     if (pcr_model_load(pos[0], &d1, &d2, &k, nullptr, nullptr) != PCR_OK) { fprintf(stderr, "can't open model file %s\n", pos[0]); return 1; }
@@ -289,8 +320,13 @@ int main(int argc, char** argv) {
     for (int64_t b0 = 0; b0 < n && ok; b0 += batch) {
         const int64_t m = std::min(batch, n - b0);
         items.resize((size_t)(m * K)); scores.resize((size_t)(m * K));
-        if (pcr_recommend_model(U.data(), d1, V.data(), d2, k, xdir ? xindex.data() : nullptr, xdir ? xitem.data() : nullptr, m, users.data() + b0, K,
-                                f32 ? PCR_F32 : PCR_F64, items.data(), scores.data(), 0) != PCR_OK) {
+        const int64_t* xi = xdir ? xindex.data() : nullptr;
+        const int32_t* xt = xdir ? xitem.data() : nullptr;
+        const int rc = mmr ? pcr_recommend_diverse_model(U.data(), d1, V.data(), d2, k, xi, xt, m, users.data() + b0, K, pool, theta,
+                                                         f32 ? PCR_F32 : PCR_F64, items.data(), scores.data(), 0)
+                           : pcr_recommend_model(U.data(), d1, V.data(), d2, k, xi, xt, m, users.data() + b0, K, f32 ? PCR_F32 : PCR_F64,
+                                                 items.data(), scores.data(), 0);
+        if (rc != PCR_OK) {
             fprintf(stderr, "recommend: %s\n", pcr_last_error());
             fclose(out_fp);
             return 1;

@@ -577,6 +577,9 @@ struct CcdSolver final : pcr_solver {
     int recommend(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores) override {
         return base->recommend_with(n, local, K, flags, items, scores, &prof);
     }
+    int recommend_diverse(int64_t n, const int32_t* local, int topk, int pool, double theta, int flags, int32_t* items, double* scores) override {
+        return base->recommend_diverse_with(n, local, topk, pool, theta, flags, items, scores, &prof);
+    }
     int evaluate_topn(int ncut, const int* cuts, double thr, int flags, pcr_topn_stats* stats, double* per_user) override {
         return base->evaluate_topn_with(ncut, cuts, thr, flags, stats, per_user, &prof);
     }

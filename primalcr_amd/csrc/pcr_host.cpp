@@ -362,7 +362,7 @@ extern "C" int pcr_dataset_from_csr(int64_t d1, int64_t d2, const int64_t* index
 static std::map<std::string, std::string>& tune_table() { static thread_local std::map<std::string, std::string> t; return t; }
 static const char* const TUNE_KEYS[] = {"ustep_mode", "cluster_k", "cluster_users", "ubins", "ustep_gram", "spmm_tiles", "spmm_chunk", "sddmm_csc",
                                         "lanes", "pipeline", "window_cache", "prepare_merged", "resort_window", "allreduce_chunks", "p2p_ll",
-                                        "p2p_timeout_ms", "p2p_queue_budget", "count_rows", "debug", "win16", "ustep_win_lds", "plan_key64", "ustep_newton", "vblock_users", "recommend_select", "ranks_batch_users", "fault_cluster_member", "fault_p2p_skip", "fault_p2p_coarse", nullptr};
+                                        "p2p_timeout_ms", "p2p_queue_budget", "count_rows", "debug", "win16", "ustep_win_lds", "plan_key64", "ustep_newton", "vblock_users", "recommend_select", "ranks_batch_users", "rerank_lds", "fault_cluster_member", "fault_p2p_skip", "fault_p2p_coarse", nullptr};
 extern "C" int pcr_tune(const char* key, const char* value) {
     if (!key) { pcr_set_error("pcr_tune: null key"); return PCR_ERR_ARG; }
     bool known = false;
@@ -1252,6 +1252,25 @@ int pcr_evaluate_diversity_model_check(const double* U, int64_t d1, const double
     static const int32_t no_items = 0;         // (the lists stay on the device: nothing for the output check to find missing)
     static const double no_scores = 0.0;
     return pcr_recommend_model_check(U, d1, V, d2, k, index, item, n, users, cutoffs[ncut - 1], dtype, &no_items, &no_scores, sorted, who);
+}
+
+// ------------------------------------------------------------------------------ MMR re-ranking (include/primalcr.h)
+int pcr_rerank_check(const char* who, int topk, int pool, double theta) {
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
+    if (topk < 1) return bad("topk = " + std::to_string(topk) + " below 1");
+    if (pool < topk) return bad("pool = " + std::to_string(pool) + " below topk = " + std::to_string(topk));
+    if (pool > PCR_RECOMMEND_MAX_K) return bad("pool = " + std::to_string(pool) + " above " + std::to_string(PCR_RECOMMEND_MAX_K));
+    if (!(theta >= 0.0 && theta <= 1.0)) return bad("theta must be in [0, 1]");       // (a NaN fails both compares)
+    return PCR_OK;
+}
+
+int pcr_recommend_diverse_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
+                                      const int32_t* item, int64_t n, const int32_t* users, int topk, int pool, double theta, int dtype,
+                                      const int32_t* items, const double* scores, bool* sorted) {
+    static const char* who = "pcr_recommend_diverse_model";
+    const int rc = pcr_rerank_check(who, topk, pool, theta);
+    if (rc != PCR_OK) return rc;
+    return pcr_recommend_model_check(U, d1, V, d2, k, index, item, n, users, pool, dtype, items, scores, sorted, who);
 }
 
 int pcr_exposure_stats(const int64_t* exposure, int64_t d2, int64_t* recs, int64_t* items_covered, double* coverage, double* gini) {

@@ -110,6 +110,13 @@ int pcr_evaluate_diversity_model_check(const double* U, int64_t d1, const double
                                        const pcr_diversity_stats* stats, bool* sorted);
 // info[j] = log2((d1 + 1) / (pop[j] + 1)) for the d2 popularity counts pop (exact integers in fp64)
 void pcr_diversity_info(int64_t d1, const double* pop, int64_t d2, double* info);
+// pcr_recommend_diverse's own arguments: 1 <= topk <= pool <= PCR_RECOMMEND_MAX_K, theta in [0, 1] (a NaN is refused)
+int pcr_rerank_check(const char* who, int topk, int pool, double theta);
+// pcr_recommend_diverse_model's argument checks (shared with the sanitizer build's stub): pcr_rerank_check, then the factor /
+// user / exclusion / output checks of pcr_recommend_model.  *sorted as pcr_recommend_model_check.
+int pcr_recommend_diverse_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
+                                      const int32_t* item, int64_t n, const int32_t* users, int topk, int pool, double theta, int dtype,
+                                      const int32_t* items, const double* scores, bool* sorted);
 // stats[c] from the reduced sums (k_topn_fin's layout: [ncut][8] = sum len, sum novelty, -, users with len >= 1, -, -, sum ild,
 // users_ild; then the requested users) and the cumulative exposure rows expo[ncut][d2] (exact integers in fp64); exposure
 // (may be NULL) receives them as int64.  pcr_exposure_stats' return code.

@@ -449,6 +449,80 @@ static int div_run(hipStream_t st, const T* U, const T* V, int r, int ld, int64_
     return PCR_OK;
 }
 
+// MMR re-ranking (pcr_recommend_diverse, pcr_topk.h): the form and the workgroup shape of k_rec_merge_mmr for a pool of K rows
+// of ld values.  The streaming form is the default: it was the faster one at every shape measured.
+// pcr_tune("rerank_lds", "1") takes the LDS form, which stages the pool's rows, whenever one wave's image fits a workgroup's
+// 160 KiB.  waves = users per workgroup (4, 2 or 1, as many as fit).
+static const size_t MMR_LDS_CU = (size_t)160 * 1024;
+struct MmrShape { int form = 0, waves = 0; size_t lds = 0; };
+template <typename T>
+static MmrShape mmr_shape(int K, int ld, int knob) {
+    MmrShape s;
+    s.form = (knob > 0 && mmr_wave_lds<T>(K, ld, 1) <= MMR_LDS_CU) ? 1 : 0;
+    const size_t per = mmr_wave_lds<T>(K, ld, s.form);
+    for (int w = 4; w >= 1; w >>= 1) if ((size_t)w * per <= MMR_LDS_CU) { s.waves = w; break; }
+    s.lds = (size_t)s.waves * per;
+    return s;
+}
+
+// rec_run's sink for the re-ranking: merge + greedy selection (k_rec_merge_mmr) of topk from the pool of K, to the host arrays
+// items / scores (n x topk)
+template <typename T>
+struct RecRerank {
+    hipStream_t st;
+    int K, topk;
+    double theta;
+    const T* V;
+    int r, ld;
+    const double* inv;
+    MmrShape shape;
+    int32_t* items;
+    double* scores;
+    DBuf<int32_t> oi;
+    DBuf<double> os;
+    RecRerank(hipStream_t st_, int K_, int topk_, double theta_, const T* V_, int r_, int ld_, const double* inv_, MmrShape shape_,
+              int32_t* items_, double* scores_)
+        : st(st_), K(K_), topk(topk_), theta(theta_), V(V_), r(r_), ld(ld_), inv(inv_), shape(shape_), items(items_), scores(scores_) {}
+    int begin(int64_t nb) { RC(oi.alloc((size_t)nb * topk)); RC(os.alloc((size_t)nb * topk)); return PCR_OK; }
+    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp, Profiler* prof) {
+        MmrArgs ma;
+        ma.inv = inv; ma.out_i = oi.p; ma.out_s = os.p; ma.topk = topk; ma.theta = theta;
+        {
+            ProfScope ps(prof, "recommend/rerank", st);
+            const dim3 grid((unsigned)cdiv(m, shape.waves)), block(64 * shape.waves);
+            if (shape.form) hipLaunchKernelGGL((k_rec_merge_mmr<T, 1>), grid, block, shape.lds, st, ls, li, ln, nsp, m, K, V, r, ld, ma);
+            else hipLaunchKernelGGL((k_rec_merge_mmr<T, 0>), grid, block, shape.lds, st, ls, li, ln, nsp, m, K, V, r, ld, ma);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(items + b0 * topk, oi.p, (size_t)m * topk * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(scores + b0 * topk, os.p, (size_t)m * topk * sizeof(double), hipMemcpyDeviceToHost, st));
+        return PCR_OK;
+    }
+};
+
+// The re-ranked lists of the n users h_users (rows of U and of the exclusion CSR, as rec_run; NULL: rows 0..n-1): the row norms
+// (k_div_prepare, as the ILD's), then the sweep with K = pool and RecRerank.  "recommend/rerank" times everything but the
+// score kernel.  pcr_tune("rerank_lds") is read at every call.  k_div_prepare is reused as it is, so its second table q[d2] (the
+// ILD's |v^_j|^2) is allocated and written here too although the re-ranking never reads it: one d2-sized buffer per call.
+template <typename T>
+static int rerank_run(hipStream_t st, const T* U, const T* V, int r, int ld, int64_t d2, const int64_t* xptr, const int32_t* xitem,
+                      int64_t n, const int32_t* h_users, int topk, int pool, double theta, Profiler* prof, int32_t* items, double* scores) {
+    if (n <= 0) return PCR_OK;
+    const MmrShape shape = mmr_shape<T>(pool, ld, pcr_tune_int("rerank_lds", 0));
+    if (shape.waves < 1) { pcr_set_error("pcr_recommend_diverse: rank " + std::to_string(r) + " is too large for the re-ranking kernel's LDS"); return PCR_ERR_UNSUPPORTED; }
+    DBuf<double> inv, q;
+    RC(inv.alloc((size_t)d2)); RC(q.alloc((size_t)d2));
+    if (shape.form) HIPCHK(hipFuncSetAttribute((const void*)k_rec_merge_mmr<T, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds));
+    else HIPCHK(hipFuncSetAttribute((const void*)k_rec_merge_mmr<T, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds));
+    {
+        ProfScope ps(prof, "recommend/rerank", st);
+        hipLaunchKernelGGL((k_div_prepare<T>), dim3((unsigned)cdiv(d2, 4)), dim3(256), 0, st, V, r, ld, d2, inv.p, q.p);
+        HIPCHK(hipGetLastError());
+    }
+    return rec_run<T>(st, U, V, r, ld, d2, xptr, xitem, n, h_users, pool, 1, prof,
+                      RecRerank<T>(st, pool, topk, theta, V, r, ld, inv.p, shape, items, scores));
+}
+
 // Exact rank metrics (pcr_evaluate_ranks, pcr_topk.h): the relevance table of a threshold on the device (PcrTopnRel's users,
 // rptr and ritem; uploaded once per threshold) and the outputs: rrank[nrel] the ranks of ritem entry for entry, met[n][6]
 // k_rank_finish's rows, the reduced sums [8] + the count
@@ -626,6 +700,9 @@ struct pcr_solver {
     virtual int set_ccd_params(const pcr_ccd_params*) { pcr_set_error("pcr_solver_set_ccd_params: not a CCDR1 solver (solver type 0)"); return PCR_ERR_STATE; }
     // pcr_recommend: `local` = rows of this shard (checked by the caller)
     virtual int recommend(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores) = 0;
+    // pcr_recommend_diverse: `local` = rows of this shard (arguments checked by the caller)
+    virtual int recommend_diverse(int64_t n, const int32_t* local, int topk, int pool, double theta, int flags, int32_t* items,
+                                  double* scores) = 0;
     // pcr_evaluate_topn (arguments checked by the caller)
     virtual int evaluate_topn(int ncut, const int* cuts, double threshold, int flags, pcr_topn_stats* stats, double* per_user) = 0;
     // pcr_evaluate_ranks (arguments checked by the caller)
@@ -2758,6 +2835,16 @@ struct Solver final : pcr_solver {
     int recommend(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores) override {
         return recommend_with(n, local, K, flags, items, scores, &prof);
     }
+    // MMR re-ranked lists from the device factors: per user, nothing is exchanged
+    int recommend_diverse_with(int64_t n, const int32_t* local, int topk, int pool, double theta, int flags, int32_t* items, double* scores,
+                               Profiler* prof) {
+        const bool ex = (flags & PCR_REC_EXCLUDE_TRAIN) != 0;
+        return rerank_run<T>(st, d_U.p, d_V.p, geo.r, geo.ld, d2, ex ? d_uptr.p : nullptr, ex ? d_item.p : nullptr, n, local, topk, pool, theta,
+                             prof, items, scores);
+    }
+    int recommend_diverse(int64_t n, const int32_t* local, int topk, int pool, double theta, int flags, int32_t* items, double* scores) override {
+        return recommend_diverse_with(n, local, topk, pool, theta, flags, items, scores, &prof);
+    }
     // beyond-accuracy metrics of the shard's users from the device factors; the self-information table comes from the shard's
     // training ratings (all-reduced with a communicator) and is kept: the ratings never change, the exchange mode can
     int evaluate_diversity_with(int64_t n, const int32_t* local, int ncut, const int* cuts, int flags, pcr_diversity_stats* stats,
@@ -3143,6 +3230,26 @@ int pcr_evaluate_diversity_model(const double* U, int64_t d1, const double* V, i
     });
 }
 
+int pcr_recommend_diverse_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                                int64_t n, const int32_t* users, int topk, int pool, double theta, int dtype, int32_t* items, double* scores,
+                                int device) {
+    return abi_guard("pcr_recommend_diverse_model", [&]() -> int {
+    bool sorted = true;
+    RC(pcr_recommend_diverse_model_check(U, d1, V, d2, k, index, item, n, users, topk, pool, theta, dtype, items, scores, &sorted));
+    RC(model_device(device));
+    if (n == 0) return PCR_OK;
+    auto run = [&](auto zero) -> int {
+        using T = decltype(zero);
+        hipStream_t st = nullptr;
+        ModelDev<T> M;
+        RC(M.upload_exclusion(d1, index, item, sorted));
+        RC(M.upload_factors(st, U, d1, V, d2, k));
+        return rerank_run<T>(st, M.U(), M.V(), (int)k, M.ld, d2, M.dx.p, M.di.p, n, users, topk, pool, theta, nullptr, items, scores);
+    };
+    return dtype == PCR_F64 ? run(0.0) : run(0.0f);
+    });
+}
+
 // users[n] (global ids, NULL: the whole shard) as rows of s's shard in loc (left empty for NULL); *n the count
 static int shard_rows(const char* who, const pcr_solver* s, int64_t* n, const int32_t* users, std::vector<int32_t>& loc) {
     if (!users) { *n = s->n_users; return PCR_OK; }
@@ -3183,6 +3290,20 @@ int pcr_recommend(pcr_solver* s, int64_t n, const int32_t* users, int topk, int 
         std::vector<int32_t> loc;
         RC(shard_rows("pcr_recommend", s, &n, users, loc));
         return s->recommend(n, users ? loc.data() : nullptr, topk, flags, items, scores);
+    });
+}
+
+int pcr_recommend_diverse(pcr_solver* s, int64_t n, const int32_t* users, int topk, int pool, double theta, int flags, int32_t* items,
+                          double* scores) {
+    S_OR_ARG;
+    RC(pcr_rerank_check("pcr_recommend_diverse", topk, pool, theta));
+    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_recommend_diverse: unknown flags"); return PCR_ERR_ARG; }
+    if (!users) n = s->n_users;
+    if (n < 0 || (n > 0 && (!items || !scores))) { pcr_set_error("pcr_recommend_diverse: bad argument"); return PCR_ERR_ARG; }
+    return abi_guard("pcr_recommend_diverse", [&]() -> int {
+        std::vector<int32_t> loc;
+        RC(shard_rows("pcr_recommend_diverse", s, &n, users, loc));
+        return s->recommend_diverse(n, users ? loc.data() : nullptr, topk, pool, theta, flags, items, scores);
     });
 }
 

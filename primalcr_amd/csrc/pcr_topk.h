@@ -19,6 +19,8 @@
 //   stays in LDS and is scored against the user's relevant test items; k_topn_sum1 / k_topn_fin reduce the per-user metrics.
 // k_rank_relscore / k_rank_sort / k_rank_count / k_rank_finish: the exact full-catalogue rank metrics (pcr_evaluate_ranks, DESIGN.md
 //   section 3.12): the same sweep with a counting tail in place of the selecting one, at the end of this file.
+// k_rec_merge_div / k_rec_merge_mmr: the same merge with the beyond-accuracy metrics (section 3.13) or the greedy MMR re-ranking
+//   (pcr_recommend_diverse, section 3.14) fused into its tail, further down in this file.
 // No atomic decides a result: the LDS slot counter only decides where a candidate sits in the buffer, and the merges rank by
 // the total order (score, id), so every list is the same whatever the order of arrival.
 #pragma once
@@ -748,4 +750,203 @@ __global__ __launch_bounds__(256) void k_rec_merge_div(const T* __restrict__ lst
     const int myc = lane / 6, myf = lane - 6 * myc;
     const double f0 = __shfl(dl, myc), f1 = __shfl(novelty, myc), f5 = __shfl(ild, myc);
     if (lane < 6 * da.ncut) da.out[(size_t)idx * 6 * da.ncut + lane] = myf == 0 ? f0 : myf == 1 ? f1 : myf == 5 ? f5 : 0.0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// MMR diversity re-ranking (pcr_recommend_diverse, include/primalcr.h): greedy selection of topk entries
+// from the merged pool of K = pool entries, m_i = (1 - theta) (s_i - smin) - theta R max_{a in S} cos(j_i, j_a), in fp64.
+namespace rec {
+constexpr int MMR_ROWS = DIV_ROWS;   // streaming form: rows of V in flight per wave (one transposing butterfly reduces them together)
+constexpr int MMR_PT = 4;            // LDS form: candidates a lane scores against one read of the winner's row
+}  // namespace rec
+
+struct MmrArgs {
+    const double* inv;    // [d2] 1 / |V[j]| (k_div_prepare)
+    int32_t* out_i;       // [n][topk]
+    double* out_s;        // [n][topk]
+    int topk;
+    double theta;
+};
+
+// LDS form: the row stride of the staged image in elements -- an odd number of 16-byte slots, so that by the bank rule the 16
+// lanes of a ds_read_b128 group, one row each, fall on 16 different slots of the 64-bank row (not confirmed by a counter run)
+template <typename T>
+__host__ __device__ inline int mmr_row_stride(int ld) {
+    const int per = 16 / (int)sizeof(T);
+    return ((ld / per) | 1) * per;
+}
+// LDS of one wave of k_rec_merge_mmr: the image [K][stride] (LDS form) or the winner's row [ld] doubles (streaming form), then
+// c[K] doubles, the pool's scores [K] and ids [K]
+template <typename T>
+__host__ __device__ inline size_t mmr_wave_lds(int K, int ld, int form) {
+    const size_t b = (form ? (size_t)K * mmr_row_stride<T>(ld) * sizeof(T) : (size_t)ld * sizeof(double)) +
+                     (size_t)K * (sizeof(double) + sizeof(T) + sizeof(int));
+    return (b + 15) & ~(size_t)15;
+}
+
+// one step of the arg-max butterfly: the larger m, equal m to the smaller position (INT_MAX: no entry)
+template <int OFF>
+__device__ __forceinline__ void mmr_best(double& bm, int& bp) {
+    const double om = lane_xor<OFF>(bm);
+    const int op = lane_xor_i<OFF>(bp);
+    if (op != INT_MAX && (bp == INT_MAX || om > bm || (om == bm && op < bp))) { bm = om; bp = op; }
+}
+
+// k_rec_merge with the greedy re-ranking fused into its tail, one wave per user (blockDim.x / 64 users per workgroup): the
+// merged pool goes to the wave's LDS (ids, scores) with c_i next to it.  The pool is in list order, so smin and the maximum are
+// its two ends.  Each round: every lane forms m_i of its positions p = lane, lane + 64, ... (ascending, strict compare: the
+// smaller position keeps a tie), a fixed xor butterfly picks the winner, lane 0 writes it out and marks it (id -> -1 - id), then
+// c_i = max(c_i, cos(j_i, j_w)) for the entries left, cos = (sum_c V[j_i][c] V[j_w][c]) (inv[j_i] inv[j_w]) with every product
+// and sum in fp64.  theta R = 0 needs no cosine at all.
+//   FORM 0 (streaming)  lane = component: the winner's row sits in LDS as doubles; MMR_ROWS candidate rows are gathered coalesced
+//          from global memory before the first is used, their partial dot products are reduced together by a transposing
+//          butterfly (8 -> 4 -> 2 -> 1 values per lane over xor 32, 16, 8, then xor 4, 2, 1) and lanes 0, 8, ..., 56 update one
+//          candidate each.
+//   FORM 1 (LDS)        lane = candidate: the pool's rows are staged once into the image (padding components zeroed); a lane
+//          walks its candidates' rows 16 bytes at a time against a broadcast read of the winner's row, MMR_PT candidates per read.
+// Both forms add the products of a pair in an order fixed by the code; a row depends on its pool and V alone.
+template <typename T, int FORM>
+__global__ __launch_bounds__(256) void k_rec_merge_mmr(const T* __restrict__ lst_s, const int32_t* __restrict__ lst_i,
+                                                       const int32_t* __restrict__ lst_n, int nsplit, int64_t n, int K,
+                                                       const T* __restrict__ V, int r, int ld, MmrArgs ma) {
+    typedef typename RecMma<T>::vec_t vec_t;
+    constexpr int PER = RecMma<T>::KV;                               // elements per 16 bytes
+    extern __shared__ __align__(16) char rec_lds[];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t idx = (int64_t)blockIdx.x * (blockDim.x >> 6) + w;
+    if (idx >= n) return;
+    const int rs = mmr_row_stride<T>(ld);
+    char* wl = rec_lds + (size_t)w * mmr_wave_lds<T>(K, ld, FORM);
+    T* img = (T*)wl;
+    double* wr = (double*)wl;
+    double* cc = (double*)(wl + (FORM ? (size_t)K * rs * sizeof(T) : (size_t)ld * sizeof(double)));
+    T* ss = (T*)(cc + K);
+    int* si = (int*)(ss + K);
+    const int tot = rec_merge_ranks(lst_s, lst_i, lst_n, nsplit, n, K, idx, lane, [&](int rk, int j, T s) { si[rk] = j; ss[rk] = s; });
+    const int L = __builtin_amdgcn_readfirstlane(min(tot, K));      // the pool is [0, L): no padding inside
+    const int rounds = min(ma.topk, L);
+    int32_t* oi = ma.out_i + (size_t)idx * ma.topk;
+    double* os = ma.out_s + (size_t)idx * ma.topk;
+    for (int p = rounds + lane; p < ma.topk; p += 64) { oi[p] = -1; os[p] = -INFINITY; }
+    if (L == 0) return;
+    wave_sync();
+    for (int p = lane; p < L; p += 64) cc[p] = -INFINITY;
+    if (FORM) {
+        const int nv = ld / PER;
+#pragma unroll 4
+        for (int e = lane; e < L * nv; e += 64) {
+            const int p = e / nv, v = e - p * nv;
+            vec_t x = *(const vec_t*)(V + (size_t)(unsigned)si[p] * (unsigned)ld + v * PER);
+#pragma unroll
+            for (int q = 0; q < PER; ++q) if (v * PER + q >= r) x[q] = (T)0;
+            *(vec_t*)(img + (size_t)p * rs + v * PER) = x;
+        }
+    }
+    const double smin = (double)ss[L - 1];
+    double R = (double)ss[0] - smin;
+    if (R == 0.0) R = 1.0;
+    const double a = 1.0 - ma.theta, b = ma.theta * R;
+    wave_sync();
+    for (int t = 0; t < rounds; ++t) {
+        const bool usec = t > 0 && b != 0.0;                         // (c_i = 0 while S is empty)
+        double bm = -INFINITY;
+        int bp = INT_MAX;
+        for (int p = lane; p < L; p += 64) {
+            if (si[p] < 0) continue;
+            double m = a * ((double)ss[p] - smin);
+            if (usec) m -= b * cc[p];
+            if (!(m == m)) m = -INFINITY;                            // (a total order whatever the factors hold)
+            if (bp == INT_MAX || m > bm) { bm = m; bp = p; }
+        }
+        mmr_best<32>(bm, bp); mmr_best<16>(bm, bp); mmr_best<8>(bm, bp); mmr_best<4>(bm, bp); mmr_best<2>(bm, bp); mmr_best<1>(bm, bp);
+        const int wp = __builtin_amdgcn_readfirstlane(bp);
+        if (wp < 0 || wp >= L) break;                                // (cannot happen: rounds <= L entries are left)
+        const int jw = __builtin_amdgcn_readfirstlane(si[wp]);
+        wave_sync();
+        if (lane == 0) { oi[t] = jw; os[t] = (double)ss[wp]; si[wp] = -1 - jw; }
+        wave_sync();
+        if (t + 1 == rounds || b == 0.0) continue;                   // (wave-uniform)
+        const double invw = ma.inv[jw];
+        if (FORM) {
+            const int nv = ld / PER;
+            const T* wrow = img + (size_t)wp * rs;
+            for (int p0 = 0; p0 < L; p0 += 64 * rec::MMR_PT) {
+                double acc[rec::MMR_PT];
+                const T* row[rec::MMR_PT];
+                int id[rec::MMR_PT];
+#pragma unroll
+                for (int e = 0; e < rec::MMR_PT; ++e) {
+                    const int p = p0 + 64 * e + lane;
+                    id[e] = p < L ? si[p] : -1;
+                    row[e] = img + (size_t)(id[e] >= 0 ? p : wp) * rs;
+                    acc[e] = 0.0;
+                }
+                for (int v = 0; v < nv; ++v) {
+                    const vec_t xw = *(const vec_t*)(wrow + v * PER);
+#pragma unroll
+                    for (int e = 0; e < rec::MMR_PT; ++e) {
+                        if (p0 + 64 * e >= L) break;                 // (wave-uniform)
+                        const vec_t x = *(const vec_t*)(row[e] + v * PER);
+#pragma unroll
+                        for (int q = 0; q < PER; ++q) acc[e] += (double)x[q] * (double)xw[q];
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < rec::MMR_PT; ++e) {
+                    const int p = p0 + 64 * e + lane;
+                    if (id[e] >= 0) cc[p] = fmax(cc[p], acc[e] * (ma.inv[id[e]] * invw));
+                }
+            }
+        } else {
+            static_assert(rec::MMR_ROWS == 8, "the transposing butterfly below reduces eight rows");
+            for (int c = lane; c < ld; c += 64) wr[c] = c < r ? (double)V[(size_t)(unsigned)jw * (unsigned)ld + c] : 0.0;
+            wave_sync();
+            for (int i0 = 0; i0 < L; i0 += rec::MMR_ROWS) {
+                double acc[rec::MMR_ROWS];
+                int id[rec::MMR_ROWS];
+                bool any = false;
+#pragma unroll
+                for (int e = 0; e < rec::MMR_ROWS; ++e) {
+                    id[e] = __builtin_amdgcn_readfirstlane(i0 + e < L ? si[i0 + e] : -1);
+                    any = any || id[e] >= 0;
+                    acc[e] = 0.0;
+                }
+                if (!any) continue;                                  // (wave-uniform)
+                for (int cb = 0; cb < r; cb += 64 * rec::DIV_CH) {
+                    T x[rec::MMR_ROWS][rec::DIV_CH];
+#pragma unroll
+                    for (int e = 0; e < rec::MMR_ROWS; ++e)
+#pragma unroll
+                        for (int q = 0; q < rec::DIV_CH; ++q) {
+                            const int c = cb + 64 * q + lane;
+                            x[e][q] = (id[e] >= 0 && c < r) ? V[(size_t)(unsigned)id[e] * (unsigned)ld + c] : (T)0;
+                        }
+#pragma unroll
+                    for (int q = 0; q < rec::DIV_CH; ++q) {
+                        const int c = cb + 64 * q + lane;
+                        const double wv = c < r ? wr[c] : 0.0;
+#pragma unroll
+                        for (int e = 0; e < rec::MMR_ROWS; ++e) acc[e] += (double)x[e][q] * wv;
+                    }
+                }
+                // eight sums over the 64 lanes at once: each xor step halves the values a lane carries
+                const bool h32 = (lane & 32) != 0, h16 = (lane & 16) != 0, h8 = (lane & 8) != 0;
+                double a4[4], a2[2];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) a4[e] = (h32 ? acc[e + 4] : acc[e]) + lane_xor<32>(h32 ? acc[e] : acc[e + 4]);
+#pragma unroll
+                for (int e = 0; e < 2; ++e) a2[e] = (h16 ? a4[e + 2] : a4[e]) + lane_xor<16>(h16 ? a4[e] : a4[e + 2]);
+                double a1 = (h8 ? a2[1] : a2[0]) + lane_xor<8>(h8 ? a2[0] : a2[1]);
+                a1 += lane_xor<4>(a1);
+                a1 += lane_xor2(a1);
+                a1 += lane_xor1(a1);
+                const int p = i0 + (h32 ? 4 : 0) + (h16 ? 2 : 0) + (h8 ? 1 : 0);   // the candidate this lane's sum belongs to
+                if ((lane & 7) == 0 && p < L) {
+                    const int j = si[p];
+                    if (j >= 0) cc[p] = fmax(cc[p], a1 * (ma.inv[j] * invw));
+                }
+            }
+        }
+        wave_sync();
+    }
 }

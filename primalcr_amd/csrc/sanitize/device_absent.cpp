@@ -91,4 +91,10 @@ int pcr_evaluate_diversity_model(const double* U, int64_t d1, const double* V, i
     return rc != PCR_OK ? rc : absent();
 }
 NO_SOLVER(pcr_evaluate_diversity, pcr_solver*, int64_t, const int32_t*, int, const int*, int, pcr_diversity_stats*, double*, int64_t*)
+int pcr_recommend_diverse_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                                int64_t n, const int32_t* users, int topk, int pool, double theta, int dtype, int32_t* items, double* scores, int) {
+    const int rc = pcr_recommend_diverse_model_check(U, d1, V, d2, k, index, item, n, users, topk, pool, theta, dtype, items, scores, nullptr);
+    return rc != PCR_OK ? rc : absent();
+}
+NO_SOLVER(pcr_recommend_diverse, pcr_solver*, int64_t, const int32_t*, int, int, double, int, int32_t*, double*)
 }
