@@ -574,22 +574,7 @@ struct CcdSolver final : pcr_solver {
     int set_factors(const double* U, const double* V, bool local) override { begun = false; return base->set_factors(U, V, local); }
     int get_factors(double* U, double* V, bool local) override { return base->get_factors(U, V, local); }
     int evaluate(int which, int ndcg_k, double* err, double* ndcg) override { return base->evaluate(which, ndcg_k, err, ndcg); }
-    int recommend(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores) override {
-        return base->recommend_with(n, local, K, flags, items, scores, &prof);
-    }
-    int recommend_diverse(int64_t n, const int32_t* local, int topk, int pool, double theta, int flags, int32_t* items, double* scores) override {
-        return base->recommend_diverse_with(n, local, topk, pool, theta, flags, items, scores, &prof);
-    }
-    int evaluate_topn(int ncut, const int* cuts, double thr, int flags, pcr_topn_stats* stats, double* per_user) override {
-        return base->evaluate_topn_with(ncut, cuts, thr, flags, stats, per_user, &prof);
-    }
-    int evaluate_ranks(double thr, int flags, pcr_rank_stats* stats, double* per_user, int64_t* ranks) override {
-        return base->evaluate_ranks_with(thr, flags, stats, per_user, ranks, &prof);
-    }
-    int evaluate_diversity(int64_t n, const int32_t* local, int ncut, const int* cuts, int flags, pcr_diversity_stats* stats, double* per_user,
-                           int64_t* exposure) override {
-        return base->evaluate_diversity_with(n, local, ncut, cuts, flags, stats, per_user, exposure, &prof);
-    }
+    void serve_view(ServeView* v) override { base->serve_view(v); v->prof = &prof; }   // (the "recommend/..." slots are this solver's)
     int residual_mismatch(double* value) override {
         hipLaunchKernelGGL((k_ccd_mismatch<RT>), dim3(B), dim3(ccd::BLOCK), 0, st, (const RT*)d_res_r.p, (const RT*)d_res_c.p, (const int32_t*)d_c2r.p,
                            nnz, d_pmis.p);

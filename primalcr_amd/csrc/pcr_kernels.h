@@ -1,8 +1,8 @@
 // pcr_kernels.h -- hand-written HIP kernels for gfx950 (CDNA4, wave64) of the PrimalCR /
 // PrimalCR++ hot path.  Header-only templates, instantiated in pcr_solver.hip:
 //   pcr_prims.h (wave / team primitives, sorts, sweep coefficients, row primitives), pcr_vside.h (V step), pcr_ustep.h (U step),
-//   pcr_eval.h (evaluator, objective reductions, predict); pcr_gram.h (optional dual-form U step on MFMA); pcr_topk.h (top-K
-//   recommendation: MFMA scores with a fused streaming selection).
+//   pcr_eval.h (evaluator, objective reductions, predict); pcr_gram.h (optional dual-form U step on MFMA).  Not part of this header:
+//   pcr_topk.h (top-K recommendation: MFMA scores with a fused streaming selection), instantiated in pcr_serve.hip over pcr_prims.h.
 //
 // Kernel map (reference site -> kernel); design and rooflines: DESIGN.md section 3:
 //   K1        comp_m_new, b = u.a in compute_Ha_new        -> k_sddmm     (rating-parallel)
@@ -32,4 +32,3 @@
 #include "pcr_vside.h"
 #include "pcr_ustep.h"
 #include "pcr_eval.h"
-#include "pcr_topk.h"

@@ -724,3 +724,23 @@ static inline size_t carve_bytes(size_t n, size_t elt) { return (n * elt + 15) &
 
 __device__ __forceinline__ int next_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
 
+#define PCR_EW_BLOCK 256      // workgroup of the elementwise kernels and of the two-stage reductions (pcr_vside.h, pcr_topk.h)
+
+// fp64 row-major rows x r (the reference's mat_t payload) <-> the device's rows x ld matrix of T (pad columns zero)
+template <typename T>
+__global__ __launch_bounds__(256) void k_mat_in(const double* __restrict__ src, T* __restrict__ dst, int64_t rows, int r, int ld) {
+    const int64_t n = rows * ld;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / ld;
+        const int col = (int)(i - row * ld);
+        dst[i] = col < r ? (T)src[row * r + col] : (T)0;
+    }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_mat_out(const T* __restrict__ src, double* __restrict__ dst, int64_t rows, int r, int ld) {
+    const int64_t n = rows * r;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / r;
+        dst[i] = (double)src[row * ld + (i - row * r)];
+    }
+}

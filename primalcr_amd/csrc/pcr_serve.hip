@@ -1,0 +1,728 @@
+// pcr_serve.hip -- the serving layer behind the C ABI of include/primalcr.h: top-K recommendation, its top-N, rank and
+// beyond-accuracy evaluations and the MMR re-ranking, over the kernels of pcr_topk.h.
+//
+// Every entry exists twice: on a trained solver (pcr_recommend, ...) and on a model in host memory (pcr_recommend_model, ...).
+// Both come down to a ServeView (pcr_dev.h) -- filled by the solver (pcr_solver::serve_view) or by ModelDev, which uploads the
+// model for one call -- and one function per entry over that view, which picks the precision.  Training is pcr_solver.hip.
+// There is NO CPU compute path in this file: every [device] entry point fails with PCR_ERR_DEVICE when HIP is unusable.
+#include <cmath>
+
+#include "pcr_dev.h"
+#include "pcr_prims.h"
+#include "pcr_topk.h"
+
+int ServeView::sum(double* dev, size_t count) const { return owner ? owner->allreduce_f64(dev, count) : PCR_OK; }
+int ServeView::wait() const { if (owner) return owner->sync(); HIPCHK(hipStreamSynchronize(st)); return PCR_OK; }
+template <typename T> static const T* serve_U(const ServeView& v) { return static_cast<const T*>(v.U); }
+template <typename T> static const T* serve_V(const ServeView& v) { return static_cast<const T*>(v.V); }
+// run(T()) for the view's precision
+template <class F>
+static int by_precision(const ServeView& v, F&& run) { return v.dtype == PCR_F64 ? run(0.0) : run(0.0f); }
+// the cut[] array of TopnArgs / DivArgs: the ncut cutoffs, then zeros
+static void fill_cuts(int* dst, int ncut, const int* cuts) {
+    for (int c = 0; c < PCR_TOPN_MAX_CUTOFFS; ++c) dst[c] = c < ncut ? cuts[c] : 0;
+}
+
+// Top-K recommendation (pcr_topk.h) for the n users h_users[0..n) -- rows of v's U and of its exclusion CSR (xptr() NULL:
+// none), or rows 0..n-1 when h_users is NULL.  Users go in batches whose partial lists stay under REC_SCRATCH bytes; the item
+// range is split across workgroups until the grid holds about REC_TARGET_WG workgroups (ml1m's 6 040 users are 95 workgroups
+// of 64).  Each batch's partial lists go to the sink: sink.begin(nb) once with the largest batch, then sink.batch(b0, m, ...)
+// per batch, which merges them (RecCopy: into pcr_recommend's host arrays; RecTopn: into the top-N metrics).  The launches
+// are timed in v.prof's "recommend/..." slots (NULL: not profiled).  select = 0 only for tools/exp_recommend.py's GEMM-alone timing (lists come back empty).
+static const size_t REC_SCRATCH = (size_t)1 << 30;
+static const int REC_TARGET_WG = 1024, REC_MAX_SPLIT = 16, REC_MIN_SPLIT_ITEMS = 1024;
+// The user batches and item splits of a sweep over n users whose scratch takes per_user bytes per user and split (rec_run and
+// rank_run share this arithmetic): nb users per batch, at most smax splits
+struct RecGeom {
+    int64_t d2, nb = 0;
+    int smax = 1;
+    static constexpr int64_t users_per_wg = (int64_t)rec::WAVES * rec::UW;
+    int splits_for(int64_t users) const {
+        const int64_t wg = (users + users_per_wg - 1) / users_per_wg;
+        int64_t s = std::max<int64_t>(1, (REC_TARGET_WG + wg - 1) / wg);
+        s = std::min<int64_t>(s, std::max<int64_t>(1, d2 / REC_MIN_SPLIT_ITEMS));
+        return (int)std::min<int64_t>(s, REC_MAX_SPLIT);
+    }
+    RecGeom(int64_t n, int64_t d2_, size_t per_user) : d2(d2_) {
+        nb = std::min<int64_t>(n, std::max<int64_t>(users_per_wg, (int64_t)(REC_SCRATCH / (per_user * 2)) / users_per_wg * users_per_wg));
+        while (nb > users_per_wg && (size_t)nb * (size_t)splits_for(nb) * per_user > REC_SCRATCH) nb = std::max<int64_t>(users_per_wg, nb / 2);
+        smax = splits_for(std::min(nb, n));
+    }
+    // a batch of m users: the items per split (whole steps) and the splits launched
+    void batch(int64_t m, int* per, int* nsp) const {
+        const int ns = std::min(splits_for(m), smax);      // (a short last batch keeps the scratch of the first)
+        *per = (int)(((d2 + ns - 1) / ns + rec::TILE - 1) / rec::TILE * rec::TILE);
+        *nsp = (int)((d2 + *per - 1) / *per);
+    }
+};
+
+template <typename T, class Sink>
+static int rec_run(const ServeView& v, int64_t n, const int32_t* h_users, int K, int select, Sink&& sink) {
+    if (n <= 0) return PCR_OK;
+    hipStream_t st = v.st;
+    const size_t per_user = (size_t)K * (sizeof(T) + sizeof(int32_t)) + sizeof(int32_t);
+    const RecGeom geom(n, v.d2, per_user);
+    const int64_t users_per_wg = RecGeom::users_per_wg, nb = geom.nb;
+    const int smax = geom.smax;
+    DBuf<T> ls; DBuf<int32_t> li, ln, du;
+    RC(ls.alloc((size_t)nb * smax * K)); RC(li.alloc((size_t)nb * smax * K)); RC(ln.alloc((size_t)nb * smax));
+    RC(du.alloc((size_t)nb)); RC(sink.begin(nb));
+    const size_t lds = rec_wave_lds<T>(K) * rec::WAVES;
+    HIPCHK(hipFuncSetAttribute((const void*)k_rec_score<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    std::vector<int32_t> seq;
+    for (int64_t b0 = 0; b0 < n; b0 += nb) {
+        const int64_t m = std::min(nb, n - b0);
+        const int32_t* hu = h_users ? h_users + b0 : nullptr;
+        if (!hu) { seq.resize((size_t)m); for (int64_t i = 0; i < m; ++i) seq[(size_t)i] = (int32_t)(b0 + i); hu = seq.data(); }
+        HIPCHK(hipMemcpyAsync(du.p, hu, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        int per, nsp;
+        geom.batch(m, &per, &nsp);
+        {
+            ProfScope ps(v.prof, "recommend/score", st);
+            hipLaunchKernelGGL((k_rec_score<T>), dim3((unsigned)cdiv(m, users_per_wg), (unsigned)nsp), dim3(rec::WAVES * 64), lds, st, serve_U<T>(v),
+                               serve_V<T>(v), v.r, v.ld, (int)v.d2, du.p, m, v.xptr(), v.xitem(), K, per, ls.p, li.p, ln.p, select);
+            HIPCHK(hipGetLastError());
+        }
+        RC(sink.batch(b0, m, (const T*)ls.p, (const int32_t*)li.p, (const int32_t*)ln.p, nsp));
+        HIPCHK(hipStreamSynchronize(st));                  // (the next batch's users overwrite du / seq)
+    }
+    return PCR_OK;
+}
+
+// rec_run's sink for pcr_recommend: merged lists to the host arrays items / scores (n x K)
+template <typename T>
+struct RecCopy {
+    const ServeView& v;
+    int K;
+    int32_t* items;
+    double* scores;
+    DBuf<int32_t> oi;
+    DBuf<double> os;
+    int begin(int64_t nb) { RC(oi.alloc((size_t)nb * K)); RC(os.alloc((size_t)nb * K)); return PCR_OK; }
+    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp) {
+        {
+            ProfScope ps(v.prof, "recommend/merge", v.st);
+            hipLaunchKernelGGL((k_rec_merge<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), 0, v.st, ls, li, ln, nsp, m, K, oi.p, os.p);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(items + b0 * K, oi.p, (size_t)m * K * sizeof(int32_t), hipMemcpyDeviceToHost, v.st));
+        HIPCHK(hipMemcpyAsync(scores + b0 * K, os.p, (size_t)m * K * sizeof(double), hipMemcpyDeviceToHost, v.st));
+        return PCR_OK;
+    }
+};
+
+static int no_more() { return PCR_OK; }
+// The end of an evaluation: the fixed-order sums over the n per-user rows met[n][ncut][6] into sums[ncut * 8 + 1] ([ncut][8], then the
+// count: k_topn_sum1 / k_topn_fin's two stages, one block row per cutoff; timed in v.prof's `slot`), summed across the ranks and read
+// back into hs once v.wait() has synchronised.  A caller with more to finish (div_run's exposure) launches it from in_slot(), in
+// the slot's scope, and exchanges it and queues its read-backs in before_wait().
+template <class InSlot = int (*)(), class BeforeWait = int (*)()>
+static int met_sums(const ServeView& v, const char* slot, const double* met, int64_t n, int ncut, DBuf<double>& part, double* sums, double* hs,
+                    InSlot&& in_slot = no_more, BeforeWait&& before_wait = no_more) {
+    {
+        ProfScope ps(v.prof, slot, v.st);
+        const int nb = (int)std::min<int64_t>(512, std::max<int64_t>(1, cdiv(n, 2048)));
+        const int per = cdiv(std::max<int64_t>(n, 1), nb);
+        if (part.n < (size_t)nb * ncut * 8) RC(part.alloc((size_t)nb * ncut * 8));
+        hipLaunchKernelGGL(k_topn_sum1, dim3(nb, ncut), dim3(PCR_EW_BLOCK), 0, v.st, met, n, ncut, per, part.p);
+        hipLaunchKernelGGL(k_topn_fin, dim3(ncut), dim3(PCR_EW_BLOCK), 0, v.st, (const double*)part.p, nb, n, sums);
+        RC(in_slot());
+        HIPCHK(hipGetLastError());
+    }
+    RC(v.sum(sums, (size_t)ncut * 8 + 1));
+    RC(before_wait());
+    HIPCHK(hipMemcpyAsync(hs, sums, ((size_t)ncut * 8 + 1) * sizeof(double), hipMemcpyDeviceToHost, v.st));
+    return v.wait();
+}
+
+// Top-N evaluation's device tables (PcrTopnRel of pcr_host.h, uploaded once per (threshold, cutoffs)) and its outputs: the
+// per-user metric rows met[n][ncut][6] of the counted users and the reduced sums [ncut][8] + the count (k_topn_fin)
+struct TopnDev {
+    PcrTopnRel rel;
+    int ncut = 0;
+    int cut[PCR_TOPN_MAX_CUTOFFS] = {};
+    double threshold = 0.0;
+    bool valid = false;
+    DBuf<int64_t> rptr;
+    DBuf<int32_t> ritem;
+    DBuf<double> rgain, idcg, disc, met, part, sums;
+    bool same(int nc, const int* cuts, double thr) const {
+        if (!valid || nc != ncut || !(thr == threshold)) return false;
+        for (int c = 0; c < nc; ++c) if (cuts[c] != cut[c]) return false;
+        return true;
+    }
+    // the relevance tables of rows [0, rows) of the test CSR, to the device
+    int build(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, int nc, const int* cuts, double thr) {
+        valid = false;
+        pcr_topn_relevance(rows, tptr, titem, tval, thr, nc, cuts, rel);
+        ncut = nc; threshold = thr;
+        fill_cuts(cut, nc, cuts);
+        RC(rptr.upload(rel.rptr, nullptr)); RC(ritem.upload(rel.ritem, nullptr)); RC(rgain.upload(rel.rgain, nullptr));
+        RC(idcg.upload(rel.idcg, nullptr)); RC(disc.upload(rel.disc, nullptr));
+        RC(met.alloc(rel.users.size() * (size_t)ncut * 6)); RC(sums.alloc((size_t)ncut * 8 + 1));
+        valid = true;
+        return PCR_OK;
+    }
+    // The end of an evaluation, after rec_run: met_sums over the counted users ("recommend/metrics") into stats; with per_user,
+    // per_user[rows][ncut][6]: NaN, then the counted users' rows
+    int finish(const ServeView& v, pcr_topn_stats* stats, double* per_user) {
+        std::vector<double> hs((size_t)ncut * 8 + 1);
+        RC(met_sums(v, "recommend/metrics", met.p, (int64_t)rel.users.size(), ncut, part, sums.p, hs.data()));
+        pcr_topn_stats_from(hs.data(), ncut, cut, stats);
+        if (!per_user) return PCR_OK;
+        const size_t w = (size_t)ncut * 6;
+        std::vector<double> h(rel.users.size() * w);
+        if (!h.empty()) HIPCHK(hipMemcpyAsync(h.data(), met.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, v.st));
+        HIPCHK(hipStreamSynchronize(v.st));
+        std::fill(per_user, per_user + (size_t)v.rows * w, (double)NAN);
+        for (size_t i = 0; i < rel.users.size(); ++i) std::copy(h.begin() + i * w, h.begin() + (i + 1) * w, per_user + (size_t)rel.users[i] * w);
+        return PCR_OK;
+    }
+};
+
+// rec_run's sink for the top-N evaluation: merge + metrics (k_rec_merge_topn) into d.met at the batch's rows
+template <typename T>
+struct RecTopn {
+    const ServeView& v;
+    int K;
+    TopnDev& d;
+    int begin(int64_t) { return PCR_OK; }
+    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp) {
+        TopnArgs ta;
+        ta.rptr = d.rptr.p + b0; ta.ritem = d.ritem.p; ta.rgain = d.rgain.p; ta.idcg = d.idcg.p + (size_t)b0 * d.ncut * 2;
+        ta.disc = d.disc.p; ta.out = d.met.p + (size_t)b0 * d.ncut * 6; ta.ncut = d.ncut;
+        fill_cuts(ta.cut, d.ncut, d.cut);
+        ProfScope ps(v.prof, "recommend/metrics", v.st);
+        hipLaunchKernelGGL((k_rec_merge_topn<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), (size_t)4 * K * sizeof(int32_t), v.st, ls, li, ln, nsp, m, K, ta);
+        HIPCHK(hipGetLastError());
+        return PCR_OK;
+    }
+};
+
+// Beyond-accuracy metrics (pcr_evaluate_diversity, pcr_topk.h): the per-item tables and the outputs of one call -- the exposure
+// counters [ncut][d2] (they live across rec_run's user batches and are zeroed once per call), the per-user rows met[n][ncut][6]
+// in the column order k_topn_sum1 reduces, the reduced sums [ncut][8] + the count
+struct DivDev {
+    int ncut = 0;
+    int cut[PCR_TOPN_MAX_CUTOFFS] = {};
+    DBuf<double> inv, q, met, part, sums, expod;
+    DBuf<unsigned long long> expo;
+    const double* info = nullptr;
+};
+
+// rec_run's sink for the beyond-accuracy metrics: merge + exposure, novelty and ILD (k_rec_merge_div) into d.expo and d.met
+template <typename T>
+struct RecDiversity {
+    const ServeView& v;
+    int K;
+    DivDev& d;
+    int begin(int64_t) { return PCR_OK; }
+    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp) {
+        DivArgs da;
+        da.inv = d.inv.p; da.q = d.q.p; da.info = d.info; da.expo = d.expo.p; da.out = d.met.p + (size_t)b0 * d.ncut * 6;
+        da.d2 = v.d2; da.ncut = d.ncut;
+        fill_cuts(da.cut, d.ncut, d.cut);
+        ProfScope ps(v.prof, "recommend/diversity", v.st);
+        hipLaunchKernelGGL((k_rec_merge_div<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), (size_t)4 * K * sizeof(int32_t), v.st, ls, li, ln, nsp, m, K,
+                           serve_V<T>(v), v.r, v.ld, da);
+        HIPCHK(hipGetLastError());
+        return PCR_OK;
+    }
+};
+
+// info[] of v's training ratings item[0, nnz) on the device (NULL: pop = 0) into `info`: the counts by integer adds, summed
+// across the ranks, the logarithms on the host (pcr_diversity_info), like the top-N discount table
+static int div_info_build(const ServeView& v, DBuf<double>& info) {
+    hipStream_t st = v.st;
+    const int64_t d2 = v.d2;
+    DBuf<unsigned long long> cnt;
+    DBuf<double> pop;
+    RC(cnt.alloc((size_t)d2)); RC(pop.alloc((size_t)d2));
+    HIPCHK(hipMemsetAsync(cnt.p, 0, (size_t)d2 * sizeof(unsigned long long), st));
+    if (v.item && v.nnz > 0)
+        hipLaunchKernelGGL(k_div_pop, dim3((unsigned)std::min<int64_t>(4096, cdiv(v.nnz, 256))), dim3(256), 0, st, v.item, v.nnz, cnt.p);
+    hipLaunchKernelGGL(k_div_pop_f64, dim3((unsigned)cdiv(d2, 256)), dim3(256), 0, st, (const unsigned long long*)cnt.p, d2, pop.p);
+    HIPCHK(hipGetLastError());
+    RC(v.sum(pop.p, (size_t)d2));
+    std::vector<double> h((size_t)d2), hi((size_t)d2);
+    HIPCHK(hipMemcpyAsync(h.data(), pop.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    RC(v.wait());
+    pcr_diversity_info(v.d1, h.data(), d2, hi.data());
+    RC(info.upload(hi, st));
+    return PCR_OK;
+}
+
+// The beyond-accuracy evaluation of the n users h_users (rows of U and of the exclusion CSR, as rec_run; NULL: rows 0..n-1)
+// with the self-information table info: the row norms, the sweep with RecDiversity, the fixed-order sums over the users
+// (met_sums, unchanged) and the cumulative exposure; sums and exposure are summed across the ranks and read back once
+// v.wait() has synchronised the stream.  "recommend/diversity" times everything but the score kernel.
+template <typename T>
+static int div_run(const ServeView& v, const double* info, int64_t n, const int32_t* h_users, int ncut, const int* cuts,
+                   pcr_diversity_stats* stats, double* per_user, int64_t* exposure) {
+    hipStream_t st = v.st;
+    const int64_t d2 = v.d2;
+    DivDev D;
+    D.ncut = ncut; D.info = info;
+    fill_cuts(D.cut, ncut, cuts);
+    const int K = cuts[ncut - 1];
+    RC(D.inv.alloc((size_t)d2)); RC(D.q.alloc((size_t)d2)); RC(D.expo.alloc((size_t)ncut * d2)); RC(D.expod.alloc((size_t)ncut * d2));
+    RC(D.met.alloc((size_t)n * ncut * 6)); RC(D.sums.alloc((size_t)ncut * 8 + 1));
+    {
+        ProfScope ps(v.prof, "recommend/diversity", st);
+        HIPCHK(hipMemsetAsync(D.expo.p, 0, (size_t)ncut * d2 * sizeof(unsigned long long), st));
+        hipLaunchKernelGGL((k_div_prepare<T>), dim3((unsigned)cdiv(d2, 4)), dim3(256), 0, st, serve_V<T>(v), v.r, v.ld, d2, D.inv.p, D.q.p);
+        HIPCHK(hipGetLastError());
+    }
+    RC(rec_run<T>(v, n, h_users, K, 1, RecDiversity<T>{v, K, D}));
+    std::vector<double> hs((size_t)ncut * 8 + 1), he((size_t)ncut * d2), hm;
+    RC(met_sums(v, "recommend/diversity", D.met.p, n, ncut, D.part, D.sums.p, hs.data(),
+                [&]() -> int {   // (the exposure counters as doubles, in the same slot)
+                    hipLaunchKernelGGL(k_div_expo_finish, dim3((unsigned)cdiv(d2, 256)), dim3(256), 0, st, (const unsigned long long*)D.expo.p, d2, ncut, D.expod.p);
+                    return PCR_OK;
+                },
+                [&]() -> int {
+                    RC(v.sum(D.expod.p, (size_t)ncut * d2));
+                    HIPCHK(hipMemcpyAsync(he.data(), D.expod.p, he.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+                    if (per_user && n > 0) {
+                        hm.resize((size_t)n * ncut * 6);
+                        HIPCHK(hipMemcpyAsync(hm.data(), D.met.p, hm.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+                    }
+                    return PCR_OK;
+                }));
+    RC(pcr_diversity_stats_from(hs.data(), ncut, cuts, he.data(), d2, stats, exposure));
+    for (size_t i = 0; i < hm.size() / 6; ++i) {           // met: len, novelty (0 when len = 0), -, -, -, ild
+        const double* m = hm.data() + i * 6;
+        double* o = per_user + i * PCR_DIVERSITY_FIELDS;
+        o[0] = m[0]; o[1] = m[0] > 0.0 ? m[1] : (double)NAN; o[2] = m[5];
+    }
+    return PCR_OK;
+}
+
+// MMR re-ranking (pcr_recommend_diverse, pcr_topk.h): the form and the workgroup shape of k_rec_merge_mmr for a pool of K rows
+// of ld values.  The streaming form is the default: it was the faster one at every shape measured.
+// pcr_tune("rerank_lds", "1") takes the LDS form, which stages the pool's rows, whenever one wave's image fits a workgroup's
+// 160 KiB.  waves = users per workgroup (4, 2 or 1, as many as fit).
+static const size_t MMR_LDS_CU = (size_t)160 * 1024;
+struct MmrShape { int form = 0, waves = 0; size_t lds = 0; };
+template <typename T>
+static MmrShape mmr_shape(int K, int ld, int knob) {
+    MmrShape s;
+    s.form = (knob > 0 && mmr_wave_lds<T>(K, ld, 1) <= MMR_LDS_CU) ? 1 : 0;
+    const size_t per = mmr_wave_lds<T>(K, ld, s.form);
+    for (int w = 4; w >= 1; w >>= 1) if ((size_t)w * per <= MMR_LDS_CU) { s.waves = w; break; }
+    s.lds = (size_t)s.waves * per;
+    return s;
+}
+
+// rec_run's sink for the re-ranking: merge + greedy selection (k_rec_merge_mmr) of topk from the pool of K, to the host arrays
+// items / scores (n x topk)
+template <typename T>
+struct RecRerank {
+    const ServeView& v;
+    int K, topk;
+    double theta;
+    const double* inv;
+    MmrShape shape;
+    int32_t* items;
+    double* scores;
+    DBuf<int32_t> oi;
+    DBuf<double> os;
+    int begin(int64_t nb) { RC(oi.alloc((size_t)nb * topk)); RC(os.alloc((size_t)nb * topk)); return PCR_OK; }
+    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp) {
+        hipStream_t st = v.st; const T* V = serve_V<T>(v);
+        const int r = v.r, ld = v.ld;
+        MmrArgs ma;
+        ma.inv = inv; ma.out_i = oi.p; ma.out_s = os.p; ma.topk = topk; ma.theta = theta;
+        {
+            ProfScope ps(v.prof, "recommend/rerank", st);
+            const dim3 grid((unsigned)cdiv(m, shape.waves)), block(64 * shape.waves);
+            if (shape.form) hipLaunchKernelGGL((k_rec_merge_mmr<T, 1>), grid, block, shape.lds, st, ls, li, ln, nsp, m, K, V, r, ld, ma);
+            else hipLaunchKernelGGL((k_rec_merge_mmr<T, 0>), grid, block, shape.lds, st, ls, li, ln, nsp, m, K, V, r, ld, ma);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(items + b0 * topk, oi.p, (size_t)m * topk * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(scores + b0 * topk, os.p, (size_t)m * topk * sizeof(double), hipMemcpyDeviceToHost, st));
+        return PCR_OK;
+    }
+};
+
+// The re-ranked lists of the n users h_users (rows of U and of the exclusion CSR, as rec_run; NULL: rows 0..n-1): the row norms
+// (k_div_prepare, as the ILD's), then the sweep with K = pool and RecRerank.  "recommend/rerank" times everything but the
+// score kernel.  pcr_tune("rerank_lds") is read at every call.  k_div_prepare is reused as it is, so its second table q[d2] (the
+// ILD's |v^_j|^2) is allocated and written here too although the re-ranking never reads it: one d2-sized buffer per call.
+template <typename T>
+static int rerank_run(const ServeView& v, int64_t n, const int32_t* h_users, int topk, int pool, double theta, int32_t* items, double* scores) {
+    if (n <= 0) return PCR_OK;
+    const MmrShape shape = mmr_shape<T>(pool, v.ld, pcr_tune_int("rerank_lds", 0));
+    if (shape.waves < 1) { pcr_set_error("pcr_recommend_diverse: rank " + std::to_string(v.r) + " is too large for the re-ranking kernel's LDS"); return PCR_ERR_UNSUPPORTED; }
+    DBuf<double> inv, q;
+    RC(inv.alloc((size_t)v.d2)); RC(q.alloc((size_t)v.d2));
+    if (shape.form) HIPCHK(hipFuncSetAttribute((const void*)k_rec_merge_mmr<T, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds));
+    else HIPCHK(hipFuncSetAttribute((const void*)k_rec_merge_mmr<T, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds));
+    {
+        ProfScope ps(v.prof, "recommend/rerank", v.st);
+        hipLaunchKernelGGL((k_div_prepare<T>), dim3((unsigned)cdiv(v.d2, 4)), dim3(256), 0, v.st, serve_V<T>(v), v.r, v.ld, v.d2, inv.p, q.p);
+        HIPCHK(hipGetLastError());
+    }
+    return rec_run<T>(v, n, h_users, pool, 1, RecRerank<T>{v, pool, topk, theta, inv.p, shape, items, scores});
+}
+
+// Exact rank metrics (pcr_evaluate_ranks, pcr_topk.h): the relevance table of a threshold on the device (PcrTopnRel's users,
+// rptr and ritem; uploaded once per threshold) and the outputs: rrank[nrel] the ranks of ritem entry for entry, met[n][6]
+// k_rank_finish's rows, the reduced sums [8] + the count
+struct RankDev {
+    PcrTopnRel rel;
+    double threshold = 0.0;
+    bool valid = false;
+    DBuf<int64_t> rptr, rrank;
+    DBuf<int32_t> ritem, rslot, users;
+    DBuf<double> met, part, sums;
+    bool same(double thr) const { return valid && thr == threshold; }
+    int build(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, double thr) {
+        valid = false;
+        const int one = 1;
+        pcr_topn_relevance(rows, tptr, titem, tval, thr, 1, &one, rel);
+        threshold = thr;
+        RC(rptr.upload(rel.rptr, nullptr)); RC(ritem.upload(rel.ritem, nullptr)); RC(users.upload(rel.users, nullptr));
+        RC(rslot.alloc(rel.ritem.size())); RC(rrank.alloc(rel.ritem.size()));
+        RC(met.alloc(rel.users.size() * 6)); RC(sums.alloc(9));
+        valid = true;
+        return PCR_OK;
+    }
+    // The end of an evaluation, after rank_run: met_sums with one "cutoff" ("ranks/finish"; the same two kernels sum met's
+    // columns), then per_user[rows][PCR_RANK_FIELDS] and ranks[] of v's test CSR (the rows of this table's build)
+    int finish(const ServeView& v, pcr_rank_stats* stats, double* per_user, int64_t* ranks) {
+        hipStream_t st = v.st;
+        const int64_t n = (int64_t)rel.users.size();
+        double hs[9];
+        RC(met_sums(v, "ranks/finish", met.p, n, 1, part, sums.p, hs));
+        pcr_rank_stats_from(hs, stats);
+        if (per_user) {
+            std::vector<double> h((size_t)n * 6);
+            if (n) HIPCHK(hipMemcpyAsync(h.data(), met.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            std::fill(per_user, per_user + (size_t)v.rows * PCR_RANK_FIELDS, (double)NAN);
+            for (int64_t i = 0; i < n; ++i) {           // met: |R_u|, rr, mean_rank, mpr, first_rank, auc
+                const double* m = h.data() + (size_t)i * 6;
+                double* o = per_user + (size_t)rel.users[(size_t)i] * PCR_RANK_FIELDS;
+                o[0] = m[4]; o[1] = m[1]; o[2] = m[2]; o[3] = m[5]; o[4] = m[3];
+            }
+        }
+        if (ranks) {
+            std::vector<int64_t> h(rel.ritem.size());
+            if (!h.empty()) HIPCHK(hipMemcpyAsync(h.data(), rrank.p, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            pcr_rank_scatter(v.rows, v.tptr, v.titem, v.tval, threshold, rel, h.data(), ranks);
+        }
+        return PCR_OK;
+    }
+};
+
+// The rank metrics' sweep for the counted users of d (rows of U and of the exclusion CSR, as rec_run): the relevant items'
+// scores and their sort once for all users ("ranks/relscore"), then per user batch (RecGeom, the scratch being the splits'
+// histograms: |R_u| + 1 counters per user) the counting sweep ("ranks/count") and the scan ("ranks/finish") into d.rrank / d.met.
+// pcr_tune("ranks_batch_users") is read at every call.
+template <typename T>
+static int rank_run(const ServeView& v, RankDev& d) {
+    hipStream_t st = v.st; const T *U = serve_U<T>(v), *V = serve_V<T>(v);
+    const int r = v.r, ld = v.ld;
+    const int64_t d2 = v.d2, n = (int64_t)d.rel.users.size(), nrel = (int64_t)d.rel.ritem.size();
+    if (n <= 0) return PCR_OK;
+    DBuf<T> us, rs;
+    DBuf<int32_t> ri, hist;
+    RC(us.alloc((size_t)nrel)); RC(rs.alloc((size_t)nrel)); RC(ri.alloc((size_t)nrel));
+    {
+        ProfScope ps(v.prof, "ranks/relscore", st);
+        hipLaunchKernelGGL((k_rank_relscore<T>), dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, U, V, r, ld, (const int32_t*)d.users.p, n,
+                           (const int64_t*)d.rptr.p, (const int32_t*)d.ritem.p, us.p);
+        hipLaunchKernelGGL((k_rank_sort<T>), dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, n, (const int64_t*)d.rptr.p, (const int32_t*)d.ritem.p,
+                           (const T*)us.p, rs.p, ri.p, d.rslot.p);
+        HIPCHK(hipGetLastError());
+    }
+    RecGeom geom(n, d2, sizeof(int32_t) * (size_t)((nrel + n + n - 1) / n));
+    const int64_t cap = pcr_tune_int("ranks_batch_users", 0);
+    if (cap > 0) {
+        geom.nb = std::min(geom.nb, (cap + RecGeom::users_per_wg - 1) / RecGeom::users_per_wg * RecGeom::users_per_wg);
+        geom.smax = geom.splits_for(std::min(geom.nb, n));
+    }
+    const std::vector<int64_t>& rp = d.rel.rptr;
+    auto buckets = [&](int64_t b0, int64_t m) { return rp[(size_t)(b0 + m)] - rp[(size_t)b0] + m; };
+    size_t hmax = 0;
+    for (int64_t b0 = 0; b0 < n; b0 += geom.nb) hmax = std::max(hmax, (size_t)buckets(b0, std::min(geom.nb, n - b0)));
+    RC(hist.alloc(hmax * (size_t)geom.smax));
+    const size_t lds = rank_wave_lds<T>() * rec::WAVES;
+    for (int64_t b0 = 0; b0 < n; b0 += geom.nb) {
+        const int64_t m = std::min(geom.nb, n - b0), hsplit = buckets(b0, m);
+        int per, nsp;
+        geom.batch(m, &per, &nsp);
+        {
+            ProfScope ps(v.prof, "ranks/count", st);
+            HIPCHK(hipMemsetAsync(hist.p, 0, (size_t)nsp * (size_t)hsplit * sizeof(int32_t), st));
+            hipLaunchKernelGGL((k_rank_count<T>), dim3((unsigned)cdiv(m, RecGeom::users_per_wg), (unsigned)nsp), dim3(rec::WAVES * 64), lds, st, U, V,
+                               r, ld, (int)d2, (const int32_t*)d.users.p + b0, m, v.xptr(), v.xitem(), per, (const int64_t*)d.rptr.p + b0, (const T*)rs.p,
+                               (const int32_t*)ri.p, hist.p, hsplit);
+            HIPCHK(hipGetLastError());
+        }
+        ProfScope ps(v.prof, "ranks/finish", st);
+        hipLaunchKernelGGL(k_rank_finish, dim3((unsigned)cdiv(m, 4)), dim3(256), 0, st, (const int32_t*)hist.p, hsplit, nsp, m,
+                           (const int64_t*)d.rptr.p + b0, (const int32_t*)d.rslot.p, d.rrank.p, d.met.p + (size_t)b0 * 6);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(st));                      // (us / rs / ri / hist are freed on return)
+    return PCR_OK;
+}
+
+// ---- the five entries over a view, for a solver and for a model alike
+static int serve_recommend(const ServeView& v, int64_t n, const int32_t* rows, int K, int32_t* items, double* scores) {
+    return by_precision(v, [&](auto zero) -> int {
+        using T = decltype(zero);
+        return rec_run<T>(v, n, rows, K, v.select, RecCopy<T>{v, K, items, scores});
+    });
+}
+// MMR re-ranked lists: per user, nothing is exchanged
+static int serve_recommend_diverse(const ServeView& v, int64_t n, const int32_t* rows, int topk, int pool, double theta, int32_t* items,
+                                   double* scores) {
+    return by_precision(v, [&](auto zero) -> int { return rerank_run<decltype(zero)>(v, n, rows, topk, pool, theta, items, scores); });
+}
+// full-catalogue top-N evaluation of v's rows against their test ratings; the relevance tables are built on the first call for a
+// (threshold, cutoffs) and kept in D
+static int serve_topn(const ServeView& v, TopnDev& D, int ncut, const int* cuts, double thr, pcr_topn_stats* stats, double* per_user) {
+    if (!D.same(ncut, cuts, thr)) RC(D.build(v.rows, v.tptr, v.titem, v.tval, ncut, cuts, thr));
+    const int K = cuts[ncut - 1];
+    RC(by_precision(v, [&](auto zero) -> int {
+        using T = decltype(zero);
+        return rec_run<T>(v, (int64_t)D.rel.users.size(), D.rel.users.data(), K, 1, RecTopn<T>{v, K, D});
+    }));
+    return D.finish(v, stats, per_user);
+}
+// exact rank metrics of v's rows against their test ratings; the relevance table is built on the first call for a threshold and
+// kept in D
+static int serve_ranks(const ServeView& v, RankDev& D, double thr, pcr_rank_stats* stats, double* per_user, int64_t* ranks) {
+    if (!D.same(thr)) RC(D.build(v.rows, v.tptr, v.titem, v.tval, thr));
+    RC(by_precision(v, [&](auto zero) -> int { return rank_run<decltype(zero)>(v, D); }));
+    return D.finish(v, stats, per_user, ranks);
+}
+// beyond-accuracy metrics of v's rows; the self-information table comes from the training ratings (summed across the ranks with
+// a communicator) and is kept in info: the ratings never change, the exchange mode can (info_mode 0: not built, 1: from this
+// shard's ratings alone, 2: all-reduced)
+static int serve_diversity(const ServeView& v, DBuf<double>& info, int& info_mode, int64_t n, const int32_t* rows, int ncut, const int* cuts,
+                           pcr_diversity_stats* stats, double* per_user, int64_t* exposure) {
+    // (the peer-to-peer communicator's fp64 exchange is its 64-double scalar slot: the d2-sized tables do not fit it)
+    if (v.exchange == SERVE_P2P) { pcr_set_error("pcr_evaluate_diversity: not available on a peer-to-peer communicator (use RCCL, or local-only shards and pcr_exposure_stats)"); return PCR_ERR_UNSUPPORTED; }
+    const int mode = v.exchange == SERVE_LOCAL ? 1 : 2;
+    if (info_mode != mode) {
+        info_mode = 0;
+        RC(div_info_build(v, info));
+        info_mode = mode;
+    }
+    return by_precision(v, [&](auto zero) -> int { return div_run<decltype(zero)>(v, info.p, n, rows, ncut, cuts, stats, per_user, exposure); });
+}
+
+// what a solver keeps between calls of the serving layer
+struct ServeState {
+    TopnDev topn;
+    RankDev rankd;
+    DBuf<double> div_info;        // info[d2] of pcr_evaluate_diversity
+    int div_info_mode = 0;
+};
+pcr_solver::pcr_solver() : serve(new ServeState) {}
+pcr_solver::~pcr_solver() {}
+
+// s's view for one call: the launches are timed in s's profiler (that of a CCDR1 solver, not of the Solver<T> it holds)
+static ServeView solver_view(pcr_solver* s, int flags) {
+    ServeView v;
+    s->serve_view(&v); v.exclude = (flags & PCR_REC_EXCLUDE_TRAIN) != 0;
+    return v;
+}
+
+// A model in host memory on the device for one call: the exclusion CSR (item-ascending rows: a CSR that is not gets a sorted
+// copy, for the kernel's cursor) and both host fp64 factors in the requested type, rows padded to ld: U then V in one buffer.
+// open() fills the view: the default stream, nothing profiled, nothing exchanged.
+struct ModelDev {
+    DBuf<int64_t> dx;
+    DBuf<int32_t> di;
+    DBuf<char> F;
+    int open(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item, bool sorted,
+             int dtype, ServeView* v) {
+        if (index) {
+            std::vector<int32_t> sitem;
+            const int64_t nnz = index[d1];
+            if (!sorted) {
+                sitem.assign(item, item + nnz);
+                pcr_parallel_ranges(d1, pcr_host_threads(), [&](int, int64_t lo, int64_t hi) {
+                    for (int64_t u = lo; u < hi; ++u) std::sort(sitem.begin() + index[u], sitem.begin() + index[u + 1]);
+                });
+            }
+            RC(dx.upload_n(index, (size_t)d1 + 1)); RC(di.upload_n(sorted ? item : sitem.data(), (size_t)nnz));
+        }
+        const int ld = ((int)k + 3) & ~3;
+        const size_t row = (size_t)ld * (dtype == PCR_F64 ? sizeof(double) : sizeof(float));
+        RC(F.alloc((size_t)(d1 + d2) * row));
+        char* dV = F.p + (size_t)d1 * row;
+        if (dtype == PCR_F64) RC(upload_rows<double>(v->st, (int)k, ld, {{U, d1, (double*)F.p}, {V, d2, (double*)dV}}));
+        else RC(upload_rows<float>(v->st, (int)k, ld, {{U, d1, (float*)F.p}, {V, d2, (float*)dV}}));
+        v->dtype = dtype; v->U = F.p; v->V = dV; v->r = (int)k; v->ld = ld; v->rows = v->d1 = d1; v->d2 = d2;
+        v->uptr = dx.p; v->item = di.p; v->nnz = index ? index[d1] : 0;
+        return PCR_OK;
+    }
+};
+
+static int model_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { pcr_set_error("no HIP device available"); return PCR_ERR_DEVICE; }
+    if (device < 0 || device >= ndev) { pcr_set_error("device ordinal out of range"); return PCR_ERR_ARG; }
+    HIPCHK(hipSetDevice(device));
+    return PCR_OK;
+}
+
+extern "C" {
+
+// users[n] (global ids, NULL: the whole shard) as rows of s's shard in loc (left empty for NULL); *n the count
+static int shard_rows(const char* who, const pcr_solver* s, int64_t* n, const int32_t* users, std::vector<int32_t>& loc) {
+    if (!users) { *n = s->n_users; return PCR_OK; }
+    loc.resize((size_t)*n);
+    for (int64_t i = 0; i < *n; ++i) {
+        const int64_t x = (int64_t)users[i] - s->first_user;
+        if (x < 0 || x >= s->n_users) {
+            pcr_set_error(std::string(who) + ": user " + std::to_string(users[i]) + " is not in this shard [" + std::to_string(s->first_user) + ", " +
+                          std::to_string(s->first_user + s->n_users) + ")");
+            return PCR_ERR_ARG;
+        }
+        loc[(size_t)i] = (int32_t)x;
+    }
+    return PCR_OK;
+}
+
+int pcr_evaluate_diversity(pcr_solver* s, int64_t n, const int32_t* users, int ncut, const int* cutoffs, int flags, pcr_diversity_stats* stats,
+                           double* per_user, int64_t* exposure) {
+    S_OR_ARG;
+    RC(pcr_cutoffs_check("pcr_evaluate_diversity", ncut, cutoffs));
+    if (!stats) { pcr_set_error("pcr_evaluate_diversity: null stats"); return PCR_ERR_ARG; }
+    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_evaluate_diversity: unknown flags"); return PCR_ERR_ARG; }
+    if (users && n < 0) { pcr_set_error("pcr_evaluate_diversity: bad argument"); return PCR_ERR_ARG; }
+    return abi_guard("pcr_evaluate_diversity", [&]() -> int {
+        std::vector<int32_t> loc;
+        RC(shard_rows("pcr_evaluate_diversity", s, &n, users, loc));
+        return serve_diversity(solver_view(s, flags), s->serve->div_info, s->serve->div_info_mode, n, users ? loc.data() : nullptr, ncut, cutoffs,
+                               stats, per_user, exposure);
+    });
+}
+
+int pcr_recommend(pcr_solver* s, int64_t n, const int32_t* users, int topk, int flags, int32_t* items, double* scores) {
+    S_OR_ARG;
+    if (topk < 1 || topk > PCR_RECOMMEND_MAX_K) { pcr_set_error("pcr_recommend: K = " + std::to_string(topk) + " outside [1, " + std::to_string(PCR_RECOMMEND_MAX_K) + "]"); return PCR_ERR_ARG; }
+    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_recommend: unknown flags"); return PCR_ERR_ARG; }
+    if (!users) n = s->n_users;
+    if (n < 0 || (n > 0 && (!items || !scores))) { pcr_set_error("pcr_recommend: bad argument"); return PCR_ERR_ARG; }
+    return abi_guard("pcr_recommend", [&]() -> int {
+        std::vector<int32_t> loc;
+        RC(shard_rows("pcr_recommend", s, &n, users, loc));
+        return serve_recommend(solver_view(s, flags), n, users ? loc.data() : nullptr, topk, items, scores);
+    });
+}
+
+int pcr_recommend_diverse(pcr_solver* s, int64_t n, const int32_t* users, int topk, int pool, double theta, int flags, int32_t* items,
+                          double* scores) {
+    S_OR_ARG;
+    RC(pcr_rerank_check("pcr_recommend_diverse", topk, pool, theta));
+    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_recommend_diverse: unknown flags"); return PCR_ERR_ARG; }
+    if (!users) n = s->n_users;
+    if (n < 0 || (n > 0 && (!items || !scores))) { pcr_set_error("pcr_recommend_diverse: bad argument"); return PCR_ERR_ARG; }
+    return abi_guard("pcr_recommend_diverse", [&]() -> int {
+        std::vector<int32_t> loc;
+        RC(shard_rows("pcr_recommend_diverse", s, &n, users, loc));
+        return serve_recommend_diverse(solver_view(s, flags), n, users ? loc.data() : nullptr, topk, pool, theta, items, scores);
+    });
+}
+
+int pcr_evaluate_topn(pcr_solver* s, int ncut, const int* cutoffs, double threshold, int flags, pcr_topn_stats* stats, double* per_user) {
+    S_OR_ARG;
+    RC(pcr_topn_check("pcr_evaluate_topn", ncut, cutoffs, threshold, stats));
+    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_evaluate_topn: unknown flags"); return PCR_ERR_ARG; }
+    return abi_guard("pcr_evaluate_topn", [&]() -> int { return serve_topn(solver_view(s, flags), s->serve->topn, ncut, cutoffs, threshold, stats, per_user); });
+}
+
+int pcr_evaluate_ranks(pcr_solver* s, double threshold, int flags, pcr_rank_stats* stats, double* per_user, int64_t* ranks) {
+    S_OR_ARG;
+    if (std::isnan(threshold)) { pcr_set_error("pcr_evaluate_ranks: threshold is NaN"); return PCR_ERR_ARG; }
+    if (!stats) { pcr_set_error("pcr_evaluate_ranks: null stats"); return PCR_ERR_ARG; }
+    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_evaluate_ranks: unknown flags"); return PCR_ERR_ARG; }
+    return abi_guard("pcr_evaluate_ranks", [&]() -> int { return serve_ranks(solver_view(s, flags), s->serve->rankd, threshold, stats, per_user, ranks); });
+}
+
+int pcr_recommend_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                        int64_t n, const int32_t* users, int topk, int dtype, int32_t* items, double* scores, int device) {
+    return abi_guard("pcr_recommend_model", [&]() -> int {
+    bool sorted = true;
+    RC(pcr_recommend_model_check(U, d1, V, d2, k, index, item, n, users, topk, dtype, items, scores, &sorted));
+    RC(model_device(device));
+    if (n == 0) return PCR_OK;
+    ServeView v;
+    v.select = pcr_tune_int("recommend_select", 1);
+    ModelDev M;
+    RC(M.open(U, d1, V, d2, k, index, item, sorted, dtype, &v));
+    return serve_recommend(v, n, users, topk, items, scores);
+    });
+}
+
+int pcr_evaluate_topn_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                            const int64_t* tindex, const int32_t* titem, const double* tval, int ncut, const int* cutoffs, double threshold,
+                            int dtype, pcr_topn_stats* stats, double* per_user, int device) {
+    return abi_guard("pcr_evaluate_topn_model", [&]() -> int {
+    bool sorted = true;
+    RC(pcr_evaluate_topn_model_check(U, d1, V, d2, k, index, item, tindex, titem, tval, ncut, cutoffs, threshold, dtype, stats, &sorted));
+    RC(model_device(device));
+    ServeView v;
+    v.tptr = tindex; v.titem = titem; v.tval = tval;
+    ModelDev M;
+    RC(M.open(U, d1, V, d2, k, index, item, sorted, dtype, &v));
+    TopnDev D;
+    return serve_topn(v, D, ncut, cutoffs, threshold, stats, per_user);
+    });
+}
+
+int pcr_evaluate_ranks_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                             const int64_t* tindex, const int32_t* titem, const double* tval, double threshold, int dtype,
+                             pcr_rank_stats* stats, double* per_user, int64_t* ranks, int device) {
+    return abi_guard("pcr_evaluate_ranks_model", [&]() -> int {
+    bool sorted = true;
+    RC(pcr_evaluate_ranks_model_check(U, d1, V, d2, k, index, item, tindex, titem, tval, threshold, dtype, stats, &sorted));
+    RC(model_device(device));
+    ServeView v;
+    v.tptr = tindex; v.titem = titem; v.tval = tval;
+    ModelDev M;
+    RC(M.open(U, d1, V, d2, k, index, item, sorted, dtype, &v));
+    RankDev D;
+    return serve_ranks(v, D, threshold, stats, per_user, ranks);
+    });
+}
+
+int pcr_evaluate_diversity_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                                 int64_t n, const int32_t* users, int ncut, const int* cutoffs, int dtype, pcr_diversity_stats* stats,
+                                 double* per_user, int64_t* exposure, int device) {
+    return abi_guard("pcr_evaluate_diversity_model", [&]() -> int {
+    bool sorted = true;
+    RC(pcr_evaluate_diversity_model_check(U, d1, V, d2, k, index, item, n, users, ncut, cutoffs, dtype, stats, &sorted));
+    RC(model_device(device));
+    ServeView v; ModelDev M;
+    RC(M.open(U, d1, V, d2, k, index, item, sorted, dtype, &v));
+    DBuf<double> info; int info_mode = 0;
+    return serve_diversity(v, info, info_mode, n, users, ncut, cutoffs, stats, per_user, exposure);
+    });
+}
+
+int pcr_recommend_diverse_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                                int64_t n, const int32_t* users, int topk, int pool, double theta, int dtype, int32_t* items, double* scores,
+                                int device) {
+    return abi_guard("pcr_recommend_diverse_model", [&]() -> int {
+    bool sorted = true;
+    RC(pcr_recommend_diverse_model_check(U, d1, V, d2, k, index, item, n, users, topk, pool, theta, dtype, items, scores, &sorted));
+    RC(model_device(device));
+    if (n == 0) return PCR_OK;
+    ServeView v; ModelDev M;
+    RC(M.open(U, d1, V, d2, k, index, item, sorted, dtype, &v));
+    return serve_recommend_diverse(v, n, users, topk, pool, theta, items, scores);
+    });
+}
+
+}  // extern "C"

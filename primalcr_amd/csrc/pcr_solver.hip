@@ -5,6 +5,8 @@
 // sharded across ranks (contiguous, nnz-balanced), V and the CG vectors are replicated, the
 // V-gradient and every Hessian-vector product are combined with an RCCL all-reduce.
 //
+// The serving layer (recommendation and its metrics) is pcr_serve.hip; it reads this unit's state through Solver<T>::serve_view.
+//
 // There is NO CPU compute path in this file: every [device] entry point fails with
 // PCR_ERR_DEVICE when HIP is unusable.
 #include <hip/hip_runtime.h>
@@ -15,28 +17,18 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <initializer_list>
-#include <map>
 #include <memory>
 #include <string>
-#include <string_view>
 #include <vector>
 
 #include "pcr_host.h"
+#include "pcr_dev.h"
 #include "pcr_kernels.h"
 #include "pcr_gram.h"
 #include "pcr_newton.h"
 #include "pcr_vblock.h"
 #include "pcr_p2p.h"
 
-#define HIPCHK(expr)                                                                           \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            pcr_set_error(std::string(#expr) + ": " + hipGetErrorString(e_) + " (" + __FILE__ + ":" + std::to_string(__LINE__) + ")"); \
-            return PCR_ERR_DEVICE;                                                             \
-        }                                                                                      \
-    } while (0)
 #define NCCLCHK(expr)                                                                          \
     do {                                                                                       \
         ncclResult_t e_ = (expr);                                                              \
@@ -45,598 +37,8 @@
             return PCR_ERR_COMM;                                                               \
         }                                                                                      \
     } while (0)
-#define RC(expr) do { int rc_ = (expr); if (rc_ != PCR_OK) return rc_; } while (0)
-
-static inline int host_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
-static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 #include "pcr_plan.h"
 #include "pcr_plan_dev.h"
-
-// device buffer with RAII
-template <typename X>
-struct DBuf {
-    X* p = nullptr;
-    size_t n = 0;
-    int alloc(size_t count) {
-        free();
-        n = count;
-        if (count == 0) count = 1;
-        HIPCHK(hipMalloc((void**)&p, count * sizeof(X)));
-        return PCR_OK;
-    }
-    int upload(const std::vector<X>& h, hipStream_t st) {
-        RC(alloc(h.size()));
-        (void)st;
-        if (!h.empty()) HIPCHK(hipMemcpy(p, h.data(), h.size() * sizeof(X), hipMemcpyHostToDevice));
-        return PCR_OK;
-    }
-    int upload_n(const X* h, size_t count) {
-        RC(alloc(count));
-        if (count) HIPCHK(hipMemcpy(p, h, count * sizeof(X), hipMemcpyHostToDevice));
-        return PCR_OK;
-    }
-    void free() { if (p) { (void)hipFree(p); p = nullptr; } n = 0; }
-    DBuf() = default;
-    DBuf(const DBuf&) = delete;
-    DBuf& operator=(const DBuf&) = delete;
-    DBuf(DBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
-    DBuf& operator=(DBuf&& o) noexcept { if (this != &o) { free(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
-    ~DBuf() { free(); }
-};
-
-// Factor matrices cross the boundary as the reference's fp64 row-major payload (mat_t), k values per row; the device keeps rows
-// padded to ld elements of T.  upload_rows converts each {host rows H, row count, device rows D} on the device (k_mat_in) in slabs
-// of at most 64 M values, staged straight from the caller's buffer through one device buffer sized for the longest matrix, and
-// synchronises st after every slab: no host-side staging copy, no serial conversion loop (48 M values at the Netflix shape).
-template <typename T>
-struct HostRows { const double* H; int64_t rows; T* D; };
-template <typename T>
-static int upload_rows(hipStream_t st, int k, int ld, std::initializer_list<HostRows<T>> mats) {
-    const int64_t slab_rows = std::max<int64_t>(1, ((int64_t)64 << 20) / k);
-    int64_t longest = 0;
-    for (const HostRows<T>& m : mats) longest = std::max(longest, m.rows);
-    DBuf<double> stage;
-    RC(stage.alloc((size_t)std::min(longest, slab_rows) * k));
-    for (const HostRows<T>& m : mats)
-        for (int64_t r0 = 0; r0 < m.rows; r0 += slab_rows) {
-            const int64_t nr = std::min(slab_rows, m.rows - r0);
-            HIPCHK(hipMemcpyAsync(stage.p, m.H + r0 * k, (size_t)nr * k * sizeof(double), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL((k_mat_in<T>), dim3((unsigned)std::min<int64_t>(1 << 16, cdiv(nr * ld, 256))), dim3(256), 0, st, stage.p, m.D + r0 * ld, nr, k, ld);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(st));
-        }
-    return PCR_OK;
-}
-
-// ------------------------------------------------------------------------------ profiling (pcr_profile_*)
-struct ProfSlot {
-    int64_t ratings = -1, users = -1;      // what one launch covers (-1: the whole shard)
-    int64_t seen = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-    double ms = 0.0;
-    int64_t n = 0;
-};
-// A solver's named timing slots and the HIP events behind them
-struct Profiler {
-    bool on = false;
-    int period = 1;                       // time every period-th launch of each slot
-    std::map<std::string, ProfSlot> slots;
-    std::vector<hipEvent_t> pool;         // timing events are recycled: creating one per launch costs more than the launch
-    ~Profiler() {
-        for (auto& kv : slots)
-            for (auto& pr : kv.second.pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-        for (hipEvent_t e : pool) (void)hipEventDestroy(e);
-    }
-    hipEvent_t get() {
-        if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
-        hipEvent_t e = nullptr;
-        (void)hipEventCreate(&e);
-        return e;
-    }
-    void prewarm(int n) {
-        while ((int)pool.size() < n) { hipEvent_t e = nullptr; if (hipEventCreate(&e) != hipSuccess) break; pool.push_back(e); }
-    }
-    // waits for the recorded pairs, adds their times to the slots and returns their events to the pool
-    void resolve() {
-        for (auto& kv : slots) {
-            for (auto& pr : kv.second.pending) {
-                float ms = 0.f;
-                (void)hipEventSynchronize(pr.second);
-                if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) kv.second.ms += ms;
-                pool.push_back(pr.first); pool.push_back(pr.second);
-            }
-            kv.second.pending.clear();
-        }
-    }
-};
-// One launch (or group of launches) of slot `name` on stream q, timed by an event pair when it is sampled.  p NULL: not profiled.
-struct ProfScope {
-    Profiler* p; ProfSlot* slot = nullptr; hipEvent_t a = nullptr, b = nullptr; hipStream_t q;
-    ProfScope(Profiler* p_, std::string_view name, hipStream_t q_, int64_t ratings = -1, int64_t users = -1) : p(p_), q(q_) {
-        if (!p || !p->on) return;
-        ProfSlot* sl = &p->slots[std::string(name)];
-        sl->ratings = ratings; sl->users = users;
-        // sampled: an event pair costs ~3 us of queue time.  Slots launched once per outer iteration (the U-step classes,
-        // the prepares, the fork..join walls) are sampled at least every 4th launch, so that a 20-step run still
-        // averages five of them; the per-CG-iteration kernels every period-th
-        const bool rare = name.compare(0, 5, "ustep") == 0 || name.compare(0, 5, "wall:") == 0 || name.compare(0, 7, "prepare") == 0;
-        const int period = rare ? std::min(p->period, 4) : p->period;
-        if ((sl->seen++ % period) != 0) return;
-        slot = sl;
-        a = p->get(); b = p->get();
-        (void)hipEventRecord(a, q);
-    }
-    ~ProfScope() {
-        if (!slot) return;
-        (void)hipEventRecord(b, q);
-        slot->pending.emplace_back(a, b);
-        slot->n += 1;
-    }
-};
-
-// Top-K recommendation (pcr_topk.h) for the n users h_users[0..n) -- rows of U and of the exclusion CSR xptr / xitem (NULL:
-// none), or rows 0..n-1 when h_users is NULL.  Users go in batches whose partial lists stay under REC_SCRATCH bytes; the item
-// range is split across workgroups until the grid holds about REC_TARGET_WG workgroups (ml1m's 6 040 users are 95 workgroups
-// of 64).  Each batch's partial lists go to the sink: sink.begin(nb) once with the largest batch, then sink.batch(b0, m, ...)
-// per batch, which merges them (RecCopy: into pcr_recommend's host arrays; RecTopn: into the top-N metrics).  The launches
-// are timed in prof's "recommend/..." slots (NULL: not profiled).  select = 0 only for tools/exp_recommend.py's GEMM-alone timing (lists come back empty).
-static const size_t REC_SCRATCH = (size_t)1 << 30;
-static const int REC_TARGET_WG = 1024, REC_MAX_SPLIT = 16, REC_MIN_SPLIT_ITEMS = 1024;
-// The user batches and item splits of a sweep over n users whose scratch takes per_user bytes per user and split (rec_run and
-// rank_run share this arithmetic): nb users per batch, at most smax splits
-struct RecGeom {
-    int64_t d2, nb = 0;
-    int smax = 1;
-    static constexpr int64_t users_per_wg = (int64_t)rec::WAVES * rec::UW;
-    int splits_for(int64_t users) const {
-        const int64_t wg = (users + users_per_wg - 1) / users_per_wg;
-        int64_t s = std::max<int64_t>(1, (REC_TARGET_WG + wg - 1) / wg);
-        s = std::min<int64_t>(s, std::max<int64_t>(1, d2 / REC_MIN_SPLIT_ITEMS));
-        return (int)std::min<int64_t>(s, REC_MAX_SPLIT);
-    }
-    RecGeom(int64_t n, int64_t d2_, size_t per_user) : d2(d2_) {
-        nb = std::min<int64_t>(n, std::max<int64_t>(users_per_wg, (int64_t)(REC_SCRATCH / (per_user * 2)) / users_per_wg * users_per_wg));
-        while (nb > users_per_wg && (size_t)nb * (size_t)splits_for(nb) * per_user > REC_SCRATCH) nb = std::max<int64_t>(users_per_wg, nb / 2);
-        smax = splits_for(std::min(nb, n));
-    }
-    // a batch of m users: the items per split (whole steps) and the splits launched
-    void batch(int64_t m, int* per, int* nsp) const {
-        const int ns = std::min(splits_for(m), smax);      // (a short last batch keeps the scratch of the first)
-        *per = (int)(((d2 + ns - 1) / ns + rec::TILE - 1) / rec::TILE * rec::TILE);
-        *nsp = (int)((d2 + *per - 1) / *per);
-    }
-};
-
-template <typename T, class Sink>
-static int rec_run(hipStream_t st, const T* U, const T* V, int r, int ld, int64_t d2, const int64_t* xptr, const int32_t* xitem,
-                   int64_t n, const int32_t* h_users, int K, int select, Profiler* prof, Sink&& sink) {
-    if (n <= 0) return PCR_OK;
-    const size_t per_user = (size_t)K * (sizeof(T) + sizeof(int32_t)) + sizeof(int32_t);
-    const RecGeom geom(n, d2, per_user);
-    const int64_t users_per_wg = RecGeom::users_per_wg, nb = geom.nb;
-    const int smax = geom.smax;
-    DBuf<T> ls; DBuf<int32_t> li, ln, du;
-    RC(ls.alloc((size_t)nb * smax * K)); RC(li.alloc((size_t)nb * smax * K)); RC(ln.alloc((size_t)nb * smax));
-    RC(du.alloc((size_t)nb)); RC(sink.begin(nb));
-    const size_t lds = rec_wave_lds<T>(K) * rec::WAVES;
-    HIPCHK(hipFuncSetAttribute((const void*)k_rec_score<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    std::vector<int32_t> seq;
-    for (int64_t b0 = 0; b0 < n; b0 += nb) {
-        const int64_t m = std::min(nb, n - b0);
-        const int32_t* hu = h_users ? h_users + b0 : nullptr;
-        if (!hu) { seq.resize((size_t)m); for (int64_t i = 0; i < m; ++i) seq[(size_t)i] = (int32_t)(b0 + i); hu = seq.data(); }
-        HIPCHK(hipMemcpyAsync(du.p, hu, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        int per, nsp;
-        geom.batch(m, &per, &nsp);
-        {
-            ProfScope ps(prof, "recommend/score", st);
-            hipLaunchKernelGGL((k_rec_score<T>), dim3((unsigned)cdiv(m, users_per_wg), (unsigned)nsp), dim3(rec::WAVES * 64), lds, st, U, V, r, ld,
-                               (int)d2, du.p, m, xptr, xitem, K, per, ls.p, li.p, ln.p, select);
-            HIPCHK(hipGetLastError());
-        }
-        RC(sink.batch(b0, m, (const T*)ls.p, (const int32_t*)li.p, (const int32_t*)ln.p, nsp, prof));
-        HIPCHK(hipStreamSynchronize(st));                  // (the next batch's users overwrite du / seq)
-    }
-    return PCR_OK;
-}
-
-// rec_run's sink for pcr_recommend: merged lists to the host arrays items / scores (n x K)
-template <typename T>
-struct RecCopy {
-    hipStream_t st;
-    int K;
-    int32_t* items;
-    double* scores;
-    DBuf<int32_t> oi;
-    DBuf<double> os;
-    RecCopy(hipStream_t st_, int K_, int32_t* items_, double* scores_) : st(st_), K(K_), items(items_), scores(scores_) {}
-    int begin(int64_t nb) { RC(oi.alloc((size_t)nb * K)); RC(os.alloc((size_t)nb * K)); return PCR_OK; }
-    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp, Profiler* prof) {
-        {
-            ProfScope ps(prof, "recommend/merge", st);
-            hipLaunchKernelGGL((k_rec_merge<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), 0, st, ls, li, ln, nsp, m, K, oi.p, os.p);
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipMemcpyAsync(items + b0 * K, oi.p, (size_t)m * K * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(scores + b0 * K, os.p, (size_t)m * K * sizeof(double), hipMemcpyDeviceToHost, st));
-        return PCR_OK;
-    }
-};
-
-// Top-N evaluation's device tables (PcrTopnRel of pcr_host.h, uploaded once per (threshold, cutoffs)) and its outputs: the
-// per-user metric rows met[n][ncut][6] of the counted users and the reduced sums [ncut][8] + the count (k_topn_fin)
-struct TopnDev {
-    PcrTopnRel rel;
-    int ncut = 0;
-    int cut[PCR_TOPN_MAX_CUTOFFS] = {};
-    double threshold = 0.0;
-    bool valid = false;
-    DBuf<int64_t> rptr;
-    DBuf<int32_t> ritem;
-    DBuf<double> rgain, idcg, disc, met, part, sums;
-    bool same(int nc, const int* cuts, double thr) const {
-        if (!valid || nc != ncut || !(thr == threshold)) return false;
-        for (int c = 0; c < nc; ++c) if (cuts[c] != cut[c]) return false;
-        return true;
-    }
-    // the relevance tables of rows [0, rows) of the test CSR, to the device
-    int build(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, int nc, const int* cuts, double thr) {
-        valid = false;
-        pcr_topn_relevance(rows, tptr, titem, tval, thr, nc, cuts, rel);
-        ncut = nc; threshold = thr;
-        for (int c = 0; c < nc; ++c) cut[c] = cuts[c];
-        RC(rptr.upload(rel.rptr, nullptr)); RC(ritem.upload(rel.ritem, nullptr)); RC(rgain.upload(rel.rgain, nullptr));
-        RC(idcg.upload(rel.idcg, nullptr)); RC(disc.upload(rel.disc, nullptr));
-        RC(met.alloc(rel.users.size() * (size_t)ncut * 6)); RC(sums.alloc((size_t)ncut * 8 + 1));
-        valid = true;
-        return PCR_OK;
-    }
-    // The end of an evaluation, after rec_run: the fixed-order sums over the counted users into sums (k_sum4_stage1 / k_fin4's
-    // two stages, one block row per cutoff; timed in prof's "recommend/metrics"), combined across ranks by combine(sums, count),
-    // read back into stats once wait() has synchronised st; with per_user, per_user[rows][ncut][6]: NaN, then the counted users' rows
-    template <class Combine, class Wait>
-    int finish(hipStream_t st, Profiler* prof, Combine&& combine, Wait&& wait, pcr_topn_stats* stats, int64_t rows, double* per_user) {
-        {
-            ProfScope ps(prof, "recommend/metrics", st);
-            const int64_t n = (int64_t)rel.users.size();
-            const int nb = (int)std::min<int64_t>(512, std::max<int64_t>(1, cdiv(n, 2048)));
-            const int per = cdiv(std::max<int64_t>(n, 1), nb);
-            if (part.n < (size_t)nb * ncut * 8) RC(part.alloc((size_t)nb * ncut * 8));
-            hipLaunchKernelGGL(k_topn_sum1, dim3(nb, ncut), dim3(PCR_EW_BLOCK), 0, st, (const double*)met.p, n, ncut, per, part.p);
-            hipLaunchKernelGGL(k_topn_fin, dim3(ncut), dim3(PCR_EW_BLOCK), 0, st, (const double*)part.p, nb, n, sums.p);
-            HIPCHK(hipGetLastError());
-        }
-        RC(combine(sums.p, (size_t)ncut * 8 + 1));
-        std::vector<double> hs((size_t)ncut * 8 + 1);
-        HIPCHK(hipMemcpyAsync(hs.data(), sums.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        RC(wait());
-        pcr_topn_stats_from(hs.data(), ncut, cut, stats);
-        if (!per_user) return PCR_OK;
-        const size_t w = (size_t)ncut * 6;
-        std::vector<double> h(rel.users.size() * w);
-        if (!h.empty()) HIPCHK(hipMemcpyAsync(h.data(), met.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        std::fill(per_user, per_user + (size_t)rows * w, (double)NAN);
-        for (size_t i = 0; i < rel.users.size(); ++i) std::copy(h.begin() + i * w, h.begin() + (i + 1) * w, per_user + (size_t)rel.users[i] * w);
-        return PCR_OK;
-    }
-};
-
-// rec_run's sink for the top-N evaluation: merge + metrics (k_rec_merge_topn) into d.met at the batch's rows
-template <typename T>
-struct RecTopn {
-    hipStream_t st;
-    int K;
-    TopnDev& d;
-    RecTopn(hipStream_t st_, int K_, TopnDev& d_) : st(st_), K(K_), d(d_) {}
-    int begin(int64_t) { return PCR_OK; }
-    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp, Profiler* prof) {
-        TopnArgs ta;
-        ta.rptr = d.rptr.p + b0; ta.ritem = d.ritem.p; ta.rgain = d.rgain.p; ta.idcg = d.idcg.p + (size_t)b0 * d.ncut * 2;
-        ta.disc = d.disc.p; ta.out = d.met.p + (size_t)b0 * d.ncut * 6; ta.ncut = d.ncut;
-        for (int c = 0; c < PCR_TOPN_MAX_CUTOFFS; ++c) ta.cut[c] = c < d.ncut ? d.cut[c] : 0;
-        ProfScope ps(prof, "recommend/metrics", st);
-        hipLaunchKernelGGL((k_rec_merge_topn<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), (size_t)4 * K * sizeof(int32_t), st, ls, li, ln, nsp, m, K, ta);
-        HIPCHK(hipGetLastError());
-        return PCR_OK;
-    }
-};
-
-// Beyond-accuracy metrics (pcr_evaluate_diversity, pcr_topk.h): the per-item tables and the outputs of one call -- the exposure
-// counters [ncut][d2] (they live across rec_run's user batches and are zeroed once per call), the per-user rows met[n][ncut][6]
-// in the column order k_topn_sum1 reduces, the reduced sums [ncut][8] + the count
-struct DivDev {
-    int ncut = 0;
-    int cut[PCR_TOPN_MAX_CUTOFFS] = {};
-    int64_t d2 = 0;
-    DBuf<double> inv, q, met, part, sums, expod;
-    DBuf<unsigned long long> expo;
-    const double* info = nullptr;
-};
-
-// rec_run's sink for the beyond-accuracy metrics: merge + exposure, novelty and ILD (k_rec_merge_div) into d.expo and d.met
-template <typename T>
-struct RecDiversity {
-    hipStream_t st;
-    int K;
-    const T* V;
-    int r, ld;
-    DivDev& d;
-    RecDiversity(hipStream_t st_, int K_, const T* V_, int r_, int ld_, DivDev& d_) : st(st_), K(K_), V(V_), r(r_), ld(ld_), d(d_) {}
-    int begin(int64_t) { return PCR_OK; }
-    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp, Profiler* prof) {
-        DivArgs da;
-        da.inv = d.inv.p; da.q = d.q.p; da.info = d.info; da.expo = d.expo.p; da.out = d.met.p + (size_t)b0 * d.ncut * 6;
-        da.d2 = d.d2; da.ncut = d.ncut;
-        for (int c = 0; c < PCR_TOPN_MAX_CUTOFFS; ++c) da.cut[c] = c < d.ncut ? d.cut[c] : 0;
-        ProfScope ps(prof, "recommend/diversity", st);
-        hipLaunchKernelGGL((k_rec_merge_div<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), (size_t)4 * K * sizeof(int32_t), st, ls, li, ln, nsp, m, K, V, r,
-                           ld, da);
-        HIPCHK(hipGetLastError());
-        return PCR_OK;
-    }
-};
-
-// info[] of the training ratings pitem[0, pnnz) on the device (NULL: pop = 0) into `info`: the counts by integer adds, combined
-// across ranks by combine(), the logarithms on the host (pcr_diversity_info), like the top-N discount table
-template <class Combine, class Wait>
-static int div_info_build(hipStream_t st, const int32_t* pitem, int64_t pnnz, int64_t d1, int64_t d2, Combine&& combine, Wait&& wait,
-                          DBuf<double>& info) {
-    DBuf<unsigned long long> cnt;
-    DBuf<double> pop;
-    RC(cnt.alloc((size_t)d2)); RC(pop.alloc((size_t)d2));
-    HIPCHK(hipMemsetAsync(cnt.p, 0, (size_t)d2 * sizeof(unsigned long long), st));
-    if (pitem && pnnz > 0)
-        hipLaunchKernelGGL(k_div_pop, dim3((unsigned)std::min<int64_t>(4096, cdiv(pnnz, 256))), dim3(256), 0, st, pitem, pnnz, cnt.p);
-    hipLaunchKernelGGL(k_div_pop_f64, dim3((unsigned)cdiv(d2, 256)), dim3(256), 0, st, (const unsigned long long*)cnt.p, d2, pop.p);
-    HIPCHK(hipGetLastError());
-    RC(combine(pop.p, (size_t)d2));
-    std::vector<double> h((size_t)d2), hi((size_t)d2);
-    HIPCHK(hipMemcpyAsync(h.data(), pop.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    RC(wait());
-    pcr_diversity_info(d1, h.data(), d2, hi.data());
-    RC(info.upload(hi, st));
-    return PCR_OK;
-}
-
-// The beyond-accuracy evaluation of the n users h_users (rows of U and of the exclusion CSR, as rec_run; NULL: rows 0..n-1)
-// with the self-information table info: the row norms, the sweep with RecDiversity, the fixed-order sums over the users
-// (k_topn_sum1 / k_topn_fin on met, unchanged) and the cumulative exposure; sums and exposure are combined across ranks by
-// combine() and read back once wait() has synchronised st.  "recommend/diversity" times everything but the score kernel.
-template <typename T, class Combine, class Wait>
-static int div_run(hipStream_t st, const T* U, const T* V, int r, int ld, int64_t d2, const int64_t* xptr, const int32_t* xitem,
-                   const double* info, int64_t n, const int32_t* h_users, int ncut, const int* cuts, Profiler* prof, Combine&& combine,
-                   Wait&& wait, pcr_diversity_stats* stats, double* per_user, int64_t* exposure) {
-    DivDev D;
-    D.ncut = ncut; D.d2 = d2; D.info = info;
-    for (int c = 0; c < ncut; ++c) D.cut[c] = cuts[c];
-    const int K = cuts[ncut - 1];
-    RC(D.inv.alloc((size_t)d2)); RC(D.q.alloc((size_t)d2)); RC(D.expo.alloc((size_t)ncut * d2)); RC(D.expod.alloc((size_t)ncut * d2));
-    RC(D.met.alloc((size_t)n * ncut * 6)); RC(D.sums.alloc((size_t)ncut * 8 + 1));
-    {
-        ProfScope ps(prof, "recommend/diversity", st);
-        HIPCHK(hipMemsetAsync(D.expo.p, 0, (size_t)ncut * d2 * sizeof(unsigned long long), st));
-        hipLaunchKernelGGL((k_div_prepare<T>), dim3((unsigned)cdiv(d2, 4)), dim3(256), 0, st, V, r, ld, d2, D.inv.p, D.q.p);
-        HIPCHK(hipGetLastError());
-    }
-    RC(rec_run<T>(st, U, V, r, ld, d2, xptr, xitem, n, h_users, K, 1, prof, RecDiversity<T>(st, K, V, r, ld, D)));
-    {
-        ProfScope ps(prof, "recommend/diversity", st);
-        const int nb = (int)std::min<int64_t>(512, std::max<int64_t>(1, cdiv(n, 2048)));
-        const int per = cdiv(std::max<int64_t>(n, 1), nb);
-        RC(D.part.alloc((size_t)nb * ncut * 8));
-        hipLaunchKernelGGL(k_topn_sum1, dim3(nb, ncut), dim3(PCR_EW_BLOCK), 0, st, (const double*)D.met.p, n, ncut, per, D.part.p);
-        hipLaunchKernelGGL(k_topn_fin, dim3(ncut), dim3(PCR_EW_BLOCK), 0, st, (const double*)D.part.p, nb, n, D.sums.p);
-        hipLaunchKernelGGL(k_div_expo_finish, dim3((unsigned)cdiv(d2, 256)), dim3(256), 0, st, (const unsigned long long*)D.expo.p, d2, ncut, D.expod.p);
-        HIPCHK(hipGetLastError());
-    }
-    RC(combine(D.sums.p, (size_t)ncut * 8 + 1));
-    RC(combine(D.expod.p, (size_t)ncut * d2));
-    std::vector<double> hs((size_t)ncut * 8 + 1), he((size_t)ncut * d2), hm;
-    HIPCHK(hipMemcpyAsync(hs.data(), D.sums.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(he.data(), D.expod.p, he.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (per_user && n > 0) {
-        hm.resize((size_t)n * ncut * 6);
-        HIPCHK(hipMemcpyAsync(hm.data(), D.met.p, hm.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    RC(wait());
-    RC(pcr_diversity_stats_from(hs.data(), ncut, cuts, he.data(), d2, stats, exposure));
-    for (size_t i = 0; i < hm.size() / 6; ++i) {           // met: len, novelty (0 when len = 0), -, -, -, ild
-        const double* m = hm.data() + i * 6;
-        double* o = per_user + i * PCR_DIVERSITY_FIELDS;
-        o[0] = m[0]; o[1] = m[0] > 0.0 ? m[1] : (double)NAN; o[2] = m[5];
-    }
-    return PCR_OK;
-}
-
-// MMR re-ranking (pcr_recommend_diverse, pcr_topk.h): the form and the workgroup shape of k_rec_merge_mmr for a pool of K rows
-// of ld values.  The streaming form is the default: it was the faster one at every shape measured.
-// pcr_tune("rerank_lds", "1") takes the LDS form, which stages the pool's rows, whenever one wave's image fits a workgroup's
-// 160 KiB.  waves = users per workgroup (4, 2 or 1, as many as fit).
-static const size_t MMR_LDS_CU = (size_t)160 * 1024;
-struct MmrShape { int form = 0, waves = 0; size_t lds = 0; };
-template <typename T>
-static MmrShape mmr_shape(int K, int ld, int knob) {
-    MmrShape s;
-    s.form = (knob > 0 && mmr_wave_lds<T>(K, ld, 1) <= MMR_LDS_CU) ? 1 : 0;
-    const size_t per = mmr_wave_lds<T>(K, ld, s.form);
-    for (int w = 4; w >= 1; w >>= 1) if ((size_t)w * per <= MMR_LDS_CU) { s.waves = w; break; }
-    s.lds = (size_t)s.waves * per;
-    return s;
-}
-
-// rec_run's sink for the re-ranking: merge + greedy selection (k_rec_merge_mmr) of topk from the pool of K, to the host arrays
-// items / scores (n x topk)
-template <typename T>
-struct RecRerank {
-    hipStream_t st;
-    int K, topk;
-    double theta;
-    const T* V;
-    int r, ld;
-    const double* inv;
-    MmrShape shape;
-    int32_t* items;
-    double* scores;
-    DBuf<int32_t> oi;
-    DBuf<double> os;
-    RecRerank(hipStream_t st_, int K_, int topk_, double theta_, const T* V_, int r_, int ld_, const double* inv_, MmrShape shape_,
-              int32_t* items_, double* scores_)
-        : st(st_), K(K_), topk(topk_), theta(theta_), V(V_), r(r_), ld(ld_), inv(inv_), shape(shape_), items(items_), scores(scores_) {}
-    int begin(int64_t nb) { RC(oi.alloc((size_t)nb * topk)); RC(os.alloc((size_t)nb * topk)); return PCR_OK; }
-    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp, Profiler* prof) {
-        MmrArgs ma;
-        ma.inv = inv; ma.out_i = oi.p; ma.out_s = os.p; ma.topk = topk; ma.theta = theta;
-        {
-            ProfScope ps(prof, "recommend/rerank", st);
-            const dim3 grid((unsigned)cdiv(m, shape.waves)), block(64 * shape.waves);
-            if (shape.form) hipLaunchKernelGGL((k_rec_merge_mmr<T, 1>), grid, block, shape.lds, st, ls, li, ln, nsp, m, K, V, r, ld, ma);
-            else hipLaunchKernelGGL((k_rec_merge_mmr<T, 0>), grid, block, shape.lds, st, ls, li, ln, nsp, m, K, V, r, ld, ma);
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipMemcpyAsync(items + b0 * topk, oi.p, (size_t)m * topk * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(scores + b0 * topk, os.p, (size_t)m * topk * sizeof(double), hipMemcpyDeviceToHost, st));
-        return PCR_OK;
-    }
-};
-
-// The re-ranked lists of the n users h_users (rows of U and of the exclusion CSR, as rec_run; NULL: rows 0..n-1): the row norms
-// (k_div_prepare, as the ILD's), then the sweep with K = pool and RecRerank.  "recommend/rerank" times everything but the
-// score kernel.  pcr_tune("rerank_lds") is read at every call.  k_div_prepare is reused as it is, so its second table q[d2] (the
-// ILD's |v^_j|^2) is allocated and written here too although the re-ranking never reads it: one d2-sized buffer per call.
-template <typename T>
-static int rerank_run(hipStream_t st, const T* U, const T* V, int r, int ld, int64_t d2, const int64_t* xptr, const int32_t* xitem,
-                      int64_t n, const int32_t* h_users, int topk, int pool, double theta, Profiler* prof, int32_t* items, double* scores) {
-    if (n <= 0) return PCR_OK;
-    const MmrShape shape = mmr_shape<T>(pool, ld, pcr_tune_int("rerank_lds", 0));
-    if (shape.waves < 1) { pcr_set_error("pcr_recommend_diverse: rank " + std::to_string(r) + " is too large for the re-ranking kernel's LDS"); return PCR_ERR_UNSUPPORTED; }
-    DBuf<double> inv, q;
-    RC(inv.alloc((size_t)d2)); RC(q.alloc((size_t)d2));
-    if (shape.form) HIPCHK(hipFuncSetAttribute((const void*)k_rec_merge_mmr<T, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds));
-    else HIPCHK(hipFuncSetAttribute((const void*)k_rec_merge_mmr<T, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds));
-    {
-        ProfScope ps(prof, "recommend/rerank", st);
-        hipLaunchKernelGGL((k_div_prepare<T>), dim3((unsigned)cdiv(d2, 4)), dim3(256), 0, st, V, r, ld, d2, inv.p, q.p);
-        HIPCHK(hipGetLastError());
-    }
-    return rec_run<T>(st, U, V, r, ld, d2, xptr, xitem, n, h_users, pool, 1, prof,
-                      RecRerank<T>(st, pool, topk, theta, V, r, ld, inv.p, shape, items, scores));
-}
-
-// Exact rank metrics (pcr_evaluate_ranks, pcr_topk.h): the relevance table of a threshold on the device (PcrTopnRel's users,
-// rptr and ritem; uploaded once per threshold) and the outputs: rrank[nrel] the ranks of ritem entry for entry, met[n][6]
-// k_rank_finish's rows, the reduced sums [8] + the count
-struct RankDev {
-    PcrTopnRel rel;
-    double threshold = 0.0;
-    bool valid = false;
-    DBuf<int64_t> rptr, rrank;
-    DBuf<int32_t> ritem, rslot, users;
-    DBuf<double> met, part, sums;
-    bool same(double thr) const { return valid && thr == threshold; }
-    int build(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, double thr) {
-        valid = false;
-        const int one = 1;
-        pcr_topn_relevance(rows, tptr, titem, tval, thr, 1, &one, rel);
-        threshold = thr;
-        RC(rptr.upload(rel.rptr, nullptr)); RC(ritem.upload(rel.ritem, nullptr)); RC(users.upload(rel.users, nullptr));
-        RC(rslot.alloc(rel.ritem.size())); RC(rrank.alloc(rel.ritem.size()));
-        RC(met.alloc(rel.users.size() * 6)); RC(sums.alloc(9));
-        valid = true;
-        return PCR_OK;
-    }
-    // The end of an evaluation, after rank_run: TopnDev::finish's steps with one "cutoff" (the same two kernels sum met's
-    // columns), then per_user[rows][PCR_RANK_FIELDS] and ranks[] of the test CSR tptr / titem / tval (rows of this table's build)
-    template <class Combine, class Wait>
-    int finish(hipStream_t st, Profiler* prof, Combine&& combine, Wait&& wait, pcr_rank_stats* stats, int64_t rows, double* per_user,
-               const int64_t* tptr, const int32_t* titem, const double* tval, int64_t* ranks) {
-        const int64_t n = (int64_t)rel.users.size();
-        {
-            ProfScope ps(prof, "ranks/finish", st);
-            const int nb = (int)std::min<int64_t>(512, std::max<int64_t>(1, cdiv(n, 2048)));
-            const int per = cdiv(std::max<int64_t>(n, 1), nb);
-            if (part.n < (size_t)nb * 8) RC(part.alloc((size_t)nb * 8));
-            hipLaunchKernelGGL(k_topn_sum1, dim3(nb, 1), dim3(PCR_EW_BLOCK), 0, st, (const double*)met.p, n, 1, per, part.p);
-            hipLaunchKernelGGL(k_topn_fin, dim3(1), dim3(PCR_EW_BLOCK), 0, st, (const double*)part.p, nb, n, sums.p);
-            HIPCHK(hipGetLastError());
-        }
-        RC(combine(sums.p, (size_t)9));
-        double hs[9];
-        HIPCHK(hipMemcpyAsync(hs, sums.p, sizeof hs, hipMemcpyDeviceToHost, st));
-        RC(wait());
-        pcr_rank_stats_from(hs, stats);
-        if (per_user) {
-            std::vector<double> h((size_t)n * 6);
-            if (n) HIPCHK(hipMemcpyAsync(h.data(), met.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            std::fill(per_user, per_user + (size_t)rows * PCR_RANK_FIELDS, (double)NAN);
-            for (int64_t i = 0; i < n; ++i) {           // met: |R_u|, rr, mean_rank, mpr, first_rank, auc
-                const double* m = h.data() + (size_t)i * 6;
-                double* o = per_user + (size_t)rel.users[(size_t)i] * PCR_RANK_FIELDS;
-                o[0] = m[4]; o[1] = m[1]; o[2] = m[2]; o[3] = m[5]; o[4] = m[3];
-            }
-        }
-        if (ranks) {
-            std::vector<int64_t> h(rel.ritem.size());
-            if (!h.empty()) HIPCHK(hipMemcpyAsync(h.data(), rrank.p, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            pcr_rank_scatter(rows, tptr, titem, tval, threshold, rel, h.data(), ranks);
-        }
-        return PCR_OK;
-    }
-};
-
-// The rank metrics' sweep for the counted users of d (rows of U and of the exclusion CSR, as rec_run): the relevant items'
-// scores and their sort once for all users ("ranks/relscore"), then per user batch (RecGeom, the scratch being the splits'
-// histograms: |R_u| + 1 counters per user) the counting sweep ("ranks/count") and the scan ("ranks/finish") into d.rrank / d.met.
-template <typename T>
-static int rank_run(hipStream_t st, const T* U, const T* V, int r, int ld, int64_t d2, const int64_t* xptr, const int32_t* xitem,
-                    RankDev& d, Profiler* prof) {
-    const int64_t n = (int64_t)d.rel.users.size(), nrel = (int64_t)d.rel.ritem.size();
-    if (n <= 0) return PCR_OK;
-    DBuf<T> us, rs;
-    DBuf<int32_t> ri, hist;
-    RC(us.alloc((size_t)nrel)); RC(rs.alloc((size_t)nrel)); RC(ri.alloc((size_t)nrel));
-    {
-        ProfScope ps(prof, "ranks/relscore", st);
-        hipLaunchKernelGGL((k_rank_relscore<T>), dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, U, V, r, ld, (const int32_t*)d.users.p, n,
-                           (const int64_t*)d.rptr.p, (const int32_t*)d.ritem.p, us.p);
-        hipLaunchKernelGGL((k_rank_sort<T>), dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, n, (const int64_t*)d.rptr.p, (const int32_t*)d.ritem.p,
-                           (const T*)us.p, rs.p, ri.p, d.rslot.p);
-        HIPCHK(hipGetLastError());
-    }
-    RecGeom geom(n, d2, sizeof(int32_t) * (size_t)((nrel + n + n - 1) / n));
-    const int64_t cap = pcr_tune_int("ranks_batch_users", 0);
-    if (cap > 0) {
-        geom.nb = std::min(geom.nb, (cap + RecGeom::users_per_wg - 1) / RecGeom::users_per_wg * RecGeom::users_per_wg);
-        geom.smax = geom.splits_for(std::min(geom.nb, n));
-    }
-    const std::vector<int64_t>& rp = d.rel.rptr;
-    auto buckets = [&](int64_t b0, int64_t m) { return rp[(size_t)(b0 + m)] - rp[(size_t)b0] + m; };
-    size_t hmax = 0;
-    for (int64_t b0 = 0; b0 < n; b0 += geom.nb) hmax = std::max(hmax, (size_t)buckets(b0, std::min(geom.nb, n - b0)));
-    RC(hist.alloc(hmax * (size_t)geom.smax));
-    const size_t lds = rank_wave_lds<T>() * rec::WAVES;
-    for (int64_t b0 = 0; b0 < n; b0 += geom.nb) {
-        const int64_t m = std::min(geom.nb, n - b0), hsplit = buckets(b0, m);
-        int per, nsp;
-        geom.batch(m, &per, &nsp);
-        {
-            ProfScope ps(prof, "ranks/count", st);
-            HIPCHK(hipMemsetAsync(hist.p, 0, (size_t)nsp * (size_t)hsplit * sizeof(int32_t), st));
-            hipLaunchKernelGGL((k_rank_count<T>), dim3((unsigned)cdiv(m, RecGeom::users_per_wg), (unsigned)nsp), dim3(rec::WAVES * 64), lds, st, U, V,
-                               r, ld, (int)d2, (const int32_t*)d.users.p + b0, m, xptr, xitem, per, (const int64_t*)d.rptr.p + b0, (const T*)rs.p,
-                               (const int32_t*)ri.p, hist.p, hsplit);
-            HIPCHK(hipGetLastError());
-        }
-        ProfScope ps(prof, "ranks/finish", st);
-        hipLaunchKernelGGL(k_rank_finish, dim3((unsigned)cdiv(m, 4)), dim3(256), 0, st, (const int32_t*)hist.p, hsplit, nsp, m,
-                           (const int64_t*)d.rptr.p + b0, (const int32_t*)d.rslot.p, d.rrank.p, d.met.p + (size_t)b0 * 6);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipStreamSynchronize(st));                      // (us / rs / ri / hist are freed on return)
-    return PCR_OK;
-}
 
 // users of one CSR grouped by length class; each class has its own workgroup size
 struct Bin {
@@ -663,54 +65,6 @@ struct Bin {
 static const int BIN_LIMIT[3] = {128, 512, 4096};
 static const int BIN_BLOCK[4] = {64, 256, 512, 512};
 static const int GRAM_DEFAULT_CAP = 0;       // default length bound of the dual-form U-step class (0: off; pcr_tune "ustep_gram")
-
-struct pcr_solver {
-    virtual ~pcr_solver() {}
-    virtual int set_factors(const double* U, const double* V, bool local) = 0;
-    virtual int get_factors(double* U, double* V, bool local) = 0;
-    // PrimalCR / PrimalCR++ only (Solver<T>)
-    static int pcr_only(const char* what) {
-        pcr_set_error(std::string(what) + ": a PrimalCR / PrimalCR++ entry point; this solver is CCDR1 (solver type 0)");
-        return PCR_ERR_STATE;
-    }
-    virtual int comp_m(double*) { return pcr_only("pcr_comp_m"); }
-    virtual int objective(double*) { return pcr_only("pcr_objective"); }
-    virtual int obtain_g(double*) { return pcr_only("pcr_obtain_g"); }
-    virtual int compute_Ha(const double*, double*) { return pcr_only("pcr_compute_Ha"); }
-    virtual int solve_delta(const double*, double*, int*) { return pcr_only("pcr_solve_delta"); }
-    virtual int update_V(double*, int*) { return pcr_only("pcr_update_V"); }
-    virtual int update_U(double*, int64_t*) { return pcr_only("pcr_update_U"); }
-    virtual int evaluate(int which, int ndcg_k, double* err, double* ndcg) = 0;
-    virtual int train(pcr_log_fn log, void* ctx, pcr_iter_stats* hist) = 0;
-    virtual int iterate_abi(int n, pcr_iter_stats* out) = 0;
-    virtual int comm_init(const void* id) = 0;
-    virtual int comm_init_p2p(const char* shm_name) = 0;
-    virtual void comm_abort() = 0;
-    virtual int comm_nranks() = 0;
-    virtual int sync() = 0;
-    virtual std::string ustep_classes() = 0;                       // comma-separated profile slot names of the U-step length classes
-    virtual int class_rows(const std::string& slot, double* v) = 0; // rows of V that class has gathered so far (pcr_tune "count_rows")
-    int64_t first_user = 0, n_users = 0, nnz_local = 0;
-    double ustep_rows = 0.0;      // rows of V gathered by all U steps so far (all ranks); pcr_solver_counter("ustep_row_gathers")
-    bool local_only = false;      // nranks > 1 without a communicator: entry points return this shard's partials
-    Profiler prof;
-    std::vector<std::pair<std::string, double>> setup_ms;   // wall time of the phases of pcr_solver_create, in order (pcr_solver_counter "setup_ms/<i>", pcr_solver_setup_phase)
-    // CCDR1 only (pcr_ccd.h): the "ccd_residual_mismatch" counter, pcr_solver_set_ccd_params
-    virtual int residual_mismatch(double*) { pcr_set_error("pcr_solver_counter: 'ccd_residual_mismatch' exists on a CCDR1 solver only"); return PCR_ERR_STATE; }
-    virtual int set_ccd_params(const pcr_ccd_params*) { pcr_set_error("pcr_solver_set_ccd_params: not a CCDR1 solver (solver type 0)"); return PCR_ERR_STATE; }
-    // pcr_recommend: `local` = rows of this shard (checked by the caller)
-    virtual int recommend(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores) = 0;
-    // pcr_recommend_diverse: `local` = rows of this shard (arguments checked by the caller)
-    virtual int recommend_diverse(int64_t n, const int32_t* local, int topk, int pool, double theta, int flags, int32_t* items,
-                                  double* scores) = 0;
-    // pcr_evaluate_topn (arguments checked by the caller)
-    virtual int evaluate_topn(int ncut, const int* cuts, double threshold, int flags, pcr_topn_stats* stats, double* per_user) = 0;
-    // pcr_evaluate_ranks (arguments checked by the caller)
-    virtual int evaluate_ranks(double threshold, int flags, pcr_rank_stats* stats, double* per_user, int64_t* ranks) = 0;
-    // pcr_evaluate_diversity: `local` = rows of this shard (arguments checked by the caller)
-    virtual int evaluate_diversity(int64_t n, const int32_t* local, int ncut, const int* cuts, int flags, pcr_diversity_stats* stats,
-                                   double* per_user, int64_t* exposure) = 0;
-};
 
 // launch knobs: pcr_tune() values read once when the solver is created (include/primalcr.h lists them)
 struct Tune {
@@ -839,8 +193,6 @@ struct Solver final : pcr_solver {
     DBuf<double> d_out4;
     std::vector<int32_t> h_test_item;             // the test shard's ratings (rows: ev[1].h_uptr), for pcr_evaluate_topn
     std::vector<double> h_test_val;
-    TopnDev topn;
-    RankDev rankd;
     // ---- factors and CG vectors (d2 x ld, nu x ld)
     DBuf<T> d_U, d_V, d_Vnew, d_g, d_delta, d_rr, d_p, d_Hp;
     CGState* d_cgp = nullptr;                     // the CG scalars live in d_scal[32..43): they come back with the objective's read-back
@@ -2090,7 +1442,7 @@ struct Solver final : pcr_solver {
         NCCLCHK(ncclAllReduce(buf, buf, count, sizeof(T) == 4 ? ncclFloat : ncclDouble, ncclSum, comm, q));
         return PCR_OK;
     }
-    int allreduce_f64(double* buf, size_t count) {
+    int allreduce_f64(double* buf, size_t count) override {
         if (single()) return PCR_OK;
         if (!comm && !p2p) { pcr_set_error("nranks > 1 but neither pcr_solver_comm_init nor pcr_solver_comm_init_p2p was called"); return PCR_ERR_STATE; }
         ProfScope ps(&prof, "allreduce", st);
@@ -2795,138 +2147,24 @@ struct Solver final : pcr_solver {
         return n;
     }
     int sync() override { RC(sync_checked()); return PCR_OK; }
-
-    // top-K recommendation from the device factors (pcr_topk.h); reads U, V and the shard's CSR (item-ascending per user: the
-    // data set's CSR as uploaded, never permuted -- the (level, m) sorts write their own arrays), writes nothing of the solver
-    // The launches are timed in prof: this solver's own, or that of the CCDR1 solver that holds this one.
-    int recommend_with(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores, Profiler* prof) {
-        const bool ex = (flags & PCR_REC_EXCLUDE_TRAIN) != 0;
-        return rec_run<T>(st, d_U.p, d_V.p, geo.r, geo.ld, d2, ex ? d_uptr.p : nullptr, ex ? d_item.p : nullptr, n, local, K,
-                          tune.recommend_select, prof, RecCopy<T>(st, K, items, scores));
+    // What the serving layer (pcr_serve.hip) reads: U, V, the shard's CSR (item-ascending per user: the data set's CSR as uploaded,
+    // never permuted -- the (level, m) sorts write their own arrays) and its test ratings (h_test_*, kept at creation); nothing of
+    // the solver is written.  The launches are timed in prof, unless the CCDR1 solver that holds this one puts its own there.
+    void serve_view(ServeView* v) override {
+        v->dtype = sizeof(T) == sizeof(double) ? PCR_F64 : PCR_F32;
+        v->st = st; v->U = d_U.p; v->V = d_V.p; v->r = geo.r; v->ld = geo.ld; v->rows = n_users; v->d1 = d1; v->d2 = d2;
+        v->uptr = d_uptr.p; v->item = d_item.p; v->nnz = nnz_local;
+        v->tptr = ev[1].h_uptr.data(); v->titem = h_test_item.data(); v->tval = h_test_val.data();
+        v->select = tune.recommend_select; v->prof = &prof;
+        v->exchange = single() ? SERVE_LOCAL : p2p ? SERVE_P2P : SERVE_RCCL; v->owner = this;
     }
-    // full-catalogue top-N evaluation of the shard's users against its test ratings (h_test_*, kept at creation); the relevance
-    // tables are built on the first call for a (threshold, cutoffs) and kept in topn
-    int evaluate_topn_with(int ncut, const int* cuts, double thr, int flags, pcr_topn_stats* stats, double* per_user, Profiler* prof) {
-        if (!topn.same(ncut, cuts, thr))
-            RC(topn.build(n_users, ev[1].h_uptr.data(), h_test_item.data(), h_test_val.data(), ncut, cuts, thr));
-        const bool ex = (flags & PCR_REC_EXCLUDE_TRAIN) != 0;
-        const int K = cuts[ncut - 1];
-        RC(rec_run<T>(st, d_U.p, d_V.p, geo.r, geo.ld, d2, ex ? d_uptr.p : nullptr, ex ? d_item.p : nullptr, (int64_t)topn.rel.users.size(),
-                      topn.rel.users.data(), K, 1, prof, RecTopn<T>(st, K, topn)));
-        // (the read-back waits through sync_checked: a peer-to-peer exchange that missed its deadline is reported there)
-        return topn.finish(st, prof, [this](double* p, size_t n) { return allreduce_f64(p, n); }, [this] { return sync_checked(); }, stats,
-                           n_users, per_user);
-    }
-    int evaluate_topn(int ncut, const int* cuts, double thr, int flags, pcr_topn_stats* stats, double* per_user) override {
-        return evaluate_topn_with(ncut, cuts, thr, flags, stats, per_user, &prof);
-    }
-    // exact rank metrics of the shard's users against its test ratings; the relevance table is built on the first call for a
-    // threshold and kept in rankd
-    int evaluate_ranks_with(double thr, int flags, pcr_rank_stats* stats, double* per_user, int64_t* ranks, Profiler* prof) {
-        if (!rankd.same(thr)) RC(rankd.build(n_users, ev[1].h_uptr.data(), h_test_item.data(), h_test_val.data(), thr));
-        const bool ex = (flags & PCR_REC_EXCLUDE_TRAIN) != 0;
-        RC(rank_run<T>(st, d_U.p, d_V.p, geo.r, geo.ld, d2, ex ? d_uptr.p : nullptr, ex ? d_item.p : nullptr, rankd, prof));
-        return rankd.finish(st, prof, [this](double* p, size_t n) { return allreduce_f64(p, n); }, [this] { return sync_checked(); }, stats,
-                            n_users, per_user, ev[1].h_uptr.data(), h_test_item.data(), h_test_val.data(), ranks);
-    }
-    int evaluate_ranks(double thr, int flags, pcr_rank_stats* stats, double* per_user, int64_t* ranks) override {
-        return evaluate_ranks_with(thr, flags, stats, per_user, ranks, &prof);
-    }
-    int recommend(int64_t n, const int32_t* local, int K, int flags, int32_t* items, double* scores) override {
-        return recommend_with(n, local, K, flags, items, scores, &prof);
-    }
-    // MMR re-ranked lists from the device factors: per user, nothing is exchanged
-    int recommend_diverse_with(int64_t n, const int32_t* local, int topk, int pool, double theta, int flags, int32_t* items, double* scores,
-                               Profiler* prof) {
-        const bool ex = (flags & PCR_REC_EXCLUDE_TRAIN) != 0;
-        return rerank_run<T>(st, d_U.p, d_V.p, geo.r, geo.ld, d2, ex ? d_uptr.p : nullptr, ex ? d_item.p : nullptr, n, local, topk, pool, theta,
-                             prof, items, scores);
-    }
-    int recommend_diverse(int64_t n, const int32_t* local, int topk, int pool, double theta, int flags, int32_t* items, double* scores) override {
-        return recommend_diverse_with(n, local, topk, pool, theta, flags, items, scores, &prof);
-    }
-    // beyond-accuracy metrics of the shard's users from the device factors; the self-information table comes from the shard's
-    // training ratings (all-reduced with a communicator) and is kept: the ratings never change, the exchange mode can
-    int evaluate_diversity_with(int64_t n, const int32_t* local, int ncut, const int* cuts, int flags, pcr_diversity_stats* stats,
-                                double* per_user, int64_t* exposure, Profiler* prof) {
-        // (the peer-to-peer communicator's fp64 exchange is its 64-double scalar slot: the d2-sized tables do not fit it)
-        if (p2p && !single()) { pcr_set_error("pcr_evaluate_diversity: not available on a peer-to-peer communicator (use RCCL, or local-only shards and pcr_exposure_stats)"); return PCR_ERR_UNSUPPORTED; }
-        auto combine = [this](double* p, size_t cnt) { return allreduce_f64(p, cnt); };
-        auto wait = [this] { return sync_checked(); };
-        const int mode = single() ? 1 : 2;
-        if (div_info_mode != mode) {
-            div_info_mode = 0;
-            RC(div_info_build(st, d_item.p, nnz_local, d1, d2, combine, wait, div_info));
-            div_info_mode = mode;
-        }
-        const bool ex = (flags & PCR_REC_EXCLUDE_TRAIN) != 0;
-        return div_run<T>(st, d_U.p, d_V.p, geo.r, geo.ld, d2, ex ? d_uptr.p : nullptr, ex ? d_item.p : nullptr, div_info.p, n, local, ncut, cuts,
-                          prof, combine, wait, stats, per_user, exposure);
-    }
-    int evaluate_diversity(int64_t n, const int32_t* local, int ncut, const int* cuts, int flags, pcr_diversity_stats* stats, double* per_user,
-                           int64_t* exposure) override {
-        return evaluate_diversity_with(n, local, ncut, cuts, flags, stats, per_user, exposure, &prof);
-    }
-    DBuf<double> div_info;        // info[d2] of pcr_evaluate_diversity
-    int div_info_mode = 0;        // 0: not built, 1: from this shard's ratings alone, 2: all-reduced
 };
 
 #include "pcr_ccd.h"
 
 // ------------------------------------------------------------------------------------------
-// C ABI
+// C ABI (abi_guard of pcr_dev.h: no C++ exception may cross it)
 // ------------------------------------------------------------------------------------------
-// No C++ exception may cross the C ABI (a host allocation that fails while a 700 M-rating shard is being set up is an error
-// code, not std::terminate).
-template <class F>
-static int abi_guard(const char* what, F&& body) noexcept {
-    try { return body(); }
-    catch (const std::bad_alloc&) { try { pcr_set_error(std::string(what) + ": out of host memory"); } catch (...) {} return PCR_ERR_NOMEM; }
-    catch (const std::exception& e) { try { pcr_set_error(std::string(what) + ": " + e.what()); } catch (...) {} return PCR_ERR_ARG; }
-    catch (...) { return PCR_ERR_ARG; }
-}
-#define PCR_ABI(name, expr) return abi_guard(name, [&]() -> int { return (expr); })
-
-// pcr_recommend_model / pcr_evaluate_topn_model: the exclusion CSR (item-ascending rows: a CSR that is not gets a sorted copy,
-// for the kernel's cursor) and both host fp64 factors in the requested type T, rows padded to ld: U then V in one buffer
-template <typename T>
-struct ModelDev {
-    DBuf<int64_t> dx;
-    DBuf<int32_t> di;
-    DBuf<T> F;
-    int64_t d1 = 0;
-    int ld = 0;
-    const T* U() const { return F.p; }
-    const T* V() const { return F.p + (size_t)d1 * ld; }
-    int upload_exclusion(int64_t d1, const int64_t* index, const int32_t* item, bool sorted) {
-        if (!index) return PCR_OK;
-        std::vector<int32_t> sitem;
-        const int64_t nnz = index[d1];
-        if (!sorted) {
-            sitem.assign(item, item + nnz);
-            pcr_parallel_ranges(d1, pcr_host_threads(), [&](int, int64_t lo, int64_t hi) {
-                for (int64_t u = lo; u < hi; ++u) std::sort(sitem.begin() + index[u], sitem.begin() + index[u + 1]);
-            });
-        }
-        RC(dx.upload_n(index, (size_t)d1 + 1)); RC(di.upload_n(sorted ? item : sitem.data(), (size_t)nnz));
-        return PCR_OK;
-    }
-    int upload_factors(hipStream_t st, const double* hU, int64_t rows_u, const double* hV, int64_t rows_v, int64_t k) {
-        d1 = rows_u;
-        ld = ((int)k + 3) & ~3;
-        RC(F.alloc((size_t)(d1 + rows_v) * ld));
-        return upload_rows<T>(st, (int)k, ld, {{hU, d1, F.p}, {hV, rows_v, F.p + (size_t)d1 * ld}});
-    }
-};
-
-static int model_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { pcr_set_error("no HIP device available"); return PCR_ERR_DEVICE; }
-    if (device < 0 || device >= ndev) { pcr_set_error("device ordinal out of range"); return PCR_ERR_ARG; }
-    HIPCHK(hipSetDevice(device));
-    return PCR_OK;
-}
-
 extern "C" {
 
 static int solver_create(const pcr_dataset* ds, const pcr_params* p, int rank, int nranks, int64_t shard_first, int64_t d1_total, pcr_solver** out) {
@@ -2998,7 +2236,6 @@ int pcr_comm_unique_id(void* id128) {
     memcpy(id128, &id, sizeof id);
     return PCR_OK;
 }
-#define S_OR_ARG if (!s) { pcr_set_error("null solver"); return PCR_ERR_ARG; }
 int pcr_solver_comm_init(pcr_solver* s, const void* id128) { S_OR_ARG; PCR_ABI("pcr_solver_comm_init", s->comm_init(id128)); }
 int pcr_solver_comm_init_p2p(pcr_solver* s, const char* shm_name) {
     S_OR_ARG;
@@ -3138,188 +2375,5 @@ int pcr_predict(const double* U, int64_t d1, const double* V, int64_t d2, int64_
     });
 }
 
-int pcr_recommend_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
-                        int64_t n, const int32_t* users, int topk, int dtype, int32_t* items, double* scores, int device) {
-    return abi_guard("pcr_recommend_model", [&]() -> int {
-    bool sorted = true;
-    RC(pcr_recommend_model_check(U, d1, V, d2, k, index, item, n, users, topk, dtype, items, scores, &sorted));
-    RC(model_device(device));
-    if (n == 0) return PCR_OK;
-    const int select = pcr_tune_int("recommend_select", 1);
-    auto run = [&](auto zero) -> int {
-        using T = decltype(zero);
-        hipStream_t st = nullptr;
-        ModelDev<T> M;
-        RC(M.upload_exclusion(d1, index, item, sorted));
-        RC(M.upload_factors(st, U, d1, V, d2, k));
-        return rec_run<T>(st, M.U(), M.V(), (int)k, M.ld, d2, M.dx.p, M.di.p, n, users, topk, select, nullptr, RecCopy<T>(st, topk, items, scores));
-    };
-    return dtype == PCR_F64 ? run(0.0) : run(0.0f);
-    });
-}
-
-int pcr_evaluate_topn_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
-                            const int64_t* tindex, const int32_t* titem, const double* tval, int ncut, const int* cutoffs, double threshold,
-                            int dtype, pcr_topn_stats* stats, double* per_user, int device) {
-    return abi_guard("pcr_evaluate_topn_model", [&]() -> int {
-    bool sorted = true;
-    RC(pcr_evaluate_topn_model_check(U, d1, V, d2, k, index, item, tindex, titem, tval, ncut, cutoffs, threshold, dtype, stats, &sorted));
-    RC(model_device(device));
-    auto run = [&](auto zero) -> int {
-        using T = decltype(zero);
-        hipStream_t st = nullptr;
-        ModelDev<T> M;
-        RC(M.upload_exclusion(d1, index, item, sorted));
-        TopnDev D;
-        RC(D.build(d1, tindex, titem, tval, ncut, cutoffs, threshold));
-        const int K = cutoffs[ncut - 1];
-        RC(M.upload_factors(st, U, d1, V, d2, k));
-        RC(rec_run<T>(st, M.U(), M.V(), (int)k, M.ld, d2, M.dx.p, M.di.p, (int64_t)D.rel.users.size(), D.rel.users.data(), K, 1, nullptr,
-                      RecTopn<T>(st, K, D)));
-        return D.finish(st, nullptr, [](double*, size_t) { return PCR_OK; }, [st] { HIPCHK(hipStreamSynchronize(st)); return PCR_OK; }, stats, d1,
-                        per_user);
-    };
-    return dtype == PCR_F64 ? run(0.0) : run(0.0f);
-    });
-}
-
-int pcr_evaluate_ranks_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
-                             const int64_t* tindex, const int32_t* titem, const double* tval, double threshold, int dtype,
-                             pcr_rank_stats* stats, double* per_user, int64_t* ranks, int device) {
-    return abi_guard("pcr_evaluate_ranks_model", [&]() -> int {
-    bool sorted = true;
-    RC(pcr_evaluate_ranks_model_check(U, d1, V, d2, k, index, item, tindex, titem, tval, threshold, dtype, stats, &sorted));
-    RC(model_device(device));
-    auto run = [&](auto zero) -> int {
-        using T = decltype(zero);
-        hipStream_t st = nullptr;
-        ModelDev<T> M;
-        RC(M.upload_exclusion(d1, index, item, sorted));
-        RankDev D;
-        RC(D.build(d1, tindex, titem, tval, threshold));
-        RC(M.upload_factors(st, U, d1, V, d2, k));
-        RC(rank_run<T>(st, M.U(), M.V(), (int)k, M.ld, d2, M.dx.p, M.di.p, D, nullptr));
-        return D.finish(st, nullptr, [](double*, size_t) { return PCR_OK; }, [st] { HIPCHK(hipStreamSynchronize(st)); return PCR_OK; }, stats, d1,
-                        per_user, tindex, titem, tval, ranks);
-    };
-    return dtype == PCR_F64 ? run(0.0) : run(0.0f);
-    });
-}
-
-int pcr_evaluate_diversity_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
-                                 int64_t n, const int32_t* users, int ncut, const int* cutoffs, int dtype, pcr_diversity_stats* stats,
-                                 double* per_user, int64_t* exposure, int device) {
-    return abi_guard("pcr_evaluate_diversity_model", [&]() -> int {
-    bool sorted = true;
-    RC(pcr_evaluate_diversity_model_check(U, d1, V, d2, k, index, item, n, users, ncut, cutoffs, dtype, stats, &sorted));
-    RC(model_device(device));
-    auto run = [&](auto zero) -> int {
-        using T = decltype(zero);
-        hipStream_t st = nullptr;
-        ModelDev<T> M;
-        RC(M.upload_exclusion(d1, index, item, sorted));
-        RC(M.upload_factors(st, U, d1, V, d2, k));
-        auto combine = [](double*, size_t) { return PCR_OK; };
-        auto wait = [st] { HIPCHK(hipStreamSynchronize(st)); return PCR_OK; };
-        DBuf<double> info;
-        RC(div_info_build(st, (const int32_t*)M.di.p, index ? index[d1] : 0, d1, d2, combine, wait, info));
-        return div_run<T>(st, M.U(), M.V(), (int)k, M.ld, d2, M.dx.p, M.di.p, info.p, n, users, ncut, cutoffs, nullptr, combine, wait, stats,
-                          per_user, exposure);
-    };
-    return dtype == PCR_F64 ? run(0.0) : run(0.0f);
-    });
-}
-
-int pcr_recommend_diverse_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
-                                int64_t n, const int32_t* users, int topk, int pool, double theta, int dtype, int32_t* items, double* scores,
-                                int device) {
-    return abi_guard("pcr_recommend_diverse_model", [&]() -> int {
-    bool sorted = true;
-    RC(pcr_recommend_diverse_model_check(U, d1, V, d2, k, index, item, n, users, topk, pool, theta, dtype, items, scores, &sorted));
-    RC(model_device(device));
-    if (n == 0) return PCR_OK;
-    auto run = [&](auto zero) -> int {
-        using T = decltype(zero);
-        hipStream_t st = nullptr;
-        ModelDev<T> M;
-        RC(M.upload_exclusion(d1, index, item, sorted));
-        RC(M.upload_factors(st, U, d1, V, d2, k));
-        return rerank_run<T>(st, M.U(), M.V(), (int)k, M.ld, d2, M.dx.p, M.di.p, n, users, topk, pool, theta, nullptr, items, scores);
-    };
-    return dtype == PCR_F64 ? run(0.0) : run(0.0f);
-    });
-}
-
-// users[n] (global ids, NULL: the whole shard) as rows of s's shard in loc (left empty for NULL); *n the count
-static int shard_rows(const char* who, const pcr_solver* s, int64_t* n, const int32_t* users, std::vector<int32_t>& loc) {
-    if (!users) { *n = s->n_users; return PCR_OK; }
-    loc.resize((size_t)*n);
-    for (int64_t i = 0; i < *n; ++i) {
-        const int64_t x = (int64_t)users[i] - s->first_user;
-        if (x < 0 || x >= s->n_users) {
-            pcr_set_error(std::string(who) + ": user " + std::to_string(users[i]) + " is not in this shard [" + std::to_string(s->first_user) + ", " +
-                          std::to_string(s->first_user + s->n_users) + ")");
-            return PCR_ERR_ARG;
-        }
-        loc[(size_t)i] = (int32_t)x;
-    }
-    return PCR_OK;
-}
-
-int pcr_evaluate_diversity(pcr_solver* s, int64_t n, const int32_t* users, int ncut, const int* cutoffs, int flags, pcr_diversity_stats* stats,
-                           double* per_user, int64_t* exposure) {
-    S_OR_ARG;
-    RC(pcr_cutoffs_check("pcr_evaluate_diversity", ncut, cutoffs));
-    if (!stats) { pcr_set_error("pcr_evaluate_diversity: null stats"); return PCR_ERR_ARG; }
-    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_evaluate_diversity: unknown flags"); return PCR_ERR_ARG; }
-    if (users && n < 0) { pcr_set_error("pcr_evaluate_diversity: bad argument"); return PCR_ERR_ARG; }
-    return abi_guard("pcr_evaluate_diversity", [&]() -> int {
-        std::vector<int32_t> loc;
-        RC(shard_rows("pcr_evaluate_diversity", s, &n, users, loc));
-        return s->evaluate_diversity(n, users ? loc.data() : nullptr, ncut, cutoffs, flags, stats, per_user, exposure);
-    });
-}
-
-int pcr_recommend(pcr_solver* s, int64_t n, const int32_t* users, int topk, int flags, int32_t* items, double* scores) {
-    S_OR_ARG;
-    if (topk < 1 || topk > PCR_RECOMMEND_MAX_K) { pcr_set_error("pcr_recommend: K = " + std::to_string(topk) + " outside [1, " + std::to_string(PCR_RECOMMEND_MAX_K) + "]"); return PCR_ERR_ARG; }
-    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_recommend: unknown flags"); return PCR_ERR_ARG; }
-    if (!users) n = s->n_users;
-    if (n < 0 || (n > 0 && (!items || !scores))) { pcr_set_error("pcr_recommend: bad argument"); return PCR_ERR_ARG; }
-    return abi_guard("pcr_recommend", [&]() -> int {
-        std::vector<int32_t> loc;
-        RC(shard_rows("pcr_recommend", s, &n, users, loc));
-        return s->recommend(n, users ? loc.data() : nullptr, topk, flags, items, scores);
-    });
-}
-
-int pcr_recommend_diverse(pcr_solver* s, int64_t n, const int32_t* users, int topk, int pool, double theta, int flags, int32_t* items,
-                          double* scores) {
-    S_OR_ARG;
-    RC(pcr_rerank_check("pcr_recommend_diverse", topk, pool, theta));
-    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_recommend_diverse: unknown flags"); return PCR_ERR_ARG; }
-    if (!users) n = s->n_users;
-    if (n < 0 || (n > 0 && (!items || !scores))) { pcr_set_error("pcr_recommend_diverse: bad argument"); return PCR_ERR_ARG; }
-    return abi_guard("pcr_recommend_diverse", [&]() -> int {
-        std::vector<int32_t> loc;
-        RC(shard_rows("pcr_recommend_diverse", s, &n, users, loc));
-        return s->recommend_diverse(n, users ? loc.data() : nullptr, topk, pool, theta, flags, items, scores);
-    });
-}
-
-int pcr_evaluate_topn(pcr_solver* s, int ncut, const int* cutoffs, double threshold, int flags, pcr_topn_stats* stats, double* per_user) {
-    S_OR_ARG;
-    RC(pcr_topn_check("pcr_evaluate_topn", ncut, cutoffs, threshold, stats));
-    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_evaluate_topn: unknown flags"); return PCR_ERR_ARG; }
-    return abi_guard("pcr_evaluate_topn", [&]() -> int { return s->evaluate_topn(ncut, cutoffs, threshold, flags, stats, per_user); });
-}
-
-int pcr_evaluate_ranks(pcr_solver* s, double threshold, int flags, pcr_rank_stats* stats, double* per_user, int64_t* ranks) {
-    S_OR_ARG;
-    if (std::isnan(threshold)) { pcr_set_error("pcr_evaluate_ranks: threshold is NaN"); return PCR_ERR_ARG; }
-    if (!stats) { pcr_set_error("pcr_evaluate_ranks: null stats"); return PCR_ERR_ARG; }
-    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_evaluate_ranks: unknown flags"); return PCR_ERR_ARG; }
-    return abi_guard("pcr_evaluate_ranks", [&]() -> int { return s->evaluate_ranks(threshold, flags, stats, per_user, ranks); });
-}
 
 }  // extern "C"

@@ -26,7 +26,6 @@
 #pragma once
 #include "primalcr.h"
 #include "pcr_prims.h"
-#include "pcr_vside.h"      // PCR_EW_BLOCK
 
 namespace rec {
 constexpr int WAVES = 4;      // waves per workgroup: the four sweep the same items, so three of them read V's rows from L1

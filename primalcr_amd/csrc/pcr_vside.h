@@ -579,8 +579,6 @@ struct CGState {
     int done_at, pad_;     // iteration whose update met the stop test (0: none yet)
 };
 
-#define PCR_EW_BLOCK 256
-
 template <typename T>
 __global__ void k_axpy_out(T* __restrict__ out, const T* __restrict__ a, const T* __restrict__ b, double s, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // out = a + s*b (mat_substract_vec, util.cpp:395)

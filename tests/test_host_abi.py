@@ -274,7 +274,8 @@ def test_tune_table_rejects_unknown_keys_and_reads_no_environment():
         pcr.tune("no_such_knob", 1)
     hdr = open(os.path.join(ROOT, "include", "primalcr.h")).read()
     src_dir = os.path.join(ROOT, "primalcr_amd", "csrc")
-    keys = set(re.findall(r'pcr_tune_(?:int|get)\("([a-z_0-9]+)"', "".join(open(os.path.join(src_dir, f)).read() for f in ("pcr_solver.hip", "pcr_host.cpp"))))
+    srcs = sorted(os.path.join(d, f) for d, _, fs in os.walk(src_dir) for f in fs if f.endswith((".hip", ".h", ".cpp")))   # (headers too)
+    keys = set(re.findall(r'pcr_tune_(?:int|get)\("([a-z_0-9]+)"', "".join(open(f).read() for f in srcs)))
     assert keys, "the solver consults the tune table"
     for k in keys:
         pcr.tune(k, None)                                       # every key the solver reads is a registered key ...

@@ -1,4 +1,4 @@
-"""Top-K recommendation and top-N evaluation across the launch geometries of rec_run (primalcr_amd/csrc/pcr_solver.hip).
+"""Top-K recommendation and top-N evaluation across the launch geometries of rec_run (primalcr_amd/csrc/pcr_serve.hip).
 
 rec_run splits the catalogue across workgroups (1 to 16 item splits, merged by rank counting in k_rec_merge /
 k_rec_merge_topn) and runs the users in batches whose partial lists fit its scratch.  include/primalcr.h promises that a
@@ -23,7 +23,7 @@ from test_recommend import check_real, excl_mask, ref_topk
 from test_topn_eval import check_per_user, check_summary, make_test_csr, ref_metrics
 
 # rec_run's launch arithmetic.  Copied constants: REC_SCRATCH, REC_TARGET_WG, REC_MAX_SPLIT, REC_MIN_SPLIT_ITEMS
-# (pcr_solver.hip) and rec::WAVES * rec::UW users per workgroup, rec::TILE items per step (pcr_topk.h);
+# (pcr_serve.hip) and rec::WAVES * rec::UW users per workgroup, rec::TILE items per step (pcr_topk.h);
 # test_geometry_mirror_matches_the_source keeps them in step.
 REC_SCRATCH = 1 << 30
 REC_TARGET_WG, REC_MAX_SPLIT, REC_MIN_SPLIT_ITEMS = 1024, 16, 1024
@@ -165,7 +165,7 @@ def same_bits(a, b):
 
 # ---------------------------------------------------------------------------------------------------------------- CPU
 def test_geometry_mirror_matches_the_source():
-    src = open(os.path.join(ROOT, "primalcr_amd", "csrc", "pcr_solver.hip")).read()
+    src = open(os.path.join(ROOT, "primalcr_amd", "csrc", "pcr_serve.hip")).read()
     assert re.search(r"REC_SCRATCH = \(size_t\)1 << 30;", src)
     m = re.search(r"REC_TARGET_WG = (\d+), REC_MAX_SPLIT = (\d+), REC_MIN_SPLIT_ITEMS = (\d+);", src)
     assert m and tuple(int(x) for x in m.groups()) == (REC_TARGET_WG, REC_MAX_SPLIT, REC_MIN_SPLIT_ITEMS)
