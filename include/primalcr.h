@@ -605,6 +605,74 @@ int pcr_recommend_diverse_model(const double *U, int64_t d1, const double *V, in
 int pcr_recommend_diverse(pcr_solver *s, int64_t n, const int32_t *users, int topk, int pool, double theta,
                           int flags, int32_t *items, double *scores);                                 /* [device] */
 
+/* ------------------------------------------------------------------------- */
+/* evaluating given and re-ranked lists (no reference counterpart)            */
+/* ------------------------------------------------------------------------- */
+/* The metrics of "full-catalogue top-N evaluation" and of "beyond-accuracy top-N metrics" above, definition for definition,
+ * over lists the caller brings -- a business-rule filter, another model's output, an A/B arm -- instead of lists the library
+ * selects itself: L_u = the given list.  The lists go to the device once; both sets of metrics are reduced there.
+ *   Lists              lists[n][L], 1 <= L <= PCR_RECOMMEND_MAX_K, int32, row i in list order for users[i] (NULL: n == d1 and
+ *                      row i is user i): 0-based item ids, the non-padding entries first, -1 padding only after them, no id
+ *                      twice in a row.  len(u, c) = the number of non-padding entries among the first c.
+ *   Cutoffs            as in the top-N evaluation, with cutoffs[ncut - 1] <= L; positions from the last cutoff on belong to no
+ *                      metric.
+ *   Relevant sets      R_u, the gains and the discounts as in the top-N evaluation, from the test CSR tindex / titem / tval (all
+ *                      three NULL: no accuracy part; then topn and per_user_topn must be NULL, and with a test CSR topn is
+ *                      required).
+ *   Popularity         index / item (the training CSR) give pop[] alone; NULL: pop = 0.  Exclusion is not this entry's
+ *                      business: a listed item that also sits in the user's training row is evaluated as listed.
+ *   Counted users      div counts every requested user; topn counts the requested users with |R_u| >= 1; a user id given twice
+ *                      counts twice in both.
+ *   Determinism        as the two evaluations above: per-user rows depend on (the list, the test row, V) alone and are, on the
+ *                      list pcr_recommend returns, bit for bit those of pcr_evaluate_topn / pcr_evaluate_diversity; the sums
+ *                      over users run in a fixed order (the order of users[]); no floating-point atomics.
+ *   Errors             PCR_ERR_ARG, found on the host before any device is looked for, the message naming the entry: a list
+ *                      entry outside [0, d2) that is not -1, a non-padding entry after a -1, an id twice in one list, L outside
+ *                      [1, PCR_RECOMMEND_MAX_K], a user outside [0, d1), cutoffs[ncut - 1] > L, and the CSR and cutoff errors of
+ *                      pcr_evaluate_topn_model / pcr_evaluate_diversity_model.
+ * topn[ncut], div[ncut]: the summaries.  per_user_topn (optional): [n][ncut][6] as pcr_evaluate_topn's, row i for users[i], all
+ * NaN for an uncounted user.  per_user_div (optional): [n][ncut][PCR_DIVERSITY_FIELDS].  exposure (optional): int64 [ncut][d2].
+ * Profile slot (of the solver entry below): recommend/listmetrics. */
+int pcr_evaluate_lists_model(const double *V, int64_t d2, int64_t k, int64_t d1,
+                             const int64_t *index, const int32_t *item,
+                             const int64_t *tindex, const int32_t *titem, const double *tval,
+                             int64_t n, const int32_t *users, int L, const int32_t *lists,
+                             int ncut, const int *cutoffs, double threshold, int dtype,
+                             pcr_topn_stats *topn, double *per_user_topn,
+                             pcr_diversity_stats *div, double *per_user_div, int64_t *exposure, int device);   /* [device] */
+/* The accuracy / diversity trade-off of the MMR re-ranking: one scoring sweep, then for each of the nth values of theta the
+ * re-ranked lists and their metrics -- no list leaves the device.
+ *   Arguments          topk = cutoffs[ncut - 1] <= pool <= PCR_RECOMMEND_MAX_K; 1 <= nth <= PCR_RERANK_MAX_THETAS; every theta in
+ *                      [0, 1] and not NaN; equal thetas are allowed.
+ *   Lists              for thetas[t] the list of user u is exactly what pcr_recommend_diverse(_model) returns for (topk, pool,
+ *                      thetas[t]) with the same factors, dtype and exclusion; the metrics are those of pcr_evaluate_lists_model
+ *                      on these lists, bit for bit per user.  With thetas[t] == 0 the per-user rows are therefore those of
+ *                      pcr_evaluate_topn / pcr_evaluate_diversity at the same cutoffs.  One result does not depend on which
+ *                      other thetas are in the call.
+ *   Model entry        the test CSR is optional as above; index / item (the training CSR) give exclusion and popularity, as in
+ *                      pcr_evaluate_diversity_model.  Every argument error is PCR_ERR_ARG before any device is looked for.
+ * topn: [nth][ncut] (NULL: no accuracy part), div: [nth][ncut]; per_user_topn [nth][n][ncut][6], per_user_div
+ * [nth][n][ncut][PCR_DIVERSITY_FIELDS] and exposure [nth][ncut][d2] are optional. */
+#define PCR_RERANK_MAX_THETAS 8
+int pcr_evaluate_rerank_model(const double *U, int64_t d1, const double *V, int64_t d2, int64_t k,
+                              const int64_t *index, const int32_t *item,
+                              const int64_t *tindex, const int32_t *titem, const double *tval,
+                              int64_t n, const int32_t *users, int nth, const double *thetas, int pool,
+                              int ncut, const int *cutoffs, double threshold, int dtype,
+                              pcr_topn_stats *topn, pcr_diversity_stats *div,
+                              double *per_user_topn, double *per_user_div, int64_t *exposure, int device);   /* [device] */
+/* On a live PCR, PCR++ or CCDR1 solver: its device factors, storage type and stream, its test ratings (topn NULL: no accuracy
+ * part) and its training ratings (exclusion under PCR_REC_EXCLUDE_TRAIN, popularity always); users[n] are GLOBAL ids of this
+ * rank's shard (NULL: all of them); training state is not touched.  N ranks with an RCCL communicator: pop, exposure and the
+ * sums are all-reduced and every rank returns the totals (every rank must call); on a peer-to-peer communicator the entry is
+ * PCR_ERR_UNSUPPORTED, as pcr_evaluate_diversity; a local-only shard returns its own partials.
+ * Profile slots: recommend/score (once per user batch, whatever nth is), recommend/rerank (the selection, nth times per batch)
+ * and recommend/listmetrics (the row norms, the metrics of the lists, the reductions). */
+int pcr_evaluate_rerank(pcr_solver *s, int64_t n, const int32_t *users, int nth, const double *thetas, int pool,
+                        int ncut, const int *cutoffs, double threshold, int flags,
+                        pcr_topn_stats *topn, pcr_diversity_stats *div,
+                        double *per_user_topn, double *per_user_div, int64_t *exposure);                     /* [device] */
+
 /* per-kernel device timing (HIP events on the solver's stream, one pair per launch).
  * slot names: "<class>/<workgroup size>[.<length bound>][g][c][l][r][#n]" for the per-user kernels (classes
  * prepare, vgrad, vhv, ustep; g = global-scratch variant, c = workgroup clusters, l = k_ustep's latency form (8 rows

@@ -9,8 +9,8 @@ There is no CPU fallback: importing works without a GPU (host-side helpers such 
 and ``initial`` are usable), but every training entry point raises ``PcrError`` when the HIP
 library or a GPU is missing.
 """
-from .api import (PCR_F32, PCR_F64, PCR_REC_EXCLUDE_TRAIN, PCR_RECOMMEND_MAX_K, PCR_TOPN_MAX_CUTOFFS, PCR_SOLVER_CCDR1, PCR_SOLVER_PCR, PCR_SOLVER_PCRPP, CcdParameter, Dataset, Parameter, PcrError,
-                  Solver, comm_unique_id, initial, initial_col, initial_rows, lib, lib_path, use_library, model_load, model_save, partition_users, predict, recommend, recommend_diverse, evaluate_topn, TOPN_FIELDS, evaluate_ranks, RankStats, RANK_FIELDS, evaluate_diversity, DiversityStats, DIVERSITY_FIELDS, exposure_stats, tune, tuned)
+from .api import (PCR_F32, PCR_F64, PCR_REC_EXCLUDE_TRAIN, PCR_RECOMMEND_MAX_K, PCR_TOPN_MAX_CUTOFFS, PCR_RERANK_MAX_THETAS, PCR_SOLVER_CCDR1, PCR_SOLVER_PCR, PCR_SOLVER_PCRPP, CcdParameter, Dataset, Parameter, PcrError,
+                  Solver, comm_unique_id, initial, initial_col, initial_rows, lib, lib_path, use_library, model_load, model_save, partition_users, predict, recommend, recommend_diverse, evaluate_topn, TOPN_FIELDS, evaluate_ranks, RankStats, RANK_FIELDS, evaluate_diversity, DiversityStats, DIVERSITY_FIELDS, exposure_stats, evaluate_lists, evaluate_rerank, tune, tuned)
 
-__all__ = ["PCR_F32", "PCR_F64", "PCR_REC_EXCLUDE_TRAIN", "PCR_RECOMMEND_MAX_K", "PCR_TOPN_MAX_CUTOFFS", "PCR_SOLVER_CCDR1", "PCR_SOLVER_PCR", "PCR_SOLVER_PCRPP", "CcdParameter", "Dataset", "Parameter", "PcrError",
-           "Solver", "comm_unique_id", "initial", "initial_col", "initial_rows", "lib", "lib_path", "use_library", "model_load", "model_save", "partition_users", "predict", "recommend", "recommend_diverse", "evaluate_topn", "TOPN_FIELDS", "evaluate_ranks", "RankStats", "RANK_FIELDS", "evaluate_diversity", "DiversityStats", "DIVERSITY_FIELDS", "exposure_stats", "tune", "tuned"]
+__all__ = ["PCR_F32", "PCR_F64", "PCR_REC_EXCLUDE_TRAIN", "PCR_RECOMMEND_MAX_K", "PCR_TOPN_MAX_CUTOFFS", "PCR_RERANK_MAX_THETAS", "PCR_SOLVER_CCDR1", "PCR_SOLVER_PCR", "PCR_SOLVER_PCRPP", "CcdParameter", "Dataset", "Parameter", "PcrError",
+           "Solver", "comm_unique_id", "initial", "initial_col", "initial_rows", "lib", "lib_path", "use_library", "model_load", "model_save", "partition_users", "predict", "recommend", "recommend_diverse", "evaluate_topn", "TOPN_FIELDS", "evaluate_ranks", "RankStats", "RANK_FIELDS", "evaluate_diversity", "DiversityStats", "DIVERSITY_FIELDS", "exposure_stats", "evaluate_lists", "evaluate_rerank", "tune", "tuned"]

@@ -11,6 +11,7 @@ PCR_F32, PCR_F64 = 0, 1
 PCR_RECOMMEND_MAX_K = 1024
 PCR_REC_EXCLUDE_TRAIN = 1
 PCR_TOPN_MAX_CUTOFFS = 8
+PCR_RERANK_MAX_THETAS = 8
 TOPN_FIELDS = ("hits", "precision", "recall", "ap", "ndcg", "ndcg_graded")   # per_user columns
 RANK_FIELDS = ("first_rank", "rr", "mean_rank", "auc", "mpr")                   # evaluate_ranks' per_user columns (PCR_RANK_FIELDS)
 DIVERSITY_FIELDS = ("len", "novelty", "ild")                                     # evaluate_diversity's per_user columns (PCR_DIVERSITY_FIELDS)
@@ -170,6 +171,9 @@ def lib():
     L.pcr_evaluate_ranks.argtypes = [vp, cd, ci, vp, vp, vp]
     L.pcr_evaluate_diversity_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, vp, ci, vp, ci, vp, vp, vp, ci]
     L.pcr_evaluate_diversity.argtypes = [vp, i64, vp, ci, vp, ci, vp, vp, vp]
+    L.pcr_evaluate_lists_model.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp, ci, vp, ci, vp, cd, ci, vp, vp, vp, vp, vp, ci]
+    L.pcr_evaluate_rerank_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, i64, vp, ci, vp, ci, ci, vp, cd, ci, vp, vp, vp, vp, vp, ci]
+    L.pcr_evaluate_rerank.argtypes = [vp, i64, vp, ci, vp, ci, ci, vp, cd, ci, vp, vp, vp, vp, vp]
     L.pcr_exposure_stats.argtypes = [vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(cd), C.POINTER(cd)]
     L.pcr_profile_enable.argtypes = [vp, ci]
     L.pcr_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(cd), C.POINTER(i64)]
@@ -451,6 +455,148 @@ def evaluate_diversity(U, V, cutoffs=(10,), exclude=None, users=None, dtype=PCR_
     return _diversity_call(cutoffs, per_user, exposure, n, V.shape[0], lambda nc, cp, sp, pp, ep: lib().pcr_evaluate_diversity_model(
         U.ctypes.data, d1, V.ctypes.data, V.shape[0], k, None if idx is None else idx.ctypes.data, None if it is None else it.ctypes.data,
         n, None if users is None else users.ctypes.data, nc, cp, int(dtype), sp, pp, ep, device))
+
+
+def _csr_pair(name, csr, d1, with_val):
+    """A Dataset or an (index, item[, val]) tuple as contiguous arrays of the library's types, shape-checked against d1."""
+    if isinstance(csr, Dataset):
+        idx, it, val = csr.csr(1 if with_val else 0)
+    elif with_val:
+        idx, it, val = csr
+    else:
+        (idx, it), val = csr[:2], None
+    idx = np.ascontiguousarray(idx, np.int64); it = np.ascontiguousarray(it, np.int32)
+    if with_val:
+        val = np.ascontiguousarray(val, np.float64)
+        if idx.shape[0] != d1 + 1 or idx[-1] != it.shape[0] or it.shape[0] != val.shape[0]:
+            raise ValueError(f"{name}: index must have d1 + 1 = {d1 + 1} entries, the last equal to len(item) = len(val)")
+        return idx, it, val
+    if idx.shape[0] != d1 + 1 or idx[-1] != it.shape[0]:
+        raise ValueError(f"{name}: index must have d1 + 1 = {d1 + 1} entries, the last equal to len(item) = {it.shape[0]}")
+    return idx, it
+
+
+def _cutoff_args(cutoffs, longest, what):
+    """The cutoffs of evaluate_lists() / evaluate_rerank() checked as the library checks them; the last one at most `longest`."""
+    cuts = np.ascontiguousarray(np.atleast_1d(np.asarray(cutoffs)), np.int32)
+    if cuts.ndim != 1 or not 1 <= cuts.shape[0] <= PCR_TOPN_MAX_CUTOFFS:
+        raise ValueError(f"cutoffs: 1 .. {PCR_TOPN_MAX_CUTOFFS} values")
+    if cuts[0] < 1 or cuts[-1] > PCR_RECOMMEND_MAX_K or np.any(np.diff(cuts) <= 0):
+        raise ValueError(f"cutoffs must be strictly ascending inside [1, {PCR_RECOMMEND_MAX_K}]")
+    if longest is not None and cuts[-1] > longest:
+        raise ValueError(f"the last cutoff {int(cuts[-1])} is above {what} = {longest}")
+    return cuts
+
+
+def _tradeoff_args(thetas, pool, cutoffs, threshold):
+    """Shared by evaluate_rerank() and Solver.evaluate_rerank(): (thetas, pool, cutoffs, threshold) checked as the library checks
+    them; topk = the last cutoff, pool None = _rerank_args' default."""
+    cuts = _cutoff_args(cutoffs, None, None)
+    th = np.ascontiguousarray(np.atleast_1d(np.asarray(thetas, np.float64)))
+    if th.ndim != 1 or not 1 <= th.shape[0] <= PCR_RERANK_MAX_THETAS:
+        raise ValueError(f"thetas: 1 .. {PCR_RERANK_MAX_THETAS} values")
+    pool = _rerank_args(int(cuts[-1]), pool, 0.0)[1]
+    for t in th:
+        _rerank_args(int(cuts[-1]), pool, t)
+    if np.isnan(threshold):
+        raise ValueError("threshold is NaN")
+    return th, pool, cuts
+
+
+def _lists_result(groups, n, d2, cuts, acc, per_user, exposure, fn):
+    """Shared by evaluate_lists() and the evaluate_rerank()s: fn(topn_ptr, div_ptr, per_user_topn_ptr, per_user_div_ptr,
+    exposure_ptr) -> status fills `groups` sets of outputs.  Returns one dict per group: "diversity" (and, with acc, "topn") the
+    lists of per-cutoff dicts of evaluate_diversity() / evaluate_topn(); with per_user "per_user_diversity" [n, ncut, 3] (and
+    "per_user_topn" [n, ncut, 6], NaN rows for users without a relevant test item); with exposure "exposure" int64 [ncut, d2]."""
+    ncut = int(cuts.shape[0])
+    ts = (TopnStats * (groups * ncut))() if acc else None
+    ds = (DiversityStats * (groups * ncut))()
+    put = np.empty((groups, n, ncut, len(TOPN_FIELDS)), np.float64) if per_user and acc else None
+    pud = np.empty((groups, n, ncut, len(DIVERSITY_FIELDS)), np.float64) if per_user else None
+    ex = np.empty((groups, ncut, d2), np.int64) if exposure else None
+    _chk(fn(None if ts is None else C.cast(ts, C.c_void_p), C.cast(ds, C.c_void_p), *(None if a is None else a.ctypes.data for a in (put, pud, ex))))
+    out = []
+    for g in range(groups):
+        r = {"diversity": [{f: getattr(ds[g * ncut + c], f) for f, _ in DiversityStats._fields_} for c in range(ncut)]}
+        if acc:
+            r["topn"] = [{f: getattr(ts[g * ncut + c], f) for f, _ in TopnStats._fields_} for c in range(ncut)]
+        if put is not None:
+            r["per_user_topn"] = put[g]
+        if pud is not None:
+            r["per_user_diversity"] = pud[g]
+        if ex is not None:
+            r["exposure"] = ex[g]
+        out.append(r)
+    return out
+
+
+def evaluate_lists(lists, V, d1=None, users=None, test=None, popularity=None, cutoffs=(10,), threshold=-np.inf, dtype=PCR_F64, per_user=False,
+                   exposure=False, device=0):
+    """The metrics of evaluate_topn() and evaluate_diversity() over lists the caller brings (pcr_evaluate_lists_model): lists
+    int32 [n, L] in list order, -1 padding only at the end of a row, no item twice in a row; row i is for users[i] (None: n == d1
+    and row i is user i; d1 None: n).  test: a Dataset (its test CSR) or (index, item, val), None: no accuracy part; popularity: a
+    Dataset (its training CSR) or (index, item) for the novelty, None: pop = 0 -- nothing is excluded, the lists are evaluated as
+    given.  The last cutoff is at most L.  Returns a dict: "diversity" and (with test) "topn", the per-cutoff dicts of
+    evaluate_diversity() / evaluate_topn(); with per_user "per_user_diversity" [n, ncut, 3] and "per_user_topn" [n, ncut, 6] (all
+    NaN for a user without a relevant test item); with exposure "exposure" int64 [ncut, d2]."""
+    lists = np.ascontiguousarray(lists, np.int32)
+    if lists.ndim != 2 or not 1 <= lists.shape[1] <= PCR_RECOMMEND_MAX_K:
+        raise ValueError(f"lists must be [n, L] with L in [1, {PCR_RECOMMEND_MAX_K}]")
+    V = np.ascontiguousarray(V, np.float64)
+    n, L = lists.shape
+    d2, k = V.shape
+    d1 = n if d1 is None else int(d1)
+    if users is not None:
+        users = np.ascontiguousarray(users, np.int32)
+        if users.shape != (n,):
+            raise ValueError(f"users must have one id per list ({n})")
+        if n and (users.min() < 0 or users.max() >= d1):
+            raise ValueError(f"a user id is outside [0, d1 = {d1})")
+    elif n != d1:
+        raise ValueError(f"without users there must be d1 = {d1} lists, not {n}")
+    cuts = _cutoff_args(cutoffs, L, "the list length L")
+    if np.isnan(threshold):
+        raise ValueError("threshold is NaN")
+    pad = lists < 0
+    if np.any(lists < -1) or np.any(lists >= d2):
+        raise ValueError(f"a list entry is outside [0, d2 = {d2}) and not -1")
+    if np.any(pad[:, :-1] & ~pad[:, 1:]):
+        raise ValueError("a list has an item after its -1 padding")
+    srt = np.sort(lists, axis=1)
+    if np.any((srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] >= 0)):
+        raise ValueError("a list holds an item twice")
+    t = (None, None, None) if test is None else _csr_pair("test", test, d1, True)
+    p = (None, None) if popularity is None else _csr_pair("popularity", popularity, d1, False)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    return _lists_result(1, n, d2, cuts, test is not None, per_user, exposure, lambda tp, dp, pt, pd, ep: lib().pcr_evaluate_lists_model(
+        V.ctypes.data, d2, k, d1, ptr(p[0]), ptr(p[1]), ptr(t[0]), ptr(t[1]), ptr(t[2]), n, ptr(users), L, lists.ctypes.data,
+        int(cuts.shape[0]), cuts.ctypes.data, float(threshold), int(dtype), tp, pt, dp, pd, ep, device))[0]
+
+
+def evaluate_rerank(U, V, thetas, pool=None, cutoffs=(10,), test=None, exclude=None, users=None, threshold=-np.inf, dtype=PCR_F64,
+                    per_user=False, exposure=False, device=0):
+    """The accuracy / diversity trade-off of recommend_diverse() on the GPU (pcr_evaluate_rerank_model): the catalogue is scored
+    once, then for every theta of `thetas` (at most 8) the lists recommend_diverse(topk = max(cutoffs), pool, theta) returns are
+    selected and evaluated as evaluate_lists() evaluates them; no list leaves the device.  test / exclude / users / dtype as
+    evaluate_topn() and evaluate_diversity() (exclude also gives the popularity; test None: no accuracy part).  Returns one dict
+    per theta, shaped as evaluate_lists()'s, with "theta" added."""
+    th, pool, cuts = _tradeoff_args(thetas, pool, cutoffs, threshold)
+    U = np.ascontiguousarray(U, np.float64); V = np.ascontiguousarray(V, np.float64)
+    d1, k = U.shape
+    t = (None, None, None) if test is None else _csr_pair("test", test, d1, True)
+    x = (None, None) if exclude is None else _csr_pair("exclude", exclude, d1, False)
+    if users is not None:
+        users = np.ascontiguousarray(users, np.int32)
+    n = d1 if users is None else users.shape[0]
+    ptr = lambda a: None if a is None else a.ctypes.data
+    out = _lists_result(int(th.shape[0]), n, V.shape[0], cuts, test is not None, per_user, exposure,
+                        lambda tp, dp, pt, pd, ep: lib().pcr_evaluate_rerank_model(
+                            U.ctypes.data, d1, V.ctypes.data, V.shape[0], k, ptr(x[0]), ptr(x[1]), ptr(t[0]), ptr(t[1]), ptr(t[2]), n, ptr(users),
+                            int(th.shape[0]), th.ctypes.data, pool, int(cuts.shape[0]), cuts.ctypes.data, float(threshold), int(dtype),
+                            tp, dp, pt, pd, ep, device))
+    for r, v in zip(out, th):
+        r["theta"] = float(v)
+    return out
 
 
 def exposure_stats(x):
@@ -784,6 +930,23 @@ class Solver:
         n = self.n_users if users is None else users.shape[0]
         return _diversity_call(cutoffs, per_user, exposure, n, self.d2, lambda nc, cp, sp, pp, ep: lib().pcr_evaluate_diversity(
             self._h, n, None if users is None else users.ctypes.data, nc, cp, PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, sp, pp, ep))
+
+    def evaluate_rerank(self, thetas, pool=None, cutoffs=(10,), users=None, threshold=-np.inf, exclude_train=True, per_user=False,
+                        exposure=False):
+        """The accuracy / diversity trade-off of Solver.recommend_diverse() from the device factors (pcr_evaluate_rerank): one
+        scoring sweep, then per theta the re-ranked lists and their metrics against the solver's test ratings; the result as
+        evaluate_rerank().  users: GLOBAL 0-based ids of this rank's shard (None: all of them, in order).  N ranks with a
+        communicator: the totals of all ranks (every rank must call); local-only shards: their own partials."""
+        th, pool, cuts = _tradeoff_args(thetas, pool, cutoffs, threshold)
+        if users is not None:
+            users = np.ascontiguousarray(users, np.int32)
+        n = self.n_users if users is None else users.shape[0]
+        out = _lists_result(int(th.shape[0]), n, self.d2, cuts, True, per_user, exposure, lambda tp, dp, pt, pd, ep: lib().pcr_evaluate_rerank(
+            self._h, n, None if users is None else users.ctypes.data, int(th.shape[0]), th.ctypes.data, pool, int(cuts.shape[0]),
+            cuts.ctypes.data, float(threshold), PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, tp, dp, pt, pd, ep))
+        for r, v in zip(out, th):
+            r["theta"] = float(v)
+        return out
 
     def sync(self):
         _chk(lib().pcr_solver_sync(self._h))

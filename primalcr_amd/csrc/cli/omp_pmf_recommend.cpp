@@ -20,6 +20,12 @@
 //                    greedily from the user's P best, theta in [0, 1] weighing likeness (cosine of rows of V) against score;
 //                    the output format is that of the plain list; not together with --eval or --diversity
 //     --pool P       the pool of --mmr (default min(1024, 10 K)); refused without --mmr
+//   omp-pmf-recommend --tradeoff t1,t2,... [--pool P] [-K topk] [-c c1,...] [--eval data_dir [--threshold v]] [-x data_dir] [-u users_file] [--f32] model_file
+//     --tradeoff ts  the accuracy / diversity trade-off of --mmr (pcr_evaluate_rerank_model): at most PCR_RERANK_MAX_THETAS thetas
+//                    in [0, 1]; the catalogue is scored once, every theta's lists are re-ranked and evaluated on the device.  The
+//                    lists hold the largest cutoff's items (default -K) out of the user's P best.  For each theta and cutoff
+//                    stdout gets the --eval line (with --eval) and the --diversity line, each prefixed with "theta <t> " (%g).
+//                    Not together with --mmr, --diversity, --ranks, --scores or an output file
 // Output: one line per user, in input order: the 1-based user id, then the 1-based item ids (padding is left out).  Users go
 // to the device in batches, so host memory for the lists stays bounded on any catalogue.
 // With --eval: stdout gets one line per cutoff, "cutoff c users n users_graded n hits n precision x recall x hit_rate x map x
@@ -64,7 +70,11 @@ static const char* USAGE =
     "                   theta in 0 .. 1 (0: the plain list); output as the plain list; not with --eval or --diversity\n"
     "    --pool P       the pool of --mmr, topk .. 1024 (default min(1024, 10 topk)); only with --mmr\n"
     "    output_file    with --eval optional: per counted user at the largest cutoff, hits precision recall ap ndcg ndcg_graded;\n"
-    "                   with --ranks: per counted user first_rank rr mean_rank auc mpr\n";
+    "                   with --ranks: per counted user first_rank rr mean_rank auc mpr\n"
+    "       omp-pmf-recommend --tradeoff t1,t2,... [--pool P] [-K topk] [-c c1,...] [--eval data_dir [--threshold v]] [-x data_dir] [-u users_file] [--f32] model_file\n"
+    "    --tradeoff ts  metrics of the --mmr lists for up to 8 comma-separated thetas in 0 .. 1, one scoring pass: per theta and\n"
+    "                   cutoff the --eval line (with --eval) and the --diversity line, each prefixed with \"theta <t> \";\n"
+    "                   not with --mmr, --diversity, --ranks, --scores or an output file\n";
 
 static int usage() { printf("%s", USAGE); return 1; }
 
@@ -214,6 +224,53 @@ static int run_diversity(const std::vector<double>& U, const std::vector<double>
     return 0;
 }
 
+// "0,0.25,1": 1 .. PCR_RERANK_MAX_THETAS numbers in [0, 1]
+static bool parse_thetas(const char* v, std::vector<double>& out) {
+    const char* p = v;
+    while (true) {
+        char* end = nullptr;
+        const double x = strtod(p, &end);
+        if (end == p || !(x >= 0.0 && x <= 1.0) || (*end != ',' && *end != 0)) return false;
+        out.push_back(x);
+        if ((int)out.size() > PCR_RERANK_MAX_THETAS) return false;
+        if (*end == 0) return true;
+        p = end + 1;
+    }
+}
+
+// --tradeoff: per theta and cutoff the --eval line (edir given) and the --diversity line, each prefixed with "theta <t> "
+static int run_tradeoff(const char* edir, const std::vector<double>& U, const std::vector<double>& V, int64_t d1, int64_t d2, int64_t k,
+                        const std::vector<int64_t>* xindex, const std::vector<int32_t>* xitem, const std::vector<int32_t>& users,
+                        const std::vector<double>& thetas, int pool, const std::vector<int>& cuts, double threshold, bool f32) {
+    std::vector<int64_t> tindex;
+    std::vector<int32_t> titem;
+    std::vector<double> tval;
+    if (edir && !load_csr(edir, 1, d1, d2, tindex, titem, &tval)) return 1;
+    const int nc = (int)cuts.size(), nt = (int)thetas.size();
+    std::vector<pcr_topn_stats> ts((size_t)nt * nc);
+    std::vector<pcr_diversity_stats> ds((size_t)nt * nc);
+    if (pcr_evaluate_rerank_model(U.data(), d1, V.data(), d2, k, xindex ? xindex->data() : nullptr, xitem ? xitem->data() : nullptr,
+                                  edir ? tindex.data() : nullptr, edir ? titem.data() : nullptr, edir ? tval.data() : nullptr,
+                                  (int64_t)users.size(), users.data(), nt, thetas.data(), pool, nc, cuts.data(), threshold,
+                                  f32 ? PCR_F32 : PCR_F64, edir ? ts.data() : nullptr, ds.data(), nullptr, nullptr, nullptr, 0) != PCR_OK) {
+        fprintf(stderr, "tradeoff: %s\n", pcr_last_error());
+        return 1;
+    }
+    for (int t = 0; t < nt; ++t)
+        for (int c = 0; c < nc; ++c) {
+            const pcr_topn_stats& s = ts[(size_t)t * nc + c];
+            const pcr_diversity_stats& d = ds[(size_t)t * nc + c];
+            if (edir)
+                printf("theta %g cutoff %d users %lld users_graded %lld hits %lld precision %g recall %g hit_rate %g map %g ndcg %g ndcg_graded %g\n",
+                       thetas[(size_t)t], s.cutoff, (long long)s.users, (long long)s.users_graded, (long long)s.hits, s.precision, s.recall, s.hit_rate,
+                       s.map, s.ndcg, s.ndcg_graded);
+            printf("theta %g diversity@%d users %lld users_ild %lld recs %lld items_covered %lld coverage %g gini %g novelty %g ild %g\n",
+                   thetas[(size_t)t], d.cutoff, (long long)d.users, (long long)d.users_ild, (long long)d.recs, (long long)d.items_covered, d.coverage,
+                   d.gini, d.novelty, d.ild);
+        }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     int K = 10;
     bool f32 = false, with_scores = false, with_ranks = false, diversity = false;
@@ -222,6 +279,7 @@ int main(int argc, char** argv) {
     double threshold = -INFINITY, theta = 0.0;
     bool mmr = false;
     int pool = 0;
+    std::vector<double> thetas;                                    // --tradeoff
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -247,6 +305,14 @@ int main(int argc, char** argv) {
             theta = strtod(v, &end);
             if (!*v || *end || !(theta >= 0.0 && theta <= 1.0)) { fprintf(stderr, "--mmr %s: must be a number in 0 .. 1\n", v); return 1; }
             mmr = true;
+        } else if (!strcmp(a, "--tradeoff")) {
+            if (i + 1 >= argc) { fprintf(stderr, "--tradeoff needs a value\n"); return usage(); }
+            const char* v = argv[++i];
+            thetas.clear();
+            if (!parse_thetas(v, thetas)) {
+                fprintf(stderr, "--tradeoff %s: must be 1 .. %d numbers in 0 .. 1, separated by commas\n", v, PCR_RERANK_MAX_THETAS);
+                return 1;
+            }
         } else if (!strcmp(a, "--pool")) {
             if (i + 1 >= argc) { fprintf(stderr, "--pool needs a value\n"); return usage(); }
             const char* v = argv[++i];
@@ -271,18 +337,28 @@ int main(int argc, char** argv) {
         else if (a[0] == '-' && a[1]) { fprintf(stderr, "unknown option %s\n", a); return usage(); }
         else pos.push_back(a);
     }
+    const bool tradeoff = !thetas.empty();
+    if (tradeoff) {                                                // (its own rules; the checks below are the other modes')
+        if (mmr || diversity || with_ranks || with_scores) { fprintf(stderr, "--tradeoff does not go with --mmr, --diversity, --ranks or --scores\n"); return 1; }
+        if (pos.size() > 1) { fprintf(stderr, "--tradeoff writes no output file\n"); return 1; }
+        if (pos.empty()) return usage();
+        if (!edir && threshold != -INFINITY) { fprintf(stderr, "--threshold goes with --eval\n"); return 1; }
+        if (cuts.empty()) cuts.push_back(K);
+        if (!pool) pool = std::min(PCR_RECOMMEND_MAX_K, 10 * cuts.back());
+        if (pool < cuts.back()) { fprintf(stderr, "--pool %d: below the largest cutoff %d\n", pool, cuts.back()); return 1; }
+    }
     if (diversity && edir) { fprintf(stderr, "--diversity does not go with --eval\n"); return 1; }
     if (mmr && (edir || diversity)) { fprintf(stderr, "--mmr does not go with --eval or --diversity\n"); return 1; }
-    if (pool && !mmr) { fprintf(stderr, "--pool goes with --mmr\n"); return 1; }
-    if ((edir || diversity) ? (pos.empty() || pos.size() > 2) : pos.size() != 2) return usage();
+    if (pool && !mmr && !tradeoff) { fprintf(stderr, "--pool goes with --mmr\n"); return 1; }
+    if (!tradeoff && ((edir || diversity) ? (pos.empty() || pos.size() > 2) : pos.size() != 2)) return usage();
     if (diversity && (with_scores || with_ranks || threshold != -INFINITY)) { fprintf(stderr, "--scores, --ranks and --threshold do not go with --diversity\n"); return 1; }
-    if (!edir && !diversity && (!cuts.empty() || threshold != -INFINITY)) { fprintf(stderr, "-c and --threshold go with --eval\n"); return 1; }
+    if (!edir && !diversity && !tradeoff && (!cuts.empty() || threshold != -INFINITY)) { fprintf(stderr, "-c and --threshold go with --eval\n"); return 1; }
     if (!edir && with_ranks) { fprintf(stderr, "--ranks goes with --eval\n"); return 1; }
     if (mmr) {
         if (!pool) pool = std::min(PCR_RECOMMEND_MAX_K, 10 * K);
         if (pool < K) { fprintf(stderr, "--pool %d: below -K %d\n", pool, K); return 1; }
     }
-    if (edir && (ufile || with_scores)) { fprintf(stderr, "-u and --scores do not go with --eval\n"); return 1; }
+    if (edir && !tradeoff && (ufile || with_scores)) { fprintf(stderr, "-u and --scores do not go with --eval\n"); return 1; }
     int64_t d1, d2, k;
     if (pcr_model_load(pos[0], &d1, &d2, &k, nullptr, nullptr) != PCR_OK) { fprintf(stderr, "can't open model file %s\n", pos[0]); return 1; }
     std::vector<double> U((size_t)d1 * k), V((size_t)d2 * k);
@@ -293,6 +369,12 @@ int main(int argc, char** argv) {
     std::vector<int64_t> xindex;
     std::vector<int32_t> xitem;
     if (xdir && !load_csr(xdir, 0, d1, d2, xindex, xitem, nullptr)) return 1;
+    if (tradeoff) {
+        const int rc = run_tradeoff(edir, U, V, d1, d2, k, xdir ? &xindex : nullptr, xdir ? &xitem : nullptr, users, thetas, pool, cuts, threshold, f32);
+        if (rc) return rc;
+        fflush(stdout); fflush(stderr);
+        _exit(0);
+    }
     if (diversity) {
         if (cuts.empty()) cuts.push_back(K);
         const int rc = run_diversity(U, V, d1, d2, k, xdir ? &xindex : nullptr, xdir ? &xitem : nullptr, users, cuts, f32,

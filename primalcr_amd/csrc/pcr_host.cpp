@@ -1317,3 +1317,143 @@ int pcr_diversity_stats_from(const double* sums, int ncut, const int* cutoffs, c
     }
     return PCR_OK;
 }
+
+// ------------------------------------------------------------------------------ metrics of given and re-ranked lists (include/primalcr.h)
+int pcr_lists_check(const char* who, int64_t d2, int64_t n, int L, const int32_t* lists) {
+    const int nth = pcr_host_threads();
+    struct Bad { int64_t row = -1; int pos = 0, kind = 0; };   // kind 1: outside [0, d2); 2: an entry after -1; 3: an id twice
+    std::vector<Bad> first((size_t)nth);
+    pcr_parallel_ranges(n, nth, [&](int t, int64_t lo, int64_t hi) {
+        std::vector<int32_t> row;
+        for (int64_t i = lo; i < hi; ++i) {
+            const int32_t* l = lists + (size_t)i * (size_t)L;
+            int len = 0;
+            while (len < L && l[len] != -1) ++len;
+            for (int p = 0; p < L; ++p) {
+                if (l[p] == -1) continue;
+                if (l[p] < 0 || l[p] >= d2) { first[(size_t)t] = Bad{i, p, 1}; return; }
+                if (p > len) { first[(size_t)t] = Bad{i, p, 2}; return; }
+            }
+            row.assign(l, l + len);
+            std::sort(row.begin(), row.end());
+            for (int p = 1; p < len; ++p)
+                if (row[(size_t)p] == row[(size_t)p - 1]) {
+                    int at = 0, seen = 0;
+                    for (int e = 0; e < len; ++e) if (l[e] == row[(size_t)p] && ++seen == 2) { at = e; break; }
+                    first[(size_t)t] = Bad{i, at, 3};
+                    return;
+                }
+        }
+    });
+    for (const Bad& b : first) {
+        if (b.row < 0) continue;
+        const std::string at = "list " + std::to_string(b.row) + ", position " + std::to_string(b.pos);
+        const int32_t id = lists[(size_t)b.row * (size_t)L + (size_t)b.pos];
+        pcr_set_error(std::string(who) + ": " + (b.kind == 1 ? at + ": item " + std::to_string(id) + " outside [0, d2) and not -1"
+                                                 : b.kind == 2 ? at + ": item " + std::to_string(id) + " follows the -1 padding"
+                                                               : at + ": item " + std::to_string(id) + " is in the list twice"));
+        return PCR_ERR_ARG;
+    }
+    return PCR_OK;
+}
+
+// the optional test CSR and the accuracy outputs of the list entries: *has = a test CSR is given
+static int list_outputs_check(const char* who, int64_t d1, int64_t d2, const int64_t* tindex, const int32_t* titem, const double* tval,
+                              const pcr_topn_stats* topn, const double* per_user_topn, bool* has) {
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
+    *has = tindex || titem || tval;
+    if (!*has) {
+        if (topn || per_user_topn) return bad("topn and per_user_topn must be NULL without a test CSR");
+        return PCR_OK;
+    }
+    if (!topn) return bad("null topn stats with a test CSR");
+    return test_csr_check(who, d1, d2, tindex, titem, tval);
+}
+
+int pcr_evaluate_lists_model_check(const double* V, int64_t d2, int64_t k, int64_t d1, const int64_t* index, const int32_t* item,
+                                   const int64_t* tindex, const int32_t* titem, const double* tval, int64_t n, const int32_t* users, int L,
+                                   const int32_t* lists, int ncut, const int* cutoffs, double threshold, int dtype,
+                                   const pcr_topn_stats* topn, const double* per_user_topn, const pcr_diversity_stats* div) {
+    static const char* who = "pcr_evaluate_lists_model";
+    auto bad = [](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
+    if (L < 1 || L > PCR_RECOMMEND_MAX_K) return bad("L = " + std::to_string(L) + " outside [1, " + std::to_string(PCR_RECOMMEND_MAX_K) + "]");
+    int rc = pcr_cutoffs_check(who, ncut, cutoffs);
+    if (rc != PCR_OK) return rc;
+    if (cutoffs[ncut - 1] > L) return bad("cutoff " + std::to_string(cutoffs[ncut - 1]) + " above the list length L = " + std::to_string(L));
+    if (std::isnan(threshold)) return bad("threshold is NaN");
+    if (!div) return bad("null diversity stats");
+    if (!users && n != d1) return bad("n must be d1 without a user list");
+    static const int32_t no_items = 0;         // (nothing is written through these: the output check has nothing to find missing)
+    static const double no_scores = 0.0;
+    rc = pcr_recommend_model_check(V, d1, V, d2, k, index, item, n, users, L, dtype, &no_items, &no_scores, nullptr, who);
+    if (rc != PCR_OK) return rc;
+    bool has = false;
+    rc = list_outputs_check(who, d1, d2, tindex, titem, tval, topn, per_user_topn, &has);
+    if (rc != PCR_OK) return rc;
+    if (n > 0 && !lists) return bad("null lists");
+    return pcr_lists_check(who, d2, n, L, lists);
+}
+
+int pcr_tradeoff_check(const char* who, int nth, const double* thetas, int pool, int ncut, const int* cutoffs, double threshold,
+                       const pcr_diversity_stats* div) {
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
+    int rc = pcr_cutoffs_check(who, ncut, cutoffs);
+    if (rc != PCR_OK) return rc;
+    if (nth < 1 || nth > PCR_RERANK_MAX_THETAS || !thetas)
+        return bad("nth = " + std::to_string(nth) + " outside [1, " + std::to_string(PCR_RERANK_MAX_THETAS) + "] (or no thetas)");
+    for (int t = 0; t < nth; ++t) {
+        rc = pcr_rerank_check(who, cutoffs[ncut - 1], pool, thetas[t]);
+        if (rc != PCR_OK) return rc;
+    }
+    if (std::isnan(threshold)) return bad("threshold is NaN");
+    if (!div) return bad("null diversity stats");
+    return PCR_OK;
+}
+
+int pcr_evaluate_rerank_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
+                                    const int32_t* item, const int64_t* tindex, const int32_t* titem, const double* tval, int64_t n,
+                                    const int32_t* users, int nth, const double* thetas, int pool, int ncut, const int* cutoffs,
+                                    double threshold, int dtype, const pcr_topn_stats* topn, const double* per_user_topn,
+                                    const pcr_diversity_stats* div, bool* sorted) {
+    static const char* who = "pcr_evaluate_rerank_model";
+    int rc = pcr_tradeoff_check(who, nth, thetas, pool, ncut, cutoffs, threshold, div);
+    if (rc != PCR_OK) return rc;
+    static const int32_t no_items = 0;
+    static const double no_scores = 0.0;
+    rc = pcr_recommend_model_check(U, d1, V, d2, k, index, item, n, users, pool, dtype, &no_items, &no_scores, sorted, who);
+    if (rc != PCR_OK) return rc;
+    bool has = false;
+    return list_outputs_check(who, d1, d2, tindex, titem, tval, topn, per_user_topn, &has);
+}
+
+int64_t pcr_list_relevance(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, double threshold, int ncut,
+                           const int* cutoffs, int64_t n, const int32_t* users, int L, PcrTopnRel& out) {
+    PcrTopnRel rel;
+    if (tptr) pcr_topn_relevance(rows, tptr, titem, tval, threshold, ncut, cutoffs, rel);
+    std::vector<int64_t> slot((size_t)rows, -1);       // user -> its row in the compact tables
+    for (size_t i = 0; i < rel.users.size(); ++i) slot[(size_t)rel.users[i]] = (int64_t)i;
+    out.users.clear();
+    out.disc.resize((size_t)L);
+    for (int i = 0; i < L; ++i) out.disc[(size_t)i] = 1.0 / log2((double)(i + 2));
+    out.rptr.assign((size_t)n + 1, 0);
+    int64_t counted = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t s = slot[(size_t)(users ? users[i] : i)];
+        out.rptr[(size_t)i + 1] = out.rptr[(size_t)i] + (s < 0 ? 0 : rel.rptr[(size_t)s + 1] - rel.rptr[(size_t)s]);
+        counted += s >= 0 ? 1 : 0;
+    }
+    out.ritem.resize((size_t)out.rptr[(size_t)n]);
+    out.rgain.resize((size_t)out.rptr[(size_t)n]);
+    out.idcg.assign((size_t)n * (size_t)ncut * 2, 0.0);
+    pcr_parallel_ranges(n, pcr_host_threads(), [&](int, int64_t lo, int64_t hi) {
+        for (int64_t i = lo; i < hi; ++i) {
+            const int64_t s = slot[(size_t)(users ? users[i] : i)];
+            if (s < 0) continue;
+            const int64_t b = rel.rptr[(size_t)s], e = rel.rptr[(size_t)s + 1];
+            std::copy(rel.ritem.begin() + b, rel.ritem.begin() + e, out.ritem.begin() + out.rptr[(size_t)i]);
+            std::copy(rel.rgain.begin() + b, rel.rgain.begin() + e, out.rgain.begin() + out.rptr[(size_t)i]);
+            std::copy(rel.idcg.begin() + s * ncut * 2, rel.idcg.begin() + (s + 1) * ncut * 2, out.idcg.begin() + i * ncut * 2);
+        }
+    });
+    return counted;
+}

@@ -136,3 +136,34 @@ void pcr_rank_stats_from(const double* sums, pcr_rank_stats* stats);
 // tval[z] >= threshold, 0 elsewhere
 void pcr_rank_scatter(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, double threshold,
                       const PcrTopnRel& rel, const int64_t* rrank, int64_t* ranks);
+
+// Metrics of device-resident lists (include/primalcr.h, "evaluating given and re-ranked lists").
+// lists[n][L] as pcr_evaluate_lists_model takes them: every entry -1 or inside [0, d2), no entry after a -1, no id twice in a
+// list; by the host threads.  Errors are prefixed with `who`.
+int pcr_lists_check(const char* who, int64_t d2, int64_t n, int L, const int32_t* lists);
+// pcr_evaluate_lists_model's argument checks (shared with the sanitizer build's stub): L, the cutoffs (the last one <= L), the
+// threshold, the outputs (without a test CSR topn and per_user_topn must be NULL; with one topn is required), the factor / user
+// / popularity-CSR checks of pcr_recommend_model, the test CSR's shape and pcr_lists_check.
+int pcr_evaluate_lists_model_check(const double* V, int64_t d2, int64_t k, int64_t d1, const int64_t* index, const int32_t* item,
+                                   const int64_t* tindex, const int32_t* titem, const double* tval, int64_t n, const int32_t* users, int L,
+                                   const int32_t* lists, int ncut, const int* cutoffs, double threshold, int dtype,
+                                   const pcr_topn_stats* topn, const double* per_user_topn, const pcr_diversity_stats* div);
+// the theta sweep's own arguments: the cutoffs, topk = cutoffs[ncut - 1] <= pool <= PCR_RECOMMEND_MAX_K, 1 <= nth <=
+// PCR_RERANK_MAX_THETAS, every theta in [0, 1] (a NaN is refused), threshold not NaN, div != NULL
+int pcr_tradeoff_check(const char* who, int nth, const double* thetas, int pool, int ncut, const int* cutoffs, double threshold,
+                       const pcr_diversity_stats* div);
+// pcr_evaluate_rerank_model's argument checks (shared with the sanitizer build's stub): pcr_tradeoff_check, the outputs as
+// pcr_evaluate_lists_model_check, the factor / user / exclusion checks of pcr_recommend_model and the test CSR's shape.
+// *sorted as pcr_recommend_model_check.
+int pcr_evaluate_rerank_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
+                                    const int32_t* item, const int64_t* tindex, const int32_t* titem, const double* tval, int64_t n,
+                                    const int32_t* users, int nth, const double* thetas, int pool, int ncut, const int* cutoffs,
+                                    double threshold, int dtype, const pcr_topn_stats* topn, const double* per_user_topn,
+                                    const pcr_diversity_stats* div, bool* sorted);
+// The relevance tables of n requested lists: row i is that of user users[i] (NULL: user i) among rows [0, rows) of the test CSR,
+// possibly empty -- pcr_topn_relevance's tables are compact over the counted users, these have a row for every request (a user
+// given twice has its row twice).  disc has L entries (the list length, which may exceed the last cutoff); idcg is
+// [n][ncut][2], zeros for an empty row.  users, the compact ids of pcr_topn_relevance, is left empty.  Returns the number of
+// requests with a non-empty row (the counted ones).
+int64_t pcr_list_relevance(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, double threshold, int ncut,
+                           const int* cutoffs, int64_t n, const int32_t* users, int L, PcrTopnRel& out);

@@ -1,5 +1,5 @@
 // pcr_serve.hip -- the serving layer behind the C ABI of include/primalcr.h: top-K recommendation, its top-N, rank and
-// beyond-accuracy evaluations and the MMR re-ranking, over the kernels of pcr_topk.h.
+// beyond-accuracy evaluations, the MMR re-ranking and the metrics of given and re-ranked lists, over the kernels of pcr_topk.h.
 //
 // Every entry exists twice: on a trained solver (pcr_recommend, ...) and on a model in host memory (pcr_recommend_model, ...).
 // Both come down to a ServeView (pcr_dev.h) -- filled by the solver (pcr_solver::serve_view) or by ModelDev, which uploads the
@@ -367,6 +367,197 @@ static int rerank_run(const ServeView& v, int64_t n, const int32_t* h_users, int
     return rec_run<T>(v, n, h_users, pool, 1, RecRerank<T>{v, pool, topk, theta, inv.p, shape, items, scores});
 }
 
+// Metrics of device-resident lists (pcr_evaluate_lists_model, pcr_evaluate_rerank; k_list_metrics of pcr_topk.h, DESIGN.md
+// section 3.15): the tables and outputs of one evaluation of `groups` sets of n lists of length L (the caller's lists: one
+// group; the theta sweep: one per theta).  The relevance tables have a row for every request (pcr_list_relevance; acc = false:
+// no accuracy part); the per-item tables are DivDev's; the exposure counters [groups][ncut][d2] are zeroed once per call; the
+// per-user rows dmet / tmet are [groups][n][ncut][6] in the column order k_topn_sum1 reduces.  "recommend/listmetrics" times the
+// row norms, the metric kernel and the reductions.
+struct ListEval {
+    int ncut = 0, groups = 1, L = 0;
+    int cut[PCR_TOPN_MAX_CUTOFFS] = {};
+    int64_t n = 0, d2 = 0, counted = 0;
+    bool acc = false;
+    PcrTopnRel rel;
+    DBuf<int64_t> rptr;
+    DBuf<int32_t> ritem;
+    DBuf<double> rgain, idcg, disc, inv, q, dmet, tmet, part, sums, expod;
+    DBuf<unsigned long long> expo;
+    const double* info = nullptr;
+    static constexpr const char* SLOT = "recommend/listmetrics";
+
+    // h_users: the requests as rows of v's test CSR (NULL: rows 0..n-1)
+    template <typename T>
+    int begin(const ServeView& v, const double* info_, bool acc_, int64_t n_, const int32_t* h_users, int L_, int groups_, int nc,
+              const int* cuts, double thr) {
+        info = info_; acc = acc_; n = n_; L = L_; groups = groups_; ncut = nc; d2 = v.d2;
+        fill_cuts(cut, nc, cuts);
+        const size_t g = (size_t)groups;
+        if (acc) {
+            counted = pcr_list_relevance(v.rows, v.tptr, v.titem, v.tval, thr, nc, cuts, n, h_users, L, rel);
+            RC(rptr.upload(rel.rptr, nullptr)); RC(ritem.upload(rel.ritem, nullptr)); RC(rgain.upload(rel.rgain, nullptr));
+            RC(idcg.upload(rel.idcg, nullptr)); RC(disc.upload(rel.disc, nullptr));
+            RC(tmet.alloc(g * (size_t)n * ncut * 6));
+        }
+        RC(inv.alloc((size_t)d2)); RC(q.alloc((size_t)d2)); RC(expo.alloc(g * ncut * d2)); RC(expod.alloc(g * ncut * d2));
+        RC(dmet.alloc(g * (size_t)n * ncut * 6)); RC(sums.alloc((size_t)ncut * 8 + 1));
+        ProfScope ps(v.prof, SLOT, v.st);
+        HIPCHK(hipMemsetAsync(expo.p, 0, g * ncut * d2 * sizeof(unsigned long long), v.st));
+        hipLaunchKernelGGL((k_div_prepare<T>), dim3((unsigned)cdiv(d2, 4)), dim3(256), 0, v.st, serve_V<T>(v), v.r, v.ld, d2, inv.p, q.p);
+        HIPCHK(hipGetLastError());
+        return PCR_OK;
+    }
+    // the metrics of the m lists dlists[m][L] (device) of group g, requests [b0, b0 + m)
+    template <typename T>
+    int launch(const ServeView& v, int g, int64_t b0, int64_t m, const int32_t* dlists) {
+        const size_t row0 = (size_t)g * (size_t)n + (size_t)b0;
+        DivArgs da;
+        da.inv = inv.p; da.q = q.p; da.info = info; da.expo = expo.p + (size_t)g * ncut * d2; da.out = dmet.p + row0 * ncut * 6;
+        da.d2 = d2; da.ncut = ncut;
+        fill_cuts(da.cut, ncut, cut);
+        TopnArgs ta = {};
+        if (acc) {
+            ta.rptr = rptr.p + b0; ta.ritem = ritem.p; ta.rgain = rgain.p; ta.idcg = idcg.p + (size_t)b0 * ncut * 2;
+            ta.disc = disc.p; ta.out = tmet.p + row0 * ncut * 6;
+        }
+        ta.ncut = ncut;
+        fill_cuts(ta.cut, ncut, cut);
+        ProfScope ps(v.prof, SLOT, v.st);
+        hipLaunchKernelGGL((k_list_metrics<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), (size_t)4 * L * sizeof(int32_t), v.st, dlists, m, L,
+                           serve_V<T>(v), v.r, v.ld, ta, da);
+        HIPCHK(hipGetLastError());
+        return PCR_OK;
+    }
+    // The end of the evaluation: per group met_sums over the n diversity rows (with the cumulative exposure, as div_run) and, with
+    // an accuracy part, over the n accuracy rows -- an uncounted request's row adds nothing to any sum, and the count k_topn_fin
+    // leaves behind (n) is replaced by the counted requests before the exchange.  topn / div are [groups][ncut]; the optional
+    // per_user_topn [groups][n][ncut][6] (NaN for an uncounted request), per_user_div [groups][n][ncut][3], exposure [groups][ncut][d2].
+    int finish(const ServeView& v, const int* cuts, pcr_topn_stats* topn, pcr_diversity_stats* div, double* per_user_topn, double* per_user_div,
+               int64_t* exposure) {
+        hipStream_t st = v.st;
+        const size_t w = (size_t)ncut * 6, rows = (size_t)n * w, ex = (size_t)ncut * d2;
+        std::vector<double> hs((size_t)ncut * 8 + 1), he(ex), hm;
+        const double cnt = (double)counted;
+        for (int g = 0; g < groups; ++g) {
+            const unsigned long long* eg = expo.p + (size_t)g * ex;
+            double* ed = expod.p + (size_t)g * ex;
+            hm.clear();
+            RC(met_sums(v, SLOT, dmet.p + (size_t)g * rows, n, ncut, part, sums.p, hs.data(),
+                        [&]() -> int {
+                            hipLaunchKernelGGL(k_div_expo_finish, dim3((unsigned)cdiv(d2, 256)), dim3(256), 0, st, eg, d2, ncut, ed);
+                            return PCR_OK;
+                        },
+                        [&]() -> int {
+                            RC(v.sum(ed, ex));
+                            HIPCHK(hipMemcpyAsync(he.data(), ed, ex * sizeof(double), hipMemcpyDeviceToHost, st));
+                            if (per_user_div && n > 0) {
+                                hm.resize(rows);
+                                HIPCHK(hipMemcpyAsync(hm.data(), dmet.p + (size_t)g * rows, rows * sizeof(double), hipMemcpyDeviceToHost, st));
+                            }
+                            return PCR_OK;
+                        }));
+            RC(pcr_diversity_stats_from(hs.data(), ncut, cuts, he.data(), d2, div + (size_t)g * ncut, exposure ? exposure + (size_t)g * ex : nullptr));
+            for (size_t i = 0; i < hm.size() / 6; ++i) {       // met: len, novelty (0 when len = 0), -, -, -, ild
+                const double* m = hm.data() + i * 6;
+                double* o = per_user_div + ((size_t)g * (size_t)n * ncut + i) * PCR_DIVERSITY_FIELDS;
+                o[0] = m[0]; o[1] = m[0] > 0.0 ? m[1] : (double)NAN; o[2] = m[5];
+            }
+            if (!acc) continue;
+            hm.clear();
+            RC(met_sums(v, SLOT, tmet.p + (size_t)g * rows, n, ncut, part, sums.p, hs.data(),
+                        [&]() -> int {
+                            HIPCHK(hipMemcpyAsync(sums.p + (size_t)ncut * 8, &cnt, sizeof(double), hipMemcpyHostToDevice, st));
+                            return PCR_OK;
+                        },
+                        [&]() -> int {
+                            if (per_user_topn && n > 0) {
+                                hm.resize(rows);
+                                HIPCHK(hipMemcpyAsync(hm.data(), tmet.p + (size_t)g * rows, rows * sizeof(double), hipMemcpyDeviceToHost, st));
+                            }
+                            return PCR_OK;
+                        }));
+            pcr_topn_stats_from(hs.data(), ncut, cut, topn + (size_t)g * ncut);
+            for (size_t i = 0; i < hm.size() / w; ++i) {
+                double* o = per_user_topn + (size_t)g * rows + i * w;
+                if (rel.rptr[i + 1] > rel.rptr[i]) std::copy(hm.begin() + i * w, hm.begin() + (i + 1) * w, o);
+                else std::fill(o, o + w, (double)NAN);
+            }
+        }
+        return PCR_OK;
+    }
+};
+
+// pcr_evaluate_lists_model: the caller's lists[n][L] go to the device in batches of at most LIST_BATCH entries, each batch
+// through k_list_metrics
+static const int64_t LIST_BATCH = (int64_t)1 << 24;
+template <typename T>
+static int lists_run(const ServeView& v, const double* info, int64_t n, const int32_t* h_users, int L, const int32_t* lists, int ncut,
+                     const int* cuts, double thr, bool acc, pcr_topn_stats* topn, double* per_user_topn, pcr_diversity_stats* div,
+                     double* per_user_div, int64_t* exposure) {
+    ListEval E;
+    RC(E.begin<T>(v, info, acc, n, h_users, L, 1, ncut, cuts, thr));
+    const int64_t nb = std::max<int64_t>(4, LIST_BATCH / L);
+    DBuf<int32_t> dl;
+    RC(dl.alloc((size_t)std::min(nb, n) * L));
+    for (int64_t b0 = 0; b0 < n; b0 += nb) {
+        const int64_t m = std::min(nb, n - b0);
+        HIPCHK(hipMemcpyAsync(dl.p, lists + (size_t)b0 * L, (size_t)m * L * sizeof(int32_t), hipMemcpyHostToDevice, v.st));
+        RC(E.launch<T>(v, 0, b0, m, dl.p));
+        HIPCHK(hipStreamSynchronize(v.st));                // (the next batch overwrites dl)
+    }
+    return E.finish(v, cuts, topn, div, per_user_topn, per_user_div, exposure);
+}
+
+// rec_run's sink for the theta sweep (pcr_evaluate_rerank): per theta the merge + greedy selection (k_rec_merge_mmr, exactly
+// RecRerank's launch) into the device lists oi [nb][topk], then their metrics (k_list_metrics) into group t of E.  The score
+// kernel has run once for the batch, whatever nth is.
+template <typename T>
+struct RecTradeoff {
+    const ServeView& v;
+    int K, topk, nth;
+    const double* thetas;
+    MmrShape shape;
+    ListEval& E;
+    DBuf<int32_t> oi;
+    DBuf<double> os;
+    int begin(int64_t nb) { RC(oi.alloc((size_t)nb * topk)); RC(os.alloc((size_t)nb * topk)); return PCR_OK; }
+    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp) {
+        hipStream_t st = v.st; const T* V = serve_V<T>(v);
+        const int r = v.r, ld = v.ld;
+        for (int t = 0; t < nth; ++t) {
+            MmrArgs ma;
+            ma.inv = E.inv.p; ma.out_i = oi.p; ma.out_s = os.p; ma.topk = topk; ma.theta = thetas[t];
+            {
+                ProfScope ps(v.prof, "recommend/rerank", st);
+                const dim3 grid((unsigned)cdiv(m, shape.waves)), block(64 * shape.waves);
+                if (shape.form) hipLaunchKernelGGL((k_rec_merge_mmr<T, 1>), grid, block, shape.lds, st, ls, li, ln, nsp, m, K, V, r, ld, ma);
+                else hipLaunchKernelGGL((k_rec_merge_mmr<T, 0>), grid, block, shape.lds, st, ls, li, ln, nsp, m, K, V, r, ld, ma);
+                HIPCHK(hipGetLastError());
+            }
+            RC(E.launch<T>(v, t, b0, m, oi.p));
+        }
+        return PCR_OK;
+    }
+};
+
+// The sweep over the n users h_users (rows of U, of the exclusion CSR and of the test CSR, as rec_run; NULL: rows 0..n-1): the
+// row norms and the tables once (ListEval::begin), one rec_run with K = pool and RecTradeoff, the reductions per theta.
+// pcr_tune("rerank_lds") is read at every call, as rerank_run does.
+template <typename T>
+static int tradeoff_run(const char* who, const ServeView& v, const double* info, int64_t n, const int32_t* h_users, int nth, const double* thetas,
+                        int pool, int ncut, const int* cuts, double thr, bool acc, pcr_topn_stats* topn, pcr_diversity_stats* div,
+                        double* per_user_topn, double* per_user_div, int64_t* exposure) {
+    const int topk = cuts[ncut - 1];
+    const MmrShape shape = mmr_shape<T>(pool, v.ld, pcr_tune_int("rerank_lds", 0));
+    if (shape.waves < 1) { pcr_set_error(std::string(who) + ": rank " + std::to_string(v.r) + " is too large for the re-ranking kernel's LDS"); return PCR_ERR_UNSUPPORTED; }
+    if (shape.form) HIPCHK(hipFuncSetAttribute((const void*)k_rec_merge_mmr<T, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds));
+    else HIPCHK(hipFuncSetAttribute((const void*)k_rec_merge_mmr<T, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds));
+    ListEval E;
+    RC(E.begin<T>(v, info, acc, n, h_users, topk, nth, ncut, cuts, thr));
+    RC(rec_run<T>(v, n, h_users, pool, 1, RecTradeoff<T>{v, pool, topk, nth, thetas, shape, E, {}, {}}));
+    return E.finish(v, cuts, topn, div, per_user_topn, per_user_div, exposure);
+}
+
 // Exact rank metrics (pcr_evaluate_ranks, pcr_topk.h): the relevance table of a threshold on the device (PcrTopnRel's users,
 // rptr and ritem; uploaded once per threshold) and the outputs: rrank[nrel] the ranks of ritem entry for entry, met[n][6]
 // k_rank_finish's rows, the reduced sums [8] + the count
@@ -505,16 +696,20 @@ static int serve_ranks(const ServeView& v, RankDev& D, double thr, pcr_rank_stat
 // beyond-accuracy metrics of v's rows; the self-information table comes from the training ratings (summed across the ranks with
 // a communicator) and is kept in info: the ratings never change, the exchange mode can (info_mode 0: not built, 1: from this
 // shard's ratings alone, 2: all-reduced)
-static int serve_diversity(const ServeView& v, DBuf<double>& info, int& info_mode, int64_t n, const int32_t* rows, int ncut, const int* cuts,
-                           pcr_diversity_stats* stats, double* per_user, int64_t* exposure) {
+static int div_info_ready(const char* who, const ServeView& v, DBuf<double>& info, int& info_mode) {
     // (the peer-to-peer communicator's fp64 exchange is its 64-double scalar slot: the d2-sized tables do not fit it)
-    if (v.exchange == SERVE_P2P) { pcr_set_error("pcr_evaluate_diversity: not available on a peer-to-peer communicator (use RCCL, or local-only shards and pcr_exposure_stats)"); return PCR_ERR_UNSUPPORTED; }
+    if (v.exchange == SERVE_P2P) { pcr_set_error(std::string(who) + ": not available on a peer-to-peer communicator (use RCCL, or local-only shards and pcr_exposure_stats)"); return PCR_ERR_UNSUPPORTED; }
     const int mode = v.exchange == SERVE_LOCAL ? 1 : 2;
     if (info_mode != mode) {
         info_mode = 0;
         RC(div_info_build(v, info));
         info_mode = mode;
     }
+    return PCR_OK;
+}
+static int serve_diversity(const ServeView& v, DBuf<double>& info, int& info_mode, int64_t n, const int32_t* rows, int ncut, const int* cuts,
+                           pcr_diversity_stats* stats, double* per_user, int64_t* exposure) {
+    RC(div_info_ready("pcr_evaluate_diversity", v, info, info_mode));
     return by_precision(v, [&](auto zero) -> int { return div_run<decltype(zero)>(v, info.p, n, rows, ncut, cuts, stats, per_user, exposure); });
 }
 
@@ -557,10 +752,11 @@ struct ModelDev {
         }
         const int ld = ((int)k + 3) & ~3;
         const size_t row = (size_t)ld * (dtype == PCR_F64 ? sizeof(double) : sizeof(float));
-        RC(F.alloc((size_t)(d1 + d2) * row));
-        char* dV = F.p + (size_t)d1 * row;
-        if (dtype == PCR_F64) RC(upload_rows<double>(v->st, (int)k, ld, {{U, d1, (double*)F.p}, {V, d2, (double*)dV}}));
-        else RC(upload_rows<float>(v->st, (int)k, ld, {{U, d1, (float*)F.p}, {V, d2, (float*)dV}}));
+        const int64_t ur = U ? d1 : 0;             // (U NULL: pcr_evaluate_lists_model scores nothing and brings no user factors)
+        RC(F.alloc((size_t)(ur + d2) * row));
+        char* dV = F.p + (size_t)ur * row;
+        if (dtype == PCR_F64) RC(upload_rows<double>(v->st, (int)k, ld, {{U, ur, (double*)F.p}, {V, d2, (double*)dV}}));
+        else RC(upload_rows<float>(v->st, (int)k, ld, {{U, ur, (float*)F.p}, {V, d2, (float*)dV}}));
         v->dtype = dtype; v->U = F.p; v->V = dV; v->r = (int)k; v->ld = ld; v->rows = v->d1 = d1; v->d2 = d2;
         v->uptr = dx.p; v->item = di.p; v->nnz = index ? index[d1] : 0;
         return PCR_OK;
@@ -605,6 +801,26 @@ int pcr_evaluate_diversity(pcr_solver* s, int64_t n, const int32_t* users, int n
         RC(shard_rows("pcr_evaluate_diversity", s, &n, users, loc));
         return serve_diversity(solver_view(s, flags), s->serve->div_info, s->serve->div_info_mode, n, users ? loc.data() : nullptr, ncut, cutoffs,
                                stats, per_user, exposure);
+    });
+}
+
+int pcr_evaluate_rerank(pcr_solver* s, int64_t n, const int32_t* users, int nth, const double* thetas, int pool, int ncut, const int* cutoffs,
+                        double threshold, int flags, pcr_topn_stats* topn, pcr_diversity_stats* div, double* per_user_topn, double* per_user_div,
+                        int64_t* exposure) {
+    S_OR_ARG;
+    RC(pcr_tradeoff_check("pcr_evaluate_rerank", nth, thetas, pool, ncut, cutoffs, threshold, div));
+    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_evaluate_rerank: unknown flags"); return PCR_ERR_ARG; }
+    if (users && n < 0) { pcr_set_error("pcr_evaluate_rerank: bad argument"); return PCR_ERR_ARG; }
+    if (!topn && per_user_topn) { pcr_set_error("pcr_evaluate_rerank: per_user_topn must be NULL without topn"); return PCR_ERR_ARG; }
+    return abi_guard("pcr_evaluate_rerank", [&]() -> int {
+        std::vector<int32_t> loc;
+        RC(shard_rows("pcr_evaluate_rerank", s, &n, users, loc));
+        const ServeView v = solver_view(s, flags);
+        RC(div_info_ready("pcr_evaluate_rerank", v, s->serve->div_info, s->serve->div_info_mode));
+        return by_precision(v, [&](auto zero) -> int {
+            return tradeoff_run<decltype(zero)>("pcr_evaluate_rerank", v, s->serve->div_info.p, n, users ? loc.data() : nullptr, nth, thetas, pool,
+                                                ncut, cutoffs, threshold, topn != nullptr, topn, div, per_user_topn, per_user_div, exposure);
+        });
     });
 }
 
@@ -722,6 +938,49 @@ int pcr_recommend_diverse_model(const double* U, int64_t d1, const double* V, in
     ServeView v; ModelDev M;
     RC(M.open(U, d1, V, d2, k, index, item, sorted, dtype, &v));
     return serve_recommend_diverse(v, n, users, topk, pool, theta, items, scores);
+    });
+}
+
+int pcr_evaluate_lists_model(const double* V, int64_t d2, int64_t k, int64_t d1, const int64_t* index, const int32_t* item, const int64_t* tindex,
+                             const int32_t* titem, const double* tval, int64_t n, const int32_t* users, int L, const int32_t* lists, int ncut,
+                             const int* cutoffs, double threshold, int dtype, pcr_topn_stats* topn, double* per_user_topn,
+                             pcr_diversity_stats* div, double* per_user_div, int64_t* exposure, int device) {
+    return abi_guard("pcr_evaluate_lists_model", [&]() -> int {
+    RC(pcr_evaluate_lists_model_check(V, d2, k, d1, index, item, tindex, titem, tval, n, users, L, lists, ncut, cutoffs, threshold, dtype, topn,
+                                      per_user_topn, div));
+    RC(model_device(device));
+    ServeView v;
+    v.tptr = tindex; v.titem = titem; v.tval = tval;
+    ModelDev M;                                            // (the training CSR counts popularity alone: its rows need no order)
+    RC(M.open(nullptr, d1, V, d2, k, index, item, true, dtype, &v));
+    DBuf<double> info; int info_mode = 0;
+    RC(div_info_ready("pcr_evaluate_lists_model", v, info, info_mode));
+    return by_precision(v, [&](auto zero) -> int {
+        return lists_run<decltype(zero)>(v, info.p, n, users, L, lists, ncut, cutoffs, threshold, tindex != nullptr, topn, per_user_topn, div,
+                                         per_user_div, exposure);
+    });
+    });
+}
+
+int pcr_evaluate_rerank_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                              const int64_t* tindex, const int32_t* titem, const double* tval, int64_t n, const int32_t* users, int nth,
+                              const double* thetas, int pool, int ncut, const int* cutoffs, double threshold, int dtype, pcr_topn_stats* topn,
+                              pcr_diversity_stats* div, double* per_user_topn, double* per_user_div, int64_t* exposure, int device) {
+    return abi_guard("pcr_evaluate_rerank_model", [&]() -> int {
+    bool sorted = true;
+    RC(pcr_evaluate_rerank_model_check(U, d1, V, d2, k, index, item, tindex, titem, tval, n, users, nth, thetas, pool, ncut, cutoffs, threshold,
+                                       dtype, topn, per_user_topn, div, &sorted));
+    RC(model_device(device));
+    ServeView v;
+    v.tptr = tindex; v.titem = titem; v.tval = tval;
+    ModelDev M;
+    RC(M.open(U, d1, V, d2, k, index, item, sorted, dtype, &v));
+    DBuf<double> info; int info_mode = 0;
+    RC(div_info_ready("pcr_evaluate_rerank_model", v, info, info_mode));
+    return by_precision(v, [&](auto zero) -> int {
+        return tradeoff_run<decltype(zero)>("pcr_evaluate_rerank_model", v, info.p, n, users, nth, thetas, pool, ncut, cutoffs, threshold,
+                                            tindex != nullptr, topn, div, per_user_topn, per_user_div, exposure);
+    });
     });
 }
 

@@ -21,6 +21,8 @@
 //   section 3.12): the same sweep with a counting tail in place of the selecting one, at the end of this file.
 // k_rec_merge_div / k_rec_merge_mmr: the same merge with the beyond-accuracy metrics (section 3.13) or the greedy MMR re-ranking
 //   (pcr_recommend_diverse, section 3.14) fused into its tail, further down in this file.
+// k_list_metrics: the two metric tails over a list that is already in device memory (pcr_evaluate_lists_model, and the theta sweep
+//   pcr_evaluate_rerank, which runs it on k_rec_merge_mmr's output; section 3.15), below k_rec_merge_div.
 // No atomic decides a result: the LDS slot counter only decides where a candidate sits in the buffer, and the merges rank by
 // the total order (score, id), so every list is the same whatever the order of arrival.
 #pragma once
@@ -293,17 +295,8 @@ struct TopnArgs {
 // looked up in the user's relevant row by binary search (its slot replaces the id in LDS, -1 if not relevant); a wave
 // exclusive scan of the lanes' hit counts gives every hit its hits_{<=i}; the per-cutoff sums are reduced by wave_sum's fixed
 // butterfly.
-template <typename T>
-__global__ __launch_bounds__(256) void k_rec_merge_topn(const T* __restrict__ lst_s, const int32_t* __restrict__ lst_i,
-                                                        const int32_t* __restrict__ lst_n, int nsplit, int64_t n, int K, TopnArgs ta) {
-    extern __shared__ int32_t rec_lst[];
-    const int lane = threadIdx.x & 63;
-    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (idx >= n) return;
-    int32_t* sl = rec_lst + (size_t)(threadIdx.x >> 6) * (size_t)K;
-    const int tot = rec_merge_ranks(lst_s, lst_i, lst_n, nsplit, n, K, idx, lane, [&](int rk, int j, T) { sl[rk] = j; });
-    for (int p = min(tot, K) + lane; p < K; p += 64) sl[p] = -1;
-    wave_sync();
+// (the tail is rec_topn_tail, shared with k_list_metrics)
+__device__ __forceinline__ void rec_topn_tail(int32_t* sl, int K, int64_t idx, int lane, const TopnArgs& ta) {
     const int64_t rb = ta.rptr[idx], nr = ta.rptr[idx + 1] - rb;
     const int32_t* ri = ta.ritem + rb;
     const int P = (K + 63) >> 6, p0 = min(K, lane * P), p1 = min(K, p0 + P);
@@ -353,6 +346,19 @@ __global__ __launch_bounds__(256) void k_rec_merge_topn(const T* __restrict__ ls
         }
     }
     if (lane < 6 * ta.ncut) ta.out[(size_t)idx * 6 * ta.ncut + lane] = v;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_rec_merge_topn(const T* __restrict__ lst_s, const int32_t* __restrict__ lst_i,
+                                                        const int32_t* __restrict__ lst_n, int nsplit, int64_t n, int K, TopnArgs ta) {
+    extern __shared__ int32_t rec_lst[];
+    const int lane = threadIdx.x & 63;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (idx >= n) return;
+    int32_t* sl = rec_lst + (size_t)(threadIdx.x >> 6) * (size_t)K;
+    const int tot = rec_merge_ranks(lst_s, lst_i, lst_n, nsplit, n, K, idx, lane, [&](int rk, int j, T) { sl[rk] = j; });
+    for (int p = min(tot, K) + lane; p < K; p += 64) sl[p] = -1;
+    wave_sync();
+    rec_topn_tail(sl, K, idx, lane, ta);
 }
 
 // Top-N evaluation's sums over users (fixed order, as k_sum4_stage1 / k_fin4): block x of cutoff y = blockIdx.y sums rows
@@ -672,18 +678,10 @@ __global__ __launch_bounds__(256) void k_div_expo_finish(const unsigned long lon
 //              rows are loaded before the first is used.  Ranks wider than 64 DIV_CH re-walk the list per component chunk (the
 //              squared norm is a sum over components).  Lane c keeps cutoff c's |S|^2.
 // Every value of a user depends on its list and on V alone.
+// (the tail is rec_div_tail, shared with k_list_metrics: the list is sl[0, L), no padding inside, L <= the last cutoff)
 template <typename T>
-__global__ __launch_bounds__(256) void k_rec_merge_div(const T* __restrict__ lst_s, const int32_t* __restrict__ lst_i,
-                                                       const int32_t* __restrict__ lst_n, int nsplit, int64_t n, int K,
-                                                       const T* __restrict__ V, int r, int ld, DivArgs da) {
-    extern __shared__ int32_t rec_lst[];
-    const int lane = threadIdx.x & 63;
-    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (idx >= n) return;
-    int32_t* sl = rec_lst + (size_t)(threadIdx.x >> 6) * (size_t)K;
-    const int tot = rec_merge_ranks(lst_s, lst_i, lst_n, nsplit, n, K, idx, lane, [&](int rk, int j, T) { sl[rk] = j; });
-    const int L = __builtin_amdgcn_readfirstlane(min(tot, K));      // the list is sl[0, L): no padding inside
-    wave_sync();
+__device__ __forceinline__ void rec_div_tail(const int32_t* sl, int L, int64_t idx, int lane, const T* __restrict__ V, int r, int ld,
+                                             const DivArgs& da) {
     double nov[PCR_TOPN_MAX_CUTOFFS], qs[PCR_TOPN_MAX_CUTOFFS];
 #pragma unroll
     for (int c = 0; c < PCR_TOPN_MAX_CUTOFFS; ++c) { nov[c] = 0.0; qs[c] = 0.0; }
@@ -749,6 +747,56 @@ __global__ __launch_bounds__(256) void k_rec_merge_div(const T* __restrict__ lst
     const int myc = lane / 6, myf = lane - 6 * myc;
     const double f0 = __shfl(dl, myc), f1 = __shfl(novelty, myc), f5 = __shfl(ild, myc);
     if (lane < 6 * da.ncut) da.out[(size_t)idx * 6 * da.ncut + lane] = myf == 0 ? f0 : myf == 1 ? f1 : myf == 5 ? f5 : 0.0;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_rec_merge_div(const T* __restrict__ lst_s, const int32_t* __restrict__ lst_i,
+                                                       const int32_t* __restrict__ lst_n, int nsplit, int64_t n, int K,
+                                                       const T* __restrict__ V, int r, int ld, DivArgs da) {
+    extern __shared__ int32_t rec_lst[];
+    const int lane = threadIdx.x & 63;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (idx >= n) return;
+    int32_t* sl = rec_lst + (size_t)(threadIdx.x >> 6) * (size_t)K;
+    const int tot = rec_merge_ranks(lst_s, lst_i, lst_n, nsplit, n, K, idx, lane, [&](int rk, int j, T) { sl[rk] = j; });
+    const int L = __builtin_amdgcn_readfirstlane(min(tot, K));      // the list is sl[0, L): no padding inside
+    wave_sync();
+    rec_div_tail<T>(sl, L, idx, lane, V, r, ld, da);
+}
+
+// Both tails over a list that is already in device memory (pcr_evaluate_lists_model, pcr_evaluate_rerank; DESIGN.md section
+// 3.15), one wave per list, four lists per workgroup: lists[m][L] in list order, the non-padding entries first and -1 padding
+// only after them (checked on the host, or written so by k_rec_merge_mmr).  The wave stages its list in LDS (4 L ints of dynamic
+// LDS per workgroup) and runs rec_div_tail over its first min(len, last cutoff) entries -- positions past the last cutoff
+// belong to no metric -- and then, when ta.rptr is given, rec_topn_tail over all L positions (the tail replaces the ids in LDS,
+// so it comes second).  A user with an empty relevant row gets the row that adds nothing to k_topn_sum1's sums: zeros, with
+// ndcg_graded NaN; the host counts it out.  The arithmetic is that of k_rec_merge_topn / k_rec_merge_div on the same list, bit
+// for bit.
+template <typename T>
+__global__ __launch_bounds__(256) void k_list_metrics(const int32_t* __restrict__ lists, int64_t m, int L, const T* __restrict__ V, int r,
+                                                      int ld, TopnArgs ta, DivArgs da) {
+    extern __shared__ int32_t rec_lst[];
+    const int lane = threadIdx.x & 63;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (idx >= m) return;
+    int32_t* sl = rec_lst + (size_t)(threadIdx.x >> 6) * (size_t)L;
+    const int32_t* gl = lists + (size_t)idx * (size_t)L;
+    int len = 0;
+    for (int p0 = 0; p0 < L; p0 += 64) {                            // (wave-uniform trip count)
+        const int p = p0 + lane;
+        const int j = p < L ? gl[p] : -1;
+        if (p < L) sl[p] = j;
+        len += __popcll(__ballot(j >= 0));
+    }
+    len = __builtin_amdgcn_readfirstlane(min(len, da.cut[da.ncut - 1]));
+    wave_sync();
+    rec_div_tail<T>(sl, len, idx, lane, V, r, ld, da);
+    if (!ta.rptr) return;                                            // (wave-uniform)
+    if (ta.rptr[idx + 1] == ta.rptr[idx]) {
+        if (lane < 6 * ta.ncut) ta.out[(size_t)idx * 6 * ta.ncut + lane] = (lane % 6) == 5 ? (double)NAN : 0.0;
+        return;
+    }
+    wave_sync();
+    rec_topn_tail(sl, L, idx, lane, ta);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------

@@ -97,4 +97,22 @@ int pcr_recommend_diverse_model(const double* U, int64_t d1, const double* V, in
     return rc != PCR_OK ? rc : absent();
 }
 NO_SOLVER(pcr_recommend_diverse, pcr_solver*, int64_t, const int32_t*, int, int, double, int, int32_t*, double*)
+int pcr_evaluate_lists_model(const double* V, int64_t d2, int64_t k, int64_t d1, const int64_t* index, const int32_t* item, const int64_t* tindex,
+                             const int32_t* titem, const double* tval, int64_t n, const int32_t* users, int L, const int32_t* lists, int ncut,
+                             const int* cutoffs, double threshold, int dtype, pcr_topn_stats* topn, double* per_user_topn,
+                             pcr_diversity_stats* div, double*, int64_t*, int) {
+    const int rc = pcr_evaluate_lists_model_check(V, d2, k, d1, index, item, tindex, titem, tval, n, users, L, lists, ncut, cutoffs, threshold,
+                                                  dtype, topn, per_user_topn, div);
+    return rc != PCR_OK ? rc : absent();
+}
+int pcr_evaluate_rerank_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                              const int64_t* tindex, const int32_t* titem, const double* tval, int64_t n, const int32_t* users, int nth,
+                              const double* thetas, int pool, int ncut, const int* cutoffs, double threshold, int dtype, pcr_topn_stats* topn,
+                              pcr_diversity_stats* div, double* per_user_topn, double*, int64_t*, int) {
+    const int rc = pcr_evaluate_rerank_model_check(U, d1, V, d2, k, index, item, tindex, titem, tval, n, users, nth, thetas, pool, ncut, cutoffs,
+                                                   threshold, dtype, topn, per_user_topn, div, nullptr);
+    return rc != PCR_OK ? rc : absent();
+}
+NO_SOLVER(pcr_evaluate_rerank, pcr_solver*, int64_t, const int32_t*, int, const double*, int, int, const int*, double, int, pcr_topn_stats*,
+          pcr_diversity_stats*, double*, double*, int64_t*)
 }
