@@ -673,6 +673,71 @@ int pcr_evaluate_rerank(pcr_solver *s, int64_t n, const int32_t *users, int nth,
                         pcr_topn_stats *topn, pcr_diversity_stats *div,
                         double *per_user_topn, double *per_user_div, int64_t *exposure);                     /* [device] */
 
+/* ------------------------------------------------------------------------- */
+/* fold-in: factors for users the model was not trained on (no reference      */
+/* counterpart: the reference can only retrain)                               */
+/* ------------------------------------------------------------------------- */
+/* Given a handful of ratings of each of n new users, their rows of U are found on the device with V fixed: per user,
+ * lambda/2 |u|^2 + sum over the user's comparable pairs of hinge^2 is strictly convex in u, and one workgroup runs the user's
+ * whole optimisation -- up to `steps` Newton steps, each a gradient, a truncated CG and a line search -- in one launch
+ * (k_foldin).  Each user is independent.  Starting from u = U0[i] rounded to the storage type, a step does:
+ *   1 State at u       m = V_I u in the storage type, sorted by (level, m); loss and prev_obj = lambda/2 |u|^2 + loss.  Levels as
+ *                      in training (lround buckets for PrimalCR++, the dense rank of the raw double for PrimalCR; the windows
+ *                      strict for PrimalCR, inclusive for PrimalCR++).
+ *   2 End test         the gradient g and gn2 = |g|^2.  The user ends CONVERGED, u unchanged, when it has no rating, when
+ *                      gn2 < 1e-4 (the reference's absolute threshold, pcrpp.cpp:787), or when the solver is PrimalCR and the
+ *                      user has fewer than two levels (pcr.cpp:552).
+ *   3 Newton step      exactly update_u_new (pcrpp.cpp:779-815) / update_u (pcr.cpp:523-585): CG from delta = 0, at most
+ *                      cg_max_iter iterations, tolerance cg_tol |g|; the line search from stepsize, halving, at most 20
+ *                      evaluations under strict <, each with fresh scores and a fresh sort.
+ *   4 Accepted try     u becomes that point ROUNDED TO THE STORAGE TYPE (as the training loop stores it); one more step taken.
+ *   5 No try accepted  the user ends STALLED and u IS LEFT AS IT WAS BEFORE THIS STEP.  This departs on purpose from the training
+ *                      loop, which moves to the last tried point: a serving call never returns a point worse
+ *                      than the one it was given, and never spends another 20 sorts on a user at its noise floor (long users
+ *                      often cannot reach the absolute threshold of 2).
+ *   6 Step cap         after `steps` accepted steps the user ends STEP_CAP.
+ *   Inputs             index[n + 1] / item / val: the new users' ratings as a CSR over the model's items.  Rows need not be
+ *                      item-ascending (a sorted copy is made: sums run in ascending item order); the same item twice in a row
+ *                      is two ratings, as in training.  U0 [n][k] (NULL: zeros).  steps >= 1.
+ *   Outputs            U_out [n][k]: the storage-type values widened.  per_user (optional) [n][PCR_FOLDIN_FIELDS] = steps taken,
+ *                      CG iterations, line-search evaluations, obj = lambda/2 |u|^2 + loss at the returned u, gnorm2 = |g|^2 at
+ *                      the last point where the gradient was evaluated (the returned u for CONVERGED, else the start of the last
+ *                      step), status.  stats (optional): the counts and sums over the users; obj is added in user order.
+ *   Determinism        a user's row and statistics depend on its ratings, V and the parameters alone -- not on the other users,
+ *                      its position, batches or the launch grid: the workgroup form is chosen by the user's length, every sum
+ *                      has a fixed order, no atomics touch results, nothing is exchanged between workgroups and every loop has
+ *                      a static bound.  Two identical calls are bitwise identical.
+ *   Errors             PCR_ERR_ARG before any device is looked for, the message naming the entry: an item id outside [0, d2), a
+ *                      rating that is not finite, index[0] != 0 or a non-monotone index, steps < 1, a null V / U_out, a solver
+ *                      type other than 0, 1, 2.  Whatever the level builder refuses (a user with more than 65535 levels) is
+ *                      PCR_ERR_UNSUPPORTED, as is solver type 0: the squared-loss fold-in of CCDR1 is a ridge solve, not this.
+ * Workgroup forms by user length (a user's form never depends on the call): one wave up to PCR_FOLDIN_WAVE_MAX ratings; 256
+ * threads with the per-rating arrays in LDS up to PCR_FOLDIN_LDS_MAX; 512 threads with them in global scratch beyond.  Every
+ * pass gathers the user's rows of V from L2. */
+#define PCR_FOLDIN_FIELDS 6
+#define PCR_FOLDIN_CONVERGED 0
+#define PCR_FOLDIN_STEP_CAP  1
+#define PCR_FOLDIN_STALLED   2
+#define PCR_FOLDIN_WAVE_MAX  64
+#define PCR_FOLDIN_LDS_MAX   2048
+typedef struct pcr_foldin_stats {
+    int64_t users, converged, step_cap, stalled;
+    int64_t steps, cg, ls;
+    double  obj;
+} pcr_foldin_stats;
+/* Standalone: V (d2 x k) host fp64 in model-file layout; k, lambda, solver_type, stepsize, cg_max_iter, cg_tol, precision and
+ * device are read from p. */
+int pcr_fold_in_model(const pcr_params *p, const double *V, int64_t d2, int64_t n,
+                      const int64_t *index, const int32_t *item, const double *val,
+                      const double *U0, int steps, double *U_out,
+                      pcr_foldin_stats *stats, double *per_user);                                  /* [device] */
+/* On a live PCR or PCR++ solver: its device V, storage type and parameters, on its stream (a CCDR1 solver: PCR_ERR_STATE).  V is
+ * replicated on every rank, so the call is local: nothing is exchanged and any rank may call it alone.  The solver's factors and
+ * training state are not touched.  Profile slot: foldin/newton. */
+int pcr_fold_in(pcr_solver *s, int64_t n, const int64_t *index, const int32_t *item, const double *val,
+                const double *U0, int steps, double *U_out,
+                pcr_foldin_stats *stats, double *per_user);                                        /* [device] */
+
 /* per-kernel device timing (HIP events on the solver's stream, one pair per launch).
  * slot names: "<class>/<workgroup size>[.<length bound>][g][c][l][r][#n]" for the per-user kernels (classes
  * prepare, vgrad, vhv, ustep; g = global-scratch variant, c = workgroup clusters, l = k_ustep's latency form (8 rows

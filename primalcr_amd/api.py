@@ -15,6 +15,11 @@ PCR_RERANK_MAX_THETAS = 8
 TOPN_FIELDS = ("hits", "precision", "recall", "ap", "ndcg", "ndcg_graded")   # per_user columns
 RANK_FIELDS = ("first_rank", "rr", "mean_rank", "auc", "mpr")                   # evaluate_ranks' per_user columns (PCR_RANK_FIELDS)
 DIVERSITY_FIELDS = ("len", "novelty", "ild")                                     # evaluate_diversity's per_user columns (PCR_DIVERSITY_FIELDS)
+PCR_FOLDIN_FIELDS = ("steps", "cg", "ls", "obj", "gnorm2", "status")             # fold_in's per_user columns
+PCR_FOLDIN_CONVERGED, PCR_FOLDIN_STEP_CAP, PCR_FOLDIN_STALLED = 0, 1, 2          # ... and its status values
+# fold_in's workgroup forms by user length (include/primalcr.h): one wave up to WAVE_MAX ratings, per-rating arrays in LDS up to
+# LDS_MAX, global scratch beyond
+PCR_FOLDIN_WAVE_MAX, PCR_FOLDIN_LDS_MAX = 64, 2048
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -89,6 +94,12 @@ class RankStats(C.Structure):
     """pcr_rank_stats."""
     _fields_ = [("users", C.c_int64), ("users_auc", C.c_int64), ("relevant", C.c_int64), ("mrr", C.c_double), ("mean_rank", C.c_double),
                 ("auc", C.c_double), ("mpr", C.c_double)]
+
+
+class FoldinStats(C.Structure):
+    """pcr_foldin_stats."""
+    _fields_ = [("users", C.c_int64), ("converged", C.c_int64), ("step_cap", C.c_int64), ("stalled", C.c_int64), ("steps", C.c_int64),
+                ("cg", C.c_int64), ("ls", C.c_int64), ("obj", C.c_double)]
 
 
 _LOG_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p)
@@ -174,6 +185,8 @@ def lib():
     L.pcr_evaluate_lists_model.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp, ci, vp, ci, vp, cd, ci, vp, vp, vp, vp, vp, ci]
     L.pcr_evaluate_rerank_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, i64, vp, ci, vp, ci, ci, vp, cd, ci, vp, vp, vp, vp, vp, ci]
     L.pcr_evaluate_rerank.argtypes = [vp, i64, vp, ci, vp, ci, ci, vp, cd, ci, vp, vp, vp, vp, vp]
+    L.pcr_fold_in_model.argtypes = [C.POINTER(Parameter), vp, i64, i64, vp, vp, vp, vp, ci, vp, vp, vp]
+    L.pcr_fold_in.argtypes = [vp, i64, vp, vp, vp, vp, ci, vp, vp, vp]
     L.pcr_exposure_stats.argtypes = [vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(cd), C.POINTER(cd)]
     L.pcr_profile_enable.argtypes = [vp, ci]
     L.pcr_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(cd), C.POINTER(i64)]
@@ -599,6 +612,70 @@ def evaluate_rerank(U, V, thetas, pool=None, cutoffs=(10,), test=None, exclude=N
     return out
 
 
+def foldin_boundaries(k=None, dtype=PCR_F64):
+    """The user lengths L at which fold_in() changes its code path between L and L + 1 ratings: the bounds of its workgroup
+    forms (the same for every rank and storage type)."""
+    return [PCR_FOLDIN_WAVE_MAX, PCR_FOLDIN_LDS_MAX]
+
+
+def _foldin_ratings(ratings):
+    """(index int64, item int32, val float64) of fold_in's `ratings`: a Dataset (its training CSR) or an (index, item, val) tuple."""
+    index, item, val = ratings.csr(0) if isinstance(ratings, Dataset) else ratings
+    index = np.ascontiguousarray(index, np.int64); item = np.ascontiguousarray(item, np.int32); val = np.ascontiguousarray(val, np.float64)
+    if index.ndim != 1 or index.shape[0] < 1 or item.shape != val.shape or item.ndim != 1:
+        raise ValueError("ratings: (index[n + 1], item[nnz], val[nnz])")
+    if index[-1] != item.shape[0]:
+        raise ValueError(f"ratings: the last index entry must equal len(item) = {item.shape[0]}")
+    return index, item, val
+
+
+def _foldin_call(n, k, U0, per_user, fn):
+    """Shared by fold_in() and Solver.fold_in(): the U0 / output buffers around fn(U0 pointer, U_out pointer, stats pointer,
+    per_user pointer); returns (U_new, stats dict[, per_user])."""
+    if U0 is not None:
+        U0 = np.ascontiguousarray(U0, np.float64)
+        if U0.shape != (n, k):
+            raise ValueError(f"U0 must be [n, k] = [{n}, {k}]")
+    out = np.empty((n, k), np.float64)
+    st = FoldinStats()
+    pu = np.empty((n, len(PCR_FOLDIN_FIELDS)), np.float64) if per_user else None
+    _chk(fn(None if U0 is None else U0.ctypes.data, out.ctypes.data, C.addressof(st), None if pu is None else pu.ctypes.data))
+    stats = {f: getattr(st, f) for f, _ in FoldinStats._fields_}
+    return (out, stats, pu) if per_user else (out, stats)
+
+
+def fold_in(V, ratings, lam, solver_type=PCR_SOLVER_PCRPP, U0=None, steps=10, stepsize=1.0, cg_max_iter=None, cg_tol=None, dtype=PCR_F64,
+            device=0, per_user=False):
+    """Factors for users the model was not trained on, on the GPU (pcr_fold_in_model): with V fixed, each user's
+    lambda/2 |u|^2 + pairwise squared hinge loss is minimised by up to `steps` Newton steps (CG + line search) from U0 (None:
+    zeros); a user stops early when its gradient is below the reference's threshold (CONVERGED) or when no line-search try
+    improves it (STALLED: u stays where it was).  ratings: a Dataset (its training CSR) or an (index, item, val) tuple over V's
+    items.  Returns (U_new float64 [n, k], stats dict[, per_user float64 [n, 6] of PCR_FOLDIN_FIELDS])."""
+    V = np.ascontiguousarray(V, np.float64)
+    if V.ndim != 2:
+        raise ValueError("V must be [d2, k]")
+    index, item, val = _foldin_ratings(ratings)
+    n, k = index.shape[0] - 1, V.shape[1]
+    p = Parameter(solver_type=int(solver_type), k=k, stepsize=float(stepsize), precision=int(dtype), device=int(device), **{"lambda": float(lam)})
+    if cg_max_iter is not None:
+        p.cg_max_iter = int(cg_max_iter)
+    if cg_tol is not None:
+        p.cg_tol = float(cg_tol)
+    return _foldin_call(n, k, U0, per_user, lambda u0, uo, sp, pp: lib().pcr_fold_in_model(
+        C.byref(p), V.ctypes.data, V.shape[0], n, index.ctypes.data, item.ctypes.data, val.ctypes.data, u0, int(steps), uo, sp, pp))
+
+
+def recommend_new_users(V, ratings, lam, topk, solver_type=PCR_SOLVER_PCRPP, U0=None, steps=10, stepsize=1.0, cg_max_iter=None, cg_tol=None,
+                        dtype=PCR_F64, device=0):
+    """Top-K lists for users the model was not trained on: fold_in(), then recommend(U_new, V, topk, exclude=ratings) -- the
+    ratings the users were folded in on are left out.  Returns (items, scores, U_new, stats)."""
+    index, item, val = _foldin_ratings(ratings)
+    U_new, stats = fold_in(V, (index, item, val), lam, solver_type=solver_type, U0=U0, steps=steps, stepsize=stepsize, cg_max_iter=cg_max_iter,
+                           cg_tol=cg_tol, dtype=dtype, device=device)
+    items, scores = recommend(U_new, V, topk, exclude=(index, item), dtype=dtype, device=device)
+    return items, scores, U_new, stats
+
+
 def exposure_stats(x):
     """The closing arithmetic of one exposure row (pcr_exposure_stats): dict(recs, items_covered, coverage, gini)."""
     x = np.ascontiguousarray(x, np.int64)
@@ -947,6 +1024,15 @@ class Solver:
         for r, v in zip(out, th):
             r["theta"] = float(v)
         return out
+
+    def fold_in(self, ratings, U0=None, steps=10, per_user=False):
+        """Factors for users this solver was not trained on, against its device V (pcr_fold_in), in its storage type and with its
+        parameters (lambda, solver type, stepsize, CG knobs); arguments and result as fold_in().  Local to the rank; the
+        solver's factors and training state are not touched."""
+        index, item, val = _foldin_ratings(ratings)
+        n = index.shape[0] - 1
+        return _foldin_call(n, self.k, U0, per_user, lambda u0, uo, sp, pp: lib().pcr_fold_in(
+            self._h, n, index.ctypes.data, item.ctypes.data, val.ctypes.data, u0, int(steps), uo, sp, pp))
 
     def sync(self):
         _chk(lib().pcr_solver_sync(self._h))

@@ -26,6 +26,18 @@
 //                    lists hold the largest cutoff's items (default -K) out of the user's P best.  For each theta and cutoff
 //                    stdout gets the --eval line (with --eval) and the --diversity line, each prefixed with "theta <t> " (%g).
 //                    Not together with --mmr, --diversity, --ranks, --scores or an output file
+//   omp-pmf-recommend --fold-in data_dir -l lambda [-s 1|2] [--steps S] [-K topk] [--f32] [--scores] model_file output_file
+//   omp-pmf-recommend --fold-in data_dir -l lambda [-s 1|2] [--steps S] --eval data_dir [-c ...] [--threshold v] [--f32] model_file [output_file]
+//     --fold-in dir  lists for users the model was not trained on (pcr_fold_in_model): the users are the rows of the data
+//                    directory's training file (its d2 must equal the model's, its d1 is free); their factors are found on the
+//                    device against the model's V and their ratings are left out of the lists.  stdout gets one line "foldin users n
+//                    converged n step_cap n stalled n steps n cg n ls n obj x" (%g), then the lists go to output_file in the plain
+//                    format (pcr_recommend_model on the new factors).  With --eval the folded-in users are scored against that
+//                    directory's test ratings instead (strong generalisation: held-out users, folded in on their training part,
+//                    evaluated on their test part) and the --eval lines follow.  Not together with -x, -u, --diversity, --mmr,
+//                    --tradeoff or --ranks
+//     -l lambda      the regulariser the model was trained with (required with --fold-in)
+//     -s 1|2         1 = PrimalCR, 2 = PrimalCR++ (default) levels and windows;  --steps S: at most S Newton steps per user (default 10)
 // Output: one line per user, in input order: the 1-based user id, then the 1-based item ids (padding is left out).  Users go
 // to the device in batches, so host memory for the lists stays bounded on any catalogue.
 // With --eval: stdout gets one line per cutoff, "cutoff c users n users_graded n hits n precision x recall x hit_rate x map x
@@ -74,7 +86,15 @@ static const char* USAGE =
     "       omp-pmf-recommend --tradeoff t1,t2,... [--pool P] [-K topk] [-c c1,...] [--eval data_dir [--threshold v]] [-x data_dir] [-u users_file] [--f32] model_file\n"
     "    --tradeoff ts  metrics of the --mmr lists for up to 8 comma-separated thetas in 0 .. 1, one scoring pass: per theta and\n"
     "                   cutoff the --eval line (with --eval) and the --diversity line, each prefixed with \"theta <t> \";\n"
-    "                   not with --mmr, --diversity, --ranks, --scores or an output file\n";
+    "                   not with --mmr, --diversity, --ranks, --scores or an output file\n"
+    "       omp-pmf-recommend --fold-in data_dir -l lambda [-s 1|2] [--steps S] [-K topk] [--f32] [--scores] model_file output_file\n"
+    "       omp-pmf-recommend --fold-in data_dir -l lambda [-s 1|2] [--steps S] --eval data_dir [-c ...] [--threshold v] [--f32] model_file [output_file]\n"
+    "    --fold-in dir  lists for new users: the rows of this data directory's training file (same items as the model, any number\n"
+    "                   of users) are folded into the model on the device, their ratings are left out of the lists; stdout gets a\n"
+    "                   \"foldin users n converged n step_cap n stalled n steps n cg n ls n obj x\" line; with --eval the new users\n"
+    "                   are scored against that directory's test ratings; not with -x, -u, --diversity, --mmr, --tradeoff or --ranks\n"
+    "    -l lambda      the regulariser of the model (required with --fold-in)\n"
+    "    -s 1|2         1 = PrimalCR, 2 = PrimalCR++ (default);  --steps S  at most S Newton steps per user (default 10)\n";
 
 static int usage() { printf("%s", USAGE); return 1; }
 
@@ -271,6 +291,40 @@ static int run_tradeoff(const char* edir, const std::vector<double>& U, const st
     return 0;
 }
 
+// --fold-in: the training CSR of a data directory over the model's items (any number of users) and, from it, the new users'
+// factors (pcr_fold_in_model); the summary line goes to stdout
+static bool run_fold_in(const char* dir, const std::vector<double>& V, int64_t d2, int64_t k, double lambda, int solver, int steps, bool f32,
+                        int64_t* n_out, std::vector<int64_t>& index, std::vector<int32_t>& item, std::vector<double>& U_new) {
+    pcr_dataset* ds = nullptr;
+    if (pcr_dataset_load_mt(dir, 0, &ds) != PCR_OK) { fprintf(stderr, "%s\n", pcr_last_error()); return false; }
+    int64_t n, xd2, nnz, tnnz;
+    pcr_dataset_dims(ds, &n, &xd2, &nnz, &tnnz);
+    if (xd2 != d2) {
+        fprintf(stderr, "data set %s has %lld items, the model %lld\n", dir, (long long)xd2, (long long)d2);
+        pcr_dataset_free(ds);
+        return false;
+    }
+    index.resize((size_t)n + 1);
+    std::vector<int64_t> it64((size_t)nnz);
+    std::vector<double> val((size_t)nnz);
+    pcr_dataset_csr(ds, 0, index.data(), it64.data(), val.data());
+    pcr_dataset_free(ds);
+    item.assign(it64.begin(), it64.end());
+    pcr_params p;
+    pcr_params_default(&p);
+    p.solver_type = solver; p.k = (int)k; p.lambda = lambda; p.precision = f32 ? PCR_F32 : PCR_F64;
+    U_new.resize((size_t)n * k);
+    pcr_foldin_stats st;
+    if (pcr_fold_in_model(&p, V.data(), d2, n, index.data(), item.data(), val.data(), nullptr, steps, U_new.data(), &st, nullptr) != PCR_OK) {
+        fprintf(stderr, "fold-in: %s\n", pcr_last_error());
+        return false;
+    }
+    printf("foldin users %lld converged %lld step_cap %lld stalled %lld steps %lld cg %lld ls %lld obj %g\n", (long long)st.users, (long long)st.converged,
+           (long long)st.step_cap, (long long)st.stalled, (long long)st.steps, (long long)st.cg, (long long)st.ls, st.obj);
+    *n_out = n;
+    return true;
+}
+
 int main(int argc, char** argv) {
     int K = 10;
     bool f32 = false, with_scores = false, with_ranks = false, diversity = false;
@@ -281,8 +335,32 @@ int main(int argc, char** argv) {
     int pool = 0;
     std::vector<double> thetas;                                    // --tradeoff
     std::vector<const char*> pos;
+    const char* fdir = nullptr;                                    // --fold-in
+    double lambda = 0.0;
+    bool have_lambda = false, have_s = false, have_steps = false;
+    int solver = PCR_SOLVER_PCRPP, steps = 10;
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
+        if (!strcmp(a, "--fold-in") || !strcmp(a, "-l") || !strcmp(a, "-s") || !strcmp(a, "--steps")) {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
+            const char* v = argv[++i];
+            char* end = nullptr;
+            if (!strcmp(a, "--fold-in")) fdir = v;
+            else if (a[1] == 'l') {
+                lambda = strtod(v, &end);
+                if (!*v || *end || !(lambda == lambda) || std::isinf(lambda)) { fprintf(stderr, "-l %s: must be a number\n", v); return 1; }
+                have_lambda = true;
+            } else if (a[1] == 's') {
+                const long x = strtol(v, &end, 10);
+                if (!*v || *end || (x != 1 && x != 2)) { fprintf(stderr, "-s %s: must be 1 (PrimalCR) or 2 (PrimalCR++)\n", v); return 1; }
+                solver = (int)x; have_s = true;
+            } else {
+                const long x = strtol(v, &end, 10);
+                if (!*v || *end || x < 1 || x > 1000000) { fprintf(stderr, "--steps %s: must be an integer >= 1\n", v); return 1; }
+                steps = (int)x; have_steps = true;
+            }
+            continue;
+        }
         if (!strcmp(a, "--eval") || !strcmp(a, "-c") || !strcmp(a, "--threshold")) {
             if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
             const char* v = argv[++i];
@@ -338,6 +416,10 @@ int main(int argc, char** argv) {
         else pos.push_back(a);
     }
     const bool tradeoff = !thetas.empty();
+    if (fdir) {
+        if (xdir || ufile || diversity || mmr || tradeoff || with_ranks) { fprintf(stderr, "--fold-in does not go with -x, -u, --diversity, --mmr, --tradeoff or --ranks\n"); return 1; }
+        if (!have_lambda) { fprintf(stderr, "--fold-in needs -l lambda\n"); return 1; }
+    } else if (have_lambda || have_s || have_steps) { fprintf(stderr, "-l, -s and --steps go with --fold-in\n"); return 1; }
     if (tradeoff) {                                                // (its own rules; the checks below are the other modes')
         if (mmr || diversity || with_ranks || with_scores) { fprintf(stderr, "--tradeoff does not go with --mmr, --diversity, --ranks or --scores\n"); return 1; }
         if (pos.size() > 1) { fprintf(stderr, "--tradeoff writes no output file\n"); return 1; }
@@ -369,6 +451,14 @@ int main(int argc, char** argv) {
     std::vector<int64_t> xindex;
     std::vector<int32_t> xitem;
     if (xdir && !load_csr(xdir, 0, d1, d2, xindex, xitem, nullptr)) return 1;
+    if (fdir) {                                                    // the new users take the model's users' place: their factors, their ratings excluded
+        std::vector<double> U_new;
+        if (!run_fold_in(fdir, V, d2, k, lambda, solver, steps, f32, &d1, xindex, xitem, U_new)) return 1;
+        U.swap(U_new);
+        users.resize((size_t)d1);
+        for (int64_t u = 0; u < d1; ++u) users[(size_t)u] = (int32_t)u;
+        xdir = fdir;
+    }
     if (tradeoff) {
         const int rc = run_tradeoff(edir, U, V, d1, d2, k, xdir ? &xindex : nullptr, xdir ? &xitem : nullptr, users, thetas, pool, cuts, threshold, f32);
         if (rc) return rc;

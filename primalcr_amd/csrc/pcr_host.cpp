@@ -1457,3 +1457,98 @@ int64_t pcr_list_relevance(int64_t rows, const int64_t* tptr, const int32_t* tit
     });
     return counted;
 }
+
+// ------------------------------------------------------------------------------------------
+// fold-in (include/primalcr.h, "fold-in"): argument checks and the host-side plan
+// ------------------------------------------------------------------------------------------
+int pcr_fold_in_check(const char* who, int solver_type, int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val,
+                      int steps, const double* U_out, PcrFoldinPlan* plan) {
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
+    if (solver_type == PCR_SOLVER_CCDR1) {
+        pcr_set_error(std::string(who) + ": solver type 0 (CCDR1) is not supported: its squared-loss fold-in is a ridge solve");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    if (solver_type != PCR_SOLVER_PCR && solver_type != PCR_SOLVER_PCRPP) return bad("wrong solver type (" + std::to_string(solver_type) + "): 1 = PrimalCR, 2 = PrimalCR++");
+    if (n < 0 || d2 < 1 || !index) return bad("bad argument");
+    if (d2 >= ((int64_t)1 << 31) - 64) return bad("more than 2^31 items");
+    if (n >= ((int64_t)1 << 31) - 64) return bad("more than 2^31 users in one call");
+    if (steps < 1) return bad("steps = " + std::to_string(steps) + " must be at least 1");
+    if (n > 0 && !U_out) return bad("null output");
+    if (index[0] != 0) return bad("index[0] must be 0");
+    for (int64_t u = 0; u < n; ++u) {
+        if (index[u + 1] < index[u]) return bad("index not monotone at user " + std::to_string(u));
+        if (index[u + 1] - index[u] > ((int64_t)1 << 30)) return bad("user " + std::to_string(u) + " has more than 2^30 ratings");
+    }
+    const int64_t nnz = index[n];
+    if (nnz > 0 && (!item || !val)) return bad("null item / val");
+    const int nth = pcr_host_threads();
+    std::vector<int> st((size_t)nth, 0);       // bit 0: an item outside [0, d2); bit 1: a rating that is not finite; bit 2: a row not item-ascending
+    pcr_parallel_ranges(n, nth, [&](int t, int64_t lo, int64_t hi) {
+        for (int64_t u = lo; u < hi; ++u)
+            for (int64_t z = index[u]; z < index[u + 1]; ++z) {
+                if (item[z] < 0 || item[z] >= d2) st[(size_t)t] |= 1;
+                if (!std::isfinite(val[z])) st[(size_t)t] |= 2;
+                if (z > index[u] && item[z] < item[z - 1]) st[(size_t)t] |= 4;
+            }
+    });
+    int all = 0;
+    for (int x : st) all |= x;
+    if (all & 1) return bad("an item id is outside [0, d2)");
+    if (all & 2) return bad("a rating is not finite");
+    PcrFoldinPlan local;
+    PcrFoldinPlan& P = plan ? *plan : local;
+    P.X.d1 = n; P.X.d2 = d2;
+    P.X.index.assign(index, index + n + 1);
+    P.X.item.assign(item, item + nnz);
+    P.X.val.assign(val, val + nnz);
+    if (all & 4)                               // rows in ascending item order (equal items keep their order), the ratings with them
+        pcr_parallel_ranges(n, nth, [&](int, int64_t lo, int64_t hi) {
+            std::vector<int64_t> perm;
+            for (int64_t u = lo; u < hi; ++u) {
+                const int64_t a = index[u], len = index[u + 1] - a;
+                perm.resize((size_t)len);
+                for (int64_t q = 0; q < len; ++q) perm[(size_t)q] = a + q;
+                std::stable_sort(perm.begin(), perm.end(), [&](int64_t x, int64_t y) { return item[x] < item[y]; });
+                for (int64_t q = 0; q < len; ++q) { P.X.item[(size_t)(a + q)] = item[perm[(size_t)q]]; P.X.val[(size_t)(a + q)] = val[perm[(size_t)q]]; }
+            }
+        });
+    std::string err;
+    const int rc = pcr_build_levels(P.X, 0, n, solver_type, P.lv, err);
+    if (rc != PCR_OK) { pcr_set_error(std::string(who) + ": " + err); return rc; }
+    // users by descending length (equal lengths by ascending id): the longest start first; the three workgroup forms are ranges
+    P.order.resize((size_t)n);
+    for (int64_t u = 0; u < n; ++u) P.order[(size_t)u] = (int32_t)u;
+    std::stable_sort(P.order.begin(), P.order.end(), [&](int32_t x, int32_t y) { return index[x + 1] - index[x] > index[y + 1] - index[y]; });
+    P.n_big = P.n_lds = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t len = index[P.order[(size_t)i] + 1] - index[P.order[(size_t)i]];
+        if (len > PCR_FOLDIN_LDS_MAX) P.n_big += 1;
+        else if (len > PCR_FOLDIN_WAVE_MAX) P.n_lds += 1;
+    }
+    return PCR_OK;
+}
+
+int pcr_fold_in_model_check(const pcr_params* p, const double* V, int64_t d2, int64_t n, const int64_t* index, const int32_t* item,
+                            const double* val, int steps, const double* U_out, PcrFoldinPlan* plan) {
+    auto bad = [](const std::string& why) { pcr_set_error("pcr_fold_in_model: " + why); return PCR_ERR_ARG; };
+    if (!p) return bad("null parameters");
+    if (!V) return bad("null V");
+    if (p->k < 1) return bad("rank k must be >= 1");
+    if (p->precision != PCR_F32 && p->precision != PCR_F64) return bad("precision must be PCR_F32 or PCR_F64");
+    if (!std::isfinite(p->lambda) || !std::isfinite(p->stepsize) || !std::isfinite(p->cg_tol)) return bad("lambda, stepsize and cg_tol must be finite");
+    if (p->cg_max_iter < 0) return bad("cg_max_iter must not be negative");
+    return pcr_fold_in_check("pcr_fold_in_model", p->solver_type, d2, n, index, item, val, steps, U_out, plan);
+}
+
+void pcr_foldin_stats_from(const double* per_user, int64_t n, pcr_foldin_stats* stats) {
+    pcr_foldin_stats s = {};
+    s.users = n;
+    for (int64_t u = 0; u < n; ++u) {
+        const double* o = per_user + (size_t)u * PCR_FOLDIN_FIELDS;
+        s.steps += (int64_t)o[0]; s.cg += (int64_t)o[1]; s.ls += (int64_t)o[2];
+        s.obj += o[3];
+        const int status = (int)o[5];
+        if (status == PCR_FOLDIN_CONVERGED) s.converged += 1; else if (status == PCR_FOLDIN_STEP_CAP) s.step_cap += 1; else s.stalled += 1;
+    }
+    *stats = s;
+}

@@ -167,3 +167,23 @@ int pcr_evaluate_rerank_model_check(const double* U, int64_t d1, const double* V
 // requests with a non-empty row (the counted ones).
 int64_t pcr_list_relevance(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, double threshold, int ncut,
                            const int* cutoffs, int64_t n, const int32_t* users, int L, PcrTopnRel& out);
+
+// Fold-in (include/primalcr.h, "fold-in").  What the host prepares for k_foldin: the new users' ratings with item-ascending rows
+// (a sorted copy when the caller's are not), their levels (pcr_build_levels) and the users by descending length -- order[0, n_big)
+// take the global-scratch form, the next n_lds the LDS form, the rest one wave each.
+struct PcrFoldinPlan {
+    PcrCsr X;
+    PcrLevels lv;
+    std::vector<int32_t> order;
+    int64_t n_big = 0, n_lds = 0;
+};
+// The argument checks of both entries (the library and the sanitizer build's "no device" stubs run the same ones): solver type
+// 1 or 2 (0: PCR_ERR_UNSUPPORTED), the CSR's shape, item ids inside [0, d2), finite ratings, steps >= 1, the output, whatever
+// pcr_build_levels refuses; errors are prefixed with `who`.  plan (may be NULL) receives the plan.
+int pcr_fold_in_check(const char* who, int solver_type, int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val,
+                      int steps, const double* U_out, PcrFoldinPlan* plan);
+// pcr_fold_in_model's: the parameters it reads of p (k, precision, lambda, stepsize, cg_max_iter, cg_tol), V, then pcr_fold_in_check
+int pcr_fold_in_model_check(const pcr_params* p, const double* V, int64_t d2, int64_t n, const int64_t* index, const int32_t* item,
+                            const double* val, int steps, const double* U_out, PcrFoldinPlan* plan);
+// stats from the per-user table [n][PCR_FOLDIN_FIELDS]: the counts, and obj added in user order
+void pcr_foldin_stats_from(const double* per_user, int64_t n, pcr_foldin_stats* stats);

@@ -8,6 +8,7 @@
 #include <cmath>
 
 #include "pcr_dev.h"
+#include "pcr_foldin.h"
 #include "pcr_prims.h"
 #include "pcr_topk.h"
 
@@ -771,6 +772,90 @@ static int model_device(int device) {
     return PCR_OK;
 }
 
+// Fold-in (pcr_fold_in, pcr_fold_in_model; k_foldin of pcr_foldin.h) of the plan's users against v's V: the ratings, their
+// levels and the users' order go to the device, then one launch per workgroup form -- P.order is by descending length, so the
+// forms are ranges of it and the longest users of each start first; workgroups stride over their range.  A launch's LDS is sized
+// by its longest user; the scratch form's slices are bounded by the grid (at most FOLDIN_SCRATCH bytes in all).  "foldin/newton"
+// times the launches.
+struct FoldinParams { int solver_type; double lambda, stepsize; int cg_max; double cg_tol; int steps; };
+static const size_t FOLDIN_SCRATCH = (size_t)1 << 30;
+template <typename T, int BLOCK, bool BIG>
+static int foldin_launch(const ServeView& v, const FoldinParams& c, const PcrFoldinPlan& P, const FoldinCsr& X, const Geo& geo, const int32_t* d_order,
+                         int64_t first, int64_t count, int cus, const T* dU0, T* dOut, double* dPer, DBuf<char>& scratch) {
+    if (count <= 0) return PCR_OK;
+    const std::vector<int64_t>& idx = P.X.index;
+    const int32_t longest = P.order[(size_t)first];
+    const int cap = (int)std::max<int64_t>(1, idx[(size_t)longest + 1] - idx[(size_t)longest]);
+    int rs_cap = 1;
+    for (int64_t i = first; i < first + count; ++i) {
+        const int32_t u = P.order[(size_t)i];
+        rs_cap = std::max(rs_cap, (int)(P.lv.run_ofs[(size_t)u + 1] - P.lv.run_ofs[(size_t)u]));
+    }
+    const size_t li_bytes = BIG ? 8 : 4, arr = foldin_arr_bytes(cap, rs_cap, sizeof(T), li_bytes);
+    const size_t lds = foldin_small_bytes(geo.ld, BLOCK, sizeof(T)) + (BIG ? 0 : arr);
+    if (lds > PCR_FOLDIN_LDS_CU) {
+        pcr_set_error("fold-in: rank " + std::to_string(geo.r) + " (with " + std::to_string(rs_cap - 1) + " rating levels) is too large for the kernel's LDS");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(BLOCK == 64 ? 16 : BLOCK == 256 ? 4 : 1, PCR_FOLDIN_LDS_CU / lds));
+    int64_t grid = std::min<int64_t>(count, (int64_t)cus * per_cu);
+    size_t stride = 0;
+    if (BIG) {
+        stride = (arr + 255) & ~(size_t)255;
+        grid = std::max<int64_t>(1, std::min<int64_t>(grid, (int64_t)(FOLDIN_SCRATCH / stride)));
+        RC(scratch.alloc((size_t)grid * stride));
+    }
+    HIPCHK(hipFuncSetAttribute((const void*)k_foldin<T, BLOCK, BIG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_foldin<T, BLOCK, BIG>), dim3((unsigned)grid), dim3(BLOCK), lds, v.st, X, geo, d_order + first, (int)count, dU0, dOut,
+                       serve_V<T>(v), dPer, c.lambda, c.stepsize, c.cg_max, c.cg_tol, c.steps, c.solver_type == PCR_SOLVER_PCR ? 1 : 0,
+                       c.solver_type == PCR_SOLVER_PCR ? 1 : 0, cap, rs_cap, scratch.p, stride);
+    HIPCHK(hipGetLastError());
+    return PCR_OK;
+}
+
+template <typename T>
+static int foldin_run(const ServeView& v, const FoldinParams& c, const PcrFoldinPlan& P, const double* U0, double* U_out, pcr_foldin_stats* stats,
+                      double* per_user) {
+    const int64_t n = P.X.d1;
+    hipStream_t st = v.st;
+    Geo geo;
+    geo.r = v.r; geo.ld = v.ld; geo.nchunk = v.ld / VecOf<T>::N; geo.G = std::min(64, host_pow2(geo.nchunk));
+    int dev = 0, cus = 0;
+    HIPCHK(hipGetDevice(&dev));
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    cus = std::max(cus, 1);
+    DBuf<int64_t> uptr, runofs;
+    DBuf<int32_t> item, runstart, order;
+    DBuf<uint16_t> lvl;
+    DBuf<T> dU0, dOut;
+    DBuf<double> dPer, dOutD;
+    DBuf<char> scratch;
+    RC(uptr.upload(P.X.index, st)); RC(item.upload_n(P.X.item.data(), P.X.item.size()));
+    RC(lvl.upload(P.lv.level, st)); RC(runofs.upload(P.lv.run_ofs, st)); RC(runstart.upload(P.lv.run_start, st));
+    RC(order.upload(P.order, st));
+    RC(dU0.alloc((size_t)n * v.ld)); RC(dOut.alloc((size_t)n * v.ld)); RC(dPer.alloc((size_t)n * PCR_FOLDIN_FIELDS)); RC(dOutD.alloc((size_t)n * v.r));
+    if (U0) RC(upload_rows<T>(st, v.r, v.ld, {{U0, n, dU0.p}}));
+    else HIPCHK(hipMemsetAsync(dU0.p, 0, (size_t)n * v.ld * sizeof(T), st));
+    const FoldinCsr X = {uptr.p, item.p, lvl.p, runofs.p, runstart.p};
+    {
+        ProfScope ps(v.prof, "foldin/newton", st);
+        const int64_t nw = n - P.n_big - P.n_lds;
+        RC((foldin_launch<T, 512, true>(v, c, P, X, geo, order.p, 0, P.n_big, cus, dU0.p, dOut.p, dPer.p, scratch)));
+        RC((foldin_launch<T, 256, false>(v, c, P, X, geo, order.p, P.n_big, P.n_lds, cus, dU0.p, dOut.p, dPer.p, scratch)));
+        RC((foldin_launch<T, 64, false>(v, c, P, X, geo, order.p, P.n_big + P.n_lds, nw, cus, dU0.p, dOut.p, dPer.p, scratch)));
+    }
+    hipLaunchKernelGGL((k_mat_out<T>), dim3((unsigned)std::min<int64_t>(1 << 16, cdiv(n * v.r, 256))), dim3(256), 0, st, (const T*)dOut.p, dOutD.p, n, v.r, v.ld);
+    HIPCHK(hipGetLastError());
+    std::vector<double> hp((size_t)n * PCR_FOLDIN_FIELDS);
+    HIPCHK(hipMemcpyAsync(U_out, dOutD.p, (size_t)n * v.r * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hp.data(), dPer.p, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (stats) pcr_foldin_stats_from(hp.data(), n, stats);
+    if (per_user) std::copy(hp.begin(), hp.end(), per_user);
+    return PCR_OK;
+}
+static FoldinParams foldin_params_of(const pcr_params& p, int steps) { return {p.solver_type, p.lambda, p.stepsize, p.cg_max_iter, p.cg_tol, steps}; }
+
 extern "C" {
 
 // users[n] (global ids, NULL: the whole shard) as rows of s's shard in loc (left empty for NULL); *n the count
@@ -981,6 +1066,37 @@ int pcr_evaluate_rerank_model(const double* U, int64_t d1, const double* V, int6
         return tradeoff_run<decltype(zero)>("pcr_evaluate_rerank_model", v, info.p, n, users, nth, thetas, pool, ncut, cutoffs, threshold,
                                             tindex != nullptr, topn, div, per_user_topn, per_user_div, exposure);
     });
+    });
+}
+
+int pcr_fold_in_model(const pcr_params* p, const double* V, int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val,
+                      const double* U0, int steps, double* U_out, pcr_foldin_stats* stats, double* per_user) {
+    return abi_guard("pcr_fold_in_model", [&]() -> int {
+    PcrFoldinPlan P;
+    RC(pcr_fold_in_model_check(p, V, d2, n, index, item, val, steps, U_out, &P));
+    RC(model_device(p->device));
+    if (stats) *stats = pcr_foldin_stats{};
+    if (n == 0) return PCR_OK;
+    ServeView v; ModelDev M;
+    RC(M.open(nullptr, n, V, d2, p->k, nullptr, nullptr, true, p->precision, &v));
+    const FoldinParams c = foldin_params_of(*p, steps);
+    return by_precision(v, [&](auto zero) -> int { return foldin_run<decltype(zero)>(v, c, P, U0, U_out, stats, per_user); });
+    });
+}
+
+int pcr_fold_in(pcr_solver* s, int64_t n, const int64_t* index, const int32_t* item, const double* val, const double* U0, int steps,
+                double* U_out, pcr_foldin_stats* stats, double* per_user) {
+    S_OR_ARG;
+    return abi_guard("pcr_fold_in", [&]() -> int {
+        pcr_params prm;
+        RC(s->foldin_params(&prm));
+        const ServeView v = solver_view(s, 0);
+        PcrFoldinPlan P;
+        RC(pcr_fold_in_check("pcr_fold_in", prm.solver_type, v.d2, n, index, item, val, steps, U_out, &P));
+        if (stats) *stats = pcr_foldin_stats{};
+        if (n == 0) return PCR_OK;
+        const FoldinParams c = foldin_params_of(prm, steps);
+        return by_precision(v, [&](auto zero) -> int { return foldin_run<decltype(zero)>(v, c, P, U0, U_out, stats, per_user); });
     });
 }
 

@@ -113,6 +113,12 @@ int pcr_evaluate_rerank_model(const double* U, int64_t d1, const double* V, int6
                                                    threshold, dtype, topn, per_user_topn, div, nullptr);
     return rc != PCR_OK ? rc : absent();
 }
+int pcr_fold_in_model(const pcr_params* p, const double* V, int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val,
+                      const double*, int steps, double* U_out, pcr_foldin_stats*, double*) {
+    const int rc = pcr_fold_in_model_check(p, V, d2, n, index, item, val, steps, U_out, nullptr);
+    return rc != PCR_OK ? rc : absent();
+}
+NO_SOLVER(pcr_fold_in, pcr_solver*, int64_t, const int64_t*, const int32_t*, const double*, const double*, int, double*, pcr_foldin_stats*, double*)
 NO_SOLVER(pcr_evaluate_rerank, pcr_solver*, int64_t, const int32_t*, int, const double*, int, int, const int*, double, int, pcr_topn_stats*,
           pcr_diversity_stats*, double*, double*, int64_t*)
 }
