@@ -98,7 +98,8 @@ def test_dyadic_preconditions_and_integer_brute_force(oracle, r, solver, real):
     whole number of sixteenths far inside fp64; both sides of the hinge window are populated; every user-length class boundary
     is present; feeding the ratings in another order changes no bit.  Then the oracle against the definition itself, in numpy
     INTEGER arithmetic scaled to the unit (exact_data.brute_force): objective and gradient must be equal -- that is the plain
-    high-precision reference; the oracle's sweep form is then trusted for Ha."""
+    high-precision reference; Ha is held to its own integer definition (item_edge_data.brute_force_Ha) on this fixture by
+    tests/test_item_edges.py::test_Ha_equals_its_integer_definition_on_the_user_edge_fixture."""
     c = reference(oracle, r, solver, real)
     X = c.X
     assert set(ed.CLASS_EDGES) <= set(c.lens.tolist()) and c.lens.max() > 4097
