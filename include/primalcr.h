@@ -408,6 +408,42 @@ int pcr_recommend(pcr_solver *s, int64_t n, const int32_t *users, int topk, int 
                   int32_t *items, double *scores);                         /* [device] */
 
 /* ------------------------------------------------------------------------- */
+/* filtered recommendation: top-K among allowed items and candidate lists     */
+/* ------------------------------------------------------------------------- */
+/* The recommendation above restricted to a catalogue-wide eligibility set (in stock, a category, a market), to a candidate
+ * list per user (re-ranking a retrieval stage; "one held-out item against 99 sampled negatives" is candidates followed by
+ * pcr_evaluate_lists_model), or to both.  Everything the block above promises holds unchanged: the order rule, the padding
+ * with (-1, -INFINITY), the precision, the determinism, 1 <= K <= PCR_RECOMMEND_MAX_K.  In addition:
+ *   Eligible items   of user u: all items, or the items of u's candidate row when cand_ptr is given; of those, the items
+ *                    whose allow[j] is nonzero (allow NULL: all of them) that are not in u's training row when exclusion is
+ *                    on.  The filters intersect.  The list is the K best eligible items.
+ *   Same bits        s(u, j) is bit for bit the score pcr_recommend / pcr_recommend_model computes for the pair, in fp32 and
+ *                    in fp64: a filtered list is exactly the unfiltered full ranking with the ineligible entries struck
+ *                    out.  It does not depend on the other users of the call, their order, the launch grid or the order of
+ *                    the ids inside a candidate row.
+ *   Limits           K and d2 as pcr_recommend; a candidate row may have any length.
+ *   Errors           f == NULL, or a filter with allow and cand_ptr both NULL, is PCR_ERR_ARG (pcr_recommend is the entry
+ *                    without a filter; the message says so).  Also PCR_ERR_ARG: cand_ptr[0] != 0 or cand_ptr not monotone,
+ *                    cand_ptr without cand_item, a candidate id outside [0, d2), an id twice in one row; the message names
+ *                    the entry and the user.  All are found on the host before any device is looked for.
+ * Profile slots (of the solver entry): recommend/score + recommend/merge for an allow set alone, recommend/candidates (one
+ * launch per user batch, the whole selection) whenever candidate lists are given. */
+typedef struct pcr_item_filter {
+    const uint8_t *allow;      /* [d2], nonzero = eligible for every user; NULL: every item */
+    const int64_t *cand_ptr;   /* [n + 1], cand_ptr[0] = 0, monotone; row i belongs to users[i]; NULL: no candidate lists */
+    const int32_t *cand_item;  /* 0-based item ids, any order within a row, no id twice in a row */
+} pcr_item_filter;
+/* Standalone: every argument but f as pcr_recommend_model. */
+int pcr_recommend_filtered_model(const double *U, int64_t d1, const double *V, int64_t d2, int64_t k,
+                                 const int64_t *index, const int32_t *item,
+                                 int64_t n, const int32_t *users, int topk, int dtype, const pcr_item_filter *f,
+                                 int32_t *items, double *scores, int device);        /* [device] */
+/* On a live solver of any type, as pcr_recommend: users[n] are GLOBAL ids of this rank's shard (NULL: all of them, n = its
+ * n_users, and cand_ptr has n_users + 1 entries); nothing is exchanged and the training state is not touched. */
+int pcr_recommend_filtered(pcr_solver *s, int64_t n, const int32_t *users, int topk, int flags,
+                           const pcr_item_filter *f, int32_t *items, double *scores); /* [device] */
+
+/* ------------------------------------------------------------------------- */
 /* full-catalogue top-N evaluation (no reference counterpart: util.cpp's       */
 /* evaluator ranks a user's own test items among themselves)                  */
 /* ------------------------------------------------------------------------- */

@@ -96,6 +96,11 @@ class RankStats(C.Structure):
                 ("auc", C.c_double), ("mpr", C.c_double)]
 
 
+class ItemFilter(C.Structure):
+    """pcr_item_filter."""
+    _fields_ = [("allow", C.c_void_p), ("cand_ptr", C.c_void_p), ("cand_item", C.c_void_p)]
+
+
 class FoldinStats(C.Structure):
     """pcr_foldin_stats."""
     _fields_ = [("users", C.c_int64), ("converged", C.c_int64), ("step_cap", C.c_int64), ("stalled", C.c_int64), ("steps", C.c_int64),
@@ -174,6 +179,9 @@ def lib():
     L.pcr_predict.argtypes = [_dp, i64, _dp, i64, i64, i64, _ip, _ip, _dp, ci]
     L.pcr_recommend_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, vp, ci, ci, vp, vp, ci]
     L.pcr_recommend.argtypes = [vp, i64, vp, ci, ci, vp, vp]
+    if _LIB_OVERRIDE is None or hasattr(L, "pcr_recommend_filtered"):   # (use_library may load an older build for an A/B run: tools/exp_filter.py)
+        L.pcr_recommend_filtered_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, vp, ci, ci, C.POINTER(ItemFilter), vp, vp, ci]
+        L.pcr_recommend_filtered.argtypes = [vp, i64, vp, ci, ci, C.POINTER(ItemFilter), vp, vp]
     L.pcr_recommend_diverse_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, vp, ci, ci, cd, ci, vp, vp, ci]
     L.pcr_recommend_diverse.argtypes = [vp, i64, vp, ci, ci, cd, ci, vp, vp]
     L.pcr_evaluate_topn_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, ci, vp, cd, ci, vp, vp, ci]
@@ -276,9 +284,35 @@ def predict(U, V, user, item, device=0):
     return out
 
 
-def recommend(U, V, topk, exclude=None, users=None, dtype=PCR_F64, device=0):
+def _item_filter(allow, candidates, d2, n):
+    """Shared by recommend() and Solver.recommend(): the pcr_item_filter of an allow mask (bool / uint8, length d2) and an
+    (index, item) pair of candidate rows, one per requested user; returns (filter, the arrays it points into)."""
+    f = ItemFilter()
+    keep = []
+    if allow is not None:
+        allow = np.asarray(allow)
+        if allow.ndim != 1 or allow.shape[0] != d2:
+            raise ValueError(f"allow: a mask of d2 = {d2} entries is expected, got shape {allow.shape}")
+        allow = np.ascontiguousarray(allow != 0, np.uint8)
+        f.allow = allow.ctypes.data
+        keep.append(allow)
+    if candidates is not None:
+        idx, it = candidates
+        idx = np.ascontiguousarray(idx, np.int64); it = np.ascontiguousarray(it, np.int32)
+        if idx.ndim != 1 or it.ndim != 1 or idx.shape[0] != n + 1 or idx[-1] != it.shape[0]:
+            raise ValueError(f"candidates: index must have one row per requested user (n + 1 = {n + 1} entries), the last equal to "
+                             f"len(item) = {it.shape[0]}")
+        f.cand_ptr = idx.ctypes.data; f.cand_item = it.ctypes.data
+        keep += [idx, it]
+    return f, keep
+
+
+def recommend(U, V, topk, exclude=None, users=None, dtype=PCR_F64, device=0, allow=None, candidates=None):
     """Top-K items per user on the GPU (pcr_recommend_model): descending score, equal scores by ascending item id, rows padded
     with (-1, -inf).  exclude: a Dataset (its training CSR) or an (index, item) pair, or None; users: 0-based ids (None: all).
+    allow: a boolean / uint8 mask over the d2 items, eligible where nonzero; candidates: an (index, item) CSR pair with one row
+    of 0-based item ids per requested user (any order, no id twice in a row) -- with either, the list is the K best of the items
+    that pass every filter (pcr_recommend_filtered_model), with the scores of the unfiltered call bit for bit.
     Returns (items int32 [n, topk], scores float64 [n, topk])."""
     U = np.ascontiguousarray(U, np.float64); V = np.ascontiguousarray(V, np.float64)
     d1, k = U.shape
@@ -295,6 +329,12 @@ def recommend(U, V, topk, exclude=None, users=None, dtype=PCR_F64, device=0):
         users = np.ascontiguousarray(users, np.int32)
     n = d1 if users is None else users.shape[0]
     items = np.empty((n, max(int(topk), 1)), np.int32); scores = np.empty((n, max(int(topk), 1)), np.float64)
+    if allow is not None or candidates is not None:
+        f, _keep = _item_filter(allow, candidates, V.shape[0], n)
+        _chk(lib().pcr_recommend_filtered_model(U.ctypes.data, d1, V.ctypes.data, V.shape[0], k, None if idx is None else idx.ctypes.data,
+                                                None if it is None else it.ctypes.data, n, None if users is None else users.ctypes.data,
+                                                int(topk), int(dtype), C.byref(f), items.ctypes.data, scores.ctypes.data, device))
+        return items, scores
     _chk(lib().pcr_recommend_model(U.ctypes.data, d1, V.ctypes.data, V.shape[0], k, None if idx is None else idx.ctypes.data,
                                    None if it is None else it.ctypes.data, n, None if users is None else users.ctypes.data, int(topk),
                                    int(dtype), items.ctypes.data, scores.ctypes.data, device))
@@ -955,13 +995,19 @@ class Solver:
         names = [n for n in buf.value.decode().split(",") if n]
         return {n: self.profile_get(n) for n in names}
 
-    def recommend(self, topk=10, users=None, exclude_train=True):
+    def recommend(self, topk=10, users=None, exclude_train=True, allow=None, candidates=None):
         """Top-K items per user from the device factors (pcr_recommend), in the solver's storage type.  users: GLOBAL 0-based
-        ids of this rank's shard (None: all of them, in order).  Returns (items int32 [n, topk], scores float64 [n, topk])."""
+        ids of this rank's shard (None: all of them, in order).  allow / candidates as recommend() (pcr_recommend_filtered).
+        Returns (items int32 [n, topk], scores float64 [n, topk])."""
         if users is not None:
             users = np.ascontiguousarray(users, np.int32)
         n = self.n_users if users is None else users.shape[0]
         items = np.empty((n, max(int(topk), 1)), np.int32); scores = np.empty((n, max(int(topk), 1)), np.float64)
+        if allow is not None or candidates is not None:
+            f, _keep = _item_filter(allow, candidates, self.d2, n)
+            _chk(lib().pcr_recommend_filtered(self._h, n, None if users is None else users.ctypes.data, int(topk),
+                                              PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, C.byref(f), items.ctypes.data, scores.ctypes.data))
+            return items, scores
         _chk(lib().pcr_recommend(self._h, n, None if users is None else users.ctypes.data, int(topk),
                                  PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, items.ctypes.data, scores.ctypes.data))
         return items, scores

@@ -38,6 +38,12 @@
 //                    --tradeoff or --ranks
 //     -l lambda      the regulariser the model was trained with (required with --fold-in)
 //     -s 1|2         1 = PrimalCR, 2 = PrimalCR++ (default) levels and windows;  --steps S: at most S Newton steps per user (default 10)
+//   omp-pmf-recommend [--allow items_file] [--candidates file] [-K topk] [-x data_dir] [-u users_file] [--f32] [--scores] model_file output_file
+//     --allow file   recommend among these items only (pcr_recommend_filtered_model): one 1-based item id per line, like -u
+//     --candidates f a candidate list per requested user: line i holds the space-separated 1-based item ids of the i-th requested
+//                    user (any order, no id twice; an empty line is an empty row), as many lines as users; the list is the -K best
+//                    of them.  Both go with the plain list and --scores and intersect with each other and with -x; not together
+//                    with --eval, --diversity, --mmr, --tradeoff, --ranks or --fold-in
 // Output: one line per user, in input order: the 1-based user id, then the 1-based item ids (padding is left out).  Users go
 // to the device in batches, so host memory for the lists stays bounded on any catalogue.
 // With --eval: stdout gets one line per cutoff, "cutoff c users n users_graded n hits n precision x recall x hit_rate x map x
@@ -94,7 +100,11 @@ static const char* USAGE =
     "                   \"foldin users n converged n step_cap n stalled n steps n cg n ls n obj x\" line; with --eval the new users\n"
     "                   are scored against that directory's test ratings; not with -x, -u, --diversity, --mmr, --tradeoff or --ranks\n"
     "    -l lambda      the regulariser of the model (required with --fold-in)\n"
-    "    -s 1|2         1 = PrimalCR, 2 = PrimalCR++ (default);  --steps S  at most S Newton steps per user (default 10)\n";
+    "    -s 1|2         1 = PrimalCR, 2 = PrimalCR++ (default);  --steps S  at most S Newton steps per user (default 10)\n"
+    "       omp-pmf-recommend [--allow items_file] [--candidates file] [-K topk] [-x data_dir] [-u users_file] [--f32] [--scores] model_file output_file\n"
+    "    --allow file   recommend among these items only: one 1-based item id per line\n"
+    "    --candidates f line i: the space-separated 1-based candidate items of the i-th requested user (an empty line: none);\n"
+    "                   the list is the -K best of them; both go with the plain list and --scores only\n";
 
 static int usage() { printf("%s", USAGE); return 1; }
 
@@ -119,6 +129,68 @@ static bool read_users(const char* path, int64_t d1, std::vector<int32_t>& out) 
         out.push_back((int32_t)(v - 1));
     }
     fclose(fp);
+    return ok;
+}
+
+// --allow: one 1-based item id per line (blank lines skipped); allow[j] = 1 for the listed items
+static bool read_allow(const char* path, int64_t d2, std::vector<uint8_t>& allow) {
+    FILE* fp = fopen(path, "r");
+    if (!fp) { fprintf(stderr, "can't open allow file %s\n", path); return false; }
+    allow.assign((size_t)d2, 0);
+    char line[256];
+    int64_t ln = 0;
+    bool ok = true;
+    while (fgets(line, sizeof line, fp)) {
+        ++ln;
+        char* p = line;
+        while (*p == ' ' || *p == '\t') ++p;
+        if (*p == '\n' || *p == '\r' || *p == 0) continue;
+        errno = 0;
+        char* end = nullptr;
+        const long long v = strtoll(p, &end, 10);
+        while (end && (*end == ' ' || *end == '\t' || *end == '\r' || *end == '\n')) ++end;
+        if (end == p || errno || !end || *end != 0) { fprintf(stderr, "allow file %s, line %lld: not an item id\n", path, (long long)ln); ok = false; break; }
+        if (v < 1 || v > d2) { fprintf(stderr, "allow file %s, line %lld: item %lld outside 1 .. %lld\n", path, (long long)ln, v, (long long)d2); ok = false; break; }
+        allow[(size_t)(v - 1)] = 1;
+    }
+    fclose(fp);
+    return ok;
+}
+
+// --candidates: line i = the space-separated 1-based item ids of the i-th requested user (an empty line: an empty row), exactly
+// n lines; the rows as a CSR of 0-based ids.  A line may have any length.
+static bool read_candidates(const char* path, int64_t n, int64_t d2, std::vector<int64_t>& ptr, std::vector<int32_t>& item) {
+    FILE* fp = fopen(path, "r");
+    if (!fp) { fprintf(stderr, "can't open candidates file %s\n", path); return false; }
+    ptr.assign(1, 0);
+    item.reserve(64);                                              // (a file of empty rows still hands the library a pointer)
+    char* line = nullptr;
+    size_t cap = 0;
+    bool ok = true;
+    while (ok && getline(&line, &cap, fp) >= 0) {
+        const long long ln = (long long)ptr.size();
+        const char* p = line;
+        while (true) {
+            while (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n') ++p;
+            if (*p == 0) break;
+            errno = 0;
+            char* end = nullptr;
+            const long long v = strtoll(p, &end, 10);
+            if (end == p || errno || (*end != ' ' && *end != '\t' && *end != '\r' && *end != '\n' && *end != 0)) {
+                fprintf(stderr, "candidates file %s, line %lld: not an item id\n", path, ln); ok = false; break;
+            }
+            if (v < 1 || v > d2) { fprintf(stderr, "candidates file %s, line %lld: item %lld outside 1 .. %lld\n", path, ln, v, (long long)d2); ok = false; break; }
+            item.push_back((int32_t)(v - 1));
+            p = end;
+        }
+        ptr.push_back((int64_t)item.size());
+    }
+    free(line);
+    fclose(fp);
+    if (ok && (int64_t)ptr.size() - 1 != n) {
+        fprintf(stderr, "candidates file %s: %lld lines for %lld requested users\n", path, (long long)ptr.size() - 1, (long long)n);
+        ok = false;
+    }
     return ok;
 }
 
@@ -328,7 +400,7 @@ static bool run_fold_in(const char* dir, const std::vector<double>& V, int64_t d
 int main(int argc, char** argv) {
     int K = 10;
     bool f32 = false, with_scores = false, with_ranks = false, diversity = false;
-    const char *xdir = nullptr, *ufile = nullptr, *edir = nullptr;
+    const char *xdir = nullptr, *ufile = nullptr, *edir = nullptr, *afile = nullptr, *cfile = nullptr;
     std::vector<int> cuts;
     double threshold = -INFINITY, theta = 0.0;
     bool mmr = false;
@@ -408,6 +480,9 @@ int main(int argc, char** argv) {
                 K = (int)x;
             } else if (a[1] == 'x') xdir = v;
             else ufile = v;
+        } else if (!strcmp(a, "--allow") || !strcmp(a, "--candidates")) {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
+            (a[2] == 'a' ? afile : cfile) = argv[++i];
         } else if (!strcmp(a, "--f32")) f32 = true;
         else if (!strcmp(a, "--scores")) with_scores = true;
         else if (!strcmp(a, "--ranks")) with_ranks = true;
@@ -416,6 +491,10 @@ int main(int argc, char** argv) {
         else pos.push_back(a);
     }
     const bool tradeoff = !thetas.empty();
+    if ((afile || cfile) && (edir || diversity || mmr || tradeoff || with_ranks || fdir)) {
+        fprintf(stderr, "--allow and --candidates do not go with --eval, --diversity, --mmr, --tradeoff, --ranks or --fold-in\n");
+        return 1;
+    }
     if (fdir) {
         if (xdir || ufile || diversity || mmr || tradeoff || with_ranks) { fprintf(stderr, "--fold-in does not go with -x, -u, --diversity, --mmr, --tradeoff or --ranks\n"); return 1; }
         if (!have_lambda) { fprintf(stderr, "--fold-in needs -l lambda\n"); return 1; }
@@ -451,6 +530,11 @@ int main(int argc, char** argv) {
     std::vector<int64_t> xindex;
     std::vector<int32_t> xitem;
     if (xdir && !load_csr(xdir, 0, d1, d2, xindex, xitem, nullptr)) return 1;
+    std::vector<uint8_t> allow;                                    // --allow / --candidates: the filter of every batch
+    std::vector<int64_t> cptr, bptr;
+    std::vector<int32_t> citem;
+    if (afile && !read_allow(afile, d2, allow)) return 1;
+    if (cfile && !read_candidates(cfile, (int64_t)users.size(), d2, cptr, citem)) return 1;
     if (fdir) {                                                    // the new users take the model's users' place: their factors, their ratings excluded
         std::vector<double> U_new;
         if (!run_fold_in(fdir, V, d2, k, lambda, solver, steps, f32, &d1, xindex, xitem, U_new)) return 1;
@@ -494,7 +578,15 @@ int main(int argc, char** argv) {
         items.resize((size_t)(m * K)); scores.resize((size_t)(m * K));
         const int64_t* xi = xdir ? xindex.data() : nullptr;
         const int32_t* xt = xdir ? xitem.data() : nullptr;
-        const int rc = mmr ? pcr_recommend_diverse_model(U.data(), d1, V.data(), d2, k, xi, xt, m, users.data() + b0, K, pool, theta,
+        pcr_item_filter flt = {afile ? allow.data() : nullptr, nullptr, nullptr};
+        if (cfile) {                                               // the batch's rows, cand_ptr rebased to its first
+            bptr.resize((size_t)m + 1);
+            for (int64_t i = 0; i <= m; ++i) bptr[(size_t)i] = cptr[(size_t)(b0 + i)] - cptr[(size_t)b0];
+            flt.cand_ptr = bptr.data(); flt.cand_item = citem.data() + cptr[(size_t)b0];
+        }
+        const int rc = (afile || cfile) ? pcr_recommend_filtered_model(U.data(), d1, V.data(), d2, k, xi, xt, m, users.data() + b0, K,
+                                                                       f32 ? PCR_F32 : PCR_F64, &flt, items.data(), scores.data(), 0)
+                     : mmr ? pcr_recommend_diverse_model(U.data(), d1, V.data(), d2, k, xi, xt, m, users.data() + b0, K, pool, theta,
                                                          f32 ? PCR_F32 : PCR_F64, items.data(), scores.data(), 0)
                            : pcr_recommend_model(U.data(), d1, V.data(), d2, k, xi, xt, m, users.data() + b0, K, f32 ? PCR_F32 : PCR_F64,
                                                  items.data(), scores.data(), 0);

@@ -170,6 +170,9 @@ struct ServeView {
     // host: the test CSR of the rows
     const int64_t* tptr = nullptr; const int32_t* titem = nullptr; const double* tval = nullptr;
     int select = 1;                            // pcr_tune("recommend_select")
+    // device: the packed allow set of a filtered call (bit j & 63 of word j >> 6, cdiv(d2, 64) words; pcr_recommend_filtered):
+    // NULL everywhere else, and every item is eligible
+    const unsigned long long* allow = nullptr;
     Profiler* prof = nullptr;                  // the "recommend/..." and "ranks/..." slots (NULL: not profiled)
     int exchange = SERVE_LOCAL;
     pcr_solver* owner = nullptr;               // whose communicator sum() and wait() use (NULL: a model, nothing to exchange)

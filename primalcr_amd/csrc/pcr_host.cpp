@@ -1089,6 +1089,49 @@ int pcr_recommend_model_check(const double* U, int64_t d1, const double* V, int6
     return PCR_OK;
 }
 
+int pcr_item_filter_check(const char* who, int64_t d2, int64_t n, const int32_t* users, const pcr_item_filter* f) {
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
+    if (!f) return bad("null filter (pcr_recommend is the entry without one)");
+    if (!f->allow && !f->cand_ptr) return bad("a filter without an allow set and without candidate lists (pcr_recommend is the entry without one)");
+    if (!f->cand_ptr) return PCR_OK;
+    auto user_of = [&](int64_t i) { return "user " + std::to_string(users ? (int64_t)users[i] : i) + " (row " + std::to_string(i) + ")"; };
+    const int64_t* cp = f->cand_ptr;
+    if (cp[0] != 0) return bad("cand_ptr[0] must be 0");
+    for (int64_t i = 0; i < n; ++i) if (cp[i + 1] < cp[i]) return bad("cand_ptr not monotone at " + user_of(i));
+    if (!f->cand_item) return bad("cand_ptr without cand_item");
+    const int nth = pcr_host_threads();
+    std::vector<int64_t> first((size_t)nth, -1);       // the first bad row of each thread's range
+    std::vector<int32_t> what((size_t)nth, 0);         // ... and its id; kind 0: outside [0, d2), 1: twice in the row
+    std::vector<char> kind((size_t)nth, 0);
+    pcr_parallel_ranges(n, nth, [&](int t, int64_t lo, int64_t hi) {
+        std::vector<int32_t> row;
+        for (int64_t i = lo; i < hi; ++i) {
+            const int32_t* c = f->cand_item + cp[i];
+            const int64_t len = cp[i + 1] - cp[i];
+            for (int64_t z = 0; z < len; ++z)
+                if (c[z] < 0 || c[z] >= d2) { first[(size_t)t] = i; what[(size_t)t] = c[z]; kind[(size_t)t] = 0; return; }
+            row.assign(c, c + len);
+            std::sort(row.begin(), row.end());
+            for (int64_t z = 1; z < len; ++z)
+                if (row[(size_t)z] == row[(size_t)z - 1]) { first[(size_t)t] = i; what[(size_t)t] = row[(size_t)z]; kind[(size_t)t] = 1; return; }
+        }
+    });
+    for (int t = 0; t < nth; ++t) {
+        if (first[(size_t)t] < 0) continue;
+        const std::string id = "candidate id " + std::to_string(what[(size_t)t]);
+        return bad(kind[(size_t)t] ? id + " twice in the row of " + user_of(first[(size_t)t])
+                                   : id + " of " + user_of(first[(size_t)t]) + " outside [0, " + std::to_string(d2) + ")");
+    }
+    return PCR_OK;
+}
+
+int pcr_recommend_filtered_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
+                                       const int32_t* item, int64_t n, const int32_t* users, int topk, int dtype, const pcr_item_filter* f,
+                                       const int32_t* items, const double* scores, bool* sorted) {
+    const int rc = pcr_recommend_model_check(U, d1, V, d2, k, index, item, n, users, topk, dtype, items, scores, sorted, "pcr_recommend_filtered_model");
+    return rc != PCR_OK ? rc : pcr_item_filter_check("pcr_recommend_filtered_model", d2, n, users, f);
+}
+
 int pcr_cutoffs_check(const char* who, int ncut, const int* cutoffs) {
     auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
     if (ncut < 1 || ncut > PCR_TOPN_MAX_CUTOFFS || !cutoffs)

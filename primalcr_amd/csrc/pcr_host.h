@@ -74,6 +74,17 @@ int pcr_recommend_model_check(const double* U, int64_t d1, const double* V, int6
                               const int32_t* item, int64_t n, const int32_t* users, int topk, int dtype, const int32_t* items,
                               const double* scores, bool* sorted, const char* who = "pcr_recommend_model");
 
+// The item filter of pcr_recommend_filtered / pcr_recommend_filtered_model for n requests over d2 items (both entries and the
+// sanitizer build's stub run this one): f != NULL with an allow set or candidate lists (neither: the message points to
+// pcr_recommend); cand_ptr[0] = 0 and monotone over n + 1 entries, cand_item given with it, every id inside [0, d2), no id twice
+// in a row (checked on a sorted copy of the row, by the host threads).  A message names `who` and the row's user (users[i],
+// NULL: i).
+int pcr_item_filter_check(const char* who, int64_t d2, int64_t n, const int32_t* users, const pcr_item_filter* f);
+// pcr_recommend_filtered_model's argument checks: those of pcr_recommend_model, then pcr_item_filter_check
+int pcr_recommend_filtered_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
+                                       const int32_t* item, int64_t n, const int32_t* users, int topk, int dtype, const pcr_item_filter* f,
+                                       const int32_t* items, const double* scores, bool* sorted);
+
 // the top-N evaluation's own arguments (both entries): 1 .. PCR_TOPN_MAX_CUTOFFS cutoffs, strictly ascending, inside
 // [1, PCR_RECOMMEND_MAX_K]; threshold not NaN; stats != NULL.  Errors are prefixed with `who`.
 int pcr_topn_check(const char* who, int ncut, const int* cutoffs, double threshold, const pcr_topn_stats* stats);

@@ -14,6 +14,7 @@
 //   K10       compute_pairwise_error_ndcg (util.cpp:434)   -> k_eval2 (sorted) / k_eval (brute force)
 //             pmf-predict.cpp:56-64                        -> k_predict
 //             top-K unrated items per user (no reference)  -> k_rec_score + k_rec_merge
+//             ... among an allow set / candidate lists      -> k_rec_score's allow operand / k_rec_cand
 //             top-N evaluation of those lists (no reference) -> k_rec_score + k_rec_merge_topn + k_topn_sum1 / k_topn_fin
 //
 // Formulation (replaces the sequential two-pointer sweep with data-parallel primitives,

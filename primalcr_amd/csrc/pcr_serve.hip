@@ -29,7 +29,8 @@ static void fill_cuts(int* dst, int ncut, const int* cuts) {
 // range is split across workgroups until the grid holds about REC_TARGET_WG workgroups (ml1m's 6 040 users are 95 workgroups
 // of 64).  Each batch's partial lists go to the sink: sink.begin(nb) once with the largest batch, then sink.batch(b0, m, ...)
 // per batch, which merges them (RecCopy: into pcr_recommend's host arrays; RecTopn: into the top-N metrics).  The launches
-// are timed in v.prof's "recommend/..." slots (NULL: not profiled).  select = 0 only for tools/exp_recommend.py's GEMM-alone timing (lists come back empty).
+// are timed in v.prof's "recommend/..." slots (NULL: not profiled).  v.allow (NULL but in a filtered call) goes to the score kernel as it is.
+// select = 0 only for tools/exp_recommend.py's GEMM-alone timing (lists come back empty).
 static const size_t REC_SCRATCH = (size_t)1 << 30;
 static const int REC_TARGET_WG = 1024, REC_MAX_SPLIT = 16, REC_MIN_SPLIT_ITEMS = 1024;
 // The user batches and item splits of a sweep over n users whose scratch takes per_user bytes per user and split (rec_run and
@@ -81,7 +82,7 @@ static int rec_run(const ServeView& v, int64_t n, const int32_t* h_users, int K,
         {
             ProfScope ps(v.prof, "recommend/score", st);
             hipLaunchKernelGGL((k_rec_score<T>), dim3((unsigned)cdiv(m, users_per_wg), (unsigned)nsp), dim3(rec::WAVES * 64), lds, st, serve_U<T>(v),
-                               serve_V<T>(v), v.r, v.ld, (int)v.d2, du.p, m, v.xptr(), v.xitem(), K, per, ls.p, li.p, ln.p, select);
+                               serve_V<T>(v), v.r, v.ld, (int)v.d2, du.p, m, v.xptr(), v.xitem(), K, per, ls.p, li.p, ln.p, select, v.allow);
             HIPCHK(hipGetLastError());
         }
         RC(sink.batch(b0, m, (const T*)ls.p, (const int32_t*)li.p, (const int32_t*)ln.p, nsp));
@@ -111,6 +112,49 @@ struct RecCopy {
         return PCR_OK;
     }
 };
+
+// Top-K over candidate lists (k_rec_cand of pcr_topk.h) for the n users h_users (rows of v's U and of its
+// exclusion CSR, as rec_run; NULL: rows 0..n-1): row i of the host CSR cptr[n + 1] / citem holds users[i]'s candidates.  Users go
+// in batches of at most CAND_BATCH list entries and, past the first user of a batch, CAND_ITEMS candidates; a batch uploads its
+// users, its slice of cptr (absolute values: the kernel subtracts the first) and its candidates, and one launch, timed in
+// "recommend/candidates", writes the finished lists, which are copied to items / scores (n x K).  v.allow as in rec_run.
+static const int64_t CAND_BATCH = (int64_t)1 << 24, CAND_ITEMS = (int64_t)1 << 26;
+template <typename T>
+static int cand_run(const ServeView& v, int64_t n, const int32_t* h_users, const int64_t* cptr, const int32_t* citem, int K, int32_t* items,
+                    double* scores) {
+    if (n <= 0) return PCR_OK;
+    hipStream_t st = v.st;
+    const int64_t nb = std::min(n, std::max<int64_t>(4, CAND_BATCH / K));
+    DBuf<int32_t> du, dc, oi;
+    DBuf<int64_t> dp;
+    DBuf<double> os;
+    RC(du.alloc((size_t)nb)); RC(dp.alloc((size_t)nb + 1)); RC(oi.alloc((size_t)nb * K)); RC(os.alloc((size_t)nb * K));
+    const size_t lds = cand_wave_lds<T>(K) * 4;
+    HIPCHK(hipFuncSetAttribute((const void*)k_rec_cand<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    std::vector<int32_t> seq;
+    for (int64_t b0 = 0; b0 < n;) {
+        int64_t m = 1;
+        while (m < nb && b0 + m < n && cptr[b0 + m + 1] - cptr[b0] <= CAND_ITEMS) ++m;
+        const int64_t nc = cptr[b0 + m] - cptr[b0];
+        const int32_t* hu = h_users ? h_users + b0 : nullptr;
+        if (!hu) { seq.resize((size_t)m); for (int64_t i = 0; i < m; ++i) seq[(size_t)i] = (int32_t)(b0 + i); hu = seq.data(); }
+        if (dc.n < (size_t)nc) RC(dc.alloc((size_t)nc));
+        HIPCHK(hipMemcpyAsync(du.p, hu, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(dp.p, cptr + b0, (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        if (nc > 0) HIPCHK(hipMemcpyAsync(dc.p, citem + cptr[b0], (size_t)nc * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        {
+            ProfScope ps(v.prof, "recommend/candidates", st);
+            hipLaunchKernelGGL((k_rec_cand<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), lds, st, serve_U<T>(v), serve_V<T>(v), v.r, v.ld,
+                               (const int32_t*)du.p, m, (const int64_t*)dp.p, (const int32_t*)dc.p, v.allow, v.xptr(), v.xitem(), K, oi.p, os.p);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(items + b0 * K, oi.p, (size_t)m * K * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(scores + b0 * K, os.p, (size_t)m * K * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));                  // (the next batch overwrites du / dp / dc / seq)
+        b0 += m;
+    }
+    return PCR_OK;
+}
 
 static int no_more() { return PCR_OK; }
 // The end of an evaluation: the fixed-order sums over the n per-user rows met[n][ncut][6] into sums[ncut * 8 + 1] ([ncut][8], then the
@@ -671,6 +715,23 @@ static int serve_recommend(const ServeView& v, int64_t n, const int32_t* rows, i
         return rec_run<T>(v, n, rows, K, v.select, RecCopy<T>{v, K, items, scores});
     });
 }
+// filtered lists (pcr_recommend_filtered): the allow set is packed into 64-bit words (bit j & 63 of word
+// j >> 6) and hung on the view for this call; candidate lists take k_rec_cand alone, an allow set alone the sweep
+static int serve_recommend_filtered(ServeView v, int64_t n, const int32_t* rows, int K, const pcr_item_filter& f, int32_t* items, double* scores) {
+    if (n <= 0) return PCR_OK;
+    DBuf<unsigned long long> aw;
+    if (f.allow) {
+        std::vector<unsigned long long> w((size_t)((v.d2 + 63) >> 6), 0ull);
+        for (int64_t j = 0; j < v.d2; ++j) if (f.allow[j]) w[(size_t)(j >> 6)] |= 1ull << (j & 63);
+        RC(aw.upload(w, v.st));
+        v.allow = aw.p;
+    }
+    return by_precision(v, [&](auto zero) -> int {
+        using T = decltype(zero);
+        if (f.cand_ptr) return cand_run<T>(v, n, rows, f.cand_ptr, f.cand_item, K, items, scores);
+        return rec_run<T>(v, n, rows, K, 1, RecCopy<T>{v, K, items, scores});
+    });
+}
 // MMR re-ranked lists: per user, nothing is exchanged
 static int serve_recommend_diverse(const ServeView& v, int64_t n, const int32_t* rows, int topk, int pool, double theta, int32_t* items,
                                    double* scores) {
@@ -919,6 +980,37 @@ int pcr_recommend(pcr_solver* s, int64_t n, const int32_t* users, int topk, int 
         std::vector<int32_t> loc;
         RC(shard_rows("pcr_recommend", s, &n, users, loc));
         return serve_recommend(solver_view(s, flags), n, users ? loc.data() : nullptr, topk, items, scores);
+    });
+}
+
+int pcr_recommend_filtered(pcr_solver* s, int64_t n, const int32_t* users, int topk, int flags, const pcr_item_filter* f, int32_t* items,
+                           double* scores) {
+    S_OR_ARG;
+    if (topk < 1 || topk > PCR_RECOMMEND_MAX_K) { pcr_set_error("pcr_recommend_filtered: K = " + std::to_string(topk) + " outside [1, " + std::to_string(PCR_RECOMMEND_MAX_K) + "]"); return PCR_ERR_ARG; }
+    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_recommend_filtered: unknown flags"); return PCR_ERR_ARG; }
+    if (!users) n = s->n_users;
+    if (n < 0 || (n > 0 && (!items || !scores))) { pcr_set_error("pcr_recommend_filtered: bad argument"); return PCR_ERR_ARG; }
+    return abi_guard("pcr_recommend_filtered", [&]() -> int {
+        const ServeView v = solver_view(s, flags);
+        RC(pcr_item_filter_check("pcr_recommend_filtered", v.d2, n, users, f));
+        std::vector<int32_t> loc;
+        RC(shard_rows("pcr_recommend_filtered", s, &n, users, loc));
+        return serve_recommend_filtered(v, n, users ? loc.data() : nullptr, topk, *f, items, scores);
+    });
+}
+
+int pcr_recommend_filtered_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                                 int64_t n, const int32_t* users, int topk, int dtype, const pcr_item_filter* f, int32_t* items, double* scores,
+                                 int device) {
+    return abi_guard("pcr_recommend_filtered_model", [&]() -> int {
+    bool sorted = true;
+    RC(pcr_recommend_filtered_model_check(U, d1, V, d2, k, index, item, n, users, topk, dtype, f, items, scores, &sorted));
+    RC(model_device(device));
+    if (n == 0) return PCR_OK;
+    ServeView v;
+    ModelDev M;
+    RC(M.open(U, d1, V, d2, k, index, item, sorted, dtype, &v));
+    return serve_recommend_filtered(v, n, users, topk, *f, items, scores);
     });
 }
 

@@ -12,9 +12,11 @@
 //   the user's list (global scratch, staged through LDS) by rank counting and raises the threshold.  After the first few
 //   steps almost every score fails the threshold: one compare per score.
 //   Exclusion: training rows are item-ascending (duplicates allowed); each lane walks a cursor through its user's row and
-//   builds the 64-bit mask of the step's rated items -- O(nnz) in all.
+//   builds the 64-bit mask of the step's rated items -- O(nnz) in all.  With an allow set (pcr_recommend_filtered, DESIGN.md
+//   section 3.17) the complement of the step's word of the packed set is ORed into that mask: one wave-uniform 8-byte load per step.
 // k_rec_merge: one wave per user merges the partial lists of the item splits by rank counting (binary searches into the other
 //   lists), converts the scores to double and pads with (-1, -inf).
+// k_rec_cand: top-K over a candidate list per user (pcr_recommend_filtered with cand_ptr), one wave per user, below k_rec_merge.
 // k_rec_merge_topn: the same merge for the full-catalogue top-N evaluation (pcr_evaluate_topn): the list
 //   stays in LDS and is scored against the user's relevant test items; k_topn_sum1 / k_topn_fin reduce the per-user metrics.
 // k_rank_relscore / k_rank_sort / k_rank_count / k_rank_finish: the exact full-catalogue rank metrics (pcr_evaluate_ranks, DESIGN.md
@@ -106,7 +108,8 @@ __global__ __launch_bounds__(256) void k_rec_score(const T* __restrict__ U, cons
                                                    const int32_t* __restrict__ users, int64_t n,
                                                    const int64_t* __restrict__ xptr, const int32_t* __restrict__ xitem,
                                                    int K, int per_split, T* __restrict__ lst_s, int32_t* __restrict__ lst_i,
-                                                   int32_t* __restrict__ lst_n, int select) {
+                                                   int32_t* __restrict__ lst_n, int select,
+                                                   const unsigned long long* __restrict__ allow) {
     typedef RecMma<T> M;
     typedef typename M::acc_t acc_t;
     extern __shared__ __align__(16) char rec_lds[];
@@ -205,6 +208,7 @@ __global__ __launch_bounds__(256) void k_rec_score(const T* __restrict__ U, cons
             xm |= 1ull << (it - j0);
             ++cur;
         }
+        if (allow) xm |= ~allow[j0 >> 6];              // (j0 is a multiple of 64: the step is one word of the packed allow set)
 #pragma unroll
         for (int q = 0; q < rec::NQ; ++q) {
 #pragma unroll
@@ -276,6 +280,133 @@ __global__ __launch_bounds__(256) void k_rec_merge(const T* __restrict__ lst_s, 
         out_i[(size_t)idx * K + rk] = j; out_s[(size_t)idx * K + rk] = (double)s;
     });
     for (int p = min(tot, K) + lane; p < K; p += 64) { out_i[(size_t)idx * K + p] = -1; out_s[(size_t)idx * K + p] = -INFINITY; }
+}
+
+// LDS of one wave of k_rec_cand: the user's list scores [K], the survivor buffer's scores [CAP], the step's scores [TILE], the
+// list ids [K], the buffer ids [CAP]
+template <typename T>
+__host__ __device__ inline size_t cand_wave_lds(int K) {
+    const size_t b = (size_t)(K + rec::CAP + rec::TILE) * sizeof(T) + (size_t)(K + rec::CAP) * sizeof(int);
+    return (b + 15) & ~(size_t)15;
+}
+
+// Top-K over candidate lists (pcr_recommend_filtered with cand_ptr), one wave per user, four users per
+// workgroup: row idx of the candidate CSR (cptr[n + 1] absolute, citem based at cptr[0]; ids in any order, none twice in a row)
+// belongs to users[idx].  Each step scores 64 candidates through rec_score_tile -- all 16 columns of the tile are this one user
+// and column 0 is read, as k_rank_relscore does, so a score has the bits k_rec_score gives the same (user, item) -- and hands
+// candidate t0 + lane to lane `lane` through LDS.  A candidate is eligible when its bit of the packed allow set is on (allow
+// NULL: every item) and a binary search does not find it in the user's item-ascending training row (xptr NULL: no exclusion).
+// Selection is the sweep's: an eligible score that beats the threshold (the K-th list entry, in registers; nothing while the
+// list is short) goes to the 64-slot buffer at the position of its lane among the step's survivors (a prefix count of the
+// ballot: no atomic); when a step's survivors would not fit, and at the end, the buffer merges into the list by rank counting
+// under rec_better.  The list stays in the wave's LDS for the whole call and is merged in place: a list entry moves up by the
+// number of buffer entries before it, never down, so the wave shifts the list 64 entries at a time from its end (each chunk
+// is read before it is written, and a chunk writes at or above its own positions only), then drops the buffer entries into
+// their ranks.  The ids of a row are distinct, so the order is strict and a list is the same whatever the order of the row.
+// The tail converts to double and pads with (-1, -inf).  Every loop is bounded by K, by 64 or by the row's length.
+template <typename T>
+__global__ __launch_bounds__(256) void k_rec_cand(const T* __restrict__ U, const T* __restrict__ V, int r, int ld,
+                                                  const int32_t* __restrict__ users, int64_t n, const int64_t* __restrict__ cptr,
+                                                  const int32_t* __restrict__ citem, const unsigned long long* __restrict__ allow,
+                                                  const int64_t* __restrict__ xptr, const int32_t* __restrict__ xitem, int K,
+                                                  int32_t* __restrict__ out_i, double* __restrict__ out_s) {
+    typedef RecMma<T> M;
+    typedef typename M::acc_t acc_t;
+    extern __shared__ __align__(16) char rec_lds[];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + w;
+    if (idx >= n) return;                               // (the whole wave)
+    char* wl = rec_lds + (size_t)w * cand_wave_lds<T>(K);
+    T* ls = (T*)wl;
+    T* bs = ls + K;
+    T* stg = bs + rec::CAP;
+    int* li = (int*)(stg + rec::TILE);
+    int* bi = li + K;
+
+    const int m = lane & 15, g = lane >> 4;
+    const int u = users[idx];
+    const int64_t nc = cptr[idx + 1] - cptr[idx];
+    const int32_t* ci = citem + (cptr[idx] - cptr[0]);
+    int64_t xb = 0, xe = 0;
+    if (xptr) { xb = xptr[u]; xe = xptr[u + 1]; }
+    const T* Ur = U + (size_t)(unsigned)u * (unsigned)ld;
+    int len = 0, fill = 0;                              // (wave-uniform)
+    T ts = -INFINITY;
+    int ti = INT_MAX;
+
+    auto merge = [&]() {
+        const int B = fill, L = len;
+        T s = (T)0;
+        int j = 0, rk = K;
+        if (lane < B) {                                // a buffer entry: its rank among the buffer and the list as it stands
+            s = bs[lane]; j = bi[lane];
+            rk = 0;
+            for (int e = 0; e < B; ++e) rk += rec_better(bs[e], bi[e], s, j) ? 1 : 0;
+            int a = 0, b = L;
+            while (a < b) { const int mid = (a + b) >> 1; if (rec_better(ls[mid], li[mid], s, j)) a = mid + 1; else b = mid; }
+            rk += a;
+        }
+        for (int c = (L - 1) & ~63; L > 0 && c >= 0; c -= 64) {
+            const int p = c + lane;
+            T es = (T)0;
+            int ej = 0, erk = K;
+            if (p < L) {
+                es = ls[p]; ej = li[p];
+                erk = p;
+                for (int e = 0; e < B; ++e) erk += rec_better(bs[e], bi[e], es, ej) ? 1 : 0;
+            }
+            wave_sync();
+            if (erk < K) { ls[erk] = es; li[erk] = ej; }
+            wave_sync();
+        }
+        if (rk < K) { ls[rk] = s; li[rk] = j; }
+        wave_sync();
+        len = min(K, L + B);
+        fill = 0;
+        if (len == K) { ts = ls[K - 1]; ti = li[K - 1]; }
+    };
+
+    for (int64_t t0 = 0; t0 < nc; t0 += rec::TILE) {
+        const int64_t t = t0 + lane;
+        const int id = t < nc ? (int)ci[t] : -1;
+        int jr[rec::NQ];
+#pragma unroll
+        for (int q = 0; q < rec::NQ; ++q) jr[q] = __shfl(id, 16 * q + m);
+        acc_t acc[rec::NQ];
+        rec_score_tile<T>(Ur, true, V, r, ld, g, [&](int q) { return jr[q]; }, acc);
+        if (m == 0) {
+#pragma unroll
+            for (int q = 0; q < rec::NQ; ++q)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) stg[16 * q + M::crow(j, lane)] = acc[q][j];
+        }
+        wave_sync();
+        const T s = stg[lane];
+        bool ok = id >= 0;
+        if (ok && allow) ok = ((allow[id >> 6] >> (id & 63)) & 1ull) != 0;
+        if (ok && xe > xb) {
+            int64_t a = xb, b = xe;
+            while (a < b) { const int64_t mid = (a + b) >> 1; if (xitem[mid] < id) a = mid + 1; else b = mid; }
+            ok = !(a < xe && xitem[a] == id);
+        }
+        ok = ok && rec_better(s, id, ts, ti);
+        const unsigned long long pm = __ballot(ok);
+        const int c = __popcll(pm);
+        if (fill + c > rec::CAP) merge();              // (wave-uniform)
+        if (ok) {
+            const int p = fill + __popcll(pm & ((1ull << lane) - 1ull));
+            bs[p] = s; bi[p] = id;
+        }
+        fill += c;
+        wave_sync();
+    }
+    if (fill > 0) merge();
+    wave_sync();
+    for (int p = lane; p < K; p += 64) {
+        const bool have = p < len;
+        out_i[(size_t)idx * K + p] = have ? li[p] : -1;
+        out_s[(size_t)idx * K + p] = have ? (double)ls[p] : -INFINITY;
+    }
 }
 
 // Top-N evaluation (pcr_evaluate_topn): the relevance tables of the batch's users (offset to the batch), built on the host.

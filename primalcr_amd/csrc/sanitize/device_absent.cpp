@@ -70,6 +70,12 @@ int pcr_recommend_model(const double* U, int64_t d1, const double* V, int64_t d2
     return rc != PCR_OK ? rc : absent();
 }
 NO_SOLVER(pcr_recommend, pcr_solver*, int64_t, const int32_t*, int, int, int32_t*, double*)
+int pcr_recommend_filtered_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                                 int64_t n, const int32_t* users, int topk, int dtype, const pcr_item_filter* f, int32_t* items, double* scores, int) {
+    const int rc = pcr_recommend_filtered_model_check(U, d1, V, d2, k, index, item, n, users, topk, dtype, f, items, scores, nullptr);
+    return rc != PCR_OK ? rc : absent();
+}
+NO_SOLVER(pcr_recommend_filtered, pcr_solver*, int64_t, const int32_t*, int, int, const pcr_item_filter*, int32_t*, double*)
 int pcr_evaluate_topn_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
                             const int64_t* tindex, const int32_t* titem, const double* tval, int ncut, const int* cutoffs, double threshold,
                             int dtype, pcr_topn_stats* stats, double*, int) {
