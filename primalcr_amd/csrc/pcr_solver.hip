@@ -40,31 +40,7 @@
 #include "pcr_plan.h"
 #include "pcr_plan_dev.h"
 
-// users of one CSR grouped by length class; each class has its own workgroup size
-struct Bin {
-    int block = 64;
-    bool big = false;
-    int K = 1;           // workgroups per user (k_ustep clusters)
-    int ugrid = 0;       // k_ustep grid of this bin
-    int scratch_ofs = 0; // first global-scratch slice of this bin (big bins that run concurrently must not share slices)
-    int cap = 0;         // longest user in the bin
-    int limit = 0;       // upper length bound of the class (0: none)
-    int rcap = 0;        // k_ustep: rows of V a workgroup keeps resident in LDS
-    int unr = 4;         // k_ustep: rows in flight per lane group (8: latency-bound class, one workgroup per CU)
-    bool gram = false;   // k_ustep_gram: the dual (Gram-matrix, MFMA) form for users with few ratings
-    int wcap = 0;        // k_ustep: 16-bit window entries cached in LDS (cap * ws, or 0)
-    int sym = 0;         // k_ustep: symbol id (template parameter CLS) among the classes that run the same workgroup form
-    int max_lev = 0;
-    int64_t nnz = 0;     // ratings of the users in the bin
-    std::vector<int32_t> users;
-    DBuf<int32_t> d_users;
-};
-// length classes: one wave for short users, 256 threads up to 512 ratings, 512 threads up to 4096
-// (all with the user's block in LDS), longer users through global scratch.  512 rather than 1024
-// threads for the top classes: k_ustep needs more than the 128 VGPRs a 512-thread block may use.
-static const int BIN_LIMIT[3] = {128, 512, 4096};
-static const int BIN_BLOCK[4] = {64, 256, 512, 512};
-static const int GRAM_DEFAULT_CAP = 0;       // default length bound of the dual-form U-step class (0: off; pcr_tune "ustep_gram")
+#include "pcr_classes.h"
 
 // launch knobs: pcr_tune() values read once when the solver is created (include/primalcr.h lists them)
 struct Tune {
@@ -359,42 +335,6 @@ struct Solver final : pcr_solver {
     }
 
     // ------------------------------------------------------------------------------ setup
-    // users by rating count, longest first, ties in user order (what a stable sort by descending length gives): a counting sort,
-    // once per CSR -- every class layout below is then one pass over this list
-    static void length_order(const std::vector<int64_t>& uptr, int64_t nu, std::vector<int32_t>& order) {
-        order.resize((size_t)nu);
-        int64_t maxlen = 0;
-        for (int64_t u = 0; u < nu; ++u) maxlen = std::max(maxlen, uptr[u + 1] - uptr[u]);
-        if (maxlen > ((int64_t)1 << 24)) {
-            for (int64_t u = 0; u < nu; ++u) order[u] = (int32_t)u;
-            std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return (uptr[a + 1] - uptr[a]) > (uptr[b + 1] - uptr[b]); });
-            return;
-        }
-        std::vector<int64_t> start((size_t)maxlen + 2, 0);
-        for (int64_t u = 0; u < nu; ++u) start[(size_t)(maxlen - (uptr[u + 1] - uptr[u])) + 1]++;
-        for (int64_t l = 0; l <= maxlen; ++l) start[(size_t)l + 1] += start[(size_t)l];
-        for (int64_t u = 0; u < nu; ++u) order[(size_t)start[(size_t)(maxlen - (uptr[u + 1] - uptr[u]))]++] = (int32_t)u;
-    }
-    static void make_bins(const std::vector<int64_t>& uptr, int64_t nu, const std::vector<int64_t>* runofs, std::vector<Bin>& out,
-                          const std::vector<int32_t>& order,
-                          const std::vector<int>& limits = {BIN_LIMIT[0], BIN_LIMIT[1], BIN_LIMIT[2]},
-                          const std::vector<int>& blocks = {BIN_BLOCK[0], BIN_BLOCK[1], BIN_BLOCK[2], BIN_BLOCK[3]}) {
-        const int nb = (int)limits.size() + 1;
-        out.clear();
-        out.resize(nb);
-        for (int b = 0; b < nb; ++b) { out[b].block = blocks[b]; out[b].big = (b == nb - 1); out[b].limit = b < nb - 1 ? limits[b] : 0; }
-        for (int64_t q = 0; q < nu; ++q) {       // longest first: the tail of a launch is made of short users
-            const int32_t u = order[(size_t)q];
-            int64_t len = uptr[u + 1] - uptr[u];
-            int b = 0;
-            while (b < nb - 1 && len > limits[b]) ++b;
-            out[b].users.push_back(u);
-            out[b].nnz += len;
-            out[b].cap = std::max<int>(out[b].cap, (int)len);
-            if (runofs) out[b].max_lev = std::max<int>(out[b].max_lev, (int)((*runofs)[u + 1] - (*runofs)[u]) - 1);
-        }
-    }
-
     // The SpMM plan: tiles / chunk lists / workgroup map on the host (pcr_plan.h), the tile-major CSC, flags and slab rows on the
     // device (pcr_plan_dev.h) from d_uptr / d_item.  Fills d_ruser, d_c2r, d_crow, d_cuser, d_cuf, d_chunk_ptr, d_slot_base,
     // d_slot_id, d_item_slot, d_blk_chunks and P's host-side fields.
@@ -522,12 +462,17 @@ struct Solver final : pcr_solver {
     }
 #endif
 
-    // shard_first >= 0: `ds` holds ONLY this rank's users (renumbered from 0) -- users [shard_first, shard_first + ds.d1) of a
-    // job with d1_total users (pcr_solver_create_shard); else the whole data set, partitioned here by pcr_partition_users
-    int init(const pcr_dataset* ds, const pcr_params* p, int rank_, int nranks_, int64_t shard_first = -1, int64_t d1_total = 0) {
-        prm = *p; rank = rank_; nranks = nranks_;
-        const auto t_init = std::chrono::steady_clock::now();
-        tune.read();
+    // ---- the phases of init(), in the order it runs them
+    // the host-side picture of this rank's shard that the phases share (gone when init returns)
+    struct HostShard {
+        int64_t u0 = 0;                   // this rank's first user inside the data set's arrays
+        std::vector<int64_t> uptr;
+        const int32_t* item = nullptr;    // (the data set's own array: uploaded from where it lies)
+        PcrLevels lv;
+        std::vector<int32_t> by_len;
+    };
+    // the device, the solver's streams and events; side_maker: the helper thread that creates the first side streams meanwhile
+    int open_device(std::thread& side_maker) {
         if (prm.cg_max_iter == 0) prm.cg_max_iter = 10;      // zero-filled extension fields = the reference's constants
         if (prm.cg_tol == 0.0) prm.cg_tol = 0.01;
         if (prm.cg_max_iter < 0 || prm.cg_max_iter > 100000 || !(prm.cg_tol > 0.0)) { pcr_set_error("cg_max_iter / cg_tol out of range"); return PCR_ERR_ARG; }
@@ -555,8 +500,6 @@ struct Solver final : pcr_solver {
         // not twelve -- a stream is 4-5 ms of set-up and a hardware queue of the device.  The first four, which every default
         // layout ends up creating, come up on a helper thread while this one prepares and uploads the shard: 20 ms of the set-up's
         // 80 on the ml1m shape, profiles/r06_cli_create.txt.)
-        std::thread side_maker;
-        struct JoinSide { std::thread& t; ~JoinSide() { if (t.joinable()) t.join(); } } join_side{side_maker};
         if (tune.lanes != 1) {
             const int want = tune.lanes > 0 ? std::min(MAXLANE, tune.lanes) : 4;
             side_maker = std::thread([this, dev = prm.device, n = std::min(NSIDE, want)]() {
@@ -565,7 +508,10 @@ struct Solver final : pcr_solver {
                     if (hipStreamCreateWithFlags(&side[c], hipStreamNonBlocking) != hipSuccess) { side[c] = nullptr; (void)hipGetLastError(); return; }
             });
         }
-
+        return PCR_OK;
+    }
+    // the factor geometry and this rank's user range
+    int shard_bounds(const pcr_dataset* ds, int64_t shard_first, int64_t d1_total, HostShard& H) {
         const PcrCsr& X = ds->train;
         d1 = X.d1; d2 = X.d2; tnnz_file = ds->tnnz_file;
         if (prm.k < 1) { pcr_set_error("rank k must be >= 1"); return PCR_ERR_ARG; }
@@ -575,7 +521,6 @@ struct Solver final : pcr_solver {
         geo.nchunk = geo.ld / VecOf<T>::N;
         geo.G = std::min(64, host_pow2(geo.nchunk));
 
-        int64_t ds_u0 = 0;                                   // this rank's first user inside the data set's arrays
         if (shard_first >= 0) {
             if (d1_total < shard_first + X.d1 || d1_total >= (int64_t)1 << 31) { pcr_set_error("pcr_solver_create_shard: the shard does not fit the job's user range"); return PCR_ERR_ARG; }
             if (ds->test.d1 != X.d1) { pcr_set_error("pcr_solver_create_shard: train and test user counts differ"); return PCR_ERR_ARG; }
@@ -585,39 +530,16 @@ struct Solver final : pcr_solver {
             RC(pcr_partition_users(X.index.data(), d1, nranks, bounds.data()));
             first_user = bounds[rank];
             n_users = bounds[rank + 1] - bounds[rank];
-            ds_u0 = first_user;
+            H.u0 = first_user;
         }
-        const int64_t z0 = X.index[ds_u0], z1 = X.index[ds_u0 + n_users];
-        nnz_local = z1 - z0;
+        nnz_local = X.index[H.u0 + n_users] - X.index[H.u0];
         if (nnz_local >= ((int64_t)1 << 31) - 1) { pcr_set_error("more than 2^31 ratings on one GPU"); return PCR_ERR_UNSUPPORTED; }
+        return PCR_OK;
+    }
+    // pcr_tune("vblock_users"): the users the dense V-step kernels take out of the sparse plan
+    int pick_blocked_users(const HostShard& H) {
+        const std::vector<int64_t>& uptr = H.uptr;
         const int64_t nu = n_users;
-
-        // (pcr_tune("debug"): wall time of the set-up phases)
-        // wall time of the set-up phases: kept (pcr_solver_setup_phase; omp-pmf-train --timing prints them), printed with pcr_tune("debug")
-        auto t_phase = t_init;
-        auto phase = [&](const char* what) {
-            const auto now = std::chrono::steady_clock::now();
-            const double ms = std::chrono::duration<double, std::milli>(now - t_phase).count();
-            setup_ms.emplace_back(what, ms);
-            if (tune.debug) fprintf(stderr, "[pcr] set-up: %-28s %8.1f ms\n", what, ms);
-            t_phase = now;
-        };
-        phase("device, streams, events");
-        // ---- host-side shard preparation
-        std::vector<int64_t> uptr(nu + 1);
-        for (int64_t u = 0; u <= nu; ++u) uptr[u] = X.index[ds_u0 + u] - z0;
-        const int32_t* item = X.item.data() + z0;            // (the data set's own array: uploaded from where it lies)
-        PcrLevels lv;
-        std::string err;
-        phase("copy CSR");
-        int rc = pcr_build_levels(X, ds_u0, ds_u0 + nu, prm.solver_type, lv, err);
-        if (rc != PCR_OK) { pcr_set_error(err); return rc; }
-        phase("levels");
-        // the shard's CSR goes up first: the nnz-sized part of the SpMM plan is built from it on the device (pcr_plan_dev.h)
-        RC(d_uptr.upload(uptr, st)); RC(d_item.upload_n(item, (size_t)nnz_local));
-        phase("CSR upload");
-        std::vector<int32_t> by_len;
-        length_order(uptr, nu, by_len);
         if (tune.vblock_users > 0 && nu > 0) {
             // The blocked-user V step (pcr_vblock.h): the users with the most ratings -- at most vblock_users of them, those that rate
             // at least a sixteenth of the catalogue -- go through dense MFMA kernels; the sparse plan leaves their ratings out.
@@ -628,13 +550,13 @@ struct Solver final : pcr_solver {
             std::vector<int32_t> blk;
             std::vector<int32_t> cpos;
             for (int64_t q = 0; q < nu && (int64_t)blk.size() < blk_cap; ++q) {
-                const int32_t u = by_len[(size_t)q];
+                const int32_t u = H.by_len[(size_t)q];
                 if ((uptr[u + 1] - uptr[u]) * 16 < d2) break;
                 const size_t row = blk.size() * (size_t)d2;
                 cpos.resize(row + (size_t)d2, -1);
                 bool dup = false;
                 for (int64_t z = uptr[u]; z < uptr[u + 1] && !dup; ++z) {
-                    int32_t& slot = cpos[row + (size_t)item[z]];
+                    int32_t& slot = cpos[row + (size_t)H.item[z]];
                     dup = slot != -1;
                     slot = (int32_t)z;
                 }
@@ -656,9 +578,13 @@ struct Solver final : pcr_solver {
                                         (int)std::count(excl.begin(), excl.end(), 1), vblock_nbp, (long long)d2);
             }
         }
+        return PCR_OK;
+    }
+    // the SpMM plan (build_plan), its item-range streams, the slab, and which CSC the CG's SDDMM walks
+    int adopt_plan(const HostShard& H) {
         SpmmPlan P;
         // (a block left out of the sparse plan: one item range -- the dense kernels add their share before the one exchange)
-        const SpmmPlanIn plan_in{uptr, item, nu, nnz_local, d2, geo.ld, geo.G, ncu, sizeof(T), tune.spmm_chunk, tune.spmm_tiles, vblock_nbp ? 0 : tune.allreduce_chunks};
+        const SpmmPlanIn plan_in{H.uptr, H.item, n_users, nnz_local, d2, geo.ld, geo.G, ncu, sizeof(T), tune.spmm_chunk, tune.spmm_tiles, vblock_nbp ? 0 : tune.allreduce_chunks};
         RC(build_plan(plan_in, P));
         spmm_chunk = P.chunk; n_rng = P.n_rng; rng_item = P.rng_item; rng_blk = P.rng_blk; spmm_blocks = P.blocks; spmm_tiles = P.ntiles;
         if (n_rng > 1) {          // the all-reduce of a finished item range runs on its own stream (launch_spmm)
@@ -671,194 +597,53 @@ struct Solver final : pcr_solver {
         sddmm_csc = (size_t)d2 * geo.ld * sizeof(T) > ((size_t)32 << 20) && spmm_tiles >= 8;     // item table larger than all L2s together
         if (tune.sddmm_csc >= 0) sddmm_csc = tune.sddmm_csc != 0;
         if (vblock_nbp) sddmm_csc = true;                          // the CG's SDDMM walks the plan (which leaves the block out), b in CSR order
-        phase("tile-major CSC, slab plan");
-        make_bins(uptr, nu, &lv.run_ofs, bins, by_len);
+        return PCR_OK;
+    }
+    // V side: the general classes (bins), the sweep classes (sbins), the prepare classes (pbins)
+    int setup_vside_classes(const HostShard& H) {
+        const int64_t nu = n_users;
+        make_bins(H.uptr, nu, &H.lv.run_ofs, bins, H.by_len);
         for (auto& b : bins) RC(b.d_users.upload(b.users, st));
-        // sweep / prepare classes: class 0 = one wave per user, class 1 = one 512-thread workgroup, class 2 = global scratch.
-        // The sweeps keep 12 B per rating in LDS.  Where to cut between "a wave per user, eight users per workgroup" and "a
-        // workgroup per user": a higher cut turns whole workgroups into waves (fewer workgroups to run through the CUs) but
-        // lengthens the one-wave chains and, past 384, the LDS of eight waves leaves 3 instead of 4 workgroups per CU.
-        // Cost model = rounds of workgroups through the chip x (1 + cut / 1024), over the candidate cuts (measured: ml1m 256:
-        // 20.4-22.7 us per sweep, 320: 19.4, 384: 20.1-21.0, 512: 25.9; 10 M-rating Netflix-shaped slice 256: 181, 512: 163).
-        int sweep_wave_cap = 256;
-        {
-            std::vector<int64_t> lens(nu);               // ascending
-            for (int64_t q = 0; q < nu; ++q) { const int32_t u = by_len[(size_t)(nu - 1 - q)]; lens[q] = uptr[u + 1] - uptr[u]; }
-            const int64_t max_lds = std::upper_bound(lens.begin(), lens.end(), (int64_t)4096) - lens.begin();     // users that fit LDS
-            const int64_t cap_b = max_lds > 0 ? lens[max_lds - 1] : 0;
-            double best = 0.0;
-            for (int c : {256, 320, 384, 448, 512}) {
-                const int64_t n_wave = std::upper_bound(lens.begin(), lens.end(), (int64_t)c) - lens.begin();
-                const int64_t n_blk = std::max<int64_t>(0, max_lds - n_wave);
-                const size_t wave_lds = 8 * ((size_t)c * sizeof(T) + (size_t)(c + 1) * 8 + 64);
-                const size_t blk_lds = n_blk > 0 ? (size_t)cap_b * sizeof(T) + (size_t)(cap_b + 1) * 8 + 1024 : 0;
-                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, ((size_t)160 << 10) / std::max<size_t>(1, std::max(wave_lds, blk_lds))));
-                const double rounds = (double)(cdiv(n_wave, 8) + n_blk) / ((double)ncu * per_cu);
-                const double cost = std::max(rounds, 1.0) * (1.0 + c / 1024.0);
-                if (best == 0.0 || cost < best) { best = cost; sweep_wave_cap = c; }
-            }
-        }
+        const int sweep_wave_cap = pick_sweep_wave_cap<T>(H.uptr, nu, H.by_len, ncu);
         if (tune.debug) fprintf(stderr, "[pcr] sweep wave cap %d\n", sweep_wave_cap);
-        make_bins(uptr, nu, &lv.run_ofs, sbins, by_len, {std::min(sweep_wave_cap, 4095), 4096}, {64, 512, 512});
+        make_bins(H.uptr, nu, &H.lv.run_ofs, sbins, H.by_len, {std::min(sweep_wave_cap, 4095), 4096}, {64, 512, 512});
         for (auto& b : sbins) RC(b.d_users.upload(b.users, st));
         const int prep_wave_cap = 256;
-        make_bins(uptr, nu, &lv.run_ofs, pbins, by_len, {prep_wave_cap, 4096}, {64, 512, 512});
+        make_bins(H.uptr, nu, &H.lv.run_ofs, pbins, H.by_len, {prep_wave_cap, 4096}, {64, 512, 512});
         for (auto& b : pbins) RC(b.d_users.upload(b.users, st));
         // (measured, ml1m: 1024-thread teams make both launches slower -- k_vsweep_all 23 -> 31 us, k_prepare_all 99 -> 133 us:
         // sixteen one-wave users per workgroup cost more occupancy than the longest user's chain gains -- so 512 stays)
         sweep_pf4 = true;
-        // U step: users with more than 1024 ratings are bound by one CU's gather bandwidth -> clusters of 4 workgroups
-        // The U step keeps each user's rows of V in LDS (k_ustep, stage_rows), so its occupancy is set by LDS bytes, not
-        // registers: finer length classes than the V side, and a workgroup size that grows with the class.
-        // pcr_tune("ubins", "cap:block:resident,...") overrides the classes below 1024.
-        // Measured (ml1m shape, k = 100): residency pays for users of <= 32 ratings (13 KB of rows: 10 one-wave workgroups
-        // per CU still fit); above that the LDS image costs more occupancy than the faster passes gain -- the 33..64 class
-        // was resident until its non-resident form got leaner (108 VGPRs against 124): 1.622 -> 1.604 ms, 10 M-rating
-        // Netflix-shaped slice 82.5 -> 80.9 ms over 4 iterations; 65..128 resident: 1.80 ms -- so those classes gather from
-        // the L2s with 16 waves per CU.
-        std::vector<int> ucap = {32, 64, 128, 512}, ublk = {64, 64, 64, 256}, ures = {1, 0, 0, 0};
-        if (const char* e = tune.ubins.empty() ? nullptr : tune.ubins.c_str()) {                 // "cap:block:resident,..."
-            ucap.clear(); ublk.clear(); ures.clear();
-            for (const char* q = e; *q;) {
-                int c = 0, bl = 0, rs = 1, used = 0;
-                if (sscanf(q, "%d:%d:%d%n", &c, &bl, &rs, &used) != 3 || (bl != 64 && bl != 256) || c < 1 || c >= 1024 || (rs && bl != 64) ||
-                    (!ucap.empty() && c <= ucap.back())) { pcr_set_error("bad pcr_tune ubins"); return PCR_ERR_ARG; }
-                ucap.push_back(c); ublk.push_back(bl); ures.push_back(rs);
-                q += used; if (*q == ',') ++q;
-            }
-        }
-        // Dual form (pcr_gram.h): users with at most gram_cap ratings run k_ustep_gram -- one class in place of the one-wave
-        // classes.  gram_cap = pcr_tune("ustep_gram") or the largest count whose LDS (row image / Gram matrix + n-vectors)
-        // still lets two workgroups share a CU, at most 128 (fp64: 64).
-        int gram_cap = 0;
-        if (tune.ustep_gram != 0 && tune.ubins.empty()) {
-            const int hard = sizeof(T) == 4 ? 128 : 64;
-            const int want = tune.ustep_gram > 0 ? std::min(tune.ustep_gram, hard) : GRAM_DEFAULT_CAP;
-            const int nchp0 = geo.nchunk | 1;
-            for (int c = want; c >= 16; c -= 8)
-                if (gram_bytes<T>(c, host_pow2(c), lv.max_levels + 2, geo.ld, nchp0, 256) <= (tune.ustep_gram > 0 ? (size_t)160 : (size_t)80) * 1024) { gram_cap = c; break; }
-            if (lv.max_levels > 64) gram_cap = 0;              // (real-valued ratings under PrimalCR: a level per rating -- keep the general kernel)
-        }
-        size_t ngram = 0;
-        if (gram_cap > 64) { ucap = {64, gram_cap, 512}; ublk = {64, 256, 256}; ures = {0, 0, 0}; ngram = 2; }       // one wave up to 64 ratings
-        else if (gram_cap > 0) { ucap = {gram_cap, 512}; ublk = {64, 256}; ures = {0, 0}; ngram = 1; }
-        const size_t nsmall = ucap.size();
-        // Latency or throughput?  A class with few users is one round of workgroups and is bound by the per-user dependency
-        // chain: 512 threads, 8 rows in flight per lane group, 174-205 VGPRs = one workgroup per CU.  A class with many users
-        // is bound by how busy each CU's memory pipe stays: smaller / leaner workgroups, so that two share a CU and one
-        // gathers while the other scans or sorts (<= 1024 ratings: 256 threads; above: 512 threads at 4 rows in flight =
-        // 124 VGPRs, and a class boundary at 2048 so that the per-rating arrays of two fit the LDS).  "Many" is more than
-        // CUs/4 users: the greedy one-per-CU workgroups of all long classes together must leave CUs for the short classes
-        // (ml1m: 88 + 221 users in throughput form 2.09 -> 2.03 ms per iteration; Netflix shape: U step 87 -> 69 ms).
-        const int force_mode = tune.ustep_mode;                                                  // 1 latency, 2 throughput
-        const int64_t many_users = std::max<int64_t>(1, ncu / 4);
-        auto many = [&](int64_t users) { return force_mode ? force_mode == 2 : users > many_users; };
-        int64_t n_mid = 0;
-        for (int64_t u = 0; u < nu; ++u) { const int64_t len = uptr[u + 1] - uptr[u]; n_mid += len > 1024 && len <= 4096; }
-        ucap.push_back(1024); ublk.push_back(512);
-        if (many(n_mid)) { ucap.push_back(2048); ublk.push_back(512); }
-        ucap.push_back(4096); ublk.push_back(512); ublk.push_back(512);
-        make_bins(uptr, nu, &lv.run_ofs, ubins, by_len, ucap, ublk);
-        for (size_t q = 0; q < ngram; ++q) ubins[q].gram = true;
-        // Workgroup clusters trade throughput for latency: only the longest users of the shard (the critical path, more than
-        // 1024 ratings) get them, ncu/(4K) users (all their workgroups fit the chip at once, see below) -- ONE extra class
-        // whatever length class they came from (in global scratch if any of them needs it).  pcr_tune("cluster_k", "1") disables.
-        int cluster_k = 4;
-        if (tune.cluster_k != 4) cluster_k = 1;
-        max_clusters = std::max(1, ncu / 2);
-        if (cluster_k > 1) {
-            Bin head;
-            head.block = 512; head.K = cluster_k;
-            // ncu / (4K) users = a quarter of the CUs: every cluster workgroup keeps a CU to itself (its LDS image) for the
-            // whole launch, CUs the many short users cannot use meanwhile -- ml1m: 8 users 1.610 ms, 12-20: 1.59-1.61, 24: 1.63,
-            // 32: 1.645, 48: 1.79 per iteration; 10 M-rating Netflix-shaped slice: U step 7.24 (32) -> 6.98 ms (16)
-            size_t budget = (size_t)std::max(1, ncu / (4 * cluster_k));
-            if (tune.cluster_users > 0) budget = (size_t)std::max(1, std::min(tune.cluster_users, ncu / cluster_k));
-            for (size_t q = ubins.size(); q-- > nsmall + 1 && budget > 0;) {       // longest class first; users are sorted longest first
-                Bin& b = ubins[q];
-                const size_t take = std::min(budget, b.users.size());
-                if (take == 0) continue;
-                budget -= take;
-                head.big = head.big || b.big;
-                head.max_lev = std::max(head.max_lev, b.max_lev);
-                for (size_t i = 0; i < take; ++i) {
-                    const int32_t u = b.users[i];
-                    const int64_t len = uptr[u + 1] - uptr[u];
-                    head.users.push_back(u); head.nnz += len; head.cap = std::max<int>(head.cap, (int)len);
-                    b.nnz -= len;
-                }
-                b.users.erase(b.users.begin(), b.users.begin() + take);
-                b.cap = b.users.empty() ? 0 : (int)(uptr[b.users[0] + 1] - uptr[b.users[0]]);
-            }
-            if (!head.users.empty()) ubins.push_back(std::move(head));
-        }
-        for (size_t q = nsmall; q < ubins.size(); ++q) {
-            Bin& b = ubins[q];
-            // (a class whose per-rating arrays fill more than half the LDS runs one workgroup per CU whatever its register
-            // count: it keeps the 8-rows-in-flight form)
-            const bool lds_bound = !b.big && ustep_big_bytes<T>(b.cap, host_pow2(b.cap), b.max_lev + 2, 4) > 72 * 1024;
-            if (b.K > 1 || lds_bound || !many((int64_t)b.users.size())) { b.unr = 8; continue; }
-            b.unr = 4;
-            // (re-checked in round 3 for a 513..1024 class of 200 users, one round of workgroups: 256 threads at 8 rows in flight
-            // 1.49 -> 1.69 ms per ml1m step, 512 threads at 4 rows: no change)
-            if (b.limit == 1024 && !b.big) b.block = 256;
-        }
-        // A class whose per-rating arrays + r-vectors do not fit the 160 KB of LDS (fp64 at wide ranks with users near 4096
-        // ratings, or thousands of rating levels under PrimalCR) runs the global-scratch form of the kernel instead.
-        for (auto& b : ubins) {
-            if (b.big || b.users.empty() || b.gram) continue;
-            const size_t fixed = ustep_small_bytes(geo.ld, b.block, sizeof(T)) + ustep_big_bytes<T>(b.cap, host_pow2(b.cap), b.max_lev + 2, 4);
-            if (fixed > (size_t)160 * 1024) { b.big = true; b.block = 512; }
-        }
-        // the one-wave and 256-thread classes keep 4 rows in flight per lane group (8 measured on ml1m: the one-wave classes alone
-        // 1.58 -> 1.67 ms per step, the 256-thread classes too 1.89 ms; Netflix shape U step 52 -> 68 ms: the registers cost more
-        // occupancy than the deeper gathers gain)
-        for (size_t q = 0; q < nsmall && q < ubins.size(); ++q)
-            if (!ubins[q].gram && !ubins[q].users.empty()) ubins[q].unr = 4;
-        u_big_blocks = 0;
-        for (auto& b : ubins) {
-            const int nus = (int)b.users.size();
-            b.ugrid = b.K > 1 ? std::min(nus, std::max(1, ncu / b.K)) * b.K : (b.big ? std::min(nus, 2 * ncu) : nus);
-            if (b.big) { b.scratch_ofs = u_big_blocks; u_big_blocks += b.ugrid; }
-        }
-        // window cache (pcr_kernels.h, Shard::win): one slot per other level, up to 9 levels
-        const int sh_ws_for_bins = (tune.window_cache && lv.max_levels >= 2 && lv.max_levels <= 9) ? lv.max_levels - 1 : 0;
-        {   // LDS residency: what is left of the 160 KB after the r-vectors and the per-rating arrays, in rows of V
-            const int nchp = geo.nchunk | 1;
-            // (capping the image at 128 / 112 / 96 / 64 KB, so that workgroups of the short classes could share the CU, changes
-            // nothing: ml1m 1.424-1.438 ms per step at every cap, Netflix-shaped U step 62.6-62.8 ms -- NOTES.md round 4)
-            const size_t lim = 160 * 1024;
-            for (size_t bi = 0; bi < ubins.size(); ++bi) {
-                Bin& b = ubins[bi];
-                if (b.users.empty() || b.gram) continue;
-                // the LDS image pays where LDS is spare: the one-wave classes of <= 64 ratings, and the latency-bound
-                // 512-thread classes (one workgroup per CU anyway), which keep as many rows as fit beside their arrays
-                const int res_on = bi < nsmall ? (b.block == 64 ? ures[bi] : 0) : (b.unr == 8);
-                // the window rows of the class's longest user in LDS (16 bit), where that still leaves the class its occupancy:
-                // every class of at most 1024 ratings (8 KB), the one-workgroup-per-CU classes whatever their length
-                b.wcap = 0;
-                if (tune.ustep_win_lds && !b.big && sh_ws_for_bins > 0 && (b.cap <= 1024 || b.unr == 8) &&
-                    ustep_small_bytes(geo.ld, b.block, sizeof(T)) + ustep_big_bytes<T>(b.cap, host_pow2(b.cap), b.max_lev + 2, 4) +
-                        carve_bytes((size_t)b.cap * sh_ws_for_bins, 2) <= lim - 8 * 1024)
-                    b.wcap = b.cap * sh_ws_for_bins;
-                const size_t fixed = ustep_small_bytes(geo.ld, b.block, sizeof(T)) + carve_bytes(b.wcap, 2) +
-                                     (b.big ? 0 : ustep_big_bytes<T>(b.cap, host_pow2(b.cap), b.max_lev + 2, 4));
-                const int64_t room = fixed < lim ? (int64_t)((lim - fixed) / ((size_t)nchp * 16)) : 0;
-                const int64_t want = (b.cap + b.K - 1) / b.K;                  // longest slice a member gathers
-                b.rcap = res_on ? (int)std::max<int64_t>(0, std::min(room, want)) : 0;
-            }
-        }
+        return PCR_OK;
+    }
+    // U step: the class layout (pcr_classes.h), then what it sizes on the device
+    int setup_ustep_classes(const HostShard& H) {
+        UstepLayout L;
+        std::string err;
+        const int rc = ustep_class_layout<T>({H.uptr, n_users, H.lv.run_ofs, H.by_len, H.lv.max_levels, geo.ld, geo.nchunk, ncu, tune.ubins, tune.ustep_gram,
+                                              tune.ustep_mode, tune.cluster_k, tune.cluster_users, tune.window_cache, tune.ustep_win_lds}, L, err);
+        if (rc != PCR_OK) { pcr_set_error(err); return rc; }
+        ubins = std::move(L.ubins);
+        u_big_blocks = L.u_big_blocks; max_clusters = L.max_clusters; xch_stride = L.xch_stride; bar_n = L.bar_n;
+        sh.ws = L.ws;
         for (auto& b : ubins) RC(b.d_users.upload(b.users, st));
+        RC(d_xch.alloc(xch_stride * (size_t)max_clusters * ubins.size()));
+        RC(d_rowcnt.alloc(ubins.size()));
+        HIPCHK(hipMemset(d_rowcnt.p, 0, std::max<size_t>(ubins.size(), 1) * sizeof(unsigned long long)));
+        return PCR_OK;
+    }
+    int setup_newton(const HostShard& H) {
+        const int64_t nu = n_users;
         if (tune.ustep_newton && geo.ld <= NEWTON_MAX_LD) {
             // the exact-Newton mode (pcr_newton.h): users of 1 .. NEWTON_MAX_N ratings get their direction from the explicit Hessian
             std::vector<int32_t> nus_list;
             for (int64_t q = 0; q < nu; ++q) {
-                const int32_t u = by_len[(size_t)q];
-                const int64_t len = uptr[u + 1] - uptr[u];
+                const int32_t u = H.by_len[(size_t)q];
+                const int64_t len = H.uptr[u + 1] - H.uptr[u];
                 if (len >= 1 && len <= NEWTON_MAX_N) { nus_list.push_back(u); newton_cap = std::max<int>(newton_cap, (int)len); }
             }
             newton_n = (int)nus_list.size();
-            newton_rs = lv.max_levels + 2;
+            newton_rs = H.lv.max_levels + 2;
             RC(d_newton_users.upload(nus_list, st));
             RC(d_dir.alloc((size_t)std::max<int64_t>(nu, 1) * geo.ld));
             const int ldp = (geo.ld + 15) & ~15;
@@ -870,34 +655,13 @@ struct Solver final : pcr_solver {
 #endif
             if (tune.debug) fprintf(stderr, "[pcr] exact-Newton U step: %d of %lld users through the explicit Hessian (<= %d ratings)\n", newton_n, (long long)nu, NEWTON_MAX_N);
         }
-        {
-            size_t need_x = 0;
-            for (auto& b : ubins)
-                if (b.K > 1 && !b.users.empty()) need_x = std::max(need_x, ustep_xch_bytes<T>(host_pow2(b.cap), geo.ld, b.K));
-            xch_stride = (need_x + 255) & ~(size_t)255;
-            bar_n = (size_t)max_clusters * ubins.size();               // the classes run concurrently: one set per class
-            RC(d_xch.alloc(xch_stride * (size_t)max_clusters * ubins.size()));
-            RC(d_rowcnt.alloc(ubins.size()));
-            HIPCHK(hipMemset(d_rowcnt.p, 0, std::max<size_t>(ubins.size(), 1) * sizeof(unsigned long long)));
-        }
-        {   // two length classes that run the same workgroup form get kernel symbols of their own (k_ustep's CLS), so that
-            // rocprofv3's per-symbol durations and PMC bytes belong to one class each
-            std::map<std::string, int> seen;
-            for (auto& b : ubins) {
-                if (b.users.empty() || b.gram) continue;
-                const std::string key = std::to_string(b.block) + (b.big ? "g" : "") + "k" + std::to_string(b.K) + (b.rcap > 0 ? "r" : "") + "u" + std::to_string(b.unr);
-                const bool two = !b.big && b.K == 1 && b.rcap == 0 && b.unr == 4;       // the forms instantiated twice (set_lds_limits)
-                b.sym = two ? (seen[key]++ & 1) : 0;
-                // the 512-thread throughput form: symbol 0 is the register-capped one (two workgroups per CU), compiled for at most
-                // half a CU's LDS; a class that needs more LDS than that takes symbol 1 (pcr_kernels.h, k_ustep)
-                if (two && b.block == 512 && sizeof(T) == 4)
-                    b.sym = ustep_small_bytes(geo.ld, b.block, sizeof(T)) + carve_bytes(b.wcap, 2) + ustep_big_bytes<T>(b.cap, host_pow2(b.cap), b.max_lev + 2, 4) > (size_t)80 * 1024 ? 1 : 0;
-            }
-        }
-
-        phase("length classes");
-        RC(d_lvl.upload(lv.level, st));
-        RC(d_runofs.upload(lv.run_ofs, st)); RC(d_runstart.upload(lv.run_start, st));
+        return PCR_OK;
+    }
+    // the level tables, the per-rating state arrays and the Shard the kernels read them through
+    int setup_state(const HostShard& H) {
+        const int64_t nu = n_users;
+        RC(d_lvl.upload(H.lv.level, st));
+        RC(d_runofs.upload(H.lv.run_ofs, st)); RC(d_runstart.upload(H.lv.run_start, st));
         RC(d_ms.alloc(nnz_local)); RC(d_sitem.alloc(nnz_local)); RC(d_slvl.alloc(nnz_local));
         RC(d_c.alloc(nnz_local)); RC(d_objp.alloc(nu)); RC(d_mcsr.alloc(nnz_local)); RC(d_b.alloc(nnz_local));
         sh.nu = nu; sh.nnz = nnz_local; sh.d2 = (int)d2;
@@ -906,7 +670,6 @@ struct Solver final : pcr_solver {
         sh.ms = d_ms.p; sh.sitem = d_sitem.p; sh.slvl = d_slvl.p; sh.objp = d_objp.p;
         RC(d_sidx.alloc(nnz_local)); RC(d_objr.alloc(nu));
         sh.sidx = d_sidx.p; sh.objr = d_objr.p;
-        sh.ws = sh_ws_for_bins;
         sh.resort_d = std::max(0, std::min(tune.resort_window, 64));
         sh.prev_valid = 0;                                  // set once the first k_prepare of the solver's life has been queued
         RC(d_rhint.alloc(std::max<int64_t>(nu, 1)));
@@ -914,94 +677,94 @@ struct Solver final : pcr_solver {
         sh.rhint = d_rhint.p;
         {
             int64_t longest = 0;
-            for (int64_t u = 0; u < nu; ++u) longest = std::max(longest, uptr[u + 1] - uptr[u]);
+            for (int64_t u = 0; u < nu; ++u) longest = std::max(longest, H.uptr[u + 1] - H.uptr[u]);
             sh.w16 = (longest < 65536 && tune.win16) ? 1 : 0;
         }
         RC(d_win.alloc((size_t)nnz_local * sh.ws * (sh.w16 ? 1 : 2)));
         sh.win = d_win.p;
-
-        phase("uploads, state arrays");
-        // ---- eval sets (train shard, test shard)
-        // The evaluator compares RAW ratings (util.cpp:471): per user the dense rank of the raw value (elvl + run tables), the gain
-        // 2^v - 1 per rating (util.cpp:519) and, per ndcg_k, the ideal DCG.  With at most 64 raw levels per user (every rating
-        // scale in use) all of it derives from the per-user LEVEL TABLES: the gain of a rating is the gain of its level --
-        // pow() runs once per (user, level) on the host, the per-rating array is filled on the device -- and the ideal DCG walks
-        // the level counts from the top; neither the 8-byte ratings nor a per-rating gain array cross PCIe.  The training set
-        // reuses the solver's own level arrays when its raw levels are the rounded ones (integer ratings, or PrimalCR).
-        for (int w = 0; w < 2; ++w) {
-            const PcrCsr& E = w == 0 ? ds->train : ds->test;
-            EvalSet& es = ev[w];
-            const int64_t a = E.index[ds_u0], b = E.index[ds_u0 + nu];
-            es.nnz = b - a;
-            es.h_uptr.resize(nu + 1);
-            for (int64_t u = 0; u <= nu; ++u) es.h_uptr[u] = E.index[ds_u0 + u] - a;
-            if (w == 1) {
-                RC(es.uptr.upload(es.h_uptr, st)); RC(es.item.upload_n(E.item.data() + a, (size_t)es.nnz));
-                h_test_item.assign(E.item.begin() + a, E.item.begin() + b); h_test_val.assign(E.val.begin() + a, E.val.begin() + b);
-            }
-            RC(es.idcg.alloc(nu));
-            const bool same = w == 0 && (prm.solver_type == PCR_SOLVER_PCR || lv.integer_valued);
-            PcrLevels rl_own;
-            std::string e2;
-            const PcrLevels* rl = same ? &lv : &rl_own;
-            const bool have_levels = same || pcr_build_levels(E, ds_u0, ds_u0 + nu, PCR_SOLVER_PCR, rl_own, e2) == PCR_OK;
-            std::vector<int32_t> order_own;
-            if (w == 1) length_order(es.h_uptr, nu, order_own);
-            const std::vector<int32_t>& order = w == 0 ? by_len : order_own;
-            if (have_levels) {
-                es.max_raw_levels = rl->max_levels;
-                if (same) { es.elvl_p = d_lvl.p; es.erunofs_p = d_runofs.p; es.erunstart_p = d_runstart.p; }       // (uploaded with the shard)
-                else {
-                    RC(es.elvl.upload(rl->level, st)); RC(es.erunofs.upload(rl->run_ofs, st)); RC(es.erunstart.upload(rl->run_start, st));
-                    es.elvl_p = es.elvl.p; es.erunofs_p = es.erunofs.p; es.erunstart_p = es.erunstart.p;
-                }
-                make_bins(es.h_uptr, nu, &rl->run_ofs, es.bins, order);
-            } else {
-                es.max_raw_levels = 1 << 30;
-                make_bins(es.h_uptr, nu, nullptr, es.bins, order);
-            }
-            if (es.max_raw_levels <= 64) {
-                // level tables: per (user, level) the count and the gain (pow(2, v) - 1 with the host's libm, as the reference computes it)
-                es.h_runofs = rl->run_ofs;
-                es.h_cnt.resize(rl->run_start.size());
-                es.h_lgain.resize(rl->run_start.size());
-                pcr_parallel_ranges(nu, pcr_host_threads(), [&](int, int64_t lo, int64_t hi) {
-                    for (int64_t u = lo; u < hi; ++u) {
-                        const int64_t o = rl->run_ofs[u], Tn = rl->run_ofs[u + 1] - o - 1;
-                        for (int64_t l = 0; l < Tn; ++l) {
-                            es.h_cnt[o + l] = rl->run_start[o + l + 1] - rl->run_start[o + l];
-                            es.h_lgain[o + l] = pow(2.0, rl->lev_val[o + l]) - 1.0;
-                        }
-                        es.h_cnt[o + Tn] = 0; es.h_lgain[o + Tn] = 0.0;
-                    }
-                });
-                DBuf<double> d_lgain;
-                RC(d_lgain.upload(es.h_lgain, st));
-                RC(es.gain.alloc((size_t)es.nnz));
-                if (es.nnz > 0) {
-                    const int64_t* up = w == 0 ? d_uptr.p : es.uptr.p;
-                    hipLaunchKernelGGL(k_gain_from_levels, dim3((unsigned)std::min<int64_t>(65535 * 16, cdiv(nu, 4))), dim3(256), 0, st, up, es.elvl_p, es.erunofs_p,
-                                       d_lgain.p, es.gain.p, nu);
-                    HIPCHK(hipGetLastError());
-                    HIPCHK(hipStreamSynchronize(st));              // (d_lgain goes out of scope)
-                }
-            } else {
-                // more raw levels than the level-table form of the evaluator takes (real-valued ratings): the ratings themselves
-                es.h_val.assign(E.val.begin() + a, E.val.begin() + b);
-                RC(es.val.upload(es.h_val, st));
-                std::vector<double> gain(es.nnz);
-                pcr_parallel_ranges(es.nnz, pcr_host_threads(), [&](int, int64_t lo, int64_t hi) {
-                    for (int64_t z = lo; z < hi; ++z) gain[z] = pow(2.0, es.h_val[z]) - 1.0;                  // util.cpp:519
-                });
-                RC(es.gain.upload(gain, st));
-            }
-            for (auto& bn : es.bins) RC(bn.d_users.upload(bn.users, st));
+        return PCR_OK;
+    }
+    // ---- eval sets (train shard, test shard)
+    // The evaluator compares RAW ratings (util.cpp:471): per user the dense rank of the raw value (elvl + run tables), the gain
+    // 2^v - 1 per rating (util.cpp:519) and, per ndcg_k, the ideal DCG.  With at most 64 raw levels per user (every rating
+    // scale in use) all of it derives from the per-user LEVEL TABLES: the gain of a rating is the gain of its level --
+    // pow() runs once per (user, level) on the host, the per-rating array is filled on the device -- and the ideal DCG walks
+    // the level counts from the top; neither the 8-byte ratings nor a per-rating gain array cross PCIe.  The training set
+    // reuses the solver's own level arrays when its raw levels are the rounded ones (integer ratings, or PrimalCR).
+    int build_eval_set(int w, const PcrCsr& E, const HostShard& H) {
+        EvalSet& es = ev[w];
+        const PcrLevels& lv = H.lv;
+        const int64_t nu = n_users, ds_u0 = H.u0;
+        const int64_t a = E.index[ds_u0], b = E.index[ds_u0 + nu];
+        es.nnz = b - a;
+        es.h_uptr.resize(nu + 1);
+        for (int64_t u = 0; u <= nu; ++u) es.h_uptr[u] = E.index[ds_u0 + u] - a;
+        if (w == 1) {
+            RC(es.uptr.upload(es.h_uptr, st)); RC(es.item.upload_n(E.item.data() + a, (size_t)es.nnz));
+            h_test_item.assign(E.item.begin() + a, E.item.begin() + b); h_test_val.assign(E.val.begin() + a, E.val.begin() + b);
         }
-        RC(d_out4.alloc(4 * (size_t)std::max<int64_t>(nu, 1)));
-
-        phase("evaluation sets");
+        RC(es.idcg.alloc(nu));
+        const bool same = w == 0 && (prm.solver_type == PCR_SOLVER_PCR || lv.integer_valued);
+        PcrLevels rl_own;
+        std::string e2;
+        const PcrLevels* rl = same ? &lv : &rl_own;
+        const bool have_levels = same || pcr_build_levels(E, ds_u0, ds_u0 + nu, PCR_SOLVER_PCR, rl_own, e2) == PCR_OK;
+        std::vector<int32_t> order_own;
+        if (w == 1) length_order(es.h_uptr, nu, order_own);
+        const std::vector<int32_t>& order = w == 0 ? H.by_len : order_own;
+        if (have_levels) {
+            es.max_raw_levels = rl->max_levels;
+            if (same) { es.elvl_p = d_lvl.p; es.erunofs_p = d_runofs.p; es.erunstart_p = d_runstart.p; }       // (uploaded with the shard)
+            else {
+                RC(es.elvl.upload(rl->level, st)); RC(es.erunofs.upload(rl->run_ofs, st)); RC(es.erunstart.upload(rl->run_start, st));
+                es.elvl_p = es.elvl.p; es.erunofs_p = es.erunofs.p; es.erunstart_p = es.erunstart.p;
+            }
+            make_bins(es.h_uptr, nu, &rl->run_ofs, es.bins, order);
+        } else {
+            es.max_raw_levels = 1 << 30;
+            make_bins(es.h_uptr, nu, nullptr, es.bins, order);
+        }
+        if (es.max_raw_levels <= 64) {
+            // level tables: per (user, level) the count and the gain (pow(2, v) - 1 with the host's libm, as the reference computes it)
+            es.h_runofs = rl->run_ofs;
+            es.h_cnt.resize(rl->run_start.size());
+            es.h_lgain.resize(rl->run_start.size());
+            pcr_parallel_ranges(nu, pcr_host_threads(), [&](int, int64_t lo, int64_t hi) {
+                for (int64_t u = lo; u < hi; ++u) {
+                    const int64_t o = rl->run_ofs[u], Tn = rl->run_ofs[u + 1] - o - 1;
+                    for (int64_t l = 0; l < Tn; ++l) {
+                        es.h_cnt[o + l] = rl->run_start[o + l + 1] - rl->run_start[o + l];
+                        es.h_lgain[o + l] = pow(2.0, rl->lev_val[o + l]) - 1.0;
+                    }
+                    es.h_cnt[o + Tn] = 0; es.h_lgain[o + Tn] = 0.0;
+                }
+            });
+            DBuf<double> d_lgain;
+            RC(d_lgain.upload(es.h_lgain, st));
+            RC(es.gain.alloc((size_t)es.nnz));
+            if (es.nnz > 0) {
+                const int64_t* up = w == 0 ? d_uptr.p : es.uptr.p;
+                hipLaunchKernelGGL(k_gain_from_levels, dim3((unsigned)std::min<int64_t>(65535 * 16, cdiv(nu, 4))), dim3(256), 0, st, up, es.elvl_p, es.erunofs_p,
+                                   d_lgain.p, es.gain.p, nu);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipStreamSynchronize(st));              // (d_lgain goes out of scope)
+            }
+        } else {
+            // more raw levels than the level-table form of the evaluator takes (real-valued ratings): the ratings themselves
+            es.h_val.assign(E.val.begin() + a, E.val.begin() + b);
+            RC(es.val.upload(es.h_val, st));
+            std::vector<double> gain(es.nnz);
+            pcr_parallel_ranges(es.nnz, pcr_host_threads(), [&](int, int64_t lo, int64_t hi) {
+                for (int64_t z = lo; z < hi; ++z) gain[z] = pow(2.0, es.h_val[z]) - 1.0;                  // util.cpp:519
+            });
+            RC(es.gain.upload(gain, st));
+        }
+        for (auto& bn : es.bins) RC(bn.d_users.upload(bn.users, st));
+        return PCR_OK;
+    }
+    int alloc_factors_and_scratch() {
         // ---- factors / vectors
-        const size_t nV = (size_t)d2 * geo.ld, nU = (size_t)nu * geo.ld;
+        const size_t nV = (size_t)d2 * geo.ld, nU = (size_t)n_users * geo.ld;
         RC(d_U.alloc(nU)); RC(d_V.alloc(nV)); RC(d_Vnew.alloc(nV)); RC(d_g.alloc(nV)); RC(d_delta.alloc(nV));
         RC(d_rr.alloc(nV)); RC(d_p.alloc(nV)); RC(d_Hp.alloc(nV));
         HIPCHK(hipMemsetAsync(d_U.p, 0, std::max<size_t>(nU, 1) * sizeof(T), st));
@@ -1041,6 +804,58 @@ struct Solver final : pcr_solver {
         }
         RC(set_lds_limits());
         HIPCHK(hipStreamSynchronize(st));
+        return PCR_OK;
+    }
+
+    // shard_first >= 0: `ds` holds ONLY this rank's users (renumbered from 0) -- users [shard_first, shard_first + ds.d1) of a
+    // job with d1_total users (pcr_solver_create_shard); else the whole data set, partitioned here by pcr_partition_users
+    int init(const pcr_dataset* ds, const pcr_params* p, int rank_, int nranks_, int64_t shard_first = -1, int64_t d1_total = 0) {
+        prm = *p; rank = rank_; nranks = nranks_;
+        const auto t_init = std::chrono::steady_clock::now();
+        tune.read();
+        // wall time of the set-up phases: kept (pcr_solver_setup_phase; omp-pmf-train --timing prints them), printed with pcr_tune("debug")
+        auto t_phase = t_init;
+        auto phase = [&](const char* what) {
+            const auto now = std::chrono::steady_clock::now();
+            const double ms = std::chrono::duration<double, std::milli>(now - t_phase).count();
+            setup_ms.emplace_back(what, ms);
+            if (tune.debug) fprintf(stderr, "[pcr] set-up: %-28s %8.1f ms\n", what, ms);
+            t_phase = now;
+        };
+        std::thread side_maker;
+        struct JoinSide { std::thread& t; ~JoinSide() { if (t.joinable()) t.join(); } } join_side{side_maker};
+        RC(open_device(side_maker));
+        HostShard H;
+        RC(shard_bounds(ds, shard_first, d1_total, H));
+        const int64_t nu = n_users;
+        phase("device, streams, events");
+        // ---- host-side shard preparation
+        const PcrCsr& X = ds->train;
+        H.uptr.resize(nu + 1);
+        for (int64_t u = 0; u <= nu; ++u) H.uptr[u] = X.index[H.u0 + u] - X.index[H.u0];
+        H.item = X.item.data() + X.index[H.u0];
+        phase("copy CSR");
+        std::string err;
+        int rc = pcr_build_levels(X, H.u0, H.u0 + nu, prm.solver_type, H.lv, err);
+        if (rc != PCR_OK) { pcr_set_error(err); return rc; }
+        phase("levels");
+        // the shard's CSR goes up first: the nnz-sized part of the SpMM plan is built from it on the device (pcr_plan_dev.h)
+        RC(d_uptr.upload(H.uptr, st)); RC(d_item.upload_n(H.item, (size_t)nnz_local));
+        phase("CSR upload");
+        length_order(H.uptr, nu, H.by_len);
+        RC(pick_blocked_users(H));
+        RC(adopt_plan(H));
+        phase("tile-major CSC, slab plan");
+        RC(setup_vside_classes(H));
+        RC(setup_ustep_classes(H));
+        RC(setup_newton(H));
+        phase("length classes");
+        RC(setup_state(H));
+        phase("uploads, state arrays");
+        for (int w = 0; w < 2; ++w) RC(build_eval_set(w, w == 0 ? ds->train : ds->test, H));
+        RC(d_out4.alloc(4 * (size_t)std::max<int64_t>(nu, 1)));
+        phase("evaluation sets");
+        RC(alloc_factors_and_scratch());
         phase("factors, scratch");
         if (side_maker.joinable()) side_maker.join();
         RC(pick_lanes());
@@ -1192,18 +1007,6 @@ struct Solver final : pcr_solver {
         }
         HIPCHK(hipGetLastError());
         return PCR_OK;
-    }
-    // profile slot of one kernel launch: "<class>/<workgroup size>[g]" (g = global-scratch variant)
-    // ("ustep" has several classes per workgroup size: "<class>/<workgroup size>.<length bound>")
-    static std::string pname(const char* cls, const Bin& b) {
-        if (b.gram) return std::string(cls) + "/gram" + std::to_string(b.block) + "." + std::to_string(b.limit);
-        std::string s = std::string(cls) + "/" + std::to_string(b.block);
-        if (!strcmp(cls, "ustep") && b.limit) s += "." + std::to_string(b.limit);
-        // (k_ustep: l = the latency form, 8 rows in flight; r = one-wave class with its rows LDS-resident; #n = symbol id -- together
-        // with the workgroup size they name ONE kernel symbol, so a profiler's per-symbol rows can be matched to a class)
-        const bool us = !strcmp(cls, "ustep");
-        return s + (b.big ? "g" : "") + (b.K > 1 ? "c" : "") + (us && b.K == 1 && b.unr == 8 ? "l" : "") + (us && b.block == 64 && b.rcap > 0 ? "r" : "") +
-               (b.sym ? "#" + std::to_string(b.sym) : "");
     }
     std::string ustep_classes() override {
         std::string all;

@@ -861,6 +861,24 @@ def test_cluster_class_mixes_level_counts(oracle):
     _one_outer_iteration_vs_oracle(oracle, d1, d2, user, item, val, r, lam, solver=2)
 
 
+def test_u_step_classes_are_the_host_layout_at_this_devices_cu_count(tmp_path):
+    """Ties csrc/check/classes_dump (tests/test_classes.py) to the solver: on that test's rating set, default knobs, the classes
+    a solver lays out on this device are the ones the host-only layout prints for this device's CU count."""
+    import torch
+
+    import classes_data as cd
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    d1, d2, user, item, val = cd.rating_set()
+    ds = pcr.Dataset.from_triplets(d1, d2, user, item, val)
+    exe = cd.build_dump()
+    for prec in cd.PRECISIONS:
+        s = pcr.Solver(ds, pcr.Parameter(k=cd.K, precision=pcr.PCR_F64 if prec == "f64" else pcr.PCR_F32))
+        rc, classes, _, out = cd.run_dump(exe, tmp_path, prec, {}, ncu)
+        assert rc == 0, out
+        assert s.ustep_classes() == [c["name"] for c in classes if c["users"] > 0]
+        s.close()
+
+
 @pytest.mark.parametrize("r", [200, 257])
 def test_fp64_wide_ranks_with_users_near_4096_ratings(oracle, r):
     """fp64 at configs[4]'s rank and beyond with users of 2049..4096 ratings: the LDS-resident form of k_ustep would need
