@@ -223,6 +223,8 @@ int pcr_partition_users(const int64_t *index, int64_t d1, int nparts, int64_t *b
  *                   are re-read from L2 every round; the faster one at every shape measured), 1 = the LDS form (the pool's rows
  *                   staged once per user) whenever one wave's image fits a workgroup's 160 KiB; both forms implement the same
  *                   contract, the tests hold them to each other; read at every call
+ *   ridge_form      "cg" = pcr_fold_in_ridge / pcr_fold_in_ridge_model take the CG form for every user (the A/B arm of the direct
+ *                   forms, and a test hook); "auto" (default) = the form rule; read when the call's plan is made
  *   count_rows      1 = the U-step kernels count the rows of V they gather (pcr_solver_counter; a diagnostic that
  *                   costs the short-user classes 10-20 %, so off by default)
  *   debug           1 = print launch decisions to stderr
@@ -773,6 +775,63 @@ int pcr_fold_in_model(const pcr_params *p, const double *V, int64_t d2, int64_t 
 int pcr_fold_in(pcr_solver *s, int64_t n, const int64_t *index, const int32_t *item, const double *val,
                 const double *U0, int steps, double *U_out,
                 pcr_foldin_stats *stats, double *per_user);                                        /* [device] */
+
+/* ------------------------------------------------------------------------- */
+/* ridge fold-in: squared-loss factors for rows the model was not trained on  */
+/* (CCDR1 models; no reference counterpart: the reference can only retrain)   */
+/* ------------------------------------------------------------------------- */
+/* Given a fixed factor matrix F (rows x k) and the ratings of n new users as a CSR over F's rows, each user's row is the exact
+ * minimiser of the squared loss with F fixed.  For a user with ratings r on rows I (len of them), A = F[I] (len x k):
+ *     minimise |r - A u|^2 + mu |u|^2,    mu = lambda len (weighted != 0: CCDR1's regulariser, ccd-r1.cpp's loss + lambda reg with
+ *     reg = sum over rows of nnz_row |u|^2) or mu = lambda (weighted == 0: the plain ridge, for models trained elsewhere).
+ * One workgroup solves one user in fp64 (rows of the storage type are widened as they are read; Gram matrices on
+ * v_mfma_f64_16x16x4_f64 for both storage types) and rounds the row to the storage type on store.  The same entry folds in new
+ * ITEMS: F = U and the item-major ratings (a CSR over U's rows).
+ *   Forms              a function of the user's length len and the rank k alone, never of the batch, the position or the grid:
+ *                        DUAL    len <= k and len <= PCR_RIDGE_DIRECT_MAX:  (A A^T + mu I) a = r by blocked Cholesky, u = A^T a
+ *                        PRIMAL  len > k and roundup(k, 16) <= PCR_RIDGE_DIRECT_MAX:  (A^T A + mu I) u = A^T r by blocked Cholesky,
+ *                                the ratings streamed in chunks of 16 (any len)
+ *                        CG      everything else: matrix-free conjugate gradient on the primal system from u = 0, until
+ *                                |residual|^2 <= 1e-24 |A^T r|^2, at most 2 min(len, k) + 10 iterations
+ *                      Users of at most PCR_RIDGE_WAVE_MAX ratings run on one wave (a 64-thread workgroup), longer ones on 256
+ *                      threads.  pcr_tune("ridge_form", "cg") forces the CG form for every user ("auto" or removal: the rule).
+ *   Statuses           PCR_RIDGE_OK; PCR_RIDGE_SINGULAR: a Cholesky pivot that is <= 0 or not finite, or a CG step with
+ *                      p.Hp <= 0 or not finite -- the row is zeros and loss = obj = |r|^2; PCR_RIDGE_CG_CAP: the CG reached its
+ *                      iteration cap and its last iterate is returned.
+ *   Inputs             index[n + 1] / item / val as pcr_fold_in_model's: rows need not be item-ascending (a sorted copy is made:
+ *                      every sum runs in ascending item order); the same item twice in a row is two ratings, as in training.  A
+ *                      user without ratings gets a zero row, status OK, loss = obj = 0.
+ *   Outputs            U_out [n][k]: the storage-type values widened.  per_user (optional) [n][PCR_RIDGE_FIELDS] = len, form,
+ *                      iters (CG form; 0 otherwise), loss, obj, status, where loss = |r - A u^|^2 and obj = loss + mu |u^|^2 are
+ *                      evaluated at the RETURNED (rounded) row u^.  stats (optional): the counts, and loss / obj added in user
+ *                      order.
+ *   Determinism        a user's row and table line depend on its ratings, F and the parameters alone: every sum has a fixed
+ *                      order, no atomics, nothing is exchanged between workgroups, every loop has a static bound.  Two identical
+ *                      calls are bitwise identical.
+ *   Errors             PCR_ERR_ARG before any device is looked for, the message naming the entry: a null F or U_out, k < 1 or
+ *                      rows < 1, an item id outside [0, rows), a rating that is not finite, index[0] != 0 or a non-monotone index,
+ *                      a lambda that is negative or not finite, an unknown precision.  Without a device: PCR_ERR_DEVICE. */
+#define PCR_RIDGE_FIELDS 6
+#define PCR_RIDGE_DUAL   0
+#define PCR_RIDGE_PRIMAL 1
+#define PCR_RIDGE_CG     2
+#define PCR_RIDGE_OK       0
+#define PCR_RIDGE_SINGULAR 1
+#define PCR_RIDGE_CG_CAP   2
+#define PCR_RIDGE_WAVE_MAX   64
+#define PCR_RIDGE_DIRECT_MAX 112   /* the lower-triangular tiles of a 112 x 112 matrix are 60 KB of LDS: two workgroups per CU */
+typedef struct pcr_ridge_stats {
+    int64_t users, dual, primal, cg, singular, cg_cap, iters;
+    double  loss, obj;
+} pcr_ridge_stats;
+/* Standalone: F (rows x k) host fp64 in model-file layout. */
+int pcr_fold_in_ridge_model(const double *F, int64_t rows, int64_t k, double lambda, int weighted, int precision, int device,
+                            int64_t n, const int64_t *index, const int32_t *item, const double *val,
+                            double *U_out, pcr_ridge_stats *stats, double *per_user);               /* [device] */
+/* On ANY live solver, CCDR1 included: its device V, storage type, stream and lambda.  V is replicated on every rank, so the call
+ * is local: nothing is exchanged and any rank may call it alone.  Nothing of the solver is written.  Profile slot: foldin/ridge. */
+int pcr_fold_in_ridge(pcr_solver *s, int weighted, int64_t n, const int64_t *index, const int32_t *item, const double *val,
+                      double *U_out, pcr_ridge_stats *stats, double *per_user);                     /* [device] */
 
 /* per-kernel device timing (HIP events on the solver's stream, one pair per launch).
  * slot names: "<class>/<workgroup size>[.<length bound>][g][c][l][r][#n]" for the per-user kernels (classes

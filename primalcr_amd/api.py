@@ -20,6 +20,11 @@ PCR_FOLDIN_CONVERGED, PCR_FOLDIN_STEP_CAP, PCR_FOLDIN_STALLED = 0, 1, 2         
 # fold_in's workgroup forms by user length (include/primalcr.h): one wave up to WAVE_MAX ratings, per-rating arrays in LDS up to
 # LDS_MAX, global scratch beyond
 PCR_FOLDIN_WAVE_MAX, PCR_FOLDIN_LDS_MAX = 64, 2048
+PCR_RIDGE_FIELDS = ("n", "form", "iters", "loss", "obj", "status")               # fold_in_ridge's per_user columns
+PCR_RIDGE_DUAL, PCR_RIDGE_PRIMAL, PCR_RIDGE_CG = 0, 1, 2                         # ... its forms
+PCR_RIDGE_OK, PCR_RIDGE_SINGULAR, PCR_RIDGE_CG_CAP = 0, 1, 2                     # ... and its status values
+# fold_in_ridge's rule (include/primalcr.h): one wave up to WAVE_MAX ratings; the direct (Cholesky) forms up to a system of side DIRECT_MAX
+PCR_RIDGE_WAVE_MAX, PCR_RIDGE_DIRECT_MAX = 64, 112
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -105,6 +110,12 @@ class FoldinStats(C.Structure):
     """pcr_foldin_stats."""
     _fields_ = [("users", C.c_int64), ("converged", C.c_int64), ("step_cap", C.c_int64), ("stalled", C.c_int64), ("steps", C.c_int64),
                 ("cg", C.c_int64), ("ls", C.c_int64), ("obj", C.c_double)]
+
+
+class RidgeStats(C.Structure):
+    """pcr_ridge_stats."""
+    _fields_ = [("users", C.c_int64), ("dual", C.c_int64), ("primal", C.c_int64), ("cg", C.c_int64), ("singular", C.c_int64),
+                ("cg_cap", C.c_int64), ("iters", C.c_int64), ("loss", C.c_double), ("obj", C.c_double)]
 
 
 _LOG_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p)
@@ -195,6 +206,9 @@ def lib():
     L.pcr_evaluate_rerank.argtypes = [vp, i64, vp, ci, vp, ci, ci, vp, cd, ci, vp, vp, vp, vp, vp]
     L.pcr_fold_in_model.argtypes = [C.POINTER(Parameter), vp, i64, i64, vp, vp, vp, vp, ci, vp, vp, vp]
     L.pcr_fold_in.argtypes = [vp, i64, vp, vp, vp, vp, ci, vp, vp, vp]
+    if _LIB_OVERRIDE is None or hasattr(L, "pcr_fold_in_ridge"):
+        L.pcr_fold_in_ridge_model.argtypes = [vp, i64, i64, cd, ci, ci, ci, i64, vp, vp, vp, vp, vp, vp]
+        L.pcr_fold_in_ridge.argtypes = [vp, ci, i64, vp, vp, vp, vp, vp, vp]
     L.pcr_exposure_stats.argtypes = [vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(cd), C.POINTER(cd)]
     L.pcr_profile_enable.argtypes = [vp, ci]
     L.pcr_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(cd), C.POINTER(i64)]
@@ -716,6 +730,61 @@ def recommend_new_users(V, ratings, lam, topk, solver_type=PCR_SOLVER_PCRPP, U0=
     return items, scores, U_new, stats
 
 
+def ridge_form(n, k):
+    """The form fold_in_ridge() solves a user of n ratings in at rank k (include/primalcr.h): PCR_RIDGE_DUAL for n <= k and
+    n <= PCR_RIDGE_DIRECT_MAX, PCR_RIDGE_PRIMAL for n > k when k padded to 16 is <= PCR_RIDGE_DIRECT_MAX, PCR_RIDGE_CG otherwise."""
+    if n <= k and n <= PCR_RIDGE_DIRECT_MAX:
+        return PCR_RIDGE_DUAL
+    if n > k and (k + 15) // 16 * 16 <= PCR_RIDGE_DIRECT_MAX:
+        return PCR_RIDGE_PRIMAL
+    return PCR_RIDGE_CG
+
+
+def ridge_boundaries(k):
+    """The user lengths L at which fold_in_ridge() changes its form between L and L + 1 ratings at rank k."""
+    top = max(int(k), PCR_RIDGE_DIRECT_MAX) + 1
+    return [L for L in range(top) if ridge_form(L, k) != ridge_form(L + 1, k)]
+
+
+def _ridge_call(n, k, per_user, fn):
+    """Shared by fold_in_ridge() and Solver.fold_in_ridge(): the buffers around fn(U_out pointer, stats pointer, per_user
+    pointer); returns (rows, stats dict[, per_user])."""
+    out = np.empty((n, k), np.float64)
+    st = RidgeStats()
+    pu = np.empty((n, len(PCR_RIDGE_FIELDS)), np.float64) if per_user else None
+    _chk(fn(out.ctypes.data, C.addressof(st), None if pu is None else pu.ctypes.data))
+    stats = {f: getattr(st, f) for f, _ in RidgeStats._fields_}
+    return (out, stats, pu) if per_user else (out, stats)
+
+
+def fold_in_ridge(F, ratings, lam, weighted=True, dtype=PCR_F64, device=0, per_user=False):
+    """Squared-loss factors for rows a model was not trained on, on the GPU (pcr_fold_in_ridge_model): with the factor matrix F
+    [rows, k] fixed, each new user's row is the exact minimiser of |r - F[I] u|^2 + mu |u|^2 over its ratings r on rows I of F,
+    with mu = lam * len(r) (weighted: CCDR1's regulariser, solver type 0) or mu = lam (weighted=False: the plain ridge).
+    ratings: a Dataset (its training CSR) or an (index, item, val) tuple over F's rows, as fold_in() takes.
+    New users: F = V and the users' ratings over the items.  New ITEMS: F = U and the item-major CSR (row j: the users who rated
+    item j and their ratings); the rows returned are rows of V.
+    Returns (rows float64 [n, k], stats dict[, per_user float64 [n, 6] of PCR_RIDGE_FIELDS]); loss and obj are evaluated at the
+    returned rows, which are rounded to `dtype`."""
+    F = np.ascontiguousarray(F, np.float64)
+    if F.ndim != 2:
+        raise ValueError("F must be [rows, k]")
+    index, item, val = _foldin_ratings(ratings)
+    n, k = index.shape[0] - 1, F.shape[1]
+    return _ridge_call(n, k, per_user, lambda uo, sp, pp: lib().pcr_fold_in_ridge_model(
+        F.ctypes.data, F.shape[0], k, float(lam), 1 if weighted else 0, int(dtype), int(device), n, index.ctypes.data, item.ctypes.data,
+        val.ctypes.data, uo, sp, pp))
+
+
+def recommend_new_users_ridge(V, ratings, lam, topk, weighted=True, dtype=PCR_F64, device=0):
+    """Top-K lists for users a squared-loss model was not trained on: fold_in_ridge(), then recommend(U_new, V, topk,
+    exclude=ratings) -- the ratings the users were folded in on are left out.  Returns (items, scores, U_new, stats)."""
+    index, item, val = _foldin_ratings(ratings)
+    U_new, stats = fold_in_ridge(V, (index, item, val), lam, weighted=weighted, dtype=dtype, device=device)
+    items, scores = recommend(U_new, V, topk, exclude=(index, item), dtype=dtype, device=device)
+    return items, scores, U_new, stats
+
+
 def exposure_stats(x):
     """The closing arithmetic of one exposure row (pcr_exposure_stats): dict(recs, items_covered, coverage, gini)."""
     x = np.ascontiguousarray(x, np.int64)
@@ -1079,6 +1148,15 @@ class Solver:
         n = index.shape[0] - 1
         return _foldin_call(n, self.k, U0, per_user, lambda u0, uo, sp, pp: lib().pcr_fold_in(
             self._h, n, index.ctypes.data, item.ctypes.data, val.ctypes.data, u0, int(steps), uo, sp, pp))
+
+    def fold_in_ridge(self, ratings, weighted=True, per_user=False):
+        """Squared-loss factors for users this solver was not trained on, against its device V (pcr_fold_in_ridge), in its storage
+        type and with its lambda; any solver type, CCDR1 included; arguments and result as fold_in_ridge().  Local to the rank;
+        nothing of the solver is written."""
+        index, item, val = _foldin_ratings(ratings)
+        n = index.shape[0] - 1
+        return _ridge_call(n, self.k, per_user, lambda uo, sp, pp: lib().pcr_fold_in_ridge(
+            self._h, 1 if weighted else 0, n, index.ctypes.data, item.ctypes.data, val.ctypes.data, uo, sp, pp))
 
     def sync(self):
         _chk(lib().pcr_solver_sync(self._h))

@@ -574,6 +574,7 @@ struct CcdSolver final : pcr_solver {
     int set_factors(const double* U, const double* V, bool local) override { begun = false; return base->set_factors(U, V, local); }
     int get_factors(double* U, double* V, bool local) override { return base->get_factors(U, V, local); }
     int evaluate(int which, int ndcg_k, double* err, double* ndcg) override { return base->evaluate(which, ndcg_k, err, ndcg); }
+    double ridge_lambda() override { return prm.lambda; }
     void serve_view(ServeView* v) override { base->serve_view(v); v->prof = &prof; }   // (the "recommend/..." slots are this solver's)
     int residual_mismatch(double* value) override {
         hipLaunchKernelGGL((k_ccd_mismatch<RT>), dim3(B), dim3(ccd::BLOCK), 0, st, (const RT*)d_res_r.p, (const RT*)d_res_c.p, (const int32_t*)d_c2r.p,

@@ -362,7 +362,7 @@ extern "C" int pcr_dataset_from_csr(int64_t d1, int64_t d2, const int64_t* index
 static std::map<std::string, std::string>& tune_table() { static thread_local std::map<std::string, std::string> t; return t; }
 static const char* const TUNE_KEYS[] = {"ustep_mode", "cluster_k", "cluster_users", "ubins", "ustep_gram", "spmm_tiles", "spmm_chunk", "sddmm_csc",
                                         "lanes", "pipeline", "window_cache", "prepare_merged", "resort_window", "allreduce_chunks", "p2p_ll",
-                                        "p2p_timeout_ms", "p2p_queue_budget", "count_rows", "debug", "win16", "ustep_win_lds", "plan_key64", "ustep_newton", "vblock_users", "recommend_select", "ranks_batch_users", "rerank_lds", "fault_cluster_member", "fault_p2p_skip", "fault_p2p_coarse", nullptr};
+                                        "p2p_timeout_ms", "p2p_queue_budget", "count_rows", "debug", "win16", "ustep_win_lds", "plan_key64", "ustep_newton", "vblock_users", "recommend_select", "ranks_batch_users", "rerank_lds", "ridge_form", "fault_cluster_member", "fault_p2p_skip", "fault_p2p_coarse", nullptr};
 extern "C" int pcr_tune(const char* key, const char* value) {
     if (!key) { pcr_set_error("pcr_tune: null key"); return PCR_ERR_ARG; }
     bool known = false;
@@ -1504,6 +1504,43 @@ int64_t pcr_list_relevance(int64_t rows, const int64_t* tptr, const int32_t* tit
 // ------------------------------------------------------------------------------------------
 // fold-in (include/primalcr.h, "fold-in"): argument checks and the host-side plan
 // ------------------------------------------------------------------------------------------
+// What both fold-in plans (pcr_fold_in_check, pcr_fold_in_ridge_check) share.  The scan of n CSR rows over d2 columns, by the host
+// threads: bit 0 = an id outside [0, d2), bit 1 = a rating that is not finite, bit 2 = a row that is not item-ascending
+int pcr_csr_rows_scan(int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val) {
+    const int nth = pcr_host_threads();
+    std::vector<int> st((size_t)nth, 0);
+    pcr_parallel_ranges(n, nth, [&](int t, int64_t lo, int64_t hi) {
+        for (int64_t u = lo; u < hi; ++u)
+            for (int64_t z = index[u]; z < index[u + 1]; ++z) {
+                if (item[z] < 0 || item[z] >= d2) st[(size_t)t] |= 1;
+                if (!std::isfinite(val[z])) st[(size_t)t] |= 2;
+                if (z > index[u] && item[z] < item[z - 1]) st[(size_t)t] |= 4;
+            }
+    });
+    int all = 0;
+    for (int x : st) all |= x;
+    return all;
+}
+// ... and the copy X of the rows; sort: rows in ascending item order (equal items keep their order), the ratings with them
+void pcr_csr_sorted_copy(int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val, bool sort, PcrCsr& X) {
+    const int64_t nnz = index[n];
+    X.d1 = n; X.d2 = d2;
+    X.index.assign(index, index + n + 1);
+    X.item.assign(item, item + nnz);
+    X.val.assign(val, val + nnz);
+    if (sort)
+        pcr_parallel_ranges(n, pcr_host_threads(), [&](int, int64_t lo, int64_t hi) {
+            std::vector<int64_t> perm;
+            for (int64_t u = lo; u < hi; ++u) {
+                const int64_t a = index[u], len = index[u + 1] - a;
+                perm.resize((size_t)len);
+                for (int64_t q = 0; q < len; ++q) perm[(size_t)q] = a + q;
+                std::stable_sort(perm.begin(), perm.end(), [&](int64_t x, int64_t y) { return item[x] < item[y]; });
+                for (int64_t q = 0; q < len; ++q) { X.item[(size_t)(a + q)] = item[perm[(size_t)q]]; X.val[(size_t)(a + q)] = val[perm[(size_t)q]]; }
+            }
+        });
+}
+
 int pcr_fold_in_check(const char* who, int solver_type, int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val,
                       int steps, const double* U_out, PcrFoldinPlan* plan) {
     auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
@@ -1524,37 +1561,12 @@ int pcr_fold_in_check(const char* who, int solver_type, int64_t d2, int64_t n, c
     }
     const int64_t nnz = index[n];
     if (nnz > 0 && (!item || !val)) return bad("null item / val");
-    const int nth = pcr_host_threads();
-    std::vector<int> st((size_t)nth, 0);       // bit 0: an item outside [0, d2); bit 1: a rating that is not finite; bit 2: a row not item-ascending
-    pcr_parallel_ranges(n, nth, [&](int t, int64_t lo, int64_t hi) {
-        for (int64_t u = lo; u < hi; ++u)
-            for (int64_t z = index[u]; z < index[u + 1]; ++z) {
-                if (item[z] < 0 || item[z] >= d2) st[(size_t)t] |= 1;
-                if (!std::isfinite(val[z])) st[(size_t)t] |= 2;
-                if (z > index[u] && item[z] < item[z - 1]) st[(size_t)t] |= 4;
-            }
-    });
-    int all = 0;
-    for (int x : st) all |= x;
+    const int all = pcr_csr_rows_scan(d2, n, index, item, val);
     if (all & 1) return bad("an item id is outside [0, d2)");
     if (all & 2) return bad("a rating is not finite");
     PcrFoldinPlan local;
     PcrFoldinPlan& P = plan ? *plan : local;
-    P.X.d1 = n; P.X.d2 = d2;
-    P.X.index.assign(index, index + n + 1);
-    P.X.item.assign(item, item + nnz);
-    P.X.val.assign(val, val + nnz);
-    if (all & 4)                               // rows in ascending item order (equal items keep their order), the ratings with them
-        pcr_parallel_ranges(n, nth, [&](int, int64_t lo, int64_t hi) {
-            std::vector<int64_t> perm;
-            for (int64_t u = lo; u < hi; ++u) {
-                const int64_t a = index[u], len = index[u + 1] - a;
-                perm.resize((size_t)len);
-                for (int64_t q = 0; q < len; ++q) perm[(size_t)q] = a + q;
-                std::stable_sort(perm.begin(), perm.end(), [&](int64_t x, int64_t y) { return item[x] < item[y]; });
-                for (int64_t q = 0; q < len; ++q) { P.X.item[(size_t)(a + q)] = item[perm[(size_t)q]]; P.X.val[(size_t)(a + q)] = val[perm[(size_t)q]]; }
-            }
-        });
+    pcr_csr_sorted_copy(d2, n, index, item, val, (all & 4) != 0, P.X);
     std::string err;
     const int rc = pcr_build_levels(P.X, 0, n, solver_type, P.lv, err);
     if (rc != PCR_OK) { pcr_set_error(std::string(who) + ": " + err); return rc; }
@@ -1592,6 +1604,86 @@ void pcr_foldin_stats_from(const double* per_user, int64_t n, pcr_foldin_stats* 
         s.obj += o[3];
         const int status = (int)o[5];
         if (status == PCR_FOLDIN_CONVERGED) s.converged += 1; else if (status == PCR_FOLDIN_STEP_CAP) s.step_cap += 1; else s.stalled += 1;
+    }
+    *stats = s;
+}
+
+// ------------------------------------------------------------------------------------------
+// ridge fold-in (include/primalcr.h, "ridge fold-in"): the form rule, argument checks and the host-side plan
+// ------------------------------------------------------------------------------------------
+int pcr_ridge_form(int64_t len, int64_t k) {
+    if (len <= k && len <= PCR_RIDGE_DIRECT_MAX) return PCR_RIDGE_DUAL;
+    if (len > k && (k + 15) / 16 * 16 <= PCR_RIDGE_DIRECT_MAX) return PCR_RIDGE_PRIMAL;
+    return PCR_RIDGE_CG;
+}
+
+int pcr_fold_in_ridge_check(const char* who, bool need_F, const double* F, int64_t rows, int64_t k, double lambda, int precision, int64_t n,
+                            const int64_t* index, const int32_t* item, const double* val, const double* U_out, PcrRidgePlan* plan) {
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
+    if (need_F && !F) return bad("null F");
+    if (k < 1) return bad("rank k must be >= 1");
+    if (rows < 1) return bad("rows must be >= 1");
+    if (rows >= ((int64_t)1 << 31) - 64) return bad("more than 2^31 rows");
+    if (k >= ((int64_t)1 << 24)) return bad("rank k is too large");
+    if (precision != PCR_F32 && precision != PCR_F64) return bad("precision must be PCR_F32 or PCR_F64");
+    if (!std::isfinite(lambda) || lambda < 0.0) return bad("lambda must be finite and not negative");
+    if (n < 0 || !index) return bad("bad argument");
+    if (n >= ((int64_t)1 << 31) - 64) return bad("more than 2^31 users in one call");
+    if (n > 0 && !U_out) return bad("null output");
+    if (index[0] != 0) return bad("index[0] must be 0");
+    for (int64_t u = 0; u < n; ++u) {
+        if (index[u + 1] < index[u]) return bad("index not monotone at user " + std::to_string(u));
+        if (index[u + 1] - index[u] > ((int64_t)1 << 30)) return bad("user " + std::to_string(u) + " has more than 2^30 ratings");
+    }
+    const int64_t nnz = index[n];
+    if (nnz > 0 && (!item || !val)) return bad("null item / val");
+    const int all = pcr_csr_rows_scan(rows, n, index, item, val);
+    if (all & 1) return bad("an item id is outside [0, rows)");
+    if (all & 2) return bad("a rating is not finite");
+    PcrRidgePlan local;
+    PcrRidgePlan& P = plan ? *plan : local;
+    pcr_csr_sorted_copy(rows, n, index, item, val, (all & 4) != 0, P.X);
+    std::string knob;
+    P.force_cg = pcr_tune_get("ridge_form", &knob) && knob == "cg";
+    // a user's launch class: the CG form first, then primal and dual, 256 threads before one wave, more tiles before fewer; inside
+    // a class the longest users start first (equal lengths by ascending id)
+    auto len_of = [&](int32_t u) { return index[u + 1] - index[u]; };
+    auto cls_of = [&](int32_t u, PcrRidgePlan::Range* r) {
+        const int64_t len = len_of(u);
+        const int form = P.force_cg ? PCR_RIDGE_CG : pcr_ridge_form(len, k);
+        const int64_t m = form == PCR_RIDGE_DUAL ? std::max<int64_t>(len, 1) : k;
+        r->form = form;
+        r->block = (form == PCR_RIDGE_CG || len > PCR_RIDGE_WAVE_MAX) ? 256 : 64;
+        r->tiles = form == PCR_RIDGE_CG ? 0 : (int)((m + 15) / 16);
+        return (int64_t)form * -1000 - (r->block == 256 ? 100 : 0) - r->tiles;
+    };
+    P.order.resize((size_t)n);
+    std::vector<int64_t> key((size_t)n);
+    PcrRidgePlan::Range tmp;
+    for (int64_t u = 0; u < n; ++u) { P.order[(size_t)u] = (int32_t)u; key[(size_t)u] = cls_of((int32_t)u, &tmp); }
+    std::stable_sort(P.order.begin(), P.order.end(), [&](int32_t x, int32_t y) {
+        return key[(size_t)x] != key[(size_t)y] ? key[(size_t)x] < key[(size_t)y] : len_of(x) > len_of(y);
+    });
+    P.ranges.clear();
+    for (int64_t i = 0; i < n; ++i) {
+        PcrRidgePlan::Range r;
+        cls_of(P.order[(size_t)i], &r);
+        if (P.ranges.empty() || key[(size_t)P.order[(size_t)i]] != key[(size_t)P.order[(size_t)(i - 1)]]) { r.first = i; r.count = 0; P.ranges.push_back(r); }
+        P.ranges.back().count += 1;
+    }
+    return PCR_OK;
+}
+
+void pcr_ridge_stats_from(const double* per_user, int64_t n, pcr_ridge_stats* stats) {
+    pcr_ridge_stats s = {};
+    s.users = n;
+    for (int64_t u = 0; u < n; ++u) {
+        const double* o = per_user + (size_t)u * PCR_RIDGE_FIELDS;
+        const int form = (int)o[1], status = (int)o[5];
+        if (form == PCR_RIDGE_DUAL) s.dual += 1; else if (form == PCR_RIDGE_PRIMAL) s.primal += 1; else s.cg += 1;
+        s.iters += (int64_t)o[2];
+        s.loss += o[3]; s.obj += o[4];
+        if (status == PCR_RIDGE_SINGULAR) s.singular += 1; else if (status == PCR_RIDGE_CG_CAP) s.cg_cap += 1;
     }
     *stats = s;
 }

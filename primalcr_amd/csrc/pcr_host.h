@@ -198,3 +198,29 @@ int pcr_fold_in_model_check(const pcr_params* p, const double* V, int64_t d2, in
                             const double* val, int steps, const double* U_out, PcrFoldinPlan* plan);
 // stats from the per-user table [n][PCR_FOLDIN_FIELDS]: the counts, and obj added in user order
 void pcr_foldin_stats_from(const double* per_user, int64_t n, pcr_foldin_stats* stats);
+
+// What both fold-in plans share, factored out of pcr_fold_in_check.  pcr_csr_rows_scan: n CSR rows over d2 columns, by the host
+// threads -- bit 0 = an id outside [0, d2), bit 1 = a rating that is not finite, bit 2 = a row that is not item-ascending.
+// pcr_csr_sorted_copy: the copy X of the rows; sort = rows in ascending item order (equal items keep their order).
+int pcr_csr_rows_scan(int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val);
+void pcr_csr_sorted_copy(int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val, bool sort, PcrCsr& X);
+
+// Ridge fold-in (include/primalcr.h, "ridge fold-in").  The form of a user of len ratings at rank k (PCR_RIDGE_DUAL / PRIMAL / CG).
+int pcr_ridge_form(int64_t len, int64_t k);
+// What the host prepares for k_ridge_direct / k_ridge_cg: the ratings with item-ascending rows (a sorted copy when the caller's are
+// not) and the users grouped into launch ranges of `order` -- one per (form, workgroup size, 16 x 16 tiles per side of the Gram
+// matrix), users in descending length inside a range.  force_cg: pcr_tune("ridge_form", "cg") when the plan was made.
+struct PcrRidgePlan {
+    struct Range { int form = 0, block = 0, tiles = 0; int64_t first = 0, count = 0; };
+    PcrCsr X;
+    std::vector<int32_t> order;
+    std::vector<Range> ranges;
+    bool force_cg = false;
+};
+// The argument checks of both entries and the plan (the library and the sanitizer build's "no device" stub run the same ones):
+// F (need_F: the model entry; the solver entry reads its device V), k, rows, lambda, precision, the CSR's shape, ids inside
+// [0, rows), finite ratings, the output; errors are PCR_ERR_ARG prefixed with `who`.  plan (may be NULL) receives the plan.
+int pcr_fold_in_ridge_check(const char* who, bool need_F, const double* F, int64_t rows, int64_t k, double lambda, int precision, int64_t n,
+                            const int64_t* index, const int32_t* item, const double* val, const double* U_out, PcrRidgePlan* plan);
+// stats from the per-user table [n][PCR_RIDGE_FIELDS]: the counts, and loss / obj added in user order
+void pcr_ridge_stats_from(const double* per_user, int64_t n, pcr_ridge_stats* stats);

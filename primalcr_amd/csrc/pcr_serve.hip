@@ -9,6 +9,7 @@
 
 #include "pcr_dev.h"
 #include "pcr_foldin.h"
+#include "pcr_ridge.h"
 #include "pcr_prims.h"
 #include "pcr_topk.h"
 
@@ -917,6 +918,70 @@ static int foldin_run(const ServeView& v, const FoldinParams& c, const PcrFoldin
 }
 static FoldinParams foldin_params_of(const pcr_params& p, int steps) { return {p.solver_type, p.lambda, p.stepsize, p.cg_max_iter, p.cg_tol, steps}; }
 
+// Ridge fold-in (pcr_fold_in_ridge, pcr_fold_in_ridge_model; pcr_ridge.h) of the plan's users against v's V: the ratings and the
+// users' order go to the device, then one launch per range of the plan -- a (form, workgroup size, tile count) class, its LDS
+// sized by the class; workgroups stride over their range, the longest users first.  "foldin/ridge" times the launches.
+static const size_t RIDGE_LDS_CU = (size_t)160 * 1024;
+template <typename T>
+static int ridge_run(const ServeView& v, double lambda, int weighted, const PcrRidgePlan& P, double* U_out, pcr_ridge_stats* stats, double* per_user) {
+    const int64_t n = P.X.d1;
+    hipStream_t st = v.st;
+    int dev = 0, cus = 0;
+    HIPCHK(hipGetDevice(&dev));
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    cus = std::max(cus, 1);
+    DBuf<int64_t> uptr;
+    DBuf<int32_t> item, order;
+    DBuf<double> val, dPer, dOutD;
+    DBuf<T> dOut;
+    RC(uptr.upload(P.X.index, st)); RC(item.upload_n(P.X.item.data(), P.X.item.size())); RC(val.upload_n(P.X.val.data(), P.X.val.size()));
+    RC(order.upload(P.order, st));
+    RC(dOut.alloc((size_t)n * v.ld)); RC(dPer.alloc((size_t)n * PCR_RIDGE_FIELDS)); RC(dOutD.alloc((size_t)n * v.r));
+    const RidgeCsr X = {uptr.p, item.p, val.p};
+    const T* F = serve_V<T>(v);
+    {
+        ProfScope ps(v.prof, "foldin/ridge", st);
+        for (const PcrRidgePlan::Range& g : P.ranges) {
+            if (g.count <= 0) continue;
+            const int32_t* users = order.p + g.first;
+            if (g.form == PCR_RIDGE_CG) {
+                const size_t lds = ridge_cg_bytes(v.ld);
+                if (lds > RIDGE_LDS_CU) { pcr_set_error("ridge fold-in: rank " + std::to_string(v.r) + " is too large for the CG form's LDS"); return PCR_ERR_UNSUPPORTED; }
+                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, RIDGE_LDS_CU / lds));
+                const int64_t grid = std::min<int64_t>(g.count, (int64_t)cus * per_cu);
+                HIPCHK(hipFuncSetAttribute((const void*)k_ridge_cg<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                hipLaunchKernelGGL((k_ridge_cg<T>), dim3((unsigned)grid), dim3(256), lds, st, X, users, (int)g.count, F, v.r, v.ld, dOut.p, dPer.p, lambda, weighted);
+            } else {
+                const int mp = g.tiles * 16, dual = g.form == PCR_RIDGE_DUAL ? 1 : 0;
+                if (mp < 16 || mp > (g.block == 64 ? 64 : PCR_RIDGE_DIRECT_MAX)) { pcr_set_error("ridge fold-in: a launch class outside the kernel's tile range"); return PCR_ERR_STATE; }
+                const size_t lds = ridge_direct_bytes(mp, v.ld, g.block);
+                if (lds > RIDGE_LDS_CU) { pcr_set_error("ridge fold-in: rank " + std::to_string(v.r) + " is too large for the direct forms' LDS"); return PCR_ERR_UNSUPPORTED; }
+                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(g.block == 64 ? 16 : 4, RIDGE_LDS_CU / lds));
+                const int64_t grid = std::min<int64_t>(g.count, (int64_t)cus * per_cu);
+                if (g.block == 64) {
+                    HIPCHK(hipFuncSetAttribute((const void*)k_ridge_direct<T, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                    hipLaunchKernelGGL((k_ridge_direct<T, 64>), dim3((unsigned)grid), dim3(64), lds, st, X, users, (int)g.count, F, v.r, v.ld, dOut.p, dPer.p,
+                                       lambda, weighted, dual, mp);
+                } else {
+                    HIPCHK(hipFuncSetAttribute((const void*)k_ridge_direct<T, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                    hipLaunchKernelGGL((k_ridge_direct<T, 256>), dim3((unsigned)grid), dim3(256), lds, st, X, users, (int)g.count, F, v.r, v.ld, dOut.p, dPer.p,
+                                       lambda, weighted, dual, mp);
+                }
+            }
+            HIPCHK(hipGetLastError());
+        }
+    }
+    hipLaunchKernelGGL((k_mat_out<T>), dim3((unsigned)std::min<int64_t>(1 << 16, cdiv(n * v.r, 256))), dim3(256), 0, st, (const T*)dOut.p, dOutD.p, n, v.r, v.ld);
+    HIPCHK(hipGetLastError());
+    std::vector<double> hp((size_t)n * PCR_RIDGE_FIELDS);
+    HIPCHK(hipMemcpyAsync(U_out, dOutD.p, (size_t)n * v.r * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hp.data(), dPer.p, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (stats) pcr_ridge_stats_from(hp.data(), n, stats);
+    if (per_user) std::copy(hp.begin(), hp.end(), per_user);
+    return PCR_OK;
+}
+
 extern "C" {
 
 // users[n] (global ids, NULL: the whole shard) as rows of s's shard in loc (left empty for NULL); *n the count
@@ -1189,6 +1254,34 @@ int pcr_fold_in(pcr_solver* s, int64_t n, const int64_t* index, const int32_t* i
         if (n == 0) return PCR_OK;
         const FoldinParams c = foldin_params_of(prm, steps);
         return by_precision(v, [&](auto zero) -> int { return foldin_run<decltype(zero)>(v, c, P, U0, U_out, stats, per_user); });
+    });
+}
+
+int pcr_fold_in_ridge_model(const double* F, int64_t rows, int64_t k, double lambda, int weighted, int precision, int device, int64_t n,
+                            const int64_t* index, const int32_t* item, const double* val, double* U_out, pcr_ridge_stats* stats, double* per_user) {
+    return abi_guard("pcr_fold_in_ridge_model", [&]() -> int {
+    PcrRidgePlan P;
+    RC(pcr_fold_in_ridge_check("pcr_fold_in_ridge_model", true, F, rows, k, lambda, precision, n, index, item, val, U_out, &P));
+    RC(model_device(device));
+    if (stats) *stats = pcr_ridge_stats{};
+    if (n == 0) return PCR_OK;
+    ServeView v; ModelDev M;
+    RC(M.open(nullptr, n, F, rows, k, nullptr, nullptr, true, precision, &v));
+    return by_precision(v, [&](auto zero) -> int { return ridge_run<decltype(zero)>(v, lambda, weighted != 0, P, U_out, stats, per_user); });
+    });
+}
+
+int pcr_fold_in_ridge(pcr_solver* s, int weighted, int64_t n, const int64_t* index, const int32_t* item, const double* val, double* U_out,
+                      pcr_ridge_stats* stats, double* per_user) {
+    S_OR_ARG;
+    return abi_guard("pcr_fold_in_ridge", [&]() -> int {
+        const ServeView v = solver_view(s, 0);
+        const double lambda = s->ridge_lambda();
+        PcrRidgePlan P;
+        RC(pcr_fold_in_ridge_check("pcr_fold_in_ridge", false, nullptr, v.d2, v.r, lambda, v.dtype, n, index, item, val, U_out, &P));
+        if (stats) *stats = pcr_ridge_stats{};
+        if (n == 0) return PCR_OK;
+        return by_precision(v, [&](auto zero) -> int { return ridge_run<decltype(zero)>(v, lambda, weighted != 0, P, U_out, stats, per_user); });
     });
 }
 

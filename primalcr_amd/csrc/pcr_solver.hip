@@ -1028,6 +1028,7 @@ struct Solver final : pcr_solver {
     size_t small_common(int block) const { return carve_bytes(geo.ld, sizeof(T)) + carve_bytes(block / PCR_WAVE + 1, 8); }
     int strict() const { return prm.solver_type == PCR_SOLVER_PCR ? 1 : 0; }
     int foldin_params(pcr_params* p) override { *p = prm; return PCR_OK; }      // what pcr_fold_in (pcr_serve.hip) reads
+    double ridge_lambda() override { return prm.lambda; }
 
     // ------------------------------------------------------------------------------ launches
     // m = V_I u, sort, per-user loss -> objp.  Vm = matrix the scores are taken against.
