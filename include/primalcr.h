@@ -225,6 +225,8 @@ int pcr_partition_users(const int64_t *index, int64_t d1, int nparts, int64_t *b
  *                   contract, the tests hold them to each other; read at every call
  *   ridge_form      "cg" = pcr_fold_in_ridge / pcr_fold_in_ridge_model take the CG form for every user (the A/B arm of the direct
  *                   forms, and a test hook); "auto" (default) = the form rule; read when the call's plan is made
+ *   nnls_form       "cg" = pcr_fold_in_nnls / pcr_fold_in_nnls_model take the CG form at every rank (the A/B arm of the direct
+ *                   form, and a test hook); "auto" (default) = the form rule; read when the call's plan is made
  *   count_rows      1 = the U-step kernels count the rows of V they gather (pcr_solver_counter; a diagnostic that
  *                   costs the short-user classes 10-20 %, so off by default)
  *   debug           1 = print launch decisions to stderr
@@ -832,6 +834,66 @@ int pcr_fold_in_ridge_model(const double *F, int64_t rows, int64_t k, double lam
  * is local: nothing is exchanged and any rank may call it alone.  Nothing of the solver is written.  Profile slot: foldin/ridge. */
 int pcr_fold_in_ridge(pcr_solver *s, int weighted, int64_t n, const int64_t *index, const int32_t *item, const double *val,
                       double *U_out, pcr_ridge_stats *stats, double *per_user);                     /* [device] */
+
+/* ------------------------------------------------------------------------- */
+/* non-negative fold-in: rows >= 0 for CCDR1 models trained with -N 1         */
+/* (do_nmf, ccd-r1.cpp:19; no reference counterpart)                          */
+/* ------------------------------------------------------------------------- */
+/* The ridge fold-in's problem under the constraint the model was trained with.  For a user with ratings r on rows I of F (len of
+ * them), A = F[I], mu = lambda len (weighted != 0) or lambda (weighted == 0) as above:
+ *     minimise |r - A u|^2 + mu |u|^2   subject to u >= 0.
+ * With G = A^T A + mu I and b = A^T r the minimiser (unique for mu > 0) has a passive set P with u_P = G_PP^-1 b_P >= 0, u_Z = 0
+ * on the complement Z and y = G u - b >= 0 on Z.  It is found by block principal pivoting with exact solves (the Kim-Park rule):
+ *     P = all k coordinates;  alpha = 3;  beta = k + 1
+ *     for pivot = 1 .. PCR_NNLS_PIVOT_CAP:
+ *         u_P = G_PP^-1 b_P,  u_Z = 0;   y_Z = (G u - b)_Z,  y_P = 0
+ *         V = { j in P : u_j < 0 }  union  { j in Z : y_j < 0 }
+ *         if V is empty: PCR_NNLS_OK, stop
+ *         if |V| < beta:   beta = |V|; alpha = 3; X = V
+ *         elif alpha > 0:  alpha -= 1;          X = V
+ *         else:                                 X = { max V }
+ *         P = P xor X
+ * Pivot 1 is the unconstrained ridge solve: a user whose ridge row is already >= 0 stops there.  One workgroup solves one user in
+ * fp64 and rounds the row to the storage type on store (which keeps >= 0).  F = U and the item-major CSR fold in new items.
+ *   Forms              a function of the rank k alone (pcr_nnls_form):
+ *                        DIRECT  roundup(k, 16) <= PCR_RIDGE_DIRECT_MAX: G is built once on v_mfma_f64_16x16x4_f64 (the ridge
+ *                                entry's primal build) and kept in LDS; every pivot factors a copy with Z masked to a unit
+ *                                diagonal by blocked Cholesky and solves for b masked to P; 64 threads per user when the padded
+ *                                rank is <= 64, 256 beyond
+ *                        CG      wider ranks: the solve on P is the ridge entry's matrix-free CG from u = 0 with the search
+ *                                direction masked to P, Hp = mask_P(A^T (A p) + mu p), until |residual|^2 <= 1e-24 |b_P|^2, at
+ *                                most 2 min(len, |P|) + 10 iterations; one more pass gives y
+ *                      pcr_tune("nnls_form", "cg") forces the CG form ("auto" or removal: the rule).
+ *   Statuses           PCR_NNLS_OK; PCR_NNLS_SINGULAR: a masked Cholesky pivot that is <= 0 or not finite, or a CG step with
+ *                      p.Hp <= 0 or not finite -- the row is zeros and loss = obj = |r|^2; PCR_NNLS_CAP: PCR_NNLS_PIVOT_CAP pivots
+ *                      without an empty V, or a solve that stopped at its CG cap -- the row is the last iterate with its negative
+ *                      entries set to 0.  The pivot cap is a safety bound (the rule is finite in exact arithmetic).
+ *   Inputs             as pcr_fold_in_ridge_model's.  A user without ratings gets a zero row, status OK, 0 pivots.
+ *   Outputs            U_out [n][k]: the storage-type values widened, every one >= 0.  per_user (optional) [n][PCR_NNLS_FIELDS] =
+ *                      len, form, pivots, zeros (the coordinates of the returned row that are 0), loss, obj, status; loss and obj
+ *                      at the RETURNED (rounded) row.  stats (optional): the counts, and loss / obj added in user order.
+ *   Determinism        as the ridge entry's: a user's bits depend on its ratings, F and the parameters alone.
+ *   Errors             the ridge entry's, the message naming the nnls entry; PCR_ERR_ARG before any device is looked for.
+ *                      Without a device: PCR_ERR_DEVICE. */
+#define PCR_NNLS_FIELDS 7
+#define PCR_NNLS_DIRECT 0
+#define PCR_NNLS_CG     1
+#define PCR_NNLS_OK       0
+#define PCR_NNLS_SINGULAR 1
+#define PCR_NNLS_CAP      2
+#define PCR_NNLS_PIVOT_CAP 64
+typedef struct pcr_nnls_stats {
+    int64_t users, direct, cg, singular, cap, pivots, zeros;
+    double  loss, obj;
+} pcr_nnls_stats;
+/* Standalone: F (rows x k) host fp64 in model-file layout. */
+int pcr_fold_in_nnls_model(const double *F, int64_t rows, int64_t k, double lambda, int weighted, int precision, int device,
+                           int64_t n, const int64_t *index, const int32_t *item, const double *val,
+                           double *U_out, pcr_nnls_stats *stats, double *per_user);                 /* [device] */
+/* On ANY live solver: its device V, storage type, stream and lambda (pcr_fold_in_ridge's conventions).  Nothing of the solver is
+ * written.  Profile slot: foldin/nnls. */
+int pcr_fold_in_nnls(pcr_solver *s, int weighted, int64_t n, const int64_t *index, const int32_t *item, const double *val,
+                     double *U_out, pcr_nnls_stats *stats, double *per_user);                       /* [device] */
 
 /* per-kernel device timing (HIP events on the solver's stream, one pair per launch).
  * slot names: "<class>/<workgroup size>[.<length bound>][g][c][l][r][#n]" for the per-user kernels (classes

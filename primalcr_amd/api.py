@@ -25,6 +25,10 @@ PCR_RIDGE_DUAL, PCR_RIDGE_PRIMAL, PCR_RIDGE_CG = 0, 1, 2                        
 PCR_RIDGE_OK, PCR_RIDGE_SINGULAR, PCR_RIDGE_CG_CAP = 0, 1, 2                     # ... and its status values
 # fold_in_ridge's rule (include/primalcr.h): one wave up to WAVE_MAX ratings; the direct (Cholesky) forms up to a system of side DIRECT_MAX
 PCR_RIDGE_WAVE_MAX, PCR_RIDGE_DIRECT_MAX = 64, 112
+PCR_NNLS_FIELDS = ("n", "form", "pivots", "zeros", "loss", "obj", "status")       # fold_in_nnls's per_user columns
+PCR_NNLS_DIRECT, PCR_NNLS_CG = 0, 1                                               # ... its forms
+PCR_NNLS_OK, PCR_NNLS_SINGULAR, PCR_NNLS_CAP = 0, 1, 2                            # ... its status values
+PCR_NNLS_PIVOT_CAP = 64                                                           # ... and the pivots a user may take
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -118,6 +122,12 @@ class RidgeStats(C.Structure):
                 ("cg_cap", C.c_int64), ("iters", C.c_int64), ("loss", C.c_double), ("obj", C.c_double)]
 
 
+class NnlsStats(C.Structure):
+    """pcr_nnls_stats."""
+    _fields_ = [("users", C.c_int64), ("direct", C.c_int64), ("cg", C.c_int64), ("singular", C.c_int64), ("cap", C.c_int64),
+                ("pivots", C.c_int64), ("zeros", C.c_int64), ("loss", C.c_double), ("obj", C.c_double)]
+
+
 _LOG_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p)
 _lib = None
 _dp = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
@@ -209,6 +219,9 @@ def lib():
     if _LIB_OVERRIDE is None or hasattr(L, "pcr_fold_in_ridge"):
         L.pcr_fold_in_ridge_model.argtypes = [vp, i64, i64, cd, ci, ci, ci, i64, vp, vp, vp, vp, vp, vp]
         L.pcr_fold_in_ridge.argtypes = [vp, ci, i64, vp, vp, vp, vp, vp, vp]
+    if _LIB_OVERRIDE is None or hasattr(L, "pcr_fold_in_nnls"):
+        L.pcr_fold_in_nnls_model.argtypes = [vp, i64, i64, cd, ci, ci, ci, i64, vp, vp, vp, vp, vp, vp]
+        L.pcr_fold_in_nnls.argtypes = [vp, ci, i64, vp, vp, vp, vp, vp, vp]
     L.pcr_exposure_stats.argtypes = [vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(cd), C.POINTER(cd)]
     L.pcr_profile_enable.argtypes = [vp, ci]
     L.pcr_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(cd), C.POINTER(i64)]
@@ -785,6 +798,48 @@ def recommend_new_users_ridge(V, ratings, lam, topk, weighted=True, dtype=PCR_F6
     return items, scores, U_new, stats
 
 
+def nnls_form(k):
+    """The form fold_in_nnls() takes at rank k (include/primalcr.h), a function of k alone: PCR_NNLS_DIRECT when k padded to 16 is
+    <= PCR_RIDGE_DIRECT_MAX, PCR_NNLS_CG beyond."""
+    return PCR_NNLS_DIRECT if (k + 15) // 16 * 16 <= PCR_RIDGE_DIRECT_MAX else PCR_NNLS_CG
+
+
+def _nnls_call(n, k, per_user, fn):
+    """Shared by fold_in_nnls() and Solver.fold_in_nnls(): the buffers around fn(U_out pointer, stats pointer, per_user pointer);
+    returns (rows, stats dict[, per_user])."""
+    out = np.empty((n, k), np.float64)
+    st = NnlsStats()
+    pu = np.empty((n, len(PCR_NNLS_FIELDS)), np.float64) if per_user else None
+    _chk(fn(out.ctypes.data, C.addressof(st), None if pu is None else pu.ctypes.data))
+    stats = {f: getattr(st, f) for f, _ in NnlsStats._fields_}
+    return (out, stats, pu) if per_user else (out, stats)
+
+
+def fold_in_nnls(F, ratings, lam, weighted=True, dtype=PCR_F64, device=0, per_user=False):
+    """Non-negative factors for rows a model was not trained on, on the GPU (pcr_fold_in_nnls_model): fold_in_ridge()'s problem
+    under u >= 0, the constraint of a CCDR1 model trained with -N 1 -- each row is the exact minimiser of
+    |r - F[I] u|^2 + mu |u|^2 over u >= 0, found by block principal pivoting around exact solves.  Arguments as fold_in_ridge().
+    Returns (rows float64 [n, k], every entry >= 0, stats dict[, per_user float64 [n, 7] of PCR_NNLS_FIELDS]); loss and obj are
+    evaluated at the returned rows, which are rounded to `dtype`."""
+    F = np.ascontiguousarray(F, np.float64)
+    if F.ndim != 2:
+        raise ValueError("F must be [rows, k]")
+    index, item, val = _foldin_ratings(ratings)
+    n, k = index.shape[0] - 1, F.shape[1]
+    return _nnls_call(n, k, per_user, lambda uo, sp, pp: lib().pcr_fold_in_nnls_model(
+        F.ctypes.data, F.shape[0], k, float(lam), 1 if weighted else 0, int(dtype), int(device), n, index.ctypes.data, item.ctypes.data,
+        val.ctypes.data, uo, sp, pp))
+
+
+def recommend_new_users_nnls(V, ratings, lam, topk, weighted=True, dtype=PCR_F64, device=0):
+    """Top-K lists for users a non-negative model was not trained on: fold_in_nnls(), then recommend(U_new, V, topk,
+    exclude=ratings) -- the ratings the users were folded in on are left out.  Returns (items, scores, U_new, stats)."""
+    index, item, val = _foldin_ratings(ratings)
+    U_new, stats = fold_in_nnls(V, (index, item, val), lam, weighted=weighted, dtype=dtype, device=device)
+    items, scores = recommend(U_new, V, topk, exclude=(index, item), dtype=dtype, device=device)
+    return items, scores, U_new, stats
+
+
 def exposure_stats(x):
     """The closing arithmetic of one exposure row (pcr_exposure_stats): dict(recs, items_covered, coverage, gini)."""
     x = np.ascontiguousarray(x, np.int64)
@@ -1156,6 +1211,15 @@ class Solver:
         index, item, val = _foldin_ratings(ratings)
         n = index.shape[0] - 1
         return _ridge_call(n, self.k, per_user, lambda uo, sp, pp: lib().pcr_fold_in_ridge(
+            self._h, 1 if weighted else 0, n, index.ctypes.data, item.ctypes.data, val.ctypes.data, uo, sp, pp))
+
+    def fold_in_nnls(self, ratings, weighted=True, per_user=False):
+        """Non-negative factors for users this solver was not trained on, against its device V (pcr_fold_in_nnls), in its storage
+        type and with its lambda; any solver type; arguments and result as fold_in_nnls().  Local to the rank; nothing of the
+        solver is written."""
+        index, item, val = _foldin_ratings(ratings)
+        n = index.shape[0] - 1
+        return _nnls_call(n, self.k, per_user, lambda uo, sp, pp: lib().pcr_fold_in_nnls(
             self._h, 1 if weighted else 0, n, index.ctypes.data, item.ctypes.data, val.ctypes.data, uo, sp, pp))
 
     def sync(self):

@@ -45,6 +45,12 @@
 //                    --plain-reg, mu = lambda.  stdout gets one line "foldin_ridge users n dual n primal n cg n singular n cg_cap n
 //                    iters n loss x obj x" (%g); everything else as --fold-in, with the same exclusions of other modes; takes no -s
 //                    and no --steps
+//   omp-pmf-recommend --fold-in-nnls data_dir -l lambda [--plain-reg] [-K topk] [--f32] [--scores] model_file output_file
+//   omp-pmf-recommend --fold-in-nnls data_dir -l lambda [--plain-reg] --eval data_dir [-c ...] [--threshold v] [--f32] model_file [output_file]
+//     --fold-in-nnls dir  --fold-in-ridge under u >= 0, for CCDR1 models trained with -N 1 (pcr_fold_in_nnls_model): each new user's
+//                    row is the exact minimiser of the same objective over the non-negative rows.  stdout gets one line
+//                    "foldin_nnls users n direct n cg n singular n cap n pivots n zeros n loss x obj x" (%g); combinations and
+//                    refusals as --fold-in-ridge, which it does not go with
 //   omp-pmf-recommend [--allow items_file] [--candidates file] [-K topk] [-x data_dir] [-u users_file] [--f32] [--scores] model_file output_file
 //     --allow file   recommend among these items only (pcr_recommend_filtered_model): one 1-based item id per line, like -u
 //     --candidates f a candidate list per requested user: line i holds the space-separated 1-based item ids of the i-th requested
@@ -113,6 +119,11 @@ static const char* USAGE =
     "    --fold-in-ridge dir  --fold-in for squared-loss (CCDR1, -s 0) models: the exact ridge solution per new user; stdout gets a\n"
     "                   \"foldin_ridge users n dual n primal n cg n singular n cg_cap n iters n loss x obj x\" line; -l lambda is\n"
     "                   weighted by each user's rating count as in CCDR1 training; --plain-reg: the plain lambda |u|^2; no -s, --steps\n"
+    "       omp-pmf-recommend --fold-in-nnls data_dir -l lambda [--plain-reg] [-K topk] [--f32] [--scores] model_file output_file\n"
+    "       omp-pmf-recommend --fold-in-nnls data_dir -l lambda [--plain-reg] --eval data_dir [-c ...] [--threshold v] [--f32] model_file [output_file]\n"
+    "    --fold-in-nnls dir  --fold-in-ridge under u >= 0, for CCDR1 models trained with -N 1: the exact non-negative minimiser per new\n"
+    "                   user; stdout gets a \"foldin_nnls users n direct n cg n singular n cap n pivots n zeros n loss x obj x\" line;\n"
+    "                   -l, --plain-reg and the refusals as --fold-in-ridge, which it does not go with\n"
     "       omp-pmf-recommend [--allow items_file] [--candidates file] [-K topk] [-x data_dir] [-u users_file] [--f32] [--scores] model_file output_file\n"
     "    --allow file   recommend among these items only: one 1-based item id per line\n"
     "    --candidates f line i: the space-separated 1-based candidate items of the i-th requested user (an empty line: none);\n"
@@ -377,9 +388,10 @@ static int run_tradeoff(const char* edir, const std::vector<double>& U, const st
 
 // --fold-in: the training CSR of a data directory over the model's items (any number of users) and, from it, the new users'
 // factors (pcr_fold_in_model); the summary line goes to stdout
-// (ridge: pcr_fold_in_ridge_model instead, mu = lambda x count unless plain_reg; its own summary line)
+// (ridge: pcr_fold_in_ridge_model instead, mu = lambda x count unless plain_reg; its own summary line; nnls: pcr_fold_in_nnls_model,
+// likewise)
 static bool run_fold_in(const char* dir, const std::vector<double>& V, int64_t d2, int64_t k, double lambda, int solver, int steps, bool f32,
-                        bool ridge, bool plain_reg, int64_t* n_out, std::vector<int64_t>& index, std::vector<int32_t>& item, std::vector<double>& U_new) {
+                        bool ridge, bool nnls, bool plain_reg, int64_t* n_out, std::vector<int64_t>& index, std::vector<int32_t>& item, std::vector<double>& U_new) {
     pcr_dataset* ds = nullptr;
     if (pcr_dataset_load_mt(dir, 0, &ds) != PCR_OK) { fprintf(stderr, "%s\n", pcr_last_error()); return false; }
     int64_t n, xd2, nnz, tnnz;
@@ -399,6 +411,18 @@ static bool run_fold_in(const char* dir, const std::vector<double>& V, int64_t d
     pcr_params_default(&p);
     p.solver_type = solver; p.k = (int)k; p.lambda = lambda; p.precision = f32 ? PCR_F32 : PCR_F64;
     U_new.resize((size_t)n * k);
+    if (nnls) {
+        pcr_nnls_stats ns;
+        if (pcr_fold_in_nnls_model(V.data(), d2, k, lambda, plain_reg ? 0 : 1, p.precision, 0, n, index.data(), item.data(), val.data(), U_new.data(),
+                                   &ns, nullptr) != PCR_OK) {
+            fprintf(stderr, "fold-in-nnls: %s\n", pcr_last_error());
+            return false;
+        }
+        printf("foldin_nnls users %lld direct %lld cg %lld singular %lld cap %lld pivots %lld zeros %lld loss %g obj %g\n", (long long)ns.users,
+               (long long)ns.direct, (long long)ns.cg, (long long)ns.singular, (long long)ns.cap, (long long)ns.pivots, (long long)ns.zeros, ns.loss, ns.obj);
+        *n_out = n;
+        return true;
+    }
     if (ridge) {
         pcr_ridge_stats rs;
         if (pcr_fold_in_ridge_model(V.data(), d2, k, lambda, plain_reg ? 0 : 1, p.precision, 0, n, index.data(), item.data(), val.data(), U_new.data(),
@@ -434,6 +458,7 @@ int main(int argc, char** argv) {
     std::vector<const char*> pos;
     const char* fdir = nullptr;                                    // --fold-in
     const char* rdir = nullptr;                                    // --fold-in-ridge
+    const char* ndir = nullptr;                                    // --fold-in-nnls
     bool plain_reg = false;
     double lambda = 0.0;
     bool have_lambda = false, have_s = false, have_steps = false;
@@ -443,6 +468,11 @@ int main(int argc, char** argv) {
         if (!strcmp(a, "--fold-in-ridge")) {
             if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
             rdir = argv[++i];
+            continue;
+        }
+        if (!strcmp(a, "--fold-in-nnls")) {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
+            ndir = argv[++i];
             continue;
         }
         if (!strcmp(a, "--plain-reg")) { plain_reg = true; continue; }
@@ -524,7 +554,15 @@ int main(int argc, char** argv) {
         else pos.push_back(a);
     }
     const bool tradeoff = !thetas.empty();
-    if (rdir) {                                                    // (its own rules; then it follows --fold-in's flow)
+    if (ndir) {                                                    // (--fold-in-ridge's rules under its own name)
+        if (rdir) { fprintf(stderr, "--fold-in-nnls does not go with --fold-in-ridge\n"); return 1; }
+        if (fdir) { fprintf(stderr, "--fold-in-nnls does not go with --fold-in\n"); return 1; }
+        if (afile || cfile) { fprintf(stderr, "--allow and --candidates do not go with --fold-in-nnls\n"); return 1; }
+        if (xdir || ufile || diversity || mmr || tradeoff || with_ranks) { fprintf(stderr, "--fold-in-nnls does not go with -x, -u, --diversity, --mmr, --tradeoff or --ranks\n"); return 1; }
+        if (have_s || have_steps) { fprintf(stderr, "--fold-in-nnls takes no -s and no --steps\n"); return 1; }
+        if (!have_lambda) { fprintf(stderr, "--fold-in-nnls needs -l lambda\n"); return 1; }
+        if (lambda < 0.0) { fprintf(stderr, "-l %g: must not be negative with --fold-in-nnls\n", lambda); return 1; }
+    } else if (rdir) {                                             // (its own rules; then it follows --fold-in's flow)
         if (fdir) { fprintf(stderr, "--fold-in-ridge does not go with --fold-in\n"); return 1; }
         if (afile || cfile) { fprintf(stderr, "--allow and --candidates do not go with --fold-in-ridge\n"); return 1; }
         if (xdir || ufile || diversity || mmr || tradeoff || with_ranks) { fprintf(stderr, "--fold-in-ridge does not go with -x, -u, --diversity, --mmr, --tradeoff or --ranks\n"); return 1; }
@@ -532,8 +570,8 @@ int main(int argc, char** argv) {
         if (!have_lambda) { fprintf(stderr, "--fold-in-ridge needs -l lambda\n"); return 1; }
         if (lambda < 0.0) { fprintf(stderr, "-l %g: must not be negative with --fold-in-ridge\n", lambda); return 1; }
     } else if (plain_reg) { fprintf(stderr, "--plain-reg goes with --fold-in-ridge\n"); return 1; }
-    const bool ridge = rdir != nullptr;
-    if (ridge) fdir = rdir;
+    const bool nnls = ndir != nullptr, ridge = rdir != nullptr || nnls;          // (ridge: both take --fold-in-ridge's flow)
+    if (ridge) fdir = nnls ? ndir : rdir;
     if ((afile || cfile) && (edir || diversity || mmr || tradeoff || with_ranks || fdir)) {
         fprintf(stderr, "--allow and --candidates do not go with --eval, --diversity, --mmr, --tradeoff, --ranks or --fold-in\n");
         return 1;
@@ -580,7 +618,7 @@ int main(int argc, char** argv) {
     if (cfile && !read_candidates(cfile, (int64_t)users.size(), d2, cptr, citem)) return 1;
     if (fdir) {                                                    // the new users take the model's users' place: their factors, their ratings excluded
         std::vector<double> U_new;
-        if (!run_fold_in(fdir, V, d2, k, lambda, solver, steps, f32, ridge, plain_reg, &d1, xindex, xitem, U_new)) return 1;
+        if (!run_fold_in(fdir, V, d2, k, lambda, solver, steps, f32, ridge, nnls, plain_reg, &d1, xindex, xitem, U_new)) return 1;
         U.swap(U_new);
         users.resize((size_t)d1);
         for (int64_t u = 0; u < d1; ++u) users[(size_t)u] = (int32_t)u;

@@ -362,7 +362,7 @@ extern "C" int pcr_dataset_from_csr(int64_t d1, int64_t d2, const int64_t* index
 static std::map<std::string, std::string>& tune_table() { static thread_local std::map<std::string, std::string> t; return t; }
 static const char* const TUNE_KEYS[] = {"ustep_mode", "cluster_k", "cluster_users", "ubins", "ustep_gram", "spmm_tiles", "spmm_chunk", "sddmm_csc",
                                         "lanes", "pipeline", "window_cache", "prepare_merged", "resort_window", "allreduce_chunks", "p2p_ll",
-                                        "p2p_timeout_ms", "p2p_queue_budget", "count_rows", "debug", "win16", "ustep_win_lds", "plan_key64", "ustep_newton", "vblock_users", "recommend_select", "ranks_batch_users", "rerank_lds", "ridge_form", "fault_cluster_member", "fault_p2p_skip", "fault_p2p_coarse", nullptr};
+                                        "p2p_timeout_ms", "p2p_queue_budget", "count_rows", "debug", "win16", "ustep_win_lds", "plan_key64", "ustep_newton", "vblock_users", "recommend_select", "ranks_batch_users", "rerank_lds", "ridge_form", "nnls_form", "fault_cluster_member", "fault_p2p_skip", "fault_p2p_coarse", nullptr};
 extern "C" int pcr_tune(const char* key, const char* value) {
     if (!key) { pcr_set_error("pcr_tune: null key"); return PCR_ERR_ARG; }
     bool known = false;
@@ -1617,8 +1617,9 @@ int pcr_ridge_form(int64_t len, int64_t k) {
     return PCR_RIDGE_CG;
 }
 
-int pcr_fold_in_ridge_check(const char* who, bool need_F, const double* F, int64_t rows, int64_t k, double lambda, int precision, int64_t n,
-                            const int64_t* index, const int32_t* item, const double* val, const double* U_out, PcrRidgePlan* plan) {
+// the argument checks of the ridge and the non-negative entries, and the copy X of the ratings with item-ascending rows
+static int fold_in_ls_args(const char* who, bool need_F, const double* F, int64_t rows, int64_t k, double lambda, int precision, int64_t n,
+                           const int64_t* index, const int32_t* item, const double* val, const double* U_out, PcrCsr& X) {
     auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
     if (need_F && !F) return bad("null F");
     if (k < 1) return bad("rank k must be >= 1");
@@ -1640,9 +1641,16 @@ int pcr_fold_in_ridge_check(const char* who, bool need_F, const double* F, int64
     const int all = pcr_csr_rows_scan(rows, n, index, item, val);
     if (all & 1) return bad("an item id is outside [0, rows)");
     if (all & 2) return bad("a rating is not finite");
+    pcr_csr_sorted_copy(rows, n, index, item, val, (all & 4) != 0, X);
+    return PCR_OK;
+}
+
+int pcr_fold_in_ridge_check(const char* who, bool need_F, const double* F, int64_t rows, int64_t k, double lambda, int precision, int64_t n,
+                            const int64_t* index, const int32_t* item, const double* val, const double* U_out, PcrRidgePlan* plan) {
     PcrRidgePlan local;
     PcrRidgePlan& P = plan ? *plan : local;
-    pcr_csr_sorted_copy(rows, n, index, item, val, (all & 4) != 0, P.X);
+    const int rc = fold_in_ls_args(who, need_F, F, rows, k, lambda, precision, n, index, item, val, U_out, P.X);
+    if (rc != PCR_OK) return rc;
     std::string knob;
     P.force_cg = pcr_tune_get("ridge_form", &knob) && knob == "cg";
     // a user's launch class: the CG form first, then primal and dual, 256 threads before one wave, more tiles before fewer; inside
@@ -1684,6 +1692,47 @@ void pcr_ridge_stats_from(const double* per_user, int64_t n, pcr_ridge_stats* st
         s.iters += (int64_t)o[2];
         s.loss += o[3]; s.obj += o[4];
         if (status == PCR_RIDGE_SINGULAR) s.singular += 1; else if (status == PCR_RIDGE_CG_CAP) s.cg_cap += 1;
+    }
+    *stats = s;
+}
+
+// ------------------------------------------------------------------------------------------
+// non-negative fold-in (include/primalcr.h, "non-negative fold-in"): the form rule, argument checks and the host-side plan
+// ------------------------------------------------------------------------------------------
+int pcr_nnls_form(int64_t k) { return (k + 15) / 16 * 16 <= PCR_RIDGE_DIRECT_MAX ? PCR_NNLS_DIRECT : PCR_NNLS_CG; }
+
+int pcr_fold_in_nnls_check(const char* who, bool need_F, const double* F, int64_t rows, int64_t k, double lambda, int precision, int64_t n,
+                           const int64_t* index, const int32_t* item, const double* val, const double* U_out, PcrRidgePlan* plan) {
+    PcrRidgePlan local;
+    PcrRidgePlan& P = plan ? *plan : local;
+    const int rc = fold_in_ls_args(who, need_F, F, rows, k, lambda, precision, n, index, item, val, U_out, P.X);
+    if (rc != PCR_OK) return rc;
+    std::string knob;
+    P.force_cg = pcr_tune_get("nnls_form", &knob) && knob == "cg";
+    // (form, workgroup size) are functions of the rank, so the users of a call are one launch class: the longest start first
+    // (equal lengths by ascending id)
+    PcrRidgePlan::Range g;
+    g.form = P.force_cg ? PCR_NNLS_CG : pcr_nnls_form(k);
+    g.tiles = g.form == PCR_NNLS_CG ? 0 : (int)((k + 15) / 16);
+    g.block = (g.form == PCR_NNLS_CG || g.tiles * 16 > 64) ? 256 : 64;
+    g.first = 0; g.count = n;
+    P.order.resize((size_t)n);
+    for (int64_t u = 0; u < n; ++u) P.order[(size_t)u] = (int32_t)u;
+    std::stable_sort(P.order.begin(), P.order.end(), [&](int32_t x, int32_t y) { return index[x + 1] - index[x] > index[y + 1] - index[y]; });
+    P.ranges.assign(1, g);
+    return PCR_OK;
+}
+
+void pcr_nnls_stats_from(const double* per_user, int64_t n, pcr_nnls_stats* stats) {
+    pcr_nnls_stats s = {};
+    s.users = n;
+    for (int64_t u = 0; u < n; ++u) {
+        const double* o = per_user + (size_t)u * PCR_NNLS_FIELDS;
+        const int form = (int)o[1], status = (int)o[6];
+        if (form == PCR_NNLS_DIRECT) s.direct += 1; else s.cg += 1;
+        s.pivots += (int64_t)o[2]; s.zeros += (int64_t)o[3];
+        s.loss += o[4]; s.obj += o[5];
+        if (status == PCR_NNLS_SINGULAR) s.singular += 1; else if (status == PCR_NNLS_CAP) s.cap += 1;
     }
     *stats = s;
 }

@@ -224,3 +224,13 @@ int pcr_fold_in_ridge_check(const char* who, bool need_F, const double* F, int64
                             const int64_t* index, const int32_t* item, const double* val, const double* U_out, PcrRidgePlan* plan);
 // stats from the per-user table [n][PCR_RIDGE_FIELDS]: the counts, and loss / obj added in user order
 void pcr_ridge_stats_from(const double* per_user, int64_t n, pcr_ridge_stats* stats);
+
+// Non-negative fold-in (include/primalcr.h, "non-negative fold-in").  The form at rank k (PCR_NNLS_DIRECT / CG), a function of k alone.
+int pcr_nnls_form(int64_t k);
+// The ridge entries' argument checks under the nnls entry's name (one shared routine), and the plan for k_nnls_direct / k_nnls_cg
+// in a PcrRidgePlan: form and workgroup size follow from the rank, so there is one range, its users in descending length.
+// force_cg: pcr_tune("nnls_form", "cg") when the plan was made.
+int pcr_fold_in_nnls_check(const char* who, bool need_F, const double* F, int64_t rows, int64_t k, double lambda, int precision, int64_t n,
+                           const int64_t* index, const int32_t* item, const double* val, const double* U_out, PcrRidgePlan* plan);
+// stats from the per-user table [n][PCR_NNLS_FIELDS]: the counts, and loss / obj added in user order
+void pcr_nnls_stats_from(const double* per_user, int64_t n, pcr_nnls_stats* stats);

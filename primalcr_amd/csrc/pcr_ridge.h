@@ -112,6 +112,250 @@ static inline size_t ridge_direct_bytes(int mp, int ld, int block) {
            carve_bytes(mp, 4) + std::max(stage, tiles);
 }
 
+// The three stages of the direct forms as workgroup functions: k_ridge_direct below and k_nnls_direct (pcr_nnls.h) run the same
+// ones.  Every thread of the workgroup calls ridge_gram and ridge_chol (both hold barriers); ridge_trisolve is wave 0's.
+//
+// 1. M's lower-triangular tiles on the matrix cores, 16 contraction indices at a time.  dual != 0: M = A A^T + mu I (m = n; itm:
+//    the user's items in LDS); else M = A^T A + mu I (m = r) and the return value is b[tid] = (A^T r)[tid] for tid < mp.  Zc: the
+//    staging chunk [16][mp + 1], over which the tiles are written at the end (the caller's barrier makes them visible); rch: 16
+//    doubles.  Rows / columns beyond m are zeros with a unit diagonal, which the factorisation passes through unchanged.
+template <typename T, int BLOCK>
+__device__ __forceinline__ double ridge_gram(const T* __restrict__ F, const int32_t* __restrict__ uit, const double* __restrict__ uval, int n, int r, int ld,
+                                             int m, int mp, int dual, double mu, const int32_t* itm, double* rch, double* Zc) {
+    constexpr int NW = BLOCK / PCR_WAVE, MAXM = BLOCK == 64 ? 64 : 112, MAXT = MAXM / 16;
+    constexpr int MAXP = (MAXT * (MAXT + 1) / 2 + NW - 1) / NW;          // tile pairs per wave: 10 (one wave, 4 x 4 tiles) or 7 (four waves, 7 x 7)
+    constexpr int RPP = BLOCK / 16, NREG = 16 * MAXM / BLOCK;            // staging: rows per pass, values per thread (16 or 7)
+    double* Tl = Zc;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int mps = mp + 1, nt = mp / 16, npairs = nt * (nt + 1) / 2;
+    const int row = lane & 15, kh = lane >> 4;                           // MFMA operand indices of this lane
+    const int pp = tid >> 4, t16 = tid & 15;
+    const int clen = dual ? r : n;                                   // contraction length: columns (dual) or ratings (primal)
+    ridge_f64x4 acc[MAXP];
+#pragma unroll
+    for (int q = 0; q < MAXP; ++q)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[q][e] = 0.0;
+    int offA[MAXP], offB[MAXP];                                      // this wave's tile pairs (I >= J) as offsets inside a staged row
+#pragma unroll
+    for (int q = 0; q < MAXP; ++q) {
+        const int pr = wid + q * NW;
+        int I = 0, rem = pr < npairs ? pr : 0;                       // pr -> (I, J), J <= I, row-major over the lower triangle
+        while (rem > I) { rem -= I + 1; ++I; }
+        offA[q] = I * 16 + row; offB[q] = rem * 16 + row;
+    }
+    T xr[NREG];
+    double rreg = 0.0;
+    // issue(): the next chunk's values into registers; consume(): into the (idle) staging chunk as fp64.
+    //   primal: thread (pp, t16) holds ratings c0 + pp + RPP j (j < 16 / RPP) x columns t16 + 16 k  -> Zc[rating][column]
+    //   dual:   thread (pp, t16) holds column c0 + t16 of the user's rows pp + RPP j (j < NREG)      -> Zc[column][rating]
+    auto issue = [&](int c0) {
+#pragma unroll
+        for (int j = 0; j < NREG; ++j) xr[j] = (T)0;
+        if (dual) {
+            const int c = c0 + t16;
+#pragma unroll
+            for (int j = 0; j < NREG; ++j) {
+                const int p = pp + RPP * j;
+                if (p < n && c < r) xr[j] = F[(size_t)itm[p] * ld + c];
+            }
+        } else {
+            constexpr int NCK = MAXM / 16;
+#pragma unroll
+            for (int j = 0; j < 16 / RPP; ++j) {
+                const int p = c0 + pp + RPP * j;
+                if (p < n) {
+                    const T* frow = F + (size_t)uit[p] * ld;
+#pragma unroll
+                    for (int k = 0; k < NCK; ++k) { const int c = t16 + 16 * k; if (c < r) xr[j * NCK + k] = frow[c]; }
+                }
+            }
+            if (tid < 16) rreg = c0 + tid < n ? uval[c0 + tid] : 0.0;
+        }
+    };
+    auto consume = [&]() {
+        if (dual) {
+#pragma unroll
+            for (int j = 0; j < NREG; ++j) { const int p = pp + RPP * j; if (p < mp) Zc[t16 * mps + p] = (double)xr[j]; }
+        } else {
+            constexpr int NCK = MAXM / 16;
+#pragma unroll
+            for (int j = 0; j < 16 / RPP; ++j)
+#pragma unroll
+                for (int k = 0; k < NCK; ++k) { const int c = t16 + 16 * k; if (c < mp) Zc[(pp + RPP * j) * mps + c] = (double)xr[j * NCK + k]; }
+            if (tid < 16) rch[tid] = rreg;
+        }
+    };
+    double bacc = 0.0;                                               // primal: b[tid] = (A^T r)[tid]
+    issue(0);
+    consume();
+    __syncthreads();
+    for (int c0 = 0; c0 < clen; c0 += 16) {
+        const bool more = c0 + 16 < clen;
+        if (more) issue(c0 + 16);
+#pragma unroll 1
+        for (int s4 = 0; s4 < 4; ++s4) {                             // (not unrolled: one k-step's operands in registers at a time)
+            const int pb = (s4 * 4 + kh) * mps;
+#pragma unroll
+            for (int q = 0; q < MAXP; ++q)
+                if (wid + q * NW < npairs) acc[q] = ridge_mma(Zc[pb + offA[q]], Zc[pb + offB[q]], acc[q]);      // (wave-uniform)
+        }
+        if (!dual && tid < mp) {
+#pragma unroll
+            for (int p = 0; p < 16; ++p) bacc += Zc[p * mps + tid] * rch[p];
+        }
+        __syncthreads();
+        if (more) { consume(); __syncthreads(); }
+    }
+    // M = Z^T Z + mu I into the tiles (over the staging chunk: the loop above ends in a barrier); beyond m a unit diagonal
+#pragma unroll
+    for (int q = 0; q < MAXP; ++q) {
+        const int pr = wid + q * NW;
+        if (pr < npairs) {
+            int I = 0, rem = pr;
+            while (rem > I) { rem -= I + 1; ++I; }
+            double* tile = Tl + (size_t)ridge_tix(I, rem) * RIDGE_TILE;
+            const int cl = lane & 15, col = rem * 16 + cl;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int rl = (lane >> 4) + 4 * e, rw = I * 16 + rl;
+                double v = acc[q][e] + (rw == col ? mu : 0.0);
+                if (rw >= m || col >= m) v = rw == col ? 1.0 : 0.0;
+                tile[rl * RIDGE_TP + cl] = v;
+            }
+        }
+    }
+    return bacc;
+}
+
+// 2. blocked Cholesky of the nt x nt tiles Tl (lower triangle, in place; pcr_newton.h's scheme); dinv: 1 / L[i][i].  The caller
+//    has set red[7] = 0 (the "not positive definite" flag) behind a barrier.  Returns true for a pivot that is <= 0 or not finite.
+template <int BLOCK>
+__device__ __forceinline__ bool ridge_chol(double* Tl, double* dinv, double* red, int nt) {
+    constexpr int NW = BLOCK / PCR_WAVE;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int row = lane & 15, kh = lane >> 4;
+    for (int k = 0; k < nt; ++k) {
+        double* D = Tl + (size_t)ridge_tix(k, k) * RIDGE_TILE;
+        if (wid == 0) {                                              // (a) the diagonal tile: lanes 0..15 hold one ROW each in registers
+            double a[16];
+            const int rr = lane & 15;
+#pragma unroll
+            for (int c = 0; c < 16; ++c) a[c] = D[rr * RIDGE_TP + c];
+            bool pd = true;
+#pragma unroll
+            for (int kk = 0; kk < 16; ++kk) {
+#pragma unroll
+                for (int j = 0; j < kk; ++j) a[kk] -= a[j] * ridge_readlane(a[j], kk);
+                const double dkk = ridge_readlane(a[kk], kk);
+                pd = pd && ridge_pos(dkk);                           // (uniform)
+                const double ri = 1.0 / sqrt(dkk);
+                a[kk] = rr == kk ? dkk * ri : a[kk] * ri;
+                if (lane == 0) dinv[k * 16 + kk] = ri;
+            }
+            if (!pd) { if (lane == 0) red[7] = 1.0; }
+            else if (lane < 16) {
+#pragma unroll
+                for (int c = 0; c < 16; ++c) D[rr * RIDGE_TP + c] = a[c];
+            }
+        }
+        __syncthreads();
+        if (red[7] != 0.0) break;                                    // (uniform: read behind the barrier)
+        const int below = nt - k - 1;
+        if (tid < below * 16) {                                      // (b) the panel below: X L_kk^T = A, one row per thread (below <= 6, 3 on one wave)
+            double* A = Tl + (size_t)ridge_tix(k + 1 + (tid >> 4), k) * RIDGE_TILE + (tid & 15) * RIDGE_TP;
+            double x[16];
+#pragma unroll
+            for (int c = 0; c < 16; ++c) x[c] = A[c];
+#pragma unroll
+            for (int c = 0; c < 16; ++c) {
+                double sacc = x[c];
+#pragma unroll
+                for (int j = 0; j < c; ++j) sacc -= x[j] * D[c * RIDGE_TP + j];
+                x[c] = sacc * dinv[k * 16 + c];
+            }
+#pragma unroll
+            for (int c = 0; c < 16; ++c) A[c] = x[c];
+        }
+        __syncthreads();
+        const int tp = below * (below + 1) / 2;                      // (c) trailing update A_ij -= L_ik L_jk^T on the matrix cores
+        for (int pr = wid; pr < tp; pr += NW) {
+            int i = 0, rem = pr;
+            while (rem > i) { rem -= i + 1; ++i; }
+            double* Cm = Tl + (size_t)ridge_tix(k + 1 + i, k + 1 + rem) * RIDGE_TILE;
+            const double* Li = Tl + (size_t)ridge_tix(k + 1 + i, k) * RIDGE_TILE;
+            const double* Lj = Tl + (size_t)ridge_tix(k + 1 + rem, k) * RIDGE_TILE;
+            ridge_f64x4 c4;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) c4[e] = Cm[((lane >> 4) + 4 * e) * RIDGE_TP + (lane & 15)];
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) c4 = ridge_mma(-Li[row * RIDGE_TP + s4 * 4 + kh], Lj[row * RIDGE_TP + s4 * 4 + kh], c4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) Cm[((lane >> 4) + 4 * e) * RIDGE_TP + (lane & 15)] = c4[e];
+        }
+        __syncthreads();
+    }
+    return red[7] != 0.0;
+}
+
+// 3. the two triangular solves, M x = gv in place, with the factor ridge_chol left: one wave, lane l holds entries l and l + 64
+//    (pcr_newton.h)
+__device__ __forceinline__ void ridge_trisolve(const double* Tl, const double* dinv, double* gv, int mp, int nt) {
+    const int lane = threadIdx.x & 63;
+    const int j0 = lane, j1 = lane + 64, t0 = j0 >> 4, t1 = j1 >> 4;
+    double y0 = j0 < mp ? gv[j0] : 0.0, y1 = j1 < mp ? gv[j1] : 0.0;
+    const double dv0 = j0 < mp ? dinv[j0] : 1.0, dv1 = j1 < mp ? dinv[j1] : 1.0;
+    const int tc0 = t0 < nt ? t0 : nt - 1, tc1 = t1 < nt ? t1 : nt - 1;
+    for (int ib = 0; ib < nt; ++ib) {                            // L y = g, one tile column of L at a time
+        double l0[16], l1[16];
+        const double* q0 = Tl + (size_t)ridge_tix(tc0 < ib ? ib : tc0, ib) * RIDGE_TILE + (j0 & 15) * RIDGE_TP;
+        const double* q1 = Tl + (size_t)ridge_tix(tc1 < ib ? ib : tc1, ib) * RIDGE_TILE + (j1 & 15) * RIDGE_TP;
+#pragma unroll
+        for (int ii = 0; ii < 16; ++ii) { l0[ii] = q0[ii]; l1[ii] = q1[ii]; }
+        if (ib < 4) {
+#pragma unroll
+            for (int ii = 0; ii < 16; ++ii) {
+                const int i = ib * 16 + ii;
+                const double yi = ridge_readlane(y0 * dv0, i);
+                y0 = j0 == i ? yi : (j0 > i ? y0 - l0[ii] * yi : y0);
+                y1 = j1 < mp ? y1 - l1[ii] * yi : y1;
+            }
+        } else {
+#pragma unroll
+            for (int ii = 0; ii < 16; ++ii) {
+                const int i = ib * 16 + ii;
+                const double yi = ridge_readlane(y1 * dv1, i - 64);
+                y1 = j1 == i ? yi : ((j1 > i && j1 < mp) ? y1 - l1[ii] * yi : y1);
+            }
+        }
+    }
+    for (int ib = nt - 1; ib >= 0; --ib) {                       // L^T x = y (in place), one tile ROW of L at a time
+        double l0[16], l1[16];
+        const double* q0 = Tl + (size_t)ridge_tix(ib, tc0 > ib ? ib : tc0) * RIDGE_TILE + (j0 & 15);
+        const double* q1 = Tl + (size_t)ridge_tix(ib, tc1 > ib ? ib : tc1) * RIDGE_TILE + (j1 & 15);
+#pragma unroll
+        for (int ii = 0; ii < 16; ++ii) { l0[ii] = q0[ii * RIDGE_TP]; l1[ii] = q1[ii * RIDGE_TP]; }
+        if (ib >= 4) {
+#pragma unroll
+            for (int ii = 15; ii >= 0; --ii) {
+                const int i = ib * 16 + ii;
+                const double xi = ridge_readlane(y1 * dv1, i - 64);
+                y1 = j1 == i ? xi : ((j1 < i && j1 < mp) ? y1 - l1[ii] * xi : y1);
+                y0 -= l0[ii] * xi;                               // (j0 < i for every i >= 64)
+            }
+        } else {
+#pragma unroll
+            for (int ii = 15; ii >= 0; --ii) {
+                const int i = ib * 16 + ii;
+                const double xi = ridge_readlane(y0 * dv0, i);
+                y0 = j0 == i ? xi : ((j0 < i && j0 < mp) ? y0 - l0[ii] * xi : y0);
+            }
+        }
+    }
+    if (j0 < mp) gv[j0] = y0;
+    if (j1 < mp) gv[j1] = y1;
+}
+
 // dual != 0: M = A A^T + mu I (m = n); else M = A^T A + mu I (m = r).  mp: the launch's padded side (a multiple of 16, at least
 // every user's m; BLOCK = 64: at most 64, BLOCK = 256: at most 112).  A user's results do not depend on mp: rows / columns beyond
 // m are zeros with a unit diagonal, which the factorisation passes through unchanged.
@@ -119,9 +363,6 @@ template <typename T, int BLOCK>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2))) void k_ridge_direct(RidgeCsr X, const int32_t* __restrict__ users, int nusers, const T* __restrict__ F, int r, int ld,
                                                         T* __restrict__ Uout, double* __restrict__ per_user, double lambda, int weighted, int dual,
                                                         int mp) {
-    constexpr int NW = BLOCK / PCR_WAVE, MAXM = BLOCK == 64 ? 64 : 112, MAXT = MAXM / 16;
-    constexpr int MAXP = (MAXT * (MAXT + 1) / 2 + NW - 1) / NW;          // tile pairs per wave: 10 (one wave, 4 x 4 tiles) or 7 (four waves, 7 x 7)
-    constexpr int RPP = BLOCK / 16, NREG = 16 * MAXM / BLOCK;            // staging: rows per pass, values per thread (16 or 7)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Carver cv(smem);
     double* red = cv.take<double>(8);
@@ -132,12 +373,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2))) void
     double* rv = cv.take<double>(mp);                                    // dual: the user's ratings
     double* uvec = cv.take<double>(mp > ld ? mp : ld);
     int32_t* itm = cv.take<int32_t>(mp);                                 // dual: the user's items
-    double* Zc = reinterpret_cast<double*>(cv.p);                        // staging chunk [16][mps] ...
+    double* Zc = reinterpret_cast<double*>(cv.p);                        // staging chunk [16][mp + 1] ...
     double* Tl = Zc;                                                     // ... and the tiles of M over it
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int mps = mp + 1, nt = mp / 16, npairs = nt * (nt + 1) / 2;
-    const int row = lane & 15, kh = lane >> 4;                           // MFMA operand indices of this lane
-    const int pp = tid >> 4, t16 = tid & 15;
+    const int tid = threadIdx.x, wid = tid >> 6;
+    const int nt = mp / 16;
 
     for (int ui = blockIdx.x; ui < nusers; ui += gridDim.x) {
         const int u = users[ui];
@@ -158,222 +397,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2))) void
         if (dual)
             for (int p = tid; p < mp; p += BLOCK) { itm[p] = p < n ? uit[p] : 0; rv[p] = p < n ? uval[p] : 0.0; }
         __syncthreads();
-        // ---- 1. M's lower-triangular tiles on the matrix cores, 16 contraction indices at a time
-        const int clen = dual ? r : n;                                   // contraction length: columns (dual) or ratings (primal)
-        ridge_f64x4 acc[MAXP];
-#pragma unroll
-        for (int q = 0; q < MAXP; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[q][e] = 0.0;
-        int offA[MAXP], offB[MAXP];                                      // this wave's tile pairs (I >= J) as offsets inside a staged row
-#pragma unroll
-        for (int q = 0; q < MAXP; ++q) {
-            const int pr = wid + q * NW;
-            int I = 0, rem = pr < npairs ? pr : 0;                       // pr -> (I, J), J <= I, row-major over the lower triangle
-            while (rem > I) { rem -= I + 1; ++I; }
-            offA[q] = I * 16 + row; offB[q] = rem * 16 + row;
-        }
-        T xr[NREG];
-        double rreg = 0.0;
-        // issue(): the next chunk's values into registers; consume(): into the (idle) staging chunk as fp64.
-        //   primal: thread (pp, t16) holds ratings c0 + pp + RPP j (j < 16 / RPP) x columns t16 + 16 k  -> Zc[rating][column]
-        //   dual:   thread (pp, t16) holds column c0 + t16 of the user's rows pp + RPP j (j < NREG)      -> Zc[column][rating]
-        auto issue = [&](int c0) {
-#pragma unroll
-            for (int j = 0; j < NREG; ++j) xr[j] = (T)0;
-            if (dual) {
-                const int c = c0 + t16;
-#pragma unroll
-                for (int j = 0; j < NREG; ++j) {
-                    const int p = pp + RPP * j;
-                    if (p < n && c < r) xr[j] = F[(size_t)itm[p] * ld + c];
-                }
-            } else {
-                constexpr int NCK = MAXM / 16;
-#pragma unroll
-                for (int j = 0; j < 16 / RPP; ++j) {
-                    const int p = c0 + pp + RPP * j;
-                    if (p < n) {
-                        const T* frow = F + (size_t)uit[p] * ld;
-#pragma unroll
-                        for (int k = 0; k < NCK; ++k) { const int c = t16 + 16 * k; if (c < r) xr[j * NCK + k] = frow[c]; }
-                    }
-                }
-                if (tid < 16) rreg = c0 + tid < n ? uval[c0 + tid] : 0.0;
-            }
-        };
-        auto consume = [&]() {
-            if (dual) {
-#pragma unroll
-                for (int j = 0; j < NREG; ++j) { const int p = pp + RPP * j; if (p < mp) Zc[t16 * mps + p] = (double)xr[j]; }
-            } else {
-                constexpr int NCK = MAXM / 16;
-#pragma unroll
-                for (int j = 0; j < 16 / RPP; ++j)
-#pragma unroll
-                    for (int k = 0; k < NCK; ++k) { const int c = t16 + 16 * k; if (c < mp) Zc[(pp + RPP * j) * mps + c] = (double)xr[j * NCK + k]; }
-                if (tid < 16) rch[tid] = rreg;
-            }
-        };
-        double bacc = 0.0;                                               // primal: b[tid] = (A^T r)[tid]
-        issue(0);
-        consume();
-        __syncthreads();
-        for (int c0 = 0; c0 < clen; c0 += 16) {
-            const bool more = c0 + 16 < clen;
-            if (more) issue(c0 + 16);
-#pragma unroll 1
-            for (int s4 = 0; s4 < 4; ++s4) {                             // (not unrolled: one k-step's operands in registers at a time)
-                const int pb = (s4 * 4 + kh) * mps;
-#pragma unroll
-                for (int q = 0; q < MAXP; ++q)
-                    if (wid + q * NW < npairs) acc[q] = ridge_mma(Zc[pb + offA[q]], Zc[pb + offB[q]], acc[q]);      // (wave-uniform)
-            }
-            if (!dual && tid < mp) {
-#pragma unroll
-                for (int p = 0; p < 16; ++p) bacc += Zc[p * mps + tid] * rch[p];
-            }
-            __syncthreads();
-            if (more) { consume(); __syncthreads(); }
-        }
-        // M = Z^T Z + mu I into the tiles (over the staging chunk: the loop above ends in a barrier); beyond m a unit diagonal
-#pragma unroll
-        for (int q = 0; q < MAXP; ++q) {
-            const int pr = wid + q * NW;
-            if (pr < npairs) {
-                int I = 0, rem = pr;
-                while (rem > I) { rem -= I + 1; ++I; }
-                double* tile = Tl + (size_t)ridge_tix(I, rem) * RIDGE_TILE;
-                const int cl = lane & 15, col = rem * 16 + cl;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int rl = (lane >> 4) + 4 * e, rw = I * 16 + rl;
-                    double v = acc[q][e] + (rw == col ? mu : 0.0);
-                    if (rw >= m || col >= m) v = rw == col ? 1.0 : 0.0;
-                    tile[rl * RIDGE_TP + cl] = v;
-                }
-            }
-        }
+        const double bacc = ridge_gram<T, BLOCK>(F, uit, uval, n, r, ld, m, mp, dual, mu, itm, rch, Zc);
         for (int t = tid; t < mp; t += BLOCK) gv[t] = dual ? rv[t] : (t < m ? bacc : 0.0);      // (primal: mp <= BLOCK, one pass)
         if (tid == 0) red[7] = 0.0;                                      // "not positive definite" flag
         __syncthreads();
-        // ---- 2. blocked Cholesky of the tiles (lower triangle, in place; pcr_newton.h's scheme)
-        for (int k = 0; k < nt; ++k) {
-            double* D = Tl + (size_t)ridge_tix(k, k) * RIDGE_TILE;
-            if (wid == 0) {                                              // (a) the diagonal tile: lanes 0..15 hold one ROW each in registers
-                double a[16];
-                const int rr = lane & 15;
-#pragma unroll
-                for (int c = 0; c < 16; ++c) a[c] = D[rr * RIDGE_TP + c];
-                bool pd = true;
-#pragma unroll
-                for (int kk = 0; kk < 16; ++kk) {
-#pragma unroll
-                    for (int j = 0; j < kk; ++j) a[kk] -= a[j] * ridge_readlane(a[j], kk);
-                    const double dkk = ridge_readlane(a[kk], kk);
-                    pd = pd && ridge_pos(dkk);                           // (uniform)
-                    const double ri = 1.0 / sqrt(dkk);
-                    a[kk] = rr == kk ? dkk * ri : a[kk] * ri;
-                    if (lane == 0) dinv[k * 16 + kk] = ri;
-                }
-                if (!pd) { if (lane == 0) red[7] = 1.0; }
-                else if (lane < 16) {
-#pragma unroll
-                    for (int c = 0; c < 16; ++c) D[rr * RIDGE_TP + c] = a[c];
-                }
-            }
-            __syncthreads();
-            if (red[7] != 0.0) break;                                    // (uniform: read behind the barrier)
-            const int below = nt - k - 1;
-            if (tid < below * 16) {                                      // (b) the panel below: X L_kk^T = A, one row per thread (below <= 6, 3 on one wave)
-                double* A = Tl + (size_t)ridge_tix(k + 1 + (tid >> 4), k) * RIDGE_TILE + (tid & 15) * RIDGE_TP;
-                double x[16];
-#pragma unroll
-                for (int c = 0; c < 16; ++c) x[c] = A[c];
-#pragma unroll
-                for (int c = 0; c < 16; ++c) {
-                    double sacc = x[c];
-#pragma unroll
-                    for (int j = 0; j < c; ++j) sacc -= x[j] * D[c * RIDGE_TP + j];
-                    x[c] = sacc * dinv[k * 16 + c];
-                }
-#pragma unroll
-                for (int c = 0; c < 16; ++c) A[c] = x[c];
-            }
-            __syncthreads();
-            const int tp = below * (below + 1) / 2;                      // (c) trailing update A_ij -= L_ik L_jk^T on the matrix cores
-            for (int pr = wid; pr < tp; pr += NW) {
-                int i = 0, rem = pr;
-                while (rem > i) { rem -= i + 1; ++i; }
-                double* Cm = Tl + (size_t)ridge_tix(k + 1 + i, k + 1 + rem) * RIDGE_TILE;
-                const double* Li = Tl + (size_t)ridge_tix(k + 1 + i, k) * RIDGE_TILE;
-                const double* Lj = Tl + (size_t)ridge_tix(k + 1 + rem, k) * RIDGE_TILE;
-                ridge_f64x4 c4;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) c4[e] = Cm[((lane >> 4) + 4 * e) * RIDGE_TP + (lane & 15)];
-#pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) c4 = ridge_mma(-Li[row * RIDGE_TP + s4 * 4 + kh], Lj[row * RIDGE_TP + s4 * 4 + kh], c4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) Cm[((lane >> 4) + 4 * e) * RIDGE_TP + (lane & 15)] = c4[e];
-            }
-            __syncthreads();
-        }
-        const bool bad = red[7] != 0.0;
-        // ---- 3. the two triangular solves, M x = gv: one wave, lane l holds entries l and l + 64 (pcr_newton.h)
-        if (wid == 0 && !bad) {
-            const int j0 = lane, j1 = lane + 64, t0 = j0 >> 4, t1 = j1 >> 4;
-            double y0 = j0 < mp ? gv[j0] : 0.0, y1 = j1 < mp ? gv[j1] : 0.0;
-            const double dv0 = j0 < mp ? dinv[j0] : 1.0, dv1 = j1 < mp ? dinv[j1] : 1.0;
-            const int tc0 = t0 < nt ? t0 : nt - 1, tc1 = t1 < nt ? t1 : nt - 1;
-            for (int ib = 0; ib < nt; ++ib) {                            // L y = g, one tile column of L at a time
-                double l0[16], l1[16];
-                const double* q0 = Tl + (size_t)ridge_tix(tc0 < ib ? ib : tc0, ib) * RIDGE_TILE + (j0 & 15) * RIDGE_TP;
-                const double* q1 = Tl + (size_t)ridge_tix(tc1 < ib ? ib : tc1, ib) * RIDGE_TILE + (j1 & 15) * RIDGE_TP;
-#pragma unroll
-                for (int ii = 0; ii < 16; ++ii) { l0[ii] = q0[ii]; l1[ii] = q1[ii]; }
-                if (ib < 4) {
-#pragma unroll
-                    for (int ii = 0; ii < 16; ++ii) {
-                        const int i = ib * 16 + ii;
-                        const double yi = ridge_readlane(y0 * dv0, i);
-                        y0 = j0 == i ? yi : (j0 > i ? y0 - l0[ii] * yi : y0);
-                        y1 = j1 < mp ? y1 - l1[ii] * yi : y1;
-                    }
-                } else {
-#pragma unroll
-                    for (int ii = 0; ii < 16; ++ii) {
-                        const int i = ib * 16 + ii;
-                        const double yi = ridge_readlane(y1 * dv1, i - 64);
-                        y1 = j1 == i ? yi : ((j1 > i && j1 < mp) ? y1 - l1[ii] * yi : y1);
-                    }
-                }
-            }
-            for (int ib = nt - 1; ib >= 0; --ib) {                       // L^T x = y (in place), one tile ROW of L at a time
-                double l0[16], l1[16];
-                const double* q0 = Tl + (size_t)ridge_tix(ib, tc0 > ib ? ib : tc0) * RIDGE_TILE + (j0 & 15);
-                const double* q1 = Tl + (size_t)ridge_tix(ib, tc1 > ib ? ib : tc1) * RIDGE_TILE + (j1 & 15);
-#pragma unroll
-                for (int ii = 0; ii < 16; ++ii) { l0[ii] = q0[ii * RIDGE_TP]; l1[ii] = q1[ii * RIDGE_TP]; }
-                if (ib >= 4) {
-#pragma unroll
-                    for (int ii = 15; ii >= 0; --ii) {
-                        const int i = ib * 16 + ii;
-                        const double xi = ridge_readlane(y1 * dv1, i - 64);
-                        y1 = j1 == i ? xi : ((j1 < i && j1 < mp) ? y1 - l1[ii] * xi : y1);
-                        y0 -= l0[ii] * xi;                               // (j0 < i for every i >= 64)
-                    }
-                } else {
-#pragma unroll
-                    for (int ii = 15; ii >= 0; --ii) {
-                        const int i = ib * 16 + ii;
-                        const double xi = ridge_readlane(y0 * dv0, i);
-                        y0 = j0 == i ? xi : ((j0 < i && j0 < mp) ? y0 - l0[ii] * xi : y0);
-                    }
-                }
-            }
-            if (j0 < mp) gv[j0] = y0;
-            if (j1 < mp) gv[j1] = y1;
-        }
+        const bool bad = ridge_chol<BLOCK>(Tl, dinv, red, nt);
+        if (wid == 0 && !bad) ridge_trisolve(Tl, dinv, gv, mp, nt);
         __syncthreads();
         // ---- 4. the row: the solution itself (primal) or u = A^T a (dual; one thread per column, the ratings in order)
         if (!bad) {
@@ -397,6 +426,91 @@ static inline size_t ridge_cg_bytes(int ld) {
     return carve_bytes(8, 8) + carve_bytes(16, 8) + 4 * carve_bytes(ld, 8) + carve_bytes(RIDGE_CG_CHUNK, 8) + carve_bytes(RIDGE_CG_CHUNK, 4);
 }
 
+// The CG form's two pieces as functions of a 256-thread workgroup: k_ridge_cg below and k_nnls_cg (pcr_nnls.h) run the same ones.
+//
+// out[t] (+)= sum over the user's ratings of w_p F[item p][t], w = the ratings (vec NULL) or the scores F[item p] . vec; in chunks of
+// RIDGE_CG_CHUNK ratings (scores by 16-lane groups, then one thread per column).  sc, itc: LDS, one chunk each.
+template <typename T>
+__device__ __forceinline__ void ridge_cg_apply(const T* __restrict__ F, const int32_t* __restrict__ uit, const double* __restrict__ uval, int n, int r, int ld,
+                                               const double* vec, double* out, double* sc, int32_t* itc) {
+    constexpr int BLOCK = 256, CH = RIDGE_CG_CHUNK;
+    const int tid = threadIdx.x, g = tid & 15, gi = tid >> 4;
+    for (int c0 = 0; c0 < n; c0 += CH) {
+        const int cn = n - c0 < CH ? n - c0 : CH;
+        if (tid < cn) { itc[tid] = uit[c0 + tid]; if (!vec) sc[tid] = uval[c0 + tid]; }
+        __syncthreads();
+        if (vec) {
+            for (int base = 0; base < cn; base += 16) {
+                const int p = base + gi;
+                double d = 0.0;
+                if (p < cn) {
+                    const T* row = F + (size_t)itc[p] * ld;
+                    for (int t = g; t < r; t += 16) d += (double)row[t] * vec[t];
+                }
+                d = ridge_sum16(d);
+                if (p < cn && g == 0) sc[p] = d;
+            }
+            __syncthreads();
+        }
+        for (int t = tid; t < r; t += BLOCK) {
+            double s = out[t];
+#pragma unroll 4
+            for (int p = 0; p < cn; ++p) s += sc[p] * (double)F[(size_t)itc[p] * ld + t];
+            out[t] = s;
+        }
+        __syncthreads();
+    }
+}
+
+// CG on (A^T A + mu I) u = b from u = 0 until |res|^2 <= 1e-24 |b|^2, at most 2 min(n, side) + 10 iterations.  On entry uvec = 0
+// and res = b.  pas == NULL: the whole system, side = r.  Else the system restricted to the coordinates with pas[t] != 0 (side =
+// npas of them; the caller has zeroed res on the others): the search direction stays zero outside them and Hp is masked to
+// them, Hp = mask(A^T (A p) + mu p).  Returns the status (PCR_RIDGE_OK / SINGULAR / CG_CAP); *iters: the iterations.
+template <typename T>
+__device__ __forceinline__ int ridge_cg_solve(const T* __restrict__ F, const int32_t* __restrict__ uit, const double* __restrict__ uval, int n, int r, int ld,
+                                              double mu, const int32_t* pas, int npas, double* uvec, double* res, double* pv, double* Hp, double* sc,
+                                              int32_t* itc, double* red, int* iters_out) {
+    constexpr int BLOCK = 256;
+    const int tid = threadIdx.x;
+    double a = 0.0;
+    for (int t = tid; t < r; t += BLOCK) { pv[t] = res[t]; a += res[t] * res[t]; }
+    double rr = block_sum<BLOCK>(a, red);
+    const double stop = 1e-24 * rr;
+    const int side = pas ? npas : r;
+    const int cap = 2 * (n < side ? n : side) + 10;
+    int iters = 0, status = rr <= stop ? PCR_RIDGE_OK : PCR_RIDGE_CG_CAP;          // (b = 0: u = 0 is the answer)
+    __syncthreads();
+    for (int it = 0; it < cap && status == PCR_RIDGE_CG_CAP; ++it) {
+        for (int t = tid; t < r; t += BLOCK) Hp[t] = mu * pv[t];
+        __syncthreads();
+        ridge_cg_apply<T>(F, uit, uval, n, r, ld, pv, Hp, sc, itc);
+        if (pas)
+            for (int t = tid; t < r; t += BLOCK) if (!pas[t]) Hp[t] = 0.0;       // (the thread that wrote Hp[t])
+        a = 0.0;
+        for (int t = tid; t < r; t += BLOCK) a += pv[t] * Hp[t];
+        const double pHp = block_sum<BLOCK>(a, red);
+        ++iters;
+        if (!ridge_pos(pHp)) { status = PCR_RIDGE_SINGULAR; break; }                // (uniform)
+        const double alpha = rr / pHp;
+        a = 0.0;
+        for (int t = tid; t < r; t += BLOCK) {
+            uvec[t] += alpha * pv[t];
+            const double rn = res[t] - alpha * Hp[t];
+            res[t] = rn;
+            a += rn * rn;
+        }
+        const double rr2 = block_sum<BLOCK>(a, red);
+        if (rr2 <= stop) { status = PCR_RIDGE_OK; break; }
+        const double beta = rr2 / rr;
+        rr = rr2;
+        for (int t = tid; t < r; t += BLOCK) pv[t] = res[t] + beta * pv[t];
+        __syncthreads();
+    }
+    __syncthreads();
+    *iters_out = iters;
+    return status;
+}
+
 // Matrix-free CG on (A^T A + mu I) u = A^T r from u = 0; 256 threads per user, any n and k.
 template <typename T>
 __global__ __launch_bounds__(256) void k_ridge_cg(RidgeCsr X, const int32_t* __restrict__ users, int nusers, const T* __restrict__ F, int r, int ld,
@@ -412,7 +526,7 @@ __global__ __launch_bounds__(256) void k_ridge_cg(RidgeCsr X, const int32_t* __r
     double* Hp = cv.take<double>(ld);
     double* sc = cv.take<double>(CH);
     int32_t* itc = cv.take<int32_t>(CH);
-    const int tid = threadIdx.x, g = tid & 15, gi = tid >> 4;
+    const int tid = threadIdx.x;
 
     for (int ui = blockIdx.x; ui < nusers; ui += gridDim.x) {
         const int u = users[ui];
@@ -421,70 +535,13 @@ __global__ __launch_bounds__(256) void k_ridge_cg(RidgeCsr X, const int32_t* __r
         const double mu = weighted ? lambda * (double)n : lambda;
         const int32_t* uit = X.item + s0;
         const double* uval = X.val + s0;
-        // out[t] (+)= sum over the user's ratings of w_p F[item p][t], w = the ratings (vec NULL) or the scores F[item p] . vec
-        auto apply = [&](const double* vec, double* out) {
-            for (int c0 = 0; c0 < n; c0 += CH) {
-                const int cn = n - c0 < CH ? n - c0 : CH;
-                if (tid < cn) { itc[tid] = uit[c0 + tid]; if (!vec) sc[tid] = uval[c0 + tid]; }
-                __syncthreads();
-                if (vec) {
-                    for (int base = 0; base < cn; base += 16) {
-                        const int p = base + gi;
-                        double d = 0.0;
-                        if (p < cn) {
-                            const T* row = F + (size_t)itc[p] * ld;
-                            for (int t = g; t < r; t += 16) d += (double)row[t] * vec[t];
-                        }
-                        d = ridge_sum16(d);
-                        if (p < cn && g == 0) sc[p] = d;
-                    }
-                    __syncthreads();
-                }
-                for (int t = tid; t < r; t += BLOCK) {
-                    double s = out[t];
-#pragma unroll 4
-                    for (int p = 0; p < cn; ++p) s += sc[p] * (double)F[(size_t)itc[p] * ld + t];
-                    out[t] = s;
-                }
-                __syncthreads();
-            }
-        };
         for (int t = tid; t < r; t += BLOCK) { uvec[t] = 0.0; res[t] = 0.0; }
         __syncthreads();
-        apply(nullptr, res);                                             // b = A^T r: the first residual and direction
-        double a = 0.0;
-        for (int t = tid; t < r; t += BLOCK) { pv[t] = res[t]; a += res[t] * res[t]; }
-        double rr = block_sum<BLOCK>(a, red);
-        const double stop = 1e-24 * rr;
-        const int cap = 2 * (n < r ? n : r) + 10;
-        int iters = 0, status = rr <= stop ? PCR_RIDGE_OK : PCR_RIDGE_CG_CAP;          // (b = 0: u = 0 is the answer)
-        __syncthreads();
-        for (int it = 0; it < cap && status == PCR_RIDGE_CG_CAP; ++it) {
-            for (int t = tid; t < r; t += BLOCK) Hp[t] = mu * pv[t];
-            __syncthreads();
-            apply(pv, Hp);
-            a = 0.0;
-            for (int t = tid; t < r; t += BLOCK) a += pv[t] * Hp[t];
-            const double pHp = block_sum<BLOCK>(a, red);
-            ++iters;
-            if (!ridge_pos(pHp)) { status = PCR_RIDGE_SINGULAR; break; }                // (uniform)
-            const double alpha = rr / pHp;
-            a = 0.0;
-            for (int t = tid; t < r; t += BLOCK) {
-                uvec[t] += alpha * pv[t];
-                const double rn = res[t] - alpha * Hp[t];
-                res[t] = rn;
-                a += rn * rn;
-            }
-            const double rr2 = block_sum<BLOCK>(a, red);
-            if (rr2 <= stop) { status = PCR_RIDGE_OK; break; }
-            const double beta = rr2 / rr;
-            rr = rr2;
-            for (int t = tid; t < r; t += BLOCK) pv[t] = res[t] + beta * pv[t];
-            __syncthreads();
-        }
-        __syncthreads();
+        ridge_cg_apply<T>(F, uit, uval, n, r, ld, nullptr, res, sc, itc);               // b = A^T r: the first residual and direction
+        int iters = 0;
+        const int status = ridge_cg_solve<T>(F, uit, uval, n, r, ld, mu, nullptr, 0, uvec, res, pv, Hp, sc, itc, red, &iters);
         ridge_finish<T, BLOCK>(F, uit, uval, n, uvec, r, ld, mu, PCR_RIDGE_CG, iters, status, Uout + (size_t)u * ld,
                                per_user + (size_t)u * PCR_RIDGE_FIELDS, part, red);
     }
 }
+

@@ -10,6 +10,7 @@
 #include "pcr_dev.h"
 #include "pcr_foldin.h"
 #include "pcr_ridge.h"
+#include "pcr_nnls.h"
 #include "pcr_prims.h"
 #include "pcr_topk.h"
 
@@ -982,6 +983,69 @@ static int ridge_run(const ServeView& v, double lambda, int weighted, const PcrR
     return PCR_OK;
 }
 
+// Non-negative fold-in (pcr_fold_in_nnls, pcr_fold_in_nnls_model; pcr_nnls.h) of the plan's users against v's V, laid out as
+// ridge_run: one launch per range of the plan (form and workgroup size follow from the rank: one range), workgroups striding over
+// it, the longest users first.  "foldin/nnls" times the launches.
+template <typename T>
+static int nnls_run(const ServeView& v, double lambda, int weighted, const PcrRidgePlan& P, double* U_out, pcr_nnls_stats* stats, double* per_user) {
+    const int64_t n = P.X.d1;
+    hipStream_t st = v.st;
+    int dev = 0, cus = 0;
+    HIPCHK(hipGetDevice(&dev));
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    cus = std::max(cus, 1);
+    DBuf<int64_t> uptr;
+    DBuf<int32_t> item, order;
+    DBuf<double> val, dPer, dOutD;
+    DBuf<T> dOut;
+    RC(uptr.upload(P.X.index, st)); RC(item.upload_n(P.X.item.data(), P.X.item.size())); RC(val.upload_n(P.X.val.data(), P.X.val.size()));
+    RC(order.upload(P.order, st));
+    RC(dOut.alloc((size_t)n * v.ld)); RC(dPer.alloc((size_t)n * PCR_NNLS_FIELDS)); RC(dOutD.alloc((size_t)n * v.r));
+    const RidgeCsr X = {uptr.p, item.p, val.p};
+    const T* F = serve_V<T>(v);
+    {
+        ProfScope ps(v.prof, "foldin/nnls", st);
+        for (const PcrRidgePlan::Range& g : P.ranges) {
+            if (g.count <= 0) continue;
+            const int32_t* users = order.p + g.first;
+            if (g.form == PCR_NNLS_CG) {
+                const size_t lds = nnls_cg_bytes(v.ld);
+                if (lds > RIDGE_LDS_CU) { pcr_set_error("nnls fold-in: rank " + std::to_string(v.r) + " is too large for the CG form's LDS"); return PCR_ERR_UNSUPPORTED; }
+                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, RIDGE_LDS_CU / lds));
+                const int64_t grid = std::min<int64_t>(g.count, (int64_t)cus * per_cu);
+                HIPCHK(hipFuncSetAttribute((const void*)k_nnls_cg<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                hipLaunchKernelGGL((k_nnls_cg<T>), dim3((unsigned)grid), dim3(256), lds, st, X, users, (int)g.count, F, v.r, v.ld, dOut.p, dPer.p, lambda, weighted);
+            } else {
+                const int mp = g.tiles * 16;
+                if (mp < 16 || mp < v.r || mp > (g.block == 64 ? 64 : PCR_RIDGE_DIRECT_MAX)) { pcr_set_error("nnls fold-in: a launch class outside the kernel's tile range"); return PCR_ERR_STATE; }
+                const size_t lds = nnls_direct_bytes(mp, v.ld, g.block);
+                if (lds > RIDGE_LDS_CU) { pcr_set_error("nnls fold-in: rank " + std::to_string(v.r) + " is too large for the direct form's LDS"); return PCR_ERR_UNSUPPORTED; }
+                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(g.block == 64 ? 16 : 4, RIDGE_LDS_CU / lds));
+                const int64_t grid = std::min<int64_t>(g.count, (int64_t)cus * per_cu);
+                if (g.block == 64) {
+                    HIPCHK(hipFuncSetAttribute((const void*)k_nnls_direct<T, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                    hipLaunchKernelGGL((k_nnls_direct<T, 64>), dim3((unsigned)grid), dim3(64), lds, st, X, users, (int)g.count, F, v.r, v.ld, dOut.p, dPer.p,
+                                       lambda, weighted, mp);
+                } else {
+                    HIPCHK(hipFuncSetAttribute((const void*)k_nnls_direct<T, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                    hipLaunchKernelGGL((k_nnls_direct<T, 256>), dim3((unsigned)grid), dim3(256), lds, st, X, users, (int)g.count, F, v.r, v.ld, dOut.p, dPer.p,
+                                       lambda, weighted, mp);
+                }
+            }
+            HIPCHK(hipGetLastError());
+        }
+    }
+    hipLaunchKernelGGL((k_mat_out<T>), dim3((unsigned)std::min<int64_t>(1 << 16, cdiv(n * v.r, 256))), dim3(256), 0, st, (const T*)dOut.p, dOutD.p, n, v.r, v.ld);
+    HIPCHK(hipGetLastError());
+    std::vector<double> hp((size_t)n * PCR_NNLS_FIELDS);
+    HIPCHK(hipMemcpyAsync(U_out, dOutD.p, (size_t)n * v.r * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hp.data(), dPer.p, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (stats) pcr_nnls_stats_from(hp.data(), n, stats);
+    if (per_user) std::copy(hp.begin(), hp.end(), per_user);
+    return PCR_OK;
+}
+
 extern "C" {
 
 // users[n] (global ids, NULL: the whole shard) as rows of s's shard in loc (left empty for NULL); *n the count
@@ -1282,6 +1346,34 @@ int pcr_fold_in_ridge(pcr_solver* s, int weighted, int64_t n, const int64_t* ind
         if (stats) *stats = pcr_ridge_stats{};
         if (n == 0) return PCR_OK;
         return by_precision(v, [&](auto zero) -> int { return ridge_run<decltype(zero)>(v, lambda, weighted != 0, P, U_out, stats, per_user); });
+    });
+}
+
+int pcr_fold_in_nnls_model(const double* F, int64_t rows, int64_t k, double lambda, int weighted, int precision, int device, int64_t n,
+                           const int64_t* index, const int32_t* item, const double* val, double* U_out, pcr_nnls_stats* stats, double* per_user) {
+    return abi_guard("pcr_fold_in_nnls_model", [&]() -> int {
+    PcrRidgePlan P;
+    RC(pcr_fold_in_nnls_check("pcr_fold_in_nnls_model", true, F, rows, k, lambda, precision, n, index, item, val, U_out, &P));
+    RC(model_device(device));
+    if (stats) *stats = pcr_nnls_stats{};
+    if (n == 0) return PCR_OK;
+    ServeView v; ModelDev M;
+    RC(M.open(nullptr, n, F, rows, k, nullptr, nullptr, true, precision, &v));
+    return by_precision(v, [&](auto zero) -> int { return nnls_run<decltype(zero)>(v, lambda, weighted != 0, P, U_out, stats, per_user); });
+    });
+}
+
+int pcr_fold_in_nnls(pcr_solver* s, int weighted, int64_t n, const int64_t* index, const int32_t* item, const double* val, double* U_out,
+                     pcr_nnls_stats* stats, double* per_user) {
+    S_OR_ARG;
+    return abi_guard("pcr_fold_in_nnls", [&]() -> int {
+        const ServeView v = solver_view(s, 0);
+        const double lambda = s->ridge_lambda();
+        PcrRidgePlan P;
+        RC(pcr_fold_in_nnls_check("pcr_fold_in_nnls", false, nullptr, v.d2, v.r, lambda, v.dtype, n, index, item, val, U_out, &P));
+        if (stats) *stats = pcr_nnls_stats{};
+        if (n == 0) return PCR_OK;
+        return by_precision(v, [&](auto zero) -> int { return nnls_run<decltype(zero)>(v, lambda, weighted != 0, P, U_out, stats, per_user); });
     });
 }
 
