@@ -227,6 +227,8 @@ int pcr_partition_users(const int64_t *index, int64_t d1, int nparts, int64_t *b
  *                   forms, and a test hook); "auto" (default) = the form rule; read when the call's plan is made
  *   nnls_form       "cg" = pcr_fold_in_nnls / pcr_fold_in_nnls_model take the CG form at every rank (the A/B arm of the direct
  *                   form, and a test hook); "auto" (default) = the form rule; read when the call's plan is made
+ *   itemfold_table_bytes  test hook: the cap of pcr_fold_in_items' rater table (scores + levels) in bytes; a call whose unique
+ *                   raters exceed it runs in batches of items (results do not depend on it); default 2^30; read at every call
  *   count_rows      1 = the U-step kernels count the rows of V they gather (pcr_solver_counter; a diagnostic that
  *                   costs the short-user classes 10-20 %, so off by default)
  *   debug           1 = print launch decisions to stderr
@@ -894,6 +896,92 @@ int pcr_fold_in_nnls_model(const double *F, int64_t rows, int64_t k, double lamb
  * written.  Profile slot: foldin/nnls. */
 int pcr_fold_in_nnls(pcr_solver *s, int weighted, int64_t n, const int64_t *index, const int32_t *item, const double *val,
                      double *U_out, pcr_nnls_stats *stats, double *per_user);                       /* [device] */
+
+/* ------------------------------------------------------------------------- */
+/* item fold-in: rows of V for items a PrimalCR / PrimalCR++ model was not    */
+/* trained on (no reference counterpart: the reference can only retrain)      */
+/* ------------------------------------------------------------------------- */
+/* U and the trained rows of V are fixed.  New item j has raters R_j, user i gave it r_ij; its row v minimises
+ *     F_j(v) = lambda/2 |v|^2 + sum_{i in R_j} phi_ij(u_i . v)
+ *     phi_ij(s) = sum_{k in Omega_i, lev(r_ik) < lev(r_ij)} max(0, 1 - s + m_ik)^2
+ *               + sum_{k in Omega_i, lev(r_ik) > lev(r_ij)} max(0, 1 + s - m_ik)^2
+ * where Omega_i is user i's TRAINING row, m_ik = u_i . v_k rounded to the storage type as training stores it, and lev is the
+ * solver's level key (lround for PrimalCR++, the raw double for PrimalCR).  F_j is exactly the change of the training objective
+ * when item j and its ratings are appended to the data; it is strictly convex for lambda > 0.  Its gradient is lambda v + U_R^T c
+ * with c_i = phi_ij'(s_i), its generalised Hessian lambda I + U_R^T diag(h) U_R with h_i = 2 * (active pairs of rater i at s_i):
+ * row j of obtain_g_new / compute_Ha_new on the appended data.  A pair at the boundary (its hinge argument exactly 0) counts as
+ * active for PrimalCR++ and not for PrimalCR, as the training windows have it.
+ * NEW ITEMS ARE FOLDED IN INDEPENDENTLY OF EACH OTHER: a pair of two new items rated by the same user is not modelled.
+ * The user-side kernel cannot serve with the roles swapped: the loss compares items within a user, so a new row couples to the
+ * whole training row of every rater.  Two kernels (pcr_itemfold.h): k_rater_scores builds the rater table -- the scores m of the
+ * training row of every UNIQUE rater of the batch, once, with the dense level of every rating -- and k_itemfold runs an item's
+ * whole optimisation in one workgroup and one launch.  Starting from v = V0[j] rounded to the storage type, a step does:
+ *   1 State at v       s = U_R v in the storage type; one scan of each rater's table segment gives phi, c and h.
+ *   2 End test         g and gn2 = |g|^2.  The item ends CONVERGED, v unchanged, when it has no rater, when gn2 < 1e-4, or when
+ *                      the solver is PrimalCR and no rater's row holds a level different from the new rating's.
+ *   3 Newton step      CG from delta = 0 on the generalised Hessian with h frozen at v, at most cg_max_iter iterations, tolerance
+ *                      cg_tol |g|; the line search from stepsize, halving, at most 20 evaluations under strict <, each with
+ *                      fresh scores and a fresh scan.
+ *   4 Accepted try     v becomes that point ROUNDED TO THE STORAGE TYPE; one more step taken.  The try's state is carried: it is
+ *                      bit for bit what a fresh evaluation at that v gives, so steps = S equals S chained calls of steps = 1.
+ *   5 No try accepted  the item ends STALLED and v IS LEFT AS IT WAS BEFORE THIS STEP.
+ *   6 Step cap         after `steps` accepted steps the item ends STEP_CAP.
+ *   Inputs             U (d1 x k), V (d2 x k) host fp64 in model-file layout; tr_index[d1 + 1] / tr_item / tr_val: the training
+ *                      CSR of the d1 users (only the raters' rows are read; their sums run in the rows' own order; the same item
+ *                      twice in a row is two ratings).  index[n + 1] / user / val: the new items' ratings, item-major (a CSR over
+ *                      the users).  An item's raters are taken in ascending user order (a sorted copy is made).  The same user
+ *                      twice in an item's row counts as two ratings: each is compared with the training row, they are not
+ *                      compared with each other.  A rater with an empty training row adds nothing.  V0 [n][k] (NULL: zeros).
+ *   Outputs            V_out [n][k]: the storage-type values widened.  per_item (optional) [n][PCR_ITEMFOLD_FIELDS] = raters,
+ *                      steps taken, CG iterations, line-search evaluations, obj0 = F_j at the start point, obj = F_j at the
+ *                      returned row, gnorm2 = |g|^2 at the last point where the gradient was evaluated (the returned v for
+ *                      CONVERGED, else the start of the last step), status (the PCR_FOLDIN_* values).  An item without raters
+ *                      ends CONVERGED with its V0 row, gnorm2 = 0.  stats (optional): the counts and sums; obj in item order.
+ *   Forms              by the item's rater count alone: one wave up to PCR_ITEMFOLD_WAVE_MAX raters; 256 threads with the
+ *                      per-rater arrays in LDS up to PCR_ITEMFOLD_LDS_MAX; 512 threads with them in a per-workgroup slice of
+ *                      global scratch beyond (the grid bounded so that the slices stay within 1 GiB).  The rater table takes a
+ *                      rater on one wave up to PCR_ITEMFOLD_SCORES_WAVE_MAX training ratings, on 256 threads beyond.
+ *   Determinism        an item's row and table line depend on its ratings, its raters' training rows, U, V and the parameters
+ *                      alone -- not on the other items, its position, batches or the launch grid: every sum has a fixed order,
+ *                      no atomics touch results, nothing is handed between workgroups, there is no spin-wait and every loop has
+ *                      a static bound.  The host orders items by descending rater count.  Two identical calls are bitwise equal.
+ *   Memory             the rater table (sizeof(T) + 2 bytes per training rating of a unique rater, plus 4 for the item id) is
+ *                      capped at 1 GiB of scores and levels (pcr_tune("itemfold_table_bytes")): when a call's unique raters
+ *                      exceed it the items are processed in batches (a batch holds at least one item); a row's result does not
+ *                      depend on the batching.
+ *   Errors             PCR_ERR_ARG before any device is looked for, the message naming the entry: a user id outside [0, d1), a
+ *                      rating that is not finite, index[0] != 0 or a non-monotone index (either CSR), a training item of a rater
+ *                      outside [0, d2), steps < 1, a null U, V, V_out or training array.  PCR_ERR_UNSUPPORTED: solver type 0 (a
+ *                      CCDR1 item is a ridge solve: pcr_fold_in_ridge with F = U), and a rater with more than 65535 levels.
+ *                      Two limits of the device forms are PCR_ERR_UNSUPPORTED too, reported when the call reaches the form: a rank
+ *                      whose vectors and the per-rater arrays of the form's LARGEST item (PCR_ITEMFOLD_WAVE_MAX resp.
+ *                      PCR_ITEMFOLD_LDS_MAX raters) do not fit a workgroup's 160 KiB of LDS -- a function of the rank, the storage
+ *                      type and the item's form alone, never of the other items of the call (ranks up to several hundred fit every
+ *                      form) -- and an item whose per-rater arrays alone exceed the 1 GiB scratch cap (tens of millions of raters).
+ *                      Without a device: PCR_ERR_DEVICE. */
+#define PCR_ITEMFOLD_FIELDS 8   /* raters, steps, cg, ls, obj0, obj, gnorm2, status */
+#define PCR_ITEMFOLD_WAVE_MAX 64
+#define PCR_ITEMFOLD_LDS_MAX  2048
+#define PCR_ITEMFOLD_SCORES_WAVE_MAX 64
+typedef struct pcr_itemfold_stats {
+    int64_t items, converged, step_cap, stalled;
+    int64_t steps, cg, ls, raters, unique_raters;
+    double  obj;
+} pcr_itemfold_stats;
+/* Standalone: k, lambda, solver_type, stepsize, cg_max_iter, cg_tol, precision and device are read from p. */
+int pcr_fold_in_items_model(const pcr_params *p, const double *U, int64_t d1, const double *V, int64_t d2,
+                            const int64_t *tr_index, const int32_t *tr_item, const double *tr_val,
+                            int64_t n, const int64_t *index, const int32_t *user, const double *val,
+                            const double *V0, int steps, double *V_out,
+                            pcr_itemfold_stats *stats, double *per_item);                           /* [device] */
+/* On a live PCR or PCR++ solver: its device U and V, storage type, stream and parameters; nothing of the solver is written.  The
+ * solver keeps only dense ranks of its ratings, not comparable keys, so `train` supplies the rating values: it must be the data
+ * set the solver was created from (its dimensions and nnz are checked against the solver).  Every user must be on the rank: a
+ * shard or multi-rank solver returns PCR_ERR_STATE, as does a CCDR1 solver.  Profile slots: itemfold/scores (the rater table) and
+ * itemfold/newton. */
+int pcr_fold_in_items(pcr_solver *s, const pcr_dataset *train, int64_t n, const int64_t *index, const int32_t *user,
+                      const double *val, const double *V0, int steps, double *V_out,
+                      pcr_itemfold_stats *stats, double *per_item);                                 /* [device] */
 
 /* per-kernel device timing (HIP events on the solver's stream, one pair per launch).
  * slot names: "<class>/<workgroup size>[.<length bound>][g][c][l][r][#n]" for the per-user kernels (classes

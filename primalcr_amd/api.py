@@ -20,6 +20,10 @@ PCR_FOLDIN_CONVERGED, PCR_FOLDIN_STEP_CAP, PCR_FOLDIN_STALLED = 0, 1, 2         
 # fold_in's workgroup forms by user length (include/primalcr.h): one wave up to WAVE_MAX ratings, per-rating arrays in LDS up to
 # LDS_MAX, global scratch beyond
 PCR_FOLDIN_WAVE_MAX, PCR_FOLDIN_LDS_MAX = 64, 2048
+PCR_ITEMFOLD_FIELDS = ("raters", "steps", "cg", "ls", "obj0", "obj", "gnorm2", "status")   # fold_in_items' per_item columns (status: PCR_FOLDIN_*)
+# fold_in_items' workgroup forms by rater count (include/primalcr.h): one wave up to WAVE_MAX raters, per-rater arrays in LDS up to
+# LDS_MAX, global scratch beyond; its rater table takes a rater on one wave up to SCORES_WAVE_MAX training ratings
+PCR_ITEMFOLD_WAVE_MAX, PCR_ITEMFOLD_LDS_MAX, PCR_ITEMFOLD_SCORES_WAVE_MAX = 64, 2048, 64
 PCR_RIDGE_FIELDS = ("n", "form", "iters", "loss", "obj", "status")               # fold_in_ridge's per_user columns
 PCR_RIDGE_DUAL, PCR_RIDGE_PRIMAL, PCR_RIDGE_CG = 0, 1, 2                         # ... its forms
 PCR_RIDGE_OK, PCR_RIDGE_SINGULAR, PCR_RIDGE_CG_CAP = 0, 1, 2                     # ... and its status values
@@ -114,6 +118,12 @@ class FoldinStats(C.Structure):
     """pcr_foldin_stats."""
     _fields_ = [("users", C.c_int64), ("converged", C.c_int64), ("step_cap", C.c_int64), ("stalled", C.c_int64), ("steps", C.c_int64),
                 ("cg", C.c_int64), ("ls", C.c_int64), ("obj", C.c_double)]
+
+
+class ItemfoldStats(C.Structure):
+    """pcr_itemfold_stats."""
+    _fields_ = [("items", C.c_int64), ("converged", C.c_int64), ("step_cap", C.c_int64), ("stalled", C.c_int64), ("steps", C.c_int64),
+                ("cg", C.c_int64), ("ls", C.c_int64), ("raters", C.c_int64), ("unique_raters", C.c_int64), ("obj", C.c_double)]
 
 
 class RidgeStats(C.Structure):
@@ -222,6 +232,9 @@ def lib():
     if _LIB_OVERRIDE is None or hasattr(L, "pcr_fold_in_nnls"):
         L.pcr_fold_in_nnls_model.argtypes = [vp, i64, i64, cd, ci, ci, ci, i64, vp, vp, vp, vp, vp, vp]
         L.pcr_fold_in_nnls.argtypes = [vp, ci, i64, vp, vp, vp, vp, vp, vp]
+    if _LIB_OVERRIDE is None or hasattr(L, "pcr_fold_in_items"):
+        L.pcr_fold_in_items_model.argtypes = [C.POINTER(Parameter), vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, ci, vp, vp, vp]
+        L.pcr_fold_in_items.argtypes = [vp, vp, i64, vp, vp, vp, vp, ci, vp, vp, vp]
     L.pcr_exposure_stats.argtypes = [vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(cd), C.POINTER(cd)]
     L.pcr_profile_enable.argtypes = [vp, ci]
     L.pcr_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(cd), C.POINTER(i64)]
@@ -743,6 +756,60 @@ def recommend_new_users(V, ratings, lam, topk, solver_type=PCR_SOLVER_PCRPP, U0=
     return items, scores, U_new, stats
 
 
+def itemfold_boundaries(k=None, dtype=PCR_F64):
+    """The rater counts R at which fold_in_items() changes its code path between R and R + 1 raters: the bounds of its workgroup
+    forms (the same for every rank and storage type)."""
+    return [PCR_ITEMFOLD_WAVE_MAX, PCR_ITEMFOLD_LDS_MAX]
+
+
+def rater_scores_boundaries():
+    """The training-row lengths L at which fold_in_items()' rater table changes its workgroup form between L and L + 1 ratings."""
+    return [PCR_ITEMFOLD_SCORES_WAVE_MAX]
+
+
+def _itemfold_call(n, k, V0, per_item, fn):
+    """Shared by fold_in_items() and Solver.fold_in_items(): the V0 / output buffers around fn(V0 pointer, V_out pointer, stats
+    pointer, per_item pointer); returns (rows, stats dict[, per_item])."""
+    if V0 is not None:
+        V0 = np.ascontiguousarray(V0, np.float64)
+        if V0.shape != (n, k):
+            raise ValueError(f"V0 must be [n, k] = [{n}, {k}]")
+    out = np.empty((n, k), np.float64)
+    st = ItemfoldStats()
+    pi = np.empty((n, len(PCR_ITEMFOLD_FIELDS)), np.float64) if per_item else None
+    _chk(fn(None if V0 is None else V0.ctypes.data, out.ctypes.data, C.addressof(st), None if pi is None else pi.ctypes.data))
+    stats = {f: getattr(st, f) for f, _ in ItemfoldStats._fields_}
+    return (out, stats, pi) if per_item else (out, stats)
+
+
+def fold_in_items(U, V, train, new_items, lam, solver_type=PCR_SOLVER_PCRPP, V0=None, steps=10, stepsize=1.0, cg_max_iter=None, cg_tol=None,
+                  dtype=PCR_F64, device=0, per_item=False):
+    """Rows of V for items a PrimalCR / PrimalCR++ model was not trained on, on the GPU (pcr_fold_in_items_model): with U and the
+    trained V fixed, each new item's lambda/2 |v|^2 + the pairwise squared hinge loss of its ratings against its raters' training
+    rows is minimised by up to `steps` Newton steps (CG + line search) from V0 (None: zeros); statuses as fold_in()'s.  New items
+    are independent of each other: a pair of two new items rated by the same user is not modelled.
+    train: the training ratings of U's users, a Dataset (its training CSR) or an (index, item, val) tuple over V's items.
+    new_items: (index[n + 1], user, val), item-major: the raters of each new item and their ratings.
+    Returns (rows float64 [n, k], stats dict[, per_item float64 [n, 8] of PCR_ITEMFOLD_FIELDS]); np.vstack([V, rows]) serves the
+    new items through recommend() and the evaluations as items d2 .. d2 + n - 1."""
+    U = np.ascontiguousarray(U, np.float64); V = np.ascontiguousarray(V, np.float64)
+    if U.ndim != 2 or V.ndim != 2 or U.shape[1] != V.shape[1]:
+        raise ValueError("U must be [d1, k] and V [d2, k]")
+    tindex, titem, tval = _foldin_ratings(train)
+    if tindex.shape[0] - 1 != U.shape[0]:
+        raise ValueError(f"train must hold one row per user of U ({U.shape[0]})")
+    index, user, val = _foldin_ratings(new_items)
+    n, k = index.shape[0] - 1, V.shape[1]
+    p = Parameter(solver_type=int(solver_type), k=k, stepsize=float(stepsize), precision=int(dtype), device=int(device), **{"lambda": float(lam)})
+    if cg_max_iter is not None:
+        p.cg_max_iter = int(cg_max_iter)
+    if cg_tol is not None:
+        p.cg_tol = float(cg_tol)
+    return _itemfold_call(n, k, V0, per_item, lambda v0, vo, sp, pp: lib().pcr_fold_in_items_model(
+        C.byref(p), U.ctypes.data, U.shape[0], V.ctypes.data, V.shape[0], tindex.ctypes.data, titem.ctypes.data, tval.ctypes.data,
+        n, index.ctypes.data, user.ctypes.data, val.ctypes.data, v0, int(steps), vo, sp, pp))
+
+
 def ridge_form(n, k):
     """The form fold_in_ridge() solves a user of n ratings in at rank k (include/primalcr.h): PCR_RIDGE_DUAL for n <= k and
     n <= PCR_RIDGE_DIRECT_MAX, PCR_RIDGE_PRIMAL for n > k when k padded to 16 is <= PCR_RIDGE_DIRECT_MAX, PCR_RIDGE_CG otherwise."""
@@ -1203,6 +1270,19 @@ class Solver:
         n = index.shape[0] - 1
         return _foldin_call(n, self.k, U0, per_user, lambda u0, uo, sp, pp: lib().pcr_fold_in(
             self._h, n, index.ctypes.data, item.ctypes.data, val.ctypes.data, u0, int(steps), uo, sp, pp))
+
+    def fold_in_items(self, new_items, train=None, V0=None, steps=10, per_item=False):
+        """Rows of V for items this solver was not trained on, against its device U and V (pcr_fold_in_items), in its storage type
+        and with its parameters; new_items and the result as fold_in_items().  train (None: the Dataset the solver was created
+        from) supplies the rating values and must be that data set.  Needs every user on the rank (a shard solver: PcrError);
+        nothing of the solver is written."""
+        ds = self.ds if train is None else train
+        if not isinstance(ds, Dataset):
+            raise ValueError("train must be a Dataset (the one the solver was created from)")
+        index, user, val = _foldin_ratings(new_items)
+        n = index.shape[0] - 1
+        return _itemfold_call(n, self.k, V0, per_item, lambda v0, vo, sp, pp: lib().pcr_fold_in_items(
+            self._h, ds._h, n, index.ctypes.data, user.ctypes.data, val.ctypes.data, v0, int(steps), vo, sp, pp))
 
     def fold_in_ridge(self, ratings, weighted=True, per_user=False):
         """Squared-loss factors for users this solver was not trained on, against its device V (pcr_fold_in_ridge), in its storage

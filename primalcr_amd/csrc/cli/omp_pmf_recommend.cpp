@@ -51,6 +51,15 @@
 //                    row is the exact minimiser of the same objective over the non-negative rows.  stdout gets one line
 //                    "foldin_nnls users n direct n cg n singular n cap n pivots n zeros n loss x obj x" (%g); combinations and
 //                    refusals as --fold-in-ridge, which it does not go with
+//   omp-pmf-recommend --fold-in-items ratings_file -x data_dir -l lambda [-s 1|2] [--steps S] [--f32] model_file output_model
+//     --fold-in-items f  rows of V for items the model was not trained on (pcr_fold_in_items_model): the file holds lines "user item
+//                    rating", 1-based; the items are 1 .. n and number the NEW items (n, the largest id, may not exceed the number
+//                    of lines: an id without a line is an item without raters, a stray huge id is refused), the users are the model's.  -x is required and
+//                    supplies the training ratings of the model's users (d1 / d2 must match the model).  output_model is the model
+//                    file with V extended by the n rows: new item t becomes item d2 + t.  stdout gets one line "foldin_items items n
+//                    converged n step_cap n stalled n steps n cg n ls n raters n unique_raters n obj x" (obj in %g).  Refused
+//                    together with every other mode (--eval, --diversity, --mmr, --tradeoff, --ranks, --fold-in, --fold-in-ridge,
+//                    --fold-in-nnls, --allow, --candidates) and with -K, -u, -c, --threshold, --pool, --scores and --plain-reg
 //   omp-pmf-recommend [--allow items_file] [--candidates file] [-K topk] [-x data_dir] [-u users_file] [--f32] [--scores] model_file output_file
 //     --allow file   recommend among these items only (pcr_recommend_filtered_model): one 1-based item id per line, like -u
 //     --candidates f a candidate list per requested user: line i holds the space-separated 1-based item ids of the i-th requested
@@ -124,6 +133,11 @@ static const char* USAGE =
     "    --fold-in-nnls dir  --fold-in-ridge under u >= 0, for CCDR1 models trained with -N 1: the exact non-negative minimiser per new\n"
     "                   user; stdout gets a \"foldin_nnls users n direct n cg n singular n cap n pivots n zeros n loss x obj x\" line;\n"
     "                   -l, --plain-reg and the refusals as --fold-in-ridge, which it does not go with\n"
+    "       omp-pmf-recommend --fold-in-items ratings_file -x data_dir -l lambda [-s 1|2] [--steps S] [--f32] model_file output_model\n"
+    "    --fold-in-items f  rows of V for new items: lines \"user item rating\" (1-based; items 1 .. n number the new items) are folded\n"
+    "                   into the model on the device against the training ratings of -x (required); output_model is the model with V\n"
+    "                   extended by the n rows (new item t becomes item d2 + t); stdout gets a \"foldin_items items n converged n\n"
+    "                   step_cap n stalled n steps n cg n ls n raters n unique_raters n obj x\" line; not with any other mode\n"
     "       omp-pmf-recommend [--allow items_file] [--candidates file] [-K topk] [-x data_dir] [-u users_file] [--f32] [--scores] model_file output_file\n"
     "    --allow file   recommend among these items only: one 1-based item id per line\n"
     "    --candidates f line i: the space-separated 1-based candidate items of the i-th requested user (an empty line: none);\n"
@@ -446,6 +460,71 @@ static bool run_fold_in(const char* dir, const std::vector<double>& V, int64_t d
     return true;
 }
 
+// --fold-in-items: the new items' ratings ("user item rating", 1-based) as an item-major CSR over the model's users (file order
+// inside an item), the training CSR of xdir, the new rows (pcr_fold_in_items_model) and the extended model file; the summary line
+// goes to stdout
+static int run_fold_in_items(const char* path, const char* xdir, const char* model, const char* out_model, double lambda, int solver, int steps,
+                             bool f32) {
+    int64_t d1, d2, k;
+    if (pcr_model_load(model, &d1, &d2, &k, nullptr, nullptr) != PCR_OK) { fprintf(stderr, "can't open model file %s\n", model); return 1; }
+    std::vector<double> U((size_t)d1 * k), V((size_t)d2 * k);
+    if (pcr_model_load(model, &d1, &d2, &k, U.data(), V.data()) != PCR_OK) { fprintf(stderr, "%s\n", pcr_last_error()); return 1; }
+    FILE* fp = fopen(path, "r");
+    if (!fp) { fprintf(stderr, "can't open ratings file %s\n", path); return 1; }
+    std::vector<int32_t> fu, fi;
+    std::vector<double> fv;
+    int64_t n = 0;
+    char line[512];
+    for (int64_t ln = 1; fgets(line, sizeof line, fp); ++ln) {
+        char* q = line;
+        while (*q == ' ' || *q == '\t') ++q;
+        if (*q == '\n' || *q == '\r' || !*q) continue;
+        char *e1 = nullptr, *e2 = nullptr, *e3 = nullptr;
+        const long long u = strtoll(q, &e1, 10);
+        const long long it = e1 != q ? strtoll(e1, &e2, 10) : 0;
+        const double r = (e2 && e2 != e1) ? strtod(e2, &e3) : 0.0;
+        if (e1 == q || !e2 || e2 == e1 || !e3 || e3 == e2) { fprintf(stderr, "%s:%lld: expected \"user item rating\"\n", path, (long long)ln); fclose(fp); return 1; }
+        if (u < 1 || u > d1) { fprintf(stderr, "%s:%lld: user %lld is outside 1 .. %lld\n", path, (long long)ln, u, (long long)d1); fclose(fp); return 1; }
+        if (it < 1 || it > 2147483000LL) { fprintf(stderr, "%s:%lld: item %lld must be at least 1\n", path, (long long)ln, it); fclose(fp); return 1; }
+        if (!std::isfinite(r)) { fprintf(stderr, "%s:%lld: the rating is not finite\n", path, (long long)ln); fclose(fp); return 1; }
+        fu.push_back((int32_t)(u - 1)); fi.push_back((int32_t)(it - 1)); fv.push_back(r);
+        n = std::max<int64_t>(n, it);
+    }
+    fclose(fp);
+    // the ids number the new items 1 .. n: an id beyond the number of rating lines is a stray line, not n - 1 unrated items
+    if (n > (int64_t)fi.size()) {
+        fprintf(stderr, "%s: item id %lld exceeds the %lld ratings of the file (the new items are numbered 1 .. n)\n", path, (long long)n, (long long)fi.size());
+        return 1;
+    }
+    std::vector<int64_t> index((size_t)n + 1, 0);
+    for (int32_t it : fi) index[(size_t)it + 1] += 1;
+    for (int64_t j = 0; j < n; ++j) index[(size_t)j + 1] += index[(size_t)j];
+    std::vector<int64_t> at(index.begin(), index.end() - 1);
+    std::vector<int32_t> user(fu.size());
+    std::vector<double> val(fv.size());
+    for (size_t z = 0; z < fu.size(); ++z) { const int64_t o = at[(size_t)fi[z]]++; user[(size_t)o] = fu[z]; val[(size_t)o] = fv[z]; }
+    std::vector<int64_t> tindex;
+    std::vector<int32_t> titem;
+    std::vector<double> tval;
+    if (!load_csr(xdir, 0, d1, d2, tindex, titem, &tval)) return 1;
+    pcr_params p;
+    pcr_params_default(&p);
+    p.solver_type = solver; p.k = (int)k; p.lambda = lambda; p.precision = f32 ? PCR_F32 : PCR_F64;
+    std::vector<double> Vx((size_t)(d2 + n) * k);
+    std::copy(V.begin(), V.end(), Vx.begin());
+    pcr_itemfold_stats st;
+    if (pcr_fold_in_items_model(&p, U.data(), d1, V.data(), d2, tindex.data(), titem.data(), tval.data(), n, index.data(), user.data(), val.data(), nullptr,
+                                steps, Vx.data() + (size_t)d2 * k, &st, nullptr) != PCR_OK) {
+        fprintf(stderr, "fold-in-items: %s\n", pcr_last_error());
+        return 1;
+    }
+    if (pcr_model_save(out_model, U.data(), d1, Vx.data(), d2 + n, k) != PCR_OK) { fprintf(stderr, "%s\n", pcr_last_error()); return 1; }
+    printf("foldin_items items %lld converged %lld step_cap %lld stalled %lld steps %lld cg %lld ls %lld raters %lld unique_raters %lld obj %g\n",
+           (long long)st.items, (long long)st.converged, (long long)st.step_cap, (long long)st.stalled, (long long)st.steps, (long long)st.cg,
+           (long long)st.ls, (long long)st.raters, (long long)st.unique_raters, st.obj);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     int K = 10;
     bool f32 = false, with_scores = false, with_ranks = false, diversity = false;
@@ -459,6 +538,8 @@ int main(int argc, char** argv) {
     const char* fdir = nullptr;                                    // --fold-in
     const char* rdir = nullptr;                                    // --fold-in-ridge
     const char* ndir = nullptr;                                    // --fold-in-nnls
+    const char* ifile = nullptr;                                   // --fold-in-items
+    bool have_K = false;
     bool plain_reg = false;
     double lambda = 0.0;
     bool have_lambda = false, have_s = false, have_steps = false;
@@ -473,6 +554,11 @@ int main(int argc, char** argv) {
         if (!strcmp(a, "--fold-in-nnls")) {
             if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
             ndir = argv[++i];
+            continue;
+        }
+        if (!strcmp(a, "--fold-in-items")) {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
+            ifile = argv[++i];
             continue;
         }
         if (!strcmp(a, "--plain-reg")) { plain_reg = true; continue; }
@@ -540,7 +626,7 @@ int main(int argc, char** argv) {
                 char* end = nullptr;
                 const long x = strtol(v, &end, 10);
                 if (!*v || *end || x < 1 || x > PCR_RECOMMEND_MAX_K) { fprintf(stderr, "-K %s: must be an integer in 1 .. %d\n", v, PCR_RECOMMEND_MAX_K); return 1; }
-                K = (int)x;
+                K = (int)x; have_K = true;
             } else if (a[1] == 'x') xdir = v;
             else ufile = v;
         } else if (!strcmp(a, "--allow") || !strcmp(a, "--candidates")) {
@@ -554,6 +640,24 @@ int main(int argc, char** argv) {
         else pos.push_back(a);
     }
     const bool tradeoff = !thetas.empty();
+    if (ifile) {                                                   // (a mode of its own: it writes a model, no lists)
+        if (fdir || rdir || ndir) { fprintf(stderr, "--fold-in-items does not go with --fold-in, --fold-in-ridge or --fold-in-nnls\n"); return 1; }
+        if (edir || diversity || mmr || tradeoff || with_ranks || afile || cfile) {
+            fprintf(stderr, "--fold-in-items does not go with --eval, --diversity, --mmr, --tradeoff, --ranks, --allow or --candidates\n");
+            return 1;
+        }
+        if (have_K || ufile || with_scores || plain_reg || pool || !cuts.empty() || threshold != -INFINITY) {
+            fprintf(stderr, "--fold-in-items does not go with -K, -u, -c, --threshold, --pool, --scores or --plain-reg\n");
+            return 1;
+        }
+        if (!xdir) { fprintf(stderr, "--fold-in-items needs -x data_dir (the training ratings)\n"); return 1; }
+        if (!have_lambda) { fprintf(stderr, "--fold-in-items needs -l lambda\n"); return 1; }
+        if (pos.size() != 2) return usage();
+        const int rc = run_fold_in_items(ifile, xdir, pos[0], pos[1], lambda, solver, steps, f32);
+        if (rc) return rc;
+        fflush(stdout); fflush(stderr);
+        _exit(0);
+    }
     if (ndir) {                                                    // (--fold-in-ridge's rules under its own name)
         if (rdir) { fprintf(stderr, "--fold-in-nnls does not go with --fold-in-ridge\n"); return 1; }
         if (fdir) { fprintf(stderr, "--fold-in-nnls does not go with --fold-in\n"); return 1; }

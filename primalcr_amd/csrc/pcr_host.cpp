@@ -362,7 +362,7 @@ extern "C" int pcr_dataset_from_csr(int64_t d1, int64_t d2, const int64_t* index
 static std::map<std::string, std::string>& tune_table() { static thread_local std::map<std::string, std::string> t; return t; }
 static const char* const TUNE_KEYS[] = {"ustep_mode", "cluster_k", "cluster_users", "ubins", "ustep_gram", "spmm_tiles", "spmm_chunk", "sddmm_csc",
                                         "lanes", "pipeline", "window_cache", "prepare_merged", "resort_window", "allreduce_chunks", "p2p_ll",
-                                        "p2p_timeout_ms", "p2p_queue_budget", "count_rows", "debug", "win16", "ustep_win_lds", "plan_key64", "ustep_newton", "vblock_users", "recommend_select", "ranks_batch_users", "rerank_lds", "ridge_form", "nnls_form", "fault_cluster_member", "fault_p2p_skip", "fault_p2p_coarse", nullptr};
+                                        "p2p_timeout_ms", "p2p_queue_budget", "count_rows", "debug", "win16", "ustep_win_lds", "plan_key64", "ustep_newton", "vblock_users", "recommend_select", "ranks_batch_users", "rerank_lds", "ridge_form", "nnls_form", "itemfold_table_bytes", "fault_cluster_member", "fault_p2p_skip", "fault_p2p_coarse", nullptr};
 extern "C" int pcr_tune(const char* key, const char* value) {
     if (!key) { pcr_set_error("pcr_tune: null key"); return PCR_ERR_ARG; }
     bool known = false;
@@ -1603,6 +1603,143 @@ void pcr_foldin_stats_from(const double* per_user, int64_t n, pcr_foldin_stats* 
         s.steps += (int64_t)o[0]; s.cg += (int64_t)o[1]; s.ls += (int64_t)o[2];
         s.obj += o[3];
         const int status = (int)o[5];
+        if (status == PCR_FOLDIN_CONVERGED) s.converged += 1; else if (status == PCR_FOLDIN_STEP_CAP) s.step_cap += 1; else s.stalled += 1;
+    }
+    *stats = s;
+}
+
+// ------------------------------------------------------------------------------------------
+// item fold-in (include/primalcr.h, "item fold-in"): argument checks and the host-side plan
+// ------------------------------------------------------------------------------------------
+int pcr_fold_in_items_check(const char* who, bool need_factors, const pcr_params* p, const double* U, int64_t d1, const double* V, int64_t d2,
+                            const int64_t* tr_index, const int32_t* tr_item, const double* tr_val, int64_t n, const int64_t* index,
+                            const int32_t* user, const double* val, int steps, const double* V_out, PcrItemfoldPlan* plan) {
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
+    if (!p) return bad("null parameters");
+    const int solver_type = p->solver_type;
+    if (solver_type == PCR_SOLVER_CCDR1) {
+        pcr_set_error(std::string(who) + ": solver type 0 (CCDR1) is not supported: its item fold-in is the ridge solve with F = U");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    if (solver_type != PCR_SOLVER_PCR && solver_type != PCR_SOLVER_PCRPP) return bad("wrong solver type (" + std::to_string(solver_type) + "): 1 = PrimalCR, 2 = PrimalCR++");
+    if (need_factors) {
+        if (!U) return bad("null U");
+        if (!V) return bad("null V");
+        if (p->k < 1) return bad("rank k must be >= 1");
+        if (p->precision != PCR_F32 && p->precision != PCR_F64) return bad("precision must be PCR_F32 or PCR_F64");
+        if (!std::isfinite(p->lambda) || !std::isfinite(p->stepsize) || !std::isfinite(p->cg_tol)) return bad("lambda, stepsize and cg_tol must be finite");
+        if (p->cg_max_iter < 0) return bad("cg_max_iter must not be negative");
+    }
+    if (n < 0 || d1 < 1 || d2 < 1 || !index) return bad("bad argument");
+    if (d1 >= ((int64_t)1 << 31) - 64) return bad("more than 2^31 users");
+    if (d2 >= ((int64_t)1 << 31) - 64) return bad("more than 2^31 items");
+    if (n >= ((int64_t)1 << 31) - 64) return bad("more than 2^31 items in one call");
+    if (steps < 1) return bad("steps = " + std::to_string(steps) + " must be at least 1");
+    if (n > 0 && !V_out) return bad("null output");
+    if (!tr_index) return bad("null training index");
+    if (index[0] != 0) return bad("index[0] must be 0");
+    for (int64_t j = 0; j < n; ++j) {
+        if (index[j + 1] < index[j]) return bad("index not monotone at item " + std::to_string(j));
+        if (index[j + 1] - index[j] > ((int64_t)1 << 30)) return bad("item " + std::to_string(j) + " has more than 2^30 ratings");
+    }
+    const int64_t np = index[n];
+    if (np > 0 && (!user || !val)) return bad("null user / val");
+    if (tr_index[0] != 0) return bad("training index[0] must be 0");
+    for (int64_t u = 0; u < d1; ++u) {
+        if (tr_index[u + 1] < tr_index[u]) return bad("training index not monotone at user " + std::to_string(u));
+        if (tr_index[u + 1] - tr_index[u] > ((int64_t)1 << 30)) return bad("user " + std::to_string(u) + " has more than 2^30 training ratings");
+    }
+    if (tr_index[d1] > 0 && (!tr_item || !tr_val)) return bad("null training item / val");
+    const int all = pcr_csr_rows_scan(d1, n, index, user, val);
+    if (all & 1) return bad("a user id is outside [0, d1)");
+    if (all & 2) return bad("a rating is not finite");
+
+    PcrItemfoldPlan local;
+    PcrItemfoldPlan& P = plan ? *plan : local;
+    P.n = n;
+    // the unique raters, ascending, and a copy of their training rows
+    std::vector<int32_t> rpos((size_t)d1, -1);
+    for (int64_t z = 0; z < np; ++z) rpos[(size_t)user[z]] = 0;
+    P.raters.clear();
+    for (int64_t u = 0; u < d1; ++u)
+        if (rpos[(size_t)u] == 0) { rpos[(size_t)u] = (int32_t)P.raters.size(); P.raters.push_back((int32_t)u); }
+    const int64_t nr = (int64_t)P.raters.size();
+    P.R.d1 = nr; P.R.d2 = d2;
+    P.R.index.assign((size_t)nr + 1, 0);
+    for (int64_t i = 0; i < nr; ++i) P.R.index[(size_t)i + 1] = P.R.index[(size_t)i] + (tr_index[P.raters[(size_t)i] + 1] - tr_index[P.raters[(size_t)i]]);
+    P.R.item.resize((size_t)P.R.index[(size_t)nr]);
+    P.R.val.resize((size_t)P.R.index[(size_t)nr]);
+    const int nth = pcr_host_threads();
+    std::vector<int> st((size_t)nth, 0);
+    pcr_parallel_ranges(nr, nth, [&](int t, int64_t lo, int64_t hi) {
+        for (int64_t i = lo; i < hi; ++i) {
+            const int64_t a = tr_index[P.raters[(size_t)i]], len = tr_index[P.raters[(size_t)i] + 1] - a, o = P.R.index[(size_t)i];
+            for (int64_t q = 0; q < len; ++q) {
+                if (tr_item[a + q] < 0 || tr_item[a + q] >= d2) st[(size_t)t] |= 1;
+                if (!std::isfinite(tr_val[a + q])) st[(size_t)t] |= 2;
+                P.R.item[(size_t)(o + q)] = tr_item[a + q];
+                P.R.val[(size_t)(o + q)] = tr_val[a + q];
+            }
+        }
+    });
+    int trall = 0;
+    for (int x : st) trall |= x;
+    if (trall & 1) return bad("a training item id of a rater is outside [0, d2)");
+    if (trall & 2) return bad("a training rating of a rater is not finite");
+    std::string err;
+    const int rc = pcr_build_levels(P.R, 0, nr, solver_type, P.lv, err);
+    if (rc != PCR_OK) { pcr_set_error(std::string(who) + ": training row of a rater (numbered among the call's raters in ascending user order): " + err); return rc; }
+    // slots: items by descending rater count (equal counts by ascending id); the three workgroup forms are ranges
+    P.order.resize((size_t)n);
+    for (int64_t j = 0; j < n; ++j) P.order[(size_t)j] = (int32_t)j;
+    std::stable_sort(P.order.begin(), P.order.end(), [&](int32_t x, int32_t y) { return index[x + 1] - index[x] > index[y + 1] - index[y]; });
+    P.n_big = P.n_lds = 0;
+    P.sptr.assign((size_t)n + 1, 0);
+    for (int64_t t = 0; t < n; ++t) {
+        const int64_t len = index[P.order[(size_t)t] + 1] - index[P.order[(size_t)t]];
+        P.sptr[(size_t)t + 1] = P.sptr[(size_t)t] + len;
+        if (len > PCR_ITEMFOLD_LDS_MAX) P.n_big += 1;
+        else if (len > PCR_ITEMFOLD_WAVE_MAX) P.n_lds += 1;
+    }
+    P.puser.resize((size_t)np); P.prater.resize((size_t)np); P.pq.resize((size_t)np);
+    P.anypair.assign((size_t)n, 0);
+    const bool pp = solver_type == PCR_SOLVER_PCRPP;
+    pcr_parallel_ranges(n, nth, [&](int, int64_t lo, int64_t hi) {
+        std::vector<int64_t> perm;
+        for (int64_t t = lo; t < hi; ++t) {
+            const int64_t a = index[P.order[(size_t)t]], len = index[P.order[(size_t)t] + 1] - a, o = P.sptr[(size_t)t];
+            perm.resize((size_t)len);
+            for (int64_t q = 0; q < len; ++q) perm[(size_t)q] = a + q;
+            std::stable_sort(perm.begin(), perm.end(), [&](int64_t x, int64_t y) { return user[x] < user[y]; });
+            int any = 0;
+            for (int64_t q = 0; q < len; ++q) {
+                const int64_t z = perm[(size_t)q];
+                const int32_t r = rpos[(size_t)user[z]];
+                const double key = pp ? (double)fast_lround(val[z]) : val[z];
+                const double* lvv = P.lv.lev_val.data() + P.lv.run_ofs[(size_t)r];
+                const int T = (int)(P.lv.run_ofs[(size_t)r + 1] - P.lv.run_ofs[(size_t)r]) - 1;
+                const int lb = (int)(std::lower_bound(lvv, lvv + T, key) - lvv);
+                const int code = (lb < T && lvv[lb] == key) ? 2 * lb : 2 * lb - 1;
+                P.puser[(size_t)(o + q)] = user[z];
+                P.prater[(size_t)(o + q)] = r;
+                P.pq[(size_t)(o + q)] = code;
+                if (T >= 2 || (T == 1 && code != 0)) any = 1;
+            }
+            P.anypair[(size_t)t] = any;
+        }
+    });
+    return PCR_OK;
+}
+
+void pcr_itemfold_stats_from(const double* per_item, int64_t n, pcr_itemfold_stats* stats) {
+    pcr_itemfold_stats s = {};
+    s.items = n;
+    s.unique_raters = stats->unique_raters;
+    for (int64_t j = 0; j < n; ++j) {
+        const double* o = per_item + (size_t)j * PCR_ITEMFOLD_FIELDS;
+        s.raters += (int64_t)o[0]; s.steps += (int64_t)o[1]; s.cg += (int64_t)o[2]; s.ls += (int64_t)o[3];
+        s.obj += o[5];
+        const int status = (int)o[7];
         if (status == PCR_FOLDIN_CONVERGED) s.converged += 1; else if (status == PCR_FOLDIN_STEP_CAP) s.step_cap += 1; else s.stalled += 1;
     }
     *stats = s;

@@ -199,6 +199,29 @@ int pcr_fold_in_model_check(const pcr_params* p, const double* V, int64_t d2, in
 // stats from the per-user table [n][PCR_FOLDIN_FIELDS]: the counts, and obj added in user order
 void pcr_foldin_stats_from(const double* per_user, int64_t n, pcr_foldin_stats* stats);
 
+// Item fold-in (include/primalcr.h, "item fold-in").  What the host prepares for k_rater_scores / k_itemfold: the new items as
+// SLOTS by descending rater count (equal counts by ascending id) -- slots [0, n_big) take the global-scratch form, the next n_lds
+// the LDS form, the rest one wave each -- with their (item, rater) pairs in ascending user order; the call's unique raters
+// (ascending user id), a copy R of their training rows with its levels, and per pair the doubled rank of the new rating among
+// the rater's levels: 2 * rank when the row holds the level, the odd value between its neighbours when it does not.
+struct PcrItemfoldPlan {
+    int64_t n = 0, n_big = 0, n_lds = 0;
+    std::vector<int32_t> order;       // [n] slot -> item
+    std::vector<int64_t> sptr;        // [n + 1] the slots' pairs
+    std::vector<int32_t> puser, prater, pq;   // per pair: the user id, its position in `raters`, the doubled rank
+    std::vector<int32_t> anypair;     // [n] per slot: some rater's row holds a level different from the new rating's
+    std::vector<int32_t> raters;      // unique rater ids, ascending
+    PcrCsr R;                         // their training rows: row i is user raters[i]
+    PcrLevels lv;
+};
+// pcr_fold_in_items_model's / pcr_fold_in_items' argument checks, in the order include/primalcr.h lists the errors, and the plan.
+// need_factors: U and V are the caller's (the standalone entry).  Errors are prefixed with `who`.  plan may be NULL.
+int pcr_fold_in_items_check(const char* who, bool need_factors, const pcr_params* p, const double* U, int64_t d1, const double* V, int64_t d2,
+                            const int64_t* tr_index, const int32_t* tr_item, const double* tr_val, int64_t n, const int64_t* index,
+                            const int32_t* user, const double* val, int steps, const double* V_out, PcrItemfoldPlan* plan);
+// stats from the per-item table [n][PCR_ITEMFOLD_FIELDS]: the counts, and obj added in item order (unique_raters is the caller's)
+void pcr_itemfold_stats_from(const double* per_item, int64_t n, pcr_itemfold_stats* stats);
+
 // What both fold-in plans share, factored out of pcr_fold_in_check.  pcr_csr_rows_scan: n CSR rows over d2 columns, by the host
 // threads -- bit 0 = an id outside [0, d2), bit 1 = a rating that is not finite, bit 2 = a row that is not item-ascending.
 // pcr_csr_sorted_copy: the copy X of the rows; sort = rows in ascending item order (equal items keep their order).

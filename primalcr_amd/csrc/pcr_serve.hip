@@ -9,6 +9,7 @@
 
 #include "pcr_dev.h"
 #include "pcr_foldin.h"
+#include "pcr_itemfold.h"
 #include "pcr_ridge.h"
 #include "pcr_nnls.h"
 #include "pcr_prims.h"
@@ -1046,6 +1047,160 @@ static int nnls_run(const ServeView& v, double lambda, int weighted, const PcrRi
     return PCR_OK;
 }
 
+// Item fold-in (pcr_fold_in_items, pcr_fold_in_items_model; pcr_itemfold.h) of the plan's items against v's U: the slots and
+// their pairs go to the device once; the slots are then cut into batches whose unique raters' table (scores + levels) stays within
+// the cap -- a batch holds at least one slot -- and each batch uploads its raters' rows and levels, builds the score table
+// ("itemfold/scores": one launch per rater form, the longest raters first) and runs its slots ("itemfold/newton": one launch per
+// workgroup form; the scratch form's slices are bounded by the grid, at most ITEMFOLD_SCRATCH bytes in all).
+static const size_t ITEMFOLD_SCRATCH = (size_t)1 << 30, ITEMFOLD_TABLE = (size_t)1 << 30;
+struct ItemfoldDev { RaterTab R; ItemfoldCsr X; Geo geo; int cus; };
+template <typename T, int BLOCK, bool BIG>
+static int itemfold_launch(const ServeView& v, const FoldinParams& c, const PcrItemfoldPlan& P, const ItemfoldDev& D, int64_t first, int64_t end,
+                           const T* dV0, T* dOut, const T* tab, double* dPer, DBuf<char>& scratch) {
+    const int64_t count = end - first;
+    if (count <= 0) return PCR_OK;
+    const int cap = (int)std::max<int64_t>(1, P.sptr[(size_t)first + 1] - P.sptr[(size_t)first]);      // slots are by descending count
+    const size_t arr = itemfold_arr_bytes(cap, sizeof(T));
+    const size_t lds = itemfold_small_bytes(D.geo.ld, BLOCK, sizeof(T)) + (BIG ? 0 : arr);
+    // the refusal is a function of the rank and the item's form alone, never of the items that share its launch: the form's
+    // largest item must fit
+    const int form_cap = BLOCK == 64 ? PCR_ITEMFOLD_WAVE_MAX : PCR_ITEMFOLD_LDS_MAX;
+    if (itemfold_small_bytes(D.geo.ld, BLOCK, sizeof(T)) + (BIG ? 0 : itemfold_arr_bytes(form_cap, sizeof(T))) > PCR_ITEMFOLD_LDS_CU) {
+        pcr_set_error("item fold-in: rank " + std::to_string(D.geo.r) + " is too large for the LDS of the workgroup form of items " +
+                      (BIG ? "beyond " + std::to_string(PCR_ITEMFOLD_LDS_MAX) : "of up to " + std::to_string(form_cap)) + " raters");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    if (BIG && ((arr + 255) & ~(size_t)255) > ITEMFOLD_SCRATCH) {
+        pcr_set_error("item fold-in: an item of " + std::to_string(cap) + " raters needs more than 1 GiB of per-rater scratch");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(BLOCK == 64 ? 16 : BLOCK == 256 ? 4 : 1, PCR_ITEMFOLD_LDS_CU / lds));
+    int64_t grid = std::min<int64_t>(count, (int64_t)D.cus * per_cu);
+    size_t stride = 0;
+    if (BIG) {
+        stride = (arr + 255) & ~(size_t)255;
+        grid = std::max<int64_t>(1, std::min<int64_t>(grid, (int64_t)(ITEMFOLD_SCRATCH / stride)));
+        RC(scratch.alloc((size_t)grid * stride));
+    }
+    HIPCHK(hipFuncSetAttribute((const void*)k_itemfold<T, BLOCK, BIG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_itemfold<T, BLOCK, BIG>), dim3((unsigned)grid), dim3(BLOCK), lds, v.st, D.R, D.X, D.geo, (int)first, (int)count, dV0, dOut,
+                       serve_U<T>(v), tab, dPer, c.lambda, c.stepsize, c.cg_max, c.cg_tol, c.steps, c.solver_type == PCR_SOLVER_PCR ? 1 : 0, cap,
+                       scratch.p, stride);
+    HIPCHK(hipGetLastError());
+    return PCR_OK;
+}
+
+template <typename T, int BLOCK>
+static int rater_scores_launch(const ServeView& v, const ItemfoldDev& D, const int32_t* d_order, int64_t count, T* tab) {
+    if (count <= 0) return PCR_OK;
+    const int64_t grid = std::min<int64_t>(count, (int64_t)D.cus * (BLOCK == 64 ? 32 : 8));
+    hipLaunchKernelGGL((k_rater_scores<T, BLOCK>), dim3((unsigned)grid), dim3(BLOCK), carve_bytes(D.geo.ld, sizeof(T)), v.st, D.R, D.geo, d_order,
+                       (int)count, serve_U<T>(v), serve_V<T>(v), tab);
+    HIPCHK(hipGetLastError());
+    return PCR_OK;
+}
+
+template <typename T>
+static int itemfold_run(const ServeView& v, const FoldinParams& c, const PcrItemfoldPlan& P, const double* V0, double* V_out, pcr_itemfold_stats* stats,
+                        double* per_item) {
+    const int64_t n = P.n, nr = (int64_t)P.raters.size();
+    hipStream_t st = v.st;
+    ItemfoldDev D;
+    D.geo.r = v.r; D.geo.ld = v.ld; D.geo.nchunk = v.ld / VecOf<T>::N; D.geo.G = std::min(64, host_pow2(D.geo.nchunk));
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    HIPCHK(hipDeviceGetAttribute(&D.cus, hipDeviceAttributeMultiprocessorCount, dev));
+    D.cus = std::max(D.cus, 1);
+    size_t table_cap = ITEMFOLD_TABLE;
+    { std::string knob; if (pcr_tune_get("itemfold_table_bytes", &knob) && atoll(knob.c_str()) > 0) table_cap = (size_t)atoll(knob.c_str()); }
+    DBuf<int64_t> sptr;
+    DBuf<int32_t> orig, anypair, puser, pq;
+    DBuf<T> dV0, dOut;
+    DBuf<double> dPer, dOutD;
+    RC(sptr.upload(P.sptr, st)); RC(orig.upload(P.order, st)); RC(anypair.upload(P.anypair, st)); RC(puser.upload(P.puser, st)); RC(pq.upload(P.pq, st));
+    RC(dV0.alloc((size_t)n * v.ld)); RC(dOut.alloc((size_t)n * v.ld)); RC(dPer.alloc((size_t)n * PCR_ITEMFOLD_FIELDS)); RC(dOutD.alloc((size_t)n * v.r));
+    if (V0) RC(upload_rows<T>(st, v.r, v.ld, {{V0, n, dV0.p}}));
+    else HIPCHK(hipMemsetAsync(dV0.p, 0, (size_t)n * v.ld * sizeof(T), st));
+    std::vector<int32_t> local((size_t)nr, -1), braters, ploc, ruser, rorder;
+    std::vector<int64_t> rptr;
+    std::vector<int32_t> ritem;
+    std::vector<uint16_t> rlvl;
+    auto rlen = [&](int32_t r) { return P.R.index[(size_t)r + 1] - P.R.index[(size_t)r]; };
+    for (int64_t b0 = 0; b0 < n;) {
+        // the batch [b0, b1): slots are added while the table of their unique raters stays within the cap
+        for (int32_t r : braters) local[(size_t)r] = -1;
+        braters.clear();
+        size_t bytes = 0;
+        int64_t b1 = b0;
+        for (; b1 < n; ++b1) {
+            const size_t mark = braters.size();
+            size_t add = 0;
+            for (int64_t z = P.sptr[(size_t)b1]; z < P.sptr[(size_t)b1 + 1]; ++z) {
+                const int32_t r = P.prater[(size_t)z];
+                if (local[(size_t)r] < 0) { local[(size_t)r] = (int32_t)braters.size(); braters.push_back(r); add += (size_t)rlen(r) * (sizeof(T) + 2); }
+            }
+            if (b1 > b0 && bytes + add > table_cap) {
+                for (size_t q = mark; q < braters.size(); ++q) local[(size_t)braters[q]] = -1;
+                braters.resize(mark);
+                break;
+            }
+            bytes += add;
+        }
+        const int64_t nb = (int64_t)braters.size(), pair0 = P.sptr[(size_t)b0], pair1 = P.sptr[(size_t)b1];
+        rptr.assign((size_t)nb + 1, 0); ruser.resize((size_t)nb); rorder.resize((size_t)nb);
+        for (int64_t i = 0; i < nb; ++i) {
+            rptr[(size_t)i + 1] = rptr[(size_t)i] + rlen(braters[(size_t)i]);
+            ruser[(size_t)i] = P.raters[(size_t)braters[(size_t)i]];
+            rorder[(size_t)i] = (int32_t)i;
+        }
+        const int64_t flat = rptr[(size_t)nb];
+        ritem.resize((size_t)flat); rlvl.resize((size_t)flat);
+        for (int64_t i = 0; i < nb; ++i) {
+            const int64_t a = P.R.index[(size_t)braters[(size_t)i]], len = rlen(braters[(size_t)i]);
+            std::copy(P.R.item.begin() + a, P.R.item.begin() + a + len, ritem.begin() + rptr[(size_t)i]);
+            std::copy(P.lv.level.begin() + a, P.lv.level.begin() + a + len, rlvl.begin() + rptr[(size_t)i]);
+        }
+        // raters by descending length (equal lengths in batch order): the wave form is the tail
+        std::stable_sort(rorder.begin(), rorder.end(), [&](int32_t x, int32_t y) { return rptr[(size_t)x + 1] - rptr[(size_t)x] > rptr[(size_t)y + 1] - rptr[(size_t)y]; });
+        int64_t n_wg = 0;
+        while (n_wg < nb && rptr[(size_t)rorder[(size_t)n_wg] + 1] - rptr[(size_t)rorder[(size_t)n_wg]] > PCR_ITEMFOLD_SCORES_WAVE_MAX) ++n_wg;
+        ploc.resize((size_t)(pair1 - pair0));
+        for (int64_t z = pair0; z < pair1; ++z) ploc[(size_t)(z - pair0)] = local[(size_t)P.prater[(size_t)z]];
+        DBuf<int64_t> d_rptr;
+        DBuf<int32_t> d_ruser, d_ritem, d_rorder, d_ploc;
+        DBuf<uint16_t> d_rlvl;
+        DBuf<T> tab;
+        DBuf<char> scratch;
+        RC(d_rptr.upload(rptr, st)); RC(d_ruser.upload(ruser, st)); RC(d_ritem.upload(ritem, st)); RC(d_rlvl.upload(rlvl, st));
+        RC(d_rorder.upload(rorder, st)); RC(d_ploc.upload(ploc, st)); RC(tab.alloc((size_t)flat));
+        D.R = {d_rptr.p, d_ruser.p, d_ritem.p, d_rlvl.p};
+        D.X = {sptr.p, orig.p, anypair.p, puser.p, pq.p, d_ploc.p, pair0};
+        {
+            ProfScope ps(v.prof, "itemfold/scores", st);
+            RC((rater_scores_launch<T, 256>(v, D, d_rorder.p, n_wg, tab.p)));
+            RC((rater_scores_launch<T, 64>(v, D, d_rorder.p + n_wg, nb - n_wg, tab.p)));
+        }
+        {
+            ProfScope ps(v.prof, "itemfold/newton", st);
+            const int64_t e_big = std::min(b1, P.n_big), e_lds = std::min(b1, P.n_big + P.n_lds);
+            RC((itemfold_launch<T, 512, true>(v, c, P, D, b0, e_big, dV0.p, dOut.p, tab.p, dPer.p, scratch)));
+            RC((itemfold_launch<T, 256, false>(v, c, P, D, std::max(b0, P.n_big), e_lds, dV0.p, dOut.p, tab.p, dPer.p, scratch)));
+            RC((itemfold_launch<T, 64, false>(v, c, P, D, std::max(b0, P.n_big + P.n_lds), b1, dV0.p, dOut.p, tab.p, dPer.p, scratch)));
+        }
+        HIPCHK(hipStreamSynchronize(st));        // the batch's buffers go out of scope
+        b0 = b1;
+    }
+    hipLaunchKernelGGL((k_mat_out<T>), dim3((unsigned)std::min<int64_t>(1 << 16, cdiv(n * v.r, 256))), dim3(256), 0, st, (const T*)dOut.p, dOutD.p, n, v.r, v.ld);
+    HIPCHK(hipGetLastError());
+    std::vector<double> hp((size_t)n * PCR_ITEMFOLD_FIELDS);
+    HIPCHK(hipMemcpyAsync(V_out, dOutD.p, (size_t)n * v.r * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hp.data(), dPer.p, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (stats) { stats->unique_raters = nr; pcr_itemfold_stats_from(hp.data(), n, stats); }
+    if (per_item) std::copy(hp.begin(), hp.end(), per_item);
+    return PCR_OK;
+}
+
 extern "C" {
 
 // users[n] (global ids, NULL: the whole shard) as rows of s's shard in loc (left empty for NULL); *n the count
@@ -1374,6 +1529,49 @@ int pcr_fold_in_nnls(pcr_solver* s, int weighted, int64_t n, const int64_t* inde
         if (stats) *stats = pcr_nnls_stats{};
         if (n == 0) return PCR_OK;
         return by_precision(v, [&](auto zero) -> int { return nnls_run<decltype(zero)>(v, lambda, weighted != 0, P, U_out, stats, per_user); });
+    });
+}
+
+int pcr_fold_in_items_model(const pcr_params* p, const double* U, int64_t d1, const double* V, int64_t d2, const int64_t* tr_index,
+                            const int32_t* tr_item, const double* tr_val, int64_t n, const int64_t* index, const int32_t* user, const double* val,
+                            const double* V0, int steps, double* V_out, pcr_itemfold_stats* stats, double* per_item) {
+    return abi_guard("pcr_fold_in_items_model", [&]() -> int {
+    PcrItemfoldPlan P;
+    RC(pcr_fold_in_items_check("pcr_fold_in_items_model", true, p, U, d1, V, d2, tr_index, tr_item, tr_val, n, index, user, val, steps, V_out, &P));
+    RC(model_device(p->device));
+    if (stats) *stats = pcr_itemfold_stats{};
+    if (n == 0) return PCR_OK;
+    ServeView v; ModelDev M;
+    RC(M.open(U, d1, V, d2, p->k, nullptr, nullptr, true, p->precision, &v));
+    const FoldinParams c = foldin_params_of(*p, steps);
+    return by_precision(v, [&](auto zero) -> int { return itemfold_run<decltype(zero)>(v, c, P, V0, V_out, stats, per_item); });
+    });
+}
+
+int pcr_fold_in_items(pcr_solver* s, const pcr_dataset* train, int64_t n, const int64_t* index, const int32_t* user, const double* val,
+                      const double* V0, int steps, double* V_out, pcr_itemfold_stats* stats, double* per_item) {
+    S_OR_ARG;
+    return abi_guard("pcr_fold_in_items", [&]() -> int {
+        pcr_params prm;
+        if (s->foldin_params(&prm) != PCR_OK) return pcr_solver::pcr_only("pcr_fold_in_items");
+        const ServeView v = solver_view(s, 0);
+        if (s->comm_nranks() > 1 || s->first_user != 0 || s->n_users != v.d1) {
+            pcr_set_error("pcr_fold_in_items: needs every user on the rank; this solver holds a shard");
+            return PCR_ERR_STATE;
+        }
+        if (!train) { pcr_set_error("pcr_fold_in_items: null training data set"); return PCR_ERR_ARG; }
+        const PcrCsr& X = train->train;
+        if (X.d1 != v.d1 || X.d2 != v.d2 || X.nnz() != v.nnz) {
+            pcr_set_error("pcr_fold_in_items: the data set is not the one the solver was created from (dimensions or nnz differ)");
+            return PCR_ERR_ARG;
+        }
+        PcrItemfoldPlan P;
+        RC(pcr_fold_in_items_check("pcr_fold_in_items", false, &prm, nullptr, X.d1, nullptr, X.d2, X.index.data(), X.item.data(), X.val.data(), n, index,
+                                   user, val, steps, V_out, &P));
+        if (stats) *stats = pcr_itemfold_stats{};
+        if (n == 0) return PCR_OK;
+        const FoldinParams c = foldin_params_of(prm, steps);
+        return by_precision(v, [&](auto zero) -> int { return itemfold_run<decltype(zero)>(v, c, P, V0, V_out, stats, per_item); });
     });
 }
 

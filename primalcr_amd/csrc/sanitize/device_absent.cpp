@@ -137,6 +137,15 @@ int pcr_fold_in_nnls_model(const double* F, int64_t rows, int64_t k, double lamb
     return rc != PCR_OK ? rc : absent();
 }
 NO_SOLVER(pcr_fold_in_nnls, pcr_solver*, int, int64_t, const int64_t*, const int32_t*, const double*, double*, pcr_nnls_stats*, double*)
+int pcr_fold_in_items_model(const pcr_params* p, const double* U, int64_t d1, const double* V, int64_t d2, const int64_t* tr_index,
+                            const int32_t* tr_item, const double* tr_val, int64_t n, const int64_t* index, const int32_t* user, const double* val,
+                            const double*, int steps, double* V_out, pcr_itemfold_stats*, double*) {
+    const int rc = pcr_fold_in_items_check("pcr_fold_in_items_model", true, p, U, d1, V, d2, tr_index, tr_item, tr_val, n, index, user, val, steps, V_out,
+                                           nullptr);
+    return rc != PCR_OK ? rc : absent();
+}
+NO_SOLVER(pcr_fold_in_items, pcr_solver*, const pcr_dataset*, int64_t, const int64_t*, const int32_t*, const double*, const double*, int, double*,
+          pcr_itemfold_stats*, double*)
 NO_SOLVER(pcr_evaluate_rerank, pcr_solver*, int64_t, const int32_t*, int, const double*, int, int, const int*, double, int, pcr_topn_stats*,
           pcr_diversity_stats*, double*, double*, int64_t*)
 }
