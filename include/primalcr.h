@@ -219,6 +219,8 @@ int pcr_partition_users(const int64_t *index, int64_t d1, int nparts, int64_t *b
  *                   empty): tools/exp_recommend.py times the selection's share with it; default 1
  *   ranks_batch_users  test hook: at most this many counted users per batch of pcr_evaluate_ranks (rounded up to whole
  *                   workgroups of 64; 0 = the natural batch, which holds a million users and more); read at every call
+ *   sample_threads  test hook: the host threads of pcr_sample_negatives (0 = the set-up default); its rows do not depend on it;
+ *                   read at every call
  *   rerank_lds      the form of pcr_recommend_diverse's selection kernel: 0 (default) = the streaming form (the pool's rows of V
  *                   are re-read from L2 every round; the faster one at every shape measured), 1 = the LDS form (the pool's rows
  *                   staged once per user) whenever one wave's image fits a workgroup's 160 KiB; both forms implement the same
@@ -548,6 +550,75 @@ int pcr_evaluate_ranks_model(const double *U, int64_t d1, const double *V, int64
  * Profile slots: ranks/relscore (the relevant items' scores and their sort), ranks/count (the counting sweep), ranks/finish. */
 int pcr_evaluate_ranks(pcr_solver *s, double threshold, int flags,
                        pcr_rank_stats *stats, double *per_user, int64_t *ranks);                   /* [device] */
+
+/* ------------------------------------------------------------------------- */
+/* filtered evaluation: top-N and rank metrics within allowed items and       */
+/* candidate rows (no reference counterpart)                                  */
+/* ------------------------------------------------------------------------- */
+/* The two evaluations above restricted by a pcr_item_filter f (unchanged; see "filtered recommendation"): sampled-candidate
+ * evaluation (a user's held-out items against N sampled negatives: HR@10, NDCG@10, MRR, AUC over 1 + 99 candidates; the rows come
+ * from pcr_sample_negatives below) and evaluation within a catalogue subset.  For a user u let F_u be the items of u's candidate
+ * row (cand_ptr NULL: all items) whose allow[j] is nonzero (allow NULL: all of them); the filters intersect.
+ *   Relevant set     R_u^f = R_u & F_u, R_u exactly as in the two blocks above (distinct items, rating >= threshold, the largest
+ *                    rating kept).  The filter restricts the relevant set; training exclusion still does not.  Counted users are
+ *                    those with |R_u^f| >= 1, in ascending order; the others are not scored.
+ *   Top-N            L_u is exactly the list pcr_recommend_filtered(_model) returns for the same factors, dtype, K = the last
+ *                    cutoff, exclusion and filter.  Every formula of pcr_evaluate_topn applies with R_u^f in place of R_u; a list
+ *                    shorter than a cutoff is padded, padding is never relevant, precision = hits / c as before.
+ *   Ranks            N_u^f = F_u minus R_u^f minus (with exclusion on) u's training row.  rank_u(j), first_rank, rr, mean_rank,
+ *                    auc, mpr and the summary are those of pcr_evaluate_ranks with R_u^f and N_u^f.  A relevant item inside F_u
+ *                    is always ranked, also when it sits in the training row (the existing rule).  Each quotient remains one fp64
+ *                    division of exact integers.  ranks[] is 0 for test ratings below the threshold and for those whose item is
+ *                    outside F_u.
+ *   Scores, order    bit for bit those of pcr_recommend, through the same chain; ties by ascending id.
+ *   Determinism      as the unfiltered entries: integer histogram adds commute, the sums over users run in a fixed order, two
+ *                    identical calls are bitwise identical.
+ *   Rows             model entries: cand_ptr has d1 + 1 entries, one row per user of the model; solver entries: n_users + 1, in
+ *                    the shard's order.  Rows of uncounted users are checked and otherwise ignored.  A row may have any length
+ *                    and |R_u^f| has no cap.
+ *   Errors           f == NULL, or a filter with nothing in it, is PCR_ERR_ARG (the message points at pcr_evaluate_topn /
+ *                    pcr_evaluate_ranks); the filter's own errors are those of pcr_recommend_filtered with this entry's name.
+ *                    Everything is checked on the host before any device is looked for.
+ * Every other argument and output is that of the unfiltered entry of the same name.  The solver entries reduce across the
+ * communicator as the unfiltered ones do, leave the training state alone and do not touch the solver's cached unfiltered
+ * relevance tables: filtered tables are built per call.
+ * PCR_CAND_RANK_STAGE: with candidate rows the rank metrics stage a relevant row of up to this many entries in LDS and search
+ * longer ones in global memory (the full sweep's own stage length is 32); results do not depend on it.
+ * Profile slots (of the solver entries): top-N -- recommend/score + recommend/metrics for an allow set alone,
+ * recommend/candidates_metrics (selection and metrics in one launch per user batch) + recommend/metrics (the reduction) with
+ * candidate rows; ranks -- ranks/relscore, ranks/finish and ranks/count (allow alone) or ranks/candidates (candidate rows). */
+#define PCR_CAND_RANK_STAGE 64
+int pcr_evaluate_topn_filtered_model(const double *U, int64_t d1, const double *V, int64_t d2, int64_t k,
+                                     const int64_t *index, const int32_t *item,
+                                     const int64_t *tindex, const int32_t *titem, const double *tval,
+                                     int ncut, const int *cutoffs, double threshold, int dtype, const pcr_item_filter *f,
+                                     pcr_topn_stats *stats, double *per_user, int device);           /* [device] */
+int pcr_evaluate_topn_filtered(pcr_solver *s, int ncut, const int *cutoffs, double threshold, int flags,
+                               const pcr_item_filter *f, pcr_topn_stats *stats, double *per_user);   /* [device] */
+int pcr_evaluate_ranks_filtered_model(const double *U, int64_t d1, const double *V, int64_t d2, int64_t k,
+                                      const int64_t *index, const int32_t *item,
+                                      const int64_t *tindex, const int32_t *titem, const double *tval,
+                                      double threshold, int dtype, const pcr_item_filter *f,
+                                      pcr_rank_stats *stats, double *per_user, int64_t *ranks, int device);   /* [device] */
+int pcr_evaluate_ranks_filtered(pcr_solver *s, double threshold, int flags, const pcr_item_filter *f,
+                                pcr_rank_stats *stats, double *per_user, int64_t *ranks);            /* [device] */
+
+/* Candidate rows for the sampled protocol, on the host, deterministically: row u is the ascending union of sampled negatives
+ * of user u and, with include_test, u's distinct test items.  With uint64 wrapping arithmetic
+ *   mix(x):  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31
+ *   key(u)  = mix(seed + 0x9E3779B97F4A7C15 * (u + 1))                         (u: the GLOBAL user id, first_user + row)
+ *   draw t  = 0, 1, 2, ...:   j_t = mix(key(u) + 0x9E3779B97F4A7C15 * (t + 1)) % d2
+ * The pool P_u is every item in neither u's training row (index / item, both NULL: no training rows) nor its test row -- every
+ * test item is left out, whatever its rating.  m = min(n_neg, |P_u|).  m == |P_u|: the whole pool is taken.  Otherwise, if
+ * 2 m <= |P_u|, the first m distinct draws that fall in P_u are taken; otherwise the first |P_u| - m such draws are LEFT OUT and
+ * the rest of the pool is taken.  A user without test ratings gets an empty row.  The result does not depend on the number of
+ * host threads or on how users are sharded.
+ * rows: the users index / tindex describe (row i is user first_user + i).  Two calls: with cand_item NULL, cand_ptr[rows + 1]
+ * receives the row pointer; with cand_item given (cand_ptr[rows] entries), both are written.  The sizing call draws nothing: a row's length is
+ * min(n_neg, |P_u|) plus, with include_test, its distinct test items.  n_neg >= 0. */
+int pcr_sample_negatives(int64_t rows, int64_t d2, const int64_t *index, const int32_t *item,
+                         const int64_t *tindex, const int32_t *titem, int64_t first_user, int64_t n_neg, uint64_t seed,
+                         int include_test, int64_t *cand_ptr, int32_t *cand_item);
 
 /* ------------------------------------------------------------------------- */
 /* beyond-accuracy top-N metrics: catalogue coverage, Gini index of item      */

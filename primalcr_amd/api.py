@@ -12,6 +12,9 @@ PCR_RECOMMEND_MAX_K = 1024
 PCR_REC_EXCLUDE_TRAIN = 1
 PCR_TOPN_MAX_CUTOFFS = 8
 PCR_RERANK_MAX_THETAS = 8
+# evaluate_ranks' stage lengths (include/primalcr.h, pcr_topk.h): relevant rows up to these lengths are counted in LDS by the
+# full sweep / by the candidate-row kernel, longer ones in global memory; results do not depend on them (tests straddle them)
+PCR_RANK_STAGE, PCR_CAND_RANK_STAGE = 32, 64
 TOPN_FIELDS = ("hits", "precision", "recall", "ap", "ndcg", "ndcg_graded")   # per_user columns
 RANK_FIELDS = ("first_rank", "rr", "mean_rank", "auc", "mpr")                   # evaluate_ranks' per_user columns (PCR_RANK_FIELDS)
 DIVERSITY_FIELDS = ("len", "novelty", "ild")                                     # evaluate_diversity's per_user columns (PCR_DIVERSITY_FIELDS)
@@ -219,6 +222,12 @@ def lib():
     L.pcr_evaluate_topn.argtypes = [vp, ci, vp, cd, ci, vp, vp]
     L.pcr_evaluate_ranks_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, cd, ci, vp, vp, vp, ci]
     L.pcr_evaluate_ranks.argtypes = [vp, cd, ci, vp, vp, vp]
+    if hasattr(L, "pcr_evaluate_topn_filtered_model"):           # (absent from an older build loaded through use_library)
+        L.pcr_evaluate_topn_filtered_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, ci, vp, cd, ci, C.POINTER(ItemFilter), vp, vp, ci]
+        L.pcr_evaluate_topn_filtered.argtypes = [vp, ci, vp, cd, ci, C.POINTER(ItemFilter), vp, vp]
+        L.pcr_evaluate_ranks_filtered_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, cd, ci, C.POINTER(ItemFilter), vp, vp, vp, ci]
+        L.pcr_evaluate_ranks_filtered.argtypes = [vp, cd, ci, C.POINTER(ItemFilter), vp, vp, vp]
+        L.pcr_sample_negatives.argtypes = [i64, i64, vp, vp, vp, vp, i64, i64, C.c_uint64, ci, vp, vp]
     L.pcr_evaluate_diversity_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, vp, ci, vp, ci, vp, vp, vp, ci]
     L.pcr_evaluate_diversity.argtypes = [vp, i64, vp, ci, vp, ci, vp, vp, vp]
     L.pcr_evaluate_lists_model.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp, ci, vp, ci, vp, cd, ci, vp, vp, vp, vp, vp, ci]
@@ -434,12 +443,16 @@ def _topn_call(cutoffs, per_user, rows, fn):
     return (out, pu) if per_user else out
 
 
-def evaluate_topn(U, V, test, cutoffs=(10,), exclude=None, threshold=-np.inf, dtype=PCR_F64, device=0, per_user=False):
+def evaluate_topn(U, V, test, cutoffs=(10,), exclude=None, threshold=-np.inf, dtype=PCR_F64, device=0, per_user=False, allow=None,
+                  candidates=None):
     """Full-catalogue top-N evaluation on the GPU (pcr_evaluate_topn_model): every user with a relevant test rating (value >=
     threshold) gets its top max(cutoffs) list, as recommend() returns it, scored against its test items.  test / exclude: a
     Dataset (its test / training CSR) or an (index, item, val) / (index, item) tuple; exclude None: no exclusion.  Returns one
     dict per cutoff (cutoff, users, users_graded, hits, precision, recall, hit_rate, map, ndcg, ndcg_graded) and, with
-    per_user, also the array [d1, ncut, 6] of TOPN_FIELDS (NaN for users not counted and for an undefined ndcg_graded)."""
+    per_user, also the array [d1, ncut, 6] of TOPN_FIELDS (NaN for users not counted and for an undefined ndcg_graded).
+    allow / candidates as recommend(), with one candidate row per user of the model: the evaluation within the items that pass
+    every filter (pcr_evaluate_topn_filtered_model) -- the list is recommend()'s with the same filter, and a test item outside
+    the filter is not relevant.  sample_negatives() makes the rows of the sampled-candidate protocol."""
     U = np.ascontiguousarray(U, np.float64); V = np.ascontiguousarray(V, np.float64)
     d1, k = U.shape
     if isinstance(test, Dataset):
@@ -458,6 +471,11 @@ def evaluate_topn(U, V, test, cutoffs=(10,), exclude=None, threshold=-np.inf, dt
         idx = np.ascontiguousarray(idx, np.int64); it = np.ascontiguousarray(it, np.int32)
         if idx.shape[0] != d1 + 1 or idx[-1] != it.shape[0]:
             raise ValueError(f"exclude: index must have d1 + 1 = {d1 + 1} entries, the last equal to len(item) = {it.shape[0]}")
+    if allow is not None or candidates is not None:
+        f, _keep = _item_filter(allow, candidates, V.shape[0], d1)
+        return _topn_call(cutoffs, per_user, d1, lambda nc, cp, sp, pp: lib().pcr_evaluate_topn_filtered_model(
+            U.ctypes.data, d1, V.ctypes.data, V.shape[0], k, None if idx is None else idx.ctypes.data, None if it is None else it.ctypes.data,
+            tidx.ctypes.data, tit.ctypes.data, tval.ctypes.data, nc, cp, float(threshold), int(dtype), C.byref(f), sp, pp, device))
     return _topn_call(cutoffs, per_user, d1, lambda nc, cp, sp, pp: lib().pcr_evaluate_topn_model(
         U.ctypes.data, d1, V.ctypes.data, V.shape[0], k, None if idx is None else idx.ctypes.data, None if it is None else it.ctypes.data,
         tidx.ctypes.data, tit.ctypes.data, tval.ctypes.data, nc, cp, float(threshold), int(dtype), sp, pp, device))
@@ -478,12 +496,15 @@ def _ranks_call(per_user, ranks, rows, tnnz, fn):
     return out[0] if len(out) == 1 else out
 
 
-def evaluate_ranks(U, V, test, exclude=None, threshold=-np.inf, dtype=PCR_F64, device=0, per_user=False, ranks=False):
+def evaluate_ranks(U, V, test, exclude=None, threshold=-np.inf, dtype=PCR_F64, device=0, per_user=False, ranks=False, allow=None,
+                   candidates=None):
     """Exact full-catalogue rank metrics on the GPU (pcr_evaluate_ranks_model): the position of every relevant test item (value >=
     threshold) among all items the user has not rated (exclude given) in the order of recommend().  test / exclude as
     evaluate_topn().  Returns the summary dict (users, users_auc, relevant, mrr, mean_rank, auc, mpr); with per_user also the
     array [d1, 5] of RANK_FIELDS (NaN for users not counted and for an undefined auc); with ranks also the int64 array [tnnz] of
-    1-based ranks in the order of the test CSR (0 for ratings below the threshold)."""
+    1-based ranks in the order of the test CSR (0 for ratings below the threshold).
+    allow / candidates as evaluate_topn(): the ranks among the items that pass every filter (pcr_evaluate_ranks_filtered_model);
+    a test item outside the filter is not relevant and gets rank 0."""
     U = np.ascontiguousarray(U, np.float64); V = np.ascontiguousarray(V, np.float64)
     d1, k = U.shape
     if isinstance(test, Dataset):
@@ -502,9 +523,40 @@ def evaluate_ranks(U, V, test, exclude=None, threshold=-np.inf, dtype=PCR_F64, d
         idx = np.ascontiguousarray(idx, np.int64); it = np.ascontiguousarray(it, np.int32)
         if idx.shape[0] != d1 + 1 or idx[-1] != it.shape[0]:
             raise ValueError(f"exclude: index must have d1 + 1 = {d1 + 1} entries, the last equal to len(item) = {it.shape[0]}")
+    if allow is not None or candidates is not None:
+        f, _keep = _item_filter(allow, candidates, V.shape[0], d1)
+        return _ranks_call(per_user, ranks, d1, tit.shape[0], lambda sp, pp, rp: lib().pcr_evaluate_ranks_filtered_model(
+            U.ctypes.data, d1, V.ctypes.data, V.shape[0], k, None if idx is None else idx.ctypes.data, None if it is None else it.ctypes.data,
+            tidx.ctypes.data, tit.ctypes.data, tval.ctypes.data, float(threshold), int(dtype), C.byref(f), sp, pp, rp, device))
     return _ranks_call(per_user, ranks, d1, tit.shape[0], lambda sp, pp, rp: lib().pcr_evaluate_ranks_model(
         U.ctypes.data, d1, V.ctypes.data, V.shape[0], k, None if idx is None else idx.ctypes.data, None if it is None else it.ctypes.data,
         tidx.ctypes.data, tit.ctypes.data, tval.ctypes.data, float(threshold), int(dtype), sp, pp, rp, device))
+
+
+def sample_negatives(d2, test, train=None, n_neg=99, seed=0, include_test=True, first_user=0):
+    """Candidate rows for sampled-candidate evaluation (pcr_sample_negatives, on the host): per user with test ratings, n_neg
+    items drawn -- deterministically from (seed, user id) -- among the items in neither its training row nor its test row and,
+    with include_test, its distinct test items; rows ascending, a user without test ratings gets an empty row.  test / train: a
+    Dataset or an (index, item[, val]) tuple; train None: no training rows.  first_user: the global id of row 0 (a shard).
+    Returns (index int64 [rows + 1], item int32), what evaluate_topn() / evaluate_ranks() take as candidates."""
+    tidx, tit = test.csr(1)[:2] if isinstance(test, Dataset) else test[:2]
+    tidx = np.ascontiguousarray(tidx, np.int64); tit = np.ascontiguousarray(tit, np.int32)
+    rows = tidx.shape[0] - 1
+    if rows < 0 or tidx[-1] != tit.shape[0]:
+        raise ValueError("test: index must have rows + 1 entries, the last equal to len(item)")
+    idx = it = None
+    if train is not None:
+        idx, it = train.csr(0)[:2] if isinstance(train, Dataset) else train[:2]
+        idx = np.ascontiguousarray(idx, np.int64); it = np.ascontiguousarray(it, np.int32)
+        if idx.shape[0] != rows + 1 or idx[-1] != it.shape[0]:
+            raise ValueError(f"train: index must have rows + 1 = {rows + 1} entries, the last equal to len(item) = {it.shape[0]}")
+    ptr = np.zeros(rows + 1, np.int64)
+    args = (rows, int(d2), None if idx is None else idx.ctypes.data, None if it is None else it.ctypes.data, tidx.ctypes.data, tit.ctypes.data,
+            int(first_user), int(n_neg), int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if include_test else 0)
+    _chk(lib().pcr_sample_negatives(*args, ptr.ctypes.data, None))
+    item = np.empty(max(int(ptr[-1]), 1), np.int32)
+    _chk(lib().pcr_sample_negatives(*args, ptr.ctypes.data, item.ctypes.data))
+    return ptr, item[:int(ptr[-1])]
 
 
 def _diversity_call(cutoffs, per_user, exposure, n, d2, fn):
@@ -1215,22 +1267,32 @@ class Solver:
                                          PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, items.ctypes.data, scores.ctypes.data))
         return items, scores
 
-    def evaluate_topn(self, cutoffs=(10,), threshold=-np.inf, exclude_train=True, per_user=False):
+    def evaluate_topn(self, cutoffs=(10,), threshold=-np.inf, exclude_train=True, per_user=False, allow=None, candidates=None):
         """Full-catalogue top-N evaluation of this shard's users against the solver's test ratings (pcr_evaluate_topn); the
         result as evaluate_topn(), per_user rows for the shard's users.  N ranks with a communicator: the totals of all ranks
-        (every rank must call); local-only shards: their own partials."""
+        (every rank must call); local-only shards: their own partials.  allow / candidates as evaluate_topn(), one candidate
+        row per user of the shard (pcr_evaluate_topn_filtered)."""
+        if allow is not None or candidates is not None:
+            f, _keep = _item_filter(allow, candidates, self.d2, self.n_users)
+            return _topn_call(cutoffs, per_user, self.n_users, lambda nc, cp, sp, pp: lib().pcr_evaluate_topn_filtered(
+                self._h, nc, cp, float(threshold), PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, C.byref(f), sp, pp))
         return _topn_call(cutoffs, per_user, self.n_users, lambda nc, cp, sp, pp: lib().pcr_evaluate_topn(
             self._h, nc, cp, float(threshold), PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, sp, pp))
 
-    def evaluate_ranks(self, threshold=-np.inf, exclude_train=True, per_user=False, ranks=False):
+    def evaluate_ranks(self, threshold=-np.inf, exclude_train=True, per_user=False, ranks=False, allow=None, candidates=None):
         """Exact full-catalogue rank metrics of this shard's users against the solver's test ratings (pcr_evaluate_ranks); the
         result as evaluate_ranks(), per_user rows and ranks for the shard's users / test ratings.  N ranks with a communicator:
-        the totals of all ranks (every rank must call); local-only shards: their own partials."""
+        the totals of all ranks (every rank must call); local-only shards: their own partials.  allow / candidates as
+        evaluate_ranks(), one candidate row per user of the shard (pcr_evaluate_ranks_filtered)."""
         tnnz = 0
         if ranks:
             tidx = self.ds.csr(1)[0]                     # (a shard's own data set starts at its first user)
             lo = 0 if tidx.shape[0] - 1 == self.n_users else self.first_user
             tnnz = int(tidx[lo + self.n_users] - tidx[lo])
+        if allow is not None or candidates is not None:
+            f, _keep = _item_filter(allow, candidates, self.d2, self.n_users)
+            return _ranks_call(per_user, ranks, self.n_users, tnnz, lambda sp, pp, rp: lib().pcr_evaluate_ranks_filtered(
+                self._h, float(threshold), PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, C.byref(f), sp, pp, rp))
         return _ranks_call(per_user, ranks, self.n_users, tnnz, lambda sp, pp, rp: lib().pcr_evaluate_ranks(
             self._h, float(threshold), PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, sp, pp, rp))
 

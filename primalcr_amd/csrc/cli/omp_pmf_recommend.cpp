@@ -66,6 +66,14 @@
 //                    user (any order, no id twice; an empty line is an empty row), as many lines as users; the list is the -K best
 //                    of them.  Both go with the plain list and --scores and intersect with each other and with -x; not together
 //                    with --eval, --diversity, --mmr, --tradeoff, --ranks or --fold-in
+//   omp-pmf-recommend --eval data_dir [--among items_file] [--eval-candidates file | --negatives N [--seed S]] [--ranks] [-c ...] [--threshold v] [-x data_dir] [--f32] model_file [output_file]
+//     --among file   evaluate within these items only (pcr_evaluate_topn_filtered_model, pcr_evaluate_ranks_filtered_model): the
+//                    format of --allow; a test item outside them is not relevant
+//     --eval-candidates f  evaluate within a candidate row per user: the format of --candidates, one line per user of the model
+//     --negatives N  sampled-candidate evaluation: every user with test ratings is ranked among its test items and N items drawn
+//                    (pcr_sample_negatives, --seed S, default 0) from those in neither its test row nor -x's training row
+//                    All three go with --eval only (with or without --ranks), intersect, keep the formats of --eval / --ranks and
+//                    are refused with --fold-in*, --diversity, --mmr and --tradeoff; --negatives does not go with --eval-candidates
 // Output: one line per user, in input order: the 1-based user id, then the 1-based item ids (padding is left out).  Users go
 // to the device in batches, so host memory for the lists stays bounded on any catalogue.
 // With --eval: stdout gets one line per cutoff, "cutoff c users n users_graded n hits n precision x recall x hit_rate x map x
@@ -141,7 +149,12 @@ static const char* USAGE =
     "       omp-pmf-recommend [--allow items_file] [--candidates file] [-K topk] [-x data_dir] [-u users_file] [--f32] [--scores] model_file output_file\n"
     "    --allow file   recommend among these items only: one 1-based item id per line\n"
     "    --candidates f line i: the space-separated 1-based candidate items of the i-th requested user (an empty line: none);\n"
-    "                   the list is the -K best of them; both go with the plain list and --scores only\n";
+    "                   the list is the -K best of them; both go with the plain list and --scores only\n"
+    "       omp-pmf-recommend --eval data_dir [--among items_file] [--eval-candidates file | --negatives N [--seed S]] [--ranks] [-c ...] [--threshold v] [-x data_dir] [--f32] model_file [output_file]\n"
+    "    --among file   with --eval: evaluate within these items only (one 1-based item id per line); a test item outside is not relevant\n"
+    "    --eval-candidates f  with --eval: evaluate within a candidate row per user; line i: the 1-based items of user i of the model\n"
+    "    --negatives N  with --eval: every user's test items against N sampled items outside its test row and -x's training row;\n"
+    "                   --seed S (default 0) picks the sample; not with --eval-candidates; the output keeps --eval's / --ranks' formats\n";
 
 static int usage() { printf("%s", USAGE); return 1; }
 
@@ -272,19 +285,44 @@ static bool load_csr(const char* dir, int which, int64_t d1, int64_t d2, std::ve
 // --eval: the metrics per cutoff to stdout, the per-user rows at the largest cutoff to out_path (if given)
 static int run_eval(const char* edir, const std::vector<double>& U, const std::vector<double>& V, int64_t d1, int64_t d2, int64_t k,
                     const std::vector<int64_t>* xindex, const std::vector<int32_t>* xitem, const std::vector<int>& cuts, double threshold,
-                    bool f32, bool with_ranks, const char* out_path) {
+                    bool f32, bool with_ranks, const char* out_path, const char* among, const char* ecfile, long long negatives,
+                    unsigned long long seed) {
     std::vector<int64_t> tindex;
     std::vector<int32_t> titem;
     std::vector<double> tval;
     if (!load_csr(edir, 1, d1, d2, tindex, titem, &tval)) return 1;
+    std::vector<uint8_t> allow;                                    // --among / --eval-candidates / --negatives: the filter of both calls
+    std::vector<int64_t> cptr;
+    std::vector<int32_t> citem;
+    if (among && !read_allow(among, d2, allow)) return 1;
+    if (ecfile && !read_candidates(ecfile, d1, d2, cptr, citem)) return 1;
+    citem.reserve(citem.size() + 1);                               // (a file of empty rows still hands the library a pointer)
+    if (negatives >= 0) {
+        cptr.resize((size_t)d1 + 1);
+        const int64_t* xi = xindex ? xindex->data() : nullptr;
+        const int32_t* xt = xitem ? xitem->data() : nullptr;
+        int rc = pcr_sample_negatives(d1, d2, xi, xt, tindex.data(), titem.data(), 0, negatives, seed, 1, cptr.data(), nullptr);
+        if (rc == PCR_OK) {
+            citem.resize((size_t)cptr[(size_t)d1] + 1);
+            rc = pcr_sample_negatives(d1, d2, xi, xt, tindex.data(), titem.data(), 0, negatives, seed, 1, cptr.data(), citem.data());
+        }
+        if (rc != PCR_OK) { fprintf(stderr, "evaluate: %s\n", pcr_last_error()); return 1; }
+    }
+    const bool filtered = among || ecfile || negatives >= 0;
+    const pcr_item_filter flt = {among ? allow.data() : nullptr, cptr.empty() ? nullptr : cptr.data(), cptr.empty() ? nullptr : citem.data()};
     const int nc = (int)cuts.size();
     std::vector<pcr_topn_stats> st((size_t)nc);
     std::vector<double> per;
     const bool topn_rows = out_path && !with_ranks;
     if (topn_rows) per.resize((size_t)d1 * nc * 6);
-    if (pcr_evaluate_topn_model(U.data(), d1, V.data(), d2, k, xindex ? xindex->data() : nullptr, xitem ? xitem->data() : nullptr, tindex.data(),
-                                titem.data(), tval.data(), nc, cuts.data(), threshold, f32 ? PCR_F32 : PCR_F64, st.data(),
-                                topn_rows ? per.data() : nullptr, 0) != PCR_OK) {
+    const int trc = filtered
+        ? pcr_evaluate_topn_filtered_model(U.data(), d1, V.data(), d2, k, xindex ? xindex->data() : nullptr, xitem ? xitem->data() : nullptr,
+                                           tindex.data(), titem.data(), tval.data(), nc, cuts.data(), threshold, f32 ? PCR_F32 : PCR_F64, &flt,
+                                           st.data(), topn_rows ? per.data() : nullptr, 0)
+        : pcr_evaluate_topn_model(U.data(), d1, V.data(), d2, k, xindex ? xindex->data() : nullptr, xitem ? xitem->data() : nullptr, tindex.data(),
+                                  titem.data(), tval.data(), nc, cuts.data(), threshold, f32 ? PCR_F32 : PCR_F64, st.data(),
+                                  topn_rows ? per.data() : nullptr, 0);
+    if (trc != PCR_OK) {
         fprintf(stderr, "evaluate: %s\n", pcr_last_error());
         return 1;
     }
@@ -294,9 +332,14 @@ static int run_eval(const char* edir, const std::vector<double>& U, const std::v
     if (with_ranks) {
         pcr_rank_stats rs;
         if (out_path) per.resize((size_t)d1 * PCR_RANK_FIELDS);
-        if (pcr_evaluate_ranks_model(U.data(), d1, V.data(), d2, k, xindex ? xindex->data() : nullptr, xitem ? xitem->data() : nullptr,
-                                     tindex.data(), titem.data(), tval.data(), threshold, f32 ? PCR_F32 : PCR_F64, &rs,
-                                     out_path ? per.data() : nullptr, nullptr, 0) != PCR_OK) {
+        const int rrc = filtered
+            ? pcr_evaluate_ranks_filtered_model(U.data(), d1, V.data(), d2, k, xindex ? xindex->data() : nullptr, xitem ? xitem->data() : nullptr,
+                                                tindex.data(), titem.data(), tval.data(), threshold, f32 ? PCR_F32 : PCR_F64, &flt, &rs,
+                                                out_path ? per.data() : nullptr, nullptr, 0)
+            : pcr_evaluate_ranks_model(U.data(), d1, V.data(), d2, k, xindex ? xindex->data() : nullptr, xitem ? xitem->data() : nullptr,
+                                       tindex.data(), titem.data(), tval.data(), threshold, f32 ? PCR_F32 : PCR_F64, &rs,
+                                       out_path ? per.data() : nullptr, nullptr, 0);
+        if (rrc != PCR_OK) {
             fprintf(stderr, "evaluate: %s\n", pcr_last_error());
             return 1;
         }
@@ -528,7 +571,10 @@ static int run_fold_in_items(const char* path, const char* xdir, const char* mod
 int main(int argc, char** argv) {
     int K = 10;
     bool f32 = false, with_scores = false, with_ranks = false, diversity = false;
-    const char *xdir = nullptr, *ufile = nullptr, *edir = nullptr, *afile = nullptr, *cfile = nullptr;
+    const char *xdir = nullptr, *ufile = nullptr, *edir = nullptr, *afile = nullptr, *cfile = nullptr, *among = nullptr, *ecfile = nullptr;
+    long long negatives = -1;                                      // --negatives (-1: not given)
+    unsigned long long seed = 0;
+    bool have_seed = false;
     std::vector<int> cuts;
     double threshold = -INFINITY, theta = 0.0;
     bool mmr = false;
@@ -632,6 +678,22 @@ int main(int argc, char** argv) {
         } else if (!strcmp(a, "--allow") || !strcmp(a, "--candidates")) {
             if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
             (a[2] == 'a' ? afile : cfile) = argv[++i];
+        } else if (!strcmp(a, "--among") || !strcmp(a, "--eval-candidates")) {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
+            (a[2] == 'a' ? among : ecfile) = argv[++i];
+        } else if (!strcmp(a, "--negatives") || !strcmp(a, "--seed")) {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
+            const char* v = argv[++i];
+            char* end = nullptr;
+            errno = 0;
+            if (a[2] == 'n') {
+                negatives = strtoll(v, &end, 10);
+                if (!*v || *end || errno || negatives < 0) { fprintf(stderr, "--negatives %s: must be an integer >= 0\n", v); return 1; }
+            } else {
+                seed = strtoull(v, &end, 10);
+                if (!*v || *end || errno || *v == '-') { fprintf(stderr, "--seed %s: must be an integer >= 0\n", v); return 1; }
+                have_seed = true;
+            }
         } else if (!strcmp(a, "--f32")) f32 = true;
         else if (!strcmp(a, "--scores")) with_scores = true;
         else if (!strcmp(a, "--ranks")) with_ranks = true;
@@ -640,6 +702,15 @@ int main(int argc, char** argv) {
         else pos.push_back(a);
     }
     const bool tradeoff = !thetas.empty();
+    if (among || ecfile || negatives >= 0 || have_seed) {          // (the filtered evaluation: --eval's flow with a filter)
+        if (!edir) { fprintf(stderr, "--among, --eval-candidates, --negatives and --seed go with --eval\n"); return 1; }
+        if (ifile || fdir || rdir || ndir || diversity || mmr || tradeoff) {
+            fprintf(stderr, "--among, --eval-candidates and --negatives do not go with --fold-in*, --diversity, --mmr or --tradeoff\n");
+            return 1;
+        }
+        if (negatives >= 0 && ecfile) { fprintf(stderr, "--negatives does not go with --eval-candidates\n"); return 1; }
+        if (have_seed && negatives < 0) { fprintf(stderr, "--seed goes with --negatives\n"); return 1; }
+    }
     if (ifile) {                                                   // (a mode of its own: it writes a model, no lists)
         if (fdir || rdir || ndir) { fprintf(stderr, "--fold-in-items does not go with --fold-in, --fold-in-ridge or --fold-in-nnls\n"); return 1; }
         if (edir || diversity || mmr || tradeoff || with_ranks || afile || cfile) {
@@ -745,7 +816,7 @@ int main(int argc, char** argv) {
     if (edir) {
         if (cuts.empty()) cuts.push_back(K);
         const int rc = run_eval(edir, U, V, d1, d2, k, xdir ? &xindex : nullptr, xdir ? &xitem : nullptr, cuts, threshold, f32,
-                                with_ranks, pos.size() == 2 ? pos[1] : nullptr);
+                                with_ranks, pos.size() == 2 ? pos[1] : nullptr, among, ecfile, negatives, seed);
         if (rc) return rc;
         fflush(stdout); fflush(stderr);
         _exit(0);

@@ -362,7 +362,7 @@ extern "C" int pcr_dataset_from_csr(int64_t d1, int64_t d2, const int64_t* index
 static std::map<std::string, std::string>& tune_table() { static thread_local std::map<std::string, std::string> t; return t; }
 static const char* const TUNE_KEYS[] = {"ustep_mode", "cluster_k", "cluster_users", "ubins", "ustep_gram", "spmm_tiles", "spmm_chunk", "sddmm_csc",
                                         "lanes", "pipeline", "window_cache", "prepare_merged", "resort_window", "allreduce_chunks", "p2p_ll",
-                                        "p2p_timeout_ms", "p2p_queue_budget", "count_rows", "debug", "win16", "ustep_win_lds", "plan_key64", "ustep_newton", "vblock_users", "recommend_select", "ranks_batch_users", "rerank_lds", "ridge_form", "nnls_form", "itemfold_table_bytes", "fault_cluster_member", "fault_p2p_skip", "fault_p2p_coarse", nullptr};
+                                        "p2p_timeout_ms", "p2p_queue_budget", "count_rows", "debug", "win16", "ustep_win_lds", "plan_key64", "ustep_newton", "vblock_users", "recommend_select", "ranks_batch_users", "sample_threads", "rerank_lds", "ridge_form", "nnls_form", "itemfold_table_bytes", "fault_cluster_member", "fault_p2p_skip", "fault_p2p_coarse", nullptr};
 extern "C" int pcr_tune(const char* key, const char* value) {
     if (!key) { pcr_set_error("pcr_tune: null key"); return PCR_ERR_ARG; }
     bool known = false;
@@ -1170,25 +1170,24 @@ static int test_csr_check(const char* who, int64_t d1, int64_t d2, const int64_t
 
 int pcr_evaluate_topn_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
                                   const int32_t* item, const int64_t* tindex, const int32_t* titem, const double* tval, int ncut,
-                                  const int* cutoffs, double threshold, int dtype, const pcr_topn_stats* stats, bool* sorted) {
-    int rc = pcr_topn_check("pcr_evaluate_topn_model", ncut, cutoffs, threshold, stats);
+                                  const int* cutoffs, double threshold, int dtype, const pcr_topn_stats* stats, bool* sorted,
+                                  const char* who) {
+    int rc = pcr_topn_check(who, ncut, cutoffs, threshold, stats);
     if (rc != PCR_OK) return rc;
-    rc = pcr_recommend_model_check(U, d1, V, d2, k, index, item, 0, nullptr, cutoffs[ncut - 1], dtype, nullptr, nullptr, sorted,
-                                             "pcr_evaluate_topn_model");
+    rc = pcr_recommend_model_check(U, d1, V, d2, k, index, item, 0, nullptr, cutoffs[ncut - 1], dtype, nullptr, nullptr, sorted, who);
     if (rc != PCR_OK) return rc;
-    return test_csr_check("pcr_evaluate_topn_model", d1, d2, tindex, titem, tval);
+    return test_csr_check(who, d1, d2, tindex, titem, tval);
 }
 
 int pcr_evaluate_ranks_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
                                    const int32_t* item, const int64_t* tindex, const int32_t* titem, const double* tval,
-                                   double threshold, int dtype, const pcr_rank_stats* stats, bool* sorted) {
-    auto bad = [](const std::string& why) { pcr_set_error("pcr_evaluate_ranks_model: " + why); return PCR_ERR_ARG; };
+                                   double threshold, int dtype, const pcr_rank_stats* stats, bool* sorted, const char* who) {
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
     if (std::isnan(threshold)) return bad("threshold is NaN");
     if (!stats) return bad("null stats");
-    const int rc = pcr_recommend_model_check(U, d1, V, d2, k, index, item, 0, nullptr, 1, dtype, nullptr, nullptr, sorted,
-                                             "pcr_evaluate_ranks_model");
+    const int rc = pcr_recommend_model_check(U, d1, V, d2, k, index, item, 0, nullptr, 1, dtype, nullptr, nullptr, sorted, who);
     if (rc != PCR_OK) return rc;
-    return test_csr_check("pcr_evaluate_ranks_model", d1, d2, tindex, titem, tval);
+    return test_csr_check(who, d1, d2, tindex, titem, tval);
 }
 
 void pcr_topn_relevance(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, double threshold, int ncut,
@@ -1282,6 +1281,133 @@ void pcr_rank_scatter(int64_t rows, const int64_t* tptr, const int32_t* titem, c
                 if (tval[z] >= threshold) ranks[z] = rrank[std::lower_bound(rb, re, titem[z]) - rel.ritem.data()];
         }
     });
+}
+
+// ------------------------------------------------------------------------------ filtered evaluation (include/primalcr.h)
+int pcr_eval_filter_check(const char* who, const char* unfiltered, int64_t d2, int64_t rows, const pcr_item_filter* f) {
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
+    if (!f) return bad(std::string("null filter (") + unfiltered + " is the entry without one)");
+    if (!f->allow && !f->cand_ptr)
+        return bad(std::string("a filter without an allow set and without candidate lists (") + unfiltered + " is the entry without one)");
+    return pcr_item_filter_check(who, d2, rows, nullptr, f);
+}
+
+void pcr_filter_test_rows(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, const pcr_item_filter& f,
+                          PcrFilteredTest& out) {
+    const int nth = pcr_host_threads();
+    std::vector<PcrFilteredTest> parts((size_t)nth);
+    std::vector<int64_t> len((size_t)rows, 0);
+    pcr_parallel_ranges(rows, nth, [&](int t, int64_t lo, int64_t hi) {
+        PcrFilteredTest& P = parts[(size_t)t];
+        std::vector<int32_t> row;
+        for (int64_t u = lo; u < hi; ++u) {
+            if (tptr[u + 1] == tptr[u]) continue;
+            if (f.cand_ptr) {
+                row.assign(f.cand_item + f.cand_ptr[u], f.cand_item + f.cand_ptr[u + 1]);
+                std::sort(row.begin(), row.end());
+            }
+            for (int64_t z = tptr[u]; z < tptr[u + 1]; ++z) {
+                const int32_t j = titem[z];
+                if (f.allow && !f.allow[j]) continue;
+                if (f.cand_ptr && !std::binary_search(row.begin(), row.end(), j)) continue;
+                P.item.push_back(j); P.val.push_back(tval[z]); P.pos.push_back(z);
+                ++len[(size_t)u];
+            }
+        }
+    });
+    out.ptr.assign((size_t)rows + 1, 0);
+    for (int64_t u = 0; u < rows; ++u) out.ptr[(size_t)u + 1] = out.ptr[(size_t)u] + len[(size_t)u];
+    out.item.clear(); out.val.clear(); out.pos.clear();
+    for (const PcrFilteredTest& P : parts) {           // (contiguous user ranges, concatenated in order)
+        out.item.insert(out.item.end(), P.item.begin(), P.item.end());
+        out.val.insert(out.val.end(), P.val.begin(), P.val.end());
+        out.pos.insert(out.pos.end(), P.pos.begin(), P.pos.end());
+    }
+}
+
+static inline uint64_t sample_mix(uint64_t x) {
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
+    return x;
+}
+// The row of one user (include/primalcr.h, pcr_sample_negatives): its length, and with dst != NULL the row itself, ascending, at
+// dst.  The length needs no draw -- min(n_neg, |P_u|) negatives and, with include_test, the distinct test items -- so a call that
+// only sizes the rows samples nothing.  `ex`, `test` and `drawn` are scratch.
+static int64_t sample_row(int64_t d2, const int32_t* tr, int64_t ntr, const int32_t* te, int64_t nte, uint64_t user, int64_t n_neg, uint64_t seed,
+                          bool include_test, std::vector<int32_t>& ex, std::vector<int32_t>& test, std::vector<int32_t>& drawn, int32_t* dst) {
+    if (nte == 0) return 0;
+    test.assign(te, te + nte);
+    std::sort(test.begin(), test.end());
+    test.erase(std::unique(test.begin(), test.end()), test.end());
+    ex.assign(tr, tr + ntr);
+    ex.insert(ex.end(), test.begin(), test.end());
+    std::sort(ex.begin(), ex.end());
+    ex.erase(std::unique(ex.begin(), ex.end()), ex.end());          // the items outside the pool, ascending
+    const int64_t pool = d2 - (int64_t)ex.size(), m = std::min(n_neg, pool);
+    const int64_t len = m + (include_test ? (int64_t)test.size() : 0);
+    if (!dst) return len;
+    const bool whole = m == pool, keep = 2 * m <= pool;
+    const int64_t want = whole ? 0 : keep ? m : pool - m;           // distinct draws inside the pool
+    drawn.clear();
+    const uint64_t golden = 0x9E3779B97F4A7C15ull, key = sample_mix(seed + golden * (user + 1));
+    for (uint64_t t = 0; (int64_t)drawn.size() < want; ++t) {
+        const int32_t j = (int32_t)(sample_mix(key + golden * (t + 1)) % (uint64_t)d2);
+        if (std::binary_search(ex.begin(), ex.end(), j)) continue;
+        const auto it = std::lower_bound(drawn.begin(), drawn.end(), j);
+        if (it != drawn.end() && *it == j) continue;
+        drawn.insert(it, j);
+    }
+    if (whole || !keep) {                                           // the pool, without the draws that are left out
+        size_t e = 0, d = 0;
+        for (int64_t j = 0; j < d2; ++j) {
+            while (e < ex.size() && ex[e] < j) ++e;
+            while (d < drawn.size() && drawn[d] < j) ++d;
+            const bool is_ex = e < ex.size() && ex[e] == j, is_dr = d < drawn.size() && drawn[d] == j;
+            if (!is_ex && !is_dr) *dst++ = (int32_t)j;
+            else if (is_ex && include_test && std::binary_search(test.begin(), test.end(), (int32_t)j)) *dst++ = (int32_t)j;
+        }
+        return len;
+    }
+    if (include_test) std::merge(drawn.begin(), drawn.end(), test.begin(), test.end(), dst);
+    else std::copy(drawn.begin(), drawn.end(), dst);
+    return len;
+}
+
+extern "C" int pcr_sample_negatives(int64_t rows, int64_t d2, const int64_t* index, const int32_t* item, const int64_t* tindex,
+                                    const int32_t* titem, int64_t first_user, int64_t n_neg, uint64_t seed, int include_test,
+                                    int64_t* cand_ptr, int32_t* cand_item) {
+    auto bad = [](const std::string& why) { pcr_set_error("pcr_sample_negatives: " + why); return PCR_ERR_ARG; };
+    try {
+        if (rows < 0 || d2 < 1 || first_user < 0 || n_neg < 0 || !cand_ptr) return bad("bad argument");
+        if (d2 >= ((int64_t)1 << 31) - 64) return bad("more than 2^31 items");
+        if ((index == nullptr) != (item == nullptr)) return bad("index and item go together");
+        if (!tindex || (tindex[rows] > 0 && !titem)) return bad("null test CSR");
+        if (tindex[0] != 0 || (index && index[0] != 0)) return bad("index[0] and tindex[0] must be 0");
+        for (int64_t u = 0; u < rows; ++u) {
+            if (tindex[u + 1] < tindex[u]) return bad("tindex not monotone at row " + std::to_string(u));
+            if (index && index[u + 1] < index[u]) return bad("index not monotone at row " + std::to_string(u));
+        }
+        for (int64_t z = 0; z < tindex[rows]; ++z) if (titem[z] < 0 || titem[z] >= d2) return bad("an item id of the test CSR is outside [0, d2)");
+        if (index) for (int64_t z = 0; z < index[rows]; ++z) if (item[z] < 0 || item[z] >= d2) return bad("an item id of the training CSR is outside [0, d2)");
+        const int knob = pcr_tune_int("sample_threads", 0), nth = knob > 0 ? knob : pcr_host_threads();
+        // a row is a function of its own user alone.  Pass 1 sizes the rows without a draw and makes the pointer; pass 2 (with
+        // cand_item) writes each row where the pointer puts it
+        auto pass = [&](int32_t* out) {
+            pcr_parallel_ranges(rows, nth, [&](int, int64_t lo, int64_t hi) {
+                std::vector<int32_t> ex, test, drawn;
+                for (int64_t u = lo; u < hi; ++u) {
+                    const int64_t len = sample_row(d2, index ? item + index[u] : nullptr, index ? index[u + 1] - index[u] : 0, titem + tindex[u],
+                                                   tindex[u + 1] - tindex[u], (uint64_t)(first_user + u), n_neg, seed, include_test != 0, ex, test,
+                                                   drawn, out ? out + cand_ptr[u] : nullptr);
+                    if (!out) cand_ptr[u + 1] = len;
+                }
+            });
+        };
+        pass(nullptr);
+        cand_ptr[0] = 0;
+        for (int64_t u = 0; u < rows; ++u) cand_ptr[u + 1] += cand_ptr[u];
+        if (cand_item) pass(cand_item);
+        return PCR_OK;
+    } catch (const std::bad_alloc&) { pcr_set_error("pcr_sample_negatives: out of host memory"); return PCR_ERR_NOMEM; }
 }
 
 // ------------------------------------------------------------------------------ beyond-accuracy metrics (include/primalcr.h)

@@ -92,7 +92,8 @@ int pcr_topn_check(const char* who, int ncut, const int* cutoffs, double thresho
 // pcr_recommend_model, pcr_topn_check and the test CSR's shape.  *sorted as pcr_recommend_model_check.
 int pcr_evaluate_topn_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
                                   const int32_t* item, const int64_t* tindex, const int32_t* titem, const double* tval, int ncut,
-                                  const int* cutoffs, double threshold, int dtype, const pcr_topn_stats* stats, bool* sorted);
+                                  const int* cutoffs, double threshold, int dtype, const pcr_topn_stats* stats, bool* sorted,
+                                  const char* who = "pcr_evaluate_topn_model");
 
 // Top-N evaluation's relevance tables (include/primalcr.h, "full-catalogue top-N evaluation") of rows [0, rows) of a test CSR
 // (tptr[rows + 1] relative, items in any order): the counted users (|R_u| >= 1, ascending), their relevant rows (distinct items
@@ -139,7 +140,8 @@ int pcr_diversity_stats_from(const double* sums, int ncut, const int* cutoffs, c
 // factor / exclusion checks of pcr_recommend_model and the test CSR's shape.  *sorted as pcr_recommend_model_check.
 int pcr_evaluate_ranks_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
                                    const int32_t* item, const int64_t* tindex, const int32_t* titem, const double* tval,
-                                   double threshold, int dtype, const pcr_rank_stats* stats, bool* sorted);
+                                   double threshold, int dtype, const pcr_rank_stats* stats, bool* sorted,
+                                   const char* who = "pcr_evaluate_ranks_model");
 // stats from the reduced sums of k_rank_finish's rows (k_topn_fin's layout with one cutoff: |R_u|, rr, mean_rank, users, mpr,
 // first_rank, auc, users_auc summed, then the counted users)
 void pcr_rank_stats_from(const double* sums, pcr_rank_stats* stats);
@@ -147,6 +149,22 @@ void pcr_rank_stats_from(const double* sums, pcr_rank_stats* stats);
 // tval[z] >= threshold, 0 elsewhere
 void pcr_rank_scatter(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, double threshold,
                       const PcrTopnRel& rel, const int64_t* rrank, int64_t* ranks);
+
+// Filtered evaluation (include/primalcr.h, "filtered evaluation").
+// The filter of a filtered evaluation entry over `rows` users: f != NULL with an allow set or candidate rows (neither: the
+// message points to `unfiltered`), then pcr_item_filter_check as it is, with rows 0 .. rows - 1.
+int pcr_eval_filter_check(const char* who, const char* unfiltered, int64_t d2, int64_t rows, const pcr_item_filter* f);
+// Rows [0, rows) of a test CSR restricted to F_u: the ratings whose item passes f's allow set and sits in the user's candidate
+// row (a sorted copy of the row makes the membership test), in their order; pos[z'] is where rating z' stood in the test CSR.
+// pcr_topn_relevance over this CSR gives R_u^f.
+struct PcrFilteredTest {
+    std::vector<int64_t> ptr;        // rows + 1
+    std::vector<int32_t> item;
+    std::vector<double> val;
+    std::vector<int64_t> pos;
+};
+void pcr_filter_test_rows(int64_t rows, const int64_t* tptr, const int32_t* titem, const double* tval, const pcr_item_filter& f,
+                          PcrFilteredTest& out);
 
 // Metrics of device-resident lists (include/primalcr.h, "evaluating given and re-ranked lists").
 // lists[n][L] as pcr_evaluate_lists_model takes them: every entry -1 or inside [0, d2), no entry after a -1, no id twice in a

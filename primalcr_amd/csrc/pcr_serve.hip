@@ -133,7 +133,7 @@ static int cand_run(const ServeView& v, int64_t n, const int32_t* h_users, const
     DBuf<double> os;
     RC(du.alloc((size_t)nb)); RC(dp.alloc((size_t)nb + 1)); RC(oi.alloc((size_t)nb * K)); RC(os.alloc((size_t)nb * K));
     const size_t lds = cand_wave_lds<T>(K) * 4;
-    HIPCHK(hipFuncSetAttribute((const void*)k_rec_cand<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_rec_cand<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     std::vector<int32_t> seq;
     for (int64_t b0 = 0; b0 < n;) {
         int64_t m = 1;
@@ -147,8 +147,9 @@ static int cand_run(const ServeView& v, int64_t n, const int32_t* h_users, const
         if (nc > 0) HIPCHK(hipMemcpyAsync(dc.p, citem + cptr[b0], (size_t)nc * sizeof(int32_t), hipMemcpyHostToDevice, st));
         {
             ProfScope ps(v.prof, "recommend/candidates", st);
-            hipLaunchKernelGGL((k_rec_cand<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), lds, st, serve_U<T>(v), serve_V<T>(v), v.r, v.ld,
-                               (const int32_t*)du.p, m, (const int64_t*)dp.p, (const int32_t*)dc.p, v.allow, v.xptr(), v.xitem(), K, oi.p, os.p);
+            hipLaunchKernelGGL((k_rec_cand<T, false>), dim3((unsigned)cdiv(m, 4)), dim3(256), lds, st, serve_U<T>(v), serve_V<T>(v), v.r, v.ld,
+                               (const int32_t*)du.p, m, (const int64_t*)dp.p, (const int32_t*)dc.p, v.allow, v.xptr(), v.xitem(), K, oi.p, os.p,
+                               TopnArgs{});
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipMemcpyAsync(items + b0 * K, oi.p, (size_t)m * K * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -211,6 +212,14 @@ struct TopnDev {
         valid = true;
         return PCR_OK;
     }
+    // the tables and the output rows of the batch of counted users that starts at b0, for a kernel that counts from 0
+    TopnArgs args(int64_t b0) const {
+        TopnArgs ta;
+        ta.rptr = rptr.p + b0; ta.ritem = ritem.p; ta.rgain = rgain.p; ta.idcg = idcg.p + (size_t)b0 * ncut * 2;
+        ta.disc = disc.p; ta.out = met.p + (size_t)b0 * ncut * 6; ta.ncut = ncut;
+        fill_cuts(ta.cut, ncut, cut);
+        return ta;
+    }
     // The end of an evaluation, after rec_run: met_sums over the counted users ("recommend/metrics") into stats; with per_user,
     // per_user[rows][ncut][6]: NaN, then the counted users' rows
     int finish(const ServeView& v, pcr_topn_stats* stats, double* per_user) {
@@ -236,10 +245,7 @@ struct RecTopn {
     TopnDev& d;
     int begin(int64_t) { return PCR_OK; }
     int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp) {
-        TopnArgs ta;
-        ta.rptr = d.rptr.p + b0; ta.ritem = d.ritem.p; ta.rgain = d.rgain.p; ta.idcg = d.idcg.p + (size_t)b0 * d.ncut * 2;
-        ta.disc = d.disc.p; ta.out = d.met.p + (size_t)b0 * d.ncut * 6; ta.ncut = d.ncut;
-        fill_cuts(ta.cut, d.ncut, d.cut);
+        const TopnArgs ta = d.args(b0);
         ProfScope ps(v.prof, "recommend/metrics", v.st);
         hipLaunchKernelGGL((k_rec_merge_topn<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), (size_t)4 * K * sizeof(int32_t), v.st, ls, li, ln, nsp, m, K, ta);
         HIPCHK(hipGetLastError());
@@ -657,10 +663,25 @@ struct RankDev {
     }
 };
 
+// the relevant items' scores and their sort for all counted users of d ("ranks/relscore"): rs / ri the sorted rows, d.rslot
+template <typename T>
+static int rank_relsort(const ServeView& v, RankDev& d, DBuf<T>& us, DBuf<T>& rs, DBuf<int32_t>& ri) {
+    hipStream_t st = v.st;
+    const int64_t n = (int64_t)d.rel.users.size(), nrel = (int64_t)d.rel.ritem.size();
+    RC(us.alloc((size_t)nrel)); RC(rs.alloc((size_t)nrel)); RC(ri.alloc((size_t)nrel));
+    ProfScope ps(v.prof, "ranks/relscore", st);
+    hipLaunchKernelGGL((k_rank_relscore<T>), dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, serve_U<T>(v), serve_V<T>(v), v.r, v.ld,
+                       (const int32_t*)d.users.p, n, (const int64_t*)d.rptr.p, (const int32_t*)d.ritem.p, us.p);
+    hipLaunchKernelGGL((k_rank_sort<T>), dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, n, (const int64_t*)d.rptr.p, (const int32_t*)d.ritem.p,
+                       (const T*)us.p, rs.p, ri.p, d.rslot.p);
+    HIPCHK(hipGetLastError());
+    return PCR_OK;
+}
+
 // The rank metrics' sweep for the counted users of d (rows of U and of the exclusion CSR, as rec_run): the relevant items'
 // scores and their sort once for all users ("ranks/relscore"), then per user batch (RecGeom, the scratch being the splits'
 // histograms: |R_u| + 1 counters per user) the counting sweep ("ranks/count") and the scan ("ranks/finish") into d.rrank / d.met.
-// pcr_tune("ranks_batch_users") is read at every call.
+// pcr_tune("ranks_batch_users") is read at every call.  v.allow (NULL but in a filtered call) goes to the counting sweep as it is.
 template <typename T>
 static int rank_run(const ServeView& v, RankDev& d) {
     hipStream_t st = v.st; const T *U = serve_U<T>(v), *V = serve_V<T>(v);
@@ -669,15 +690,7 @@ static int rank_run(const ServeView& v, RankDev& d) {
     if (n <= 0) return PCR_OK;
     DBuf<T> us, rs;
     DBuf<int32_t> ri, hist;
-    RC(us.alloc((size_t)nrel)); RC(rs.alloc((size_t)nrel)); RC(ri.alloc((size_t)nrel));
-    {
-        ProfScope ps(v.prof, "ranks/relscore", st);
-        hipLaunchKernelGGL((k_rank_relscore<T>), dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, U, V, r, ld, (const int32_t*)d.users.p, n,
-                           (const int64_t*)d.rptr.p, (const int32_t*)d.ritem.p, us.p);
-        hipLaunchKernelGGL((k_rank_sort<T>), dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, n, (const int64_t*)d.rptr.p, (const int32_t*)d.ritem.p,
-                           (const T*)us.p, rs.p, ri.p, d.rslot.p);
-        HIPCHK(hipGetLastError());
-    }
+    RC(rank_relsort<T>(v, d, us, rs, ri));
     RecGeom geom(n, d2, sizeof(int32_t) * (size_t)((nrel + n + n - 1) / n));
     const int64_t cap = pcr_tune_int("ranks_batch_users", 0);
     if (cap > 0) {
@@ -699,7 +712,7 @@ static int rank_run(const ServeView& v, RankDev& d) {
             HIPCHK(hipMemsetAsync(hist.p, 0, (size_t)nsp * (size_t)hsplit * sizeof(int32_t), st));
             hipLaunchKernelGGL((k_rank_count<T>), dim3((unsigned)cdiv(m, RecGeom::users_per_wg), (unsigned)nsp), dim3(rec::WAVES * 64), lds, st, U, V,
                                r, ld, (int)d2, (const int32_t*)d.users.p + b0, m, v.xptr(), v.xitem(), per, (const int64_t*)d.rptr.p + b0, (const T*)rs.p,
-                               (const int32_t*)ri.p, hist.p, hsplit);
+                               (const int32_t*)ri.p, hist.p, hsplit, v.allow);
             HIPCHK(hipGetLastError());
         }
         ProfScope ps(v.prof, "ranks/finish", st);
@@ -707,6 +720,99 @@ static int rank_run(const ServeView& v, RankDev& d) {
                            (const int64_t*)d.rptr.p + b0, (const int32_t*)d.rslot.p, d.rrank.p, d.met.p + (size_t)b0 * 6);
         HIPCHK(hipGetLastError());
     }
+    HIPCHK(hipStreamSynchronize(st));                      // (us / rs / ri / hist are freed on return)
+    return PCR_OK;
+}
+
+// Filtered evaluation with candidate rows: the batches of cand_run over the candidate rows of the counted
+// users `users` (ascending rows of f's candidate CSR, and of v's U and exclusion CSR).  A batch uploads its users, its rows'
+// pointers (absolute values: the kernels subtract the first) and its candidates -- straight from the caller's arrays when the
+// batch's users are consecutive rows, which every batch is when all users are counted; gathered into a staging row otherwise --
+// then launch(b0, m, users, cptr, citem) -- device pointers, counted from the batch's start -- queues the batch's kernels; the
+// stream is synchronised before the next batch overwrites the uploads.
+template <class Launch>
+static int cand_batches(const ServeView& v, const std::vector<int32_t>& users, const pcr_item_filter& f, int64_t nb, Launch&& launch) {
+    hipStream_t st = v.st;
+    const int64_t n = (int64_t)users.size();
+    const int64_t* cp = f.cand_ptr;
+    auto len = [&](int64_t i) { return cp[users[(size_t)i] + 1] - cp[users[(size_t)i]]; };
+    nb = std::min(n, std::max<int64_t>(4, nb));
+    DBuf<int32_t> du, dc;
+    DBuf<int64_t> dp;
+    RC(du.alloc((size_t)nb)); RC(dp.alloc((size_t)nb + 1));
+    std::vector<int64_t> bptr;
+    std::vector<int32_t> stage;
+    for (int64_t b0 = 0; b0 < n;) {
+        int64_t m = 1, nc = len(b0);
+        while (m < nb && b0 + m < n && nc + len(b0 + m) <= CAND_ITEMS) { nc += len(b0 + m); ++m; }
+        const int64_t* hp = cp + users[(size_t)b0];
+        const int32_t* hc = f.cand_item + cp[users[(size_t)b0]];
+        if ((int64_t)users[(size_t)(b0 + m - 1)] - users[(size_t)b0] != m - 1) {       // rows with gaps between them
+            bptr.resize((size_t)m + 1); stage.resize((size_t)nc);
+            bptr[0] = 0;
+            for (int64_t i = 0; i < m; ++i) bptr[(size_t)i + 1] = bptr[(size_t)i] + len(b0 + i);
+            pcr_parallel_ranges(m, pcr_host_threads(), [&](int, int64_t lo, int64_t hi) {
+                for (int64_t i = lo; i < hi; ++i) {
+                    const int32_t* row = f.cand_item + cp[users[(size_t)(b0 + i)]];
+                    std::copy(row, row + len(b0 + i), stage.begin() + bptr[(size_t)i]);
+                }
+            });
+            hp = bptr.data(); hc = stage.data();
+        }
+        if (dc.n < (size_t)nc) RC(dc.alloc((size_t)nc));
+        HIPCHK(hipMemcpyAsync(du.p, users.data() + b0, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(dp.p, hp, (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        if (nc > 0) HIPCHK(hipMemcpyAsync(dc.p, hc, (size_t)nc * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        RC(launch(b0, m, (const int32_t*)du.p, (const int64_t*)dp.p, (const int32_t*)dc.p));
+        HIPCHK(hipStreamSynchronize(st));
+        b0 += m;
+    }
+    return PCR_OK;
+}
+
+// top-N within candidate rows: k_rec_cand's selection with the metrics tail, one launch per batch ("recommend/candidates_metrics"),
+// into d.met at the batch's rows; no list leaves the device
+template <typename T>
+static int cand_topn_run(const ServeView& v, TopnDev& d, int K, const pcr_item_filter& f) {
+    if (d.rel.users.empty()) return PCR_OK;
+    const size_t lds = cand_wave_lds<T>(K) * 4;
+    HIPCHK(hipFuncSetAttribute((const void*)k_rec_cand<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return cand_batches(v, d.rel.users, f, CAND_BATCH / K, [&](int64_t b0, int64_t m, const int32_t* du, const int64_t* dp, const int32_t* dc) -> int {
+        ProfScope ps(v.prof, "recommend/candidates_metrics", v.st);
+        hipLaunchKernelGGL((k_rec_cand<T, true>), dim3((unsigned)cdiv(m, 4)), dim3(256), lds, v.st, serve_U<T>(v), serve_V<T>(v), v.r, v.ld, du, m, dp, dc,
+                           v.allow, v.xptr(), v.xitem(), K, (int32_t*)nullptr, (double*)nullptr, d.args(b0));
+        HIPCHK(hipGetLastError());
+        return PCR_OK;
+    });
+}
+
+// rank metrics within candidate rows: rank_run with k_cand_count ("ranks/candidates") in place of the counting sweep -- one split,
+// the batch's histogram zeroed before it, k_rank_finish ("ranks/finish") unchanged behind it
+template <typename T>
+static int cand_rank_run(const ServeView& v, RankDev& d, const pcr_item_filter& f) {
+    hipStream_t st = v.st;
+    const int64_t n = (int64_t)d.rel.users.size();
+    if (n <= 0) return PCR_OK;
+    DBuf<T> us, rs;
+    DBuf<int32_t> ri, hist;
+    RC(rank_relsort<T>(v, d, us, rs, ri));
+    const std::vector<int64_t>& rp = d.rel.rptr;
+    RC(cand_batches(v, d.rel.users, f, CAND_BATCH, [&](int64_t b0, int64_t m, const int32_t* du, const int64_t* dp, const int32_t* dc) -> int {
+        const int64_t hsplit = rp[(size_t)(b0 + m)] - rp[(size_t)b0] + m;
+        if (hist.n < (size_t)hsplit) RC(hist.alloc((size_t)hsplit));
+        {
+            ProfScope ps(v.prof, "ranks/candidates", st);
+            HIPCHK(hipMemsetAsync(hist.p, 0, (size_t)hsplit * sizeof(int32_t), st));
+            hipLaunchKernelGGL((k_cand_count<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), 0, st, serve_U<T>(v), serve_V<T>(v), v.r, v.ld, du, m, dp, dc,
+                               v.allow, v.xptr(), v.xitem(), (const int64_t*)d.rptr.p + b0, (const T*)rs.p, (const int32_t*)ri.p, hist.p);
+            HIPCHK(hipGetLastError());
+        }
+        ProfScope ps(v.prof, "ranks/finish", st);
+        hipLaunchKernelGGL(k_rank_finish, dim3((unsigned)cdiv(m, 4)), dim3(256), 0, st, (const int32_t*)hist.p, hsplit, 1, m,
+                           (const int64_t*)d.rptr.p + b0, (const int32_t*)d.rslot.p, d.rrank.p, d.met.p + (size_t)b0 * 6);
+        HIPCHK(hipGetLastError());
+        return PCR_OK;
+    }));
     HIPCHK(hipStreamSynchronize(st));                      // (us / rs / ri / hist are freed on return)
     return PCR_OK;
 }
@@ -720,15 +826,18 @@ static int serve_recommend(const ServeView& v, int64_t n, const int32_t* rows, i
 }
 // filtered lists (pcr_recommend_filtered): the allow set is packed into 64-bit words (bit j & 63 of word
 // j >> 6) and hung on the view for this call; candidate lists take k_rec_cand alone, an allow set alone the sweep
+static int pack_allow(ServeView& v, const pcr_item_filter& f, DBuf<unsigned long long>& aw) {
+    if (!f.allow) return PCR_OK;
+    std::vector<unsigned long long> w((size_t)((v.d2 + 63) >> 6), 0ull);
+    for (int64_t j = 0; j < v.d2; ++j) if (f.allow[j]) w[(size_t)(j >> 6)] |= 1ull << (j & 63);
+    RC(aw.upload(w, v.st));
+    v.allow = aw.p;
+    return PCR_OK;
+}
 static int serve_recommend_filtered(ServeView v, int64_t n, const int32_t* rows, int K, const pcr_item_filter& f, int32_t* items, double* scores) {
     if (n <= 0) return PCR_OK;
     DBuf<unsigned long long> aw;
-    if (f.allow) {
-        std::vector<unsigned long long> w((size_t)((v.d2 + 63) >> 6), 0ull);
-        for (int64_t j = 0; j < v.d2; ++j) if (f.allow[j]) w[(size_t)(j >> 6)] |= 1ull << (j & 63);
-        RC(aw.upload(w, v.st));
-        v.allow = aw.p;
-    }
+    RC(pack_allow(v, f, aw));
     return by_precision(v, [&](auto zero) -> int {
         using T = decltype(zero);
         if (f.cand_ptr) return cand_run<T>(v, n, rows, f.cand_ptr, f.cand_item, K, items, scores);
@@ -757,6 +866,46 @@ static int serve_ranks(const ServeView& v, RankDev& D, double thr, pcr_rank_stat
     if (!D.same(thr)) RC(D.build(v.rows, v.tptr, v.titem, v.tval, thr));
     RC(by_precision(v, [&](auto zero) -> int { return rank_run<decltype(zero)>(v, D); }));
     return D.finish(v, stats, per_user, ranks);
+}
+// The filtered evaluations (pcr_evaluate_topn_filtered, pcr_evaluate_ranks_filtered) of v's rows: the test
+// rows are restricted to F_u on the host (pcr_filter_test_rows) and the relevance tables built from them, per call, in tables of
+// the call's own -- a solver's cached unfiltered tables are not looked at.  An allow set alone takes the unfiltered sweeps with
+// the packed set on the view; candidate rows take k_rec_cand's metrics form and k_cand_count.  The reductions are the unfiltered ones.
+static int serve_topn_filtered(ServeView v, const pcr_item_filter& f, int ncut, const int* cuts, double thr, pcr_topn_stats* stats, double* per_user) {
+    DBuf<unsigned long long> aw;
+    RC(pack_allow(v, f, aw));
+    PcrFilteredTest ft;
+    pcr_filter_test_rows(v.rows, v.tptr, v.titem, v.tval, f, ft);
+    TopnDev D;
+    RC(D.build(v.rows, ft.ptr.data(), ft.item.data(), ft.val.data(), ncut, cuts, thr));
+    const int K = cuts[ncut - 1];
+    RC(by_precision(v, [&](auto zero) -> int {
+        using T = decltype(zero);
+        if (f.cand_ptr) return cand_topn_run<T>(v, D, K, f);
+        return rec_run<T>(v, (int64_t)D.rel.users.size(), D.rel.users.data(), K, 1, RecTopn<T>{v, K, D});
+    }));
+    return D.finish(v, stats, per_user);
+}
+static int serve_ranks_filtered(ServeView v, const pcr_item_filter& f, double thr, pcr_rank_stats* stats, double* per_user, int64_t* ranks) {
+    DBuf<unsigned long long> aw;
+    RC(pack_allow(v, f, aw));
+    PcrFilteredTest ft;
+    pcr_filter_test_rows(v.rows, v.tptr, v.titem, v.tval, f, ft);
+    const int64_t tnnz = v.tptr[v.rows];
+    v.tptr = ft.ptr.data(); v.titem = ft.item.data(); v.tval = ft.val.data();      // (RankDev::finish scatters over the rows it was built from)
+    RankDev D;
+    RC(D.build(v.rows, v.tptr, v.titem, v.tval, thr));
+    RC(by_precision(v, [&](auto zero) -> int {
+        using T = decltype(zero);
+        return f.cand_ptr ? cand_rank_run<T>(v, D, f) : rank_run<T>(v, D);
+    }));
+    std::vector<int64_t> fr(ranks ? ft.item.size() + 1 : 0);
+    RC(D.finish(v, stats, per_user, ranks ? fr.data() : nullptr));
+    if (ranks) {                                           // a rating outside F_u has rank 0
+        std::fill(ranks, ranks + tnnz, (int64_t)0);
+        for (size_t z = 0; z < ft.pos.size(); ++z) ranks[ft.pos[z]] = fr[z];
+    }
+    return PCR_OK;
 }
 // beyond-accuracy metrics of v's rows; the self-information table comes from the training ratings (summed across the ranks with
 // a communicator) and is kept in info: the ratings never change, the exchange mode can (info_mode 0: not built, 1: from this
@@ -1325,6 +1474,65 @@ int pcr_evaluate_ranks(pcr_solver* s, double threshold, int flags, pcr_rank_stat
     if (!stats) { pcr_set_error("pcr_evaluate_ranks: null stats"); return PCR_ERR_ARG; }
     if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_evaluate_ranks: unknown flags"); return PCR_ERR_ARG; }
     return abi_guard("pcr_evaluate_ranks", [&]() -> int { return serve_ranks(solver_view(s, flags), s->serve->rankd, threshold, stats, per_user, ranks); });
+}
+
+int pcr_evaluate_topn_filtered(pcr_solver* s, int ncut, const int* cutoffs, double threshold, int flags, const pcr_item_filter* f,
+                               pcr_topn_stats* stats, double* per_user) {
+    S_OR_ARG;
+    RC(pcr_topn_check("pcr_evaluate_topn_filtered", ncut, cutoffs, threshold, stats));
+    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_evaluate_topn_filtered: unknown flags"); return PCR_ERR_ARG; }
+    return abi_guard("pcr_evaluate_topn_filtered", [&]() -> int {
+        const ServeView v = solver_view(s, flags);
+        RC(pcr_eval_filter_check("pcr_evaluate_topn_filtered", "pcr_evaluate_topn", v.d2, v.rows, f));
+        return serve_topn_filtered(v, *f, ncut, cutoffs, threshold, stats, per_user);
+    });
+}
+
+int pcr_evaluate_ranks_filtered(pcr_solver* s, double threshold, int flags, const pcr_item_filter* f, pcr_rank_stats* stats, double* per_user,
+                                int64_t* ranks) {
+    S_OR_ARG;
+    if (std::isnan(threshold)) { pcr_set_error("pcr_evaluate_ranks_filtered: threshold is NaN"); return PCR_ERR_ARG; }
+    if (!stats) { pcr_set_error("pcr_evaluate_ranks_filtered: null stats"); return PCR_ERR_ARG; }
+    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_evaluate_ranks_filtered: unknown flags"); return PCR_ERR_ARG; }
+    return abi_guard("pcr_evaluate_ranks_filtered", [&]() -> int {
+        const ServeView v = solver_view(s, flags);
+        RC(pcr_eval_filter_check("pcr_evaluate_ranks_filtered", "pcr_evaluate_ranks", v.d2, v.rows, f));
+        return serve_ranks_filtered(v, *f, threshold, stats, per_user, ranks);
+    });
+}
+
+int pcr_evaluate_topn_filtered_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                                     const int64_t* tindex, const int32_t* titem, const double* tval, int ncut, const int* cutoffs,
+                                     double threshold, int dtype, const pcr_item_filter* f, pcr_topn_stats* stats, double* per_user, int device) {
+    return abi_guard("pcr_evaluate_topn_filtered_model", [&]() -> int {
+    bool sorted = true;
+    RC(pcr_evaluate_topn_model_check(U, d1, V, d2, k, index, item, tindex, titem, tval, ncut, cutoffs, threshold, dtype, stats, &sorted,
+                                     "pcr_evaluate_topn_filtered_model"));
+    RC(pcr_eval_filter_check("pcr_evaluate_topn_filtered_model", "pcr_evaluate_topn_model", d2, d1, f));
+    RC(model_device(device));
+    ServeView v;
+    v.tptr = tindex; v.titem = titem; v.tval = tval;
+    ModelDev M;
+    RC(M.open(U, d1, V, d2, k, index, item, sorted, dtype, &v));
+    return serve_topn_filtered(v, *f, ncut, cutoffs, threshold, stats, per_user);
+    });
+}
+
+int pcr_evaluate_ranks_filtered_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                                      const int64_t* tindex, const int32_t* titem, const double* tval, double threshold, int dtype,
+                                      const pcr_item_filter* f, pcr_rank_stats* stats, double* per_user, int64_t* ranks, int device) {
+    return abi_guard("pcr_evaluate_ranks_filtered_model", [&]() -> int {
+    bool sorted = true;
+    RC(pcr_evaluate_ranks_model_check(U, d1, V, d2, k, index, item, tindex, titem, tval, threshold, dtype, stats, &sorted,
+                                      "pcr_evaluate_ranks_filtered_model"));
+    RC(pcr_eval_filter_check("pcr_evaluate_ranks_filtered_model", "pcr_evaluate_ranks_model", d2, d1, f));
+    RC(model_device(device));
+    ServeView v;
+    v.tptr = tindex; v.titem = titem; v.tval = tval;
+    ModelDev M;
+    RC(M.open(U, d1, V, d2, k, index, item, sorted, dtype, &v));
+    return serve_ranks_filtered(v, *f, threshold, stats, per_user, ranks);
+    });
 }
 
 int pcr_recommend_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,

@@ -16,11 +16,14 @@
 //   section 3.17) the complement of the step's word of the packed set is ORed into that mask: one wave-uniform 8-byte load per step.
 // k_rec_merge: one wave per user merges the partial lists of the item splits by rank counting (binary searches into the other
 //   lists), converts the scores to double and pads with (-1, -inf).
-// k_rec_cand: top-K over a candidate list per user (pcr_recommend_filtered with cand_ptr), one wave per user, below k_rec_merge.
+// k_rec_cand: top-K over a candidate list per user (pcr_recommend_filtered with cand_ptr), one wave per user, below k_rec_merge;
+//   its TOPN instantiation keeps the list in LDS and scores it (pcr_evaluate_topn_filtered with cand_ptr; section 3.21).
 // k_rec_merge_topn: the same merge for the full-catalogue top-N evaluation (pcr_evaluate_topn): the list
 //   stays in LDS and is scored against the user's relevant test items; k_topn_sum1 / k_topn_fin reduce the per-user metrics.
 // k_rank_relscore / k_rank_sort / k_rank_count / k_rank_finish: the exact full-catalogue rank metrics (pcr_evaluate_ranks, DESIGN.md
 //   section 3.12): the same sweep with a counting tail in place of the selecting one, at the end of this file.
+// k_cand_count: that counting tail over a candidate row per user (pcr_evaluate_ranks_filtered with cand_ptr; section 3.21), one
+//   wave per user, below k_rank_count.
 // k_rec_merge_div / k_rec_merge_mmr: the same merge with the beyond-accuracy metrics (section 3.13) or the greedy MMR re-ranking
 //   (pcr_recommend_diverse, section 3.14) fused into its tail, further down in this file.
 // k_list_metrics: the two metric tails over a list that is already in device memory (pcr_evaluate_lists_model, and the theta sweep
@@ -39,6 +42,7 @@ constexpr int TILE = 16 * NQ; // items per step
 constexpr int CAP = 64;       // candidate slots per user; a merge is due when fewer than 16 are free
 constexpr int RANK_STAGE = 32;            // k_rank_count: relevant rows up to this length are staged (and counted) in LDS
 constexpr int RANK_LD = RANK_STAGE + 1;   // their LDS row stride (scores, ids, histogram): odd, see rank_wave_lds
+constexpr int CAND_STAGE = PCR_CAND_RANK_STAGE;   // k_cand_count: relevant rows up to this length are staged (and counted) in LDS
 }  // namespace rec
 
 template <typename T> struct RecMma;
@@ -282,6 +286,57 @@ __global__ __launch_bounds__(256) void k_rec_merge(const T* __restrict__ lst_s, 
     for (int p = min(tot, K) + lane; p < K; p += 64) { out_i[(size_t)idx * K + p] = -1; out_s[(size_t)idx * K + p] = -INFINITY; }
 }
 
+// Top-N evaluation (pcr_evaluate_topn): the relevance tables of the batch's users (offset to the batch), built on the host.
+struct TopnArgs {
+    const int64_t* rptr;   // [n + 1] relevant CSR: distinct items, item-ascending
+    const int32_t* ritem;
+    const double* rgain;   // graded gain of each relevant item
+    const double* idcg;    // [n][ncut][2] ideal DCG, binary then graded
+    const double* disc;    // [K] d(i) = 1 / log2(i + 2)
+    double* out;           // [n][ncut][6] hits, precision, recall, ap, ndcg, ndcg_graded
+    int ncut;
+    int cut[PCR_TOPN_MAX_CUTOFFS];
+};
+
+// One step of a candidate-row kernel (k_rec_cand, k_cand_count), the whole wave: candidates ci[t0 .. t0 + 64) of a row of nc ids
+// are scored against the one user row Ur through rec_score_tile -- all 16 columns of the tile are this user and column 0 is
+// read, as k_rank_relscore does, so a score has the bits k_rec_score gives the pair -- and handed to the lanes through the wave's
+// 64-entry LDS stage stg: lane `lane` gets candidate t0 + lane, its id (-1 past the row's end) and its score s.  Returns whether
+// the candidate is eligible: its bit of the packed allow set is on (allow NULL: every item) and a binary search does not find it
+// in the user's item-ascending training row xitem[xb, xe) (an empty range: no exclusion).  The caller orders the wave
+// (wave_sync) before the next step overwrites stg.  Both kernels score and filter through here, so they cannot drift apart.
+template <typename T>
+__device__ __forceinline__ bool cand_step(const T* __restrict__ Ur, const T* __restrict__ V, int r, int ld, const int32_t* __restrict__ ci,
+                                          int64_t nc, int64_t t0, int lane, T* stg, const unsigned long long* __restrict__ allow,
+                                          const int32_t* __restrict__ xitem, int64_t xb, int64_t xe, int& id, T& s) {
+    typedef RecMma<T> M;
+    typedef typename M::acc_t acc_t;
+    const int m = lane & 15, g = lane >> 4;
+    const int64_t t = t0 + lane;
+    id = t < nc ? (int)ci[t] : -1;
+    int jr[rec::NQ];
+#pragma unroll
+    for (int q = 0; q < rec::NQ; ++q) jr[q] = __shfl(id, 16 * q + m);
+    acc_t acc[rec::NQ];
+    rec_score_tile<T>(Ur, true, V, r, ld, g, [&](int q) { return jr[q]; }, acc);
+    if (m == 0) {
+#pragma unroll
+        for (int q = 0; q < rec::NQ; ++q)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) stg[16 * q + M::crow(j, lane)] = acc[q][j];
+    }
+    wave_sync();
+    s = stg[lane];
+    bool ok = id >= 0;
+    if (ok && allow) ok = ((allow[id >> 6] >> (id & 63)) & 1ull) != 0;
+    if (ok && xe > xb) {
+        int64_t a = xb, b = xe;
+        while (a < b) { const int64_t mid = (a + b) >> 1; if (xitem[mid] < id) a = mid + 1; else b = mid; }
+        ok = !(a < xe && xitem[a] == id);
+    }
+    return ok;
+}
+
 // LDS of one wave of k_rec_cand: the user's list scores [K], the survivor buffer's scores [CAP], the step's scores [TILE], the
 // list ids [K], the buffer ids [CAP]
 template <typename T>
@@ -292,7 +347,7 @@ __host__ __device__ inline size_t cand_wave_lds(int K) {
 
 // Top-K over candidate lists (pcr_recommend_filtered with cand_ptr), one wave per user, four users per
 // workgroup: row idx of the candidate CSR (cptr[n + 1] absolute, citem based at cptr[0]; ids in any order, none twice in a row)
-// belongs to users[idx].  Each step scores 64 candidates through rec_score_tile -- all 16 columns of the tile are this one user
+// belongs to users[idx].  Each step (cand_step, shared with k_cand_count) scores 64 candidates through rec_score_tile -- all 16 columns of the tile are this one user
 // and column 0 is read, as k_rank_relscore does, so a score has the bits k_rec_score gives the same (user, item) -- and hands
 // candidate t0 + lane to lane `lane` through LDS.  A candidate is eligible when its bit of the packed allow set is on (allow
 // NULL: every item) and a binary search does not find it in the user's item-ascending training row (xptr NULL: no exclusion).
@@ -304,14 +359,16 @@ __host__ __device__ inline size_t cand_wave_lds(int K) {
 // is read before it is written, and a chunk writes at or above its own positions only), then drops the buffer entries into
 // their ranks.  The ids of a row are distinct, so the order is strict and a list is the same whatever the order of the row.
 // The tail converts to double and pads with (-1, -inf).  Every loop is bounded by K, by 64 or by the row's length.
-template <typename T>
+// TOPN (pcr_evaluate_topn_filtered): the finished list is not written out; it is padded with -1 where it
+// stands, in the wave's LDS, and scored by rec_topn_tail against ta's relevance tables (offset to the batch, as k_rec_merge_topn's):
+// the selection above is the same code, so the list scored is the list the plain instantiation returns.
+__device__ __forceinline__ void rec_topn_tail(int32_t* sl, int K, int64_t idx, int lane, const TopnArgs& ta);   // (below)
+template <typename T, bool TOPN>
 __global__ __launch_bounds__(256) void k_rec_cand(const T* __restrict__ U, const T* __restrict__ V, int r, int ld,
                                                   const int32_t* __restrict__ users, int64_t n, const int64_t* __restrict__ cptr,
                                                   const int32_t* __restrict__ citem, const unsigned long long* __restrict__ allow,
                                                   const int64_t* __restrict__ xptr, const int32_t* __restrict__ xitem, int K,
-                                                  int32_t* __restrict__ out_i, double* __restrict__ out_s) {
-    typedef RecMma<T> M;
-    typedef typename M::acc_t acc_t;
+                                                  int32_t* __restrict__ out_i, double* __restrict__ out_s, TopnArgs ta) {
     extern __shared__ __align__(16) char rec_lds[];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t idx = (int64_t)blockIdx.x * 4 + w;
@@ -323,7 +380,6 @@ __global__ __launch_bounds__(256) void k_rec_cand(const T* __restrict__ U, const
     int* li = (int*)(stg + rec::TILE);
     int* bi = li + K;
 
-    const int m = lane & 15, g = lane >> 4;
     const int u = users[idx];
     const int64_t nc = cptr[idx + 1] - cptr[idx];
     const int32_t* ci = citem + (cptr[idx] - cptr[0]);
@@ -367,28 +423,9 @@ __global__ __launch_bounds__(256) void k_rec_cand(const T* __restrict__ U, const
     };
 
     for (int64_t t0 = 0; t0 < nc; t0 += rec::TILE) {
-        const int64_t t = t0 + lane;
-        const int id = t < nc ? (int)ci[t] : -1;
-        int jr[rec::NQ];
-#pragma unroll
-        for (int q = 0; q < rec::NQ; ++q) jr[q] = __shfl(id, 16 * q + m);
-        acc_t acc[rec::NQ];
-        rec_score_tile<T>(Ur, true, V, r, ld, g, [&](int q) { return jr[q]; }, acc);
-        if (m == 0) {
-#pragma unroll
-            for (int q = 0; q < rec::NQ; ++q)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) stg[16 * q + M::crow(j, lane)] = acc[q][j];
-        }
-        wave_sync();
-        const T s = stg[lane];
-        bool ok = id >= 0;
-        if (ok && allow) ok = ((allow[id >> 6] >> (id & 63)) & 1ull) != 0;
-        if (ok && xe > xb) {
-            int64_t a = xb, b = xe;
-            while (a < b) { const int64_t mid = (a + b) >> 1; if (xitem[mid] < id) a = mid + 1; else b = mid; }
-            ok = !(a < xe && xitem[a] == id);
-        }
+        int id;
+        T s;
+        bool ok = cand_step<T>(Ur, V, r, ld, ci, nc, t0, lane, stg, allow, xitem, xb, xe, id, s);
         ok = ok && rec_better(s, id, ts, ti);
         const unsigned long long pm = __ballot(ok);
         const int c = __popcll(pm);
@@ -402,24 +439,18 @@ __global__ __launch_bounds__(256) void k_rec_cand(const T* __restrict__ U, const
     }
     if (fill > 0) merge();
     wave_sync();
+    if (TOPN) {
+        for (int p = len + lane; p < K; p += 64) li[p] = -1;
+        wave_sync();
+        rec_topn_tail(li, K, idx, lane, ta);
+        return;
+    }
     for (int p = lane; p < K; p += 64) {
         const bool have = p < len;
         out_i[(size_t)idx * K + p] = have ? li[p] : -1;
         out_s[(size_t)idx * K + p] = have ? (double)ls[p] : -INFINITY;
     }
 }
-
-// Top-N evaluation (pcr_evaluate_topn): the relevance tables of the batch's users (offset to the batch), built on the host.
-struct TopnArgs {
-    const int64_t* rptr;   // [n + 1] relevant CSR: distinct items, item-ascending
-    const int32_t* ritem;
-    const double* rgain;   // graded gain of each relevant item
-    const double* idcg;    // [n][ncut][2] ideal DCG, binary then graded
-    const double* disc;    // [K] d(i) = 1 / log2(i + 2)
-    double* out;           // [n][ncut][6] hits, precision, recall, ap, ndcg, ndcg_graded
-    int ncut;
-    int cut[PCR_TOPN_MAX_CUTOFFS];
-};
 
 // k_rec_merge with the metrics fused into its tail, one wave per user: the merged list goes to the wave's LDS row (K ids; 4 K
 // ints of dynamic LDS per workgroup) and is never written out.  Lanes own contiguous position ranges; each list entry is
@@ -606,12 +637,15 @@ __device__ __forceinline__ int rank_bucket(const S s, const I id, int nr, T sc, 
 // global integer add.  An item that compares equal to a row entry (same score, same id) is a relevant item meeting itself and
 // is not counted.  Integer adds commute: the histogram is the same whatever the order of arrival.
 // hist: [split][hsplit] counters, zeroed by the caller; user idx's nr + 1 buckets start at (rptr[idx] - rptr[0]) + idx.
+// allow (pcr_evaluate_ranks_filtered; NULL: every item): the packed allow set, ORed complemented into the
+// step's exclusion mask exactly as k_rec_score does.
 template <typename T>
 __global__ __launch_bounds__(256) void k_rank_count(const T* __restrict__ U, const T* __restrict__ V, int r, int ld, int d2,
                                                     const int32_t* __restrict__ users, int64_t n,
                                                     const int64_t* __restrict__ xptr, const int32_t* __restrict__ xitem, int per_split,
                                                     const int64_t* __restrict__ rptr, const T* __restrict__ rs, const int32_t* __restrict__ ri,
-                                                    int32_t* __restrict__ hist, int64_t hsplit) {
+                                                    int32_t* __restrict__ hist, int64_t hsplit,
+                                                    const unsigned long long* __restrict__ allow) {
     typedef RecMma<T> M;
     typedef typename M::acc_t acc_t;
     extern __shared__ __align__(16) char rec_lds[];
@@ -665,6 +699,7 @@ __global__ __launch_bounds__(256) void k_rank_count(const T* __restrict__ U, con
             xm |= 1ull << (it - j0);
             ++cur;
         }
+        if (allow) xm |= ~allow[j0 >> 6];              // (as k_rec_score: the step is one word of the packed allow set)
 #pragma unroll
         for (int q = 0; q < rec::NQ; ++q) {
 #pragma unroll
@@ -695,6 +730,71 @@ __global__ __launch_bounds__(256) void k_rank_count(const T* __restrict__ U, con
         atomicAdd(&gh[0], c_lo);
         atomicAdd(&gh[nr], c_hi);
     }
+}
+
+// The counting tail over candidate rows (pcr_evaluate_ranks_filtered with cand_ptr), one wave per counted
+// user, four users per workgroup: row idx of the candidate CSR (cptr / citem as k_rec_cand's) belongs to users[idx].  A step scores
+// 64 candidates and hands candidate t0 + lane to lane `lane` through cand_step, the step k_rec_cand takes -- the bits k_rec_score,
+// k_rank_count and k_rank_relscore give the pair.  An eligible candidate (its allow bit on, allow NULL: every
+// item; not found in the item-ascending training row, xptr NULL: no exclusion) is placed into the user's sorted relevant row by
+// rank_bucket and counted by an integer add: rows of at most CAND_STAGE entries are staged in the wave's LDS with their
+// histogram, longer ones are searched in global memory (rs / ri, L2-resident) with a global add.  A candidate that meets itself
+// in the relevant row is not counted.  One split: hist holds the batch's buckets once, zeroed by the caller, user idx's nr + 1
+// starting at (rptr[idx] - rptr[0]) + idx, and k_rank_finish runs on it with nsplit = 1.  Every loop is bounded by the row's
+// length, by 64 or by nr.
+template <typename T>
+__global__ __launch_bounds__(256) void k_cand_count(const T* __restrict__ U, const T* __restrict__ V, int r, int ld,
+                                                    const int32_t* __restrict__ users, int64_t n, const int64_t* __restrict__ cptr,
+                                                    const int32_t* __restrict__ citem, const unsigned long long* __restrict__ allow,
+                                                    const int64_t* __restrict__ xptr, const int32_t* __restrict__ xitem,
+                                                    const int64_t* __restrict__ rptr, const T* __restrict__ rs, const int32_t* __restrict__ ri,
+                                                    int32_t* __restrict__ hist) {
+    __shared__ T stg_[4][rec::TILE];
+    __shared__ T ls_[4][rec::CAND_STAGE];
+    __shared__ int li_[4][rec::CAND_STAGE];
+    __shared__ int lh_[4][rec::CAND_STAGE + 1];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + w;
+    if (idx >= n) return;                               // (the whole wave)
+    T* stg = stg_[w];
+    T* ls = ls_[w];
+    int* li = li_[w];
+    int* lh = lh_[w];
+
+    const int u = users[idx];
+    const int64_t nc = cptr[idx + 1] - cptr[idx];
+    const int32_t* ci = citem + (cptr[idx] - cptr[0]);
+    int64_t xb = 0, xe = 0;
+    if (xptr) { xb = xptr[u]; xe = xptr[u + 1]; }
+    const int64_t rb = rptr[idx];
+    const int nr = (int)(rptr[idx + 1] - rb);           // (a counted user: nr >= 1)
+    const T* gs = rs + rb;
+    const int32_t* gi = ri + rb;
+    int32_t* gh = hist + (size_t)(rb - rptr[0]) + (size_t)idx;
+    const bool staged = nr <= rec::CAND_STAGE;          // (wave-uniform)
+    if (staged) {
+        for (int t = lane; t < nr; t += 64) { ls[t] = gs[t]; li[t] = gi[t]; }
+        for (int t = lane; t <= nr; t += 64) lh[t] = 0;
+    }
+    wave_sync();
+
+    const T* Ur = U + (size_t)(unsigned)u * (unsigned)ld;
+    for (int64_t t0 = 0; t0 < nc; t0 += rec::TILE) {
+        int id;
+        T s;
+        const bool ok = cand_step<T>(Ur, V, r, ld, ci, nc, t0, lane, stg, allow, xitem, xb, xe, id, s);
+        if (ok) {
+            if (staged) {
+                const int b = rank_bucket<T>(ls, li, nr, s, id);
+                if (b >= 0) atomicAdd(&lh[b], 1);
+            } else {
+                const int b = rank_bucket<T>(gs, gi, nr, s, id);
+                if (b >= 0) atomicAdd(&gh[b], 1);
+            }
+        }
+        wave_sync();                                   // (the next step overwrites stg)
+    }
+    if (staged) for (int t = lane; t <= nr; t += 64) gh[t] = lh[t];
 }
 
 // One wave per counted user: the splits' histograms summed and scanned.  With cum(t) = sum_{b <= t} hist[b], the t-th entry of

@@ -90,6 +90,24 @@ int pcr_evaluate_ranks_model(const double* U, int64_t d1, const double* V, int64
     return rc != PCR_OK ? rc : absent();
 }
 NO_SOLVER(pcr_evaluate_ranks, pcr_solver*, double, int, pcr_rank_stats*, double*, int64_t*)
+int pcr_evaluate_topn_filtered_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                                     const int64_t* tindex, const int32_t* titem, const double* tval, int ncut, const int* cutoffs, double threshold,
+                                     int dtype, const pcr_item_filter* f, pcr_topn_stats* stats, double*, int) {
+    int rc = pcr_evaluate_topn_model_check(U, d1, V, d2, k, index, item, tindex, titem, tval, ncut, cutoffs, threshold, dtype, stats, nullptr,
+                                           "pcr_evaluate_topn_filtered_model");
+    if (rc == PCR_OK) rc = pcr_eval_filter_check("pcr_evaluate_topn_filtered_model", "pcr_evaluate_topn_model", d2, d1, f);
+    return rc != PCR_OK ? rc : absent();
+}
+NO_SOLVER(pcr_evaluate_topn_filtered, pcr_solver*, int, const int*, double, int, const pcr_item_filter*, pcr_topn_stats*, double*)
+int pcr_evaluate_ranks_filtered_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                                      const int64_t* tindex, const int32_t* titem, const double* tval, double threshold, int dtype,
+                                      const pcr_item_filter* f, pcr_rank_stats* stats, double*, int64_t*, int) {
+    int rc = pcr_evaluate_ranks_model_check(U, d1, V, d2, k, index, item, tindex, titem, tval, threshold, dtype, stats, nullptr,
+                                            "pcr_evaluate_ranks_filtered_model");
+    if (rc == PCR_OK) rc = pcr_eval_filter_check("pcr_evaluate_ranks_filtered_model", "pcr_evaluate_ranks_model", d2, d1, f);
+    return rc != PCR_OK ? rc : absent();
+}
+NO_SOLVER(pcr_evaluate_ranks_filtered, pcr_solver*, double, int, const pcr_item_filter*, pcr_rank_stats*, double*, int64_t*)
 int pcr_evaluate_diversity_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
                                  int64_t n, const int32_t* users, int ncut, const int* cutoffs, int dtype, pcr_diversity_stats* stats, double*,
                                  int64_t*, int) {
