@@ -148,6 +148,22 @@ int pcr_dataset_csr(const pcr_dataset *ds, int which, int64_t *index, int64_t *i
 /* #Omega = #{(i,j,k): R_ij > R_ik} after the solver's level bucketing (lround for
  * PrimalCR++, pcrpp.cpp:41; raw doubles for PrimalCR, pcr.cpp:23) */
 int64_t pcr_dataset_count_pairs(const pcr_dataset *ds, int solver_type);   /* [host] */
+/* The same count user by user: pairs[u] = |Omega_u|, the number of terms of user u's loss (pcrpp.cpp:361-412 / pcr.cpp:5-44 sum
+ * over exactly these pairs), d1 entries, under the same level bucketing; their sum is pcr_dataset_count_pairs. */
+int pcr_dataset_user_pairs(const pcr_dataset *ds, int solver_type, int64_t *pairs /* d1 */);   /* [host] */
+
+/* Per-user loss weights c_u > 0 for PrimalCR / PrimalCR++ (no counterpart in the reference, whose objective pcrpp.cpp:361-412
+ * gives every user weight one): min sum_u c_u L_u + lambda/2 (|U|^2 + |V|^2).  pcr_user_weights fills w (d1 entries) by scheme:
+ *   PCR_WEIGHT_UNIFORM   w_u = 1
+ *   PCR_WEIGHT_PAIRS     w_u = (|Omega| / #{u: |Omega_u| > 0}) / |Omega_u|, and 1 where |Omega_u| = 0: every user with a
+ *                        comparable pair carries the same mass, sum_u w_u |Omega_u| = |Omega|
+ *   PCR_WEIGHT_RATINGS   w_u = (nnz / #{u: n_u > 0}) / n_u, and 1 where n_u = 0: sum_u w_u n_u = nnz
+ * Both normalising schemes keep the total mass of the unweighted problem, so lambda keeps its scale.  Another scheme, or
+ * solver_type 0, is PCR_ERR_ARG. */
+#define PCR_WEIGHT_UNIFORM 0
+#define PCR_WEIGHT_PAIRS   1
+#define PCR_WEIGHT_RATINGS 2
+int pcr_user_weights(const pcr_dataset *ds, int solver_type, int scheme, double *w /* d1 */);   /* [host] */
 
 /* A rating file on its own (omp-pmf-predict's test file: pmf-predict.cpp:52-55 reads "user item rating" triples until fscanf
  * fails, no meta file).  count: the file's non-blank lines.  read: at most n entries by `threads` host threads (0 = up to 16),
@@ -319,6 +335,22 @@ int pcr_solver_get_factors(pcr_solver *s, double *U, double *V);
 /* the same with U_local = this rank's n_users x k rows only (what a rank created by pcr_solver_create_shard holds) */
 int pcr_solver_set_factors_local(pcr_solver *s, const double *U_local, const double *V);
 int pcr_solver_get_factors_local(pcr_solver *s, double *U_local, double *V);
+
+/* Per-user loss weights (PrimalCR / PrimalCR++; the reference's update_V_new pcrpp.cpp:415-444 and update_u_new :779-815 are
+ * the case c_u = 1): w holds one weight per user of the JOB (d1 entries; each rank reads only its own users'), w_local this
+ * rank's n_users entries only, as with set_factors / set_factors_local.  NULL returns to the unweighted problem.  Every weight
+ * read must be finite and > 0, else PCR_ERR_ARG and the solver keeps what it had.  From then on pcr_objective, pcr_obtain_g,
+ * pcr_compute_Ha, pcr_solve_delta, pcr_update_V, pcr_update_U, pcr_train, pcr_iterate and pcr_iter_stats.obj are those of
+ *     min sum_u c_u L_u(U, V) + lambda/2 (|U|^2 + |V|^2):
+ * the V side's gradient and Hessian-vector products are sum_u c_u (user u's share), and user u's Newton step is the
+ * unweighted step with lambda / c_u -- so a trained user's row is what pcr_fold_in returns for that user with lambda / c_u.
+ * pcr_evaluate and the serving entries never see the loss and are unchanged.  May be called at any point between entry
+ * points: the solver synchronises, drops the objective sums a pipelined loop had queued and continues from the weighted
+ * objective at the current factors (the sorted state of the last pcr_comp_m stays valid).
+ * PCR_ERR_UNSUPPORTED (reason in pcr_last_error): a CCDR1 solver; a solver created under pcr_tune "ustep_newton",
+ * "ustep_gram" or "vblock_users", whose optional kernels do not carry weights. */
+int pcr_solver_set_user_weights(pcr_solver *s, const double *w /* d1 of the job */);        /* [device] */
+int pcr_solver_set_user_weights_local(pcr_solver *s, const double *w_local /* n_users */);  /* [device] */
 
 /* pcrpp.cpp:17-35 comp_m_new (pcr.cpp:47 comp_m): m = u_i . v_j for every rating,
  * from the current device U, V; also builds the per-user (level, m)-sorted state

@@ -8,6 +8,7 @@ import numpy as np
 
 PCR_SOLVER_CCDR1, PCR_SOLVER_PCR, PCR_SOLVER_PCRPP = 0, 1, 2
 PCR_F32, PCR_F64 = 0, 1
+PCR_WEIGHT_UNIFORM, PCR_WEIGHT_PAIRS, PCR_WEIGHT_RATINGS = 0, 1, 2               # user_weights' schemes
 PCR_RECOMMEND_MAX_K = 1024
 PCR_REC_EXCLUDE_TRAIN = 1
 PCR_TOPN_MAX_CUTOFFS = 8
@@ -181,6 +182,11 @@ def lib():
     L.pcr_dataset_csr.argtypes = [vp, ci, vp, vp, vp]
     L.pcr_dataset_count_pairs.argtypes = [vp, ci]
     L.pcr_dataset_count_pairs.restype = i64
+    if _LIB_OVERRIDE is None or hasattr(L, "pcr_solver_set_user_weights"):
+        L.pcr_dataset_user_pairs.argtypes = [vp, ci, vp]
+        L.pcr_user_weights.argtypes = [vp, ci, ci, vp]
+        L.pcr_solver_set_user_weights.argtypes = [vp, vp]
+        L.pcr_solver_set_user_weights_local.argtypes = [vp, vp]
     L.pcr_model_save.argtypes = [C.c_char_p, _dp, i64, _dp, i64, i64]
     L.pcr_model_load.argtypes = [C.c_char_p, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp, vp]
     L.pcr_partition_users.argtypes = [_lp, i64, ci, _lp]
@@ -1053,10 +1059,25 @@ class Dataset:
     def count_pairs(self, solver_type=PCR_SOLVER_PCRPP):
         return lib().pcr_dataset_count_pairs(self._h, solver_type)
 
+    def user_pairs(self, solver_type=PCR_SOLVER_PCRPP):
+        """|Omega_u| per user under the solver's level bucketing (int64, d1 entries); its sum is count_pairs."""
+        pairs = np.zeros(max(self.dims()[0], 1), np.int64)
+        _chk(lib().pcr_dataset_user_pairs(self._h, solver_type, pairs.ctypes.data))
+        return pairs[:self.dims()[0]]
+
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.pcr_dataset_free(self._h)
             self._h = None
+
+
+def user_weights(ds: Dataset, scheme=PCR_WEIGHT_PAIRS, solver_type=PCR_SOLVER_PCRPP):
+    """Per-user loss weights for Solver.set_user_weights by scheme: PCR_WEIGHT_UNIFORM (all 1), PCR_WEIGHT_PAIRS (every user
+    with a comparable pair carries the same mass: sum w_u |Omega_u| = |Omega|) or PCR_WEIGHT_RATINGS (sum w_u n_u = nnz)."""
+    d1 = ds.dims()[0]
+    w = np.ones(max(d1, 1), np.float64)
+    _chk(lib().pcr_user_weights(ds._h, solver_type, scheme, w.ctypes.data))
+    return w[:d1]
 
 
 class Solver:
@@ -1138,6 +1159,19 @@ class Solver:
         if U is not None and U.shape != (self.n_users, self.k):
             raise ValueError(f"U_local must be {self.n_users} x {self.k}")
         _chk(lib().pcr_solver_set_factors_local(self._h, None if U is None else U.ctypes.data, None if V is None else V.ctypes.data))
+
+    def set_user_weights(self, w=None, local=False):
+        """Per-user loss weights c_u > 0 (PrimalCR / PrimalCR++): the solver then minimises sum_u c_u L_u + lambda/2 (|U|^2 + |V|^2).
+        w: one weight per user of the job (with local=True: this rank's n_users only); None returns to the unweighted problem."""
+        fn = lib().pcr_solver_set_user_weights_local if local else lib().pcr_solver_set_user_weights
+        if w is None:
+            _chk(fn(self._h, None))
+            return
+        w = np.ascontiguousarray(w, np.float64)
+        want = self.n_users if local else self.d1
+        if w.shape != (want,):
+            raise ValueError(f"w must hold {want} weights")
+        _chk(fn(self._h, w.ctypes.data))
 
     def get_factors_local(self):
         U = np.zeros((self.n_users, self.k)); V = np.zeros((self.d2, self.k))

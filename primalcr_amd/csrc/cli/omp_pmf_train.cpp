@@ -20,6 +20,11 @@
 //   --devices a,b,..  the HIP device of every rank (default 0..N-1)
 //   --comm rccl|p2p   exchange step: ncclAllReduce over RCCL (default) or the direct peer-to-peer reduce-scatter /
 //                     all-gather of pcr_solver_comm_init_p2p
+//   --user-weights F  per-user loss weights (pcr_solver_set_user_weights; -s 1 and -s 2): F holds one positive weight per line,
+//                     one line per user, as many lines as meta has users; with --gpus N every worker reads its own range
+//   --normalize pairs|ratings  the weights of pcr_user_weights instead: every user with a comparable pair (a rating) carries the
+//                     same mass, the total stays that of the unweighted problem.  Not together with --user-weights.
+//                     The log lines keep their format; the objective they print is the weighted one.
 //   --tune key=value  a launch knob of pcr_tune() (repeatable)
 //   --timing          one "[timing] load_s=... init_s=... create_s=... train_s=... iter_s=... eval_s=... write_s=... wall_s=..." line
 //                     on stderr at the end: where the run's wall time went (iter_s = the reference's own "Iter k time" clock,
@@ -70,6 +75,8 @@ static void exit_with_help() {
         "    --gpus n : shard the users over n GPUs of this node, one worker process per GPU (default 1)\n"
         "    --devices a,b,.. : HIP device of every rank (default 0..n-1)\n"
         "    --comm rccl|p2p : all-reduce through RCCL (default) or direct peer-to-peer buffers\n"
+        "    --user-weights file : per-user loss weights, one positive weight per line and user (-s 1, -s 2)\n"
+        "    --normalize pairs|ratings : weight every user by 1 / its pairs (ratings), total mass kept (not with --user-weights)\n"
         "    --tune key=value : launch knob (pcr_tune)\n"
         "    --timing : print the phases of the run's wall time on stderr\n");
     exit(1);
@@ -148,6 +155,30 @@ static void write_outputs(const pcr_params& param, const std::string& model, con
     if (pcr_model_save(model.c_str(), U.data(), d1, V.data(), d2, k) != PCR_OK) die("model");
 }
 
+// --user-weights: one positive weight per line, exactly d1 lines (blank lines at the end are ignored)
+static bool read_user_weights(const std::string& path, int64_t d1, std::vector<double>& w, std::string& err) {
+    std::ifstream f(path);
+    if (!f) { err = "can't open " + path; return false; }
+    w.clear();
+    std::string line;
+    int64_t lineno = 0;
+    while (std::getline(f, line)) {
+        ++lineno;
+        const size_t a = line.find_first_not_of(" \t\r"), b = line.find_last_not_of(" \t\r");
+        if (a == std::string::npos) continue;                                  // blank
+        const std::string tok = line.substr(a, b - a + 1);
+        char* end = nullptr;
+        errno = 0;
+        const double v = strtod(tok.c_str(), &end);
+        if (end == tok.c_str() || *end != '\0' || errno == ERANGE) { err = path + ":" + std::to_string(lineno) + ": '" + tok + "' is not a number"; return false; }
+        if (!(v > 0.0) || v > 1.7976931348623157e308) { err = path + ":" + std::to_string(lineno) + ": weight " + tok + " is not a finite number > 0"; return false; }
+        if ((int64_t)w.size() == d1) { err = path + " holds more than the " + std::to_string(d1) + " weights of meta's users"; return false; }
+        w.push_back(v);
+    }
+    if ((int64_t)w.size() != d1) { err = path + " holds " + std::to_string(w.size()) + " weights, meta has " + std::to_string(d1) + " users"; return false; }
+    return true;
+}
+
 // ---- --gpus N: one worker process per GPU -------------------------------------------------------------------------------
 // Shared between the parent and its workers (anonymous MAP_SHARED, made before the fork): the RCCL id, the result factors.
 struct SharedHdr {
@@ -181,7 +212,7 @@ static void multi_snap_log(void* vctx, const char* line);
 // body of worker `rank`: everything that touches a GPU happens here, after the fork
 static int worker(const pcr_dataset* ds, pcr_params param, int rank, int nranks, const std::string& comm_kind, SharedHdr* hdr,
                   double* Ush, double* Vsh, const std::vector<double>& U0, const std::vector<double>& V0, int64_t d1, int64_t d2,
-                  int snapshot_every, const std::string& model) {
+                  int snapshot_every, const std::string& model, const std::vector<double>& weights) {
     auto fail = [&](const char* what) { fprintf(stderr, "[rank %d] %s: %s\n", rank, what, pcr_last_error()); hdr->failed.store(1); return 1; };
     const auto t0 = std::chrono::steady_clock::now();
     pcr_solver* s = nullptr;
@@ -206,6 +237,7 @@ static int worker(const pcr_dataset* ds, pcr_params param, int rank, int nranks,
         fprintf(stderr, "[rank %d] device %d: users [%ld, %ld), %ld ratings\n", rank, param.device, (long)f0, (long)(f0 + n0), (long)z0);
     }
     if (pcr_solver_set_factors(s, U0.data(), V0.data()) != PCR_OK) return fail("set_factors");
+    if (!weights.empty() && pcr_solver_set_user_weights(s, weights.data()) != PCR_OK) return fail("user weights");     // (reads this rank's range)
     int64_t first = 0, nu = 0;
     pcr_solver_shard(s, &first, &nu, nullptr);
     MultiSnap snap{s, snapshot_every, rank, nranks, hdr, Ush, Vsh, d1, d2, first, nu, param.k, model, false};
@@ -255,7 +287,7 @@ static void multi_snap_log(void* vctx, const char* line) {
 
 static int train_multi(const pcr_dataset* ds, const pcr_params& param, int gpus, const std::vector<int>& devices,
                        const std::string& comm_kind, std::vector<double>& U, std::vector<double>& V, int64_t d1, int64_t d2,
-                       int snapshot_every, const std::string& model) {
+                       int snapshot_every, const std::string& model, const std::vector<double>& weights) {
     const size_t nU = (size_t)d1 * param.k, nV = (size_t)d2 * param.k;
     const size_t bytes = sizeof(SharedHdr) + (nU + nV) * sizeof(double) + 64;
     void* mem = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
@@ -296,7 +328,7 @@ static int train_multi(const pcr_dataset* ds, const pcr_params& param, int gpus,
             // the command line says otherwise) -- five processes that each claim half a dozen queues, with spinning probe kernels
             // measuring each other, is what the one-rank-per-GPU layout never sees.
             if (shared_device && pcr_tune_is_default_lanes) (void)pcr_tune("lanes", "1");
-            const int rc = worker(ds, p, q, gpus, comm_kind, hdr, Ush, Vsh, U, V, d1, d2, snapshot_every, model);
+            const int rc = worker(ds, p, q, gpus, comm_kind, hdr, Ush, Vsh, U, V, d1, d2, snapshot_every, model, weights);
             fflush(stdout); fflush(stderr);
             _exit(rc);
         }
@@ -391,7 +423,7 @@ int main(int argc, char** argv) {
     pcr_params_default(&param);
     pcr_ccd_params ccd;
     pcr_ccd_params_default(&ccd);
-    std::string init_model, cache, comm_kind = "rccl";
+    std::string init_model, cache, comm_kind = "rccl", weights_file, normalize;
     std::vector<int> devices;
     int snapshot_every = 0, gpus = 1;
     int i;
@@ -408,6 +440,8 @@ int main(int argc, char** argv) {
         if (!strcmp(argv[i - 1], "--cg-tol")) { param.cg_tol = atof(argv[i]); continue; }
         if (!strcmp(argv[i - 1], "--gpus")) { gpus = atoi(argv[i]); continue; }
         if (!strcmp(argv[i - 1], "--comm")) { comm_kind = argv[i]; continue; }
+        if (!strcmp(argv[i - 1], "--user-weights")) { weights_file = argv[i]; continue; }
+        if (!strcmp(argv[i - 1], "--normalize")) { normalize = argv[i]; continue; }
         if (!strcmp(argv[i - 1], "--devices")) {
             for (const char* q = argv[i]; *q;) { devices.push_back(atoi(q)); while (*q && *q != ',') ++q; if (*q == ',') ++q; }
             continue;
@@ -456,10 +490,12 @@ int main(int argc, char** argv) {
     }
     if (param.solver_type == PCR_SOLVER_CCDR1) {                     // options CCDR1 does not have: refused, never ignored
         const char* bad = gpus != 1 ? "--gpus" : devices.size() > 1 ? "--devices with more than one device" : !init_model.empty() ? "--init-model"
-                        : snapshot_every != 0 ? "--snapshot-every" : nullptr;
+                        : snapshot_every != 0 ? "--snapshot-every" : !weights_file.empty() ? "--user-weights" : !normalize.empty() ? "--normalize" : nullptr;
         if (bad) { fprintf(stderr, "omp-pmf-train: %s is not supported with -s 0 (CCDR1 runs on one GPU from initial_col)\n", bad); return 1; }
         if (comm_kind != "rccl" && comm_kind != "p2p") { fprintf(stderr, "--comm must be rccl or p2p\n"); return 1; }
     }
+    if (!weights_file.empty() && !normalize.empty()) { fprintf(stderr, "omp-pmf-train: --user-weights and --normalize are mutually exclusive\n"); return 1; }
+    if (!normalize.empty() && normalize != "pairs" && normalize != "ratings") { fprintf(stderr, "omp-pmf-train: --normalize must be pairs or ratings\n"); return 1; }
     // the reference opens the model file BEFORE training (pmf-train.cpp:252-259)
     FILE* fp = fopen(model.c_str(), "wb");
     if (!fp) { fprintf(stderr, "can't open output file %s\n", model.c_str()); return 1; }
@@ -485,6 +521,14 @@ int main(int argc, char** argv) {
     if (param.solver_type == PCR_SOLVER_CCDR1) {
         pcr_initial_col(U.data(), d1, k);              // pmf-train.cpp:156-158 (H is zeroed by ccdr1 itself, ccd-r1.cpp:116)
         return run_ccdr1(ds, param, ccd, devices, model, U, V, d1, d2, timing, load_s, lap() , t_main);
+    }
+    std::vector<double> weights;                       // per-user loss weights (empty: the reference's unweighted problem)
+    if (!weights_file.empty()) {
+        std::string werr;
+        if (!read_user_weights(weights_file, d1, weights, werr)) { fprintf(stderr, "--user-weights: %s\n", werr.c_str()); return 1; }
+    } else if (!normalize.empty()) {
+        weights.resize((size_t)d1);
+        if (pcr_user_weights(ds, param.solver_type, normalize == "pairs" ? PCR_WEIGHT_PAIRS : PCR_WEIGHT_RATINGS, weights.data()) != PCR_OK) die("normalize");
     }
     pcr_initial(U.data(), d1, k);                      // pmf-train.cpp:264-266
     pcr_initial(V.data(), d2, k);
@@ -515,7 +559,7 @@ int main(int argc, char** argv) {
     };
     if (gpus > 1) {
         (void)lap();
-        const int rc = train_multi(ds, param, gpus, devices, comm_kind, U, V, d1, d2, snapshot_every, model);
+        const int rc = train_multi(ds, param, gpus, devices, comm_kind, U, V, d1, d2, snapshot_every, model, weights);
         if (rc != 0) return rc;
         train_s = lap();                                  // (workers: solver creation + training + deposit; rank 0 prints its own split)
         write_outputs(param, model, U, V, d1, d2);
@@ -534,6 +578,7 @@ int main(int argc, char** argv) {
     auto fail = [](const char* what) { fprintf(stderr, "%s: %s\n", what, pcr_last_error()); return 1; };
     const double solver_s = lap();                        // pcr_solver_create alone (its phases: pcr_solver_setup_phase)
     if (pcr_solver_set_factors(s, U.data(), V.data()) != PCR_OK) return fail("set_factors");
+    if (!weights.empty() && pcr_solver_set_user_weights(s, weights.data()) != PCR_OK) return fail("user weights");
     create_s = warm_wait_s + solver_s + lap();
     if (timing) {
         // where solver creation went: the join with the thread that brought the HIP runtime up, then the library's own phases

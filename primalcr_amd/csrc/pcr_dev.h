@@ -199,6 +199,11 @@ struct pcr_solver {
     virtual int update_V(double*, int*) { return pcr_only("pcr_update_V"); }
     virtual int update_U(double*, int64_t*) { return pcr_only("pcr_update_U"); }
     virtual int foldin_params(pcr_params*) { return pcr_only("pcr_fold_in"); }    // the parameters pcr_fold_in runs with
+    // per-user loss weights (w: d1 of the job, or this rank's n_users with local; NULL: unweighted)
+    virtual int set_user_weights(const double*, bool) {
+        pcr_set_error("pcr_solver_set_user_weights: per-user loss weights exist for PrimalCR / PrimalCR++ only; this solver is CCDR1 (solver type 0)");
+        return PCR_ERR_UNSUPPORTED;
+    }
     virtual double ridge_lambda() = 0;                             // the lambda pcr_fold_in_ridge runs with (every solver type)
     virtual int evaluate(int which, int ndcg_k, double* err, double* ndcg) = 0;
     virtual int train(pcr_log_fn log, void* ctx, pcr_iter_stats* hist) = 0;

@@ -221,16 +221,18 @@ __global__ __launch_bounds__(PCR_EW_BLOCK) void k_sum4_stage1(const double* __re
 }
 // the three sums of an objective in one pass: sum(objx[0..nx)), |a|^2 over na elements, |b|^2 over nb (b may be null),
 // and optionally a second per-user sum, sum(objx2[0..nx)); block-sliced partials part[blk][4] for k_fin4 (deterministic
-// two-stage sums, as k_sum_stage1 / k_dots)
+// two-stage sums, as k_sum_stage1 / k_dots).  wx (per-user loss weights, NULL on the unweighted problem) multiplies the terms of
+// objx: sum_u c_u objx[u], for the raw per-user losses of objp; the terms of objx2 (k_ustep's objr) carry their weight already.
 template <typename T>
 __global__ __launch_bounds__(PCR_EW_BLOCK) void k_obj3(const double* __restrict__ objx, const double* __restrict__ objx2, int64_t nx,
                                                         const T* __restrict__ a, int64_t na, const T* __restrict__ b, int64_t nb,
-                                                        double* __restrict__ part) {
+                                                        double* __restrict__ part, const double* __restrict__ wx = nullptr) {
     __shared__ double red[PCR_EW_BLOCK / PCR_WAVE + 1];
     const int64_t G = gridDim.x, blk = blockIdx.x;
     double s[4] = {0.0, 0.0, 0.0, 0.0};
     { const int64_t per = (nx + G - 1) / G, lo = blk * per, hi = lo + per < nx ? lo + per : nx;
-      for (int64_t i = lo + threadIdx.x; i < hi; i += PCR_EW_BLOCK) s[0] += objx[i];
+      if (wx) for (int64_t i = lo + threadIdx.x; i < hi; i += PCR_EW_BLOCK) s[0] += wx[i] * objx[i];
+      else for (int64_t i = lo + threadIdx.x; i < hi; i += PCR_EW_BLOCK) s[0] += objx[i];
       if (objx2) for (int64_t i = lo + threadIdx.x; i < hi; i += PCR_EW_BLOCK) s[3] += objx2[i]; }
     { const int64_t per = (na + G - 1) / G, lo = blk * per, hi = lo + per < na ? lo + per : na;
       for (int64_t i = lo + threadIdx.x; i < hi; i += PCR_EW_BLOCK) { const double v = (double)a[i]; s[1] += v * v; } }

@@ -960,22 +960,61 @@ int pcr_build_levels(const PcrCsr& X, int64_t u0, int64_t u1, int solver_type, P
     return PCR_OK;
 }
 
-extern "C" int64_t pcr_dataset_count_pairs(const pcr_dataset* ds, int solver_type) {
-    if (!ds) return -1;
+// |Omega_u| per user under the solver's level bucketing: the pairs of ratings at different levels
+static int pcr_user_pairs(const pcr_dataset* ds, int solver_type, std::vector<int64_t>& pairs) {
     const PcrCsr& X = ds->train;
     PcrLevels lv;
     std::string err;
-    if (pcr_build_levels(X, 0, X.d1, solver_type, lv, err) != PCR_OK) { pcr_set_error(err); return -1; }
-    int64_t total = 0;
+    const int rc = pcr_build_levels(X, 0, X.d1, solver_type, lv, err);
+    if (rc != PCR_OK) { pcr_set_error(err); return rc; }
+    pairs.assign((size_t)X.d1, 0);
     for (int64_t u = 0; u < X.d1; ++u) {
         int64_t n = X.index[u + 1] - X.index[u], same = 0;
         for (int64_t q = lv.run_ofs[u]; q + 1 < lv.run_ofs[u + 1]; ++q) {
             int64_t c = lv.run_start[q + 1] - lv.run_start[q];
             same += c * c;
         }
-        total += (n * n - same) / 2;
+        pairs[(size_t)u] = (n * n - same) / 2;
     }
+    return PCR_OK;
+}
+
+extern "C" int64_t pcr_dataset_count_pairs(const pcr_dataset* ds, int solver_type) {
+    if (!ds) return -1;
+    std::vector<int64_t> pairs;
+    if (pcr_user_pairs(ds, solver_type, pairs) != PCR_OK) return -1;
+    int64_t total = 0;
+    for (int64_t c : pairs) total += c;
     return total;
+}
+
+extern "C" int pcr_dataset_user_pairs(const pcr_dataset* ds, int solver_type, int64_t* pairs) {
+    if (!ds || (!pairs && ds->train.d1 > 0)) { pcr_set_error("pcr_dataset_user_pairs: bad argument"); return PCR_ERR_ARG; }
+    if (solver_type != PCR_SOLVER_PCR && solver_type != PCR_SOLVER_PCRPP) { pcr_set_error("pcr_dataset_user_pairs: solver type must be 1 (PrimalCR) or 2 (PrimalCR++)"); return PCR_ERR_ARG; }
+    std::vector<int64_t> v;
+    const int rc = pcr_user_pairs(ds, solver_type, v);
+    if (rc != PCR_OK) return rc;
+    std::copy(v.begin(), v.end(), pairs);
+    return PCR_OK;
+}
+
+// per-user loss weights by scheme (primalcr.h): both normalising schemes keep the unweighted problem's total mass
+extern "C" int pcr_user_weights(const pcr_dataset* ds, int solver_type, int scheme, double* w) {
+    if (!ds || (!w && ds->train.d1 > 0)) { pcr_set_error("pcr_user_weights: bad argument"); return PCR_ERR_ARG; }
+    if (solver_type != PCR_SOLVER_PCR && solver_type != PCR_SOLVER_PCRPP) { pcr_set_error("pcr_user_weights: solver type must be 1 (PrimalCR) or 2 (PrimalCR++)"); return PCR_ERR_ARG; }
+    if (scheme != PCR_WEIGHT_UNIFORM && scheme != PCR_WEIGHT_PAIRS && scheme != PCR_WEIGHT_RATINGS) {
+        pcr_set_error("pcr_user_weights: unknown scheme " + std::to_string(scheme) + " (0 = uniform, 1 = pairs, 2 = ratings)");
+        return PCR_ERR_ARG;
+    }
+    const PcrCsr& X = ds->train;
+    std::vector<int64_t> cnt((size_t)X.d1, 0);               // the user's mass: |Omega_u| or n_u
+    if (scheme == PCR_WEIGHT_PAIRS) { const int rc = pcr_user_pairs(ds, solver_type, cnt); if (rc != PCR_OK) return rc; }
+    else if (scheme == PCR_WEIGHT_RATINGS) for (int64_t u = 0; u < X.d1; ++u) cnt[(size_t)u] = X.index[u + 1] - X.index[u];
+    int64_t total = 0, active = 0;
+    for (int64_t c : cnt) { total += c; active += c > 0 ? 1 : 0; }
+    const double mean = active > 0 ? (double)total / (double)active : 1.0;
+    for (int64_t u = 0; u < X.d1; ++u) w[u] = cnt[(size_t)u] > 0 ? mean / (double)cnt[(size_t)u] : 1.0;
+    return PCR_OK;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -60,6 +60,12 @@ struct Shard {
     // k_prepare's per-user back-off: 1 = the user's last fast-path attempt failed (both tiers, then the network anyway: the
     // long users of the first ~10 iterations) -> the next prepare sorts it with the network straight away and sets 2 = try again
     unsigned char* rhint;
+    // per-user loss weights c_u (pcr_solver_set_user_weights), both NULL on the unweighted problem: uw[u] = c_u
+    // scales the V side's sweep coefficients and the per-user objective terms, ulam[u] = lambda / c_u (divided on the host)
+    // is the regulariser of user u's Newton step.  One wave-uniform scalar per user.  Read by the WT = true instantiations of
+    // the sweeps and of k_ustep only: the unweighted symbols compile to what they were before the weights existed.
+    const double* uw = nullptr;
+    const double* ulam = nullptr;
 };
 
 // ---------------------------------------------------------------------------------------
@@ -408,9 +414,10 @@ __device__ __forceinline__ double sweep_coeff_win4(uint2 wv, const double* S, co
 // the sweep's output loop for that layout: the per-rating loads (level, boundaries, CSR index) of FOUR rounds are issued before
 // the first is used.  The sweep is bound by bytes in flight on large shards (Little's law: ~35 % occupancy x 3 small loads per
 // wave = 1.5 TB/s on the Netflix shape); on ml1m the launch is as long as its longest user and this changes nothing.
-template <typename T, int STRIDE, bool HV>
+// WT: the coefficients are scaled by the user's loss weight cu (Shard::uw), in fp64 before the conversion to T
+template <typename T, int STRIDE, bool HV, bool WT = false>
 __device__ __forceinline__ void sweep_out4(const Shard<T>& S, int64_t s0, int n, int nlev, int tid, const T* xs, const double* Sx,
-                                           const int* rs, T* __restrict__ c_out) {
+                                           const int* rs, T* __restrict__ c_out, double cu = 1.0) {
     const uint2* __restrict__ w2 = reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(S.win) + (size_t)s0 * 4);
     for (int p0 = tid; p0 < n; p0 += STRIDE * 4) {
         uint2 wv[4];
@@ -423,7 +430,10 @@ __device__ __forceinline__ void sweep_out4(const Shard<T>& S, int64_t s0, int n,
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int p = p0 + q * STRIDE;
-            if (p < n) c_out[s0 + si[q]] = (T)sweep_coeff_win4(wv[q], Sx, rs, nlev, lv[q], (double)xs[p], HV ? 0.0 : 1.0);
+            if (p < n) {
+                const double c = sweep_coeff_win4(wv[q], Sx, rs, nlev, lv[q], (double)xs[p], HV ? 0.0 : 1.0);
+                c_out[s0 + si[q]] = (T)(WT ? c * cu : c);
+            }
         }
     }
 }

@@ -868,20 +868,27 @@ struct Solver final : pcr_solver {
         const int lim = 160 * 1024;
         HIPCHK(hipFuncSetAttribute((const void*)k_prepare<T, 512, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
         HIPCHK(hipFuncSetAttribute((const void*)k_prepare_all<T, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-        HIPCHK(hipFuncSetAttribute((const void*)k_vsweep<T, 512, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-        HIPCHK(hipFuncSetAttribute((const void*)k_vsweep<T, 512, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-        HIPCHK(hipFuncSetAttribute((const void*)k_vsweep_all<T, false, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-        HIPCHK(hipFuncSetAttribute((const void*)k_vsweep_all<T, true, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-        HIPCHK(hipFuncSetAttribute((const void*)k_vsweep_all<T, false, 512, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 40 * 1024));
-        HIPCHK(hipFuncSetAttribute((const void*)k_vsweep_all<T, true, 512, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 40 * 1024));
-#define UL(BL, BG, KK, RS, UN) HIPCHK(hipFuncSetAttribute((const void*)k_ustep<T, BL, BG, KK, RS, UN>, hipFuncAttributeMaxDynamicSharedMemorySize, lim))
+        // (every sweep and U-step symbol twice: the unweighted one and its per-user-weight instantiation, WT = true)
+#define VL(HV, WT) do { \
+        HIPCHK(hipFuncSetAttribute((const void*)k_vsweep<T, 512, false, HV, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)); \
+        HIPCHK(hipFuncSetAttribute((const void*)k_vsweep_all<T, HV, 512, 1, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)); \
+        HIPCHK(hipFuncSetAttribute((const void*)k_vsweep_all<T, HV, 512, 8, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, 40 * 1024)); } while (0)
+        VL(false, false); VL(true, false); VL(false, true); VL(true, true);
+#undef VL
+#define UL(BL, BG, KK, RS, UN) do { \
+        HIPCHK(hipFuncSetAttribute((const void*)k_ustep<T, BL, BG, KK, RS, UN>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)); \
+        HIPCHK(hipFuncSetAttribute((const void*)k_ustep<T, BL, BG, KK, RS, UN, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)); } while (0)
         UL(64, false, 1, true, 4); UL(64, false, 1, false, 4); UL(256, false, 1, false, 4);
-#define UL1(BL) HIPCHK(hipFuncSetAttribute((const void*)k_ustep<T, BL, false, 1, false, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lim))
+#define UL1(BL) do { \
+        HIPCHK(hipFuncSetAttribute((const void*)k_ustep<T, BL, false, 1, false, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)); \
+        HIPCHK(hipFuncSetAttribute((const void*)k_ustep<T, BL, false, 1, false, 4, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)); } while (0)
         UL1(64); UL1(256); UL1(512);
 #undef UL1
         UL(512, false, 1, true, 8); UL(512, false, 4, true, 8);
-        if (sizeof(T) == 4) HIPCHK(hipFuncSetAttribute((const void*)k_ustep<T, 512, false, 1, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-        else UL(512, false, 1, false, 4);
+        if (sizeof(T) == 4) {
+            HIPCHK(hipFuncSetAttribute((const void*)k_ustep<T, 512, false, 1, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
+            HIPCHK(hipFuncSetAttribute((const void*)k_ustep<T, 512, false, 1, false, 4, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
+        } else UL(512, false, 1, false, 4);
         UL(512, true, 1, true, 8); UL(512, true, 1, false, 4); UL(512, true, 4, true, 8);
 #undef UL
 #ifndef PCR_NO_OPTIONAL_KERNELS      // (a measurement build without the three optional kernel families: profiles/r06_cli_create.txt)
@@ -1137,21 +1144,25 @@ struct Solver final : pcr_solver {
     int launch_sweeps(bool hv, const int* skip, bool b_csr = false) {
         const int bc = (b_csr ? 1 : 0) | (sweep_pf4 ? 2 : 0);
         const bool two = hv && !sh.ws;                      // scores and sweep values both live in LDS (no window cache)
+        const bool wt = sh.uw != nullptr;                   // per-user loss weights: the WT instantiations
         auto fn = [&](Bin& b, hipStream_t q) {
             const int nus = (int)b.users.size();
             const int rsc = b.max_lev + 2;
             if (b.block == 64) {                         // short users: one wave each, four per workgroup
                 const size_t wb = (vsweep_wave_bytes<T>(b.cap, rsc, two) + 15) & ~(size_t)15;
-                if (hv) hipLaunchKernelGGL((k_vsweep_wave<T, true>), dim3(cdiv(nus, 4)), dim3(256), wb * 4, q, sh, b.d_users.p, nus, d_b.p, d_c.p, b.cap, rsc, wb, strict(), skip, bc);
-                else hipLaunchKernelGGL((k_vsweep_wave<T, false>), dim3(cdiv(nus, 4)), dim3(256), wb * 4, q, sh, b.d_users.p, nus, d_b.p, d_c.p, b.cap, rsc, wb, strict(), skip, bc);
+#define LW(HV, WT) hipLaunchKernelGGL((k_vsweep_wave<T, HV, WT>), dim3(cdiv(nus, 4)), dim3(256), wb * 4, q, sh, b.d_users.p, nus, d_b.p, d_c.p, b.cap, rsc, wb, strict(), skip, bc)
+                if (hv) { if (wt) LW(true, true); else LW(true, false); } else { if (wt) LW(false, true); else LW(false, false); }
+#undef LW
                 return;
             }
             const size_t bigb = vsweep_bytes<T>(b.cap, rsc, two);
             const size_t lds = small_common(b.block) + (b.big ? 0 : bigb);
             const int grid = b.big ? std::min(nus, scratch_blocks) : nus;
-#define LV(BL, BG, HV) hipLaunchKernelGGL((k_vsweep<T, BL, BG, HV>), dim3(grid), dim3(BL), lds, q, sh, geo, b.d_users.p, nus, d_b.p, d_c.p, b.cap, rsc, d_scratch.p, scratch_stride, strict(), skip, bc)
+#define LV(BL, BG, HV) do { if (wt) LVW(BL, BG, HV, true); else LVW(BL, BG, HV, false); } while (0)
+#define LVW(BL, BG, HV, WT) hipLaunchKernelGGL((k_vsweep<T, BL, BG, HV, WT>), dim3(grid), dim3(BL), lds, q, sh, geo, b.d_users.p, nus, d_b.p, d_c.p, b.cap, rsc, d_scratch.p, scratch_stride, strict(), skip, bc)
             if (hv) { if (b.big) LV(512, true, true); else LV(512, false, true); }
             else { if (b.big) LV(512, true, false); else LV(512, false, false); }
+#undef LVW
 #undef LV
         };
         Bin &ba = sbins[0], &bb = sbins[1];
@@ -1165,11 +1176,13 @@ struct Solver final : pcr_solver {
             const int grid = nb + cdiv(na, wpb);
             {
                 ProfScope ps(&prof, std::string(hv ? "vhv" : "vgrad") + "/all", st, ba.nnz + bb.nnz, (int64_t)(na + nb));
-#define LVA(HV, WBS, MW) hipLaunchKernelGGL((k_vsweep_all<T, HV, WBS, MW>), dim3(grid), dim3(WBS), lds, st, sh, ba.d_users.p, na, ba.cap, rsa, wb, \
+#define LVA(HV, WBS, MW) do { if (wt) LVAW(HV, WBS, MW, true); else LVAW(HV, WBS, MW, false); } while (0)
+#define LVAW(HV, WBS, MW, WT) hipLaunchKernelGGL((k_vsweep_all<T, HV, WBS, MW, WT>), dim3(grid), dim3(WBS), lds, st, sh, ba.d_users.p, na, ba.cap, rsa, wb, \
                                         bb.d_users.p, nb, bb.cap, rsb, nb, d_b.p, d_c.p, strict(), skip, bc)
                 // (four workgroups per CU where the longest user's arrays fit a quarter of the LDS: the 64-VGPR symbol)
                 const bool dense = lds <= (size_t)40 * 1024;
-                if (hv) { if (dense) LVA(true, 512, 8); else LVA(true, 512, 1); } else { if (dense) LVA(false, 512, 8); else LVA(false, 512, 1); }
+                if (hv) { if (dense) { LVA(true, 512, 8); } else { LVA(true, 512, 1); } } else { if (dense) { LVA(false, 512, 8); } else { LVA(false, 512, 1); } }
+#undef LVAW
 #undef LVA
             }
             if (!sbins[2].users.empty()) { ProfScope ps(&prof, pname(hv ? "vhv" : "vgrad", sbins[2]), st, sbins[2].nnz, (int64_t)sbins[2].users.size()); fn(sbins[2], st); }
@@ -1296,7 +1309,8 @@ struct Solver final : pcr_solver {
     int objective_sums(const double* objx, const T* Vm, bool with_u, int slot = 0, const double* objx2 = nullptr, bool after_ustep = false) {
         const int64_t nV = (int64_t)d2 * geo.ld, nU = (int64_t)n_users * geo.ld;
         const int nb = (int)std::min<int64_t>(512, std::max<int64_t>(1, cdiv(std::max(nV, nU), 4096)));
-        hipLaunchKernelGGL((k_obj3<T>), dim3(nb), dim3(PCR_EW_BLOCK), 0, st, objx, objx2, n_users, Vm, nV, with_u ? d_U.p : (const T*)nullptr, nU, d_partA.p);
+        hipLaunchKernelGGL((k_obj3<T>), dim3(nb), dim3(PCR_EW_BLOCK), 0, st, objx, objx2, n_users, Vm, nV, with_u ? d_U.p : (const T*)nullptr, nU, d_partA.p,
+                           objx == d_objp.p ? sh.uw : (const double*)nullptr);      // raw losses take their user's weight; objr carries it already
         // N ranks: ONE all-reduce of the four columns -- the per-user sums and |U|^2 are shard partials, |Vm|^2 (replicated) is
         // contributed by rank 0 alone
         const bool reduce = !single();
@@ -1341,6 +1355,45 @@ struct Solver final : pcr_solver {
         if (U) { RC(upload_mat(U + (local ? 0 : first_user * geo.r), n_users, d_U.p)); unorm_valid = false; }
         if (V) RC(upload_mat(V, d2, d_V.p));
         have_sorted = false; state_of_rejected_V = false;
+        return PCR_OK;
+    }
+    // Per-user loss weights c_u: uw[u] = c_u for the V side's sweeps, k_obj3 and k_ustep's objr; ulam[u] =
+    // lambda / c_u, divided here in fp64, is the regulariser of user u's Newton step -- the very double an unweighted solver
+    // created with lambda / c_u is handed.  The sorted state (raw per-user losses in objp) does not depend on the weights and
+    // stays; the objective sums a pipelined loop had queued do, and are dropped.
+    DBuf<double> d_uw, d_ulam;
+    int set_user_weights(const double* w, bool local) override {
+        if (tune.ustep_newton != 0 || tune.ustep_gram > 0 || tune.vblock_users > 0) {
+            pcr_set_error(std::string("pcr_solver_set_user_weights: this solver was created under pcr_tune \"") +
+                          (tune.ustep_newton != 0 ? "ustep_newton" : tune.ustep_gram > 0 ? "ustep_gram" : "vblock_users") +
+                          "\", whose kernels do not carry per-user weights");
+            return PCR_ERR_UNSUPPORTED;
+        }
+        for (const Bin& b : ubins)
+            if (b.gram) { pcr_set_error("pcr_solver_set_user_weights: the dual-form U-step class (k_ustep_gram) does not carry per-user weights"); return PCR_ERR_UNSUPPORTED; }
+        std::vector<double> hw, hl;
+        if (w) {
+            const double* mine = w + (local ? 0 : first_user);
+            hw.assign(mine, mine + n_users);
+            hl.resize((size_t)n_users);
+            for (int64_t u = 0; u < n_users; ++u) {
+                if (!(hw[(size_t)u] > 0.0) || !std::isfinite(hw[(size_t)u])) {
+                    pcr_set_error("pcr_solver_set_user_weights: the weight of user " + std::to_string(first_user + u) + " is not a finite number > 0");
+                    return PCR_ERR_ARG;
+                }
+                hl[(size_t)u] = prm.lambda / hw[(size_t)u];
+            }
+        }
+        RC(sync_checked());
+        if (ustep_pending) RC(ustep_finish(nullptr, nullptr));
+        start_sums_queued = false;
+        if (w) {
+            RC(d_uw.upload_n(hw.data(), hw.size()));
+            RC(d_ulam.upload_n(hl.data(), hl.size()));
+            sh.uw = d_uw.p; sh.ulam = d_ulam.p;
+        } else {
+            sh.uw = nullptr; sh.ulam = nullptr;
+        }
         return PCR_OK;
     }
     int get_factors(double* U, double* V, bool local) override {
@@ -1626,7 +1679,8 @@ struct Solver final : pcr_solver {
             // clusters: grid <= one workgroup per CU so that every member of every cluster is resident
             const int grid = b.ugrid;
             char* scr = d_scratch.p + (size_t)b.scratch_ofs * scratch_stride;
-#define LUS(BL, BG, KK, RS, UN, SY) hipLaunchKernelGGL((k_ustep<T, BL, BG, KK, RS, UN, SY>), dim3(grid), dim3(BL), lds, q, sh, geo, b.d_users.p, nus, d_U.p, d_V.p, prm.lambda, prm.stepsize, cg_max_u, cg_tol_u, strict(), strict(), b.cap, cap_pad, rsc, b.rcap, nchp, scr, scratch_stride, d_counters.p, cb, (tune.fault_cluster_member ? 1 : 0) | (tune.count_rows ? 2 : 0) | (state_of_rejected_V ? 4 : 0), b.wcap, dirp)
+#define LUS(BL, BG, KK, RS, UN, SY) do { if (sh.ulam) LUW(BL, BG, KK, RS, UN, SY, true); else LUW(BL, BG, KK, RS, UN, SY, false); } while (0)
+#define LUW(BL, BG, KK, RS, UN, SY, WT) hipLaunchKernelGGL((k_ustep<T, BL, BG, KK, RS, UN, SY, WT>), dim3(grid), dim3(BL), lds, q, sh, geo, b.d_users.p, nus, d_U.p, d_V.p, prm.lambda, prm.stepsize, cg_max_u, cg_tol_u, strict(), strict(), b.cap, cap_pad, rsc, b.rcap, nchp, scr, scratch_stride, d_counters.p, cb, (tune.fault_cluster_member ? 1 : 0) | (tune.count_rows ? 2 : 0) | (state_of_rejected_V ? 4 : 0), b.wcap, dirp)
 #define LU(BL, BG, KK, RS, UN) LUS(BL, BG, KK, RS, UN, 0)
 #define LU2(BL) do { if (b.sym) LUS(BL, false, 1, false, 4, 1); else LUS(BL, false, 1, false, 4, 0); } while (0)
 #ifndef PCR_NO_OPTIONAL_KERNELS
@@ -1649,6 +1703,7 @@ struct Solver final : pcr_solver {
             else LU2(512);
 #undef LU2
 #undef LU
+#undef LUW
 #undef LUS
         };
         RC(for_ubins(fn));
@@ -2083,6 +2138,8 @@ int pcr_solver_set_factors(pcr_solver* s, const double* U, const double* V) { S_
 int pcr_solver_get_factors(pcr_solver* s, double* U, double* V) { S_OR_ARG; PCR_ABI("pcr_solver_get_factors", s->get_factors(U, V, false)); }
 int pcr_solver_set_factors_local(pcr_solver* s, const double* U_local, const double* V) { S_OR_ARG; PCR_ABI("pcr_solver_set_factors_local", s->set_factors(U_local, V, true)); }
 int pcr_solver_get_factors_local(pcr_solver* s, double* U_local, double* V) { S_OR_ARG; PCR_ABI("pcr_solver_get_factors_local", s->get_factors(U_local, V, true)); }
+int pcr_solver_set_user_weights(pcr_solver* s, const double* w) { S_OR_ARG; PCR_ABI("pcr_solver_set_user_weights", s->set_user_weights(w, false)); }
+int pcr_solver_set_user_weights_local(pcr_solver* s, const double* w_local) { S_OR_ARG; PCR_ABI("pcr_solver_set_user_weights_local", s->set_user_weights(w_local, true)); }
 int pcr_comp_m(pcr_solver* s, double* m_out) { S_OR_ARG; PCR_ABI("pcr_comp_m", s->comp_m(m_out)); }
 int pcr_objective(pcr_solver* s, double* obj) { S_OR_ARG; PCR_ABI("pcr_objective", s->objective(obj)); }
 int pcr_obtain_g(pcr_solver* s, double* g) { S_OR_ARG; PCR_ABI("pcr_obtain_g", s->obtain_g(g)); }

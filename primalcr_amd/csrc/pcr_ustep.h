@@ -87,7 +87,9 @@ static inline size_t ustep_xch_bytes(int cap_pad, int ld, int K) {
 // that two workgroups share a CU: its CLS = 0 symbol is compiled under HIP's minimum-waves-per-SIMD bound (the second
 // __launch_bounds__ argument), which also caps the dynamic LDS a launch may ask for at half a CU's -- a class whose
 // per-rating arrays need more than that runs one workgroup per CU whatever its registers and takes the CLS = 1 symbol.
-template <typename T, int BLOCK, bool BIG, int K, bool RES, int UNR, int CLS = 0>
+// WT: per-user loss weights are set (Shard::uw / ulam != NULL): the instantiation whose lambda is the user's own, lambda / c_u.
+// WT = false is the unweighted problem's symbol, untouched by the weights.
+template <typename T, int BLOCK, bool BIG, int K, bool RES, int UNR, int CLS = 0, bool WT = false>
 __global__ __launch_bounds__(BLOCK, (BLOCK == 512 && UNR == 4 && !RES && K == 1 && !BIG && CLS == 0 && sizeof(T) == 4) ? 4 : 1) void k_ustep(Shard<T> S, Geo geo, const int32_t* __restrict__ users, int nusers,
                                                  T* __restrict__ U, const T* __restrict__ Vm, double lambda, double stepsize0,
                                                  int cg_max, double cg_tol, int strict, int solver1, int cap, int cap_pad, int rs_cap, int rcap, int nchp,
@@ -176,6 +178,10 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == 512 && UNR == 4 && !RES && K == 1 
         const int n = (int)(S.uptr[u + 1] - s0);
         const int nlev = (int)(S.runofs[u + 1] - S.runofs[u]) - 1;
         const int r0 = (int)((int64_t)n * mem / K), r1 = (int)((int64_t)n * (mem + 1) / K);
+        // per-user loss weight c_u (Shard::uw): c_u L_u(u) + lambda/2 |u|^2 = c_u (L_u(u) + (lambda/c_u)/2 |u|^2), so the
+        // user's whole step -- gradient, CG, line search, skip test, the state it leaves -- is the unweighted one at lam = lambda / c_u
+        double lam = lambda;
+        if constexpr (WT) lam = S.ulam[u];
         const int q0 = r0, q1 = RES ? min(r1, r0 + rcap) : r0;       // rows [q0, q1) are LDS-resident, [q1, r1) stay in L2
         // out[p] = vec . V[item p] over this member's rows
         auto sddmm = [&](T* out) {
@@ -229,7 +235,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == 512 && UNR == 4 && !RES && K == 1 
             key[p] = (T)(wl ? sweep_coeff_win(winL + (size_t)p * S.ws, Sx, rs, nlev, lv0[p], (double)ms0[p], 1.0)
                          : win ? sweep_coeff_cached<T>(S, (size_t)s0 + p, Sx, rs, nlev, lv0[p], (double)ms0[p], 1.0)
                                : sweep_coeff<T>(ms0, Sx, rs, nlev, lv0[p], ms0[p], (double)ms0[p], 1.0, strict));
-        for (int t = tid; t < ld; t += BLOCK) gvec[t] = (n == 0) ? 0.0 : uvec[t] * lambda;   // :495-498
+        for (int t = tid; t < ld; t += BLOCK) gvec[t] = (n == 0) ? 0.0 : uvec[t] * lam;   // :495-498
         if (RES) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // the LDS-DMA of stage_rows
         __syncthreads();
         UPROF(1);
@@ -242,7 +248,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == 512 && UNR == 4 && !RES && K == 1 
         // ---- prev_obj, objective_u_new (pcrpp.cpp:542-573)
         // the user's loss at the gradient point is what the last k_prepare left in objp[u] (same m, same windows):
         // no need to sweep for it again
-        const double prev_obj = lambda / 2.0 * un2 + S.objp[u];
+        const double prev_obj = lam / 2.0 * un2 + S.objp[u];
         double obj_new = prev_obj, loss_new = 0.0;
         int n_cg = 0, n_ls = 0, ls_free = 0;
         // pcrpp.cpp:787-790; PrimalCR additionally keeps u when no comparable pair exists
@@ -270,7 +276,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == 512 && UNR == 4 && !RES && K == 1 
             ls_free = mrec ? 1 : 0;
             __syncthreads();
             for (int k = 1; k <= (have_dir ? 0 : cg_max); ++k) {                // 10 in the reference (:636)
-                for (int t = tid; t < ld; t += BLOCK) { vecT[t] = (T)pv[t]; Hp[t] = pv[t] * lambda; }
+                for (int t = tid; t < ld; t += BLOCK) { vecT[t] = (T)pv[t]; Hp[t] = pv[t] * lam; }
                 __syncthreads();
                 sddmm(key);                                                     // b = V_I p  (:592-594)
                 __syncthreads();
@@ -355,7 +361,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == 512 && UNR == 4 && !RES && K == 1 
                     loss_new = block_objective_win<T, BLOCK>(key, [&](int p) { return (int)LiOps<LI>::lev(li[p]); }, rs, nlev, n, winL, S.ws, Sx, red);
                 } else
                     loss_new = block_objective<T, BLOCK>(key, [&](int p) { return (int)LiOps<LI>::lev(li[p]); }, rs, nlev, n, Sx, red, strict);
-                obj_new = lambda / 2.0 * nn + loss_new;
+                obj_new = lam / 2.0 * nn + loss_new;
                 ++n_ls;
                 UPROF(9);
                 if (obj_new < prev_obj) break;
@@ -394,7 +400,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == 512 && UNR == 4 && !RES && K == 1 
         }
         if (mem == 0) for (int t = tid; t < ld; t += BLOCK) U[(size_t)u * ld + t] = (T)unew[t];
         if (tid == 0 && mem == 0) {
-            S.objr[u] = obj_new;
+            S.objr[u] = WT ? S.uw[u] * obj_new : obj_new;         // the user's term of the weighted objective; objp stays the raw loss
             if (!skip) S.objp[u] = loss_new;
             if (n_cg) atomicAdd(counters + 0, (unsigned long long)n_cg);
             if (n_ls) atomicAdd(counters + 1, (unsigned long long)n_ls);

@@ -264,7 +264,9 @@ static inline size_t vsweep_bytes(int cap, int rs_cap, bool two) {      // two: 
 }
 
 // body of k_vsweep: workgroup `blk` of `nblk` walks users blk, blk + nblk, ...
-template <typename T, int BLOCK, bool BIG, bool HV>
+// WT (every sweep kernel): per-user loss weights are set (Shard::uw != NULL) -- the instantiation that multiplies the coefficients
+// of user u by c_u; WT = false is the unweighted problem's symbol, untouched by the weights
+template <typename T, int BLOCK, bool BIG, bool HV, bool WT = false>
 __device__ __forceinline__ void vsweep_block_body(char* smem, const Shard<T>& S, const int32_t* __restrict__ users, int nusers,
                                                   const T* __restrict__ bsrc, T* __restrict__ c_out, int cap, int rs_cap,
                                                   char* scratch, size_t stride, int strict, int blk, int nblk, int flags = 0) {
@@ -284,6 +286,9 @@ __device__ __forceinline__ void vsweep_block_body(char* smem, const Shard<T>& S,
         const int n = (int)(S.uptr[u + 1] - s0);
         const int nlev = (int)(S.runofs[u + 1] - S.runofs[u]) - 1;
         if (n == 0) continue;
+        // the user's loss weight c_u (NULL: the unweighted problem): gradient and Hessian-vector products are sum_u c_u (user u's share)
+        double cu = 1.0;
+        if constexpr (WT) cu = S.uw[u];
         if (!HV || !S.ws) {
 #pragma unroll 4
             for (int p = tid; p < n; p += BLOCK) ms[p] = S.ms[s0 + p];
@@ -297,7 +302,7 @@ __device__ __forceinline__ void vsweep_block_body(char* smem, const Shard<T>& S,
         }
         __syncthreads();
         block_excl_scan<BLOCK>([&](int i) { return (double)xs[i]; }, Sx, n, red);
-        if (S.ws == 4 && S.w16 && pf4) { sweep_out4<T, BLOCK, HV>(S, s0, n, nlev, tid, xs, Sx, rs, c_out); __syncthreads(); continue; }
+        if (S.ws == 4 && S.w16 && pf4) { sweep_out4<T, BLOCK, HV, WT>(S, s0, n, nlev, tid, xs, Sx, rs, c_out, cu); __syncthreads(); continue; }
         for (int p = tid; p < n; p += BLOCK) {
             const int lev = S.slvl[s0 + p];
             const double c = S.ws
@@ -306,19 +311,19 @@ __device__ __forceinline__ void vsweep_block_body(char* smem, const Shard<T>& S,
             // c goes out in CSR order -- a permutation inside this user's own segment, so the lines it touches are written in
             // full by this workgroup (staging the permutation through LDS was measured slower: 2.11 against 1.65 ms per
             // launch on the Netflix shape, the extra array costs occupancy)
-            c_out[s0 + S.sidx[s0 + p]] = (T)c;
+            c_out[s0 + S.sidx[s0 + p]] = (T)(WT ? c * cu : c);
         }
         __syncthreads();
     }
 }
-template <typename T, int BLOCK, bool BIG, bool HV>
+template <typename T, int BLOCK, bool BIG, bool HV, bool WT = false>
 __global__ __launch_bounds__(BLOCK) void k_vsweep(Shard<T> S, Geo geo, const int32_t* __restrict__ users, int nusers,
                                                   const T* __restrict__ bsrc, T* __restrict__ c_out,
                                                   int cap, int rs_cap, char* scratch, size_t stride, int strict, const int* skip,
                                                   int b_csr) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (skip && *skip) return;
-    vsweep_block_body<T, BLOCK, BIG, HV>(smem, S, users, nusers, bsrc, c_out, cap, rs_cap, scratch, stride, strict,
+    vsweep_block_body<T, BLOCK, BIG, HV, WT>(smem, S, users, nusers, bsrc, c_out, cap, rs_cap, scratch, stride, strict,
                                          (int)blockIdx.x, (int)gridDim.x, b_csr);
 }
 
@@ -330,7 +335,7 @@ static inline size_t vsweep_wave_bytes(int cap, int rs_cap, bool two) {      // 
     return carve_bytes(cap, sizeof(T)) * (two ? 2 : 1) + carve_bytes(cap + 1, 8) + carve_bytes(rs_cap, 4);
 }
 // body: this wave sweeps user number ui of the list
-template <typename T, bool HV>
+template <typename T, bool HV, bool WT = false>
 __device__ __forceinline__ void vsweep_wave_body(char* smem, const Shard<T>& S, const int32_t* __restrict__ users, int nusers,
                                                  const T* __restrict__ bsrc, T* __restrict__ c_out,
                                                  int cap, int rs_cap, size_t wave_bytes, int strict, int ui, int flags = 0) {
@@ -347,6 +352,8 @@ __device__ __forceinline__ void vsweep_wave_body(char* smem, const Shard<T>& S, 
     const int n = (int)(S.uptr[u + 1] - s0);
     const int nlev = (int)(S.runofs[u + 1] - S.runofs[u]) - 1;
     if (n == 0) return;
+    double cu = 1.0;                                        // the user's loss weight, as in vsweep_block_body
+    if constexpr (WT) cu = S.uw[u];
     if (!HV || !S.ws) {
 #pragma unroll 4
         for (int p = lane; p < n; p += 64) ms[p] = S.ms[s0 + p];
@@ -369,22 +376,22 @@ __device__ __forceinline__ void vsweep_wave_body(char* smem, const Shard<T>& S, 
     }
     if (lane == 0) Sx[n] = carry;
     wave_sync();
-    if (S.ws == 4 && S.w16 && pf4) { sweep_out4<T, 64, HV>(S, s0, n, nlev, lane, xs, Sx, rs, c_out); return; }
+    if (S.ws == 4 && S.w16 && pf4) { sweep_out4<T, 64, HV, WT>(S, s0, n, nlev, lane, xs, Sx, rs, c_out, cu); return; }
     for (int p = lane; p < n; p += 64) {
         const int lev = S.slvl[s0 + p];
         const double c = S.ws
             ? sweep_coeff_cached<T>(S, (size_t)(s0 + p), Sx, rs, nlev, lev, (double)xs[p], HV ? 0.0 : 1.0)
             : sweep_coeff<T>(ms, Sx, rs, nlev, lev, ms[p], (double)xs[p], HV ? 0.0 : 1.0, strict);
-        c_out[s0 + S.sidx[s0 + p]] = (T)c;
+        c_out[s0 + S.sidx[s0 + p]] = (T)(WT ? c * cu : c);
     }
 }
-template <typename T, bool HV>
+template <typename T, bool HV, bool WT = false>
 __global__ __launch_bounds__(256) void k_vsweep_wave(Shard<T> S, const int32_t* __restrict__ users, int nusers,
                                                      const T* __restrict__ bsrc, T* __restrict__ c_out,
                                                      int cap, int rs_cap, size_t wave_bytes, int strict, const int* skip, int b_csr) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (skip && *skip) return;
-    vsweep_wave_body<T, HV>(smem, S, users, nusers, bsrc, c_out, cap, rs_cap, wave_bytes, strict,
+    vsweep_wave_body<T, HV, WT>(smem, S, users, nusers, bsrc, c_out, cap, rs_cap, wave_bytes, strict,
                             (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), b_csr);
 }
 
@@ -393,7 +400,7 @@ __global__ __launch_bounds__(256) void k_vsweep_wave(Shard<T> S, const int32_t* 
 // take the long users of list B one per workgroup, the others take eight short users of list A, one per wave.
 // MINW: the minimum-waves-per-SIMD bound of the symbol (8: at most 64 VGPRs -- four 512-thread workgroups per CU instead of three --
 // which also caps the launch's dynamic LDS at a quarter of a CU's: for shards whose longest users fit 40 KB; 1: no bound)
-template <typename T, bool HV, int WB, int MINW = 1>
+template <typename T, bool HV, int WB, int MINW = 1, bool WT = false>
 __global__ __launch_bounds__(WB, MINW) void k_vsweep_all(Shard<T> S, const int32_t* __restrict__ users_a, int nusers_a, int cap_a,
                                                     int rs_cap_a, size_t wave_bytes, const int32_t* __restrict__ users_b,
                                                     int nusers_b, int cap_b, int rs_cap_b, int nblk_b,
@@ -401,10 +408,10 @@ __global__ __launch_bounds__(WB, MINW) void k_vsweep_all(Shard<T> S, const int32
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (skip && *skip) return;
     if ((int)blockIdx.x < nblk_b)
-        vsweep_block_body<T, WB, false, HV>(smem, S, users_b, nusers_b, bsrc, c_out, cap_b, rs_cap_b, nullptr, 0, strict,
+        vsweep_block_body<T, WB, false, HV, WT>(smem, S, users_b, nusers_b, bsrc, c_out, cap_b, rs_cap_b, nullptr, 0, strict,
                                             (int)blockIdx.x, nblk_b, b_csr);
     else
-        vsweep_wave_body<T, HV>(smem, S, users_a, nusers_a, bsrc, c_out, cap_a, rs_cap_a, wave_bytes, strict,
+        vsweep_wave_body<T, HV, WT>(smem, S, users_a, nusers_a, bsrc, c_out, cap_a, rs_cap_a, wave_bytes, strict,
                                 ((int)blockIdx.x - nblk_b) * (WB / 64) + (int)(threadIdx.x >> 6), b_csr);
 }
 

@@ -42,6 +42,8 @@ NO_SOLVER(pcr_solver_shard, const pcr_solver*, int64_t*, int64_t*, int64_t*)
 NO_SOLVER(pcr_solver_set_factors, pcr_solver*, const double*, const double*)
 NO_SOLVER(pcr_solver_get_factors, pcr_solver*, double*, double*)
 NO_SOLVER(pcr_solver_set_factors_local, pcr_solver*, const double*, const double*)
+NO_SOLVER(pcr_solver_set_user_weights, pcr_solver*, const double*)
+NO_SOLVER(pcr_solver_set_user_weights_local, pcr_solver*, const double*)
 NO_SOLVER(pcr_solver_get_factors_local, pcr_solver*, double*, double*)
 NO_SOLVER(pcr_comp_m, pcr_solver*, double*)
 NO_SOLVER(pcr_objective, pcr_solver*, double*)
