@@ -1,7 +1,8 @@
-// pcr_dev.h -- host-side device infrastructure shared by the two HIP translation units (pcr_solver.hip: training,
-// pcr_serve.hip: recommendation and its metrics): error macros, the RAII device buffer, the factor upload, the profiler, the
-// solver's base class with the ServeView it hands to the serving layer, and the C ABI's exception guard.
-// Everything here is a template, a class or static inline: no non-template kernel is compiled into both units.
+// pcr_dev.h -- host-side device infrastructure shared by the three HIP translation units (pcr_solver.hip: training,
+// pcr_serve.hip: recommendation and its metrics, pcr_fold.hip: the fold-in families): error macros, the RAII device buffer, the
+// factor upload, the profiler, the solver's base class with the ServeView it hands to the two serving units, what both of them
+// need around that view (ModelDev, model_device, solver_view, by_precision), and the C ABI's exception guard.
+// Everything here is a template, a class or static inline: no non-template kernel is compiled into two units.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -29,6 +30,8 @@
 
 static inline int host_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// the LDS of a CU: what a serving kernel's workgroup may ask for, and what the workgroups per CU are counted against
+static const size_t PCR_LDS_CU = (size_t)160 * 1024;
 
 // device buffer with RAII
 template <typename X>
@@ -153,7 +156,7 @@ struct ProfScope {
 };
 
 // What the serving layer reads of a trained model: a solver's device state (pcr_solver::serve_view) or the model one call
-// uploaded (ModelDev of pcr_serve.hip).  Plain pointers, nothing is owned or written through them.
+// uploaded (ModelDev below).  Plain pointers, nothing is owned or written through them.
 struct pcr_solver;
 enum ServeExchange { SERVE_LOCAL = 0, SERVE_RCCL, SERVE_P2P };     // no exchange step (one shard, or shard-local mode) / which communicator
 struct ServeView {
@@ -179,6 +182,11 @@ struct ServeView {
     int sum(double* dev, size_t count) const;  // dev[0..count) summed across the ranks, in place, on st
     int wait() const;                          // synchronises st; a peer-to-peer exchange that missed its deadline is reported here
 };
+template <typename T> static const T* serve_U(const ServeView& v) { return static_cast<const T*>(v.U); }
+template <typename T> static const T* serve_V(const ServeView& v) { return static_cast<const T*>(v.V); }
+// run(T()) for the view's precision
+template <class F>
+static int by_precision(const ServeView& v, F&& run) { return v.dtype == PCR_F64 ? run(0.0) : run(0.0f); }
 struct ServeState;                             // the serving layer's cached device tables (pcr_serve.hip)
 
 struct pcr_solver {
@@ -223,12 +231,60 @@ struct pcr_solver {
     // CCDR1 only (pcr_ccd.h): the "ccd_residual_mismatch" counter, pcr_solver_set_ccd_params
     virtual int residual_mismatch(double*) { pcr_set_error("pcr_solver_counter: 'ccd_residual_mismatch' exists on a CCDR1 solver only"); return PCR_ERR_STATE; }
     virtual int set_ccd_params(const pcr_ccd_params*) { pcr_set_error("pcr_solver_set_ccd_params: not a CCDR1 solver (solver type 0)"); return PCR_ERR_STATE; }
-    // the serving layer (pcr_serve.hip): the view of this solver's factors and shard, the exchange behind ServeView::sum (sync()
+    // the serving layer (pcr_serve.hip, pcr_fold.hip): the view of this solver's factors and shard, the exchange behind ServeView::sum (sync()
     // is ServeView::wait), the tables it keeps between calls
     virtual void serve_view(ServeView* v) = 0;
     virtual int allreduce_f64(double*, size_t) { return PCR_OK; }
     std::unique_ptr<ServeState> serve;
 };
+
+// s's view for one call: the launches are timed in s's profiler (that of a CCDR1 solver, not of the Solver<T> it holds)
+static inline ServeView solver_view(pcr_solver* s, int flags) {
+    ServeView v;
+    s->serve_view(&v); v.exclude = (flags & PCR_REC_EXCLUDE_TRAIN) != 0;
+    return v;
+}
+
+// A model in host memory on the device for one call: the exclusion CSR (item-ascending rows: a CSR that is not gets a sorted
+// copy, for the kernel's cursor) and both host fp64 factors in the requested type, rows padded to ld: U then V in one buffer.
+// open() fills the view: the default stream, nothing profiled, nothing exchanged.
+struct ModelDev {
+    DBuf<int64_t> dx;
+    DBuf<int32_t> di;
+    DBuf<char> F;
+    int open(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item, bool sorted,
+             int dtype, ServeView* v) {
+        if (index) {
+            std::vector<int32_t> sitem;
+            const int64_t nnz = index[d1];
+            if (!sorted) {
+                sitem.assign(item, item + nnz);
+                pcr_parallel_ranges(d1, pcr_host_threads(), [&](int, int64_t lo, int64_t hi) {
+                    for (int64_t u = lo; u < hi; ++u) std::sort(sitem.begin() + index[u], sitem.begin() + index[u + 1]);
+                });
+            }
+            RC(dx.upload_n(index, (size_t)d1 + 1)); RC(di.upload_n(sorted ? item : sitem.data(), (size_t)nnz));
+        }
+        const int ld = ((int)k + 3) & ~3;
+        const size_t row = (size_t)ld * (dtype == PCR_F64 ? sizeof(double) : sizeof(float));
+        const int64_t ur = U ? d1 : 0;             // (U NULL: pcr_evaluate_lists_model scores nothing and brings no user factors)
+        RC(F.alloc((size_t)(ur + d2) * row));
+        char* dV = F.p + (size_t)ur * row;
+        if (dtype == PCR_F64) RC(upload_rows<double>(v->st, (int)k, ld, {{U, ur, (double*)F.p}, {V, d2, (double*)dV}}));
+        else RC(upload_rows<float>(v->st, (int)k, ld, {{U, ur, (float*)F.p}, {V, d2, (float*)dV}}));
+        v->dtype = dtype; v->U = F.p; v->V = dV; v->r = (int)k; v->ld = ld; v->rows = v->d1 = d1; v->d2 = d2;
+        v->uptr = dx.p; v->item = di.p; v->nnz = index ? index[d1] : 0;
+        return PCR_OK;
+    }
+};
+
+static inline int model_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { pcr_set_error("no HIP device available"); return PCR_ERR_DEVICE; }
+    if (device < 0 || device >= ndev) { pcr_set_error("device ordinal out of range"); return PCR_ERR_ARG; }
+    HIPCHK(hipSetDevice(device));
+    return PCR_OK;
+}
 
 // ------------------------------------------------------------------------------------------ C ABI
 // No C++ exception may cross the C ABI (a host allocation that fails while a 700 M-rating shard is being set up is an error

@@ -1,0 +1,483 @@
+// pcr_fold.hip -- the fold-in families behind the C ABI of include/primalcr.h: rows for users or items the model was not trained
+// on, against the fixed other factor.  Four families, each a solver entry and a _model entry over one ServeView (pcr_dev.h):
+//   pcr_fold_in          new users of a ranking model     k_foldin (pcr_foldin.h)                    "foldin/newton"
+//   pcr_fold_in_ridge    squared loss                     k_ridge_direct, k_ridge_cg (pcr_ridge.h)   "foldin/ridge"
+//   pcr_fold_in_nnls     squared loss, row >= 0           k_nnls_direct, k_nnls_cg (pcr_nnls.h)      "foldin/nnls"
+//   pcr_fold_in_items    new items of a ranking model     k_rater_scores, k_itemfold (pcr_itemfold.h) "itemfold/scores", "itemfold/newton"
+// A run uploads its plan (pcr_host.cpp built and checked it), launches one kernel per workgroup form inside the family's profile
+// slot -- workgroups stride over their range, the longest rows first -- and hands the rows, the stats and the per-row records
+// back through one FoldOut.  Recommendation and its metrics are pcr_serve.hip, training is pcr_solver.hip.
+// There is NO CPU compute path in this file: every [device] entry point fails with PCR_ERR_DEVICE when HIP is unusable.
+#include "pcr_dev.h"
+#include "pcr_foldin.h"
+#include "pcr_itemfold.h"
+#include "pcr_ridge.h"
+#include "pcr_nnls.h"
+#include "pcr_prims.h"
+
+static int device_cus(int* cus) {
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    HIPCHK(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev));
+    *cus = std::max(*cus, 1);
+    return PCR_OK;
+}
+
+// What a run hands back: the n rows in the storage type (ld values each), widened to fp64 for the caller, and the per-row
+// records of `fields` doubles the kernels write
+template <typename T>
+struct FoldOut {
+    int64_t n = 0;
+    int fields = 0;
+    DBuf<T> rows;
+    DBuf<double> per, rowsD;
+    int alloc(const ServeView& v, int64_t n_, int fields_) {
+        n = n_; fields = fields_;
+        RC(rows.alloc((size_t)n * v.ld)); RC(per.alloc((size_t)n * fields)); RC(rowsD.alloc((size_t)n * v.r));
+        return PCR_OK;
+    }
+    // the rows to out [n][r], the records to stats(records) and, if asked for, to per_row [n][fields]; synchronises v.st
+    template <class Stats>
+    int finish(const ServeView& v, double* out, double* per_row, Stats&& stats) {
+        hipLaunchKernelGGL((k_mat_out<T>), dim3((unsigned)std::min<int64_t>(1 << 16, cdiv(n * v.r, 256))), dim3(256), 0, v.st, (const T*)rows.p, rowsD.p, n, v.r, v.ld);
+        HIPCHK(hipGetLastError());
+        std::vector<double> hp((size_t)n * fields);
+        HIPCHK(hipMemcpyAsync(out, rowsD.p, (size_t)n * v.r * sizeof(double), hipMemcpyDeviceToHost, v.st));
+        HIPCHK(hipMemcpyAsync(hp.data(), per.p, hp.size() * sizeof(double), hipMemcpyDeviceToHost, v.st));
+        HIPCHK(hipStreamSynchronize(v.st));
+        stats(hp.data());
+        if (per_row) std::copy(hp.begin(), hp.end(), per_row);
+        return PCR_OK;
+    }
+};
+
+// The grid of a launch over count rows: at most cap workgroups per CU (fold_wg_cap: the forms' cap by workgroup size) and as many
+// as their lds bytes each leave room for
+static int fold_wg_cap(int block) { return block == 64 ? 16 : block == 256 ? 4 : 1; }
+static int64_t fold_grid(int64_t count, int cus, int cap, size_t lds) {
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(cap, PCR_LDS_CU / lds));
+    return std::min<int64_t>(count, (int64_t)cus * per_cu);
+}
+// The scratch form (BIG) of k_foldin / k_itemfold: a slice of arr bytes, in steps of 256, per workgroup and at most FOLD_SCRATCH
+// bytes in all, which bounds the grid
+static const size_t FOLD_SCRATCH = (size_t)1 << 30;
+static int fold_slices(size_t arr, int64_t* grid, size_t* stride, DBuf<char>& scratch) {
+    *stride = (arr + 255) & ~(size_t)255;
+    *grid = std::max<int64_t>(1, std::min<int64_t>(*grid, (int64_t)(FOLD_SCRATCH / *stride)));
+    return scratch.alloc((size_t)*grid * *stride);
+}
+// kernel<<<grid, block, lds, st>>>(args...) with lds bytes of dynamic LDS allowed
+template <class... P, class... A>
+static int fold_launch(void (*kernel)(P...), int64_t grid, int block, size_t lds, hipStream_t st, A... args) {
+    HIPCHK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), lds, st, static_cast<P>(args)...);
+    HIPCHK(hipGetLastError());
+    return PCR_OK;
+}
+
+// Fold-in (pcr_fold_in, pcr_fold_in_model; k_foldin of pcr_foldin.h) of the plan's users against v's V: the ratings, their
+// levels and the users' order go to the device, then one launch per workgroup form -- P.order is by descending length, so the
+// forms are ranges of it and the longest users of each start first.  A launch's LDS is sized by its longest user.
+struct FoldinParams { int solver_type; double lambda, stepsize; int cg_max; double cg_tol; int steps; };
+static FoldinParams foldin_params_of(const pcr_params& p, int steps) { return {p.solver_type, p.lambda, p.stepsize, p.cg_max_iter, p.cg_tol, steps}; }
+template <typename T, int BLOCK, bool BIG>
+static int foldin_launch(const ServeView& v, const FoldinParams& c, const PcrFoldinPlan& P, const FoldinCsr& X, const Geo& geo, const int32_t* d_order,
+                         int64_t first, int64_t count, int cus, const T* dU0, T* dOut, double* dPer, DBuf<char>& scratch) {
+    if (count <= 0) return PCR_OK;
+    const std::vector<int64_t>& idx = P.X.index;
+    const int32_t longest = P.order[(size_t)first];
+    const int cap = (int)std::max<int64_t>(1, idx[(size_t)longest + 1] - idx[(size_t)longest]);
+    int rs_cap = 1;
+    for (int64_t i = first; i < first + count; ++i) {
+        const int32_t u = P.order[(size_t)i];
+        rs_cap = std::max(rs_cap, (int)(P.lv.run_ofs[(size_t)u + 1] - P.lv.run_ofs[(size_t)u]));
+    }
+    const size_t li_bytes = BIG ? 8 : 4, arr = foldin_arr_bytes(cap, rs_cap, sizeof(T), li_bytes);
+    const size_t lds = fold_small_bytes(geo.ld, BLOCK, sizeof(T)) + (BIG ? 0 : arr);
+    if (lds > PCR_LDS_CU) {
+        pcr_set_error("fold-in: rank " + std::to_string(geo.r) + " (with " + std::to_string(rs_cap - 1) + " rating levels) is too large for the kernel's LDS");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    int64_t grid = fold_grid(count, cus, fold_wg_cap(BLOCK), lds);
+    size_t stride = 0;
+    if (BIG) RC(fold_slices(arr, &grid, &stride, scratch));
+    const int pcr1 = c.solver_type == PCR_SOLVER_PCR ? 1 : 0;
+    return fold_launch(k_foldin<T, BLOCK, BIG>, grid, BLOCK, lds, v.st, X, geo, d_order + first, (int)count, dU0, dOut, serve_V<T>(v), dPer, c.lambda,
+                       c.stepsize, c.cg_max, c.cg_tol, c.steps, pcr1, pcr1, cap, rs_cap, scratch.p, stride);
+}
+
+template <typename T>
+static int foldin_run(const ServeView& v, const FoldinParams& c, const PcrFoldinPlan& P, const double* U0, double* U_out, pcr_foldin_stats* stats,
+                      double* per_user) {
+    const int64_t n = P.X.d1;
+    hipStream_t st = v.st;
+    Geo geo;
+    geo.r = v.r; geo.ld = v.ld; geo.nchunk = v.ld / VecOf<T>::N; geo.G = std::min(64, host_pow2(geo.nchunk));
+    int cus = 0;
+    RC(device_cus(&cus));
+    DBuf<int64_t> uptr, runofs;
+    DBuf<int32_t> item, runstart, order;
+    DBuf<uint16_t> lvl;
+    DBuf<T> dU0;
+    DBuf<char> scratch;
+    FoldOut<T> out;
+    RC(uptr.upload(P.X.index, st)); RC(item.upload_n(P.X.item.data(), P.X.item.size()));
+    RC(lvl.upload(P.lv.level, st)); RC(runofs.upload(P.lv.run_ofs, st)); RC(runstart.upload(P.lv.run_start, st));
+    RC(order.upload(P.order, st));
+    RC(dU0.alloc((size_t)n * v.ld)); RC(out.alloc(v, n, PCR_FOLDIN_FIELDS));
+    if (U0) RC(upload_rows<T>(st, v.r, v.ld, {{U0, n, dU0.p}}));
+    else HIPCHK(hipMemsetAsync(dU0.p, 0, (size_t)n * v.ld * sizeof(T), st));
+    const FoldinCsr X = {uptr.p, item.p, lvl.p, runofs.p, runstart.p};
+    {
+        ProfScope ps(v.prof, "foldin/newton", st);
+        const int64_t nw = n - P.n_big - P.n_lds;
+        RC((foldin_launch<T, 512, true>(v, c, P, X, geo, order.p, 0, P.n_big, cus, dU0.p, out.rows.p, out.per.p, scratch)));
+        RC((foldin_launch<T, 256, false>(v, c, P, X, geo, order.p, P.n_big, P.n_lds, cus, dU0.p, out.rows.p, out.per.p, scratch)));
+        RC((foldin_launch<T, 64, false>(v, c, P, X, geo, order.p, P.n_big + P.n_lds, nw, cus, dU0.p, out.rows.p, out.per.p, scratch)));
+    }
+    return out.finish(v, U_out, per_user, [&](const double* hp) { if (stats) pcr_foldin_stats_from(hp, n, stats); });
+}
+
+// Ridge fold-in (pcr_fold_in_ridge*; pcr_ridge.h) and non-negative fold-in (pcr_fold_in_nnls*; pcr_nnls.h) of the plan's users
+// against v's V are one run over a family: the ratings and the users' order go to the device, then one launch per range of the
+// plan -- a (form, workgroup size, tile count) class, its LDS sized by the class (nnls: form and workgroup size follow from the
+// rank: one range).  The family names its kernels and their LDS, its slot and messages, the tile counts its direct kernel takes,
+// and its records.
+struct RidgeFamily {
+    typedef pcr_ridge_stats Stats;
+    static constexpr int FIELDS = PCR_RIDGE_FIELDS, CG = PCR_RIDGE_CG;
+    static constexpr const char *slot = "foldin/ridge", *name = "ridge", *direct_lds = "direct forms'";
+    static void stats_from(const double* hp, int64_t n, Stats* s) { pcr_ridge_stats_from(hp, n, s); }
+    static size_t cg_bytes(int ld) { return ridge_cg_bytes(ld); }
+    static size_t direct_bytes(int mp, int ld, int block) { return ridge_direct_bytes(mp, ld, block); }
+    static bool tiles_ok(int mp, int, int block) { return mp >= 16 && mp <= (block == 64 ? 64 : PCR_RIDGE_DIRECT_MAX); }
+    template <typename T> static auto cg() { return k_ridge_cg<T>; }
+    template <typename T, int BLOCK, class... A>
+    static int direct(int64_t grid, size_t lds, hipStream_t st, int form, int mp, A... args) {
+        return fold_launch(k_ridge_direct<T, BLOCK>, grid, BLOCK, lds, st, args..., form == PCR_RIDGE_DUAL ? 1 : 0, mp);
+    }
+};
+struct NnlsFamily {
+    typedef pcr_nnls_stats Stats;
+    static constexpr int FIELDS = PCR_NNLS_FIELDS, CG = PCR_NNLS_CG;
+    static constexpr const char *slot = "foldin/nnls", *name = "nnls", *direct_lds = "direct form's";
+    static void stats_from(const double* hp, int64_t n, Stats* s) { pcr_nnls_stats_from(hp, n, s); }
+    static size_t cg_bytes(int ld) { return nnls_cg_bytes(ld); }
+    static size_t direct_bytes(int mp, int ld, int block) { return nnls_direct_bytes(mp, ld, block); }
+    static bool tiles_ok(int mp, int r, int block) { return mp >= 16 && mp >= r && mp <= (block == 64 ? 64 : PCR_RIDGE_DIRECT_MAX); }
+    template <typename T> static auto cg() { return k_nnls_cg<T>; }
+    template <typename T, int BLOCK, class... A>
+    static int direct(int64_t grid, size_t lds, hipStream_t st, int, int mp, A... args) {
+        return fold_launch(k_nnls_direct<T, BLOCK>, grid, BLOCK, lds, st, args..., mp);
+    }
+};
+template <class Fam, typename T>
+static int ridge_run(const ServeView& v, double lambda, int weighted, const PcrRidgePlan& P, double* U_out, typename Fam::Stats* stats, double* per_user) {
+    const int64_t n = P.X.d1;
+    hipStream_t st = v.st;
+    int cus = 0;
+    RC(device_cus(&cus));
+    DBuf<int64_t> uptr;
+    DBuf<int32_t> item, order;
+    DBuf<double> val;
+    FoldOut<T> out;
+    RC(uptr.upload(P.X.index, st)); RC(item.upload_n(P.X.item.data(), P.X.item.size())); RC(val.upload_n(P.X.val.data(), P.X.val.size()));
+    RC(order.upload(P.order, st));
+    RC(out.alloc(v, n, Fam::FIELDS));
+    const RidgeCsr X = {uptr.p, item.p, val.p};
+    const T* F = serve_V<T>(v);
+    const std::string who = std::string(Fam::name) + " fold-in: ";
+    {
+        ProfScope ps(v.prof, Fam::slot, st);
+        for (const PcrRidgePlan::Range& g : P.ranges) {
+            if (g.count <= 0) continue;
+            const int32_t* users = order.p + g.first;
+            if (g.form == Fam::CG) {
+                const size_t lds = Fam::cg_bytes(v.ld);
+                if (lds > PCR_LDS_CU) { pcr_set_error(who + "rank " + std::to_string(v.r) + " is too large for the CG form's LDS"); return PCR_ERR_UNSUPPORTED; }
+                RC(fold_launch(Fam::template cg<T>(), fold_grid(g.count, cus, 8, lds), 256, lds, st, X, users, (int)g.count, F, v.r, v.ld, out.rows.p,
+                               out.per.p, lambda, weighted));
+                continue;
+            }
+            const int mp = g.tiles * 16;
+            if (!Fam::tiles_ok(mp, v.r, g.block)) { pcr_set_error(who + "a launch class outside the kernel's tile range"); return PCR_ERR_STATE; }
+            const size_t lds = Fam::direct_bytes(mp, v.ld, g.block);
+            if (lds > PCR_LDS_CU) {
+                pcr_set_error(who + "rank " + std::to_string(v.r) + " is too large for the " + Fam::direct_lds + " LDS");
+                return PCR_ERR_UNSUPPORTED;
+            }
+            const int64_t grid = fold_grid(g.count, cus, fold_wg_cap(g.block), lds);
+            if (g.block == 64) RC((Fam::template direct<T, 64>(grid, lds, st, g.form, mp, X, users, (int)g.count, F, v.r, v.ld, out.rows.p, out.per.p, lambda, weighted)));
+            else RC((Fam::template direct<T, 256>(grid, lds, st, g.form, mp, X, users, (int)g.count, F, v.r, v.ld, out.rows.p, out.per.p, lambda, weighted)));
+        }
+    }
+    return out.finish(v, U_out, per_user, [&](const double* hp) { if (stats) Fam::stats_from(hp, n, stats); });
+}
+
+// Item fold-in (pcr_fold_in_items, pcr_fold_in_items_model; pcr_itemfold.h) of the plan's items against v's U: the slots and
+// their pairs go to the device once; the slots are then cut into batches whose unique raters' table (scores + levels) stays within
+// the cap -- a batch holds at least one slot -- and each batch uploads its raters' rows and levels, builds the score table
+// ("itemfold/scores": one launch per rater form, the longest raters first) and runs its slots ("itemfold/newton": one launch per
+// workgroup form).
+static const size_t ITEMFOLD_TABLE = (size_t)1 << 30;
+struct ItemfoldDev { RaterTab R; ItemfoldCsr X; Geo geo; int cus; };
+template <typename T, int BLOCK, bool BIG>
+static int itemfold_launch(const ServeView& v, const FoldinParams& c, const PcrItemfoldPlan& P, const ItemfoldDev& D, int64_t first, int64_t end,
+                           const T* dV0, T* dOut, const T* tab, double* dPer, DBuf<char>& scratch) {
+    const int64_t count = end - first;
+    if (count <= 0) return PCR_OK;
+    const int cap = (int)std::max<int64_t>(1, P.sptr[(size_t)first + 1] - P.sptr[(size_t)first]);      // slots are by descending count
+    const size_t arr = itemfold_arr_bytes(cap, sizeof(T));
+    const size_t lds = fold_small_bytes(D.geo.ld, BLOCK, sizeof(T)) + (BIG ? 0 : arr);
+    // the refusal is a function of the rank and the item's form alone, never of the items that share its launch: the form's
+    // largest item must fit
+    const int form_cap = BLOCK == 64 ? PCR_ITEMFOLD_WAVE_MAX : PCR_ITEMFOLD_LDS_MAX;
+    if (fold_small_bytes(D.geo.ld, BLOCK, sizeof(T)) + (BIG ? 0 : itemfold_arr_bytes(form_cap, sizeof(T))) > PCR_LDS_CU) {
+        pcr_set_error("item fold-in: rank " + std::to_string(D.geo.r) + " is too large for the LDS of the workgroup form of items " +
+                      (BIG ? "beyond " + std::to_string(PCR_ITEMFOLD_LDS_MAX) : "of up to " + std::to_string(form_cap)) + " raters");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    if (BIG && ((arr + 255) & ~(size_t)255) > FOLD_SCRATCH) {
+        pcr_set_error("item fold-in: an item of " + std::to_string(cap) + " raters needs more than 1 GiB of per-rater scratch");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    int64_t grid = fold_grid(count, D.cus, fold_wg_cap(BLOCK), lds);
+    size_t stride = 0;
+    if (BIG) RC(fold_slices(arr, &grid, &stride, scratch));
+    return fold_launch(k_itemfold<T, BLOCK, BIG>, grid, BLOCK, lds, v.st, D.R, D.X, D.geo, (int)first, (int)count, dV0, dOut, serve_U<T>(v), tab, dPer,
+                       c.lambda, c.stepsize, c.cg_max, c.cg_tol, c.steps, c.solver_type == PCR_SOLVER_PCR ? 1 : 0, cap, scratch.p, stride);
+}
+
+template <typename T, int BLOCK>
+static int rater_scores_launch(const ServeView& v, const ItemfoldDev& D, const int32_t* d_order, int64_t count, T* tab) {
+    if (count <= 0) return PCR_OK;
+    const int64_t grid = std::min<int64_t>(count, (int64_t)D.cus * (BLOCK == 64 ? 32 : 8));
+    hipLaunchKernelGGL((k_rater_scores<T, BLOCK>), dim3((unsigned)grid), dim3(BLOCK), carve_bytes(D.geo.ld, sizeof(T)), v.st, D.R, D.geo, d_order,
+                       (int)count, serve_U<T>(v), serve_V<T>(v), tab);
+    HIPCHK(hipGetLastError());
+    return PCR_OK;
+}
+
+template <typename T>
+static int itemfold_run(const ServeView& v, const FoldinParams& c, const PcrItemfoldPlan& P, const double* V0, double* V_out, pcr_itemfold_stats* stats,
+                        double* per_item) {
+    const int64_t n = P.n, nr = (int64_t)P.raters.size();
+    hipStream_t st = v.st;
+    ItemfoldDev D;
+    D.geo.r = v.r; D.geo.ld = v.ld; D.geo.nchunk = v.ld / VecOf<T>::N; D.geo.G = std::min(64, host_pow2(D.geo.nchunk));
+    RC(device_cus(&D.cus));
+    size_t table_cap = ITEMFOLD_TABLE;
+    { std::string knob; if (pcr_tune_get("itemfold_table_bytes", &knob) && atoll(knob.c_str()) > 0) table_cap = (size_t)atoll(knob.c_str()); }
+    DBuf<int64_t> sptr;
+    DBuf<int32_t> orig, anypair, puser, pq;
+    DBuf<T> dV0;
+    FoldOut<T> out;
+    RC(sptr.upload(P.sptr, st)); RC(orig.upload(P.order, st)); RC(anypair.upload(P.anypair, st)); RC(puser.upload(P.puser, st)); RC(pq.upload(P.pq, st));
+    RC(dV0.alloc((size_t)n * v.ld)); RC(out.alloc(v, n, PCR_ITEMFOLD_FIELDS));
+    if (V0) RC(upload_rows<T>(st, v.r, v.ld, {{V0, n, dV0.p}}));
+    else HIPCHK(hipMemsetAsync(dV0.p, 0, (size_t)n * v.ld * sizeof(T), st));
+    std::vector<int32_t> local((size_t)nr, -1), braters, ploc, ruser, rorder;
+    std::vector<int64_t> rptr;
+    std::vector<int32_t> ritem;
+    std::vector<uint16_t> rlvl;
+    auto rlen = [&](int32_t r) { return P.R.index[(size_t)r + 1] - P.R.index[(size_t)r]; };
+    for (int64_t b0 = 0; b0 < n;) {
+        // the batch [b0, b1): slots are added while the table of their unique raters stays within the cap
+        for (int32_t r : braters) local[(size_t)r] = -1;
+        braters.clear();
+        size_t bytes = 0;
+        int64_t b1 = b0;
+        for (; b1 < n; ++b1) {
+            const size_t mark = braters.size();
+            size_t add = 0;
+            for (int64_t z = P.sptr[(size_t)b1]; z < P.sptr[(size_t)b1 + 1]; ++z) {
+                const int32_t r = P.prater[(size_t)z];
+                if (local[(size_t)r] < 0) { local[(size_t)r] = (int32_t)braters.size(); braters.push_back(r); add += (size_t)rlen(r) * (sizeof(T) + 2); }
+            }
+            if (b1 > b0 && bytes + add > table_cap) {
+                for (size_t q = mark; q < braters.size(); ++q) local[(size_t)braters[q]] = -1;
+                braters.resize(mark);
+                break;
+            }
+            bytes += add;
+        }
+        const int64_t nb = (int64_t)braters.size(), pair0 = P.sptr[(size_t)b0], pair1 = P.sptr[(size_t)b1];
+        rptr.assign((size_t)nb + 1, 0); ruser.resize((size_t)nb); rorder.resize((size_t)nb);
+        for (int64_t i = 0; i < nb; ++i) {
+            rptr[(size_t)i + 1] = rptr[(size_t)i] + rlen(braters[(size_t)i]);
+            ruser[(size_t)i] = P.raters[(size_t)braters[(size_t)i]];
+            rorder[(size_t)i] = (int32_t)i;
+        }
+        const int64_t flat = rptr[(size_t)nb];
+        ritem.resize((size_t)flat); rlvl.resize((size_t)flat);
+        for (int64_t i = 0; i < nb; ++i) {
+            const int64_t a = P.R.index[(size_t)braters[(size_t)i]], len = rlen(braters[(size_t)i]);
+            std::copy(P.R.item.begin() + a, P.R.item.begin() + a + len, ritem.begin() + rptr[(size_t)i]);
+            std::copy(P.lv.level.begin() + a, P.lv.level.begin() + a + len, rlvl.begin() + rptr[(size_t)i]);
+        }
+        // raters by descending length (equal lengths in batch order): the wave form is the tail
+        std::stable_sort(rorder.begin(), rorder.end(), [&](int32_t x, int32_t y) { return rptr[(size_t)x + 1] - rptr[(size_t)x] > rptr[(size_t)y + 1] - rptr[(size_t)y]; });
+        int64_t n_wg = 0;
+        while (n_wg < nb && rptr[(size_t)rorder[(size_t)n_wg] + 1] - rptr[(size_t)rorder[(size_t)n_wg]] > PCR_ITEMFOLD_SCORES_WAVE_MAX) ++n_wg;
+        ploc.resize((size_t)(pair1 - pair0));
+        for (int64_t z = pair0; z < pair1; ++z) ploc[(size_t)(z - pair0)] = local[(size_t)P.prater[(size_t)z]];
+        DBuf<int64_t> d_rptr;
+        DBuf<int32_t> d_ruser, d_ritem, d_rorder, d_ploc;
+        DBuf<uint16_t> d_rlvl;
+        DBuf<T> tab;
+        DBuf<char> scratch;
+        RC(d_rptr.upload(rptr, st)); RC(d_ruser.upload(ruser, st)); RC(d_ritem.upload(ritem, st)); RC(d_rlvl.upload(rlvl, st));
+        RC(d_rorder.upload(rorder, st)); RC(d_ploc.upload(ploc, st)); RC(tab.alloc((size_t)flat));
+        D.R = {d_rptr.p, d_ruser.p, d_ritem.p, d_rlvl.p};
+        D.X = {sptr.p, orig.p, anypair.p, puser.p, pq.p, d_ploc.p, pair0};
+        {
+            ProfScope ps(v.prof, "itemfold/scores", st);
+            RC((rater_scores_launch<T, 256>(v, D, d_rorder.p, n_wg, tab.p)));
+            RC((rater_scores_launch<T, 64>(v, D, d_rorder.p + n_wg, nb - n_wg, tab.p)));
+        }
+        {
+            ProfScope ps(v.prof, "itemfold/newton", st);
+            const int64_t e_big = std::min(b1, P.n_big), e_lds = std::min(b1, P.n_big + P.n_lds);
+            RC((itemfold_launch<T, 512, true>(v, c, P, D, b0, e_big, dV0.p, out.rows.p, tab.p, out.per.p, scratch)));
+            RC((itemfold_launch<T, 256, false>(v, c, P, D, std::max(b0, P.n_big), e_lds, dV0.p, out.rows.p, tab.p, out.per.p, scratch)));
+            RC((itemfold_launch<T, 64, false>(v, c, P, D, std::max(b0, P.n_big + P.n_lds), b1, dV0.p, out.rows.p, tab.p, out.per.p, scratch)));
+        }
+        HIPCHK(hipStreamSynchronize(st));        // the batch's buffers go out of scope
+        b0 = b1;
+    }
+    return out.finish(v, V_out, per_item, [&](const double* hp) { if (stats) { stats->unique_raters = nr; pcr_itemfold_stats_from(hp, n, stats); } });
+}
+
+// The entries' common end: the stats zeroed, nothing more for n == 0, then open() -- a _model entry's upload, nothing on a
+// solver -- and run(T()) in the view's precision
+template <class Stats, class Open, class Run>
+static int fold_serve(Stats* stats, int64_t n, const ServeView& v, Open&& open, Run&& run) {
+    if (stats) *stats = Stats{};
+    if (n == 0) return PCR_OK;
+    RC(open());
+    return by_precision(v, run);
+}
+static int on_solver() { return PCR_OK; }
+
+extern "C" {
+
+int pcr_fold_in_model(const pcr_params* p, const double* V, int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val,
+                      const double* U0, int steps, double* U_out, pcr_foldin_stats* stats, double* per_user) {
+    return abi_guard("pcr_fold_in_model", [&]() -> int {
+    PcrFoldinPlan P;
+    RC(pcr_fold_in_model_check(p, V, d2, n, index, item, val, steps, U_out, &P));
+    RC(model_device(p->device));
+    ServeView v; ModelDev M;
+    const FoldinParams c = foldin_params_of(*p, steps);
+    return fold_serve(stats, n, v, [&] { return M.open(nullptr, n, V, d2, p->k, nullptr, nullptr, true, p->precision, &v); },
+                      [&](auto zero) -> int { return foldin_run<decltype(zero)>(v, c, P, U0, U_out, stats, per_user); });
+    });
+}
+
+int pcr_fold_in(pcr_solver* s, int64_t n, const int64_t* index, const int32_t* item, const double* val, const double* U0, int steps,
+                double* U_out, pcr_foldin_stats* stats, double* per_user) {
+    S_OR_ARG;
+    return abi_guard("pcr_fold_in", [&]() -> int {
+        pcr_params prm;
+        RC(s->foldin_params(&prm));
+        const ServeView v = solver_view(s, 0);
+        PcrFoldinPlan P;
+        RC(pcr_fold_in_check("pcr_fold_in", prm.solver_type, v.d2, n, index, item, val, steps, U_out, &P));
+        const FoldinParams c = foldin_params_of(prm, steps);
+        return fold_serve(stats, n, v, on_solver, [&](auto zero) -> int { return foldin_run<decltype(zero)>(v, c, P, U0, U_out, stats, per_user); });
+    });
+}
+
+int pcr_fold_in_ridge_model(const double* F, int64_t rows, int64_t k, double lambda, int weighted, int precision, int device, int64_t n,
+                            const int64_t* index, const int32_t* item, const double* val, double* U_out, pcr_ridge_stats* stats, double* per_user) {
+    return abi_guard("pcr_fold_in_ridge_model", [&]() -> int {
+    PcrRidgePlan P;
+    RC(pcr_fold_in_ridge_check("pcr_fold_in_ridge_model", true, F, rows, k, lambda, precision, n, index, item, val, U_out, &P));
+    RC(model_device(device));
+    ServeView v; ModelDev M;
+    return fold_serve(stats, n, v, [&] { return M.open(nullptr, n, F, rows, k, nullptr, nullptr, true, precision, &v); }, [&](auto zero) -> int {
+        return ridge_run<RidgeFamily, decltype(zero)>(v, lambda, weighted != 0, P, U_out, stats, per_user);
+    });
+    });
+}
+
+int pcr_fold_in_ridge(pcr_solver* s, int weighted, int64_t n, const int64_t* index, const int32_t* item, const double* val, double* U_out,
+                      pcr_ridge_stats* stats, double* per_user) {
+    S_OR_ARG;
+    return abi_guard("pcr_fold_in_ridge", [&]() -> int {
+        const ServeView v = solver_view(s, 0);
+        const double lambda = s->ridge_lambda();
+        PcrRidgePlan P;
+        RC(pcr_fold_in_ridge_check("pcr_fold_in_ridge", false, nullptr, v.d2, v.r, lambda, v.dtype, n, index, item, val, U_out, &P));
+        return fold_serve(stats, n, v, on_solver, [&](auto zero) -> int {
+            return ridge_run<RidgeFamily, decltype(zero)>(v, lambda, weighted != 0, P, U_out, stats, per_user);
+        });
+    });
+}
+
+int pcr_fold_in_nnls_model(const double* F, int64_t rows, int64_t k, double lambda, int weighted, int precision, int device, int64_t n,
+                           const int64_t* index, const int32_t* item, const double* val, double* U_out, pcr_nnls_stats* stats, double* per_user) {
+    return abi_guard("pcr_fold_in_nnls_model", [&]() -> int {
+    PcrRidgePlan P;
+    RC(pcr_fold_in_nnls_check("pcr_fold_in_nnls_model", true, F, rows, k, lambda, precision, n, index, item, val, U_out, &P));
+    RC(model_device(device));
+    ServeView v; ModelDev M;
+    return fold_serve(stats, n, v, [&] { return M.open(nullptr, n, F, rows, k, nullptr, nullptr, true, precision, &v); }, [&](auto zero) -> int {
+        return ridge_run<NnlsFamily, decltype(zero)>(v, lambda, weighted != 0, P, U_out, stats, per_user);
+    });
+    });
+}
+
+int pcr_fold_in_nnls(pcr_solver* s, int weighted, int64_t n, const int64_t* index, const int32_t* item, const double* val, double* U_out,
+                     pcr_nnls_stats* stats, double* per_user) {
+    S_OR_ARG;
+    return abi_guard("pcr_fold_in_nnls", [&]() -> int {
+        const ServeView v = solver_view(s, 0);
+        const double lambda = s->ridge_lambda();
+        PcrRidgePlan P;
+        RC(pcr_fold_in_nnls_check("pcr_fold_in_nnls", false, nullptr, v.d2, v.r, lambda, v.dtype, n, index, item, val, U_out, &P));
+        return fold_serve(stats, n, v, on_solver, [&](auto zero) -> int {
+            return ridge_run<NnlsFamily, decltype(zero)>(v, lambda, weighted != 0, P, U_out, stats, per_user);
+        });
+    });
+}
+
+int pcr_fold_in_items_model(const pcr_params* p, const double* U, int64_t d1, const double* V, int64_t d2, const int64_t* tr_index,
+                            const int32_t* tr_item, const double* tr_val, int64_t n, const int64_t* index, const int32_t* user, const double* val,
+                            const double* V0, int steps, double* V_out, pcr_itemfold_stats* stats, double* per_item) {
+    return abi_guard("pcr_fold_in_items_model", [&]() -> int {
+    PcrItemfoldPlan P;
+    RC(pcr_fold_in_items_check("pcr_fold_in_items_model", true, p, U, d1, V, d2, tr_index, tr_item, tr_val, n, index, user, val, steps, V_out, &P));
+    RC(model_device(p->device));
+    ServeView v; ModelDev M;
+    const FoldinParams c = foldin_params_of(*p, steps);
+    return fold_serve(stats, n, v, [&] { return M.open(U, d1, V, d2, p->k, nullptr, nullptr, true, p->precision, &v); },
+                      [&](auto zero) -> int { return itemfold_run<decltype(zero)>(v, c, P, V0, V_out, stats, per_item); });
+    });
+}
+
+int pcr_fold_in_items(pcr_solver* s, const pcr_dataset* train, int64_t n, const int64_t* index, const int32_t* user, const double* val,
+                      const double* V0, int steps, double* V_out, pcr_itemfold_stats* stats, double* per_item) {
+    S_OR_ARG;
+    return abi_guard("pcr_fold_in_items", [&]() -> int {
+        pcr_params prm;
+        if (s->foldin_params(&prm) != PCR_OK) return pcr_solver::pcr_only("pcr_fold_in_items");
+        const ServeView v = solver_view(s, 0);
+        if (s->comm_nranks() > 1 || s->first_user != 0 || s->n_users != v.d1) {
+            pcr_set_error("pcr_fold_in_items: needs every user on the rank; this solver holds a shard");
+            return PCR_ERR_STATE;
+        }
+        if (!train) { pcr_set_error("pcr_fold_in_items: null training data set"); return PCR_ERR_ARG; }
+        const PcrCsr& X = train->train;
+        if (X.d1 != v.d1 || X.d2 != v.d2 || X.nnz() != v.nnz) {
+            pcr_set_error("pcr_fold_in_items: the data set is not the one the solver was created from (dimensions or nnz differ)");
+            return PCR_ERR_ARG;
+        }
+        PcrItemfoldPlan P;
+        RC(pcr_fold_in_items_check("pcr_fold_in_items", false, &prm, nullptr, X.d1, nullptr, X.d2, X.index.data(), X.item.data(), X.val.data(), n, index,
+                                   user, val, steps, V_out, &P));
+        const FoldinParams c = foldin_params_of(prm, steps);
+        return fold_serve(stats, n, v, on_solver, [&](auto zero) -> int { return itemfold_run<decltype(zero)>(v, c, P, V0, V_out, stats, per_item); });
+    });
+}
+}  // extern "C"

@@ -1,7 +1,7 @@
 // pcr_foldin.h -- k_foldin: fold-in of users the model was not trained on (pcr_fold_in, pcr_fold_in_model of
 // include/primalcr.h).  One workgroup runs a user's WHOLE optimisation over u with V fixed -- up to `steps` Newton steps, each
 // the gradient, a truncated CG and a line search of update_u_new (pcrpp.cpp:779-815) / update_u (pcr.cpp:523-585) -- in one
-// launch.  Part of pcr_serve.hip; the building blocks are those of k_ustep (pcr_prims.h) in its uncached form.
+// launch.  Part of pcr_fold.hip; the building blocks are those of k_ustep (pcr_prims.h) in its uncached form.
 //
 // What differs from k_ustep:
 //   - nothing is handed over: no Shard<T>, no window cache, no sorted state from a k_prepare, no clusters.  The user's ratings
@@ -24,7 +24,6 @@
 #include "pcr_prims.h"
 
 // The workgroup forms by user length (PCR_FOLDIN_WAVE_MAX, PCR_FOLDIN_LDS_MAX) are part of the contract: include/primalcr.h.
-#define PCR_FOLDIN_LDS_CU ((size_t)160 * 1024)
 
 // the new users' ratings on the device: CSR (item-ascending rows), dense level per rating, per user T_u + 1 cumulative level counts
 struct FoldinCsr {
@@ -35,7 +34,9 @@ struct FoldinCsr {
     const int32_t* runstart;
 };
 
-static inline size_t foldin_small_bytes(int ld, int block, size_t elt) {
+// The LDS vectors of one row's optimisation, k_foldin's and k_itemfold's (pcr_itemfold.h) alike: vecT, red, the seven fp64 vectors
+// of ld values and the gather's per-wave partial rows
+static inline size_t fold_small_bytes(int ld, int block, size_t elt) {
     return carve_bytes(ld, elt) + carve_bytes(block / PCR_WAVE + 1, 8) + 7 * carve_bytes(ld, 8) + carve_bytes((size_t)(block / PCR_WAVE) * ld, 8);
 }
 // the per-rating arrays of a user of at most cap ratings and rs_cap - 1 levels (LDS, or one workgroup's slice of the scratch)

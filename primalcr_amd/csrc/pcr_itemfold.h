@@ -5,7 +5,7 @@
 //     phi_ij(s) = sum_{k in Omega_i, lev(r_ik) < lev(r_ij)} max(0, 1 - s + m_ik)^2 + sum_{k, lev(r_ik) > lev(r_ij)} max(0, 1 + s - m_ik)^2,
 // Omega_i the rater's TRAINING row and m_ik = u_i . v_k as the storage type holds it: F_j is the change of the training objective
 // when item j and its ratings are appended to the data.  New items are folded in independently of each other: a pair of two new
-// items rated by the same user is NOT modelled.  Part of pcr_serve.hip; the building blocks are those of k_foldin (pcr_prims.h).
+// items rated by the same user is NOT modelled.  Part of pcr_fold.hip; the building blocks are those of k_foldin (pcr_prims.h).
 //
 // The user-side kernel cannot be reused with the roles swapped: the loss compares items WITHIN a user, so the new row couples to
 // the whole training row of every rater.  Two kernels:
@@ -27,11 +27,11 @@
 #include <type_traits>
 
 #include "pcr_host.h"
+#include "pcr_foldin.h"      // fold_small_bytes: the small carve is k_foldin's
 #include "pcr_prims.h"
 
 // The workgroup forms (PCR_ITEMFOLD_WAVE_MAX, PCR_ITEMFOLD_LDS_MAX, PCR_ITEMFOLD_SCORES_WAVE_MAX) are part of the contract:
 // include/primalcr.h.
-#define PCR_ITEMFOLD_LDS_CU ((size_t)160 * 1024)
 #define ITEMFOLD_SCAN_UNR 8
 #define ITEMFOLD_SCAN_LANES 16
 
@@ -53,9 +53,6 @@ struct ItemfoldCsr {
     int64_t pair0;
 };
 
-static inline size_t itemfold_small_bytes(int ld, int block, size_t elt) {
-    return carve_bytes(ld, elt) + carve_bytes(block / PCR_WAVE + 1, 8) + 7 * carve_bytes(ld, 8) + carve_bytes((size_t)(block / PCR_WAVE) * ld, 8);
-}
 // the per-rater arrays of an item of at most cap raters (LDS, or one workgroup's slice of the scratch)
 static inline size_t itemfold_arr_bytes(int cap, size_t elt) { return 3 * carve_bytes(cap, elt) + 2 * carve_bytes(cap, 4); }
 

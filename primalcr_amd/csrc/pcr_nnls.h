@@ -1,5 +1,5 @@
 // pcr_nnls.h -- k_nnls_direct, k_nnls_cg: non-negative fold-in against a fixed factor matrix F (pcr_fold_in_nnls,
-// pcr_fold_in_nnls_model of include/primalcr.h).  Part of pcr_serve.hip.
+// pcr_fold_in_nnls_model of include/primalcr.h).  Part of pcr_fold.hip.
 //
 // Per user with ratings r on rows I of F (n of them), A = F[I], mu = lambda n (weighted) or lambda, G = A^T A + mu I, b = A^T r:
 //     minimise |r - A u|^2 + mu |u|^2  subject to u >= 0

@@ -1,5 +1,5 @@
 // pcr_ridge.h -- k_ridge_direct, k_ridge_cg: squared-loss (ridge) fold-in against a fixed factor matrix F (pcr_fold_in_ridge,
-// pcr_fold_in_ridge_model of include/primalcr.h).  Part of pcr_serve.hip.
+// pcr_fold_in_ridge_model of include/primalcr.h).  Part of pcr_fold.hip.
 //
 // Per user with ratings r on rows I of F (n of them), A = F[I] (n x k), mu = lambda n (weighted) or lambda:
 //     minimise |r - A u|^2 + mu |u|^2   <=>   (A^T A + mu I) u = A^T r  (primal, k x k)   <=>   u = A^T a, (A A^T + mu I) a = r  (dual, n x n)

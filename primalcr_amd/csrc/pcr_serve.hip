@@ -3,25 +3,17 @@
 //
 // Every entry exists twice: on a trained solver (pcr_recommend, ...) and on a model in host memory (pcr_recommend_model, ...).
 // Both come down to a ServeView (pcr_dev.h) -- filled by the solver (pcr_solver::serve_view) or by ModelDev, which uploads the
-// model for one call -- and one function per entry over that view, which picks the precision.  Training is pcr_solver.hip.
+// model for one call -- and one function per entry over that view, which picks the precision.  Training is pcr_solver.hip; the
+// four fold-in families are pcr_fold.hip.
 // There is NO CPU compute path in this file: every [device] entry point fails with PCR_ERR_DEVICE when HIP is unusable.
 #include <cmath>
 
 #include "pcr_dev.h"
-#include "pcr_foldin.h"
-#include "pcr_itemfold.h"
-#include "pcr_ridge.h"
-#include "pcr_nnls.h"
 #include "pcr_prims.h"
 #include "pcr_topk.h"
 
 int ServeView::sum(double* dev, size_t count) const { return owner ? owner->allreduce_f64(dev, count) : PCR_OK; }
 int ServeView::wait() const { if (owner) return owner->sync(); HIPCHK(hipStreamSynchronize(st)); return PCR_OK; }
-template <typename T> static const T* serve_U(const ServeView& v) { return static_cast<const T*>(v.U); }
-template <typename T> static const T* serve_V(const ServeView& v) { return static_cast<const T*>(v.V); }
-// run(T()) for the view's precision
-template <class F>
-static int by_precision(const ServeView& v, F&& run) { return v.dtype == PCR_F64 ? run(0.0) : run(0.0f); }
 // the cut[] array of TopnArgs / DivArgs: the ncut cutoffs, then zeros
 static void fill_cuts(int* dst, int ncut, const int* cuts) {
     for (int c = 0; c < PCR_TOPN_MAX_CUTOFFS; ++c) dst[c] = c < ncut ? cuts[c] : 0;
@@ -356,14 +348,13 @@ static int div_run(const ServeView& v, const double* info, int64_t n, const int3
 // of ld values.  The streaming form is the default: it was the faster one at every shape measured.
 // pcr_tune("rerank_lds", "1") takes the LDS form, which stages the pool's rows, whenever one wave's image fits a workgroup's
 // 160 KiB.  waves = users per workgroup (4, 2 or 1, as many as fit).
-static const size_t MMR_LDS_CU = (size_t)160 * 1024;
 struct MmrShape { int form = 0, waves = 0; size_t lds = 0; };
 template <typename T>
 static MmrShape mmr_shape(int K, int ld, int knob) {
     MmrShape s;
-    s.form = (knob > 0 && mmr_wave_lds<T>(K, ld, 1) <= MMR_LDS_CU) ? 1 : 0;
+    s.form = (knob > 0 && mmr_wave_lds<T>(K, ld, 1) <= PCR_LDS_CU) ? 1 : 0;
     const size_t per = mmr_wave_lds<T>(K, ld, s.form);
-    for (int w = 4; w >= 1; w >>= 1) if ((size_t)w * per <= MMR_LDS_CU) { s.waves = w; break; }
+    for (int w = 4; w >= 1; w >>= 1) if ((size_t)w * per <= PCR_LDS_CU) { s.waves = w; break; }
     s.lds = (size_t)s.waves * per;
     return s;
 }
@@ -937,419 +928,6 @@ struct ServeState {
 pcr_solver::pcr_solver() : serve(new ServeState) {}
 pcr_solver::~pcr_solver() {}
 
-// s's view for one call: the launches are timed in s's profiler (that of a CCDR1 solver, not of the Solver<T> it holds)
-static ServeView solver_view(pcr_solver* s, int flags) {
-    ServeView v;
-    s->serve_view(&v); v.exclude = (flags & PCR_REC_EXCLUDE_TRAIN) != 0;
-    return v;
-}
-
-// A model in host memory on the device for one call: the exclusion CSR (item-ascending rows: a CSR that is not gets a sorted
-// copy, for the kernel's cursor) and both host fp64 factors in the requested type, rows padded to ld: U then V in one buffer.
-// open() fills the view: the default stream, nothing profiled, nothing exchanged.
-struct ModelDev {
-    DBuf<int64_t> dx;
-    DBuf<int32_t> di;
-    DBuf<char> F;
-    int open(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item, bool sorted,
-             int dtype, ServeView* v) {
-        if (index) {
-            std::vector<int32_t> sitem;
-            const int64_t nnz = index[d1];
-            if (!sorted) {
-                sitem.assign(item, item + nnz);
-                pcr_parallel_ranges(d1, pcr_host_threads(), [&](int, int64_t lo, int64_t hi) {
-                    for (int64_t u = lo; u < hi; ++u) std::sort(sitem.begin() + index[u], sitem.begin() + index[u + 1]);
-                });
-            }
-            RC(dx.upload_n(index, (size_t)d1 + 1)); RC(di.upload_n(sorted ? item : sitem.data(), (size_t)nnz));
-        }
-        const int ld = ((int)k + 3) & ~3;
-        const size_t row = (size_t)ld * (dtype == PCR_F64 ? sizeof(double) : sizeof(float));
-        const int64_t ur = U ? d1 : 0;             // (U NULL: pcr_evaluate_lists_model scores nothing and brings no user factors)
-        RC(F.alloc((size_t)(ur + d2) * row));
-        char* dV = F.p + (size_t)ur * row;
-        if (dtype == PCR_F64) RC(upload_rows<double>(v->st, (int)k, ld, {{U, ur, (double*)F.p}, {V, d2, (double*)dV}}));
-        else RC(upload_rows<float>(v->st, (int)k, ld, {{U, ur, (float*)F.p}, {V, d2, (float*)dV}}));
-        v->dtype = dtype; v->U = F.p; v->V = dV; v->r = (int)k; v->ld = ld; v->rows = v->d1 = d1; v->d2 = d2;
-        v->uptr = dx.p; v->item = di.p; v->nnz = index ? index[d1] : 0;
-        return PCR_OK;
-    }
-};
-
-static int model_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { pcr_set_error("no HIP device available"); return PCR_ERR_DEVICE; }
-    if (device < 0 || device >= ndev) { pcr_set_error("device ordinal out of range"); return PCR_ERR_ARG; }
-    HIPCHK(hipSetDevice(device));
-    return PCR_OK;
-}
-
-// Fold-in (pcr_fold_in, pcr_fold_in_model; k_foldin of pcr_foldin.h) of the plan's users against v's V: the ratings, their
-// levels and the users' order go to the device, then one launch per workgroup form -- P.order is by descending length, so the
-// forms are ranges of it and the longest users of each start first; workgroups stride over their range.  A launch's LDS is sized
-// by its longest user; the scratch form's slices are bounded by the grid (at most FOLDIN_SCRATCH bytes in all).  "foldin/newton"
-// times the launches.
-struct FoldinParams { int solver_type; double lambda, stepsize; int cg_max; double cg_tol; int steps; };
-static const size_t FOLDIN_SCRATCH = (size_t)1 << 30;
-template <typename T, int BLOCK, bool BIG>
-static int foldin_launch(const ServeView& v, const FoldinParams& c, const PcrFoldinPlan& P, const FoldinCsr& X, const Geo& geo, const int32_t* d_order,
-                         int64_t first, int64_t count, int cus, const T* dU0, T* dOut, double* dPer, DBuf<char>& scratch) {
-    if (count <= 0) return PCR_OK;
-    const std::vector<int64_t>& idx = P.X.index;
-    const int32_t longest = P.order[(size_t)first];
-    const int cap = (int)std::max<int64_t>(1, idx[(size_t)longest + 1] - idx[(size_t)longest]);
-    int rs_cap = 1;
-    for (int64_t i = first; i < first + count; ++i) {
-        const int32_t u = P.order[(size_t)i];
-        rs_cap = std::max(rs_cap, (int)(P.lv.run_ofs[(size_t)u + 1] - P.lv.run_ofs[(size_t)u]));
-    }
-    const size_t li_bytes = BIG ? 8 : 4, arr = foldin_arr_bytes(cap, rs_cap, sizeof(T), li_bytes);
-    const size_t lds = foldin_small_bytes(geo.ld, BLOCK, sizeof(T)) + (BIG ? 0 : arr);
-    if (lds > PCR_FOLDIN_LDS_CU) {
-        pcr_set_error("fold-in: rank " + std::to_string(geo.r) + " (with " + std::to_string(rs_cap - 1) + " rating levels) is too large for the kernel's LDS");
-        return PCR_ERR_UNSUPPORTED;
-    }
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(BLOCK == 64 ? 16 : BLOCK == 256 ? 4 : 1, PCR_FOLDIN_LDS_CU / lds));
-    int64_t grid = std::min<int64_t>(count, (int64_t)cus * per_cu);
-    size_t stride = 0;
-    if (BIG) {
-        stride = (arr + 255) & ~(size_t)255;
-        grid = std::max<int64_t>(1, std::min<int64_t>(grid, (int64_t)(FOLDIN_SCRATCH / stride)));
-        RC(scratch.alloc((size_t)grid * stride));
-    }
-    HIPCHK(hipFuncSetAttribute((const void*)k_foldin<T, BLOCK, BIG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_foldin<T, BLOCK, BIG>), dim3((unsigned)grid), dim3(BLOCK), lds, v.st, X, geo, d_order + first, (int)count, dU0, dOut,
-                       serve_V<T>(v), dPer, c.lambda, c.stepsize, c.cg_max, c.cg_tol, c.steps, c.solver_type == PCR_SOLVER_PCR ? 1 : 0,
-                       c.solver_type == PCR_SOLVER_PCR ? 1 : 0, cap, rs_cap, scratch.p, stride);
-    HIPCHK(hipGetLastError());
-    return PCR_OK;
-}
-
-template <typename T>
-static int foldin_run(const ServeView& v, const FoldinParams& c, const PcrFoldinPlan& P, const double* U0, double* U_out, pcr_foldin_stats* stats,
-                      double* per_user) {
-    const int64_t n = P.X.d1;
-    hipStream_t st = v.st;
-    Geo geo;
-    geo.r = v.r; geo.ld = v.ld; geo.nchunk = v.ld / VecOf<T>::N; geo.G = std::min(64, host_pow2(geo.nchunk));
-    int dev = 0, cus = 0;
-    HIPCHK(hipGetDevice(&dev));
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    cus = std::max(cus, 1);
-    DBuf<int64_t> uptr, runofs;
-    DBuf<int32_t> item, runstart, order;
-    DBuf<uint16_t> lvl;
-    DBuf<T> dU0, dOut;
-    DBuf<double> dPer, dOutD;
-    DBuf<char> scratch;
-    RC(uptr.upload(P.X.index, st)); RC(item.upload_n(P.X.item.data(), P.X.item.size()));
-    RC(lvl.upload(P.lv.level, st)); RC(runofs.upload(P.lv.run_ofs, st)); RC(runstart.upload(P.lv.run_start, st));
-    RC(order.upload(P.order, st));
-    RC(dU0.alloc((size_t)n * v.ld)); RC(dOut.alloc((size_t)n * v.ld)); RC(dPer.alloc((size_t)n * PCR_FOLDIN_FIELDS)); RC(dOutD.alloc((size_t)n * v.r));
-    if (U0) RC(upload_rows<T>(st, v.r, v.ld, {{U0, n, dU0.p}}));
-    else HIPCHK(hipMemsetAsync(dU0.p, 0, (size_t)n * v.ld * sizeof(T), st));
-    const FoldinCsr X = {uptr.p, item.p, lvl.p, runofs.p, runstart.p};
-    {
-        ProfScope ps(v.prof, "foldin/newton", st);
-        const int64_t nw = n - P.n_big - P.n_lds;
-        RC((foldin_launch<T, 512, true>(v, c, P, X, geo, order.p, 0, P.n_big, cus, dU0.p, dOut.p, dPer.p, scratch)));
-        RC((foldin_launch<T, 256, false>(v, c, P, X, geo, order.p, P.n_big, P.n_lds, cus, dU0.p, dOut.p, dPer.p, scratch)));
-        RC((foldin_launch<T, 64, false>(v, c, P, X, geo, order.p, P.n_big + P.n_lds, nw, cus, dU0.p, dOut.p, dPer.p, scratch)));
-    }
-    hipLaunchKernelGGL((k_mat_out<T>), dim3((unsigned)std::min<int64_t>(1 << 16, cdiv(n * v.r, 256))), dim3(256), 0, st, (const T*)dOut.p, dOutD.p, n, v.r, v.ld);
-    HIPCHK(hipGetLastError());
-    std::vector<double> hp((size_t)n * PCR_FOLDIN_FIELDS);
-    HIPCHK(hipMemcpyAsync(U_out, dOutD.p, (size_t)n * v.r * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hp.data(), dPer.p, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (stats) pcr_foldin_stats_from(hp.data(), n, stats);
-    if (per_user) std::copy(hp.begin(), hp.end(), per_user);
-    return PCR_OK;
-}
-static FoldinParams foldin_params_of(const pcr_params& p, int steps) { return {p.solver_type, p.lambda, p.stepsize, p.cg_max_iter, p.cg_tol, steps}; }
-
-// Ridge fold-in (pcr_fold_in_ridge, pcr_fold_in_ridge_model; pcr_ridge.h) of the plan's users against v's V: the ratings and the
-// users' order go to the device, then one launch per range of the plan -- a (form, workgroup size, tile count) class, its LDS
-// sized by the class; workgroups stride over their range, the longest users first.  "foldin/ridge" times the launches.
-static const size_t RIDGE_LDS_CU = (size_t)160 * 1024;
-template <typename T>
-static int ridge_run(const ServeView& v, double lambda, int weighted, const PcrRidgePlan& P, double* U_out, pcr_ridge_stats* stats, double* per_user) {
-    const int64_t n = P.X.d1;
-    hipStream_t st = v.st;
-    int dev = 0, cus = 0;
-    HIPCHK(hipGetDevice(&dev));
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    cus = std::max(cus, 1);
-    DBuf<int64_t> uptr;
-    DBuf<int32_t> item, order;
-    DBuf<double> val, dPer, dOutD;
-    DBuf<T> dOut;
-    RC(uptr.upload(P.X.index, st)); RC(item.upload_n(P.X.item.data(), P.X.item.size())); RC(val.upload_n(P.X.val.data(), P.X.val.size()));
-    RC(order.upload(P.order, st));
-    RC(dOut.alloc((size_t)n * v.ld)); RC(dPer.alloc((size_t)n * PCR_RIDGE_FIELDS)); RC(dOutD.alloc((size_t)n * v.r));
-    const RidgeCsr X = {uptr.p, item.p, val.p};
-    const T* F = serve_V<T>(v);
-    {
-        ProfScope ps(v.prof, "foldin/ridge", st);
-        for (const PcrRidgePlan::Range& g : P.ranges) {
-            if (g.count <= 0) continue;
-            const int32_t* users = order.p + g.first;
-            if (g.form == PCR_RIDGE_CG) {
-                const size_t lds = ridge_cg_bytes(v.ld);
-                if (lds > RIDGE_LDS_CU) { pcr_set_error("ridge fold-in: rank " + std::to_string(v.r) + " is too large for the CG form's LDS"); return PCR_ERR_UNSUPPORTED; }
-                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, RIDGE_LDS_CU / lds));
-                const int64_t grid = std::min<int64_t>(g.count, (int64_t)cus * per_cu);
-                HIPCHK(hipFuncSetAttribute((const void*)k_ridge_cg<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL((k_ridge_cg<T>), dim3((unsigned)grid), dim3(256), lds, st, X, users, (int)g.count, F, v.r, v.ld, dOut.p, dPer.p, lambda, weighted);
-            } else {
-                const int mp = g.tiles * 16, dual = g.form == PCR_RIDGE_DUAL ? 1 : 0;
-                if (mp < 16 || mp > (g.block == 64 ? 64 : PCR_RIDGE_DIRECT_MAX)) { pcr_set_error("ridge fold-in: a launch class outside the kernel's tile range"); return PCR_ERR_STATE; }
-                const size_t lds = ridge_direct_bytes(mp, v.ld, g.block);
-                if (lds > RIDGE_LDS_CU) { pcr_set_error("ridge fold-in: rank " + std::to_string(v.r) + " is too large for the direct forms' LDS"); return PCR_ERR_UNSUPPORTED; }
-                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(g.block == 64 ? 16 : 4, RIDGE_LDS_CU / lds));
-                const int64_t grid = std::min<int64_t>(g.count, (int64_t)cus * per_cu);
-                if (g.block == 64) {
-                    HIPCHK(hipFuncSetAttribute((const void*)k_ridge_direct<T, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    hipLaunchKernelGGL((k_ridge_direct<T, 64>), dim3((unsigned)grid), dim3(64), lds, st, X, users, (int)g.count, F, v.r, v.ld, dOut.p, dPer.p,
-                                       lambda, weighted, dual, mp);
-                } else {
-                    HIPCHK(hipFuncSetAttribute((const void*)k_ridge_direct<T, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    hipLaunchKernelGGL((k_ridge_direct<T, 256>), dim3((unsigned)grid), dim3(256), lds, st, X, users, (int)g.count, F, v.r, v.ld, dOut.p, dPer.p,
-                                       lambda, weighted, dual, mp);
-                }
-            }
-            HIPCHK(hipGetLastError());
-        }
-    }
-    hipLaunchKernelGGL((k_mat_out<T>), dim3((unsigned)std::min<int64_t>(1 << 16, cdiv(n * v.r, 256))), dim3(256), 0, st, (const T*)dOut.p, dOutD.p, n, v.r, v.ld);
-    HIPCHK(hipGetLastError());
-    std::vector<double> hp((size_t)n * PCR_RIDGE_FIELDS);
-    HIPCHK(hipMemcpyAsync(U_out, dOutD.p, (size_t)n * v.r * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hp.data(), dPer.p, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (stats) pcr_ridge_stats_from(hp.data(), n, stats);
-    if (per_user) std::copy(hp.begin(), hp.end(), per_user);
-    return PCR_OK;
-}
-
-// Non-negative fold-in (pcr_fold_in_nnls, pcr_fold_in_nnls_model; pcr_nnls.h) of the plan's users against v's V, laid out as
-// ridge_run: one launch per range of the plan (form and workgroup size follow from the rank: one range), workgroups striding over
-// it, the longest users first.  "foldin/nnls" times the launches.
-template <typename T>
-static int nnls_run(const ServeView& v, double lambda, int weighted, const PcrRidgePlan& P, double* U_out, pcr_nnls_stats* stats, double* per_user) {
-    const int64_t n = P.X.d1;
-    hipStream_t st = v.st;
-    int dev = 0, cus = 0;
-    HIPCHK(hipGetDevice(&dev));
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    cus = std::max(cus, 1);
-    DBuf<int64_t> uptr;
-    DBuf<int32_t> item, order;
-    DBuf<double> val, dPer, dOutD;
-    DBuf<T> dOut;
-    RC(uptr.upload(P.X.index, st)); RC(item.upload_n(P.X.item.data(), P.X.item.size())); RC(val.upload_n(P.X.val.data(), P.X.val.size()));
-    RC(order.upload(P.order, st));
-    RC(dOut.alloc((size_t)n * v.ld)); RC(dPer.alloc((size_t)n * PCR_NNLS_FIELDS)); RC(dOutD.alloc((size_t)n * v.r));
-    const RidgeCsr X = {uptr.p, item.p, val.p};
-    const T* F = serve_V<T>(v);
-    {
-        ProfScope ps(v.prof, "foldin/nnls", st);
-        for (const PcrRidgePlan::Range& g : P.ranges) {
-            if (g.count <= 0) continue;
-            const int32_t* users = order.p + g.first;
-            if (g.form == PCR_NNLS_CG) {
-                const size_t lds = nnls_cg_bytes(v.ld);
-                if (lds > RIDGE_LDS_CU) { pcr_set_error("nnls fold-in: rank " + std::to_string(v.r) + " is too large for the CG form's LDS"); return PCR_ERR_UNSUPPORTED; }
-                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, RIDGE_LDS_CU / lds));
-                const int64_t grid = std::min<int64_t>(g.count, (int64_t)cus * per_cu);
-                HIPCHK(hipFuncSetAttribute((const void*)k_nnls_cg<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL((k_nnls_cg<T>), dim3((unsigned)grid), dim3(256), lds, st, X, users, (int)g.count, F, v.r, v.ld, dOut.p, dPer.p, lambda, weighted);
-            } else {
-                const int mp = g.tiles * 16;
-                if (mp < 16 || mp < v.r || mp > (g.block == 64 ? 64 : PCR_RIDGE_DIRECT_MAX)) { pcr_set_error("nnls fold-in: a launch class outside the kernel's tile range"); return PCR_ERR_STATE; }
-                const size_t lds = nnls_direct_bytes(mp, v.ld, g.block);
-                if (lds > RIDGE_LDS_CU) { pcr_set_error("nnls fold-in: rank " + std::to_string(v.r) + " is too large for the direct form's LDS"); return PCR_ERR_UNSUPPORTED; }
-                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(g.block == 64 ? 16 : 4, RIDGE_LDS_CU / lds));
-                const int64_t grid = std::min<int64_t>(g.count, (int64_t)cus * per_cu);
-                if (g.block == 64) {
-                    HIPCHK(hipFuncSetAttribute((const void*)k_nnls_direct<T, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    hipLaunchKernelGGL((k_nnls_direct<T, 64>), dim3((unsigned)grid), dim3(64), lds, st, X, users, (int)g.count, F, v.r, v.ld, dOut.p, dPer.p,
-                                       lambda, weighted, mp);
-                } else {
-                    HIPCHK(hipFuncSetAttribute((const void*)k_nnls_direct<T, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    hipLaunchKernelGGL((k_nnls_direct<T, 256>), dim3((unsigned)grid), dim3(256), lds, st, X, users, (int)g.count, F, v.r, v.ld, dOut.p, dPer.p,
-                                       lambda, weighted, mp);
-                }
-            }
-            HIPCHK(hipGetLastError());
-        }
-    }
-    hipLaunchKernelGGL((k_mat_out<T>), dim3((unsigned)std::min<int64_t>(1 << 16, cdiv(n * v.r, 256))), dim3(256), 0, st, (const T*)dOut.p, dOutD.p, n, v.r, v.ld);
-    HIPCHK(hipGetLastError());
-    std::vector<double> hp((size_t)n * PCR_NNLS_FIELDS);
-    HIPCHK(hipMemcpyAsync(U_out, dOutD.p, (size_t)n * v.r * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hp.data(), dPer.p, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (stats) pcr_nnls_stats_from(hp.data(), n, stats);
-    if (per_user) std::copy(hp.begin(), hp.end(), per_user);
-    return PCR_OK;
-}
-
-// Item fold-in (pcr_fold_in_items, pcr_fold_in_items_model; pcr_itemfold.h) of the plan's items against v's U: the slots and
-// their pairs go to the device once; the slots are then cut into batches whose unique raters' table (scores + levels) stays within
-// the cap -- a batch holds at least one slot -- and each batch uploads its raters' rows and levels, builds the score table
-// ("itemfold/scores": one launch per rater form, the longest raters first) and runs its slots ("itemfold/newton": one launch per
-// workgroup form; the scratch form's slices are bounded by the grid, at most ITEMFOLD_SCRATCH bytes in all).
-static const size_t ITEMFOLD_SCRATCH = (size_t)1 << 30, ITEMFOLD_TABLE = (size_t)1 << 30;
-struct ItemfoldDev { RaterTab R; ItemfoldCsr X; Geo geo; int cus; };
-template <typename T, int BLOCK, bool BIG>
-static int itemfold_launch(const ServeView& v, const FoldinParams& c, const PcrItemfoldPlan& P, const ItemfoldDev& D, int64_t first, int64_t end,
-                           const T* dV0, T* dOut, const T* tab, double* dPer, DBuf<char>& scratch) {
-    const int64_t count = end - first;
-    if (count <= 0) return PCR_OK;
-    const int cap = (int)std::max<int64_t>(1, P.sptr[(size_t)first + 1] - P.sptr[(size_t)first]);      // slots are by descending count
-    const size_t arr = itemfold_arr_bytes(cap, sizeof(T));
-    const size_t lds = itemfold_small_bytes(D.geo.ld, BLOCK, sizeof(T)) + (BIG ? 0 : arr);
-    // the refusal is a function of the rank and the item's form alone, never of the items that share its launch: the form's
-    // largest item must fit
-    const int form_cap = BLOCK == 64 ? PCR_ITEMFOLD_WAVE_MAX : PCR_ITEMFOLD_LDS_MAX;
-    if (itemfold_small_bytes(D.geo.ld, BLOCK, sizeof(T)) + (BIG ? 0 : itemfold_arr_bytes(form_cap, sizeof(T))) > PCR_ITEMFOLD_LDS_CU) {
-        pcr_set_error("item fold-in: rank " + std::to_string(D.geo.r) + " is too large for the LDS of the workgroup form of items " +
-                      (BIG ? "beyond " + std::to_string(PCR_ITEMFOLD_LDS_MAX) : "of up to " + std::to_string(form_cap)) + " raters");
-        return PCR_ERR_UNSUPPORTED;
-    }
-    if (BIG && ((arr + 255) & ~(size_t)255) > ITEMFOLD_SCRATCH) {
-        pcr_set_error("item fold-in: an item of " + std::to_string(cap) + " raters needs more than 1 GiB of per-rater scratch");
-        return PCR_ERR_UNSUPPORTED;
-    }
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(BLOCK == 64 ? 16 : BLOCK == 256 ? 4 : 1, PCR_ITEMFOLD_LDS_CU / lds));
-    int64_t grid = std::min<int64_t>(count, (int64_t)D.cus * per_cu);
-    size_t stride = 0;
-    if (BIG) {
-        stride = (arr + 255) & ~(size_t)255;
-        grid = std::max<int64_t>(1, std::min<int64_t>(grid, (int64_t)(ITEMFOLD_SCRATCH / stride)));
-        RC(scratch.alloc((size_t)grid * stride));
-    }
-    HIPCHK(hipFuncSetAttribute((const void*)k_itemfold<T, BLOCK, BIG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_itemfold<T, BLOCK, BIG>), dim3((unsigned)grid), dim3(BLOCK), lds, v.st, D.R, D.X, D.geo, (int)first, (int)count, dV0, dOut,
-                       serve_U<T>(v), tab, dPer, c.lambda, c.stepsize, c.cg_max, c.cg_tol, c.steps, c.solver_type == PCR_SOLVER_PCR ? 1 : 0, cap,
-                       scratch.p, stride);
-    HIPCHK(hipGetLastError());
-    return PCR_OK;
-}
-
-template <typename T, int BLOCK>
-static int rater_scores_launch(const ServeView& v, const ItemfoldDev& D, const int32_t* d_order, int64_t count, T* tab) {
-    if (count <= 0) return PCR_OK;
-    const int64_t grid = std::min<int64_t>(count, (int64_t)D.cus * (BLOCK == 64 ? 32 : 8));
-    hipLaunchKernelGGL((k_rater_scores<T, BLOCK>), dim3((unsigned)grid), dim3(BLOCK), carve_bytes(D.geo.ld, sizeof(T)), v.st, D.R, D.geo, d_order,
-                       (int)count, serve_U<T>(v), serve_V<T>(v), tab);
-    HIPCHK(hipGetLastError());
-    return PCR_OK;
-}
-
-template <typename T>
-static int itemfold_run(const ServeView& v, const FoldinParams& c, const PcrItemfoldPlan& P, const double* V0, double* V_out, pcr_itemfold_stats* stats,
-                        double* per_item) {
-    const int64_t n = P.n, nr = (int64_t)P.raters.size();
-    hipStream_t st = v.st;
-    ItemfoldDev D;
-    D.geo.r = v.r; D.geo.ld = v.ld; D.geo.nchunk = v.ld / VecOf<T>::N; D.geo.G = std::min(64, host_pow2(D.geo.nchunk));
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    HIPCHK(hipDeviceGetAttribute(&D.cus, hipDeviceAttributeMultiprocessorCount, dev));
-    D.cus = std::max(D.cus, 1);
-    size_t table_cap = ITEMFOLD_TABLE;
-    { std::string knob; if (pcr_tune_get("itemfold_table_bytes", &knob) && atoll(knob.c_str()) > 0) table_cap = (size_t)atoll(knob.c_str()); }
-    DBuf<int64_t> sptr;
-    DBuf<int32_t> orig, anypair, puser, pq;
-    DBuf<T> dV0, dOut;
-    DBuf<double> dPer, dOutD;
-    RC(sptr.upload(P.sptr, st)); RC(orig.upload(P.order, st)); RC(anypair.upload(P.anypair, st)); RC(puser.upload(P.puser, st)); RC(pq.upload(P.pq, st));
-    RC(dV0.alloc((size_t)n * v.ld)); RC(dOut.alloc((size_t)n * v.ld)); RC(dPer.alloc((size_t)n * PCR_ITEMFOLD_FIELDS)); RC(dOutD.alloc((size_t)n * v.r));
-    if (V0) RC(upload_rows<T>(st, v.r, v.ld, {{V0, n, dV0.p}}));
-    else HIPCHK(hipMemsetAsync(dV0.p, 0, (size_t)n * v.ld * sizeof(T), st));
-    std::vector<int32_t> local((size_t)nr, -1), braters, ploc, ruser, rorder;
-    std::vector<int64_t> rptr;
-    std::vector<int32_t> ritem;
-    std::vector<uint16_t> rlvl;
-    auto rlen = [&](int32_t r) { return P.R.index[(size_t)r + 1] - P.R.index[(size_t)r]; };
-    for (int64_t b0 = 0; b0 < n;) {
-        // the batch [b0, b1): slots are added while the table of their unique raters stays within the cap
-        for (int32_t r : braters) local[(size_t)r] = -1;
-        braters.clear();
-        size_t bytes = 0;
-        int64_t b1 = b0;
-        for (; b1 < n; ++b1) {
-            const size_t mark = braters.size();
-            size_t add = 0;
-            for (int64_t z = P.sptr[(size_t)b1]; z < P.sptr[(size_t)b1 + 1]; ++z) {
-                const int32_t r = P.prater[(size_t)z];
-                if (local[(size_t)r] < 0) { local[(size_t)r] = (int32_t)braters.size(); braters.push_back(r); add += (size_t)rlen(r) * (sizeof(T) + 2); }
-            }
-            if (b1 > b0 && bytes + add > table_cap) {
-                for (size_t q = mark; q < braters.size(); ++q) local[(size_t)braters[q]] = -1;
-                braters.resize(mark);
-                break;
-            }
-            bytes += add;
-        }
-        const int64_t nb = (int64_t)braters.size(), pair0 = P.sptr[(size_t)b0], pair1 = P.sptr[(size_t)b1];
-        rptr.assign((size_t)nb + 1, 0); ruser.resize((size_t)nb); rorder.resize((size_t)nb);
-        for (int64_t i = 0; i < nb; ++i) {
-            rptr[(size_t)i + 1] = rptr[(size_t)i] + rlen(braters[(size_t)i]);
-            ruser[(size_t)i] = P.raters[(size_t)braters[(size_t)i]];
-            rorder[(size_t)i] = (int32_t)i;
-        }
-        const int64_t flat = rptr[(size_t)nb];
-        ritem.resize((size_t)flat); rlvl.resize((size_t)flat);
-        for (int64_t i = 0; i < nb; ++i) {
-            const int64_t a = P.R.index[(size_t)braters[(size_t)i]], len = rlen(braters[(size_t)i]);
-            std::copy(P.R.item.begin() + a, P.R.item.begin() + a + len, ritem.begin() + rptr[(size_t)i]);
-            std::copy(P.lv.level.begin() + a, P.lv.level.begin() + a + len, rlvl.begin() + rptr[(size_t)i]);
-        }
-        // raters by descending length (equal lengths in batch order): the wave form is the tail
-        std::stable_sort(rorder.begin(), rorder.end(), [&](int32_t x, int32_t y) { return rptr[(size_t)x + 1] - rptr[(size_t)x] > rptr[(size_t)y + 1] - rptr[(size_t)y]; });
-        int64_t n_wg = 0;
-        while (n_wg < nb && rptr[(size_t)rorder[(size_t)n_wg] + 1] - rptr[(size_t)rorder[(size_t)n_wg]] > PCR_ITEMFOLD_SCORES_WAVE_MAX) ++n_wg;
-        ploc.resize((size_t)(pair1 - pair0));
-        for (int64_t z = pair0; z < pair1; ++z) ploc[(size_t)(z - pair0)] = local[(size_t)P.prater[(size_t)z]];
-        DBuf<int64_t> d_rptr;
-        DBuf<int32_t> d_ruser, d_ritem, d_rorder, d_ploc;
-        DBuf<uint16_t> d_rlvl;
-        DBuf<T> tab;
-        DBuf<char> scratch;
-        RC(d_rptr.upload(rptr, st)); RC(d_ruser.upload(ruser, st)); RC(d_ritem.upload(ritem, st)); RC(d_rlvl.upload(rlvl, st));
-        RC(d_rorder.upload(rorder, st)); RC(d_ploc.upload(ploc, st)); RC(tab.alloc((size_t)flat));
-        D.R = {d_rptr.p, d_ruser.p, d_ritem.p, d_rlvl.p};
-        D.X = {sptr.p, orig.p, anypair.p, puser.p, pq.p, d_ploc.p, pair0};
-        {
-            ProfScope ps(v.prof, "itemfold/scores", st);
-            RC((rater_scores_launch<T, 256>(v, D, d_rorder.p, n_wg, tab.p)));
-            RC((rater_scores_launch<T, 64>(v, D, d_rorder.p + n_wg, nb - n_wg, tab.p)));
-        }
-        {
-            ProfScope ps(v.prof, "itemfold/newton", st);
-            const int64_t e_big = std::min(b1, P.n_big), e_lds = std::min(b1, P.n_big + P.n_lds);
-            RC((itemfold_launch<T, 512, true>(v, c, P, D, b0, e_big, dV0.p, dOut.p, tab.p, dPer.p, scratch)));
-            RC((itemfold_launch<T, 256, false>(v, c, P, D, std::max(b0, P.n_big), e_lds, dV0.p, dOut.p, tab.p, dPer.p, scratch)));
-            RC((itemfold_launch<T, 64, false>(v, c, P, D, std::max(b0, P.n_big + P.n_lds), b1, dV0.p, dOut.p, tab.p, dPer.p, scratch)));
-        }
-        HIPCHK(hipStreamSynchronize(st));        // the batch's buffers go out of scope
-        b0 = b1;
-    }
-    hipLaunchKernelGGL((k_mat_out<T>), dim3((unsigned)std::min<int64_t>(1 << 16, cdiv(n * v.r, 256))), dim3(256), 0, st, (const T*)dOut.p, dOutD.p, n, v.r, v.ld);
-    HIPCHK(hipGetLastError());
-    std::vector<double> hp((size_t)n * PCR_ITEMFOLD_FIELDS);
-    HIPCHK(hipMemcpyAsync(V_out, dOutD.p, (size_t)n * v.r * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hp.data(), dPer.p, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (stats) { stats->unique_raters = nr; pcr_itemfold_stats_from(hp.data(), n, stats); }
-    if (per_item) std::copy(hp.begin(), hp.end(), per_item);
-    return PCR_OK;
-}
-
 extern "C" {
 
 // users[n] (global ids, NULL: the whole shard) as rows of s's shard in loc (left empty for NULL); *n the count
@@ -1650,136 +1228,6 @@ int pcr_evaluate_rerank_model(const double* U, int64_t d1, const double* V, int6
         return tradeoff_run<decltype(zero)>("pcr_evaluate_rerank_model", v, info.p, n, users, nth, thetas, pool, ncut, cutoffs, threshold,
                                             tindex != nullptr, topn, div, per_user_topn, per_user_div, exposure);
     });
-    });
-}
-
-int pcr_fold_in_model(const pcr_params* p, const double* V, int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val,
-                      const double* U0, int steps, double* U_out, pcr_foldin_stats* stats, double* per_user) {
-    return abi_guard("pcr_fold_in_model", [&]() -> int {
-    PcrFoldinPlan P;
-    RC(pcr_fold_in_model_check(p, V, d2, n, index, item, val, steps, U_out, &P));
-    RC(model_device(p->device));
-    if (stats) *stats = pcr_foldin_stats{};
-    if (n == 0) return PCR_OK;
-    ServeView v; ModelDev M;
-    RC(M.open(nullptr, n, V, d2, p->k, nullptr, nullptr, true, p->precision, &v));
-    const FoldinParams c = foldin_params_of(*p, steps);
-    return by_precision(v, [&](auto zero) -> int { return foldin_run<decltype(zero)>(v, c, P, U0, U_out, stats, per_user); });
-    });
-}
-
-int pcr_fold_in(pcr_solver* s, int64_t n, const int64_t* index, const int32_t* item, const double* val, const double* U0, int steps,
-                double* U_out, pcr_foldin_stats* stats, double* per_user) {
-    S_OR_ARG;
-    return abi_guard("pcr_fold_in", [&]() -> int {
-        pcr_params prm;
-        RC(s->foldin_params(&prm));
-        const ServeView v = solver_view(s, 0);
-        PcrFoldinPlan P;
-        RC(pcr_fold_in_check("pcr_fold_in", prm.solver_type, v.d2, n, index, item, val, steps, U_out, &P));
-        if (stats) *stats = pcr_foldin_stats{};
-        if (n == 0) return PCR_OK;
-        const FoldinParams c = foldin_params_of(prm, steps);
-        return by_precision(v, [&](auto zero) -> int { return foldin_run<decltype(zero)>(v, c, P, U0, U_out, stats, per_user); });
-    });
-}
-
-int pcr_fold_in_ridge_model(const double* F, int64_t rows, int64_t k, double lambda, int weighted, int precision, int device, int64_t n,
-                            const int64_t* index, const int32_t* item, const double* val, double* U_out, pcr_ridge_stats* stats, double* per_user) {
-    return abi_guard("pcr_fold_in_ridge_model", [&]() -> int {
-    PcrRidgePlan P;
-    RC(pcr_fold_in_ridge_check("pcr_fold_in_ridge_model", true, F, rows, k, lambda, precision, n, index, item, val, U_out, &P));
-    RC(model_device(device));
-    if (stats) *stats = pcr_ridge_stats{};
-    if (n == 0) return PCR_OK;
-    ServeView v; ModelDev M;
-    RC(M.open(nullptr, n, F, rows, k, nullptr, nullptr, true, precision, &v));
-    return by_precision(v, [&](auto zero) -> int { return ridge_run<decltype(zero)>(v, lambda, weighted != 0, P, U_out, stats, per_user); });
-    });
-}
-
-int pcr_fold_in_ridge(pcr_solver* s, int weighted, int64_t n, const int64_t* index, const int32_t* item, const double* val, double* U_out,
-                      pcr_ridge_stats* stats, double* per_user) {
-    S_OR_ARG;
-    return abi_guard("pcr_fold_in_ridge", [&]() -> int {
-        const ServeView v = solver_view(s, 0);
-        const double lambda = s->ridge_lambda();
-        PcrRidgePlan P;
-        RC(pcr_fold_in_ridge_check("pcr_fold_in_ridge", false, nullptr, v.d2, v.r, lambda, v.dtype, n, index, item, val, U_out, &P));
-        if (stats) *stats = pcr_ridge_stats{};
-        if (n == 0) return PCR_OK;
-        return by_precision(v, [&](auto zero) -> int { return ridge_run<decltype(zero)>(v, lambda, weighted != 0, P, U_out, stats, per_user); });
-    });
-}
-
-int pcr_fold_in_nnls_model(const double* F, int64_t rows, int64_t k, double lambda, int weighted, int precision, int device, int64_t n,
-                           const int64_t* index, const int32_t* item, const double* val, double* U_out, pcr_nnls_stats* stats, double* per_user) {
-    return abi_guard("pcr_fold_in_nnls_model", [&]() -> int {
-    PcrRidgePlan P;
-    RC(pcr_fold_in_nnls_check("pcr_fold_in_nnls_model", true, F, rows, k, lambda, precision, n, index, item, val, U_out, &P));
-    RC(model_device(device));
-    if (stats) *stats = pcr_nnls_stats{};
-    if (n == 0) return PCR_OK;
-    ServeView v; ModelDev M;
-    RC(M.open(nullptr, n, F, rows, k, nullptr, nullptr, true, precision, &v));
-    return by_precision(v, [&](auto zero) -> int { return nnls_run<decltype(zero)>(v, lambda, weighted != 0, P, U_out, stats, per_user); });
-    });
-}
-
-int pcr_fold_in_nnls(pcr_solver* s, int weighted, int64_t n, const int64_t* index, const int32_t* item, const double* val, double* U_out,
-                     pcr_nnls_stats* stats, double* per_user) {
-    S_OR_ARG;
-    return abi_guard("pcr_fold_in_nnls", [&]() -> int {
-        const ServeView v = solver_view(s, 0);
-        const double lambda = s->ridge_lambda();
-        PcrRidgePlan P;
-        RC(pcr_fold_in_nnls_check("pcr_fold_in_nnls", false, nullptr, v.d2, v.r, lambda, v.dtype, n, index, item, val, U_out, &P));
-        if (stats) *stats = pcr_nnls_stats{};
-        if (n == 0) return PCR_OK;
-        return by_precision(v, [&](auto zero) -> int { return nnls_run<decltype(zero)>(v, lambda, weighted != 0, P, U_out, stats, per_user); });
-    });
-}
-
-int pcr_fold_in_items_model(const pcr_params* p, const double* U, int64_t d1, const double* V, int64_t d2, const int64_t* tr_index,
-                            const int32_t* tr_item, const double* tr_val, int64_t n, const int64_t* index, const int32_t* user, const double* val,
-                            const double* V0, int steps, double* V_out, pcr_itemfold_stats* stats, double* per_item) {
-    return abi_guard("pcr_fold_in_items_model", [&]() -> int {
-    PcrItemfoldPlan P;
-    RC(pcr_fold_in_items_check("pcr_fold_in_items_model", true, p, U, d1, V, d2, tr_index, tr_item, tr_val, n, index, user, val, steps, V_out, &P));
-    RC(model_device(p->device));
-    if (stats) *stats = pcr_itemfold_stats{};
-    if (n == 0) return PCR_OK;
-    ServeView v; ModelDev M;
-    RC(M.open(U, d1, V, d2, p->k, nullptr, nullptr, true, p->precision, &v));
-    const FoldinParams c = foldin_params_of(*p, steps);
-    return by_precision(v, [&](auto zero) -> int { return itemfold_run<decltype(zero)>(v, c, P, V0, V_out, stats, per_item); });
-    });
-}
-
-int pcr_fold_in_items(pcr_solver* s, const pcr_dataset* train, int64_t n, const int64_t* index, const int32_t* user, const double* val,
-                      const double* V0, int steps, double* V_out, pcr_itemfold_stats* stats, double* per_item) {
-    S_OR_ARG;
-    return abi_guard("pcr_fold_in_items", [&]() -> int {
-        pcr_params prm;
-        if (s->foldin_params(&prm) != PCR_OK) return pcr_solver::pcr_only("pcr_fold_in_items");
-        const ServeView v = solver_view(s, 0);
-        if (s->comm_nranks() > 1 || s->first_user != 0 || s->n_users != v.d1) {
-            pcr_set_error("pcr_fold_in_items: needs every user on the rank; this solver holds a shard");
-            return PCR_ERR_STATE;
-        }
-        if (!train) { pcr_set_error("pcr_fold_in_items: null training data set"); return PCR_ERR_ARG; }
-        const PcrCsr& X = train->train;
-        if (X.d1 != v.d1 || X.d2 != v.d2 || X.nnz() != v.nnz) {
-            pcr_set_error("pcr_fold_in_items: the data set is not the one the solver was created from (dimensions or nnz differ)");
-            return PCR_ERR_ARG;
-        }
-        PcrItemfoldPlan P;
-        RC(pcr_fold_in_items_check("pcr_fold_in_items", false, &prm, nullptr, X.d1, nullptr, X.d2, X.index.data(), X.item.data(), X.val.data(), n, index,
-                                   user, val, steps, V_out, &P));
-        if (stats) *stats = pcr_itemfold_stats{};
-        if (n == 0) return PCR_OK;
-        const FoldinParams c = foldin_params_of(prm, steps);
-        return by_precision(v, [&](auto zero) -> int { return itemfold_run<decltype(zero)>(v, c, P, V0, V_out, stats, per_item); });
     });
 }
 
