@@ -63,8 +63,9 @@ def class_of(n):
     return f"len {n} (class > 4096, global scratch)"
 
 
-def brute_force(c, idx, item, val, block=512):
-    """The definition, in integers.  With M = 4 m, U2 = 2 U, V2 = 2 V:
+def brute_force(c, idx, item, val, block=512, levels=None):
+    """The definition, in integers (levels: each rating's level, in CSR order; None: levels_of(val, c.solver)).
+    With M = 4 m, U2 = 2 U, V2 = 2 V:
         16 obj = sum_u sum_{level_j > level_k} max(0, 4 - (M_j - M_k))^2 + 2 lambda (|U2|^2 + |V2|^2)
         4 g[item_j] += -d U2[u],  4 g[item_k] += +d U2[u]   for every such pair with d = 4 - (M_j - M_k) > 0,   4 g += 2 lambda V2
     Returns (16 obj, 4 g, 4 m, pairs inside the hinge, comparable pairs), all int64."""
@@ -73,7 +74,7 @@ def brute_force(c, idx, item, val, block=512):
     lam2 = int(2 * c.lam)
     assert lam2 == 2 * c.lam
     M = (U2[np.repeat(np.arange(c.d1), np.diff(idx))] * V2[item]).sum(1)          # 4 m, CSR order
-    lev = levels_of(val, c.solver)
+    lev = levels_of(val, c.solver) if levels is None else np.asarray(levels)
     g4 = lam2 * V2
     obj16 = lam2 * int((U2 * U2).sum() + (V2 * V2).sum())
     active = comparable = 0

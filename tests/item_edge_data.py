@@ -97,8 +97,9 @@ def item_edge_case(r, solver, real=False):
     return c
 
 
-def brute_force_Ha(c, idx, item, val, a, block=512):
-    """The definition of the Hessian-vector product, in integers, beside exact_data.brute_force.  With M = 4 m, U2 = 2 U, A2 = 2 a
+def brute_force_Ha(c, idx, item, val, a, block=512, levels=None):
+    """The definition of the Hessian-vector product, in integers, beside exact_data.brute_force (levels: each rating's level, in
+    CSR order; None: exact_data.levels_of(val, c.solver)).  With M = 4 m, U2 = 2 U, A2 = 2 a
     and S = 4 (u . a) = U2[u] . A2[item] per rating:
         4 Ha[item_j] += (S_j - S_k) U2[u],  4 Ha[item_k] -= (S_j - S_k) U2[u]   for every active pair level_j > level_k,
         4 Ha += 2 lambda A2
@@ -114,7 +115,7 @@ def brute_force_Ha(c, idx, item, val, a, block=512):
     ru = np.repeat(np.arange(d1), np.diff(idx))
     M = (U2[ru] * V2[item]).sum(1)
     S = (U2[ru] * A2[item]).sum(1)
-    lev = ed.levels_of(val, c.solver)
+    lev = ed.levels_of(val, c.solver) if levels is None else np.asarray(levels)
     Ha4 = lam2 * A2
     for u in range(d1):
         s, e = int(idx[u]), int(idx[u + 1])
