@@ -751,6 +751,59 @@ int pcr_recommend_diverse(pcr_solver *s, int64_t n, const int32_t *users, int to
                           int flags, int32_t *items, double *scores);                                 /* [device] */
 
 /* ------------------------------------------------------------------------- */
+/* group-capped top-K lists: at most `cap` items of one group (no reference    */
+/* counterpart)                                                               */
+/* ------------------------------------------------------------------------- */
+/* "At most two items of the same artist / brand / seller / genre in a list": topk items are taken in recommendation order from
+ * a pool of the user's `pool` best items, skipping an item once its group is full.  Selected on the device; only the capped lists
+ * and one status byte per user leave it.  The library knows no item metadata: the caller brings group[d2], one int32 per item
+ * -- any non-negative values are group ids, they need not be dense; a negative value means the item belongs to no group and is
+ * never capped.  cap >= 1; 1 <= topk <= pool <= PCR_RECOMMEND_MAX_K.  For each requested user u:
+ *   Pool P_u           exactly the list pcr_recommend_filtered(_model) returns for the same factors, dtype, exclusion, allow set
+ *                      and K = pool, without its padding (without an allow set: pcr_recommend(_model)'s list): L entries
+ *                      (j_i, s_i), i = 0 .. L - 1, in the recommendation order, the scores the same bits.
+ *   Rule               walk the pool in order; entry i is kept iff group[j_i] < 0 or fewer than cap earlier pool entries (kept
+ *                      or not) have the same group id.  (Counting kept entries only gives the same lists: once a group is full
+ *                      every later entry of it is dropped anyway.)  Integer compares only.
+ *   Output             items[n * topk] and scores[n * topk]: the first topk kept entries in pool order, each with its original
+ *                      s_i converted to double; a row shorter than topk ends with (-1, -INFINITY).
+ *   Status             status[n], one uint8 per requested user (NULL: not written): PCR_CAP_EXACT when the row holds topk items
+ *                      or L < pool (the pool is the user's whole eligible catalogue); PCR_CAP_POOL_EXHAUSTED otherwise: a full
+ *                      pool ran out before topk items were kept, and a larger pool may continue the list.  A PCR_CAP_EXACT row
+ *                      is bit for bit the group-capped top-topk of the user's whole eligible catalogue (an entry's fate depends
+ *                      on the entries before it alone, and the pool is a prefix of the catalogue in recommendation order); a
+ *                      PCR_CAP_POOL_EXHAUSTED row is a prefix of that list.
+ *   Summary            stats (NULL: not written): users = n, exact / exhausted = the users of either status, short_rows = the
+ *                      rows with fewer than topk items, kept = the items listed in all rows.
+ *   Consequences       with every group id negative, or all group ids distinct, or cap >= pool, the result is pcr_recommend's
+ *                      top-topk list bit for bit and every status is PCR_CAP_EXACT; the first kept entry is always pool position
+ *                      0; with cap = 1 and a single group every non-empty pool gives exactly one item.
+ *   Determinism        a row depends on (u, its pool, group, cap) alone -- not on the other users, the order of users[], batches
+ *                      or item splits; two identical calls are bitwise identical; no floating-point arithmetic at all.
+ *   Filter             f (NULL: none) as in pcr_recommend_filtered: an allow set restricts the pool.  Candidate rows (cand_ptr)
+ *                      are PCR_ERR_UNSUPPORTED; a filter with nothing in it is PCR_ERR_ARG (pass NULL).
+ *   Errors             group == NULL, cap < 1, topk < 1, pool < topk, pool > PCR_RECOMMEND_MAX_K and every argument error of
+ *                      pcr_recommend_filtered_model are PCR_ERR_ARG, reported on the host before any device is looked for; the
+ *                      message names the entry.  Without a device: PCR_ERR_DEVICE. */
+#define PCR_CAP_EXACT          0
+#define PCR_CAP_POOL_EXHAUSTED 1
+typedef struct pcr_cap_stats {
+    int64_t users, exact, exhausted, short_rows, kept;
+} pcr_cap_stats;
+int pcr_recommend_capped_model(const double *U, int64_t d1, const double *V, int64_t d2, int64_t k,
+                               const int64_t *index, const int32_t *item, int64_t n, const int32_t *users,
+                               int topk, int pool, const int32_t *group, int cap, int dtype, const pcr_item_filter *f,
+                               int32_t *items, double *scores, uint8_t *status, pcr_cap_stats *stats,
+                               int device);                                                           /* [device] */
+/* On a live PCR, PCR++ or CCDR1 solver, as pcr_recommend: its device factors, storage type and stream; users[n] are GLOBAL ids
+ * of this rank's shard (NULL: all of them); flags PCR_REC_EXCLUDE_TRAIN; training state is not touched.  stats are this rank's
+ * own counts: per user, nothing is exchanged, so it works on every communicator and on local-only shards.
+ * Profile slots: recommend/score, and recommend/cap (the merge with the selection fused in). */
+int pcr_recommend_capped(pcr_solver *s, int64_t n, const int32_t *users, int topk, int pool, const int32_t *group,
+                         int cap, int flags, const pcr_item_filter *f, int32_t *items, double *scores,
+                         uint8_t *status, pcr_cap_stats *stats);                                      /* [device] */
+
+/* ------------------------------------------------------------------------- */
 /* evaluating given and re-ranked lists (no reference counterpart)            */
 /* ------------------------------------------------------------------------- */
 /* The metrics of "full-catalogue top-N evaluation" and of "beyond-accuracy top-N metrics" above, definition for definition,

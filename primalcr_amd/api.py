@@ -13,6 +13,7 @@ PCR_RECOMMEND_MAX_K = 1024
 PCR_REC_EXCLUDE_TRAIN = 1
 PCR_TOPN_MAX_CUTOFFS = 8
 PCR_RERANK_MAX_THETAS = 8
+PCR_CAP_EXACT, PCR_CAP_POOL_EXHAUSTED = 0, 1
 # evaluate_ranks' stage lengths (include/primalcr.h, pcr_topk.h): relevant rows up to these lengths are counted in LDS by the
 # full sweep / by the candidate-row kernel, longer ones in global memory; results do not depend on them (tests straddle them)
 PCR_RANK_STAGE, PCR_CAND_RANK_STAGE = 32, 64
@@ -116,6 +117,11 @@ class RankStats(C.Structure):
 class ItemFilter(C.Structure):
     """pcr_item_filter."""
     _fields_ = [("allow", C.c_void_p), ("cand_ptr", C.c_void_p), ("cand_item", C.c_void_p)]
+
+
+class CapStats(C.Structure):
+    """pcr_cap_stats."""
+    _fields_ = [("users", C.c_int64), ("exact", C.c_int64), ("exhausted", C.c_int64), ("short_rows", C.c_int64), ("kept", C.c_int64)]
 
 
 class FoldinStats(C.Structure):
@@ -224,6 +230,10 @@ def lib():
         L.pcr_recommend_filtered.argtypes = [vp, i64, vp, ci, ci, C.POINTER(ItemFilter), vp, vp]
     L.pcr_recommend_diverse_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, vp, ci, ci, cd, ci, vp, vp, ci]
     L.pcr_recommend_diverse.argtypes = [vp, i64, vp, ci, ci, cd, ci, vp, vp]
+    if hasattr(L, "pcr_recommend_capped"):                      # (absent from an older build loaded through use_library)
+        L.pcr_recommend_capped_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, vp, ci, ci, vp, ci, ci, C.POINTER(ItemFilter), vp, vp, vp,
+                                                 C.POINTER(CapStats), ci]
+        L.pcr_recommend_capped.argtypes = [vp, i64, vp, ci, ci, vp, ci, ci, C.POINTER(ItemFilter), vp, vp, vp, C.POINTER(CapStats)]
     L.pcr_evaluate_topn_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, ci, vp, cd, ci, vp, vp, ci]
     L.pcr_evaluate_topn.argtypes = [vp, ci, vp, cd, ci, vp, vp]
     L.pcr_evaluate_ranks_model.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, cd, ci, vp, vp, vp, ci]
@@ -436,6 +446,58 @@ def recommend_diverse(U, V, topk, pool=None, theta=0.5, exclude=None, users=None
                                            None if it is None else it.ctypes.data, n, None if users is None else users.ctypes.data,
                                            topk, pool, theta, int(dtype), items.ctypes.data, scores.ctypes.data, device))
     return items, scores
+
+
+def _cap_args(topk, pool, groups, cap, d2):
+    """Shared by recommend_capped() and Solver.recommend_capped(): (topk, pool, groups int32 [d2], cap) checked as the library
+    checks them; pool None = _rerank_args' default.  d2 None: the length of groups is left to the caller."""
+    topk, pool, _ = _rerank_args(topk, pool, 0.0)
+    cap = int(cap)
+    if cap < 1:
+        raise ValueError(f"cap = {cap} must be at least 1")
+    if groups is None:
+        raise ValueError("groups: one group id per item is expected")
+    g = np.asarray(groups)
+    if g.ndim != 1 or (d2 is not None and g.shape[0] != d2) or not np.issubdtype(g.dtype, np.integer):
+        raise ValueError(f"groups: d2 = {d2} integer group ids are expected, got shape {g.shape} of {g.dtype}")
+    if g.size and (g.max() > np.iinfo(np.int32).max or g.min() < np.iinfo(np.int32).min):
+        raise ValueError("groups: a group id outside int32")
+    return topk, pool, np.ascontiguousarray(g, np.int32), cap
+
+
+def _cap_result(items, scores, status, st):
+    return items, scores, status, dict(users=st.users, exact=st.exact, exhausted=st.exhausted, short_rows=st.short_rows, kept=st.kept)
+
+
+def recommend_capped(U, V, topk, groups, cap, pool=None, exclude=None, users=None, dtype=PCR_F64, device=0, allow=None):
+    """Group-capped top-K lists on the GPU (pcr_recommend_capped_model): the first topk of the `pool` best items of recommend()
+    that the rule "at most cap items of one group" keeps.  groups: one integer per item, a negative id = in no group, never
+    capped.  pool None: min(1024, 10 topk).  exclude / users / dtype / allow as recommend().  Returns (items int32 [n, topk],
+    scores float64 [n, topk], status uint8 [n], stats dict): status PCR_CAP_EXACT = the row is the capped top-K of the whole
+    eligible catalogue, PCR_CAP_POOL_EXHAUSTED = a full pool ran out first (the row is a prefix; a larger pool may continue it)."""
+    U = np.ascontiguousarray(U, np.float64); V = np.ascontiguousarray(V, np.float64)
+    d1, k = U.shape
+    topk, pool, groups, cap = _cap_args(topk, pool, groups, cap, V.shape[0])
+    idx = it = None
+    if exclude is not None:
+        if isinstance(exclude, Dataset):
+            idx, it, _ = exclude.csr(0)
+        else:
+            idx, it = exclude[:2]
+        idx = np.ascontiguousarray(idx, np.int64); it = np.ascontiguousarray(it, np.int32)
+        if idx.shape[0] != d1 + 1 or idx[-1] != it.shape[0]:
+            raise ValueError(f"exclude: index must have d1 + 1 = {d1 + 1} entries, the last equal to len(item) = {it.shape[0]}")
+    if users is not None:
+        users = np.ascontiguousarray(users, np.int32)
+    n = d1 if users is None else users.shape[0]
+    f, _keep = _item_filter(allow, None, V.shape[0], n)
+    items = np.empty((n, topk), np.int32); scores = np.empty((n, topk), np.float64); status = np.empty(n, np.uint8)
+    st = CapStats()
+    _chk(lib().pcr_recommend_capped_model(U.ctypes.data, d1, V.ctypes.data, V.shape[0], k, None if idx is None else idx.ctypes.data,
+                                          None if it is None else it.ctypes.data, n, None if users is None else users.ctypes.data,
+                                          topk, pool, groups.ctypes.data, cap, int(dtype), None if allow is None else C.byref(f),
+                                          items.ctypes.data, scores.ctypes.data, status.ctypes.data, C.byref(st), device))
+    return _cap_result(items, scores, status, st)
 
 
 def _topn_call(cutoffs, per_user, rows, fn):
@@ -1300,6 +1362,21 @@ class Solver:
         _chk(lib().pcr_recommend_diverse(self._h, n, None if users is None else users.ctypes.data, topk, pool, theta,
                                          PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, items.ctypes.data, scores.ctypes.data))
         return items, scores
+
+    def recommend_capped(self, topk=10, groups=None, cap=1, pool=None, users=None, exclude_train=True, allow=None):
+        """Group-capped top-K lists from the device factors (pcr_recommend_capped), in the solver's storage type; arguments and
+        result as recommend_capped(), users as Solver.recommend().  The stats are this rank's own counts."""
+        topk, pool, groups, cap = _cap_args(topk, pool, groups, cap, None if self is None else self.d2)
+        if users is not None:
+            users = np.ascontiguousarray(users, np.int32)
+        n = self.n_users if users is None else users.shape[0]
+        f, _keep = _item_filter(allow, None, self.d2, n)
+        items = np.empty((n, topk), np.int32); scores = np.empty((n, topk), np.float64); status = np.empty(n, np.uint8)
+        st = CapStats()
+        _chk(lib().pcr_recommend_capped(self._h, n, None if users is None else users.ctypes.data, topk, pool, groups.ctypes.data, cap,
+                                        PCR_REC_EXCLUDE_TRAIN if exclude_train else 0, None if allow is None else C.byref(f),
+                                        items.ctypes.data, scores.ctypes.data, status.ctypes.data, C.byref(st)))
+        return _cap_result(items, scores, status, st)
 
     def evaluate_topn(self, cutoffs=(10,), threshold=-np.inf, exclude_train=True, per_user=False, allow=None, candidates=None):
         """Full-catalogue top-N evaluation of this shard's users against the solver's test ratings (pcr_evaluate_topn); the

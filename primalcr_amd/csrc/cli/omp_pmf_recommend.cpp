@@ -19,7 +19,7 @@
 //     --mmr theta    re-rank every list by Maximal Marginal Relevance (pcr_recommend_diverse_model): the -K items are taken
 //                    greedily from the user's P best, theta in [0, 1] weighing likeness (cosine of rows of V) against score;
 //                    the output format is that of the plain list; not together with --eval or --diversity
-//     --pool P       the pool of --mmr (default min(1024, 10 K)); refused without --mmr
+//     --pool P       the pool of --mmr (default min(1024, 10 K)); refused without --mmr, --tradeoff or --max-per-group
 //   omp-pmf-recommend --tradeoff t1,t2,... [--pool P] [-K topk] [-c c1,...] [--eval data_dir [--threshold v]] [-x data_dir] [-u users_file] [--f32] model_file
 //     --tradeoff ts  the accuracy / diversity trade-off of --mmr (pcr_evaluate_rerank_model): at most PCR_RERANK_MAX_THETAS thetas
 //                    in [0, 1]; the catalogue is scored once, every theta's lists are re-ranked and evaluated on the device.  The
@@ -74,6 +74,13 @@
 //                    (pcr_sample_negatives, --seed S, default 0) from those in neither its test row nor -x's training row
 //                    All three go with --eval only (with or without --ranks), intersect, keep the formats of --eval / --ranks and
 //                    are refused with --fold-in*, --diversity, --mmr and --tradeoff; --negatives does not go with --eval-candidates
+//   omp-pmf-recommend --groups file --max-per-group q [--pool P] [--allow items_file] [-K topk] [-x data_dir] [-u users_file] [--f32] [--scores] model_file output_file
+//     --groups file  exactly d2 lines: line j holds the integer group id of item j, a negative id means "in no group"
+//     --max-per-group q  at most q items of one group in a list (pcr_recommend_capped_model): the -K items are the first of the
+//                    user's P best (--pool, default min(1024, 10 K)) that the rule keeps; the output format is that of the plain
+//                    list; stdout gets one line "capped users n exact n pool_exhausted n short n kept n".  The two flags go
+//                    together and with --allow; not together with --candidates, --eval, --diversity, --mmr, --tradeoff, --ranks
+//                    or any --fold-in*
 // Output: one line per user, in input order: the 1-based user id, then the 1-based item ids (padding is left out).  Users go
 // to the device in batches, so host memory for the lists stays bounded on any catalogue.
 // With --eval: stdout gets one line per cutoff, "cutoff c users n users_graded n hits n precision x recall x hit_rate x map x
@@ -87,6 +94,7 @@
 #include <algorithm>
 #include <cerrno>
 #include <charconv>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -154,7 +162,13 @@ static const char* USAGE =
     "    --among file   with --eval: evaluate within these items only (one 1-based item id per line); a test item outside is not relevant\n"
     "    --eval-candidates f  with --eval: evaluate within a candidate row per user; line i: the 1-based items of user i of the model\n"
     "    --negatives N  with --eval: every user's test items against N sampled items outside its test row and -x's training row;\n"
-    "                   --seed S (default 0) picks the sample; not with --eval-candidates; the output keeps --eval's / --ranks' formats\n";
+    "                   --seed S (default 0) picks the sample; not with --eval-candidates; the output keeps --eval's / --ranks' formats\n"
+    "       omp-pmf-recommend --groups file --max-per-group q [--pool P] [--allow items_file] [-K topk] [-x data_dir] [-u users_file] [--f32] [--scores] model_file output_file\n"
+    "    --groups file  one line per item of the model: line j holds the integer group id of item j (negative: in no group)\n"
+    "    --max-per-group q  at most q items of one group in a list: the -K items are the first of the user's P best (--pool, default\n"
+    "                   min(1024, 10 topk)) that the rule keeps; output as the plain list; stdout gets a \"capped users n exact n\n"
+    "                   pool_exhausted n short n kept n\" line; both flags go together and with --allow, not with --candidates,\n"
+    "                   --eval, --diversity, --mmr, --tradeoff, --ranks or --fold-in*\n";
 
 static int usage() { printf("%s", USAGE); return 1; }
 
@@ -568,6 +582,34 @@ static int run_fold_in_items(const char* path, const char* xdir, const char* mod
     return 0;
 }
 
+// --groups: exactly d2 lines, line j the integer group id of item j (negative: in no group)
+static bool read_groups(const char* path, int64_t d2, std::vector<int32_t>& group) {
+    FILE* fp = fopen(path, "r");
+    if (!fp) { fprintf(stderr, "can't open groups file %s\n", path); return false; }
+    group.clear();
+    char line[256];
+    int64_t ln = 0;
+    bool ok = true;
+    while (fgets(line, sizeof line, fp)) {
+        ++ln;
+        char* p = line;
+        while (*p == ' ' || *p == '\t') ++p;
+        errno = 0;
+        char* end = nullptr;
+        const long long v = strtoll(p, &end, 10);
+        const bool none = end == p;                                // (a blank line is no id)
+        while (end && (*end == ' ' || *end == '\t' || *end == '\r' || *end == '\n')) ++end;
+        if (none || errno || !end || *end != 0 || v < INT32_MIN || v > INT32_MAX) {
+            fprintf(stderr, "groups file %s, line %lld: not a group id\n", path, (long long)ln); ok = false; break;
+        }
+        if (ln > d2) break;                                        // (reported below)
+        group.push_back((int32_t)v);
+    }
+    fclose(fp);
+    if (ok && ln != d2) { fprintf(stderr, "groups file %s: %s than the model's %lld items\n", path, ln > d2 ? "more lines" : "fewer lines", (long long)d2); ok = false; }
+    return ok;
+}
+
 int main(int argc, char** argv) {
     int K = 10;
     bool f32 = false, with_scores = false, with_ranks = false, diversity = false;
@@ -585,6 +627,8 @@ int main(int argc, char** argv) {
     const char* rdir = nullptr;                                    // --fold-in-ridge
     const char* ndir = nullptr;                                    // --fold-in-nnls
     const char* ifile = nullptr;                                   // --fold-in-items
+    const char* gfile = nullptr;                                   // --groups
+    int max_per_group = 0;                                         // --max-per-group (0: not given)
     bool have_K = false;
     bool plain_reg = false;
     double lambda = 0.0;
@@ -678,6 +722,17 @@ int main(int argc, char** argv) {
         } else if (!strcmp(a, "--allow") || !strcmp(a, "--candidates")) {
             if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
             (a[2] == 'a' ? afile : cfile) = argv[++i];
+        } else if (!strcmp(a, "--groups")) {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
+            gfile = argv[++i];
+        } else if (!strcmp(a, "--max-per-group")) {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
+            const char* v = argv[++i];
+            char* end = nullptr;
+            errno = 0;
+            const long x = strtol(v, &end, 10);
+            if (!*v || *end || errno || x < 1 || x > INT_MAX) { fprintf(stderr, "--max-per-group %s: must be an integer >= 1\n", v); return 1; }
+            max_per_group = (int)x;
         } else if (!strcmp(a, "--among") || !strcmp(a, "--eval-candidates")) {
             if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
             (a[2] == 'a' ? among : ecfile) = argv[++i];
@@ -702,6 +757,14 @@ int main(int argc, char** argv) {
         else pos.push_back(a);
     }
     const bool tradeoff = !thetas.empty();
+    const bool capped = gfile || max_per_group;                    // (the plain list's flow with pcr_recommend_capped_model)
+    if (capped) {
+        if (!gfile || !max_per_group) { fprintf(stderr, "--groups and --max-per-group go together\n"); return 1; }
+        if (edir || diversity || mmr || tradeoff || with_ranks || ifile || fdir || rdir || ndir || cfile) {
+            fprintf(stderr, "--groups and --max-per-group do not go with --eval, --diversity, --mmr, --tradeoff, --ranks, --fold-in* or --candidates\n");
+            return 1;
+        }
+    }
     if (among || ecfile || negatives >= 0 || have_seed) {          // (the filtered evaluation: --eval's flow with a filter)
         if (!edir) { fprintf(stderr, "--among, --eval-candidates, --negatives and --seed go with --eval\n"); return 1; }
         if (ifile || fdir || rdir || ndir || diversity || mmr || tradeoff) {
@@ -766,12 +829,12 @@ int main(int argc, char** argv) {
     }
     if (diversity && edir) { fprintf(stderr, "--diversity does not go with --eval\n"); return 1; }
     if (mmr && (edir || diversity)) { fprintf(stderr, "--mmr does not go with --eval or --diversity\n"); return 1; }
-    if (pool && !mmr && !tradeoff) { fprintf(stderr, "--pool goes with --mmr\n"); return 1; }
+    if (pool && !mmr && !tradeoff && !capped) { fprintf(stderr, "--pool goes with --mmr\n"); return 1; }
     if (!tradeoff && ((edir || diversity) ? (pos.empty() || pos.size() > 2) : pos.size() != 2)) return usage();
     if (diversity && (with_scores || with_ranks || threshold != -INFINITY)) { fprintf(stderr, "--scores, --ranks and --threshold do not go with --diversity\n"); return 1; }
     if (!edir && !diversity && !tradeoff && (!cuts.empty() || threshold != -INFINITY)) { fprintf(stderr, "-c and --threshold go with --eval\n"); return 1; }
     if (!edir && with_ranks) { fprintf(stderr, "--ranks goes with --eval\n"); return 1; }
-    if (mmr) {
+    if (mmr || capped) {
         if (!pool) pool = std::min(PCR_RECOMMEND_MAX_K, 10 * K);
         if (pool < K) { fprintf(stderr, "--pool %d: below -K %d\n", pool, K); return 1; }
     }
@@ -791,6 +854,8 @@ int main(int argc, char** argv) {
     std::vector<int32_t> citem;
     if (afile && !read_allow(afile, d2, allow)) return 1;
     if (cfile && !read_candidates(cfile, (int64_t)users.size(), d2, cptr, citem)) return 1;
+    std::vector<int32_t> group;                                    // --groups
+    if (gfile && !read_groups(gfile, d2, group)) return 1;
     if (fdir) {                                                    // the new users take the model's users' place: their factors, their ratings excluded
         std::vector<double> U_new;
         if (!run_fold_in(fdir, V, d2, k, lambda, solver, steps, f32, ridge, nnls, plain_reg, &d1, xindex, xitem, U_new)) return 1;
@@ -829,6 +894,7 @@ int main(int argc, char** argv) {
     std::vector<double> scores;
     std::string o;
     bool ok = true;
+    pcr_cap_stats cap_all = {0, 0, 0, 0, 0};                       // --groups: the batches' summaries added up
     for (int64_t b0 = 0; b0 < n && ok; b0 += batch) {
         const int64_t m = std::min(batch, n - b0);
         items.resize((size_t)(m * K)); scores.resize((size_t)(m * K));
@@ -840,7 +906,11 @@ int main(int argc, char** argv) {
             for (int64_t i = 0; i <= m; ++i) bptr[(size_t)i] = cptr[(size_t)(b0 + i)] - cptr[(size_t)b0];
             flt.cand_ptr = bptr.data(); flt.cand_item = citem.data() + cptr[(size_t)b0];
         }
-        const int rc = (afile || cfile) ? pcr_recommend_filtered_model(U.data(), d1, V.data(), d2, k, xi, xt, m, users.data() + b0, K,
+        pcr_cap_stats cst = {0, 0, 0, 0, 0};
+        const int rc = capped ? pcr_recommend_capped_model(U.data(), d1, V.data(), d2, k, xi, xt, m, users.data() + b0, K, pool, group.data(),
+                                                           max_per_group, f32 ? PCR_F32 : PCR_F64, afile ? &flt : nullptr, items.data(),
+                                                           scores.data(), nullptr, &cst, 0)
+                     : (afile || cfile) ? pcr_recommend_filtered_model(U.data(), d1, V.data(), d2, k, xi, xt, m, users.data() + b0, K,
                                                                        f32 ? PCR_F32 : PCR_F64, &flt, items.data(), scores.data(), 0)
                      : mmr ? pcr_recommend_diverse_model(U.data(), d1, V.data(), d2, k, xi, xt, m, users.data() + b0, K, pool, theta,
                                                          f32 ? PCR_F32 : PCR_F64, items.data(), scores.data(), 0)
@@ -851,6 +921,8 @@ int main(int argc, char** argv) {
             fclose(out_fp);
             return 1;
         }
+        cap_all.users += cst.users; cap_all.exact += cst.exact; cap_all.exhausted += cst.exhausted;
+        cap_all.short_rows += cst.short_rows; cap_all.kept += cst.kept;
         o.resize((size_t)(m * (12 + (int64_t)K * (with_scores ? 348 : 12))));
         char* p = &o[0];
         for (int64_t i = 0; i < m; ++i) {
@@ -868,6 +940,9 @@ int main(int argc, char** argv) {
     }
     ok = (fclose(out_fp) == 0) && ok;
     if (!ok) { fprintf(stderr, "short write to %s\n", pos[1]); return 1; }
+    if (capped)
+        printf("capped users %lld exact %lld pool_exhausted %lld short %lld kept %lld\n", (long long)cap_all.users, (long long)cap_all.exact,
+               (long long)cap_all.exhausted, (long long)cap_all.short_rows, (long long)cap_all.kept);
     fflush(stdout); fflush(stderr);
     _exit(0);
 }

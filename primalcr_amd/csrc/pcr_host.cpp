@@ -1481,6 +1481,46 @@ int pcr_recommend_diverse_model_check(const double* U, int64_t d1, const double*
     return pcr_recommend_model_check(U, d1, V, d2, k, index, item, n, users, pool, dtype, items, scores, sorted, who);
 }
 
+// ------------------------------------------------------------------------------ group-capped lists (include/primalcr.h)
+int pcr_cap_check(const char* who, int topk, int pool, const int32_t* group, int cap) {
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
+    if (!group) return bad("null group");
+    if (cap < 1) return bad("cap = " + std::to_string(cap) + " below 1");
+    if (topk < 1) return bad("topk = " + std::to_string(topk) + " below 1");
+    if (pool < topk) return bad("pool = " + std::to_string(pool) + " below topk = " + std::to_string(topk));
+    if (pool > PCR_RECOMMEND_MAX_K) return bad("pool = " + std::to_string(pool) + " above " + std::to_string(PCR_RECOMMEND_MAX_K));
+    return PCR_OK;
+}
+
+int pcr_cap_filter_check(const char* who, const pcr_item_filter* f) {
+    if (!f) return PCR_OK;
+    if (f->cand_ptr) { pcr_set_error(std::string(who) + ": candidate rows do not go with a group cap (an allow set does)"); return PCR_ERR_UNSUPPORTED; }
+    if (!f->allow) { pcr_set_error(std::string(who) + ": a filter without an allow set (NULL is the filter that allows everything)"); return PCR_ERR_ARG; }
+    return PCR_OK;
+}
+
+int pcr_recommend_capped_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
+                                     const int32_t* item, int64_t n, const int32_t* users, int topk, int pool, const int32_t* group, int cap,
+                                     int dtype, const pcr_item_filter* f, const int32_t* items, const double* scores, bool* sorted) {
+    static const char* who = "pcr_recommend_capped_model";
+    int rc = pcr_cap_check(who, topk, pool, group, cap);
+    if (rc == PCR_OK) rc = pcr_recommend_model_check(U, d1, V, d2, k, index, item, n, users, pool, dtype, items, scores, sorted, who);
+    return rc != PCR_OK ? rc : pcr_cap_filter_check(who, f);
+}
+
+void pcr_cap_stats_from(int64_t n, int topk, const uint8_t* status, const int32_t* items, pcr_cap_stats* stats) {
+    pcr_cap_stats t = {n, 0, 0, 0, 0};
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t* row = items + i * topk;
+        int len = 0;
+        while (len < topk && row[len] >= 0) ++len;
+        (status[i] == PCR_CAP_EXACT ? t.exact : t.exhausted) += 1;
+        t.short_rows += len < topk ? 1 : 0;
+        t.kept += len;
+    }
+    *stats = t;
+}
+
 int pcr_exposure_stats(const int64_t* exposure, int64_t d2, int64_t* recs, int64_t* items_covered, double* coverage, double* gini) {
     if (!exposure || d2 < 1) { pcr_set_error("pcr_exposure_stats: bad argument"); return PCR_ERR_ARG; }
     std::vector<int64_t> x(exposure, exposure + d2);

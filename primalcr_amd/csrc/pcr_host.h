@@ -129,6 +129,18 @@ int pcr_rerank_check(const char* who, int topk, int pool, double theta);
 int pcr_recommend_diverse_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
                                       const int32_t* item, int64_t n, const int32_t* users, int topk, int pool, double theta, int dtype,
                                       const int32_t* items, const double* scores, bool* sorted);
+// Group-capped lists (include/primalcr.h, "group-capped top-K lists").
+// pcr_recommend_capped's own arguments (both entries): group != NULL, cap >= 1, 1 <= topk <= pool <= PCR_RECOMMEND_MAX_K
+int pcr_cap_check(const char* who, int topk, int pool, const int32_t* group, int cap);
+// its filter (NULL: none): candidate rows are PCR_ERR_UNSUPPORTED, a filter with nothing in it is PCR_ERR_ARG
+int pcr_cap_filter_check(const char* who, const pcr_item_filter* f);
+// pcr_recommend_capped_model's argument checks (shared with the sanitizer build's stub): pcr_cap_check, the factor / user /
+// exclusion / output checks of pcr_recommend_model with K = pool, then pcr_cap_filter_check.  *sorted as pcr_recommend_model_check.
+int pcr_recommend_capped_model_check(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index,
+                                     const int32_t* item, int64_t n, const int32_t* users, int topk, int pool, const int32_t* group, int cap,
+                                     int dtype, const pcr_item_filter* f, const int32_t* items, const double* scores, bool* sorted);
+// stats from the finished rows: status[n] and items[n][topk] (padding -1 only at a row's end)
+void pcr_cap_stats_from(int64_t n, int topk, const uint8_t* status, const int32_t* items, pcr_cap_stats* stats);
 // stats[c] from the reduced sums (k_topn_fin's layout: [ncut][8] = sum len, sum novelty, -, users with len >= 1, -, -, sum ild,
 // users_ild; then the requested users) and the cumulative exposure rows expo[ncut][d2] (exact integers in fp64); exposure
 // (may be NULL) receives them as int64.  pcr_exposure_stats' return code.

@@ -1,5 +1,6 @@
 // pcr_serve.hip -- the serving layer behind the C ABI of include/primalcr.h: top-K recommendation, its top-N, rank and
-// beyond-accuracy evaluations, the MMR re-ranking and the metrics of given and re-ranked lists, over the kernels of pcr_topk.h.
+// beyond-accuracy evaluations, the MMR re-ranking, the group cap and the metrics of given and re-ranked lists, over the kernels of
+// pcr_topk.h.
 //
 // Every entry exists twice: on a trained solver (pcr_recommend, ...) and on a model in host memory (pcr_recommend_model, ...).
 // Both come down to a ServeView (pcr_dev.h) -- filled by the solver (pcr_solver::serve_view) or by ModelDev, which uploads the
@@ -410,6 +411,51 @@ static int rerank_run(const ServeView& v, int64_t n, const int32_t* h_users, int
         HIPCHK(hipGetLastError());
     }
     return rec_run<T>(v, n, h_users, pool, 1, RecRerank<T>{v, pool, topk, theta, inv.p, shape, items, scores});
+}
+
+// rec_run's sink for the group cap: merge + selection (k_rec_merge_cap) of topk from the pool of K, to the host arrays items /
+// scores (n x topk) and status (n)
+template <typename T>
+struct RecCap {
+    const ServeView& v;
+    int K, topk, cap;
+    const int32_t* group;         // device, [d2]
+    int32_t* items;
+    double* scores;
+    uint8_t* status;
+    DBuf<int32_t> oi;
+    DBuf<double> os;
+    DBuf<unsigned char> ost;
+    int begin(int64_t nb) {
+        RC(oi.alloc((size_t)nb * topk)); RC(os.alloc((size_t)nb * topk)); RC(ost.alloc((size_t)nb));
+        HIPCHK(hipFuncSetAttribute((const void*)k_rec_merge_cap<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(cap_wave_lds<T>(K) * 4)));
+        return PCR_OK;
+    }
+    int batch(int64_t b0, int64_t m, const T* ls, const int32_t* li, const int32_t* ln, int nsp) {
+        hipStream_t st = v.st;
+        {
+            ProfScope ps(v.prof, "recommend/cap", st);
+            hipLaunchKernelGGL((k_rec_merge_cap<T>), dim3((unsigned)cdiv(m, 4)), dim3(256), cap_wave_lds<T>(K) * 4, st, ls, li, ln, nsp, m, K, group,
+                               cap, topk, oi.p, os.p, ost.p);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(items + b0 * topk, oi.p, (size_t)m * topk * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(scores + b0 * topk, os.p, (size_t)m * topk * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(status + b0, ost.p, (size_t)m, hipMemcpyDeviceToHost, st));
+        return PCR_OK;
+    }
+};
+
+// The group-capped lists of the n users h_users (rows of U and of the exclusion CSR, as rec_run; NULL: rows 0..n-1): group[d2]
+// goes to the device once per call, then the sweep with K = pool and RecCap.  "recommend/cap" times the merge with the selection
+// fused in.  status is never NULL here (serve_recommend_capped brings its own when the caller has none).
+template <typename T>
+static int cap_run(const ServeView& v, int64_t n, const int32_t* h_users, int topk, int pool, const int32_t* group, int cap, int32_t* items,
+                   double* scores, uint8_t* status) {
+    if (n <= 0) return PCR_OK;
+    DBuf<int32_t> dg;
+    RC(dg.upload_n(group, (size_t)v.d2));
+    return rec_run<T>(v, n, h_users, pool, 1, RecCap<T>{v, pool, topk, cap, dg.p, items, scores, status});
 }
 
 // Metrics of device-resident lists (pcr_evaluate_lists_model, pcr_evaluate_rerank; k_list_metrics of pcr_topk.h, DESIGN.md
@@ -840,6 +886,20 @@ static int serve_recommend_diverse(const ServeView& v, int64_t n, const int32_t*
                                    double* scores) {
     return by_precision(v, [&](auto zero) -> int { return rerank_run<decltype(zero)>(v, n, rows, topk, pool, theta, items, scores); });
 }
+// group-capped lists (pcr_recommend_capped): an allow set rides on the view as in
+// serve_recommend_filtered; per user, nothing is exchanged; the summary is counted on the host from the finished rows
+static int serve_recommend_capped(ServeView v, int64_t n, const int32_t* rows, int topk, int pool, const int32_t* group, int cap,
+                                  const pcr_item_filter* f, int32_t* items, double* scores, uint8_t* status, pcr_cap_stats* stats) {
+    std::vector<uint8_t> own;
+    if (!status) { own.resize((size_t)std::max<int64_t>(n, 0)); status = own.data(); }
+    if (n > 0) {
+        DBuf<unsigned long long> aw;
+        if (f) RC(pack_allow(v, *f, aw));
+        RC(by_precision(v, [&](auto zero) -> int { return cap_run<decltype(zero)>(v, n, rows, topk, pool, group, cap, items, scores, status); }));
+    }
+    if (stats) pcr_cap_stats_from(std::max<int64_t>(n, 0), topk, status, items, stats);
+    return PCR_OK;
+}
 // full-catalogue top-N evaluation of v's rows against their test ratings; the relevance tables are built on the first call for a
 // (threshold, cutoffs) and kept in D
 static int serve_topn(const ServeView& v, TopnDev& D, int ncut, const int* cuts, double thr, pcr_topn_stats* stats, double* per_user) {
@@ -1036,6 +1096,34 @@ int pcr_recommend_diverse(pcr_solver* s, int64_t n, const int32_t* users, int to
         std::vector<int32_t> loc;
         RC(shard_rows("pcr_recommend_diverse", s, &n, users, loc));
         return serve_recommend_diverse(solver_view(s, flags), n, users ? loc.data() : nullptr, topk, pool, theta, items, scores);
+    });
+}
+
+int pcr_recommend_capped(pcr_solver* s, int64_t n, const int32_t* users, int topk, int pool, const int32_t* group, int cap, int flags,
+                         const pcr_item_filter* f, int32_t* items, double* scores, uint8_t* status, pcr_cap_stats* stats) {
+    S_OR_ARG;
+    RC(pcr_cap_check("pcr_recommend_capped", topk, pool, group, cap));
+    if (flags & ~PCR_REC_EXCLUDE_TRAIN) { pcr_set_error("pcr_recommend_capped: unknown flags"); return PCR_ERR_ARG; }
+    if (!users) n = s->n_users;
+    if (n < 0 || (n > 0 && (!items || !scores))) { pcr_set_error("pcr_recommend_capped: bad argument"); return PCR_ERR_ARG; }
+    RC(pcr_cap_filter_check("pcr_recommend_capped", f));
+    return abi_guard("pcr_recommend_capped", [&]() -> int {
+        std::vector<int32_t> loc;
+        RC(shard_rows("pcr_recommend_capped", s, &n, users, loc));
+        return serve_recommend_capped(solver_view(s, flags), n, users ? loc.data() : nullptr, topk, pool, group, cap, f, items, scores, status, stats);
+    });
+}
+
+int pcr_recommend_capped_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                               int64_t n, const int32_t* users, int topk, int pool, const int32_t* group, int cap, int dtype,
+                               const pcr_item_filter* f, int32_t* items, double* scores, uint8_t* status, pcr_cap_stats* stats, int device) {
+    return abi_guard("pcr_recommend_capped_model", [&]() -> int {
+    bool sorted = true;
+    RC(pcr_recommend_capped_model_check(U, d1, V, d2, k, index, item, n, users, topk, pool, group, cap, dtype, f, items, scores, &sorted));
+    RC(model_device(device));
+    ServeView v; ModelDev M;
+    if (n > 0) RC(M.open(U, d1, V, d2, k, index, item, sorted, dtype, &v));
+    return serve_recommend_capped(v, n, users, topk, pool, group, cap, f, items, scores, status, stats);
     });
 }
 

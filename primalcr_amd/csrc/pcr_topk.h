@@ -28,6 +28,8 @@
 //   (pcr_recommend_diverse, section 3.14) fused into its tail, further down in this file.
 // k_list_metrics: the two metric tails over a list that is already in device memory (pcr_evaluate_lists_model, and the theta sweep
 //   pcr_evaluate_rerank, which runs it on k_rec_merge_mmr's output; section 3.15), below k_rec_merge_div.
+// k_rec_merge_cap: the same merge with the group cap ("at most q items of one group", pcr_recommend_capped, section 3.23) fused
+//   into its tail, at the end of this file.
 // No atomic decides a result: the LDS slot counter only decides where a candidate sits in the buffer, and the merges rank by
 // the total order (score, id), so every list is the same whatever the order of arrival.
 #pragma once
@@ -1227,4 +1229,63 @@ __global__ __launch_bounds__(256) void k_rec_merge_mmr(const T* __restrict__ lst
         }
         wave_sync();
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Group-capped top-K (pcr_recommend_capped, include/primalcr.h): the first topk entries of the merged
+// pool of K = pool entries that are kept by the rule "at most cap entries of one group"; group[j] < 0: item j is never capped.
+
+// LDS of one wave of k_rec_merge_cap: the pool's scores [K], ids [K] and group ids [K]
+template <typename T>
+__host__ __device__ inline size_t cap_wave_lds(int K) {
+    const size_t b = (size_t)K * (sizeof(T) + 2 * sizeof(int));
+    return (b + 15) & ~(size_t)15;
+}
+
+// k_rec_merge with the selection fused into its tail, one wave per user, four users per workgroup: the merged pool goes to the
+// wave's LDS (ids, scores) with group[j_i] next to it.  The wave then walks the pool 64 positions at a time: lane p counts the
+// earlier positions e < p with its group id -- broadcast LDS reads over e = 0 .. the chunk's last position, the same trip count
+// for every lane, a lane adding only while its count is below cap -- and keeps its entry when the count stays below cap (or its
+// group id is negative).  A ballot and the popcount of the lanes below give every kept entry its output slot behind the kept
+// entries of the chunks before, a wave-uniform number; the walk ends as soon as that number reaches topk.  The scores are copied
+// (converted to double), nothing is computed from them: a row depends on its pool, group[] and cap alone.
+// status[idx] (NULL: not written): PCR_CAP_EXACT when the row holds topk items or the pool is shorter than K (it is the user's
+// whole eligible catalogue), PCR_CAP_POOL_EXHAUSTED otherwise.
+template <typename T>
+__global__ __launch_bounds__(256) void k_rec_merge_cap(const T* __restrict__ lst_s, const int32_t* __restrict__ lst_i,
+                                                       const int32_t* __restrict__ lst_n, int nsplit, int64_t n, int K,
+                                                       const int32_t* __restrict__ group, int cap, int topk,
+                                                       int32_t* __restrict__ out_i, double* __restrict__ out_s,
+                                                       unsigned char* __restrict__ out_st) {
+    extern __shared__ __align__(16) char rec_lds[];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + w;
+    if (idx >= n) return;                               // (the whole wave)
+    char* wl = rec_lds + (size_t)w * cap_wave_lds<T>(K);
+    T* ss = (T*)wl;
+    int* si = (int*)(ss + K);
+    int* sg = si + K;
+    const int tot = rec_merge_ranks(lst_s, lst_i, lst_n, nsplit, n, K, idx, lane, [&](int rk, int j, T s) {
+        si[rk] = j; ss[rk] = s; sg[rk] = group[j];
+    });
+    const int L = __builtin_amdgcn_readfirstlane(min(tot, K));      // the pool is [0, L): no padding inside
+    int32_t* oi = out_i + (size_t)idx * topk;
+    double* os = out_s + (size_t)idx * topk;
+    wave_sync();
+    int kept = 0;                                                    // (wave-uniform)
+    for (int c0 = 0; c0 < L && kept < topk; c0 += 64) {
+        const int p = c0 + lane;
+        const int g = p < L ? sg[p] : -1;
+        const int ce = min(L, c0 + 64) - 1;                          // positions before the chunk's last one
+        int cnt = 0;
+        for (int e = 0; e < ce; ++e) cnt += (e < p && cnt < cap && sg[e] == g) ? 1 : 0;
+        const bool keep = p < L && (g < 0 || cnt < cap);
+        const unsigned long long km = __ballot(keep);
+        const int slot = kept + __popcll(km & ((1ull << lane) - 1ull));
+        if (keep && slot < topk) { oi[slot] = si[p]; os[slot] = (double)ss[p]; }
+        kept += __popcll(km);
+    }
+    kept = min(kept, topk);
+    for (int p = kept + lane; p < topk; p += 64) { oi[p] = -1; os[p] = -INFINITY; }
+    if (out_st && lane == 0) out_st[idx] = (kept == topk || L < K) ? PCR_CAP_EXACT : PCR_CAP_POOL_EXHAUSTED;
 }

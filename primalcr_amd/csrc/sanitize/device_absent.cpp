@@ -123,6 +123,14 @@ int pcr_recommend_diverse_model(const double* U, int64_t d1, const double* V, in
     return rc != PCR_OK ? rc : absent();
 }
 NO_SOLVER(pcr_recommend_diverse, pcr_solver*, int64_t, const int32_t*, int, int, double, int, int32_t*, double*)
+int pcr_recommend_capped_model(const double* U, int64_t d1, const double* V, int64_t d2, int64_t k, const int64_t* index, const int32_t* item,
+                               int64_t n, const int32_t* users, int topk, int pool, const int32_t* group, int cap, int dtype,
+                               const pcr_item_filter* f, int32_t* items, double* scores, uint8_t*, pcr_cap_stats*, int) {
+    const int rc = pcr_recommend_capped_model_check(U, d1, V, d2, k, index, item, n, users, topk, pool, group, cap, dtype, f, items, scores, nullptr);
+    return rc != PCR_OK ? rc : absent();
+}
+NO_SOLVER(pcr_recommend_capped, pcr_solver*, int64_t, const int32_t*, int, int, const int32_t*, int, int, const pcr_item_filter*, int32_t*, double*,
+          uint8_t*, pcr_cap_stats*)
 int pcr_evaluate_lists_model(const double* V, int64_t d2, int64_t k, int64_t d1, const int64_t* index, const int32_t* item, const int64_t* tindex,
                              const int32_t* titem, const double* tval, int64_t n, const int32_t* users, int L, const int32_t* lists, int ncut,
                              const int* cutoffs, double threshold, int dtype, pcr_topn_stats* topn, double* per_user_topn,
