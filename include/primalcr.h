@@ -1139,6 +1139,92 @@ int pcr_fold_in_items(pcr_solver *s, const pcr_dataset *train, int64_t n, const 
                       const double *val, const double *V0, int steps, double *V_out,
                       pcr_itemfold_stats *stats, double *per_item);                                 /* [device] */
 
+/* ------------------------------------------------------------------------- */
+/* explaining recommendations: a score decomposed over the user's own rated   */
+/* items (no reference counterpart)                                           */
+/* ------------------------------------------------------------------------- */
+/* A user's row u is trained to a stationary point of f(u) = lambda_u/2 |u|^2 + sum over the user's comparable pairs of hinge^2.
+ * With I the user's training row, the gradient is g = lambda_u u + sum_{p in I} c_p v_{i_p}, c_p the sweep coefficients of
+ * obtain_g_u_new (pcrpp.cpp:493-539) that the training and fold-in kernels build.  So for ANY item j
+ *     s(u, j) = v_j . u = sum_{p in I} e_p(j) + rho(j),    e_p(j) = -(c_p / lambda_u) (v_{i_p} . v_j),    rho(j) = (v_j . g) / lambda_u
+ * one signed contribution per rated item ("because you rated X") and a residual that is zero at a converged row and reports
+ * honestly how far from stationarity the row is.  Nothing is approximated.  One workgroup explains one user (k_explain,
+ * pcr_explain.h): the state at u, then the listed items in tiles of 16 against the user's rows of V in chunks of 256 ratings.
+ *   Inputs             index[n + 1] / item / val: the n users' training rows, as pcr_fold_in_model's.  Rows need not be
+ *                      item-ascending (a sorted copy is made, equal items keeping their order; "position" below is the position
+ *                      in that sorted row); the same item twice in a row is two ratings.  Levels as in training: lround buckets
+ *                      for PrimalCR++, the raw double for PrimalCR, with inclusive resp. strict windows.  U [n][k]: row i is
+ *                      rounded to the storage type (p->precision), as training stores it.  lists [n][L]: 0-based item ids, the
+ *                      non-padding entries first, then -1 padding; an id may sit in the user's training row (a known item can
+ *                      be explained) and may occur twice (the two positions are independent).  1 <= L <= PCR_EXPLAIN_MAX_L,
+ *                      1 <= E <= PCR_EXPLAIN_MAX_E.  weights (NULL: 1) [n]: c_u > 0 and finite; the user is explained at
+ *                      lambda_u = lambda / c_u, divided once in fp64 on the host -- the rule of pcr_solver_set_user_weights.
+ *                      lambda must be finite and > 0 (the decomposition divides by it).
+ *   Arithmetic         m = V_I u is formed in the storage type by the kernel primitive pcr_fold_in_model uses: the bits its state
+ *                      has for the same row.  Everything after that is fp64: c_p from the sorted m, NOT rounded to the storage
+ *                      type; g = lambda_u u + sum c_p v_p; the dots v_{i_p} . v_j, v_j . u and v_j . g over the factors as the
+ *                      storage type holds them, widened.  The order of the k-term and n-term sums is fixed but not part of the
+ *                      contract; each e_p is good to about (k + 2) 2^-52 sum_t |v_pt v_jt| |c_p| / lambda_u, and the identity
+ *                      below to that bound summed over p plus the same for rho and score.  Against another implementation
+ *                      c_p also inherits the rounding of m: |dc_p| <= 2 n dm, dm the error of a k-term dot in the storage type.
+ *   per_pair           (optional) [n][L][PCR_EXPLAIN_PAIR_FIELDS] = score, support, opposition, residual.  score = v_j . u in
+ *                      fp64: the decomposed quantity, NOT the f32 chain of pcr_recommend's scores (they agree to f32 rounding).
+ *                      support = sum of the e_p > 0, opposition = sum of the e_p < 0, both added in ascending position;
+ *                      residual = rho(j).  score = support + opposition + residual to the bound above.  A padding position
+ *                      holds NaN in all four fields.
+ *   Contributors       expl_item / expl_contrib [n][L][E]: the user's ratings by DESCENDING e_p, equal e_p by ascending position;
+ *                      each entry is the rated item's id and its e_p.  Entries with e_p <= 0 are listed like any other: the
+ *                      caller cuts at the sign.  The SIGN OF A ZERO contribution is unspecified: a coefficient that is exactly 0
+ *                      gives +0 or -0 by the sign of the dot beside it (the two compare equal in the order).  A user with fewer than E ratings ends the row with (-1, 0.0); a padding list
+ *                      position holds (-1, 0.0) throughout.
+ *   per_user           (optional) [n][PCR_EXPLAIN_USER_FIELDS] = the rating count, loss (the hinge part of the objective at u,
+ *                      unweighted) and gnorm2 = |g|^2 of this entry's fp64 g.  A user without ratings has g = lambda_u u:
+ *                      support = opposition = 0, residual = score to rounding, every contributor padding.
+ *   stats              (optional) users = n, pairs = the non-padding list positions, contributors = the non-padding contributor
+ *                      entries, residual_abs_max = the largest |residual| of a non-padding position (0 without one).
+ *   Determinism        a user's output depends on its row, u, V, its list and the parameters alone -- not on the other users,
+ *                      its position, batches or the launch grid; its workgroup form on the length of its row alone.  No atomics
+ *                      touch results, nothing is handed between workgroups, there is no spin-wait, every loop has a static
+ *                      bound and every sum a fixed order: two identical calls are bitwise identical.
+ *   Forms              by the user's length, as pcr_fold_in's: one wave up to PCR_FOLDIN_WAVE_MAX ratings; 256 threads with the
+ *                      per-rating arrays in LDS up to PCR_FOLDIN_LDS_MAX; 512 threads with them in a per-workgroup slice of
+ *                      global scratch beyond.
+ *   Errors             PCR_ERR_ARG before any device is looked for, the message naming the entry, in this order: null
+ *                      parameters, a null V, k < 1, an unknown precision, a lambda that is not finite or <= 0; then everything
+ *                      pcr_fold_in_model refuses of the rows (a solver type other than 0, 1, 2, n < 0, d2 < 1, a null index,
+ *                      index[0] != 0, a non-monotone index, null item / val, an item id outside [0, d2), a rating that is not
+ *                      finite); a null U, lists, expl_item or expl_contrib; L or E out of range; a list id outside [0, d2) that
+ *                      is not -1; a non-padding id after a -1; a weight that is not finite or <= 0.  Solver type 0 is
+ *                      PCR_ERR_UNSUPPORTED (a squared-loss row decomposes through its residuals: another entry), as is whatever
+ *                      the level builder refuses.  A rank whose vectors, tile and the per-rating arrays of the form's LARGEST
+ *                      user do not fit a workgroup's 160 KiB of LDS is PCR_ERR_UNSUPPORTED, reported when the call reaches the
+ *                      form -- a function of the rank, the storage type and the form alone.  Without a device: PCR_ERR_DEVICE. */
+#define PCR_EXPLAIN_MAX_L 128      /* listed items per user */
+#define PCR_EXPLAIN_MAX_E 16       /* contributors reported per listed item */
+#define PCR_EXPLAIN_PAIR_FIELDS 4  /* score, support, opposition, residual */
+#define PCR_EXPLAIN_USER_FIELDS 3  /* ratings, loss, gnorm2 */
+typedef struct pcr_explain_stats {
+    int64_t users, pairs, contributors;
+    double  residual_abs_max;
+} pcr_explain_stats;
+/* Standalone: V (d2 x k) and the users' rows U (n x k) host fp64 in model-file layout; k, lambda, solver_type, precision and
+ * device are read from p. */
+int pcr_explain_model(const pcr_params *p, const double *V, int64_t d2, int64_t n,
+                      const int64_t *index, const int32_t *item, const double *val,
+                      const double *U, const double *weights, int L, const int32_t *lists, int E,
+                      int32_t *expl_item, double *expl_contrib, double *per_pair, double *per_user,
+                      pcr_explain_stats *stats);                                                   /* [device] */
+/* On a live PCR or PCR++ solver: its device U and V, storage type, lambda, solver type and stream.  users[n] are GLOBAL ids of the
+ * shard (NULL: all of them in order; n is then ignored and taken as the shard's n_users.  Ids outside it: PCR_ERR_ARG).  train must be the data set the solver was
+ * created from (its dimensions and nnz are checked, as pcr_fold_in_items does): it supplies the rows and their rating values.
+ * A CCDR1 solver, a multi-rank solver or one from pcr_solver_create_shard is PCR_ERR_STATE.  weights [n] is the caller's: the
+ * entry does not read the solver's own.  Nothing of the solver is written: training that continues afterwards gives bitwise the
+ * same factors.  Profile slot: explain/contrib. */
+int pcr_explain(pcr_solver *s, const pcr_dataset *train, int64_t n, const int32_t *users,
+                const double *weights, int L, const int32_t *lists, int E,
+                int32_t *expl_item, double *expl_contrib, double *per_pair, double *per_user,
+                pcr_explain_stats *stats);                                                         /* [device] */
+
 /* per-kernel device timing (HIP events on the solver's stream, one pair per launch).
  * slot names: "<class>/<workgroup size>[.<length bound>][g][c][l][r][#n]" for the per-user kernels (classes
  * prepare, vgrad, vhv, ustep; g = global-scratch variant, c = workgroup clusters, l = k_ustep's latency form (8 rows

@@ -38,6 +38,12 @@ PCR_NNLS_FIELDS = ("n", "form", "pivots", "zeros", "loss", "obj", "status")     
 PCR_NNLS_DIRECT, PCR_NNLS_CG = 0, 1                                               # ... its forms
 PCR_NNLS_OK, PCR_NNLS_SINGULAR, PCR_NNLS_CAP = 0, 1, 2                            # ... its status values
 PCR_NNLS_PIVOT_CAP = 64                                                           # ... and the pivots a user may take
+# explain(): the list length and the contributors per listed item it takes at most, its per_pair / per_user columns, and the
+# listed items per tile / ratings per chunk of its kernel (include/primalcr.h, pcr_explain.h)
+PCR_EXPLAIN_MAX_L, PCR_EXPLAIN_MAX_E = 128, 16
+PCR_EXPLAIN_PAIR_FIELDS = ("score", "support", "opposition", "residual")
+PCR_EXPLAIN_USER_FIELDS = ("ratings", "loss", "gnorm2")
+EXPLAIN_TILE, EXPLAIN_CHUNK = 16, 256
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -146,6 +152,11 @@ class NnlsStats(C.Structure):
     """pcr_nnls_stats."""
     _fields_ = [("users", C.c_int64), ("direct", C.c_int64), ("cg", C.c_int64), ("singular", C.c_int64), ("cap", C.c_int64),
                 ("pivots", C.c_int64), ("zeros", C.c_int64), ("loss", C.c_double), ("obj", C.c_double)]
+
+
+class ExplainStats(C.Structure):
+    """pcr_explain_stats."""
+    _fields_ = [("users", C.c_int64), ("pairs", C.c_int64), ("contributors", C.c_int64), ("residual_abs_max", C.c_double)]
 
 
 _LOG_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p)
@@ -260,6 +271,9 @@ def lib():
     if _LIB_OVERRIDE is None or hasattr(L, "pcr_fold_in_items"):
         L.pcr_fold_in_items_model.argtypes = [C.POINTER(Parameter), vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, ci, vp, vp, vp]
         L.pcr_fold_in_items.argtypes = [vp, vp, i64, vp, vp, vp, vp, ci, vp, vp, vp]
+    if _LIB_OVERRIDE is None or hasattr(L, "pcr_explain"):
+        L.pcr_explain_model.argtypes = [C.POINTER(Parameter), vp, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp]
+        L.pcr_explain.argtypes = [vp, vp, i64, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp]
     L.pcr_exposure_stats.argtypes = [vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(cd), C.POINTER(cd)]
     L.pcr_profile_enable.argtypes = [vp, ci]
     L.pcr_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(cd), C.POINTER(i64)]
@@ -876,6 +890,59 @@ def recommend_new_users(V, ratings, lam, topk, solver_type=PCR_SOLVER_PCRPP, U0=
     return items, scores, U_new, stats
 
 
+def explain_boundaries():
+    """The row lengths R at which explain() changes its code path between R and R + 1 ratings -- the bounds of its workgroup forms
+    (fold_in()'s) and the first multiples of its rating chunk -- and the list lengths at which it starts another tile: a dict
+    with "rows" and "lists"."""
+    rows = sorted({PCR_FOLDIN_WAVE_MAX, EXPLAIN_CHUNK, PCR_FOLDIN_LDS_MAX})
+    return {"rows": rows, "lists": [EXPLAIN_TILE * t for t in range(1, PCR_EXPLAIN_MAX_L // EXPLAIN_TILE + 1)]}
+
+
+def _explain_call(n, lists, top, weights, per_pair, per_user, fn):
+    """Shared by explain() and Solver.explain(): the list / weight / output buffers around fn(weights pointer, L, lists pointer, E,
+    expl_item, expl_contrib, per_pair, per_user, stats pointers); returns (items int32 [n, L, E], contrib float64 [n, L, E], stats
+    dict[, per_pair float64 [n, L, 4]][, per_user float64 [n, 3]])."""
+    lists = np.ascontiguousarray(lists, np.int32)
+    if lists.ndim != 2 or lists.shape[0] != n:
+        raise ValueError(f"lists must be [n, L] with n = {n}")
+    L, E = int(lists.shape[1]), int(top)
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, np.float64)
+        if weights.shape != (n,):
+            raise ValueError(f"weights must hold {n} values")
+    Lb, Eb = max(L, 1), min(max(E, 1), 1024)
+    items = np.empty((n, Lb, Eb), np.int32); contrib = np.empty((n, Lb, Eb), np.float64)
+    pp = np.empty((n, Lb, len(PCR_EXPLAIN_PAIR_FIELDS)), np.float64) if per_pair else None
+    pu = np.empty((n, len(PCR_EXPLAIN_USER_FIELDS)), np.float64) if per_user else None
+    st = ExplainStats()
+    _chk(fn(None if weights is None else weights.ctypes.data, L, lists.ctypes.data, E, items.ctypes.data, contrib.ctypes.data,
+            None if pp is None else pp.ctypes.data, None if pu is None else pu.ctypes.data, C.addressof(st)))
+    out = (items, contrib, {f: getattr(st, f) for f, _ in ExplainStats._fields_})
+    return out + ((pp,) if per_pair else ()) + ((pu,) if per_user else ())
+
+
+def explain(V, ratings, U, lists, lam, top=5, solver_type=PCR_SOLVER_PCRPP, weights=None, dtype=PCR_F64, device=0, per_pair=False,
+            per_user=False):
+    """Why each listed item scores as it does for a user, on the GPU (pcr_explain_model): the score v_j . u split exactly into one
+    signed contribution e_p(j) per item of the user's training row plus a residual that vanishes at a converged row.
+    ratings: the users' training rows, a Dataset or an (index, item, val) tuple over V's items; U [n, k] their rows; lists [n, L]
+    item ids with -1 padding at the end; top: the contributors reported per listed item, by descending contribution (entries
+    <= 0 included: cut at the sign); weights [n]: per-user loss weights c_u (the user is explained at lam / c_u).
+    Returns (items int32 [n, L, top] of rated item ids (-1: no more ratings), contrib float64 [n, L, top], stats dict
+    [, per_pair float64 [n, L, 4] of PCR_EXPLAIN_PAIR_FIELDS, NaN on padding][, per_user float64 [n, 3] of PCR_EXPLAIN_USER_FIELDS])."""
+    V = np.ascontiguousarray(V, np.float64); U = np.ascontiguousarray(U, np.float64)
+    if V.ndim != 2 or U.ndim != 2 or U.shape[1] != V.shape[1]:
+        raise ValueError("V must be [d2, k] and U [n, k]")
+    index, item, val = _foldin_ratings(ratings)
+    n, k = index.shape[0] - 1, V.shape[1]
+    if U.shape[0] != n:
+        raise ValueError(f"U must hold one row per user of ratings ({n})")
+    p = Parameter(solver_type=int(solver_type), k=k, precision=int(dtype), device=int(device), **{"lambda": float(lam)})
+    return _explain_call(n, lists, top, weights, per_pair, per_user, lambda wp, L, lp, E, ip, cp, pp, up, sp: lib().pcr_explain_model(
+        C.byref(p), V.ctypes.data, V.shape[0], n, index.ctypes.data, item.ctypes.data, val.ctypes.data, U.ctypes.data, wp, L, lp, E, ip, cp, pp, up,
+        sp))
+
+
 def itemfold_boundaries(k=None, dtype=PCR_F64):
     """The rater counts R at which fold_in_items() changes its code path between R and R + 1 raters: the bounds of its workgroup
     forms (the same for every rank and storage type)."""
@@ -1228,12 +1295,14 @@ class Solver:
         fn = lib().pcr_solver_set_user_weights_local if local else lib().pcr_solver_set_user_weights
         if w is None:
             _chk(fn(self._h, None))
+            self.user_weights = None
             return
         w = np.ascontiguousarray(w, np.float64)
         want = self.n_users if local else self.d1
         if w.shape != (want,):
             raise ValueError(f"w must hold {want} weights")
         _chk(fn(self._h, w.ctypes.data))
+        self.user_weights = w.copy()                        # (Solver.explain's default; the library's entry reads the caller's)
 
     def get_factors_local(self):
         U = np.zeros((self.n_users, self.k)); V = np.zeros((self.d2, self.k))
@@ -1456,6 +1525,26 @@ class Solver:
         n = index.shape[0] - 1
         return _itemfold_call(n, self.k, V0, per_item, lambda v0, vo, sp, pp: lib().pcr_fold_in_items(
             self._h, ds._h, n, index.ctypes.data, user.ctypes.data, val.ctypes.data, v0, int(steps), vo, sp, pp))
+
+    def explain(self, lists, users=None, train=None, top=5, weights=None, per_pair=False, per_user=False):
+        """Why each listed item scores as it does for this solver's users, from its device U and V (pcr_explain), in its storage
+        type and with its lambda and solver type; lists, top and the result as explain().  users: GLOBAL 0-based ids (None: all
+        of them, in order).  train (None: the Dataset the solver was created from) supplies the rows and their rating values and
+        must be that data set.  weights [n]: None takes the weights last given to set_user_weights(w) for these users -- remembered here
+        in Python, the library's entry never reads the solver's own; weights given with local=True (fewer than d1 of them) are NOT
+        taken, nor is anything after set_user_weights(None): the call then runs unweighted, so pass weights explicitly there.  Needs
+        every user on the rank (a shard solver: PcrError); nothing of the solver is written."""
+        ds = self.ds if train is None else train
+        if not isinstance(ds, Dataset):
+            raise ValueError("train must be a Dataset (the one the solver was created from)")
+        if users is not None:
+            users = np.ascontiguousarray(users, np.int32)
+        n = self.n_users if users is None else users.shape[0]
+        mine = getattr(self, "user_weights", None)
+        if weights is None and mine is not None and mine.shape[0] == self.d1:
+            weights = mine if users is None else mine[users]
+        return _explain_call(n, lists, top, weights, per_pair, per_user, lambda wp, L, lp, E, ip, cp, pp, up, sp: lib().pcr_explain(
+            self._h, ds._h, n, None if users is None else users.ctypes.data, wp, L, lp, E, ip, cp, pp, up, sp))
 
     def fold_in_ridge(self, ratings, weighted=True, per_user=False):
         """Squared-loss factors for users this solver was not trained on, against its device V (pcr_fold_in_ridge), in its storage

@@ -81,6 +81,15 @@
 //                    list; stdout gets one line "capped users n exact n pool_exhausted n short n kept n".  The two flags go
 //                    together and with --allow; not together with --candidates, --eval, --diversity, --mmr, --tradeoff, --ranks
 //                    or any --fold-in*
+//   omp-pmf-recommend --explain file [--top E] -x data_dir -l lambda [-s 1|2] [--allow items_file] [-K topk] [-u users_file] [--f32] [--scores] model_file output_file
+//     --explain file why every listed item scores as it does (pcr_explain_model): after the lists are written, `file` gets one line
+//                    per requested user and list position, "user item score support opposition residual  it1:c1 it2:c2 ...": the
+//                    1-based ids, score = v . u split exactly into the contributions c of the user's own rated items it (the
+//                    --top E largest, default 5, at most PCR_EXPLAIN_MAX_E; support / opposition: the sums of all positive /
+//                    negative ones) and a residual that is 0 at a converged row; numbers in %g, padding left out.  Needs -x (the
+//                    training ratings the model was trained on), -l (its regulariser) and -K <= PCR_EXPLAIN_MAX_L; -s as
+//                    --fold-in's.  Goes with the plain list (and --allow) only: refused with --eval, --diversity, --mmr,
+//                    --tradeoff, --ranks, any --fold-in*, --groups and --candidates
 // Output: one line per user, in input order: the 1-based user id, then the 1-based item ids (padding is left out).  Users go
 // to the device in batches, so host memory for the lists stays bounded on any catalogue.
 // With --eval: stdout gets one line per cutoff, "cutoff c users n users_graded n hits n precision x recall x hit_rate x map x
@@ -168,7 +177,13 @@ static const char* USAGE =
     "    --max-per-group q  at most q items of one group in a list: the -K items are the first of the user's P best (--pool, default\n"
     "                   min(1024, 10 topk)) that the rule keeps; output as the plain list; stdout gets a \"capped users n exact n\n"
     "                   pool_exhausted n short n kept n\" line; both flags go together and with --allow, not with --candidates,\n"
-    "                   --eval, --diversity, --mmr, --tradeoff, --ranks or --fold-in*\n";
+    "                   --eval, --diversity, --mmr, --tradeoff, --ranks or --fold-in*\n"
+    "       omp-pmf-recommend --explain file [--top E] -x data_dir -l lambda [-s 1|2] [--allow items_file] [-K topk] [-u users_file] [--f32] [--scores] model_file output_file\n"
+    "    --explain file after the lists: one line per user and list position to `file`, \"user item score support opposition residual\n"
+    "                   it1:c1 it2:c2 ...\": the score split into the contributions of the user's own rated items (the --top E largest,\n"
+    "                   default 5, 1 .. 16) and a residual that is 0 at a converged row; needs -x (the training ratings), -l (the\n"
+    "                   model's lambda) and -K <= 128; -s 1|2 as --fold-in; with the plain list and --allow only: not with --eval,\n"
+    "                   --diversity, --mmr, --tradeoff, --ranks, --fold-in*, --groups or --candidates\n";
 
 static int usage() { printf("%s", USAGE); return 1; }
 
@@ -610,6 +625,47 @@ static bool read_groups(const char* path, int64_t d2, std::vector<int32_t>& grou
     return ok;
 }
 
+// --explain: the batch's lists (items [m][K], -1 padding at the end) explained by the users' training rows; one line per user
+// and list position to fp
+static bool explain_batch(FILE* fp, const std::vector<double>& U, const std::vector<double>& V, int64_t d2, int64_t k,
+                          const std::vector<int64_t>& xindex, const std::vector<int32_t>& xitem, const std::vector<double>& xval,
+                          const int32_t* users, int64_t m, int K, const std::vector<int32_t>& items, int top, double lambda, int solver, bool f32) {
+    std::vector<int64_t> index((size_t)m + 1, 0);
+    for (int64_t i = 0; i < m; ++i) index[(size_t)i + 1] = index[(size_t)i] + (xindex[(size_t)users[i] + 1] - xindex[(size_t)users[i]]);
+    std::vector<int32_t> item((size_t)index[(size_t)m]);
+    std::vector<double> val((size_t)index[(size_t)m]), Ub((size_t)(m * k));
+    for (int64_t i = 0; i < m; ++i) {
+        const int64_t a = xindex[(size_t)users[i]], len = index[(size_t)i + 1] - index[(size_t)i];
+        std::copy(xitem.begin() + a, xitem.begin() + a + len, item.begin() + index[(size_t)i]);
+        std::copy(xval.begin() + a, xval.begin() + a + len, val.begin() + index[(size_t)i]);
+        std::copy(U.begin() + (int64_t)users[i] * k, U.begin() + ((int64_t)users[i] + 1) * k, Ub.begin() + i * k);
+    }
+    pcr_params prm;
+    pcr_params_default(&prm);
+    prm.k = (int)k; prm.lambda = lambda; prm.solver_type = solver; prm.precision = f32 ? PCR_F32 : PCR_F64;
+    std::vector<int32_t> ei((size_t)(m * K * top));
+    std::vector<double> ec((size_t)(m * K * top)), pp((size_t)(m * K * PCR_EXPLAIN_PAIR_FIELDS));
+    if (pcr_explain_model(&prm, V.data(), d2, m, index.data(), item.data(), val.data(), Ub.data(), nullptr, K, items.data(), top, ei.data(),
+                          ec.data(), pp.data(), nullptr, nullptr) != PCR_OK) {
+        fprintf(stderr, "explain: %s\n", pcr_last_error());
+        return false;
+    }
+    for (int64_t i = 0; i < m; ++i)
+        for (int l = 0; l < K; ++l) {
+            const int32_t j = items[(size_t)(i * K + l)];
+            if (j < 0) break;
+            const double* q = pp.data() + (size_t)(i * K + l) * PCR_EXPLAIN_PAIR_FIELDS;
+            if (fprintf(fp, "%lld %lld %g %g %g %g ", (long long)users[i] + 1, (long long)j + 1, q[0], q[1], q[2], q[3]) < 0) return false;
+            for (int e = 0; e < top; ++e) {
+                const size_t z = (size_t)(i * K + l) * top + e;
+                if (ei[z] < 0) break;
+                if (fprintf(fp, " %lld:%g", (long long)ei[z] + 1, ec[z]) < 0) return false;
+            }
+            if (fputc('\n', fp) == EOF) return false;
+        }
+    return true;
+}
+
 int main(int argc, char** argv) {
     int K = 10;
     bool f32 = false, with_scores = false, with_ranks = false, diversity = false;
@@ -634,8 +690,24 @@ int main(int argc, char** argv) {
     double lambda = 0.0;
     bool have_lambda = false, have_s = false, have_steps = false;
     int solver = PCR_SOLVER_PCRPP, steps = 10;
+    const char* efile = nullptr;                                   // --explain
+    int top = 0;                                                   // --top (0: not given)
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
+        if (!strcmp(a, "--explain")) {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
+            efile = argv[++i];
+            continue;
+        }
+        if (!strcmp(a, "--top")) {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
+            const char* v = argv[++i];
+            char* end = nullptr;
+            const long x = strtol(v, &end, 10);
+            if (!*v || *end || x < 1 || x > PCR_EXPLAIN_MAX_E) { fprintf(stderr, "--top %s: must be an integer in 1 .. %d\n", v, PCR_EXPLAIN_MAX_E); return 1; }
+            top = (int)x;
+            continue;
+        }
         if (!strcmp(a, "--fold-in-ridge")) {
             if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
             rdir = argv[++i];
@@ -758,6 +830,19 @@ int main(int argc, char** argv) {
     }
     const bool tradeoff = !thetas.empty();
     const bool capped = gfile || max_per_group;                    // (the plain list's flow with pcr_recommend_capped_model)
+    if (top && !efile) { fprintf(stderr, "--top goes with --explain\n"); return 1; }
+    if (efile) {                                                   // (the plain list's flow, then pcr_explain_model on its lists)
+        if (edir || diversity || mmr || tradeoff || with_ranks || ifile || fdir || rdir || ndir || capped || cfile) {
+            fprintf(stderr, "--explain does not go with --eval, --diversity, --mmr, --tradeoff, --ranks, --fold-in*, --groups or --candidates\n");
+            return 1;
+        }
+        if (!xdir) { fprintf(stderr, "--explain needs -x data_dir (the training ratings)\n"); return 1; }
+        if (!have_lambda) { fprintf(stderr, "--explain needs -l lambda\n"); return 1; }
+        if (!(lambda > 0.0)) { fprintf(stderr, "-l %g: must be > 0 with --explain\n", lambda); return 1; }
+        if (have_steps || plain_reg) { fprintf(stderr, "--explain takes no --steps and no --plain-reg\n"); return 1; }
+        if (K > PCR_EXPLAIN_MAX_L) { fprintf(stderr, "-K %d: --explain takes lists of at most %d items\n", K, PCR_EXPLAIN_MAX_L); return 1; }
+        if (!top) top = 5;
+    }
     if (capped) {
         if (!gfile || !max_per_group) { fprintf(stderr, "--groups and --max-per-group go together\n"); return 1; }
         if (edir || diversity || mmr || tradeoff || with_ranks || ifile || fdir || rdir || ndir || cfile) {
@@ -807,7 +892,7 @@ int main(int argc, char** argv) {
         if (have_s || have_steps) { fprintf(stderr, "--fold-in-ridge takes no -s and no --steps\n"); return 1; }
         if (!have_lambda) { fprintf(stderr, "--fold-in-ridge needs -l lambda\n"); return 1; }
         if (lambda < 0.0) { fprintf(stderr, "-l %g: must not be negative with --fold-in-ridge\n", lambda); return 1; }
-    } else if (plain_reg) { fprintf(stderr, "--plain-reg goes with --fold-in-ridge\n"); return 1; }
+    } else if (plain_reg && !efile) { fprintf(stderr, "--plain-reg goes with --fold-in-ridge\n"); return 1; }
     const bool nnls = ndir != nullptr, ridge = rdir != nullptr || nnls;          // (ridge: both take --fold-in-ridge's flow)
     if (ridge) fdir = nnls ? ndir : rdir;
     if ((afile || cfile) && (edir || diversity || mmr || tradeoff || with_ranks || fdir)) {
@@ -817,7 +902,7 @@ int main(int argc, char** argv) {
     if (fdir) {
         if (!ridge && (xdir || ufile || diversity || mmr || tradeoff || with_ranks)) { fprintf(stderr, "--fold-in does not go with -x, -u, --diversity, --mmr, --tradeoff or --ranks\n"); return 1; }
         if (!have_lambda && !ridge) { fprintf(stderr, "--fold-in needs -l lambda\n"); return 1; }
-    } else if (have_lambda || have_s || have_steps) { fprintf(stderr, "-l, -s and --steps go with --fold-in\n"); return 1; }
+    } else if (!efile && (have_lambda || have_s || have_steps)) { fprintf(stderr, "-l, -s and --steps go with --fold-in\n"); return 1; }
     if (tradeoff) {                                                // (its own rules; the checks below are the other modes')
         if (mmr || diversity || with_ranks || with_scores) { fprintf(stderr, "--tradeoff does not go with --mmr, --diversity, --ranks or --scores\n"); return 1; }
         if (pos.size() > 1) { fprintf(stderr, "--tradeoff writes no output file\n"); return 1; }
@@ -848,7 +933,8 @@ int main(int argc, char** argv) {
     else { users.resize((size_t)d1); for (int64_t u = 0; u < d1; ++u) users[(size_t)u] = (int32_t)u; }
     std::vector<int64_t> xindex;
     std::vector<int32_t> xitem;
-    if (xdir && !load_csr(xdir, 0, d1, d2, xindex, xitem, nullptr)) return 1;
+    std::vector<double> xval;                                      // --explain: the training ratings' values
+    if (xdir && !load_csr(xdir, 0, d1, d2, xindex, xitem, efile ? &xval : nullptr)) return 1;
     std::vector<uint8_t> allow;                                    // --allow / --candidates: the filter of every batch
     std::vector<int64_t> cptr, bptr;
     std::vector<int32_t> citem;
@@ -888,6 +974,8 @@ int main(int argc, char** argv) {
     }
     FILE* out_fp = fopen(pos[1], "wb");
     if (!out_fp) { fprintf(stderr, "can't open output file %s\n", pos[1]); return 1; }
+    FILE* ex_fp = efile ? fopen(efile, "wb") : nullptr;
+    if (efile && !ex_fp) { fprintf(stderr, "can't open explanation file %s\n", efile); fclose(out_fp); return 1; }
     const int64_t n = (int64_t)users.size();
     const int64_t batch = std::max<int64_t>(1, ((int64_t)1 << 22) / K);   // 4 M list entries per call
     std::vector<int32_t> items;
@@ -937,9 +1025,14 @@ int main(int argc, char** argv) {
             *p++ = '\n';
         }
         ok = fwrite(o.data(), 1, (size_t)(p - o.data()), out_fp) == (size_t)(p - o.data());
+        if (ex_fp && ok && !explain_batch(ex_fp, U, V, d2, k, xindex, xitem, xval, users.data() + b0, m, K, items, top, lambda, solver, f32)) {
+            fclose(out_fp); fclose(ex_fp);
+            return 1;
+        }
     }
     ok = (fclose(out_fp) == 0) && ok;
     if (!ok) { fprintf(stderr, "short write to %s\n", pos[1]); return 1; }
+    if (ex_fp && fclose(ex_fp) != 0) { fprintf(stderr, "short write to %s\n", efile); return 1; }
     if (capped)
         printf("capped users %lld exact %lld pool_exhausted %lld short %lld kept %lld\n", (long long)cap_all.users, (long long)cap_all.exact,
                (long long)cap_all.exhausted, (long long)cap_all.short_rows, (long long)cap_all.kept);

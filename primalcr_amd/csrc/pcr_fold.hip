@@ -4,12 +4,15 @@
 //   pcr_fold_in_ridge    squared loss                     k_ridge_direct, k_ridge_cg (pcr_ridge.h)   "foldin/ridge"
 //   pcr_fold_in_nnls     squared loss, row >= 0           k_nnls_direct, k_nnls_cg (pcr_nnls.h)      "foldin/nnls"
 //   pcr_fold_in_items    new items of a ranking model     k_rater_scores, k_itemfold (pcr_itemfold.h) "itemfold/scores", "itemfold/newton"
+// and, on fold-in's plan and forms, the explanation of listed items by a user's own ratings:
+//   pcr_explain          rows of a ranking model          k_explain (pcr_explain.h)                  "explain/contrib"
 // A run uploads its plan (pcr_host.cpp built and checked it), launches one kernel per workgroup form inside the family's profile
 // slot -- workgroups stride over their range, the longest rows first -- and hands the rows, the stats and the per-row records
 // back through one FoldOut.  Recommendation and its metrics are pcr_serve.hip, training is pcr_solver.hip.
 // There is NO CPU compute path in this file: every [device] entry point fails with PCR_ERR_DEVICE when HIP is unusable.
 #include "pcr_dev.h"
 #include "pcr_foldin.h"
+#include "pcr_explain.h"
 #include "pcr_itemfold.h"
 #include "pcr_ridge.h"
 #include "pcr_nnls.h"
@@ -348,6 +351,92 @@ static int itemfold_run(const ServeView& v, const FoldinParams& c, const PcrItem
     return out.finish(v, V_out, per_item, [&](const double* hp) { if (stats) { stats->unique_raters = nr; pcr_itemfold_stats_from(hp, n, stats); } });
 }
 
+// Explanations (pcr_explain, pcr_explain_model; k_explain of pcr_explain.h) of the plan's users: Um holds their rows of U (row
+// urow[i] is user i's; NULL: row i), lam their regularisers lambda / c_u.  The ratings, levels and order go to the device as
+// fold-in's, then one launch per workgroup form.  A launch's LDS is sized by its longest user; the refusal by the form's largest.
+struct ExplainOut { int32_t* item; double* contrib; double* per_pair; double* per_user; pcr_explain_stats* stats; };
+template <typename T, int BLOCK, bool BIG>
+static int explain_launch(const ServeView& v, int strict, const PcrFoldinPlan& P, const FoldinCsr& X, const Geo& geo, const int32_t* d_order, int64_t first,
+                          int64_t count, int cus, const T* Um, const int32_t* urow, const double* lam, const int32_t* lists, int L, int E,
+                          int32_t* d_item, double* d_contrib, double* d_pair, double* d_user, DBuf<char>& scratch) {
+    if (count <= 0) return PCR_OK;
+    const std::vector<int64_t>& idx = P.X.index;
+    const int32_t longest = P.order[(size_t)first];
+    const int cap = (int)std::max<int64_t>(1, idx[(size_t)longest + 1] - idx[(size_t)longest]);
+    int rs_cap = 1;
+    for (int64_t i = first; i < first + count; ++i) {
+        const int32_t u = P.order[(size_t)i];
+        rs_cap = std::max(rs_cap, (int)(P.lv.run_ofs[(size_t)u + 1] - P.lv.run_ofs[(size_t)u]));
+    }
+    const size_t li_bytes = BIG ? 8 : 4, arr = explain_arr_bytes(cap, rs_cap, sizeof(T), li_bytes);
+    const int erows = std::min(cap, EXPLAIN_CHUNK);
+    const size_t lds = explain_small_bytes(geo.ld, BLOCK, sizeof(T), erows) + (BIG ? 0 : arr);
+    // the refusal is a function of the rank and the user's form alone: the form's largest user (a level per rating) must fit
+    const int form_cap = BLOCK == 64 ? PCR_FOLDIN_WAVE_MAX : PCR_FOLDIN_LDS_MAX;
+    if (explain_small_bytes(geo.ld, BLOCK, sizeof(T), std::min(form_cap, EXPLAIN_CHUNK)) + (BIG ? 0 : explain_arr_bytes(form_cap, form_cap + 1, sizeof(T), li_bytes)) >
+        PCR_LDS_CU) {
+        pcr_set_error("explain: rank " + std::to_string(geo.r) + " is too large for the LDS of the workgroup form of users " +
+                      (BIG ? "beyond " + std::to_string(PCR_FOLDIN_LDS_MAX) : "of up to " + std::to_string(form_cap)) + " ratings");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    if (BIG && ((arr + 255) & ~(size_t)255) > FOLD_SCRATCH) {
+        pcr_set_error("explain: a user of " + std::to_string(cap) + " ratings needs more than 1 GiB of per-rating scratch");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    int64_t grid = fold_grid(count, cus, fold_wg_cap(BLOCK), lds);
+    size_t stride = 0;
+    if (BIG) RC(fold_slices(arr, &grid, &stride, scratch));
+    return fold_launch(k_explain<T, BLOCK, BIG>, grid, BLOCK, lds, v.st, X, geo, d_order + first, (int)count, Um, urow, serve_V<T>(v), lam, lists, L, E,
+                       d_item, d_contrib, d_pair, d_user, strict, cap, rs_cap, erows, scratch.p, stride);
+}
+
+template <typename T>
+static int explain_run(const ServeView& v, int solver_type, double lambda, const PcrFoldinPlan& P, const T* Um, const int32_t* urow_host,
+                       const double* weights, int L, const int32_t* lists, int E, const ExplainOut& o) {
+    const int64_t n = P.X.d1;
+    hipStream_t st = v.st;
+    Geo geo;
+    geo.r = v.r; geo.ld = v.ld; geo.nchunk = v.ld / VecOf<T>::N; geo.G = std::min(64, host_pow2(geo.nchunk));
+    int cus = 0;
+    RC(device_cus(&cus));
+    std::vector<double> lam((size_t)n);
+    for (int64_t i = 0; i < n; ++i) lam[(size_t)i] = weights ? lambda / weights[i] : lambda;
+    DBuf<int64_t> uptr, runofs;
+    DBuf<int32_t> item, runstart, order, urow, dlists, d_item;
+    DBuf<uint16_t> lvl;
+    DBuf<double> dlam, d_contrib, d_pair, d_user;
+    DBuf<char> scratch;
+    const size_t pairs = (size_t)n * L;
+    RC(uptr.upload(P.X.index, st)); RC(item.upload_n(P.X.item.data(), P.X.item.size()));
+    RC(lvl.upload(P.lv.level, st)); RC(runofs.upload(P.lv.run_ofs, st)); RC(runstart.upload(P.lv.run_start, st));
+    RC(order.upload(P.order, st)); RC(dlam.upload(lam, st)); RC(dlists.upload_n(lists, pairs));
+    if (urow_host) RC(urow.upload_n(urow_host, (size_t)n));
+    RC(d_item.alloc(pairs * E)); RC(d_contrib.alloc(pairs * E)); RC(d_pair.alloc(pairs * PCR_EXPLAIN_PAIR_FIELDS));
+    RC(d_user.alloc((size_t)n * PCR_EXPLAIN_USER_FIELDS));
+    const FoldinCsr X = {uptr.p, item.p, lvl.p, runofs.p, runstart.p};
+    const int strict = solver_type == PCR_SOLVER_PCR ? 1 : 0;
+    {
+        ProfScope ps(v.prof, "explain/contrib", st);
+        const int64_t nw = n - P.n_big - P.n_lds;
+        RC((explain_launch<T, 512, true>(v, strict, P, X, geo, order.p, 0, P.n_big, cus, Um, urow_host ? urow.p : nullptr, dlam.p, dlists.p, L, E,
+                                         d_item.p, d_contrib.p, d_pair.p, d_user.p, scratch)));
+        RC((explain_launch<T, 256, false>(v, strict, P, X, geo, order.p, P.n_big, P.n_lds, cus, Um, urow_host ? urow.p : nullptr, dlam.p, dlists.p, L, E,
+                                          d_item.p, d_contrib.p, d_pair.p, d_user.p, scratch)));
+        RC((explain_launch<T, 64, false>(v, strict, P, X, geo, order.p, P.n_big + P.n_lds, nw, cus, Um, urow_host ? urow.p : nullptr, dlam.p, dlists.p, L, E,
+                                         d_item.p, d_contrib.p, d_pair.p, d_user.p, scratch)));
+    }
+    std::vector<double> hpair;
+    double* pair_out = o.per_pair;
+    if (!pair_out && o.stats) { hpair.resize(pairs * PCR_EXPLAIN_PAIR_FIELDS); pair_out = hpair.data(); }
+    HIPCHK(hipMemcpyAsync(o.item, d_item.p, pairs * E * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(o.contrib, d_contrib.p, pairs * E * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (pair_out) HIPCHK(hipMemcpyAsync(pair_out, d_pair.p, pairs * PCR_EXPLAIN_PAIR_FIELDS * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (o.per_user) HIPCHK(hipMemcpyAsync(o.per_user, d_user.p, (size_t)n * PCR_EXPLAIN_USER_FIELDS * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (o.stats) pcr_explain_stats_from(pair_out, o.item, lists, n, L, E, o.stats);
+    return PCR_OK;
+}
+
 // The entries' common end: the stats zeroed, nothing more for n == 0, then open() -- a _model entry's upload, nothing on a
 // solver -- and run(T()) in the view's precision
 template <class Stats, class Open, class Run>
@@ -478,6 +567,68 @@ int pcr_fold_in_items(pcr_solver* s, const pcr_dataset* train, int64_t n, const 
                                    user, val, steps, V_out, &P));
         const FoldinParams c = foldin_params_of(prm, steps);
         return fold_serve(stats, n, v, on_solver, [&](auto zero) -> int { return itemfold_run<decltype(zero)>(v, c, P, V0, V_out, stats, per_item); });
+    });
+}
+
+int pcr_explain_model(const pcr_params* p, const double* V, int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val,
+                      const double* U, const double* weights, int L, const int32_t* lists, int E, int32_t* expl_item, double* expl_contrib,
+                      double* per_pair, double* per_user, pcr_explain_stats* stats) {
+    return abi_guard("pcr_explain_model", [&]() -> int {
+    PcrFoldinPlan P;
+    RC(pcr_explain_check("pcr_explain_model", true, p, V, d2, n, index, item, val, U, weights, L, lists, E, expl_item, expl_contrib, &P));
+    RC(model_device(p->device));
+    ServeView v; ModelDev M;
+    const ExplainOut o = {expl_item, expl_contrib, per_pair, per_user, stats};
+    return fold_serve(stats, n, v, [&] { return M.open(U, n, V, d2, p->k, nullptr, nullptr, true, p->precision, &v); }, [&](auto zero) -> int {
+        typedef decltype(zero) T;
+        return explain_run<T>(v, p->solver_type, p->lambda, P, serve_U<T>(v), nullptr, weights, L, lists, E, o);
+    });
+    });
+}
+
+int pcr_explain(pcr_solver* s, const pcr_dataset* train, int64_t n, const int32_t* users, const double* weights, int L, const int32_t* lists, int E,
+                int32_t* expl_item, double* expl_contrib, double* per_pair, double* per_user, pcr_explain_stats* stats) {
+    S_OR_ARG;
+    return abi_guard("pcr_explain", [&]() -> int {
+        pcr_params prm;
+        if (s->foldin_params(&prm) != PCR_OK) return pcr_solver::pcr_only("pcr_explain");
+        const ServeView v = solver_view(s, 0);
+        if (s->comm_nranks() > 1 || s->first_user != 0 || s->n_users != v.d1) {
+            pcr_set_error("pcr_explain: needs every user on the rank; this solver holds a shard");
+            return PCR_ERR_STATE;
+        }
+        if (!train) { pcr_set_error("pcr_explain: null training data set"); return PCR_ERR_ARG; }
+        const PcrCsr& X = train->train;
+        if (X.d1 != v.d1 || X.d2 != v.d2 || X.nnz() != v.nnz) {
+            pcr_set_error("pcr_explain: the data set is not the one the solver was created from (dimensions or nnz differ)");
+            return PCR_ERR_ARG;
+        }
+        if (!users) n = s->n_users;                                // (n is ignored without users)
+        if (n < 0 || n >= ((int64_t)1 << 31) - 64) { pcr_set_error("pcr_explain: bad argument"); return PCR_ERR_ARG; }
+        // the requested users' rows of the data set, and their rows of the device U
+        std::vector<int64_t> index((size_t)n + 1, 0);
+        std::vector<int32_t> urow((size_t)n);
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t u = users ? users[i] : i;
+            if (u < 0 || u >= X.d1) { pcr_set_error("pcr_explain: user id " + std::to_string(u) + " is outside the solver's users"); return PCR_ERR_ARG; }
+            urow[(size_t)i] = (int32_t)u;
+            index[(size_t)i + 1] = index[(size_t)i] + (X.index[(size_t)u + 1] - X.index[(size_t)u]);
+        }
+        std::vector<int32_t> item((size_t)index[(size_t)n]);
+        std::vector<double> val((size_t)index[(size_t)n]);
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t a = X.index[(size_t)urow[(size_t)i]], len = index[(size_t)i + 1] - index[(size_t)i];
+            std::copy(X.item.begin() + a, X.item.begin() + a + len, item.begin() + index[(size_t)i]);
+            std::copy(X.val.begin() + a, X.val.begin() + a + len, val.begin() + index[(size_t)i]);
+        }
+        PcrFoldinPlan P;
+        RC(pcr_explain_check("pcr_explain", false, &prm, nullptr, v.d2, n, index.data(), item.data(), val.data(), nullptr, weights, L, lists, E,
+                             expl_item, expl_contrib, &P));
+        const ExplainOut o = {expl_item, expl_contrib, per_pair, per_user, stats};
+        return fold_serve(stats, n, v, on_solver, [&](auto zero) -> int {
+            typedef decltype(zero) T;
+            return explain_run<T>(v, prm.solver_type, prm.lambda, P, serve_U<T>(v), urow.data(), weights, L, lists, E, o);
+        });
     });
 }
 }  // extern "C"

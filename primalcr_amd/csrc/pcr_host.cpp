@@ -1746,8 +1746,9 @@ void pcr_csr_sorted_copy(int64_t d2, int64_t n, const int64_t* index, const int3
         });
 }
 
-int pcr_fold_in_check(const char* who, int solver_type, int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val,
-                      int steps, const double* U_out, PcrFoldinPlan* plan) {
+// with_out: the fold-in entries' own arguments (steps, the output) are checked in their place; pcr_fold_in_rows_check leaves them out
+static int fold_in_check_impl(const char* who, int solver_type, int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val,
+                              bool with_out, int steps, const double* U_out, PcrFoldinPlan* plan) {
     auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
     if (solver_type == PCR_SOLVER_CCDR1) {
         pcr_set_error(std::string(who) + ": solver type 0 (CCDR1) is not supported: its squared-loss fold-in is a ridge solve");
@@ -1757,8 +1758,8 @@ int pcr_fold_in_check(const char* who, int solver_type, int64_t d2, int64_t n, c
     if (n < 0 || d2 < 1 || !index) return bad("bad argument");
     if (d2 >= ((int64_t)1 << 31) - 64) return bad("more than 2^31 items");
     if (n >= ((int64_t)1 << 31) - 64) return bad("more than 2^31 users in one call");
-    if (steps < 1) return bad("steps = " + std::to_string(steps) + " must be at least 1");
-    if (n > 0 && !U_out) return bad("null output");
+    if (with_out && steps < 1) return bad("steps = " + std::to_string(steps) + " must be at least 1");
+    if (with_out && n > 0 && !U_out) return bad("null output");
     if (index[0] != 0) return bad("index[0] must be 0");
     for (int64_t u = 0; u < n; ++u) {
         if (index[u + 1] < index[u]) return bad("index not monotone at user " + std::to_string(u));
@@ -1788,6 +1789,15 @@ int pcr_fold_in_check(const char* who, int solver_type, int64_t d2, int64_t n, c
     return PCR_OK;
 }
 
+int pcr_fold_in_check(const char* who, int solver_type, int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val,
+                      int steps, const double* U_out, PcrFoldinPlan* plan) {
+    return fold_in_check_impl(who, solver_type, d2, n, index, item, val, true, steps, U_out, plan);
+}
+int pcr_fold_in_rows_check(const char* who, int solver_type, int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val,
+                           PcrFoldinPlan* plan) {
+    return fold_in_check_impl(who, solver_type, d2, n, index, item, val, false, 0, nullptr, plan);
+}
+
 int pcr_fold_in_model_check(const pcr_params* p, const double* V, int64_t d2, int64_t n, const int64_t* index, const int32_t* item,
                             const double* val, int steps, const double* U_out, PcrFoldinPlan* plan) {
     auto bad = [](const std::string& why) { pcr_set_error("pcr_fold_in_model: " + why); return PCR_ERR_ARG; };
@@ -1810,6 +1820,68 @@ void pcr_foldin_stats_from(const double* per_user, int64_t n, pcr_foldin_stats* 
         const int status = (int)o[5];
         if (status == PCR_FOLDIN_CONVERGED) s.converged += 1; else if (status == PCR_FOLDIN_STEP_CAP) s.step_cap += 1; else s.stalled += 1;
     }
+    *stats = s;
+}
+
+// ------------------------------------------------------------------------------------------
+// explanations (include/primalcr.h, "explaining recommendations"): argument checks; the plan is fold-in's
+// ------------------------------------------------------------------------------------------
+int pcr_explain_check(const char* who, bool need_factors, const pcr_params* p, const double* V, int64_t d2, int64_t n, const int64_t* index,
+                      const int32_t* item, const double* val, const double* U, const double* weights, int L, const int32_t* lists, int E,
+                      const int32_t* expl_item, const double* expl_contrib, PcrFoldinPlan* plan) {
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
+    if (!p) return bad("null parameters");
+    if (need_factors) {
+        if (!V) return bad("null V");
+        if (p->k < 1) return bad("rank k must be >= 1");
+        if (p->precision != PCR_F32 && p->precision != PCR_F64) return bad("precision must be PCR_F32 or PCR_F64");
+    }
+    if (!std::isfinite(p->lambda) || !(p->lambda > 0.0)) return bad("lambda must be finite and > 0");
+    if (p->solver_type == PCR_SOLVER_CCDR1) {
+        pcr_set_error(std::string(who) + ": solver type 0 (CCDR1) is not supported: a squared-loss row decomposes through its residuals, not through sweep coefficients");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    const int rc = pcr_fold_in_rows_check(who, p->solver_type, d2, n, index, item, val, plan);
+    if (rc != PCR_OK) return rc;
+    if (n > 0 && need_factors && !U) return bad("null U");
+    if (n > 0 && !lists) return bad("null lists");
+    if (n > 0 && (!expl_item || !expl_contrib)) return bad("null expl_item / expl_contrib");
+    if (L < 1 || L > PCR_EXPLAIN_MAX_L) return bad("L = " + std::to_string(L) + " must be inside [1, " + std::to_string(PCR_EXPLAIN_MAX_L) + "]");
+    if (E < 1 || E > PCR_EXPLAIN_MAX_E) return bad("E = " + std::to_string(E) + " must be inside [1, " + std::to_string(PCR_EXPLAIN_MAX_E) + "]");
+    const int nth = pcr_host_threads();
+    std::vector<int> st((size_t)nth, 0);
+    pcr_parallel_ranges(n, nth, [&](int t, int64_t lo, int64_t hi) {
+        for (int64_t u = lo; u < hi; ++u) {
+            bool pad = false;
+            for (int l = 0; l < L; ++l) {
+                const int32_t j = lists[(size_t)u * L + l];
+                if (j == -1) { pad = true; continue; }
+                if (j < 0 || j >= d2) st[(size_t)t] |= 1;
+                else if (pad) st[(size_t)t] |= 2;
+            }
+        }
+    });
+    int all = 0;
+    for (int x : st) all |= x;
+    if (all & 1) return bad("a list id is outside [0, d2) and not -1");
+    if (all & 2) return bad("a list holds an id after a -1");
+    if (weights)
+        for (int64_t u = 0; u < n; ++u)
+            if (!std::isfinite(weights[u]) || !(weights[u] > 0.0)) return bad("the weight of user " + std::to_string(u) + " must be finite and > 0");
+    return PCR_OK;
+}
+
+void pcr_explain_stats_from(const double* per_pair, const int32_t* expl_item, const int32_t* lists, int64_t n, int L, int E, pcr_explain_stats* stats) {
+    pcr_explain_stats s = {};
+    s.users = n;
+    for (int64_t z = 0; z < n * L; ++z) {
+        const double* o = per_pair + (size_t)z * PCR_EXPLAIN_PAIR_FIELDS;
+        if (lists[z] < 0) continue;                                         // padding
+        s.pairs += 1;
+        const double r = std::fabs(o[3]);
+        if (r > s.residual_abs_max) s.residual_abs_max = r;
+    }
+    for (int64_t z = 0; z < n * L * E; ++z) s.contributors += expl_item[z] >= 0 ? 1 : 0;
     *stats = s;
 }
 

@@ -223,11 +223,25 @@ struct PcrFoldinPlan {
 // pcr_build_levels refuses; errors are prefixed with `who`.  plan (may be NULL) receives the plan.
 int pcr_fold_in_check(const char* who, int solver_type, int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val,
                       int steps, const double* U_out, PcrFoldinPlan* plan);
+// ... without the fold-in entries' own arguments (steps, the output): the rows, their levels and the plan alone (pcr_explain_check)
+int pcr_fold_in_rows_check(const char* who, int solver_type, int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val,
+                           PcrFoldinPlan* plan);
 // pcr_fold_in_model's: the parameters it reads of p (k, precision, lambda, stepsize, cg_max_iter, cg_tol), V, then pcr_fold_in_check
 int pcr_fold_in_model_check(const pcr_params* p, const double* V, int64_t d2, int64_t n, const int64_t* index, const int32_t* item,
                             const double* val, int steps, const double* U_out, PcrFoldinPlan* plan);
 // stats from the per-user table [n][PCR_FOLDIN_FIELDS]: the counts, and obj added in user order
 void pcr_foldin_stats_from(const double* per_user, int64_t n, pcr_foldin_stats* stats);
+
+// Explanations (include/primalcr.h, "explaining recommendations").  The argument checks of pcr_explain_model / pcr_explain in the
+// order the header lists them (the library and the sanitizer build's "no device" stub run the same ones) and the plan, which is
+// fold-in's: the rows item-ascending, their levels, the users by descending length in the three workgroup forms.  need_factors:
+// V and U are the caller's (the standalone entry; k and precision of p are checked with them); p's lambda and solver type are
+// read by both.  Errors are prefixed with `who`.  plan may be NULL.
+int pcr_explain_check(const char* who, bool need_factors, const pcr_params* p, const double* V, int64_t d2, int64_t n, const int64_t* index,
+                      const int32_t* item, const double* val, const double* U, const double* weights, int L, const int32_t* lists, int E,
+                      const int32_t* expl_item, const double* expl_contrib, PcrFoldinPlan* plan);
+// stats from the finished tables per_pair [n][L][PCR_EXPLAIN_PAIR_FIELDS] and expl_item [n][L][E]; lists [n][L] tells the padding
+void pcr_explain_stats_from(const double* per_pair, const int32_t* expl_item, const int32_t* lists, int64_t n, int L, int E, pcr_explain_stats* stats);
 
 // Item fold-in (include/primalcr.h, "item fold-in").  What the host prepares for k_rater_scores / k_itemfold: the new items as
 // SLOTS by descending rater count (equal counts by ascending id) -- slots [0, n_big) take the global-scratch form, the next n_lds

@@ -2,7 +2,9 @@
 // PrimalCR++ hot path.  Header-only templates, instantiated in pcr_solver.hip:
 //   pcr_prims.h (wave / team primitives, sorts, sweep coefficients, row primitives), pcr_vside.h (V step), pcr_ustep.h (U step),
 //   pcr_eval.h (evaluator, objective reductions, predict); pcr_gram.h (optional dual-form U step on MFMA).  Not part of this header:
-//   pcr_topk.h (top-K recommendation: MFMA scores with a fused streaming selection), instantiated in pcr_serve.hip over pcr_prims.h.
+//   pcr_topk.h (top-K recommendation: MFMA scores with a fused streaming selection), instantiated in pcr_serve.hip over pcr_prims.h;
+//   pcr_foldin.h, pcr_itemfold.h, pcr_ridge.h, pcr_nnls.h (the fold-in families) and pcr_explain.h (k_explain: a score decomposed
+//   over the user's own rated items), instantiated in pcr_fold.hip over pcr_prims.h.
 //
 // Kernel map (reference site -> kernel); design and rooflines: DESIGN.md section 3:
 //   K1        comp_m_new, b = u.a in compute_Ha_new        -> k_sddmm     (rating-parallel)
@@ -16,6 +18,7 @@
 //             top-K unrated items per user (no reference)  -> k_rec_score + k_rec_merge
 //             ... among an allow set / candidate lists      -> k_rec_score's allow operand / k_rec_cand
 //             top-N evaluation of those lists (no reference) -> k_rec_score + k_rec_merge_topn + k_topn_sum1 / k_topn_fin
+//             why an item was listed (no reference)        -> k_explain (obtain_g_u_new's coefficients, one workgroup per user)
 //
 // Formulation (replaces the sequential two-pointer sweep with data-parallel primitives,
 // same result): a user's ratings are sorted by (level, m), so every rating level is one

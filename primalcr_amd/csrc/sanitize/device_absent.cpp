@@ -174,6 +174,14 @@ int pcr_fold_in_items_model(const pcr_params* p, const double* U, int64_t d1, co
 }
 NO_SOLVER(pcr_fold_in_items, pcr_solver*, const pcr_dataset*, int64_t, const int64_t*, const int32_t*, const double*, const double*, int, double*,
           pcr_itemfold_stats*, double*)
+int pcr_explain_model(const pcr_params* p, const double* V, int64_t d2, int64_t n, const int64_t* index, const int32_t* item, const double* val,
+                      const double* U, const double* weights, int L, const int32_t* lists, int E, int32_t* expl_item, double* expl_contrib, double*,
+                      double*, pcr_explain_stats*) {
+    const int rc = pcr_explain_check("pcr_explain_model", true, p, V, d2, n, index, item, val, U, weights, L, lists, E, expl_item, expl_contrib, nullptr);
+    return rc != PCR_OK ? rc : absent();
+}
+NO_SOLVER(pcr_explain, pcr_solver*, const pcr_dataset*, int64_t, const int32_t*, const double*, int, const int32_t*, int, int32_t*, double*, double*,
+          double*, pcr_explain_stats*)
 NO_SOLVER(pcr_evaluate_rerank, pcr_solver*, int64_t, const int32_t*, int, const double*, int, int, const int*, double, int, pcr_topn_stats*,
           pcr_diversity_stats*, double*, double*, int64_t*)
 }
