@@ -1195,7 +1195,7 @@ int pcr_fold_in_items(pcr_solver *s, const pcr_dataset *train, int64_t n, const 
  *                      index[0] != 0, a non-monotone index, null item / val, an item id outside [0, d2), a rating that is not
  *                      finite); a null U, lists, expl_item or expl_contrib; L or E out of range; a list id outside [0, d2) that
  *                      is not -1; a non-padding id after a -1; a weight that is not finite or <= 0.  Solver type 0 is
- *                      PCR_ERR_UNSUPPORTED (a squared-loss row decomposes through its residuals: another entry), as is whatever
+ *                      PCR_ERR_UNSUPPORTED (a squared-loss row decomposes through its residuals: pcr_explain_ridge below), as is whatever
  *                      the level builder refuses.  A rank whose vectors, tile and the per-rating arrays of the form's LARGEST
  *                      user do not fit a workgroup's 160 KiB of LDS is PCR_ERR_UNSUPPORTED, reported when the call reaches the
  *                      form -- a function of the rank, the storage type and the form alone.  Without a device: PCR_ERR_DEVICE. */
@@ -1224,6 +1224,81 @@ int pcr_explain(pcr_solver *s, const pcr_dataset *train, int64_t n, const int32_
                 const double *weights, int L, const int32_t *lists, int E,
                 int32_t *expl_item, double *expl_contrib, double *per_pair, double *per_user,
                 pcr_explain_stats *stats);                                                         /* [device] */
+
+/* ------------------------------------------------------------------------- */
+/* explaining squared-loss recommendations: a CCDR1 / ridge row's score over   */
+/* the user's own rated items (no reference counterpart)                      */
+/* ------------------------------------------------------------------------- */
+/* For squared-loss factorisation the explanation is Hu, Koren and Volinsky's ("Collaborative filtering for implicit feedback
+ * datasets", ICDM 2008, section 5): the score is a sum over the user's rated items of rating x a user-specific similarity taken
+ * through the inverse of the user's regularised Gram matrix.  It is exact.
+ *   Definition         Take user i with its training row sorted by item id, equal items keeping their order; "position" p = 0 ..
+ *                      len - 1 is the position in that sorted row.  The row has items i_p and ratings r_p; A = F[I] is len x k,
+ *                      the storage-type values widened to fp64 as they are read; mu = lambda len when weighted != 0, else
+ *                      mu = lambda (pcr_fold_in_ridge's rule); u^ = U[i] rounded to the storage type.  The free set P is every
+ *                      coordinate when nonneg == 0 and { t : u^_t > 0 } when nonneg != 0 (a row trained with -N 1, or one that
+ *                      pcr_fold_in_nnls returned); Z is its complement.  With G = A_P^T A_P + mu I and b = A_P^T r:
+ *                          u*_P = G^-1 b, u*_Z = 0;    for a listed item j with row v_j of F: (z_j)_P = G^-1 (v_j)_P, (z_j)_Z = 0
+ *                          e_p(j)      = r_p (v_{i_p} . z_j)          contribution of rated item i_p
+ *                          sum_p e_p(j) = v_j . u*                    (exactly, in exact arithmetic)
+ *                          score(j)    = v_j . u^                     (fp64 -- not pcr_recommend's f32 chain)
+ *                          residual(j) = v_j . (u^ - u*)              how far the given row is from the exact minimiser on P
+ *                          score       = support + opposition + residual
+ *                      support / opposition are the sums of the positive / negative e_p, added in ascending position.
+ *                      U == NULL explains the exact minimiser itself: u^ := u* unrounded and residual = +0.0; U == NULL with
+ *                      nonneg != 0 is PCR_ERR_ARG (the free set comes from the row).  A user without ratings has u* = 0 and no
+ *                      system is formed (mu may be 0 there): support = opposition = 0, residual = score, every contributor is
+ *                      padding; the same holds with |P| = 0.  F = U with an item-major CSR explains an item's row by its raters:
+ *                      the entry only sees F.
+ *   Arithmetic         everything after an element of F or U is read is fp64, in both storage types, as in pcr_explain and the
+ *                      ridge kernels: G on v_mfma_f64_16x16x4_f64, a blocked Cholesky, the two triangular solves for u* and for
+ *                      every listed item, the dots.  The order of every sum is fixed but not part of the contract.  lambda must be
+ *                      finite and > 0, so G is positive definite; a Cholesky pivot that is <= 0 or not finite still gives status
+ *                      PCR_RIDGE_SINGULAR for that user: contributors are padding, support = opposition = 0, residual = score.
+ *   Outputs            as pcr_explain's.  expl_item / expl_contrib [n][L][E]: the user's ratings by DESCENDING e_p, equal e_p by
+ *                      ascending position; entries <= 0 are listed like any other; the sign of a zero is unspecified; the padding
+ *                      is (-1, 0.0).  per_pair (optional) [n][L][PCR_EXPLAIN_PAIR_FIELDS] = score, support, opposition,
+ *                      residual; padding positions hold NaN.  per_user (optional) [n][PCR_EXPLAIN_RIDGE_USER_FIELDS] = len, |P|,
+ *                      loss = |r - A u^|^2, dist2 = |u^ - u*|^2, status (PCR_RIDGE_OK or PCR_RIDGE_SINGULAR).  stats (optional):
+ *                      users = n, pairs = the non-padding list positions, contributors = the non-padding contributor entries,
+ *                      singular = the users with status SINGULAR, residual_abs_max = the largest |residual| of a non-padding
+ *                      position (0 without one).  lists [n][L] as pcr_explain's: non-padding ids first, then -1; an id may sit
+ *                      in the row and may occur twice; 1 <= L <= PCR_EXPLAIN_MAX_L, 1 <= E <= PCR_EXPLAIN_MAX_E.
+ *   Determinism        a user's output depends on its row, u^, F, its list and the parameters alone -- not on the other users, its
+ *                      position or the launch grid.  No atomics touch results, nothing is handed between workgroups, there is no
+ *                      spin-wait, every loop has a static bound and every sum a fixed order: two identical calls are bitwise
+ *                      identical.  One workgroup form (256 threads) for every row length and rank (k_explain_ridge,
+ *                      pcr_explain_ridge.h).
+ *   Errors             PCR_ERR_ARG before any device is looked for, the message naming the entry, in this order: a null F, k < 1,
+ *                      rows < 1 or beyond 2^31, an unknown precision, a lambda that is not finite or < 0, n < 0, a null index,
+ *                      index[0] != 0, a non-monotone index, null item / val, an item id outside [0, rows), a rating that is not
+ *                      finite; a lambda that is 0; U == NULL with nonneg != 0; null lists, expl_item or expl_contrib; L or E out
+ *                      of range; a list id outside [0, rows) that is not -1; a non-padding id after a -1.  Then a rank with
+ *                      roundup(k, 16) > PCR_RIDGE_DIRECT_MAX is PCR_ERR_UNSUPPORTED -- a function of k alone, reported before
+ *                      any device work (a matrix-free form for wide ranks stays out).  Without a device: PCR_ERR_DEVICE. */
+#define PCR_EXPLAIN_RIDGE_USER_FIELDS 5  /* ratings, free, loss, dist2, status */
+typedef struct pcr_explain_ridge_stats {
+    int64_t users, pairs, contributors, singular;
+    double  residual_abs_max;
+} pcr_explain_ridge_stats;
+/* Standalone: F (rows x k) and the users' rows U (n x k, or NULL) host fp64 in model-file layout. */
+int pcr_explain_ridge_model(const double *F, int64_t rows, int64_t k, double lambda, int weighted, int nonneg,
+                            int precision, int device, int64_t n,
+                            const int64_t *index, const int32_t *item, const double *val,
+                            const double *U /* [n][k] or NULL */, int L, const int32_t *lists, int E,
+                            int32_t *expl_item, double *expl_contrib, double *per_pair, double *per_user,
+                            pcr_explain_ridge_stats *stats);                                   /* [device] */
+/* On a live single-rank solver from pcr_solver_create (CCDR1 is the intended one; any solver type runs): its device U and V
+ * (F = V), storage type, stream and the lambda pcr_fold_in_ridge runs with.  users[n] are GLOBAL ids (NULL: all of them in order;
+ * n is then ignored.  Ids outside the solver's users: PCR_ERR_ARG).  train must be the data set the solver was created from (its
+ * dimensions and nnz are checked, as pcr_explain checks it): it supplies the rows and their rating values.  nonneg is the
+ * caller's: the entry does not read -N from the solver.  A multi-rank solver or one from pcr_solver_create_shard is
+ * PCR_ERR_STATE.  Nothing of the solver is written: training that continues afterwards gives bitwise the same factors.
+ * Profile slot: explain/ridge. */
+int pcr_explain_ridge(pcr_solver *s, const pcr_dataset *train, int64_t n, const int32_t *users,
+                      int weighted, int nonneg, int L, const int32_t *lists, int E,
+                      int32_t *expl_item, double *expl_contrib, double *per_pair, double *per_user,
+                      pcr_explain_ridge_stats *stats);                                         /* [device] */
 
 /* per-kernel device timing (HIP events on the solver's stream, one pair per launch).
  * slot names: "<class>/<workgroup size>[.<length bound>][g][c][l][r][#n]" for the per-user kernels (classes

@@ -16,7 +16,8 @@ from .api import (PCR_F32, PCR_F64, PCR_REC_EXCLUDE_TRAIN, PCR_RECOMMEND_MAX_K, 
                   fold_in_nnls, recommend_new_users_nnls, nnls_form, NnlsStats, PCR_NNLS_FIELDS, PCR_NNLS_DIRECT, PCR_NNLS_CG, PCR_NNLS_OK, PCR_NNLS_SINGULAR, PCR_NNLS_CAP, PCR_NNLS_PIVOT_CAP,
                   fold_in_items, itemfold_boundaries, rater_scores_boundaries, ItemfoldStats, PCR_ITEMFOLD_FIELDS, PCR_ITEMFOLD_WAVE_MAX, PCR_ITEMFOLD_LDS_MAX,
                   PCR_ITEMFOLD_SCORES_WAVE_MAX, user_weights, PCR_WEIGHT_UNIFORM, PCR_WEIGHT_PAIRS, PCR_WEIGHT_RATINGS,
-                  explain, explain_boundaries, ExplainStats, PCR_EXPLAIN_MAX_L, PCR_EXPLAIN_MAX_E, PCR_EXPLAIN_PAIR_FIELDS, PCR_EXPLAIN_USER_FIELDS, EXPLAIN_TILE, EXPLAIN_CHUNK)
+                  explain, explain_boundaries, ExplainStats, PCR_EXPLAIN_MAX_L, PCR_EXPLAIN_MAX_E, PCR_EXPLAIN_PAIR_FIELDS, PCR_EXPLAIN_USER_FIELDS, EXPLAIN_TILE, EXPLAIN_CHUNK,
+                  explain_ridge, explain_ridge_boundaries, ExplainRidgeStats, PCR_EXPLAIN_RIDGE_USER_FIELDS)
 
 __all__ = ["PCR_F32", "PCR_F64", "PCR_REC_EXCLUDE_TRAIN", "PCR_RECOMMEND_MAX_K", "PCR_TOPN_MAX_CUTOFFS", "PCR_RERANK_MAX_THETAS", "PCR_SOLVER_CCDR1", "PCR_SOLVER_PCR", "PCR_SOLVER_PCRPP", "CcdParameter", "Dataset", "Parameter", "PcrError",
            "Solver", "comm_unique_id", "initial", "initial_col", "initial_rows", "lib", "lib_path", "use_library", "model_load", "model_save", "partition_users", "predict", "recommend", "recommend_diverse", "recommend_capped", "CapStats", "PCR_CAP_EXACT", "PCR_CAP_POOL_EXHAUSTED", "evaluate_topn", "TOPN_FIELDS", "evaluate_ranks", "RankStats", "RANK_FIELDS", "sample_negatives", "PCR_RANK_STAGE", "PCR_CAND_RANK_STAGE", "evaluate_diversity", "DiversityStats", "DIVERSITY_FIELDS", "exposure_stats", "evaluate_lists", "evaluate_rerank", "tune", "tuned", "fold_in", "recommend_new_users", "foldin_boundaries", "FoldinStats",
@@ -25,4 +26,5 @@ __all__ = ["PCR_F32", "PCR_F64", "PCR_REC_EXCLUDE_TRAIN", "PCR_RECOMMEND_MAX_K",
            "fold_in_nnls", "recommend_new_users_nnls", "nnls_form", "NnlsStats", "PCR_NNLS_FIELDS", "PCR_NNLS_DIRECT", "PCR_NNLS_CG", "PCR_NNLS_OK", "PCR_NNLS_SINGULAR", "PCR_NNLS_CAP", "PCR_NNLS_PIVOT_CAP",
            "fold_in_items", "itemfold_boundaries", "rater_scores_boundaries", "ItemfoldStats", "PCR_ITEMFOLD_FIELDS", "PCR_ITEMFOLD_WAVE_MAX", "PCR_ITEMFOLD_LDS_MAX",
            "PCR_ITEMFOLD_SCORES_WAVE_MAX", "user_weights", "PCR_WEIGHT_UNIFORM", "PCR_WEIGHT_PAIRS", "PCR_WEIGHT_RATINGS",
-           "explain", "explain_boundaries", "ExplainStats", "PCR_EXPLAIN_MAX_L", "PCR_EXPLAIN_MAX_E", "PCR_EXPLAIN_PAIR_FIELDS", "PCR_EXPLAIN_USER_FIELDS", "EXPLAIN_TILE", "EXPLAIN_CHUNK"]
+           "explain", "explain_boundaries", "ExplainStats", "PCR_EXPLAIN_MAX_L", "PCR_EXPLAIN_MAX_E", "PCR_EXPLAIN_PAIR_FIELDS", "PCR_EXPLAIN_USER_FIELDS", "EXPLAIN_TILE", "EXPLAIN_CHUNK",
+           "explain_ridge", "explain_ridge_boundaries", "ExplainRidgeStats", "PCR_EXPLAIN_RIDGE_USER_FIELDS"]

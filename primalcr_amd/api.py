@@ -44,6 +44,9 @@ PCR_EXPLAIN_MAX_L, PCR_EXPLAIN_MAX_E = 128, 16
 PCR_EXPLAIN_PAIR_FIELDS = ("score", "support", "opposition", "residual")
 PCR_EXPLAIN_USER_FIELDS = ("ratings", "loss", "gnorm2")
 EXPLAIN_TILE, EXPLAIN_CHUNK = 16, 256
+# explain_ridge(): its per_user columns (status: PCR_RIDGE_OK / PCR_RIDGE_SINGULAR) and the ratings its Gram build stages at a time
+PCR_EXPLAIN_RIDGE_USER_FIELDS = ("ratings", "free", "loss", "dist2", "status")
+EXPLAIN_RIDGE_STAGE = 16
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -157,6 +160,12 @@ class NnlsStats(C.Structure):
 class ExplainStats(C.Structure):
     """pcr_explain_stats."""
     _fields_ = [("users", C.c_int64), ("pairs", C.c_int64), ("contributors", C.c_int64), ("residual_abs_max", C.c_double)]
+
+
+class ExplainRidgeStats(C.Structure):
+    """pcr_explain_ridge_stats."""
+    _fields_ = [("users", C.c_int64), ("pairs", C.c_int64), ("contributors", C.c_int64), ("singular", C.c_int64),
+                ("residual_abs_max", C.c_double)]
 
 
 _LOG_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p)
@@ -274,6 +283,9 @@ def lib():
     if _LIB_OVERRIDE is None or hasattr(L, "pcr_explain"):
         L.pcr_explain_model.argtypes = [C.POINTER(Parameter), vp, i64, i64, vp, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp]
         L.pcr_explain.argtypes = [vp, vp, i64, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp]
+    if _LIB_OVERRIDE is None or hasattr(L, "pcr_explain_ridge"):
+        L.pcr_explain_ridge_model.argtypes = [vp, i64, i64, cd, ci, ci, ci, ci, i64, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp]
+        L.pcr_explain_ridge.argtypes = [vp, vp, i64, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp]
     L.pcr_exposure_stats.argtypes = [vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(cd), C.POINTER(cd)]
     L.pcr_profile_enable.argtypes = [vp, ci]
     L.pcr_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(cd), C.POINTER(i64)]
@@ -898,10 +910,10 @@ def explain_boundaries():
     return {"rows": rows, "lists": [EXPLAIN_TILE * t for t in range(1, PCR_EXPLAIN_MAX_L // EXPLAIN_TILE + 1)]}
 
 
-def _explain_call(n, lists, top, weights, per_pair, per_user, fn):
-    """Shared by explain() and Solver.explain(): the list / weight / output buffers around fn(weights pointer, L, lists pointer, E,
-    expl_item, expl_contrib, per_pair, per_user, stats pointers); returns (items int32 [n, L, E], contrib float64 [n, L, E], stats
-    dict[, per_pair float64 [n, L, 4]][, per_user float64 [n, 3]])."""
+def _explain_call(n, lists, top, weights, per_pair, per_user, fn, stats_type=ExplainStats, user_fields=PCR_EXPLAIN_USER_FIELDS):
+    """Shared by explain(), explain_ridge() and the Solver methods: the list / weight / output buffers around fn(weights pointer, L,
+    lists pointer, E, expl_item, expl_contrib, per_pair, per_user, stats pointers); returns (items int32 [n, L, E], contrib float64
+    [n, L, E], stats dict[, per_pair float64 [n, L, 4]][, per_user float64 [n, len(user_fields)]])."""
     lists = np.ascontiguousarray(lists, np.int32)
     if lists.ndim != 2 or lists.shape[0] != n:
         raise ValueError(f"lists must be [n, L] with n = {n}")
@@ -913,11 +925,11 @@ def _explain_call(n, lists, top, weights, per_pair, per_user, fn):
     Lb, Eb = max(L, 1), min(max(E, 1), 1024)
     items = np.empty((n, Lb, Eb), np.int32); contrib = np.empty((n, Lb, Eb), np.float64)
     pp = np.empty((n, Lb, len(PCR_EXPLAIN_PAIR_FIELDS)), np.float64) if per_pair else None
-    pu = np.empty((n, len(PCR_EXPLAIN_USER_FIELDS)), np.float64) if per_user else None
-    st = ExplainStats()
+    pu = np.empty((n, len(user_fields)), np.float64) if per_user else None
+    st = stats_type()
     _chk(fn(None if weights is None else weights.ctypes.data, L, lists.ctypes.data, E, items.ctypes.data, contrib.ctypes.data,
             None if pp is None else pp.ctypes.data, None if pu is None else pu.ctypes.data, C.addressof(st)))
-    out = (items, contrib, {f: getattr(st, f) for f, _ in ExplainStats._fields_})
+    out = (items, contrib, {f: getattr(st, f) for f, _ in stats_type._fields_})
     return out + ((pp,) if per_pair else ()) + ((pu,) if per_user else ())
 
 
@@ -941,6 +953,44 @@ def explain(V, ratings, U, lists, lam, top=5, solver_type=PCR_SOLVER_PCRPP, weig
     return _explain_call(n, lists, top, weights, per_pair, per_user, lambda wp, L, lp, E, ip, cp, pp, up, sp: lib().pcr_explain_model(
         C.byref(p), V.ctypes.data, V.shape[0], n, index.ctypes.data, item.ctypes.data, val.ctypes.data, U.ctypes.data, wp, L, lp, E, ip, cp, pp, up,
         sp))
+
+
+def explain_ridge_boundaries(k):
+    """The row lengths R at which explain_ridge() changes its code path between R and R + 1 ratings at rank k -- no ratings /
+    some, the first multiples of the 16 ratings its Gram build stages at a time, and of its rating chunk -- and the list lengths at
+    which it starts another tile: a dict with "rows" and "lists".  The kernel has one workgroup form for every length and rank."""
+    rows = sorted({0, EXPLAIN_RIDGE_STAGE, 2 * EXPLAIN_RIDGE_STAGE, EXPLAIN_CHUNK, 2 * EXPLAIN_CHUNK})
+    return {"rows": rows, "lists": [EXPLAIN_TILE * t for t in range(1, PCR_EXPLAIN_MAX_L // EXPLAIN_TILE + 1)]}
+
+
+def _explain_ridge_call(n, lists, top, per_pair, per_user, fn):
+    return _explain_call(n, lists, top, None, per_pair, per_user, lambda wp, L, lp, E, ip, cp, pp, up, sp: fn(L, lp, E, ip, cp, pp, up, sp),
+                         stats_type=ExplainRidgeStats, user_fields=PCR_EXPLAIN_RIDGE_USER_FIELDS)
+
+
+def explain_ridge(F, ratings, U, lists, lam, top=5, weighted=True, nonneg=False, dtype=PCR_F64, device=0, per_pair=False, per_user=False):
+    """Why each listed item scores as it does for a squared-loss (CCDR1 / ridge) row, on the GPU (pcr_explain_ridge_model): with
+    A = F[I] the user's rated rows, mu = lam * len (weighted) or lam, and G = A^T A + mu I, the exact minimiser is u* = G^-1 A^T r
+    and v_j . u* = sum_p r_p (v_{i_p} . G^-1 v_j): one signed contribution per rated item.  score = v_j . u for the given row u,
+    residual = v_j . (u - u*).  nonneg: the system is restricted to the coordinates where the row is > 0 (a row trained with -N 1
+    or returned by fold_in_nnls).  U [n, k]: the rows to explain, or None: the minimiser itself (residual exactly 0; not with
+    nonneg).  ratings, lists, top and the result as explain(); F = U of a model with an item-major CSR explains item rows by their
+    raters.  Returns (items int32 [n, L, top], contrib float64 [n, L, top], stats dict[, per_pair float64 [n, L, 4] of
+    PCR_EXPLAIN_PAIR_FIELDS][, per_user float64 [n, 5] of PCR_EXPLAIN_RIDGE_USER_FIELDS])."""
+    F = np.ascontiguousarray(F, np.float64)
+    if F.ndim != 2:
+        raise ValueError("F must be [rows, k]")
+    index, item, val = _foldin_ratings(ratings)
+    n, k = index.shape[0] - 1, F.shape[1]
+    if U is not None:
+        U = np.ascontiguousarray(U, np.float64)
+        if U.shape != (n, k):
+            raise ValueError(f"U must be [n, k] = [{n}, {k}] (or None: the exact minimiser is explained)")
+    elif nonneg:
+        raise ValueError("nonneg needs the rows U: the free set is read from them")
+    return _explain_ridge_call(n, lists, top, per_pair, per_user, lambda L, lp, E, ip, cp, pp, up, sp: lib().pcr_explain_ridge_model(
+        F.ctypes.data, F.shape[0], k, float(lam), 1 if weighted else 0, 1 if nonneg else 0, int(dtype), int(device), n, index.ctypes.data,
+        item.ctypes.data, val.ctypes.data, None if U is None else U.ctypes.data, L, lp, E, ip, cp, pp, up, sp))
 
 
 def itemfold_boundaries(k=None, dtype=PCR_F64):
@@ -1545,6 +1595,23 @@ class Solver:
             weights = mine if users is None else mine[users]
         return _explain_call(n, lists, top, weights, per_pair, per_user, lambda wp, L, lp, E, ip, cp, pp, up, sp: lib().pcr_explain(
             self._h, ds._h, n, None if users is None else users.ctypes.data, wp, L, lp, E, ip, cp, pp, up, sp))
+
+    def explain_ridge(self, lists, users=None, train=None, top=5, weighted=True, nonneg=False, per_pair=False, per_user=False):
+        """Why each listed item scores as it does for this solver's users as squared-loss rows, from its device U and V
+        (pcr_explain_ridge), in its storage type and with its lambda; CCDR1 is the intended solver, any single-rank one runs;
+        lists, top, weighted, nonneg and the result as explain_ridge().  users: GLOBAL 0-based ids (None: all of them, in order).
+        train (None: the Dataset the solver was created from) supplies the rows and their rating values and must be that data
+        set.  nonneg is the caller's: -N is not read from the solver.  A multi-rank or shard solver: PcrError; nothing of the solver
+        is written."""
+        ds = self.ds if train is None else train
+        if not isinstance(ds, Dataset):
+            raise ValueError("train must be a Dataset (the one the solver was created from)")
+        if users is not None:
+            users = np.ascontiguousarray(users, np.int32)
+        n = self.n_users if users is None else users.shape[0]
+        return _explain_ridge_call(n, lists, top, per_pair, per_user, lambda L, lp, E, ip, cp, pp, up, sp: lib().pcr_explain_ridge(
+            self._h, ds._h, n, None if users is None else users.ctypes.data, 1 if weighted else 0, 1 if nonneg else 0, L, lp, E, ip, cp, pp, up,
+            sp))
 
     def fold_in_ridge(self, ratings, weighted=True, per_user=False):
         """Squared-loss factors for users this solver was not trained on, against its device V (pcr_fold_in_ridge), in its storage

@@ -90,6 +90,14 @@
 //                    training ratings the model was trained on), -l (its regulariser) and -K <= PCR_EXPLAIN_MAX_L; -s as
 //                    --fold-in's.  Goes with the plain list (and --allow) only: refused with --eval, --diversity, --mmr,
 //                    --tradeoff, --ranks, any --fold-in*, --groups and --candidates
+//   omp-pmf-recommend --explain-ridge file [--top E] -x data_dir -l lambda [--plain-reg] [--nonneg] [--allow items_file] [-K topk] [-u users_file] [--f32] [--scores] model_file output_file
+//     --explain-ridge file  the same for a squared-loss (CCDR1, -s 0) model (pcr_explain_ridge_model): the contributions are
+//                    rating x the similarity of the rated and the listed item through the inverse of the user's regularised
+//                    Gram matrix, the residual is the distance of the model's row from the exact minimiser.  Output format,
+//                    --top, -x, -l and -K as --explain's; the regulariser is weighted by each user's rating count as in CCDR1
+//                    training, --plain-reg: the plain lambda |u|^2; --nonneg: a model trained with -N 1 (the system is
+//                    restricted to the coordinates where the row is > 0).  No -s, no --steps; not together with --explain;
+//                    refused with what --explain is refused with
 // Output: one line per user, in input order: the 1-based user id, then the 1-based item ids (padding is left out).  Users go
 // to the device in batches, so host memory for the lists stays bounded on any catalogue.
 // With --eval: stdout gets one line per cutoff, "cutoff c users n users_graded n hits n precision x recall x hit_rate x map x
@@ -183,7 +191,12 @@ static const char* USAGE =
     "                   it1:c1 it2:c2 ...\": the score split into the contributions of the user's own rated items (the --top E largest,\n"
     "                   default 5, 1 .. 16) and a residual that is 0 at a converged row; needs -x (the training ratings), -l (the\n"
     "                   model's lambda) and -K <= 128; -s 1|2 as --fold-in; with the plain list and --allow only: not with --eval,\n"
-    "                   --diversity, --mmr, --tradeoff, --ranks, --fold-in*, --groups or --candidates\n";
+    "                   --diversity, --mmr, --tradeoff, --ranks, --fold-in*, --groups or --candidates\n"
+    "       omp-pmf-recommend --explain-ridge file [--top E] -x data_dir -l lambda [--plain-reg] [--nonneg] [--allow items_file] [-K topk] [-u users_file] [--f32] [--scores] model_file output_file\n"
+    "    --explain-ridge file  the same for a squared-loss (CCDR1) model: rating x similarity through the inverse of the user's\n"
+    "                   regularised Gram matrix, and the residual to the exact minimiser; output, --top, -x, -l and -K as --explain;\n"
+    "                   the regulariser is weighted by the user's rating count, --plain-reg: the plain lambda |u|^2; --nonneg: a\n"
+    "                   model trained with -N 1; no -s, no --steps; not with --explain, nor with what --explain is refused with\n";
 
 static int usage() { printf("%s", USAGE); return 1; }
 
@@ -629,7 +642,8 @@ static bool read_groups(const char* path, int64_t d2, std::vector<int32_t>& grou
 // and list position to fp
 static bool explain_batch(FILE* fp, const std::vector<double>& U, const std::vector<double>& V, int64_t d2, int64_t k,
                           const std::vector<int64_t>& xindex, const std::vector<int32_t>& xitem, const std::vector<double>& xval,
-                          const int32_t* users, int64_t m, int K, const std::vector<int32_t>& items, int top, double lambda, int solver, bool f32) {
+                          const int32_t* users, int64_t m, int K, const std::vector<int32_t>& items, int top, double lambda, int solver, bool f32,
+                          bool ridge, bool weighted, bool nonneg) {
     std::vector<int64_t> index((size_t)m + 1, 0);
     for (int64_t i = 0; i < m; ++i) index[(size_t)i + 1] = index[(size_t)i] + (xindex[(size_t)users[i] + 1] - xindex[(size_t)users[i]]);
     std::vector<int32_t> item((size_t)index[(size_t)m]);
@@ -645,9 +659,12 @@ static bool explain_batch(FILE* fp, const std::vector<double>& U, const std::vec
     prm.k = (int)k; prm.lambda = lambda; prm.solver_type = solver; prm.precision = f32 ? PCR_F32 : PCR_F64;
     std::vector<int32_t> ei((size_t)(m * K * top));
     std::vector<double> ec((size_t)(m * K * top)), pp((size_t)(m * K * PCR_EXPLAIN_PAIR_FIELDS));
-    if (pcr_explain_model(&prm, V.data(), d2, m, index.data(), item.data(), val.data(), Ub.data(), nullptr, K, items.data(), top, ei.data(),
-                          ec.data(), pp.data(), nullptr, nullptr) != PCR_OK) {
-        fprintf(stderr, "explain: %s\n", pcr_last_error());
+    const int rc = ridge ? pcr_explain_ridge_model(V.data(), d2, k, lambda, weighted ? 1 : 0, nonneg ? 1 : 0, prm.precision, 0, m, index.data(), item.data(),
+                                                   val.data(), Ub.data(), K, items.data(), top, ei.data(), ec.data(), pp.data(), nullptr, nullptr)
+                         : pcr_explain_model(&prm, V.data(), d2, m, index.data(), item.data(), val.data(), Ub.data(), nullptr, K, items.data(), top,
+                                             ei.data(), ec.data(), pp.data(), nullptr, nullptr);
+    if (rc != PCR_OK) {
+        fprintf(stderr, "%s: %s\n", ridge ? "explain-ridge" : "explain", pcr_last_error());
         return false;
     }
     for (int64_t i = 0; i < m; ++i)
@@ -690,15 +707,20 @@ int main(int argc, char** argv) {
     double lambda = 0.0;
     bool have_lambda = false, have_s = false, have_steps = false;
     int solver = PCR_SOLVER_PCRPP, steps = 10;
-    const char* efile = nullptr;                                   // --explain
+    const char* efile = nullptr;                                   // --explain, --explain-ridge
+    bool eridge = false, eboth = false, nonneg = false;            // --explain-ridge (eboth: given with --explain), --nonneg
     int top = 0;                                                   // --top (0: not given)
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
-        if (!strcmp(a, "--explain")) {
+        if (!strcmp(a, "--explain") || !strcmp(a, "--explain-ridge")) {
             if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
+            const bool r = a[9] != 0;
+            if (efile && r != eridge) eboth = true;
             efile = argv[++i];
+            eridge = r;
             continue;
         }
+        if (!strcmp(a, "--nonneg")) { nonneg = true; continue; }
         if (!strcmp(a, "--top")) {
             if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
             const char* v = argv[++i];
@@ -831,7 +853,20 @@ int main(int argc, char** argv) {
     const bool tradeoff = !thetas.empty();
     const bool capped = gfile || max_per_group;                    // (the plain list's flow with pcr_recommend_capped_model)
     if (top && !efile) { fprintf(stderr, "--top goes with --explain\n"); return 1; }
-    if (efile) {                                                   // (the plain list's flow, then pcr_explain_model on its lists)
+    if (eboth) { fprintf(stderr, "--explain-ridge does not go with --explain\n"); return 1; }
+    if (nonneg && !eridge) { fprintf(stderr, "--nonneg goes with --explain-ridge\n"); return 1; }
+    if (eridge) {                                                  // (--explain's flow with pcr_explain_ridge_model)
+        if (edir || diversity || mmr || tradeoff || with_ranks || ifile || fdir || rdir || ndir || capped || cfile) {
+            fprintf(stderr, "--explain-ridge does not go with --eval, --diversity, --mmr, --tradeoff, --ranks, --fold-in*, --groups or --candidates\n");
+            return 1;
+        }
+        if (!xdir) { fprintf(stderr, "--explain-ridge needs -x data_dir (the training ratings)\n"); return 1; }
+        if (!have_lambda) { fprintf(stderr, "--explain-ridge needs -l lambda\n"); return 1; }
+        if (!(lambda > 0.0)) { fprintf(stderr, "-l %g: must be > 0 with --explain-ridge\n", lambda); return 1; }
+        if (have_s || have_steps) { fprintf(stderr, "--explain-ridge takes no -s and no --steps\n"); return 1; }
+        if (K > PCR_EXPLAIN_MAX_L) { fprintf(stderr, "-K %d: --explain-ridge takes lists of at most %d items\n", K, PCR_EXPLAIN_MAX_L); return 1; }
+        if (!top) top = 5;
+    } else if (efile) {                                            // (the plain list's flow, then pcr_explain_model on its lists)
         if (edir || diversity || mmr || tradeoff || with_ranks || ifile || fdir || rdir || ndir || capped || cfile) {
             fprintf(stderr, "--explain does not go with --eval, --diversity, --mmr, --tradeoff, --ranks, --fold-in*, --groups or --candidates\n");
             return 1;
@@ -1025,7 +1060,7 @@ int main(int argc, char** argv) {
             *p++ = '\n';
         }
         ok = fwrite(o.data(), 1, (size_t)(p - o.data()), out_fp) == (size_t)(p - o.data());
-        if (ex_fp && ok && !explain_batch(ex_fp, U, V, d2, k, xindex, xitem, xval, users.data() + b0, m, K, items, top, lambda, solver, f32)) {
+        if (ex_fp && ok && !explain_batch(ex_fp, U, V, d2, k, xindex, xitem, xval, users.data() + b0, m, K, items, top, lambda, solver, f32, eridge, !plain_reg, nonneg)) {
             fclose(out_fp); fclose(ex_fp);
             return 1;
         }

@@ -18,6 +18,8 @@
 //      tile position in ascending row position.
 //   3  plain stores.  e_p(j) is never materialised beyond one chunk x one tile.
 // Every loop has a static bound, nothing is exchanged between workgroups, no atomics.
+// Stage 2's pieces -- block_dots, explain_merge, explain_store_top, explain_store_padding -- are workgroup functions:
+// k_explain_ridge (pcr_explain_ridge.h) runs the same ones on its fp64 columns.
 #pragma once
 #include <type_traits>
 
@@ -81,14 +83,27 @@ __device__ __forceinline__ void block_gradient(const T* __restrict__ M, const in
     }
 }
 
-// ebuf[(p - p0) * EXPLAIN_TILE + jj] = scale[p] * (M[rows[p]] . tile[jj]) in fp64 for p in [p0, p1), jj < EXPLAIN_TILE, with
-// scale[p] = -(c[p] / lam).  G lanes per row as block_sddmm: a lane loads ITS 16-byte chunk of the row once (global_load_dwordx4)
-// and meets the same chunk of the 16 staged rows (ds_read_b128: the G lanes of a group read consecutive slots, the other
-// groups of the wave the same addresses -- a broadcast, no bank conflict); a wide row's next chunk is in flight meanwhile.  The 16
-// partial dots are summed over the group by two group_reduce8 (G >= 8) or butterflies.  tile: LDS, EXPLAIN_TILE rows of ld.
-template <typename T, int BLOCK>
-__device__ __forceinline__ void block_dots(const T* __restrict__ M, const int32_t* rows, const double* c, double lam, int p0, int p1,
-                                           const T* tile, double* ebuf, const Geo& geo) {
+// ebuf[(p - p0) * EXPLAIN_TILE + jj] = scale(p) * (M[rows[p]] . tile[jj]) in fp64 for p in [p0, p1), jj < EXPLAIN_TILE (k_explain:
+// scale(p) = -(c[p] / lam); k_explain_ridge: the rating r_p).  G lanes per row as block_sddmm: a lane loads ITS 16-byte chunk of
+// the row once (global_load_dwordx4) and meets the same columns of the 16 staged rows (ds_read_b128: the G lanes of a group read
+// consecutive slots, the other groups of the wave the same addresses -- a broadcast, no bank conflict); a wide row's next chunk is
+// in flight meanwhile.  The 16 partial dots are summed over the group by two group_reduce8 (G >= 8) or butterflies.  tile: LDS,
+// EXPLAIN_TILE rows of tld values of TT -- the storage type T (rows of the factor as they are) or double (k_explain_ridge's solved
+// columns; tld even); at least geo.ld of them per row are read.  rows and what scale reads may be LDS or global.
+template <typename TT, int VEC>
+__device__ __forceinline__ void tile_chunk(const TT* p, double (&out)[VEC]) {
+    typedef TT nat __attribute__((ext_vector_type(16 / sizeof(TT))));
+    constexpr int PER = 16 / sizeof(TT);
+#pragma unroll
+    for (int h = 0; h < VEC / PER; ++h) {
+        const nat v = *((const PCR_LDS nat*)p + h);
+#pragma unroll
+        for (int e = 0; e < PER; ++e) out[h * PER + e] = (double)v[e];
+    }
+}
+template <typename T, int BLOCK, typename TT, class Scale>
+__device__ __forceinline__ void block_dots(const T* __restrict__ M, const int32_t* rows, Scale scale_of, int p0, int p1, const TT* tile, int tld,
+                                           double* ebuf, const Geo& geo) {
     typedef typename VecOf<T>::type V;
     constexpr int VEC = VecOf<T>::N;
     const int G = geo.G, g = threadIdx.x & (G - 1), grp = threadIdx.x / G, ngrp = BLOCK / G;
@@ -109,17 +124,19 @@ __device__ __forceinline__ void block_dots(const T* __restrict__ M, const int32_
             if (act) {
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
-                    const V ta = lds_load_vec(tile + q * geo.ld + ch * VEC), tb = lds_load_vec(tile + (q + 8) * geo.ld + ch * VEC);
+                    double ta[VEC], tb[VEC];
+                    tile_chunk<TT, VEC>(tile + q * tld + ch * VEC, ta);
+                    tile_chunk<TT, VEC>(tile + (q + 8) * tld + ch * VEC, tb);
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) {
-                        pa[q] += (double)velem(cur, e) * (double)velem(ta, e);
-                        pb[q] += (double)velem(cur, e) * (double)velem(tb, e);
+                        pa[q] += (double)velem(cur, e) * ta[e];
+                        pb[q] += (double)velem(cur, e) * tb[e];
                     }
                 }
             }
             cur = nxt;
         }
-        const double scale = -(c[row] / lam);
+        const double scale = scale_of(row);
         double* out = ebuf + (size_t)(row - p0) * EXPLAIN_TILE;
         if (G >= 8) {                                             // whole lane groups are active here
             const double ta = group_reduce8<double>(pa, g, G), tb = group_reduce8<double>(pb, g, G);
@@ -138,6 +155,65 @@ __device__ __forceinline__ void block_dots(const T* __restrict__ M, const int32_
 
 // (e, position) a precedes b in a contributor list: e descending, equal e by ascending position
 __device__ __forceinline__ bool explain_before(double ea, int pa, double eb, int pb) { return ea > eb || (ea == eb && pa < pb); }
+
+// The running top-E of the EXPLAIN_TILE tile positions: two images of 16 slots per position (values, row positions), the
+// current one first, and the entries it holds
+struct ExplainTop {
+    double *tv, *tvn;
+    int32_t *tp, *tpn;
+    int have;
+};
+// One chunk of contributions ebuf[cn][EXPLAIN_TILE] (row positions p0 ...) into the running top-E of tile positions < tl, and
+// into the support / opposition of tile position threadIdx.x (< tl).  Rank counting: the chunk's entries and the running ones
+// are the candidates of every tile position; ranks under explain_before are distinct, so every slot of the other image has one
+// writer.  The caller's barrier stands before (ebuf complete) and after (the images swapped).
+template <int BLOCK>
+__device__ __forceinline__ void explain_merge(const double* ebuf, int p0, int cn, int tl, int E, ExplainTop& top, double& sup, double& opp) {
+    const int tid = threadIdx.x, have = top.have;
+    const double* tv = top.tv;
+    const int32_t* tp = top.tp;
+    for (int x = tid; x < (cn + have) * EXPLAIN_TILE; x += BLOCK) {
+        const int cand = x / EXPLAIN_TILE, jj = x - cand * EXPLAIN_TILE;
+        if (jj >= tl) continue;
+        const bool fresh = cand < cn;
+        const double e = fresh ? ebuf[cand * EXPLAIN_TILE + jj] : tv[jj * 16 + cand - cn];
+        const int pos = fresh ? p0 + cand : tp[jj * 16 + cand - cn];
+        int rank = 0;
+        for (int q = 0; q < have && rank < E; ++q) rank += explain_before(tv[jj * 16 + q], tp[jj * 16 + q], e, pos) ? 1 : 0;
+        for (int q = 0; q < cn && rank < E; ++q) rank += explain_before(ebuf[q * EXPLAIN_TILE + jj], p0 + q, e, pos) ? 1 : 0;
+        if (rank < E) { top.tvn[jj * 16 + rank] = e; top.tpn[jj * 16 + rank] = pos; }
+    }
+    if (tid < tl) {
+        for (int q = 0; q < cn; ++q) {
+            const double e = ebuf[q * EXPLAIN_TILE + tid];
+            if (e > 0.0) sup += e; else if (e < 0.0) opp += e;
+        }
+    }
+    top.have = min(E, have + cn);
+    { double* a = top.tv; top.tv = top.tvn; top.tvn = a; int32_t* b = top.tp; top.tp = top.tpn; top.tpn = b; }
+}
+// the finished top-E of tile positions < tl to out_item / out_contrib [tl][E] (itm: the row's items, LDS or global); (-1, 0.0)
+// beyond the entries held
+template <int BLOCK>
+__device__ __forceinline__ void explain_store_top(const ExplainTop& top, const int32_t* itm, int tl, int E, int32_t* __restrict__ out_item,
+                                                  double* __restrict__ out_contrib) {
+    for (int x = threadIdx.x; x < tl * E; x += BLOCK) {
+        const int jj = x / E, r = x - jj * E;
+        const bool ok = r < top.have;
+        out_item[x] = ok ? itm[top.tp[jj * 16 + r]] : -1;
+        out_contrib[x] = ok ? top.tv[jj * 16 + r] : 0.0;
+    }
+}
+// list positions [Lu, L) of a user are padding: (-1, 0.0) contributors and NaN in the per_pair fields (base: the user's first)
+template <int BLOCK>
+__device__ __forceinline__ void explain_store_padding(int Lu, int L, int E, int32_t* __restrict__ item_base, double* __restrict__ contrib_base,
+                                                      double* __restrict__ pair_base) {
+    for (int x = threadIdx.x; x < (L - Lu) * E; x += BLOCK) {
+        item_base[(size_t)Lu * E + x] = -1; contrib_base[(size_t)Lu * E + x] = 0.0;
+    }
+    if (pair_base)
+        for (int x = threadIdx.x; x < (L - Lu) * PCR_EXPLAIN_PAIR_FIELDS; x += BLOCK) pair_base[(size_t)Lu * PCR_EXPLAIN_PAIR_FIELDS + x] = __builtin_nan("");
+}
 
 template <typename T, int BLOCK, bool BIG>
 __global__ __launch_bounds__(BLOCK) void k_explain(FoldinCsr X, Geo geo, const int32_t* __restrict__ users, int nusers, const T* __restrict__ Um,
@@ -235,56 +311,24 @@ __global__ __launch_bounds__(BLOCK) void k_explain(FoldinCsr X, Geo geo, const i
                 if (q == 0) { tile_u[jj] = a; tile_g[jj] = b; }
             }
             double sup = 0.0, opp = 0.0;                            // of tile position tid (tid < tl)
-            int have = 0;
-            double *tv = topv0, *tvn = topv1;
-            int32_t *tp = topp0, *tpn = topp1;
+            ExplainTop top = {topv0, topv1, topp0, topp1, 0};
             for (int p0 = 0; p0 < n; p0 += EXPLAIN_CHUNK) {
-                const int p1 = min(n, p0 + EXPLAIN_CHUNK), cn = p1 - p0;
+                const int p1 = min(n, p0 + EXPLAIN_CHUNK);
                 __syncthreads();
-                block_dots<T, BLOCK>(Vm, itm, cc, lam, p0, p1, tile, ebuf, geo);
+                block_dots<T, BLOCK>(Vm, itm, [&](int p) { return -(cc[p] / lam); }, p0, p1, tile, ld, ebuf, geo);
                 __syncthreads();
-                // rank counting: the chunk's entries and the running ones are the candidates of every tile position
-                for (int x = tid; x < (cn + have) * EXPLAIN_TILE; x += BLOCK) {
-                    const int cand = x / EXPLAIN_TILE, jj = x - cand * EXPLAIN_TILE;
-                    if (jj >= tl) continue;
-                    const bool fresh = cand < cn;
-                    const double e = fresh ? ebuf[cand * EXPLAIN_TILE + jj] : tv[jj * 16 + cand - cn];
-                    const int pos = fresh ? p0 + cand : tp[jj * 16 + cand - cn];
-                    int rank = 0;
-                    for (int q = 0; q < have && rank < E; ++q) rank += explain_before(tv[jj * 16 + q], tp[jj * 16 + q], e, pos) ? 1 : 0;
-                    for (int q = 0; q < cn && rank < E; ++q) rank += explain_before(ebuf[q * EXPLAIN_TILE + jj], p0 + q, e, pos) ? 1 : 0;
-                    if (rank < E) { tvn[jj * 16 + rank] = e; tpn[jj * 16 + rank] = pos; }
-                }
-                if (tid < tl) {
-                    for (int q = 0; q < cn; ++q) {
-                        const double e = ebuf[q * EXPLAIN_TILE + tid];
-                        if (e > 0.0) sup += e; else if (e < 0.0) opp += e;
-                    }
-                }
-                have = min(E, have + cn);
-                { double* a = tv; tv = tvn; tvn = a; int32_t* b = tp; tp = tpn; tpn = b; }
+                explain_merge<BLOCK>(ebuf, p0, p1 - p0, tl, E, top, sup, opp);
             }
             __syncthreads();
-            for (int x = tid; x < tl * E; x += BLOCK) {
-                const int jj = x / E, r = x - jj * E;
-                const size_t o = ((size_t)u * L + l0 + jj) * E + r;
-                const bool ok = r < have;
-                expl_item[o] = ok ? itm[tp[jj * 16 + r]] : -1;
-                expl_contrib[o] = ok ? tv[jj * 16 + r] : 0.0;
-            }
+            explain_store_top<BLOCK>(top, itm, tl, E, expl_item + ((size_t)u * L + l0) * E, expl_contrib + ((size_t)u * L + l0) * E);
             if (tid < tl && per_pair) {
                 double* o = per_pair + ((size_t)u * L + l0 + tid) * PCR_EXPLAIN_PAIR_FIELDS;
                 o[0] = tile_u[tid]; o[1] = sup; o[2] = opp; o[3] = tile_g[tid] / lam;
             }
         }
         // ---- padding positions
-        for (int x = tid; x < (L - Lu) * E; x += BLOCK) {
-            const size_t o = ((size_t)u * L + Lu) * E + x;
-            expl_item[o] = -1; expl_contrib[o] = 0.0;
-        }
-        if (per_pair)
-            for (int x = tid; x < (L - Lu) * PCR_EXPLAIN_PAIR_FIELDS; x += BLOCK)
-                per_pair[((size_t)u * L + Lu) * PCR_EXPLAIN_PAIR_FIELDS + x] = __builtin_nan("");
+        explain_store_padding<BLOCK>(Lu, L, E, expl_item + (size_t)u * L * E, expl_contrib + (size_t)u * L * E,
+                                     per_pair ? per_pair + (size_t)u * L * PCR_EXPLAIN_PAIR_FIELDS : nullptr);
         __syncthreads();
     }
 }

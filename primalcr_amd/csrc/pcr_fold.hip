@@ -6,6 +6,7 @@
 //   pcr_fold_in_items    new items of a ranking model     k_rater_scores, k_itemfold (pcr_itemfold.h) "itemfold/scores", "itemfold/newton"
 // and, on fold-in's plan and forms, the explanation of listed items by a user's own ratings:
 //   pcr_explain          rows of a ranking model          k_explain (pcr_explain.h)                  "explain/contrib"
+//   pcr_explain_ridge    squared-loss rows                k_explain_ridge (pcr_explain_ridge.h)      "explain/ridge"
 // A run uploads its plan (pcr_host.cpp built and checked it), launches one kernel per workgroup form inside the family's profile
 // slot -- workgroups stride over their range, the longest rows first -- and hands the rows, the stats and the per-row records
 // back through one FoldOut.  Recommendation and its metrics are pcr_serve.hip, training is pcr_solver.hip.
@@ -13,6 +14,7 @@
 #include "pcr_dev.h"
 #include "pcr_foldin.h"
 #include "pcr_explain.h"
+#include "pcr_explain_ridge.h"
 #include "pcr_itemfold.h"
 #include "pcr_ridge.h"
 #include "pcr_nnls.h"
@@ -437,6 +439,58 @@ static int explain_run(const ServeView& v, int solver_type, double lambda, const
     return PCR_OK;
 }
 
+// Explanations of squared-loss rows (pcr_explain_ridge, pcr_explain_ridge_model; k_explain_ridge of pcr_explain_ridge.h) of the
+// plan's users against v's V: Um holds their rows of U (row urow[i] is user i's; NULL: row i) or is NULL (the minimiser itself is
+// explained).  The ratings and the order go to the device as ridge fold-in's, then ONE launch: the plan has one range, its LDS
+// sized by the rank and the longest user's chunk.
+struct ExplainRidgeOut { int32_t* item; double* contrib; double* per_pair; double* per_user; pcr_explain_ridge_stats* stats; };
+template <typename T>
+static int explain_ridge_run(const ServeView& v, double lambda, int weighted, int nonneg, const PcrRidgePlan& P, const T* Um, const int32_t* urow_host,
+                             int L, const int32_t* lists, int E, const ExplainRidgeOut& o) {
+    const int64_t n = P.X.d1;
+    hipStream_t st = v.st;
+    Geo geo;
+    geo.r = v.r; geo.ld = v.ld; geo.nchunk = v.ld / VecOf<T>::N; geo.G = std::min(64, host_pow2(geo.nchunk));
+    int cus = 0;
+    RC(device_cus(&cus));
+    const PcrRidgePlan::Range& g = P.ranges.at(0);
+    const int mp = g.tiles * 16;
+    if (g.block != 256 || mp < v.r || mp < 16 || mp > PCR_RIDGE_DIRECT_MAX || g.first != 0 || g.count != n) {
+        pcr_set_error("explain (ridge): a launch class outside the kernel's tile range");
+        return PCR_ERR_STATE;
+    }
+    const int32_t longest = P.order[0];
+    const int erows = (int)std::max<int64_t>(1, std::min<int64_t>(P.X.index[(size_t)longest + 1] - P.X.index[(size_t)longest], EXPLAIN_CHUNK));
+    const size_t lds = explain_ridge_bytes(mp, 256, erows);
+    if (lds > PCR_LDS_CU) { pcr_set_error("explain (ridge): rank " + std::to_string(v.r) + " is too large for the kernel's LDS"); return PCR_ERR_UNSUPPORTED; }
+    DBuf<int64_t> uptr;
+    DBuf<int32_t> item, order, urow, dlists, d_item;
+    DBuf<double> val, d_contrib, d_pair, d_user;
+    const size_t pairs = (size_t)n * L;
+    RC(uptr.upload(P.X.index, st)); RC(item.upload_n(P.X.item.data(), P.X.item.size())); RC(val.upload_n(P.X.val.data(), P.X.val.size()));
+    RC(order.upload(P.order, st)); RC(dlists.upload_n(lists, pairs));
+    if (urow_host) RC(urow.upload_n(urow_host, (size_t)n));
+    RC(d_item.alloc(pairs * E)); RC(d_contrib.alloc(pairs * E)); RC(d_pair.alloc(pairs * PCR_EXPLAIN_PAIR_FIELDS));
+    RC(d_user.alloc((size_t)n * PCR_EXPLAIN_RIDGE_USER_FIELDS));
+    const RidgeCsr X = {uptr.p, item.p, val.p};
+    {
+        ProfScope ps(v.prof, "explain/ridge", st);
+        RC(fold_launch(k_explain_ridge<T, 256>, fold_grid(n, cus, fold_wg_cap(256), lds), 256, lds, st, X, geo, order.p, (int)n, serve_V<T>(v), Um,
+                       urow_host ? urow.p : nullptr, lambda, weighted, nonneg, mp, dlists.p, L, E, d_item.p, d_contrib.p, d_pair.p, d_user.p, erows));
+    }
+    std::vector<double> hpair, huser;
+    double *pair_out = o.per_pair, *user_out = o.per_user;
+    if (!pair_out && o.stats) { hpair.resize(pairs * PCR_EXPLAIN_PAIR_FIELDS); pair_out = hpair.data(); }
+    if (!user_out && o.stats) { huser.resize((size_t)n * PCR_EXPLAIN_RIDGE_USER_FIELDS); user_out = huser.data(); }
+    HIPCHK(hipMemcpyAsync(o.item, d_item.p, pairs * E * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(o.contrib, d_contrib.p, pairs * E * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (pair_out) HIPCHK(hipMemcpyAsync(pair_out, d_pair.p, pairs * PCR_EXPLAIN_PAIR_FIELDS * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (user_out) HIPCHK(hipMemcpyAsync(user_out, d_user.p, (size_t)n * PCR_EXPLAIN_RIDGE_USER_FIELDS * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (o.stats) pcr_explain_ridge_stats_from(pair_out, user_out, o.item, lists, n, L, E, o.stats);
+    return PCR_OK;
+}
+
 // The entries' common end: the stats zeroed, nothing more for n == 0, then open() -- a _model entry's upload, nothing on a
 // solver -- and run(T()) in the view's precision
 template <class Stats, class Open, class Run>
@@ -447,6 +501,47 @@ static int fold_serve(Stats* stats, int64_t n, const ServeView& v, Open&& open, 
     return by_precision(v, run);
 }
 static int on_solver() { return PCR_OK; }
+
+// What a solver entry that explains its own users (pcr_explain, pcr_explain_ridge) reads of the data set the solver was created
+// from: every user must be on the rank (PCR_ERR_STATE otherwise), train is checked by its dimensions and nnz, users[n] are global
+// ids (NULL: all of them in order; *n is then the solver's user count).  R: the requested users' rows and their rows of the device U.
+struct SolverRows {
+    std::vector<int64_t> index;
+    std::vector<int32_t> item, urow;
+    std::vector<double> val;
+};
+static int solver_rows(const char* who_, pcr_solver* s, const ServeView& v, const pcr_dataset* train, int64_t* n_, const int32_t* users, SolverRows* R) {
+    const std::string who(who_);
+    if (s->comm_nranks() > 1 || s->first_user != 0 || s->n_users != v.d1) {
+        pcr_set_error(who + ": needs every user on the rank; this solver holds a shard");
+        return PCR_ERR_STATE;
+    }
+    if (!train) { pcr_set_error(who + ": null training data set"); return PCR_ERR_ARG; }
+    const PcrCsr& X = train->train;
+    if (X.d1 != v.d1 || X.d2 != v.d2 || X.nnz() != v.nnz) {
+        pcr_set_error(who + ": the data set is not the one the solver was created from (dimensions or nnz differ)");
+        return PCR_ERR_ARG;
+    }
+    if (!users) *n_ = s->n_users;                                  // (n is ignored without users)
+    const int64_t n = *n_;
+    if (n < 0 || n >= ((int64_t)1 << 31) - 64) { pcr_set_error(who + ": bad argument"); return PCR_ERR_ARG; }
+    R->index.assign((size_t)n + 1, 0);
+    R->urow.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t u = users ? users[i] : i;
+        if (u < 0 || u >= X.d1) { pcr_set_error(who + ": user id " + std::to_string(u) + " is outside the solver's users"); return PCR_ERR_ARG; }
+        R->urow[(size_t)i] = (int32_t)u;
+        R->index[(size_t)i + 1] = R->index[(size_t)i] + (X.index[(size_t)u + 1] - X.index[(size_t)u]);
+    }
+    R->item.resize((size_t)R->index[(size_t)n]);
+    R->val.resize((size_t)R->index[(size_t)n]);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t a = X.index[(size_t)R->urow[(size_t)i]], len = R->index[(size_t)i + 1] - R->index[(size_t)i];
+        std::copy(X.item.begin() + a, X.item.begin() + a + len, R->item.begin() + R->index[(size_t)i]);
+        std::copy(X.val.begin() + a, X.val.begin() + a + len, R->val.begin() + R->index[(size_t)i]);
+    }
+    return PCR_OK;
+}
 
 extern "C" {
 
@@ -593,41 +688,51 @@ int pcr_explain(pcr_solver* s, const pcr_dataset* train, int64_t n, const int32_
         pcr_params prm;
         if (s->foldin_params(&prm) != PCR_OK) return pcr_solver::pcr_only("pcr_explain");
         const ServeView v = solver_view(s, 0);
-        if (s->comm_nranks() > 1 || s->first_user != 0 || s->n_users != v.d1) {
-            pcr_set_error("pcr_explain: needs every user on the rank; this solver holds a shard");
-            return PCR_ERR_STATE;
-        }
-        if (!train) { pcr_set_error("pcr_explain: null training data set"); return PCR_ERR_ARG; }
-        const PcrCsr& X = train->train;
-        if (X.d1 != v.d1 || X.d2 != v.d2 || X.nnz() != v.nnz) {
-            pcr_set_error("pcr_explain: the data set is not the one the solver was created from (dimensions or nnz differ)");
-            return PCR_ERR_ARG;
-        }
-        if (!users) n = s->n_users;                                // (n is ignored without users)
-        if (n < 0 || n >= ((int64_t)1 << 31) - 64) { pcr_set_error("pcr_explain: bad argument"); return PCR_ERR_ARG; }
-        // the requested users' rows of the data set, and their rows of the device U
-        std::vector<int64_t> index((size_t)n + 1, 0);
-        std::vector<int32_t> urow((size_t)n);
-        for (int64_t i = 0; i < n; ++i) {
-            const int64_t u = users ? users[i] : i;
-            if (u < 0 || u >= X.d1) { pcr_set_error("pcr_explain: user id " + std::to_string(u) + " is outside the solver's users"); return PCR_ERR_ARG; }
-            urow[(size_t)i] = (int32_t)u;
-            index[(size_t)i + 1] = index[(size_t)i] + (X.index[(size_t)u + 1] - X.index[(size_t)u]);
-        }
-        std::vector<int32_t> item((size_t)index[(size_t)n]);
-        std::vector<double> val((size_t)index[(size_t)n]);
-        for (int64_t i = 0; i < n; ++i) {
-            const int64_t a = X.index[(size_t)urow[(size_t)i]], len = index[(size_t)i + 1] - index[(size_t)i];
-            std::copy(X.item.begin() + a, X.item.begin() + a + len, item.begin() + index[(size_t)i]);
-            std::copy(X.val.begin() + a, X.val.begin() + a + len, val.begin() + index[(size_t)i]);
-        }
+        SolverRows R;
+        RC(solver_rows("pcr_explain", s, v, train, &n, users, &R));
         PcrFoldinPlan P;
-        RC(pcr_explain_check("pcr_explain", false, &prm, nullptr, v.d2, n, index.data(), item.data(), val.data(), nullptr, weights, L, lists, E,
+        RC(pcr_explain_check("pcr_explain", false, &prm, nullptr, v.d2, n, R.index.data(), R.item.data(), R.val.data(), nullptr, weights, L, lists, E,
                              expl_item, expl_contrib, &P));
         const ExplainOut o = {expl_item, expl_contrib, per_pair, per_user, stats};
         return fold_serve(stats, n, v, on_solver, [&](auto zero) -> int {
             typedef decltype(zero) T;
-            return explain_run<T>(v, prm.solver_type, prm.lambda, P, serve_U<T>(v), urow.data(), weights, L, lists, E, o);
+            return explain_run<T>(v, prm.solver_type, prm.lambda, P, serve_U<T>(v), R.urow.data(), weights, L, lists, E, o);
+        });
+    });
+}
+
+int pcr_explain_ridge_model(const double* F, int64_t rows, int64_t k, double lambda, int weighted, int nonneg, int precision, int device, int64_t n,
+                            const int64_t* index, const int32_t* item, const double* val, const double* U, int L, const int32_t* lists, int E,
+                            int32_t* expl_item, double* expl_contrib, double* per_pair, double* per_user, pcr_explain_ridge_stats* stats) {
+    return abi_guard("pcr_explain_ridge_model", [&]() -> int {
+    PcrRidgePlan P;
+    RC(pcr_explain_ridge_check("pcr_explain_ridge_model", true, F, rows, k, lambda, nonneg, precision, n, index, item, val, U != nullptr, L, lists, E,
+                               expl_item, expl_contrib, &P));
+    RC(model_device(device));
+    ServeView v; ModelDev M;
+    const ExplainRidgeOut o = {expl_item, expl_contrib, per_pair, per_user, stats};
+    return fold_serve(stats, n, v, [&] { return M.open(U, n, F, rows, k, nullptr, nullptr, true, precision, &v); }, [&](auto zero) -> int {
+        typedef decltype(zero) T;
+        return explain_ridge_run<T>(v, lambda, weighted != 0, nonneg != 0, P, U ? serve_U<T>(v) : nullptr, nullptr, L, lists, E, o);
+    });
+    });
+}
+
+int pcr_explain_ridge(pcr_solver* s, const pcr_dataset* train, int64_t n, const int32_t* users, int weighted, int nonneg, int L, const int32_t* lists,
+                      int E, int32_t* expl_item, double* expl_contrib, double* per_pair, double* per_user, pcr_explain_ridge_stats* stats) {
+    S_OR_ARG;
+    return abi_guard("pcr_explain_ridge", [&]() -> int {
+        const ServeView v = solver_view(s, 0);
+        SolverRows R;
+        RC(solver_rows("pcr_explain_ridge", s, v, train, &n, users, &R));
+        const double lambda = s->ridge_lambda();
+        PcrRidgePlan P;
+        RC(pcr_explain_ridge_check("pcr_explain_ridge", false, nullptr, v.d2, v.r, lambda, nonneg, v.dtype, n, R.index.data(), R.item.data(), R.val.data(), true,
+                                   L, lists, E, expl_item, expl_contrib, &P));
+        const ExplainRidgeOut o = {expl_item, expl_contrib, per_pair, per_user, stats};
+        return fold_serve(stats, n, v, on_solver, [&](auto zero) -> int {
+            typedef decltype(zero) T;
+            return explain_ridge_run<T>(v, lambda, weighted != 0, nonneg != 0, P, serve_U<T>(v), R.urow.data(), L, lists, E, o);
         });
     });
 }

@@ -1826,24 +1826,11 @@ void pcr_foldin_stats_from(const double* per_user, int64_t n, pcr_foldin_stats* 
 // ------------------------------------------------------------------------------------------
 // explanations (include/primalcr.h, "explaining recommendations"): argument checks; the plan is fold-in's
 // ------------------------------------------------------------------------------------------
-int pcr_explain_check(const char* who, bool need_factors, const pcr_params* p, const double* V, int64_t d2, int64_t n, const int64_t* index,
-                      const int32_t* item, const double* val, const double* U, const double* weights, int L, const int32_t* lists, int E,
-                      const int32_t* expl_item, const double* expl_contrib, PcrFoldinPlan* plan) {
+// what both explanation families check of the lists and the outputs: lists [n][L] over d2 items (named `dim` in the messages),
+// the contributor tables, L and E
+static int explain_lists_check(const char* who, int64_t d2, const char* dim, int64_t n, int L, const int32_t* lists, int E, const int32_t* expl_item,
+                               const double* expl_contrib) {
     auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
-    if (!p) return bad("null parameters");
-    if (need_factors) {
-        if (!V) return bad("null V");
-        if (p->k < 1) return bad("rank k must be >= 1");
-        if (p->precision != PCR_F32 && p->precision != PCR_F64) return bad("precision must be PCR_F32 or PCR_F64");
-    }
-    if (!std::isfinite(p->lambda) || !(p->lambda > 0.0)) return bad("lambda must be finite and > 0");
-    if (p->solver_type == PCR_SOLVER_CCDR1) {
-        pcr_set_error(std::string(who) + ": solver type 0 (CCDR1) is not supported: a squared-loss row decomposes through its residuals, not through sweep coefficients");
-        return PCR_ERR_UNSUPPORTED;
-    }
-    const int rc = pcr_fold_in_rows_check(who, p->solver_type, d2, n, index, item, val, plan);
-    if (rc != PCR_OK) return rc;
-    if (n > 0 && need_factors && !U) return bad("null U");
     if (n > 0 && !lists) return bad("null lists");
     if (n > 0 && (!expl_item || !expl_contrib)) return bad("null expl_item / expl_contrib");
     if (L < 1 || L > PCR_EXPLAIN_MAX_L) return bad("L = " + std::to_string(L) + " must be inside [1, " + std::to_string(PCR_EXPLAIN_MAX_L) + "]");
@@ -1863,8 +1850,77 @@ int pcr_explain_check(const char* who, bool need_factors, const pcr_params* p, c
     });
     int all = 0;
     for (int x : st) all |= x;
-    if (all & 1) return bad("a list id is outside [0, d2) and not -1");
+    if (all & 1) return bad(std::string("a list id is outside [0, ") + dim + ") and not -1");
     if (all & 2) return bad("a list holds an id after a -1");
+    return PCR_OK;
+}
+
+static int fold_in_ls_args(const char* who, bool need_F, const double* F, int64_t rows, int64_t k, double lambda, int precision, int64_t n,
+                           const int64_t* index, const int32_t* item, const double* val, bool with_out, const double* U_out, PcrCsr& X);
+
+int pcr_explain_ridge_check(const char* who, bool need_F, const double* F, int64_t rows, int64_t k, double lambda, int nonneg, int precision,
+                            int64_t n, const int64_t* index, const int32_t* item, const double* val, bool has_U, int L, const int32_t* lists, int E,
+                            const int32_t* expl_item, const double* expl_contrib, PcrRidgePlan* plan) {
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
+    PcrRidgePlan local;
+    PcrRidgePlan& P = plan ? *plan : local;
+    const int rc = fold_in_ls_args(who, need_F, F, rows, k, lambda, precision, n, index, item, val, false, nullptr, P.X);
+    if (rc != PCR_OK) return rc;
+    if (!(lambda > 0.0)) return bad("lambda must be finite and > 0");
+    if (!has_U && nonneg) return bad("nonneg needs the rows U: the free set is read from them");
+    const int lrc = explain_lists_check(who, rows, "rows", n, L, lists, E, expl_item, expl_contrib);
+    if (lrc != PCR_OK) return lrc;
+    if ((k + 15) / 16 * 16 > PCR_RIDGE_DIRECT_MAX) {
+        pcr_set_error(std::string(who) + ": rank " + std::to_string(k) + " padded to 16 is beyond " + std::to_string(PCR_RIDGE_DIRECT_MAX) +
+                      ": the user's k x k system would not fit the kernel's LDS");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    // one launch class: the longest users start first (equal lengths by ascending id)
+    PcrRidgePlan::Range g;
+    g.form = PCR_RIDGE_PRIMAL; g.block = 256; g.tiles = (int)((k + 15) / 16);
+    g.first = 0; g.count = n;
+    P.order.resize((size_t)n);
+    for (int64_t u = 0; u < n; ++u) P.order[(size_t)u] = (int32_t)u;
+    std::stable_sort(P.order.begin(), P.order.end(), [&](int32_t x, int32_t y) { return index[x + 1] - index[x] > index[y + 1] - index[y]; });
+    P.ranges.assign(1, g);
+    return PCR_OK;
+}
+
+void pcr_explain_ridge_stats_from(const double* per_pair, const double* per_user, const int32_t* expl_item, const int32_t* lists, int64_t n, int L,
+                                  int E, pcr_explain_ridge_stats* stats) {
+    pcr_explain_ridge_stats s = {};
+    s.users = n;
+    for (int64_t z = 0; z < n * L; ++z) {
+        if (lists[z] < 0) continue;                                         // padding
+        s.pairs += 1;
+        const double r = std::fabs(per_pair[(size_t)z * PCR_EXPLAIN_PAIR_FIELDS + 3]);
+        if (r > s.residual_abs_max) s.residual_abs_max = r;
+    }
+    for (int64_t z = 0; z < n * L * E; ++z) s.contributors += expl_item[z] >= 0 ? 1 : 0;
+    for (int64_t u = 0; u < n; ++u) s.singular += (int)per_user[(size_t)u * PCR_EXPLAIN_RIDGE_USER_FIELDS + 4] == PCR_RIDGE_SINGULAR ? 1 : 0;
+    *stats = s;
+}
+
+int pcr_explain_check(const char* who, bool need_factors, const pcr_params* p, const double* V, int64_t d2, int64_t n, const int64_t* index,
+                      const int32_t* item, const double* val, const double* U, const double* weights, int L, const int32_t* lists, int E,
+                      const int32_t* expl_item, const double* expl_contrib, PcrFoldinPlan* plan) {
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
+    if (!p) return bad("null parameters");
+    if (need_factors) {
+        if (!V) return bad("null V");
+        if (p->k < 1) return bad("rank k must be >= 1");
+        if (p->precision != PCR_F32 && p->precision != PCR_F64) return bad("precision must be PCR_F32 or PCR_F64");
+    }
+    if (!std::isfinite(p->lambda) || !(p->lambda > 0.0)) return bad("lambda must be finite and > 0");
+    if (p->solver_type == PCR_SOLVER_CCDR1) {
+        pcr_set_error(std::string(who) + ": solver type 0 (CCDR1) is not supported: a squared-loss row decomposes through its residuals, not through sweep coefficients");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    const int rc = pcr_fold_in_rows_check(who, p->solver_type, d2, n, index, item, val, plan);
+    if (rc != PCR_OK) return rc;
+    if (n > 0 && need_factors && !U) return bad("null U");
+    const int lrc = explain_lists_check(who, d2, "d2", n, L, lists, E, expl_item, expl_contrib);
+    if (lrc != PCR_OK) return lrc;
     if (weights)
         for (int64_t u = 0; u < n; ++u)
             if (!std::isfinite(weights[u]) || !(weights[u] > 0.0)) return bad("the weight of user " + std::to_string(u) + " must be finite and > 0");
@@ -2032,8 +2088,9 @@ int pcr_ridge_form(int64_t len, int64_t k) {
 }
 
 // the argument checks of the ridge and the non-negative entries, and the copy X of the ratings with item-ascending rows
+// (with_out: the fold-in entries' output is checked in its place; pcr_explain_ridge_check has other outputs)
 static int fold_in_ls_args(const char* who, bool need_F, const double* F, int64_t rows, int64_t k, double lambda, int precision, int64_t n,
-                           const int64_t* index, const int32_t* item, const double* val, const double* U_out, PcrCsr& X) {
+                           const int64_t* index, const int32_t* item, const double* val, bool with_out, const double* U_out, PcrCsr& X) {
     auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
     if (need_F && !F) return bad("null F");
     if (k < 1) return bad("rank k must be >= 1");
@@ -2044,7 +2101,7 @@ static int fold_in_ls_args(const char* who, bool need_F, const double* F, int64_
     if (!std::isfinite(lambda) || lambda < 0.0) return bad("lambda must be finite and not negative");
     if (n < 0 || !index) return bad("bad argument");
     if (n >= ((int64_t)1 << 31) - 64) return bad("more than 2^31 users in one call");
-    if (n > 0 && !U_out) return bad("null output");
+    if (with_out && n > 0 && !U_out) return bad("null output");
     if (index[0] != 0) return bad("index[0] must be 0");
     for (int64_t u = 0; u < n; ++u) {
         if (index[u + 1] < index[u]) return bad("index not monotone at user " + std::to_string(u));
@@ -2063,7 +2120,7 @@ int pcr_fold_in_ridge_check(const char* who, bool need_F, const double* F, int64
                             const int64_t* index, const int32_t* item, const double* val, const double* U_out, PcrRidgePlan* plan) {
     PcrRidgePlan local;
     PcrRidgePlan& P = plan ? *plan : local;
-    const int rc = fold_in_ls_args(who, need_F, F, rows, k, lambda, precision, n, index, item, val, U_out, P.X);
+    const int rc = fold_in_ls_args(who, need_F, F, rows, k, lambda, precision, n, index, item, val, true, U_out, P.X);
     if (rc != PCR_OK) return rc;
     std::string knob;
     P.force_cg = pcr_tune_get("ridge_form", &knob) && knob == "cg";
@@ -2119,7 +2176,7 @@ int pcr_fold_in_nnls_check(const char* who, bool need_F, const double* F, int64_
                            const int64_t* index, const int32_t* item, const double* val, const double* U_out, PcrRidgePlan* plan) {
     PcrRidgePlan local;
     PcrRidgePlan& P = plan ? *plan : local;
-    const int rc = fold_in_ls_args(who, need_F, F, rows, k, lambda, precision, n, index, item, val, U_out, P.X);
+    const int rc = fold_in_ls_args(who, need_F, F, rows, k, lambda, precision, n, index, item, val, true, U_out, P.X);
     if (rc != PCR_OK) return rc;
     std::string knob;
     P.force_cg = pcr_tune_get("nnls_form", &knob) && knob == "cg";

@@ -301,3 +301,17 @@ int pcr_fold_in_nnls_check(const char* who, bool need_F, const double* F, int64_
                            const int64_t* index, const int32_t* item, const double* val, const double* U_out, PcrRidgePlan* plan);
 // stats from the per-user table [n][PCR_NNLS_FIELDS]: the counts, and loss / obj added in user order
 void pcr_nnls_stats_from(const double* per_user, int64_t n, pcr_nnls_stats* stats);
+
+// Explanations of squared-loss rows (include/primalcr.h, "explaining squared-loss recommendations").  The argument checks of
+// pcr_explain_ridge_model / pcr_explain_ridge in the order the header lists them (the library and the sanitizer build's "no
+// device" stub run the same ones): the ridge entries' checks of F (need_F: the model entry), k, rows, lambda, precision and the
+// rows; lambda > 0; has_U: the entry has rows of U to explain (the solver entry always; false with nonneg is refused); the lists
+// and outputs as pcr_explain_check; last the rank against PCR_RIDGE_DIRECT_MAX (PCR_ERR_UNSUPPORTED).  Errors are prefixed with
+// `who`.  The plan (may be NULL) is a PcrRidgePlan with the item-ascending rows and ONE range: the users by descending length.
+int pcr_explain_ridge_check(const char* who, bool need_F, const double* F, int64_t rows, int64_t k, double lambda, int nonneg, int precision,
+                            int64_t n, const int64_t* index, const int32_t* item, const double* val, bool has_U, int L, const int32_t* lists, int E,
+                            const int32_t* expl_item, const double* expl_contrib, PcrRidgePlan* plan);
+// stats from the finished tables per_pair [n][L][PCR_EXPLAIN_PAIR_FIELDS], per_user [n][PCR_EXPLAIN_RIDGE_USER_FIELDS] and
+// expl_item [n][L][E]; lists [n][L] tells the padding
+void pcr_explain_ridge_stats_from(const double* per_pair, const double* per_user, const int32_t* expl_item, const int32_t* lists, int64_t n, int L,
+                                  int E, pcr_explain_ridge_stats* stats);

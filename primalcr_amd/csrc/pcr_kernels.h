@@ -4,7 +4,8 @@
 //   pcr_eval.h (evaluator, objective reductions, predict); pcr_gram.h (optional dual-form U step on MFMA).  Not part of this header:
 //   pcr_topk.h (top-K recommendation: MFMA scores with a fused streaming selection), instantiated in pcr_serve.hip over pcr_prims.h;
 //   pcr_foldin.h, pcr_itemfold.h, pcr_ridge.h, pcr_nnls.h (the fold-in families) and pcr_explain.h (k_explain: a score decomposed
-//   over the user's own rated items), instantiated in pcr_fold.hip over pcr_prims.h.
+//   over the user's own rated items) with pcr_explain_ridge.h (k_explain_ridge: the same for a squared-loss row), instantiated in
+//   pcr_fold.hip over pcr_prims.h.
 //
 // Kernel map (reference site -> kernel); design and rooflines: DESIGN.md section 3:
 //   K1        comp_m_new, b = u.a in compute_Ha_new        -> k_sddmm     (rating-parallel)

@@ -50,6 +50,29 @@ __device__ __forceinline__ bool nnls_rule(int nv, int& alpha, int& beta) {
     return false;
 }
 
+// dst = the nt x nt lower-triangular tiles src with the rows and columns outside P (bit j & 63 of p0 / p1 for coordinate j < 64 /
+// >= 64) replaced by a unit diagonal -- what ridge_gram already leaves beyond the rank, and what ridge_chol passes through
+// unchanged.  dst may be src.  k_nnls_direct's pivots and k_explain_ridge's free set (pcr_explain_ridge.h) run this one.
+template <int BLOCK>
+__device__ __forceinline__ void nnls_mask_tiles(const double* src, double* dst, int nt, unsigned long long p0, unsigned long long p1) {
+    constexpr int NW = BLOCK / PCR_WAVE;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, npairs = nt * (nt + 1) / 2;
+    auto in_p = [&](int j) { return (((j < 64 ? p0 : p1) >> (j & 63)) & 1ull) != 0ull; };
+    for (int pr = wid; pr < npairs; pr += NW) {
+        int I = 0, rem = pr;
+        while (rem > I) { rem -= I + 1; ++I; }
+        const double* s = src + (size_t)ridge_tix(I, rem) * RIDGE_TILE;
+        double* d = dst + (size_t)ridge_tix(I, rem) * RIDGE_TILE;
+        const int cl = lane & 15, col = rem * 16 + cl;
+        const bool pc = in_p(col);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int rl = (lane >> 4) + 4 * e, rw = I * 16 + rl;
+            d[rl * RIDGE_TP + cl] = (pc && in_p(rw)) ? s[rl * RIDGE_TP + cl] : (rw == col ? 1.0 : 0.0);
+        }
+    }
+}
+
 // LDS of k_nnls_direct: the small vectors, then the master tiles of G (the staging chunk of the build lies under them, as in
 // k_ridge_direct) and the working tiles of a pivot.  7 x 7 tiles: 2 x 60 928 B + 5 KB = 124 KB, one workgroup per CU.
 static inline size_t nnls_direct_bytes(int mp, int ld, int block) {
@@ -63,13 +86,12 @@ static inline size_t nnls_direct_bytes(int mp, int ld, int block) {
 template <typename T, int BLOCK>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2))) void k_nnls_direct(RidgeCsr X, const int32_t* __restrict__ users, int nusers, const T* __restrict__ F, int r, int ld,
                                                        T* __restrict__ Uout, double* __restrict__ per_user, double lambda, int weighted, int mp) {
-    constexpr int NW = BLOCK / PCR_WAVE;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Carver cv(smem);
     double* red = cv.take<double>(8);
     double* part = cv.take<double>(BLOCK / 16);
     double* rch = cv.take<double>(16);                                   // the staged chunk's ratings
-    double* ot = cv.take<double>(8);                                     // ridge_finish's table line
+    double* ot = cv.take<double>(8);                                    // ridge_finish's table line
     unsigned long long* pm = cv.take<unsigned long long>(4);             // P: bits of coordinates 0..63, 64..127; [2] != 0: V was empty
     double* gv = cv.take<double>(mp);                                    // b masked to P, then the pivot's solution
     double* dinv = cv.take<double>(mp);                                  // 1 / L[i][i]
@@ -107,19 +129,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2))) void
             p0 = pm[0]; p1 = pm[1];
             auto in_p = [&](int j) { return (((j < 64 ? p0 : p1) >> (j & 63)) & 1ull) != 0ull; };
             // ---- the working tiles: the master with Z's rows and columns as a unit diagonal; b masked to P
-            for (int pr = wid; pr < npairs; pr += NW) {
-                int I = 0, rem = pr;
-                while (rem > I) { rem -= I + 1; ++I; }
-                const double* src = Gm + (size_t)ridge_tix(I, rem) * RIDGE_TILE;
-                double* dst = Tw + (size_t)ridge_tix(I, rem) * RIDGE_TILE;
-                const int cl = lane & 15, col = rem * 16 + cl;
-                const bool pc = in_p(col);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int rl = (lane >> 4) + 4 * e, rw = I * 16 + rl;
-                    dst[rl * RIDGE_TP + cl] = (pc && in_p(rw)) ? src[rl * RIDGE_TP + cl] : (rw == col ? 1.0 : 0.0);
-                }
-            }
+            nnls_mask_tiles<BLOCK>(Gm, Tw, nt, p0, p1);
             for (int t = tid; t < mp; t += BLOCK) gv[t] = in_p(t) ? bv[t] : 0.0;
             if (tid == 0) red[7] = 0.0;                                  // "not positive definite" flag
             __syncthreads();

@@ -182,6 +182,15 @@ int pcr_explain_model(const pcr_params* p, const double* V, int64_t d2, int64_t 
 }
 NO_SOLVER(pcr_explain, pcr_solver*, const pcr_dataset*, int64_t, const int32_t*, const double*, int, const int32_t*, int, int32_t*, double*, double*,
           double*, pcr_explain_stats*)
+int pcr_explain_ridge_model(const double* F, int64_t rows, int64_t k, double lambda, int, int nonneg, int precision, int, int64_t n, const int64_t* index,
+                            const int32_t* item, const double* val, const double* U, int L, const int32_t* lists, int E, int32_t* expl_item,
+                            double* expl_contrib, double*, double*, pcr_explain_ridge_stats*) {
+    const int rc = pcr_explain_ridge_check("pcr_explain_ridge_model", true, F, rows, k, lambda, nonneg, precision, n, index, item, val, U != nullptr, L,
+                                           lists, E, expl_item, expl_contrib, nullptr);
+    return rc != PCR_OK ? rc : absent();
+}
+NO_SOLVER(pcr_explain_ridge, pcr_solver*, const pcr_dataset*, int64_t, const int32_t*, int, int, int, const int32_t*, int, int32_t*, double*, double*,
+          double*, pcr_explain_ridge_stats*)
 NO_SOLVER(pcr_evaluate_rerank, pcr_solver*, int64_t, const int32_t*, int, const double*, int, int, const int*, double, int, pcr_topn_stats*,
           pcr_diversity_stats*, double*, double*, int64_t*)
 }
