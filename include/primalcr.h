@@ -165,6 +165,17 @@ int pcr_dataset_user_pairs(const pcr_dataset *ds, int solver_type, int64_t *pair
 #define PCR_WEIGHT_RATINGS 2
 int pcr_user_weights(const pcr_dataset *ds, int solver_type, int scheme, double *w /* d1 */);   /* [host] */
 
+/* Per-rating weights for pcr_solver_set_rating_weights (CCDR1), in the order of pcr_dataset_csr(ds, 0, ...).
+ * pcr_dataset_match_weights puts n (user, item, weight) triplets, ids 0-based as pcr_dataset_from_triplets takes them and in any
+ * order, into that order: w_csr[z] = the weight of the triplet that names training rating z.  PCR_ERR_ARG, the first offender
+ * named in pcr_last_error: a triplet that is no training rating, a training rating named twice, one left without a weight.
+ * pcr_rating_weights_popularity: w_z = (n_max / n_item(z))^gamma, n_item = the item's training ratings, n_max the largest of them
+ * -- the inverse of a power-law propensity; gamma = 0 gives ones; a gamma that is not finite is PCR_ERR_ARG.  Not normalised: a
+ * common factor on all weights leaves the minimiser where it is. */
+int pcr_dataset_match_weights(const pcr_dataset *ds, int64_t n, const int32_t *user, const int32_t *item, const double *w,
+                              double *w_csr /* nnz */);                    /* [host] */
+int pcr_rating_weights_popularity(const pcr_dataset *ds, double gamma, double *w_csr /* nnz */);   /* [host] */
+
 /* A rating file on its own (omp-pmf-predict's test file: pmf-predict.cpp:52-55 reads "user item rating" triples until fscanf
  * fails, no meta file).  count: the file's non-blank lines.  read: at most n entries by `threads` host threads (0 = up to 16),
  * ids 0-based, val may be NULL; the input ends at the first malformed entry: *n_read entries stand before it (the reference's
@@ -351,6 +362,20 @@ int pcr_solver_get_factors_local(pcr_solver *s, double *U_local, double *V);
  * "ustep_gram" or "vblock_users", whose optional kernels do not carry weights. */
 int pcr_solver_set_user_weights(pcr_solver *s, const double *w /* d1 of the job */);        /* [device] */
 int pcr_solver_set_user_weights_local(pcr_solver *s, const double *w_local /* n_users */);  /* [device] */
+
+/* Per-rating confidence weights for CCDR1 (solver type 0; the reference's ccd-r1.cpp is the case c = 1): one weight c_z, finite
+ * and > 0, per training rating z = (i, j), in the order of pcr_dataset_csr(ds, 0, ...).  From then on pcr_train / pcr_iterate solve
+ *     min sum_z c_z (r_z - u_i . v_j)^2 + lambda (sum_i W_i |u_i|^2 + sum_j W_j |v_j|^2),   W = the sum of c_z over the row's ratings
+ * (the reference regularises by lambda times the rating count, ccd-r1.cpp:151,157: W is that count with weights, so a rating of
+ * weight 2 is the rating present twice and a common factor on all weights leaves the minimiser where it is).  The rank-one update of
+ * a non-empty column is g = sum c x r, h = lambda W + sum c x^2, new = g / h, fundec = h (old - new)^2; the printed loss / obj / reg
+ * and pcr_iter_stats.obj are the weighted ones; the stopping rule, the test rmse and pcr_evaluate do not see weights.  The weights
+ * are stored in the solver's precision (rounded as the ratings are): each must be finite and > 0 as given and as stored, else
+ * PCR_ERR_ARG and the solver keeps what it had.  NULL returns to the unweighted kernels.  Like pcr_solver_set_factors the call ends
+ * a running training (the next pcr_train / pcr_iterate begins from the current U); weights survive pcr_solver_set_factors and
+ * pcr_solver_set_ccd_params.  pcr_solver_counter "ccd_rating_weights" is 1 while weights are set.  Fold-in, explanations and the
+ * model file do not carry weights.  PCR_ERR_UNSUPPORTED on a PrimalCR / PrimalCR++ solver (those take pcr_solver_set_user_weights). */
+int pcr_solver_set_rating_weights(pcr_solver *s, const double *w /* nnz, in the order of pcr_dataset_csr(ds, 0, ...) */);   /* [device] */
 
 /* pcrpp.cpp:17-35 comp_m_new (pcr.cpp:47 comp_m): m = u_i . v_j for every rating,
  * from the current device U, V; also builds the per-user (level, m)-sorted state

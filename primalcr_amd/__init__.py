@@ -15,7 +15,7 @@ from .api import (PCR_F32, PCR_F64, PCR_REC_EXCLUDE_TRAIN, PCR_RECOMMEND_MAX_K, 
                   fold_in_ridge, recommend_new_users_ridge, ridge_boundaries, ridge_form, RidgeStats, PCR_RIDGE_FIELDS, PCR_RIDGE_DUAL, PCR_RIDGE_PRIMAL, PCR_RIDGE_CG, PCR_RIDGE_OK, PCR_RIDGE_SINGULAR, PCR_RIDGE_CG_CAP, PCR_RIDGE_WAVE_MAX, PCR_RIDGE_DIRECT_MAX,
                   fold_in_nnls, recommend_new_users_nnls, nnls_form, NnlsStats, PCR_NNLS_FIELDS, PCR_NNLS_DIRECT, PCR_NNLS_CG, PCR_NNLS_OK, PCR_NNLS_SINGULAR, PCR_NNLS_CAP, PCR_NNLS_PIVOT_CAP,
                   fold_in_items, itemfold_boundaries, rater_scores_boundaries, ItemfoldStats, PCR_ITEMFOLD_FIELDS, PCR_ITEMFOLD_WAVE_MAX, PCR_ITEMFOLD_LDS_MAX,
-                  PCR_ITEMFOLD_SCORES_WAVE_MAX, user_weights, PCR_WEIGHT_UNIFORM, PCR_WEIGHT_PAIRS, PCR_WEIGHT_RATINGS,
+                  PCR_ITEMFOLD_SCORES_WAVE_MAX, user_weights, match_weights, rating_weights_popularity, PCR_WEIGHT_UNIFORM, PCR_WEIGHT_PAIRS, PCR_WEIGHT_RATINGS,
                   explain, explain_boundaries, ExplainStats, PCR_EXPLAIN_MAX_L, PCR_EXPLAIN_MAX_E, PCR_EXPLAIN_PAIR_FIELDS, PCR_EXPLAIN_USER_FIELDS, EXPLAIN_TILE, EXPLAIN_CHUNK,
                   explain_ridge, explain_ridge_boundaries, ExplainRidgeStats, PCR_EXPLAIN_RIDGE_USER_FIELDS)
 
@@ -25,6 +25,6 @@ __all__ = ["PCR_F32", "PCR_F64", "PCR_REC_EXCLUDE_TRAIN", "PCR_RECOMMEND_MAX_K",
            "fold_in_ridge", "recommend_new_users_ridge", "ridge_boundaries", "ridge_form", "RidgeStats", "PCR_RIDGE_FIELDS", "PCR_RIDGE_DUAL", "PCR_RIDGE_PRIMAL", "PCR_RIDGE_CG", "PCR_RIDGE_OK", "PCR_RIDGE_SINGULAR", "PCR_RIDGE_CG_CAP", "PCR_RIDGE_WAVE_MAX", "PCR_RIDGE_DIRECT_MAX",
            "fold_in_nnls", "recommend_new_users_nnls", "nnls_form", "NnlsStats", "PCR_NNLS_FIELDS", "PCR_NNLS_DIRECT", "PCR_NNLS_CG", "PCR_NNLS_OK", "PCR_NNLS_SINGULAR", "PCR_NNLS_CAP", "PCR_NNLS_PIVOT_CAP",
            "fold_in_items", "itemfold_boundaries", "rater_scores_boundaries", "ItemfoldStats", "PCR_ITEMFOLD_FIELDS", "PCR_ITEMFOLD_WAVE_MAX", "PCR_ITEMFOLD_LDS_MAX",
-           "PCR_ITEMFOLD_SCORES_WAVE_MAX", "user_weights", "PCR_WEIGHT_UNIFORM", "PCR_WEIGHT_PAIRS", "PCR_WEIGHT_RATINGS",
+           "PCR_ITEMFOLD_SCORES_WAVE_MAX", "user_weights", "match_weights", "rating_weights_popularity", "PCR_WEIGHT_UNIFORM", "PCR_WEIGHT_PAIRS", "PCR_WEIGHT_RATINGS",
            "explain", "explain_boundaries", "ExplainStats", "PCR_EXPLAIN_MAX_L", "PCR_EXPLAIN_MAX_E", "PCR_EXPLAIN_PAIR_FIELDS", "PCR_EXPLAIN_USER_FIELDS", "EXPLAIN_TILE", "EXPLAIN_CHUNK",
            "explain_ridge", "explain_ridge_boundaries", "ExplainRidgeStats", "PCR_EXPLAIN_RIDGE_USER_FIELDS"]

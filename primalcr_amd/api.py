@@ -213,6 +213,10 @@ def lib():
         L.pcr_user_weights.argtypes = [vp, ci, ci, vp]
         L.pcr_solver_set_user_weights.argtypes = [vp, vp]
         L.pcr_solver_set_user_weights_local.argtypes = [vp, vp]
+    if _LIB_OVERRIDE is None or hasattr(L, "pcr_solver_set_rating_weights"):
+        L.pcr_dataset_match_weights.argtypes = [vp, i64, vp, vp, vp, vp]
+        L.pcr_rating_weights_popularity.argtypes = [vp, cd, vp]
+        L.pcr_solver_set_rating_weights.argtypes = [vp, vp]
     L.pcr_model_save.argtypes = [C.c_char_p, _dp, i64, _dp, i64, i64]
     L.pcr_model_load.argtypes = [C.c_char_p, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp, vp]
     L.pcr_partition_users.argtypes = [_lp, i64, ci, _lp]
@@ -1259,6 +1263,26 @@ def user_weights(ds: Dataset, scheme=PCR_WEIGHT_PAIRS, solver_type=PCR_SOLVER_PC
     return w[:d1]
 
 
+def match_weights(ds: Dataset, user, item, w):
+    """(user, item, weight) triplets, ids 0-based and in any order, -> the weights in Dataset.csr() order (pcr_dataset_match_weights).
+    Every training rating must be named exactly once."""
+    user = np.ascontiguousarray(user, np.int32); item = np.ascontiguousarray(item, np.int32); w = np.ascontiguousarray(w, np.float64)
+    if not (user.ndim == 1 and user.shape == item.shape == w.shape):
+        raise ValueError("user, item and weight must be vectors of one length")
+    out = np.zeros(max(ds.dims()[2], 1), np.float64)
+    _chk(lib().pcr_dataset_match_weights(ds._h, user.shape[0], user.ctypes.data, item.ctypes.data, w.ctypes.data, out.ctypes.data))
+    return out[:ds.dims()[2]]
+
+
+def rating_weights_popularity(ds: Dataset, gamma):
+    """Per-rating weights for Solver.set_rating_weights, in Dataset.csr() order: w_z = (n_max / n_item(z))^gamma, the inverse of a
+    power-law propensity in the item's popularity (gamma = 0: ones).  Not normalised: the weighted objective does not need it."""
+    nnz = ds.dims()[2]
+    w = np.ones(max(nnz, 1), np.float64)
+    _chk(lib().pcr_rating_weights_popularity(ds._h, float(gamma), w.ctypes.data))
+    return w[:nnz]
+
+
 class Solver:
     """Device solver: the reference's pcrpp()/pcr() and their building blocks on one MI355X."""
 
@@ -1353,6 +1377,23 @@ class Solver:
             raise ValueError(f"w must hold {want} weights")
         _chk(fn(self._h, w.ctypes.data))
         self.user_weights = w.copy()                        # (Solver.explain's default; the library's entry reads the caller's)
+
+    def set_rating_weights(self, w=None):
+        """Per-rating confidence weights c_z > 0 (CCDR1): the solver then minimises sum_z c_z (r_z - u_i . v_j)^2 + lambda (sum_i W_i
+        |u_i|^2 + sum_j W_j |v_j|^2), W = a row's sum of c_z.  w: a vector of nnz weights in Dataset.csr() order, or a (user, item,
+        weight) tuple of vectors (0-based ids, any order, every training rating exactly once), or None for the unweighted problem.
+        Ends a running training like set_factors; the weights survive set_factors and set_ccd_params."""
+        if w is None:
+            _chk(lib().pcr_solver_set_rating_weights(self._h, None))
+            return
+        if isinstance(w, tuple):
+            if len(w) != 3:
+                raise ValueError("a tuple must be (user, item, weight)")
+            w = match_weights(self.ds, *w)
+        w = np.ascontiguousarray(w, np.float64)
+        if w.shape != (self.nnz,):
+            raise ValueError(f"w must hold {self.nnz} weights")
+        _chk(lib().pcr_solver_set_rating_weights(self._h, w.ctypes.data))
 
     def get_factors_local(self):
         U = np.zeros((self.n_users, self.k)); V = np.zeros((self.d2, self.k))

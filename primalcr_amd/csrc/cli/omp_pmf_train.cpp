@@ -25,6 +25,11 @@
 //   --normalize pairs|ratings  the weights of pcr_user_weights instead: every user with a comparable pair (a rating) carries the
 //                     same mass, the total stays that of the unweighted problem.  Not together with --user-weights.
 //                     The log lines keep their format; the objective they print is the weighted one.
+//   --rating-weights F  per-rating confidence weights (pcr_solver_set_rating_weights; -s 0 only): F is in the format of a ratings
+//                     file, "user item weight" with the ids as in the training file, every training rating exactly once, any order
+//   --popularity-weights G  the weights of pcr_rating_weights_popularity instead: (n_max / n_item)^G.  Not together with
+//                     --rating-weights, --user-weights or --normalize.  The log lines keep their format; loss / obj / reg are the
+//                     weighted ones.
 //   --tune key=value  a launch knob of pcr_tune() (repeatable)
 //   --timing          one "[timing] load_s=... init_s=... create_s=... train_s=... iter_s=... eval_s=... write_s=... wall_s=..." line
 //                     on stderr at the end: where the run's wall time went (iter_s = the reference's own "Iter k time" clock,
@@ -77,6 +82,8 @@ static void exit_with_help() {
         "    --comm rccl|p2p : all-reduce through RCCL (default) or direct peer-to-peer buffers\n"
         "    --user-weights file : per-user loss weights, one positive weight per line and user (-s 1, -s 2)\n"
         "    --normalize pairs|ratings : weight every user by 1 / its pairs (ratings), total mass kept (not with --user-weights)\n"
+        "    --rating-weights file : per-rating confidence weights, lines of 'user item weight' as in a ratings file (-s 0)\n"
+        "    --popularity-weights gamma : weight every rating by (n_max / n_item)^gamma (-s 0; not with --rating-weights)\n"
         "    --tune key=value : launch knob (pcr_tune)\n"
         "    --timing : print the phases of the run's wall time on stderr\n");
     exit(1);
@@ -382,7 +389,7 @@ static int train_multi(const pcr_dataset* ds, const pcr_params& param, int gpus,
 // pmf-train.cpp:138-172 run_ccdr1(): "starts!", the per-rank lines of ccdr1(), "Wall-time: %lg secs", the model; no side files
 static int run_ccdr1(pcr_dataset* ds, pcr_params param, const pcr_ccd_params& ccd, const std::vector<int>& devices, const std::string& model,
                      std::vector<double>& U, std::vector<double>& V, int64_t d1, int64_t d2, bool timing, double load_s, double init_s,
-                     std::chrono::steady_clock::time_point t_main) {
+                     std::chrono::steady_clock::time_point t_main, const std::vector<double>& rating_weights) {
     auto t_lap = std::chrono::steady_clock::now();
     auto lap = [&]() { const auto n = std::chrono::steady_clock::now(); const double d = std::chrono::duration<double>(n - t_lap).count(); t_lap = n; return d; };
     struct Holder { pcr_solver* s; ~Holder() { if (s) pcr_solver_destroy(s); } } hold{nullptr};      // (the caller owns ds)
@@ -396,6 +403,7 @@ static int run_ccdr1(pcr_dataset* ds, pcr_params param, const pcr_ccd_params& cc
     hold.s = s;
     if (pcr_solver_set_ccd_params(s, &ccd) != PCR_OK) return fail("solver");
     if (pcr_solver_set_factors(s, U.data(), nullptr) != PCR_OK) return fail("set_factors");
+    if (!rating_weights.empty() && pcr_solver_set_rating_weights(s, rating_weights.data()) != PCR_OK) return fail("rating weights");
     const double create_s = lap();
     std::vector<pcr_iter_stats> hist((size_t)std::max(0, param.maxiter) + 1);
     if (pcr_train(s, nullptr, nullptr, hist.data()) != PCR_OK) return fail("train");
@@ -423,7 +431,7 @@ int main(int argc, char** argv) {
     pcr_params_default(&param);
     pcr_ccd_params ccd;
     pcr_ccd_params_default(&ccd);
-    std::string init_model, cache, comm_kind = "rccl", weights_file, normalize;
+    std::string init_model, cache, comm_kind = "rccl", weights_file, normalize, rating_weights_file, popularity;
     std::vector<int> devices;
     int snapshot_every = 0, gpus = 1;
     int i;
@@ -442,6 +450,8 @@ int main(int argc, char** argv) {
         if (!strcmp(argv[i - 1], "--comm")) { comm_kind = argv[i]; continue; }
         if (!strcmp(argv[i - 1], "--user-weights")) { weights_file = argv[i]; continue; }
         if (!strcmp(argv[i - 1], "--normalize")) { normalize = argv[i]; continue; }
+        if (!strcmp(argv[i - 1], "--rating-weights")) { rating_weights_file = argv[i]; continue; }
+        if (!strcmp(argv[i - 1], "--popularity-weights")) { popularity = argv[i]; continue; }
         if (!strcmp(argv[i - 1], "--devices")) {
             for (const char* q = argv[i]; *q;) { devices.push_back(atoi(q)); while (*q && *q != ',') ++q; if (*q == ',') ++q; }
             continue;
@@ -488,6 +498,28 @@ int main(int argc, char** argv) {
         fprintf(stderr, "Error: wrong solver type (%d)!\n", param.solver_type);   // pmf-train.cpp:331-333
         return 0;
     }
+    double gamma = 0.0;
+    if (!rating_weights_file.empty() || !popularity.empty()) {     // per-rating weights: CCDR1's alone, one source, refused before any device work
+        const char* mine = !rating_weights_file.empty() ? "--rating-weights" : "--popularity-weights";
+        if (!rating_weights_file.empty() && !popularity.empty()) { fprintf(stderr, "omp-pmf-train: --rating-weights and --popularity-weights are mutually exclusive\n"); return 1; }
+        if (!weights_file.empty() || !normalize.empty()) {
+            fprintf(stderr, "omp-pmf-train: %s (per-rating weights, -s 0) and %s (per-user weights, -s 1 and -s 2) cannot be combined\n", mine,
+                    !weights_file.empty() ? "--user-weights" : "--normalize");
+            return 1;
+        }
+        if (param.solver_type != PCR_SOLVER_CCDR1) {
+            fprintf(stderr, "omp-pmf-train: %s needs -s 0 (CCDR1); -s 1 and -s 2 take per-user weights: --user-weights, --normalize\n", mine);
+            return 1;
+        }
+        if (!popularity.empty()) {
+            char* end = nullptr;
+            gamma = strtod(popularity.c_str(), &end);
+            if (end == popularity.c_str() || *end != '\0' || !(gamma - gamma == 0.0)) {
+                fprintf(stderr, "omp-pmf-train: --popularity-weights '%s' is not a finite number\n", popularity.c_str());
+                return 1;
+            }
+        }
+    }
     if (param.solver_type == PCR_SOLVER_CCDR1) {                     // options CCDR1 does not have: refused, never ignored
         const char* bad = gpus != 1 ? "--gpus" : devices.size() > 1 ? "--devices with more than one device" : !init_model.empty() ? "--init-model"
                         : snapshot_every != 0 ? "--snapshot-every" : !weights_file.empty() ? "--user-weights" : !normalize.empty() ? "--normalize" : nullptr;
@@ -519,8 +551,22 @@ int main(int argc, char** argv) {
     const int k = param.k;
     std::vector<double> U((size_t)d1 * k), V((size_t)d2 * k);
     if (param.solver_type == PCR_SOLVER_CCDR1) {
+        std::vector<double> rw;                         // per-rating confidence weights in the training CSR's order (empty: c = 1)
+        if (!rating_weights_file.empty()) {
+            int64_t n = 0, got = 0;
+            if (pcr_rating_file_count(rating_weights_file.c_str(), &n) != PCR_OK) die("--rating-weights");
+            std::vector<int32_t> wu((size_t)n), wi((size_t)n);
+            std::vector<double> wv((size_t)n);
+            if (pcr_rating_file_read(rating_weights_file.c_str(), param.threads, n, wu.data(), wi.data(), wv.data(), &got) != PCR_OK) die("--rating-weights");
+            if (got != n) die_with("--rating-weights", rating_weights_file + ": entry " + std::to_string(got + 1) + " is malformed");
+            rw.resize((size_t)nnz);
+            if (pcr_dataset_match_weights(ds, n, wu.data(), wi.data(), wv.data(), rw.data()) != PCR_OK) die("--rating-weights");
+        } else if (!popularity.empty()) {
+            rw.resize((size_t)nnz);
+            if (pcr_rating_weights_popularity(ds, gamma, rw.data()) != PCR_OK) die("--popularity-weights");
+        }
         pcr_initial_col(U.data(), d1, k);              // pmf-train.cpp:156-158 (H is zeroed by ccdr1 itself, ccd-r1.cpp:116)
-        return run_ccdr1(ds, param, ccd, devices, model, U, V, d1, d2, timing, load_s, lap() , t_main);
+        return run_ccdr1(ds, param, ccd, devices, model, U, V, d1, d2, timing, load_s, lap() , t_main, rw);
     }
     std::vector<double> weights;                       // per-user loss weights (empty: the reference's unweighted problem)
     if (!weights_file.empty()) {

@@ -9,7 +9,10 @@
 //   * the test residuals behind the printed rmse (util.cpp:206-215);
 //   * fp64 work vectors u (d1), v (d2) and their values at the start of the rank, oldu / oldv (ccd-r1.cpp:120-125);
 //   * a control block (CcdCtl): the stopping state of ccd-r1.cpp:126-172 lives on the device, so that no inner iteration
-//     needs a host round trip.
+//     needs a host round trip;
+//   * optionally one confidence weight per rating (pcr_solver_set_rating_weights): in both orders next to the two
+//     residual copies, in their storage type, and the fp64 sums W per user and per item that stand where the rating counts stood;
+//     the weighted launches are the _w kernels, the unweighted ones keep their symbols and code.
 // Kernels per rank: k_ccd_begin, then per inner iteration k_ccd_sweep over the CSC (v), k_ccd_sweep over the
 // CSR (u) and k_ccd_decide, then k_ccd_resid and k_ccd_final: 3 T + 3 launches.  Every sum is accumulated in fp64 and reduced in
 // a fixed order (per-block partials summed by one block): results do not depend on timing and repeat bit for bit.
@@ -103,10 +106,14 @@ __global__ void __launch_bounds__(ccd::BLOCK) k_ccd_begin(CcdCtl* ctl, const T* 
 // a workgroup each.  With `addback` (inner iteration 1 of an outer iteration > 1) the rank's old term is added back into this
 // orientation's residual copy on the way (ccd-r1.cpp:127-130: r += oldu_i oldv_j), stored, and used.
 // part[block] = the block's fundec, its columns in order.
-template <typename RT>
-__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_sweep(const CcdCtl* ctl, const int64_t* ptr, const int32_t* idx, RT* res, const double* x,
-                                                          const double* oldx, const double* oldy, double* y, const int32_t* longs, int nlong,
-                                                          const int32_t* shorts, int nshort, double lambda, int do_nmf, int addback, double* part) {
+// With WT (per-rating confidence weights c_z) wt holds c in this orientation's order, read at the residual's index,
+// and Wc[c] = the column's sum of c_z: g = sum (c x) r, h = lambda W_c + sum (c x) x -- c x is formed first, so all-ones weights
+// give the unweighted bits and weights that are all the same power of two scale g, h and fundec exactly.  An empty column is
+// still decided by its count.
+template <typename RT, bool WT>
+__device__ __forceinline__ void ccd_sweep(const CcdCtl* ctl, const int64_t* ptr, const int32_t* idx, RT* res, const RT* wt, const double* Wc,
+                                          const double* x, const double* oldx, const double* oldy, double* y, const int32_t* longs, int nlong,
+                                          const int32_t* shorts, int nshort, double lambda, int do_nmf, int addback, double* part) {
     if (ctl->skip || ctl->broken) return;
     __shared__ double sg[ccd::BLOCK / 64], sh[ccd::BLOCK / 64], sf[ccd::BLOCK / 64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -120,7 +127,8 @@ __global__ void __launch_bounds__(ccd::BLOCK) k_ccd_sweep(const CcdCtl* ctl, con
             double r = (double)res[z];
             if (addback) { const RT rn = (RT)fma(oldx[i], oy, r); res[z] = rn; r = (double)rn; }
             const double xi = x[i];
-            g += xi * r; h += xi * xi;
+            if (WT) { const double cx = (double)wt[z] * xi; g += cx * r; h += cx * xi; }
+            else { g += xi * r; h += xi * xi; }
         }
         g = ccd::wave_sum(g); h = ccd::wave_sum(h);
         if (lane == 0) { sg[wv] = g; sh[wv] = h; }
@@ -129,7 +137,7 @@ __global__ void __launch_bounds__(ccd::BLOCK) k_ccd_sweep(const CcdCtl* ctl, con
             double G = 0.0, H = 0.0;
             for (int w = 0; w < ccd::BLOCK / 64; ++w) { G += sg[w]; H += sh[w]; }
             double f = 0.0;
-            y[c] = ccd::rank_one_new(G, lambda * (double)(z1 - z0) + H, y[c], do_nmf, &f);
+            y[c] = ccd::rank_one_new(G, lambda * (WT ? Wc[c] : (double)(z1 - z0)) + H, y[c], do_nmf, &f);
             part[blockIdx.x] = f;
         }
         return;
@@ -146,11 +154,12 @@ __global__ void __launch_bounds__(ccd::BLOCK) k_ccd_sweep(const CcdCtl* ctl, con
             double r = (double)res[z];
             if (addback) { const RT rn = (RT)fma(oldx[i], oy, r); res[z] = rn; r = (double)rn; }
             const double xi = x[i];
-            g += xi * r; h += xi * xi;
+            if (WT) { const double cx = (double)wt[z] * xi; g += cx * r; h += cx * xi; }
+            else { g += xi * r; h += xi * xi; }
         }
         g = ccd::wave_sum(g); h = ccd::wave_sum(h);
         if (lane == 0) {
-            if (z1 > z0) y[c] = ccd::rank_one_new(g, lambda * (double)(z1 - z0) + h, y[c], do_nmf, &f);
+            if (z1 > z0) y[c] = ccd::rank_one_new(g, lambda * (WT ? Wc[c] : (double)(z1 - z0)) + h, y[c], do_nmf, &f);
             else y[c] = 0.0;                                             // ccd-r1.cpp:9: an empty column returns 0, no fundec
         }
     }
@@ -161,6 +170,19 @@ __global__ void __launch_bounds__(ccd::BLOCK) k_ccd_sweep(const CcdCtl* ctl, con
         for (int w = 0; w < ccd::BLOCK / 64; ++w) F += sf[w];
         part[blockIdx.x] = F;
     }
+}
+template <typename RT>
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_sweep(const CcdCtl* ctl, const int64_t* ptr, const int32_t* idx, RT* res, const double* x,
+                                                          const double* oldx, const double* oldy, double* y, const int32_t* longs, int nlong,
+                                                          const int32_t* shorts, int nshort, double lambda, int do_nmf, int addback, double* part) {
+    ccd_sweep<RT, false>(ctl, ptr, idx, res, nullptr, nullptr, x, oldx, oldy, y, longs, nlong, shorts, nshort, lambda, do_nmf, addback, part);
+}
+template <typename RT>
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_sweep_w(const CcdCtl* ctl, const int64_t* ptr, const int32_t* idx, RT* res, const RT* wt,
+                                                            const double* Wc, const double* x, const double* oldx, const double* oldy, double* y,
+                                                            const int32_t* longs, int nlong, const int32_t* shorts, int nshort, double lambda,
+                                                            int do_nmf, int addback, double* part) {
+    ccd_sweep<RT, true>(ctl, ptr, idx, res, wt, Wc, x, oldx, oldy, y, longs, nlong, shorts, nshort, lambda, do_nmf, addback, part);
 }
 
 // The stopping test after both sweeps of inner iteration `iter` (ccd-r1.cpp:161-172): innerfundec_cur = v-side + u-side sums;
@@ -189,14 +211,15 @@ __global__ void __launch_bounds__(ccd::BLOCK) k_ccd_decide(CcdCtl* ctl, const do
 //                         reg partials nnz_i (u_i^2 - oldu_i^2) (:187-194)
 //   blocks [.., + Bv):    items: V[:, t] = v, reg partials
 //   blocks [.., + Bt):    test residuals tv -= u_i v_j - oldu_i oldv_j and their squares (util.cpp:206-215)
-template <typename T, typename RT>
-__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_resid(const CcdCtl* ctl, int B, int Bu, int Bv, int Bt, int64_t nnz, int64_t d1, int64_t d2, int64_t tn,
-                                                          RT* res_r, const int32_t* row_r, const int32_t* col_r,
-                                                          RT* res_c, const int32_t* row_c, const int32_t* col_c,
-                                                          const int64_t* uptr, const int64_t* cptr, const double* u, const double* oldu,
-                                                          const double* v, const double* oldv, T* U, T* V, int ld, int t,
-                                                          const int32_t* tu, const int32_t* ti, double* tres,
-                                                          double* p_loss, double* p_regu, double* p_regv, double* p_rmse, int addback) {
+// With WT: wt_r = the weights in CSR order (the loss is sum (c r) r over the CSR copy), Wu / Wv = the per-user / per-item sums of
+// c_z in the place of the counts in the reg partials; the residuals and the test segment do not see weights.
+template <typename T, typename RT, bool WT>
+__device__ __forceinline__ void ccd_resid(const CcdCtl* ctl, int B, int Bu, int Bv, int Bt, int64_t nnz, int64_t d1, int64_t d2, int64_t tn,
+                                          RT* res_r, const int32_t* row_r, const int32_t* col_r, RT* res_c, const int32_t* row_c,
+                                          const int32_t* col_c, const int64_t* uptr, const int64_t* cptr, const RT* wt_r, const double* Wu,
+                                          const double* Wv, const double* u, const double* oldu, const double* v, const double* oldv, T* U, T* V,
+                                          int ld, int t, const int32_t* tu, const int32_t* ti, double* tres, double* p_loss, double* p_regu,
+                                          double* p_regv, double* p_rmse, int addback) {
     if (ctl->skip) return;
     __shared__ double lds[ccd::BLOCK];
     int b = blockIdx.x;
@@ -215,7 +238,8 @@ __global__ void __launch_bounds__(ccd::BLOCK) k_ccd_resid(const CcdCtl* ctl, int
             const RT rn = (RT)fma(-ui, vj, (double)r0);
             res[z] = rn;
             const double r = (double)rn;
-            s += r * r;
+            if (WT) { if (csr) s += ((double)wt_r[z] * r) * r; }
+            else s += r * r;
         }
         if (!csr) return;
         out = p_loss;
@@ -223,7 +247,7 @@ __global__ void __launch_bounds__(ccd::BLOCK) k_ccd_resid(const CcdCtl* ctl, int
         for (int64_t i = (int64_t)b * ccd::BLOCK + threadIdx.x; i < d1; i += (int64_t)Bu * ccd::BLOCK) {
             const T x = (T)u[i];
             U[i * ld + t] = x;
-            const double n = (double)(uptr[i + 1] - uptr[i]), xd = (double)x;
+            const double n = WT ? Wu[i] : (double)(uptr[i + 1] - uptr[i]), xd = (double)x;
             s += n * (xd * xd) - n * (oldu[i] * oldu[i]);
         }
         out = p_regu;
@@ -231,7 +255,7 @@ __global__ void __launch_bounds__(ccd::BLOCK) k_ccd_resid(const CcdCtl* ctl, int
         for (int64_t j = (int64_t)b * ccd::BLOCK + threadIdx.x; j < d2; j += (int64_t)Bv * ccd::BLOCK) {
             const T x = (T)v[j];
             V[j * ld + t] = x;
-            const double n = (double)(cptr[j + 1] - cptr[j]), xd = (double)x;
+            const double n = WT ? Wv[j] : (double)(cptr[j + 1] - cptr[j]), xd = (double)x;
             s += n * xd * xd - n * oldv[j] * oldv[j];
         }
         out = p_regv;
@@ -248,6 +272,28 @@ __global__ void __launch_bounds__(ccd::BLOCK) k_ccd_resid(const CcdCtl* ctl, int
     }
     s = ccd::block_reduce(s, lds);
     if (threadIdx.x == 0) out[b] = s;
+}
+template <typename T, typename RT>
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_resid(const CcdCtl* ctl, int B, int Bu, int Bv, int Bt, int64_t nnz, int64_t d1, int64_t d2, int64_t tn,
+                                                          RT* res_r, const int32_t* row_r, const int32_t* col_r,
+                                                          RT* res_c, const int32_t* row_c, const int32_t* col_c,
+                                                          const int64_t* uptr, const int64_t* cptr, const double* u, const double* oldu,
+                                                          const double* v, const double* oldv, T* U, T* V, int ld, int t,
+                                                          const int32_t* tu, const int32_t* ti, double* tres,
+                                                          double* p_loss, double* p_regu, double* p_regv, double* p_rmse, int addback) {
+    ccd_resid<T, RT, false>(ctl, B, Bu, Bv, Bt, nnz, d1, d2, tn, res_r, row_r, col_r, res_c, row_c, col_c, uptr, cptr, nullptr, nullptr, nullptr,
+                            u, oldu, v, oldv, U, V, ld, t, tu, ti, tres, p_loss, p_regu, p_regv, p_rmse, addback);
+}
+template <typename T, typename RT>
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_resid_w(const CcdCtl* ctl, int B, int Bu, int Bv, int Bt, int64_t nnz, int64_t d1, int64_t d2,
+                                                            int64_t tn, RT* res_r, const int32_t* row_r, const int32_t* col_r, RT* res_c,
+                                                            const int32_t* row_c, const int32_t* col_c, const int64_t* uptr, const int64_t* cptr,
+                                                            const RT* wt_r, const double* Wu, const double* Wv, const double* u, const double* oldu,
+                                                            const double* v, const double* oldv, T* U, T* V, int ld, int t, const int32_t* tu,
+                                                            const int32_t* ti, double* tres, double* p_loss, double* p_regu, double* p_regv,
+                                                            double* p_rmse, int addback) {
+    ccd_resid<T, RT, true>(ctl, B, Bu, Bv, Bt, nnz, d1, d2, tn, res_r, row_r, col_r, res_c, row_c, col_c, uptr, cptr, wt_r, Wu, Wv, u, oldu, v,
+                           oldv, U, V, ld, t, tu, ti, tres, p_loss, p_regu, p_regv, p_rmse, addback);
 }
 
 // The rank's record (ccd-r1.cpp:180-199): reg += the item side then the user side, obj = loss + lambda reg, rmse over the test
@@ -276,17 +322,27 @@ __global__ void __launch_bounds__(ccd::BLOCK) k_ccd_final(CcdCtl* ctl, const dou
 
 // Start of training (ccd-r1.cpp:107-118): V = 0 (the reference zeroes H), residuals = ratings, test residuals = test ratings
 // (uploaded by the host), reg partials = sum_i nnz_i sum_t U_it^2
-template <typename T>
-__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_init(T* V, int64_t nV, const T* U, int k, int ld, const int64_t* uptr, int64_t d1, double* p_reg) {
+// (WT: sum_i W_i sum_t U_it^2, W_i = the user's sum of c_z)
+template <typename T, bool WT>
+__device__ __forceinline__ void ccd_init(T* V, int64_t nV, const T* U, int k, int ld, const int64_t* uptr, const double* Wu, int64_t d1, double* p_reg) {
     __shared__ double lds[ccd::BLOCK];
     for (int64_t i = (int64_t)blockIdx.x * ccd::BLOCK + threadIdx.x; i < nV; i += (int64_t)gridDim.x * ccd::BLOCK) V[i] = (T)0;
     double s = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * ccd::BLOCK + threadIdx.x; i < d1; i += (int64_t)gridDim.x * ccd::BLOCK) {
-        const double n = (double)(uptr[i + 1] - uptr[i]);
+        const double n = WT ? Wu[i] : (double)(uptr[i + 1] - uptr[i]);
         for (int t = 0; t < k; ++t) { const double x = (double)U[i * ld + t]; s += x * x * n; }
     }
     s = ccd::block_reduce(s, lds);
     if (threadIdx.x == 0) p_reg[blockIdx.x] = s;
+}
+template <typename T>
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_init(T* V, int64_t nV, const T* U, int k, int ld, const int64_t* uptr, int64_t d1, double* p_reg) {
+    ccd_init<T, false>(V, nV, U, k, ld, uptr, nullptr, d1, p_reg);
+}
+template <typename T>
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_init_w(T* V, int64_t nV, const T* U, int k, int ld, const int64_t* uptr, const double* Wu, int64_t d1,
+                                                           double* p_reg) {
+    ccd_init<T, true>(V, nV, U, k, ld, uptr, Wu, d1, p_reg);
 }
 __global__ void __launch_bounds__(ccd::BLOCK) k_ccd_init_fin(CcdCtl* ctl, const double* p_reg, int n) {
     __shared__ double lds[ccd::BLOCK];
@@ -331,6 +387,13 @@ struct CcdSolver final : pcr_solver {
     CcdCtl* h_ctl = nullptr;                          // pinned
     std::vector<RT> h_val_r, h_val_c;                 // the ratings in both orders (a training run starts from them)
     std::vector<double> h_tval;
+    // per-rating confidence weights (pcr_solver_set_rating_weights): c_z rounded to RT in both orders, each read by its
+    // sweep at the residual's index; W = their fp64 sums per user and per item, summed on the host in CSR / CSC order
+    bool weighted = false;
+    DBuf<RT> d_w_r, d_w_c;
+    DBuf<double> d_Wu, d_Wv;
+    std::vector<int32_t> h_c2r;
+    std::vector<int64_t> h_uptr, h_cptr;
     int nvb = 0, nub = 0, nilong = 0, nishort = 0, nulong = 0, nushort = 0;
     int B = 1, Bu = 1, Bv = 1, Bt = 1, Bi = 1;
     bool begun = false;
@@ -409,6 +472,7 @@ struct CcdSolver final : pcr_solver {
         B = parts(nnz); Bu = parts(d1); Bv = parts(d2); Bt = parts(tn); Bi = parts(d1);
         RC(d_cptr.upload(cptr, st));
         RC(d_row_r.upload(row_r, st)); RC(d_row_c.upload(row_c, st)); RC(d_col_c.upload(col_c, st)); RC(d_c2r.upload(c2r, st));
+        h_c2r.swap(c2r); h_cptr.swap(cptr); h_uptr.assign(X.index.begin(), X.index.begin() + d1 + 1);
         RC(d_ilong.upload(ilong, st)); RC(d_ishort.upload(ishort, st)); RC(d_ulong.upload(ulong, st)); RC(d_ushort.upload(ushort, st));
         RC(d_tu.upload(tu, st)); RC(d_ti.upload(ti, st));
         RC(d_res_r.alloc((size_t)nnz)); RC(d_res_c.alloc((size_t)nnz)); RC(d_tres.alloc((size_t)tn));
@@ -433,9 +497,13 @@ struct CcdSolver final : pcr_solver {
         HIPCHK(hipMemcpyAsync(d_res_c.p, h_val_c.data(), (size_t)nnz * sizeof(RT), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_tres.p, h_tval.data(), (size_t)tn * sizeof(double), hipMemcpyHostToDevice, st));
         {
-            ProfScope ps(&prof, "ccd/init", st);
-            hipLaunchKernelGGL((k_ccd_init<T>), dim3(Bi), dim3(ccd::BLOCK), 0, st, base->d_V.p, d2 * ld, (const T*)base->d_U.p, k, ld,
-                               (const int64_t*)base->d_uptr.p, d1, d_pregu.p);
+            ProfScope ps(&prof, weighted ? "ccd/init.w" : "ccd/init", st);
+            if (weighted)
+                hipLaunchKernelGGL((k_ccd_init_w<T>), dim3(Bi), dim3(ccd::BLOCK), 0, st, base->d_V.p, d2 * ld, (const T*)base->d_U.p, k, ld,
+                                   (const int64_t*)base->d_uptr.p, (const double*)d_Wu.p, d1, d_pregu.p);
+            else
+                hipLaunchKernelGGL((k_ccd_init<T>), dim3(Bi), dim3(ccd::BLOCK), 0, st, base->d_V.p, d2 * ld, (const T*)base->d_U.p, k, ld,
+                                   (const int64_t*)base->d_uptr.p, d1, d_pregu.p);
             hipLaunchKernelGGL(k_ccd_init_fin, dim3(1), dim3(ccd::BLOCK), 0, st, d_ctl.p, (const double*)d_pregu.p, Bi);
         }
         HIPCHK(hipGetLastError());
@@ -456,6 +524,22 @@ struct CcdSolver final : pcr_solver {
         }
         for (int iter = 1; iter <= T_in; ++iter) {
             const int addback = (iter == 1 && oi > 1) ? 1 : 0;          // ccd-r1.cpp:127-130, fused into the first sweeps
+            if (weighted) {
+                {
+                    ProfScope ps(&prof, "ccd/vsweep.w", st);
+                    hipLaunchKernelGGL((k_ccd_sweep_w<RT>), dim3(nvb), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, (const int64_t*)d_cptr.p,
+                                       (const int32_t*)d_row_c.p, d_res_c.p, (const RT*)d_w_c.p, (const double*)d_Wv.p, (const double*)d_u.p,
+                                       (const double*)d_oldu.p, (const double*)d_oldv.p, d_v.p, (const int32_t*)d_ilong.p, nilong,
+                                       (const int32_t*)d_ishort.p, nishort, prm.lambda, cp.do_nmf, addback, d_vpart.p);
+                }
+                {
+                    ProfScope ps(&prof, "ccd/usweep.w", st);
+                    hipLaunchKernelGGL((k_ccd_sweep_w<RT>), dim3(nub), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, (const int64_t*)base->d_uptr.p,
+                                       (const int32_t*)base->d_item.p, d_res_r.p, (const RT*)d_w_r.p, (const double*)d_Wu.p, (const double*)d_v.p,
+                                       (const double*)d_oldv.p, (const double*)d_oldu.p, d_u.p, (const int32_t*)d_ulong.p, nulong,
+                                       (const int32_t*)d_ushort.p, nushort, prm.lambda, cp.do_nmf, addback, d_upart.p);
+                }
+            } else {
             {
                 ProfScope ps(&prof, "ccd/vsweep", st);
                 hipLaunchKernelGGL((k_ccd_sweep<RT>), dim3(nvb), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, (const int64_t*)d_cptr.p,
@@ -468,13 +552,22 @@ struct CcdSolver final : pcr_solver {
                                    (const int32_t*)base->d_item.p, d_res_r.p, (const double*)d_v.p, (const double*)d_oldv.p, (const double*)d_oldu.p, d_u.p,
                                    (const int32_t*)d_ulong.p, nulong, (const int32_t*)d_ushort.p, nushort, prm.lambda, cp.do_nmf, addback, d_upart.p);
             }
+            }
             {
                 ProfScope ps(&prof, "ccd/decide", st);
                 hipLaunchKernelGGL(k_ccd_decide, dim3(1), dim3(ccd::BLOCK), 0, st, d_ctl.p, (const double*)d_vpart.p, nvb, (const double*)d_upart.p, nub,
                                    cp.eps, oi, t, iter);
             }
         }
-        {
+        if (weighted) {
+            ProfScope ps(&prof, "ccd/resid.w", st);
+            hipLaunchKernelGGL((k_ccd_resid_w<T, RT>), dim3(2 * B + Bu + Bv + Bt), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, B, Bu, Bv, Bt, nnz,
+                               d1, d2, tn, d_res_r.p, (const int32_t*)d_row_r.p, (const int32_t*)base->d_item.p, d_res_c.p, (const int32_t*)d_row_c.p,
+                               (const int32_t*)d_col_c.p, (const int64_t*)base->d_uptr.p, (const int64_t*)d_cptr.p, (const RT*)d_w_r.p,
+                               (const double*)d_Wu.p, (const double*)d_Wv.p, (const double*)d_u.p, (const double*)d_oldu.p, (const double*)d_v.p,
+                               (const double*)d_oldv.p, base->d_U.p, base->d_V.p, ld, t, (const int32_t*)d_tu.p, (const int32_t*)d_ti.p, d_tres.p,
+                               d_ploss.p, d_pregu.p, d_pregv.p, d_prmse.p, (T_in < 1 && oi > 1) ? 1 : 0);
+        } else {
             ProfScope ps(&prof, "ccd/resid", st);
             hipLaunchKernelGGL((k_ccd_resid<T, RT>), dim3(2 * B + Bu + Bv + Bt), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, B, Bu, Bv, Bt, nnz,
                                d1, d2, tn, d_res_r.p, (const int32_t*)d_row_r.p, (const int32_t*)base->d_item.p, d_res_c.p, (const int32_t*)d_row_c.p,
@@ -572,6 +665,42 @@ struct CcdSolver final : pcr_solver {
     }
 
     int set_factors(const double* U, const double* V, bool local) override { begun = false; return base->set_factors(U, V, local); }
+    // w: nnz weights in the training CSR's order, each finite and > 0 as given and as stored (rounded to RT, as the ratings are); NULL:
+    // the unweighted kernels.  Nothing is changed before every weight has passed.  Ends a running training, like set_factors.
+    int set_rating_weights(const double* w) override {
+        HIPCHK(hipStreamSynchronize(st));
+        if (!w) { weighted = false; begun = false; return PCR_OK; }
+        std::vector<RT> w_r((size_t)nnz), w_c((size_t)nnz);
+        for (int64_t z = 0; z < nnz; ++z) {
+            const bool in_range = w[z] > 0.0 && w[z] <= (double)std::numeric_limits<RT>::max();     // (NaN fails both)
+            const RT c = in_range ? (RT)w[z] : (RT)0;
+            if (!(c > (RT)0)) {
+                pcr_set_error("pcr_solver_set_rating_weights: the weight of training rating " + std::to_string(z) +
+                              " is not a finite number > 0 in the solver's precision");
+                return PCR_ERR_ARG;
+            }
+            w_r[(size_t)z] = c;
+        }
+        std::vector<double> Wu((size_t)d1, 0.0), Wv((size_t)d2, 0.0);
+        for (int64_t u = 0; u < d1; ++u) {
+            double s = 0.0;
+            for (int64_t z = h_uptr[(size_t)u]; z < h_uptr[(size_t)u + 1]; ++z) s += (double)w_r[(size_t)z];
+            Wu[(size_t)u] = s;
+        }
+        for (int64_t j = 0; j < d2; ++j) {                                // (CSC order: the entries of one item in user order)
+            double s = 0.0;
+            for (int64_t q = h_cptr[(size_t)j]; q < h_cptr[(size_t)j + 1]; ++q) {
+                w_c[(size_t)q] = w_r[(size_t)h_c2r[(size_t)q]];
+                s += (double)w_c[(size_t)q];
+            }
+            Wv[(size_t)j] = s;
+        }
+        RC(d_w_r.upload(w_r, st)); RC(d_w_c.upload(w_c, st)); RC(d_Wu.upload(Wu, st)); RC(d_Wv.upload(Wv, st));
+        weighted = true;
+        begun = false;
+        return PCR_OK;
+    }
+    int rating_weights_set(double* value) override { *value = weighted ? 1.0 : 0.0; return PCR_OK; }
     int get_factors(double* U, double* V, bool local) override { return base->get_factors(U, V, local); }
     int evaluate(int which, int ndcg_k, double* err, double* ndcg) override { return base->evaluate(which, ndcg_k, err, ndcg); }
     double ridge_lambda() override { return prm.lambda; }

@@ -231,6 +231,13 @@ struct pcr_solver {
     // CCDR1 only (pcr_ccd.h): the "ccd_residual_mismatch" counter, pcr_solver_set_ccd_params
     virtual int residual_mismatch(double*) { pcr_set_error("pcr_solver_counter: 'ccd_residual_mismatch' exists on a CCDR1 solver only"); return PCR_ERR_STATE; }
     virtual int set_ccd_params(const pcr_ccd_params*) { pcr_set_error("pcr_solver_set_ccd_params: not a CCDR1 solver (solver type 0)"); return PCR_ERR_STATE; }
+    // per-rating confidence weights (w: nnz, training-CSR order; NULL: unweighted) and the "ccd_rating_weights" counter
+    virtual int set_rating_weights(const double*) {
+        pcr_set_error("pcr_solver_set_rating_weights: per-rating weights exist for CCDR1 (solver type 0) only; PrimalCR / PrimalCR++ take "
+                      "per-user loss weights: pcr_solver_set_user_weights");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    virtual int rating_weights_set(double*) { pcr_set_error("pcr_solver_counter: 'ccd_rating_weights' exists on a CCDR1 solver only"); return PCR_ERR_STATE; }
     // the serving layer (pcr_serve.hip, pcr_fold.hip): the view of this solver's factors and shard, the exchange behind ServeView::sum (sync()
     // is ServeView::wait), the tables it keeps between calls
     virtual void serve_view(ServeView* v) = 0;

@@ -1017,6 +1017,60 @@ extern "C" int pcr_user_weights(const pcr_dataset* ds, int solver_type, int sche
     return PCR_OK;
 }
 
+// per-rating weights for CCDR1 (primalcr.h): (user, item, weight) triplets into the training CSR's order.  A user's items
+// ascend, so a triplet finds its rating by binary search.
+extern "C" int pcr_dataset_match_weights(const pcr_dataset* ds, int64_t n, const int32_t* user, const int32_t* item, const double* w, double* w_csr) {
+    if (!ds || n < 0 || (n > 0 && (!user || !item || !w)) || (!w_csr && ds->train.nnz() > 0)) {
+        pcr_set_error("pcr_dataset_match_weights: bad argument");
+        return PCR_ERR_ARG;
+    }
+    const PcrCsr& X = ds->train;
+    const int64_t nnz = X.nnz();
+    std::vector<char> seen((size_t)nnz, 0);
+    for (int64_t q = 0; q < n; ++q) {
+        const int64_t u = user[q], j = item[q];
+        const std::string who = "triplet " + std::to_string(q) + " (user " + std::to_string(u) + ", item " + std::to_string(j) + ")";
+        int64_t z = -1;
+        if (u >= 0 && u < X.d1 && j >= 0 && j < X.d2) {
+            const int32_t* lo = X.item.data() + X.index[(size_t)u];
+            const int32_t* hi = X.item.data() + X.index[(size_t)u + 1];
+            const int32_t* at = std::lower_bound(lo, hi, (int32_t)j);
+            if (at != hi && *at == (int32_t)j) z = at - X.item.data();
+        }
+        if (z < 0) { pcr_set_error("pcr_dataset_match_weights: " + who + " is not a training rating"); return PCR_ERR_ARG; }
+        if (seen[(size_t)z]) { pcr_set_error("pcr_dataset_match_weights: " + who + " names a training rating a second time"); return PCR_ERR_ARG; }
+        seen[(size_t)z] = 1;
+        w_csr[z] = w[q];
+    }
+    if (n < nnz) {
+        for (int64_t u = 0; u < X.d1; ++u)
+            for (int64_t z = X.index[(size_t)u]; z < X.index[(size_t)u + 1]; ++z)
+                if (!seen[(size_t)z]) {
+                    pcr_set_error("pcr_dataset_match_weights: the training rating (user " + std::to_string(u) + ", item " +
+                                  std::to_string(X.item[(size_t)z]) + ") is left without a weight");
+                    return PCR_ERR_ARG;
+                }
+    }
+    return PCR_OK;
+}
+
+// w_z = (n_max / n_item(z))^gamma: the inverse of a power-law propensity in the item's popularity; not normalised
+extern "C" int pcr_rating_weights_popularity(const pcr_dataset* ds, double gamma, double* w_csr) {
+    if (!ds || (!w_csr && ds->train.nnz() > 0)) { pcr_set_error("pcr_rating_weights_popularity: bad argument"); return PCR_ERR_ARG; }
+    if (!std::isfinite(gamma)) { pcr_set_error("pcr_rating_weights_popularity: gamma must be a finite number"); return PCR_ERR_ARG; }
+    const PcrCsr& X = ds->train;
+    const int64_t nnz = X.nnz();
+    std::vector<int64_t> cnt((size_t)X.d2, 0);
+    for (int64_t z = 0; z < nnz; ++z) cnt[(size_t)X.item[(size_t)z]]++;
+    int64_t nmax = 0;
+    for (int64_t c : cnt) nmax = std::max(nmax, c);
+    std::vector<double> wi((size_t)X.d2, 1.0);
+    for (int64_t j = 0; j < X.d2; ++j)
+        if (cnt[(size_t)j] > 0) wi[(size_t)j] = gamma == 0.0 ? 1.0 : std::pow((double)nmax / (double)cnt[(size_t)j], gamma);
+    for (int64_t z = 0; z < nnz; ++z) w_csr[z] = wi[(size_t)X.item[(size_t)z]];
+    return PCR_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // model file (pmf-train.cpp:297-310, util.cpp:30-79)
 // ------------------------------------------------------------------------------------------
