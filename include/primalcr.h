@@ -377,6 +377,23 @@ int pcr_solver_set_user_weights_local(pcr_solver *s, const double *w_local /* n_
  * model file do not carry weights.  PCR_ERR_UNSUPPORTED on a PrimalCR / PrimalCR++ solver (those take pcr_solver_set_user_weights). */
 int pcr_solver_set_rating_weights(pcr_solver *s, const double *w /* nnz, in the order of pcr_dataset_csr(ds, 0, ...) */);   /* [device] */
 
+/* Implicit feedback for CCDR1 (solver type 0): alpha > 0 is the weight of every UNRATED cell, whose target is 0.  From then on
+ * pcr_train / pcr_iterate solve
+ *     min sum_{z in Omega} c_z (r_z - u_i . v_j)^2 + alpha sum_{(i,j) not in Omega} (u_i . v_j)^2 + lambda (sum_i W_i |u_i|^2 + sum_j W_j |v_j|^2),
+ *     W_i = (the sum of c_z over user i's ratings) + alpha (d2 - n_i),  W_j likewise with d1 - n_j
+ * (c_z = the weights of pcr_solver_set_rating_weights, 1 when none are set): an unrated cell is exactly a rating 0 of weight alpha, in
+ * the regulariser too.  With rating weights 1 + a * count and alpha = 1 this is the confidence model of Hu, Koren and Volinsky.
+ * The d1 x d2 cells are never formed; while alpha is set the solver keeps two fp64 predictions per training rating on
+ * the device (16 bytes per rating, beside the two residual copies).  Every column is updated, an empty user or item too: training
+ * starts from V = 0, so its minimiser is exactly 0, and its step from the initial value counts in the stopping rule.  The printed loss / obj / reg and pcr_iter_stats.obj are those of this objective; the stopping rule, the test rmse,
+ * pcr_evaluate and "ccd_residual_mismatch" are unchanged.  alpha must be finite and >= 0; it is stored in the solver's precision
+ * and, when > 0 as given, must be > 0 as stored; else PCR_ERR_ARG and the solver keeps what it had.  0 returns to the explicit
+ * kernels.  Like pcr_solver_set_factors the call ends a running training; the setting survives pcr_solver_set_factors,
+ * pcr_solver_set_ccd_params and pcr_solver_set_rating_weights (and they survive it).  pcr_solver_counter "ccd_implicit" is the
+ * stored alpha (0 when off).  Fold-in, explanations and the model file do not carry alpha.  PCR_ERR_UNSUPPORTED on a PrimalCR /
+ * PrimalCR++ solver. */
+int pcr_solver_set_implicit(pcr_solver *s, double alpha);   /* [device] */
+
 /* pcrpp.cpp:17-35 comp_m_new (pcr.cpp:47 comp_m): m = u_i . v_j for every rating,
  * from the current device U, V; also builds the per-user (level, m)-sorted state
  * the sweeps use.  m_out (local nnz, CSR order) may be NULL. */

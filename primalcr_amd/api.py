@@ -217,6 +217,8 @@ def lib():
         L.pcr_dataset_match_weights.argtypes = [vp, i64, vp, vp, vp, vp]
         L.pcr_rating_weights_popularity.argtypes = [vp, cd, vp]
         L.pcr_solver_set_rating_weights.argtypes = [vp, vp]
+    if _LIB_OVERRIDE is None or hasattr(L, "pcr_solver_set_implicit"):
+        L.pcr_solver_set_implicit.argtypes = [vp, cd]
     L.pcr_model_save.argtypes = [C.c_char_p, _dp, i64, _dp, i64, i64]
     L.pcr_model_load.argtypes = [C.c_char_p, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp, vp]
     L.pcr_partition_users.argtypes = [_lp, i64, ci, _lp]
@@ -1394,6 +1396,13 @@ class Solver:
         if w.shape != (self.nnz,):
             raise ValueError(f"w must hold {self.nnz} weights")
         _chk(lib().pcr_solver_set_rating_weights(self._h, w.ctypes.data))
+
+    def set_implicit(self, alpha):
+        """Implicit feedback (CCDR1): every unrated cell becomes a rating 0 of weight alpha > 0, in the loss and in the regulariser
+        (W = a row's total weight, the unrated cells included); with set_rating_weights(1 + a * count) and alpha = 1 this is the
+        confidence model of Hu, Koren and Volinsky.  alpha: finite and >= 0, stored in the solver's precision; 0 returns to the
+        explicit kernels.  Ends a running training like set_factors; survives set_factors, set_ccd_params and set_rating_weights."""
+        _chk(lib().pcr_solver_set_implicit(self._h, float(alpha)))
 
     def get_factors_local(self):
         U = np.zeros((self.n_users, self.k)); V = np.zeros((self.d2, self.k))

@@ -30,6 +30,9 @@
 //   --popularity-weights G  the weights of pcr_rating_weights_popularity instead: (n_max / n_item)^G.  Not together with
 //                     --rating-weights, --user-weights or --normalize.  The log lines keep their format; loss / obj / reg are the
 //                     weighted ones.
+//   --implicit A      implicit feedback (pcr_solver_set_implicit; -s 0 only): every unrated cell is a rating 0 of weight A (finite,
+//                     >= 0; 0: the explicit problem).  Combines with --rating-weights / --popularity-weights: ratings of 1, weights
+//                     1 + a * count and --implicit 1 are the confidence model of Hu, Koren and Volinsky.
 //   --tune key=value  a launch knob of pcr_tune() (repeatable)
 //   --timing          one "[timing] load_s=... init_s=... create_s=... train_s=... iter_s=... eval_s=... write_s=... wall_s=..." line
 //                     on stderr at the end: where the run's wall time went (iter_s = the reference's own "Iter k time" clock,
@@ -44,6 +47,7 @@
 #include <csignal>
 #include <fstream>
 #include <iostream>
+#include <limits>
 #include <string>
 #include <thread>
 #include <vector>
@@ -84,6 +88,7 @@ static void exit_with_help() {
         "    --normalize pairs|ratings : weight every user by 1 / its pairs (ratings), total mass kept (not with --user-weights)\n"
         "    --rating-weights file : per-rating confidence weights, lines of 'user item weight' as in a ratings file (-s 0)\n"
         "    --popularity-weights gamma : weight every rating by (n_max / n_item)^gamma (-s 0; not with --rating-weights)\n"
+        "    --implicit alpha : implicit feedback: every unrated cell is a rating 0 of weight alpha (-s 0)\n"
         "    --tune key=value : launch knob (pcr_tune)\n"
         "    --timing : print the phases of the run's wall time on stderr\n");
     exit(1);
@@ -389,7 +394,8 @@ static int train_multi(const pcr_dataset* ds, const pcr_params& param, int gpus,
 // pmf-train.cpp:138-172 run_ccdr1(): "starts!", the per-rank lines of ccdr1(), "Wall-time: %lg secs", the model; no side files
 static int run_ccdr1(pcr_dataset* ds, pcr_params param, const pcr_ccd_params& ccd, const std::vector<int>& devices, const std::string& model,
                      std::vector<double>& U, std::vector<double>& V, int64_t d1, int64_t d2, bool timing, double load_s, double init_s,
-                     std::chrono::steady_clock::time_point t_main, const std::vector<double>& rating_weights) {
+                     std::chrono::steady_clock::time_point t_main, const std::vector<double>& rating_weights,
+                     double implicit_alpha) {
     auto t_lap = std::chrono::steady_clock::now();
     auto lap = [&]() { const auto n = std::chrono::steady_clock::now(); const double d = std::chrono::duration<double>(n - t_lap).count(); t_lap = n; return d; };
     struct Holder { pcr_solver* s; ~Holder() { if (s) pcr_solver_destroy(s); } } hold{nullptr};      // (the caller owns ds)
@@ -404,6 +410,7 @@ static int run_ccdr1(pcr_dataset* ds, pcr_params param, const pcr_ccd_params& cc
     if (pcr_solver_set_ccd_params(s, &ccd) != PCR_OK) return fail("solver");
     if (pcr_solver_set_factors(s, U.data(), nullptr) != PCR_OK) return fail("set_factors");
     if (!rating_weights.empty() && pcr_solver_set_rating_weights(s, rating_weights.data()) != PCR_OK) return fail("rating weights");
+    if (implicit_alpha > 0.0 && pcr_solver_set_implicit(s, implicit_alpha) != PCR_OK) return fail("implicit");
     const double create_s = lap();
     std::vector<pcr_iter_stats> hist((size_t)std::max(0, param.maxiter) + 1);
     if (pcr_train(s, nullptr, nullptr, hist.data()) != PCR_OK) return fail("train");
@@ -431,7 +438,7 @@ int main(int argc, char** argv) {
     pcr_params_default(&param);
     pcr_ccd_params ccd;
     pcr_ccd_params_default(&ccd);
-    std::string init_model, cache, comm_kind = "rccl", weights_file, normalize, rating_weights_file, popularity;
+    std::string init_model, cache, comm_kind = "rccl", weights_file, normalize, rating_weights_file, popularity, implicit;
     std::vector<int> devices;
     int snapshot_every = 0, gpus = 1;
     int i;
@@ -452,6 +459,7 @@ int main(int argc, char** argv) {
         if (!strcmp(argv[i - 1], "--normalize")) { normalize = argv[i]; continue; }
         if (!strcmp(argv[i - 1], "--rating-weights")) { rating_weights_file = argv[i]; continue; }
         if (!strcmp(argv[i - 1], "--popularity-weights")) { popularity = argv[i]; continue; }
+        if (!strcmp(argv[i - 1], "--implicit")) { implicit = argv[i]; continue; }
         if (!strcmp(argv[i - 1], "--devices")) {
             for (const char* q = argv[i]; *q;) { devices.push_back(atoi(q)); while (*q && *q != ',') ++q; if (*q == ',') ++q; }
             continue;
@@ -520,6 +528,25 @@ int main(int argc, char** argv) {
             }
         }
     }
+    double implicit_alpha = 0.0;
+    if (!implicit.empty()) {                                         // implicit feedback: CCDR1's alone, refused before any device work
+        if (param.solver_type != PCR_SOLVER_CCDR1) {
+            fprintf(stderr, "omp-pmf-train: --implicit needs -s 0 (CCDR1); the ranking losses of -s 1 and -s 2 have no term for an unrated cell\n");
+            return 1;
+        }
+        char* end = nullptr;
+        implicit_alpha = strtod(implicit.c_str(), &end);
+        if (end == implicit.c_str() || *end != '\0' || !(implicit_alpha - implicit_alpha == 0.0) || implicit_alpha < 0.0) {
+            fprintf(stderr, "omp-pmf-train: --implicit '%s' is not a finite number >= 0\n", implicit.c_str());
+            return 1;
+        }
+        // alpha is stored in the solver's precision: without --f64 a value > 0 that is 0 or infinite as a float is refused here too
+        if (param.precision != PCR_F64 && implicit_alpha > 0.0 &&
+            (implicit_alpha > (double)std::numeric_limits<float>::max() || !((float)implicit_alpha > 0.0f))) {
+            fprintf(stderr, "omp-pmf-train: --implicit '%s' is not a finite number > 0 in fp32 storage (use --f64)\n", implicit.c_str());
+            return 1;
+        }
+    }
     if (param.solver_type == PCR_SOLVER_CCDR1) {                     // options CCDR1 does not have: refused, never ignored
         const char* bad = gpus != 1 ? "--gpus" : devices.size() > 1 ? "--devices with more than one device" : !init_model.empty() ? "--init-model"
                         : snapshot_every != 0 ? "--snapshot-every" : !weights_file.empty() ? "--user-weights" : !normalize.empty() ? "--normalize" : nullptr;
@@ -566,7 +593,7 @@ int main(int argc, char** argv) {
             if (pcr_rating_weights_popularity(ds, gamma, rw.data()) != PCR_OK) die("--popularity-weights");
         }
         pcr_initial_col(U.data(), d1, k);              // pmf-train.cpp:156-158 (H is zeroed by ccdr1 itself, ccd-r1.cpp:116)
-        return run_ccdr1(ds, param, ccd, devices, model, U, V, d1, d2, timing, load_s, lap() , t_main, rw);
+        return run_ccdr1(ds, param, ccd, devices, model, U, V, d1, d2, timing, load_s, lap() , t_main, rw, implicit_alpha);
     }
     std::vector<double> weights;                       // per-user loss weights (empty: the reference's unweighted problem)
     if (!weights_file.empty()) {

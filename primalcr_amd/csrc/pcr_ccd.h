@@ -12,7 +12,9 @@
 //     needs a host round trip;
 //   * optionally one confidence weight per rating (pcr_solver_set_rating_weights): in both orders next to the two
 //     residual copies, in their storage type, and the fp64 sums W per user and per item that stand where the rating counts stood;
-//     the weighted launches are the _w kernels, the unweighted ones keep their symbols and code.
+//     the weighted launches are the _w kernels, the unweighted ones keep their symbols and code;
+//   * optionally a weight alpha on every UNRATED cell (pcr_solver_set_implicit): kernels of their own (_i) further
+//     down, 7 T + 5 launches per rank.
 // Kernels per rank: k_ccd_begin, then per inner iteration k_ccd_sweep over the CSC (v), k_ccd_sweep over the
 // CSR (u) and k_ccd_decide, then k_ccd_resid and k_ccd_final: 3 T + 3 launches.  Every sum is accumulated in fp64 and reduced in
 // a fixed order (per-block partials summed by one block): results do not depend on timing and repeat bit for bit.
@@ -354,6 +356,262 @@ __global__ void __launch_bounds__(ccd::BLOCK) k_ccd_init_fin(CcdCtl* ctl, const 
     ctl->inner_iters = 0; ctl->ranks_done = 0; ctl->printed = 0;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// Implicit feedback (pcr_solver_set_implicit): every unrated cell is a rating 0 of weight alpha.  The sums over all
+// d1 x d2 cells are never formed: with x the other side's work vector and s = Fother^T x (a k-vector), the all-cells sum of
+// x_i p^_ic of column c (p^ = the prediction without rank t) is q_c = sum_{s != t} F[c, s] s[s], and the all-cells sum of x^2 is
+// one number Sxx; the rated cells are then taken back out of both next to the residual:
+//   g = sum_Omega (c x) r^ - alpha (q_c - sum_Omega x p^),   h = lambda W_c + sum_Omega (c - alpha) x^2 + alpha Sxx,
+// with p^ at a rated cell from an fp64 prediction kept per rating (see ccd_sweep_i),
+// W_c = the column's sum of c_z + alpha (d - n_c).  Every term carries exactly one factor out of (c, alpha): scaling both by one
+// power of two scales g, h, fundec, loss and reg exactly and leaves g / h.
+namespace ccd {
+constexpr int GRAM_ROWS = 64;       // the Gram-column kernel runs ceil(d / GRAM_ROWS) row blocks, i.e. that many partials per entry: a block
+                                    // takes BLOCK / KW rows per step, strided over the grid, so at KW <= 2 most blocks find no row and
+                                    // write zero partials, and at k = 100 a thread walks about 32 rows in sequence (follow-up: size the
+                                    // partials from d * KW / BLOCK)
+constexpr int GRAM_PART_MAX = 512;  // its row blocks (fixed by the shape, never by the device)
+}  // namespace ccd
+
+// s = F^T x and sum x^2 as per-block partials: part[b * (k + 1) + c] = the block's share of s[c], part[b * (k + 1) + k] of sum x^2.
+// F is d x ld in the storage type, x fp64 -- or, with x == nullptr, F's own stored column xcol (the end-of-rank refresh of a Gram
+// matrix's row).  KW = the power of two >= min(k, BLOCK) lanes run along a row's contiguous values, BLOCK / KW rows side by side;
+// blockIdx.y takes the columns [y KW, (y + 1) KW) (one value of y up to k = 256).  A thread walks its rows b RPB + rr, + gridDim.x
+// RPB, ... in order; the rows of one column meet in a fixed LDS tree.  `live`: 1 = inside the inner iterations (a broken rank's
+// launches exit at entry), 0 = after them (a skipped rank's exit), -1 = at the start of training (the control block is not read).
+template <typename T>
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_gramcol(const CcdCtl* ctl, int live, const T* F, int64_t d, int k, int ld, int kw, const double* x,
+                                                            int xcol, double* part) {
+    if (live >= 0 && (ctl->skip || (live && ctl->broken))) return;
+    __shared__ double ls[ccd::BLOCK], lq[ccd::BLOCK];
+    const int rpb = ccd::BLOCK / kw;
+    const int cc = threadIdx.x & (kw - 1), rr = threadIdx.x / kw;
+    const int c = blockIdx.y * kw + cc;
+    const bool sq = cc == 0 && blockIdx.y == 0;
+    double a = 0.0, q = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * rpb + rr; i < d; i += (int64_t)gridDim.x * rpb) {
+        const double xi = x ? x[i] : (double)F[i * ld + xcol];
+        if (c < k) a += (double)F[i * ld + c] * xi;
+        if (sq) q += xi * xi;
+    }
+    ls[threadIdx.x] = a; lq[threadIdx.x] = q;
+    __syncthreads();
+    for (int w = rpb / 2; w > 0; w >>= 1) {
+        if (rr < w) { ls[threadIdx.x] += ls[threadIdx.x + w * kw]; lq[threadIdx.x] += lq[threadIdx.x + w * kw]; }
+        __syncthreads();
+    }
+    if (rr == 0) {
+        if (c < k) part[(int64_t)blockIdx.x * (k + 1) + c] = ls[threadIdx.x];
+        if (sq) part[(int64_t)blockIdx.x * (k + 1) + k] = lq[threadIdx.x];
+    }
+}
+// s[c] = the partials of c in block order, c = 0 .. k (k: sum x^2); with G (k x k, at the start of training) row and column t of G
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_gramred(const CcdCtl* ctl, int live, const double* part, int P, int k, double* s, double* G, int t) {
+    if (live > 0 && (ctl->skip || ctl->broken)) return;
+    for (int c = threadIdx.x; c <= k; c += ccd::BLOCK) {
+        double a = 0.0;
+        for (int b = 0; b < P; ++b) a += part[(int64_t)b * (k + 1) + c];
+        if (s) s[c] = a;
+        if (G && c < k) { G[(int64_t)t * k + c] = a; G[(int64_t)c * k + t] = a; }
+    }
+}
+
+// k_ccd_sweep under implicit feedback.  pd = the fp64 prediction u_i . v_j of the stored factors at every rated cell, in this
+// orientation's order (next to the residual; k_ccd_resid_i keeps it): p^ = pd - oldx oldy is the prediction without rank t, so the rated
+// cells leave the all-cells sum q_c as S = sum_Omega x p^ (the stored residual cannot give p^: in fp32 it carries its own rounding).
+// F = this side's stored factors (the column's own row, one coalesced read by the wave that owns the column), sv = k_ccd_gramred's s and Sxx of the
+// other side's CURRENT work vector, Wc = the column's total weight.  Every column is updated, an empty one too (its h is
+// lambda W_c + alpha Sxx > 0).  WT: weights c_z in wt, else c = 1.
+template <typename T, typename RT, bool WT>
+__device__ __forceinline__ void ccd_sweep_i(const CcdCtl* ctl, const int64_t* ptr, const int32_t* idx, RT* res, const double* pd, const RT* wt,
+                                            const double* Wc, const T* F, int ld, int k, int t, const double* sv, double alpha, const double* x,
+                                            const double* oldx, const double* oldy, double* y, const int32_t* longs, int nlong,
+                                            const int32_t* shorts, int nshort, double lambda, int do_nmf, int addback, double* part) {
+    if (ctl->skip || ctl->broken) return;
+    __shared__ double sg[ccd::BLOCK / 64], sh[ccd::BLOCK / 64], sf[ccd::BLOCK / 64], sp[ccd::BLOCK / 64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const bool is_long = (int)blockIdx.x < nlong;
+    const int64_t s = is_long ? 0 : (int64_t)(blockIdx.x - nlong) * (ccd::BLOCK / 64) + wv;
+    const bool have = is_long || s < nshort;
+    double f = 0.0;
+    if (have) {
+        const int c = is_long ? longs[blockIdx.x] : shorts[s];
+        const int64_t z0 = ptr[c], z1 = ptr[c + 1];
+        const double oy = oldy[c];
+        double g = 0.0, h = 0.0, S = 0.0;
+        const int step = is_long ? ccd::BLOCK : 64;
+        for (int64_t z = z0 + (is_long ? (int)threadIdx.x : lane); z < z1; z += step) {
+            const int i = idx[z];
+            double r = (double)res[z];
+            const double ox = oldx[i];
+            if (addback) { const RT rn = (RT)fma(ox, oy, r); res[z] = rn; r = (double)rn; }
+            const double xi = x[i], cz = WT ? (double)wt[z] : 1.0;
+            g += (cz * xi) * r;
+            S += xi * fma(-ox, oy, pd[z]);
+            h += ((cz - alpha) * xi) * xi;
+        }
+        double q = 0.0;
+        if (!is_long || wv == 0)
+            for (int j = lane; j < k; j += 64)
+                if (j != t) q += (double)F[(int64_t)c * ld + j] * sv[j];
+        g = ccd::wave_sum(g); h = ccd::wave_sum(h); S = ccd::wave_sum(S); q = ccd::wave_sum(q);
+        if (is_long) {
+            if (lane == 0) { sg[wv] = g; sh[wv] = h; sp[wv] = S; }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                double G = 0.0, H = 0.0, SS = 0.0;
+                for (int w = 0; w < ccd::BLOCK / 64; ++w) { G += sg[w]; H += sh[w]; SS += sp[w]; }
+                y[c] = ccd::rank_one_new(G - alpha * (q - SS), lambda * Wc[c] + H + alpha * sv[k], y[c], do_nmf, &f);
+                part[blockIdx.x] = f;
+            }
+            return;
+        }
+        if (lane == 0) y[c] = ccd::rank_one_new(g - alpha * (q - S), lambda * Wc[c] + h + alpha * sv[k], y[c], do_nmf, &f);
+    }
+    if (lane == 0) sf[wv] = f;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double Fs = 0.0;
+        for (int w = 0; w < ccd::BLOCK / 64; ++w) Fs += sf[w];
+        part[blockIdx.x] = Fs;
+    }
+}
+template <typename T, typename RT>
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_sweep_i(const CcdCtl* ctl, const int64_t* ptr, const int32_t* idx, RT* res, const double* pd,
+                                                            const double* Wc, const T* F, int ld, int k, int t, const double* sv, double alpha,
+                                                            const double* x, const double* oldx, const double* oldy, double* y,
+                                                            const int32_t* longs, int nlong, const int32_t* shorts, int nshort, double lambda,
+                                                            int do_nmf, int addback, double* part) {
+    ccd_sweep_i<T, RT, false>(ctl, ptr, idx, res, pd, nullptr, Wc, F, ld, k, t, sv, alpha, x, oldx, oldy, y, longs, nlong, shorts, nshort, lambda,
+                              do_nmf, addback, part);
+}
+template <typename T, typename RT>
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_sweep_iw(const CcdCtl* ctl, const int64_t* ptr, const int32_t* idx, RT* res, const double* pd,
+                                                             const RT* wt, const double* Wc, const T* F, int ld, int k, int t, const double* sv,
+                                                             double alpha, const double* x, const double* oldx, const double* oldy, double* y,
+                                                             const int32_t* longs, int nlong, const int32_t* shorts, int nshort, double lambda,
+                                                             int do_nmf, int addback, double* part) {
+    ccd_sweep_i<T, RT, true>(ctl, ptr, idx, res, pd, wt, Wc, F, ld, k, t, sv, alpha, x, oldx, oldy, y, longs, nlong, shorts, nshort, lambda,
+                             do_nmf, addback, part);
+}
+
+// k_ccd_resid under implicit feedback: the same segments; the loss partials are the rated cells' share of the objective,
+// sum (c r) r - (alpha p) p with p the prediction at a rated cell (k_ccd_final_i adds alpha sum_all p^2 from the Gram matrices);
+// pd_r / pd_c = that prediction in fp64 in CSR / CSC order, both moved by the same expression from rank t's old term to its stored new
+// one (0 at the start of training, where V = 0); wt_r = the weights in CSR order or nullptr (c = 1); Wu / Wv = the total weights.
+template <typename T, typename RT>
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_resid_i(const CcdCtl* ctl, int B, int Bu, int Bv, int Bt, int64_t nnz, int64_t d1, int64_t d2,
+                                                            int64_t tn, RT* res_r, const int32_t* row_r, const int32_t* col_r, RT* res_c,
+                                                            const int32_t* row_c, const int32_t* col_c, double* pd_r, double* pd_c, const RT* wt_r, double alpha,
+                                                            const double* Wu, const double* Wv, const double* u, const double* oldu, const double* v,
+                                                            const double* oldv, T* U, T* V, int ld, int t, const int32_t* tu, const int32_t* ti,
+                                                            double* tres, double* p_loss, double* p_regu, double* p_regv, double* p_rmse,
+                                                            int addback) {
+    if (ctl->skip) return;
+    __shared__ double lds[ccd::BLOCK];
+    int b = blockIdx.x;
+    double s = 0.0;
+    double* out = nullptr;
+    if (b < 2 * B) {
+        const bool csr = b < B;
+        if (!csr) b -= B;
+        RT* res = csr ? res_r : res_c;
+        const int32_t* rr = csr ? row_r : row_c;
+        const int32_t* cc = csr ? col_r : col_c;
+        double* pd = csr ? pd_r : pd_c;
+        for (int64_t z = (int64_t)b * ccd::BLOCK + threadIdx.x; z < nnz; z += (int64_t)B * ccd::BLOCK) {
+            const double ui = (double)(T)u[rr[z]], vj = (double)(T)v[cc[z]];
+            const double ou = oldu[rr[z]], ov = oldv[cc[z]];
+            RT r0 = res[z];
+            if (addback) r0 = (RT)fma(ou, ov, (double)r0);
+            const RT rn = (RT)fma(-ui, vj, (double)r0);
+            res[z] = rn;
+            const double p = fma(ui, vj, fma(-ou, ov, pd[z]));
+            pd[z] = p;
+            if (csr) {
+                const double r = (double)rn;
+                s += ((wt_r ? (double)wt_r[z] : 1.0) * r) * r - (alpha * p) * p;
+            }
+        }
+        if (!csr) return;
+        out = p_loss;
+    } else if ((b -= 2 * B) < Bu) {
+        for (int64_t i = (int64_t)b * ccd::BLOCK + threadIdx.x; i < d1; i += (int64_t)Bu * ccd::BLOCK) {
+            const T x = (T)u[i];
+            U[i * ld + t] = x;
+            const double n = Wu[i], xd = (double)x;
+            s += n * (xd * xd) - n * (oldu[i] * oldu[i]);
+        }
+        out = p_regu;
+    } else if ((b -= Bu) < Bv) {
+        for (int64_t j = (int64_t)b * ccd::BLOCK + threadIdx.x; j < d2; j += (int64_t)Bv * ccd::BLOCK) {
+            const T x = (T)v[j];
+            V[j * ld + t] = x;
+            const double n = Wv[j], xd = (double)x;
+            s += n * xd * xd - n * oldv[j] * oldv[j];
+        }
+        out = p_regv;
+    } else {
+        b -= Bv;
+        for (int64_t z = (int64_t)b * ccd::BLOCK + threadIdx.x; z < tn; z += (int64_t)Bt * ccd::BLOCK) {
+            const int i = tu[z], j = ti[z];
+            if (i < 0) { s += tres[z] * tres[z]; continue; }
+            const double r = tres[z] - ((double)(T)u[i] * (double)(T)v[j] - oldu[i] * oldv[j]);
+            tres[z] = r;
+            s += r * r;
+        }
+        out = p_rmse;
+    }
+    s = ccd::block_reduce(s, lds);
+    if (threadIdx.x == 0) out[b] = s;
+}
+
+// k_ccd_final under implicit feedback.  gu / gv = k_ccd_gramcol's partials of the STORED column t of U and of V (Pu / Pv blocks):
+// row and column t of the two k x k fp64 Gram matrices GU = U^T U, GV = V^T V are refreshed from them, then
+// loss = the rated cells' share + alpha sum_{s, s'} GU[s, s'] GV[s, s']  (= alpha times the sum of p^2 over ALL cells).
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_final_i(CcdCtl* ctl, const double* p_loss, int B, const double* p_regu, int Bu, const double* p_regv,
+                                                            int Bv, const double* p_rmse, int Bt, int64_t tn, double lambda, double alpha,
+                                                            const double* gu, int Pu, const double* gv, int Pv, double* GU, double* GV, int k, int t) {
+    __shared__ double lds[ccd::BLOCK];
+    if (ctl->skip) {
+        if (threadIdx.x == 0) ctl->printed = 0;
+        return;
+    }
+    for (int c = threadIdx.x; c < k; c += ccd::BLOCK) {
+        double a = 0.0, b = 0.0;
+        for (int p = 0; p < Pu; ++p) a += gu[(int64_t)p * (k + 1) + c];
+        for (int p = 0; p < Pv; ++p) b += gv[(int64_t)p * (k + 1) + c];
+        GU[(int64_t)t * k + c] = a; GU[(int64_t)c * k + t] = a;
+        GV[(int64_t)t * k + c] = b; GV[(int64_t)c * k + t] = b;
+    }
+    __syncthreads();
+    double dot = 0.0;
+    for (int i = threadIdx.x; i < k * k; i += ccd::BLOCK) dot += GU[i] * GV[i];
+    dot = ccd::block_reduce(dot, lds);
+    const double loss = ccd::block_sum_fixed(p_loss, B, lds) + alpha * dot;
+    const double rv = ccd::block_sum_fixed(p_regv, Bv, lds);
+    const double ru = ccd::block_sum_fixed(p_regu, Bu, lds);
+    const double se = ccd::block_sum_fixed(p_rmse, Bt, lds);
+    if (threadIdx.x != 0) return;
+    ctl->reg += rv;
+    ctl->reg += ru;
+    ctl->loss = loss;
+    ctl->oldobj = ctl->obj;
+    ctl->obj = loss + ctl->reg * lambda;
+    ctl->rmse = tn > 0 ? sqrt(se / (double)tn) : 0.0;
+    ctl->ranks_done += 1;
+    ctl->printed = 1;
+}
+
+// k_ccd_init under implicit feedback: reg = sum_i W_i sum_t U_it^2 with the total weights, V = 0 and with it V^T V = 0
+template <typename T>
+__global__ void __launch_bounds__(ccd::BLOCK) k_ccd_init_i(T* V, int64_t nV, const T* U, int k, int ld, const int64_t* uptr, const double* Wu, int64_t d1,
+                                                           double* p_reg, double* GV) {
+    if (blockIdx.x == 0)
+        for (int i = threadIdx.x; i < k * k; i += ccd::BLOCK) GV[i] = 0.0;
+    ccd_init<T, true>(V, nV, U, k, ld, uptr, Wu, d1, p_reg);
+}
+
 // the "ccd_residual_mismatch" diagnostic: positions where the CSC copy differs from the CSR copy, bit for bit
 template <typename RT>
 __global__ void __launch_bounds__(ccd::BLOCK) k_ccd_mismatch(const RT* res_r, const RT* res_c, const int32_t* c2r, int64_t nnz, double* part) {
@@ -394,6 +652,14 @@ struct CcdSolver final : pcr_solver {
     DBuf<double> d_Wu, d_Wv;
     std::vector<int32_t> h_c2r;
     std::vector<int64_t> h_uptr, h_cptr;
+    // implicit feedback (pcr_solver_set_implicit): alpha as stored (rounded to RT; 0 = off), the fp64 predictions next to both
+    // residual copies, the total weights W = Wobs + alpha (d - n) summed on the host, the Gram-column partials and reduced k-vectors of
+    // both sides (k + 1 values: s and sum x^2) and the two k x k fp64 Gram matrices behind the loss
+    double alpha = 0.0;
+    std::vector<double> h_Wu, h_Wv;                   // Wobs while weights are set
+    DBuf<double> d_pd_r, d_pd_c;
+    DBuf<double> d_Wiu, d_Wiv, d_gpu, d_gpv, d_su, d_sv, d_GU, d_GV;
+    int Pu = 1, Pv = 1, kw = 1;
     int nvb = 0, nub = 0, nilong = 0, nishort = 0, nulong = 0, nushort = 0;
     int B = 1, Bu = 1, Bv = 1, Bt = 1, Bi = 1;
     bool begun = false;
@@ -496,7 +762,20 @@ struct CcdSolver final : pcr_solver {
         HIPCHK(hipMemcpyAsync(d_res_r.p, h_val_r.data(), (size_t)nnz * sizeof(RT), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_res_c.p, h_val_c.data(), (size_t)nnz * sizeof(RT), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_tres.p, h_tval.data(), (size_t)tn * sizeof(double), hipMemcpyHostToDevice, st));
-        {
+        if (alpha > 0.0) {
+            HIPCHK(hipMemsetAsync(d_pd_r.p, 0, (size_t)nnz * sizeof(double), st));       // V = 0: every prediction is 0
+            HIPCHK(hipMemsetAsync(d_pd_c.p, 0, (size_t)nnz * sizeof(double), st));
+            // reg from the total weights, V^T V = 0; U^T U once, a row per stored column
+            ProfScope ps(&prof, "ccd/init.i", st);
+            hipLaunchKernelGGL((k_ccd_init_i<T>), dim3(Bi), dim3(ccd::BLOCK), 0, st, base->d_V.p, d2 * ld, (const T*)base->d_U.p, k, ld,
+                               (const int64_t*)base->d_uptr.p, (const double*)d_Wiu.p, d1, d_pregu.p, d_GV.p);
+            hipLaunchKernelGGL(k_ccd_init_fin, dim3(1), dim3(ccd::BLOCK), 0, st, d_ctl.p, (const double*)d_pregu.p, Bi);
+            for (int t = 0; t < k; ++t) {
+                gramcol(-1, (const T*)base->d_U.p, d1, Pu, nullptr, t, d_gpu.p);
+                hipLaunchKernelGGL(k_ccd_gramred, dim3(1), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, 0, (const double*)d_gpu.p, Pu, k,
+                                   (double*)nullptr, d_GU.p, t);
+            }
+        } else {
             ProfScope ps(&prof, weighted ? "ccd/init.w" : "ccd/init", st);
             if (weighted)
                 hipLaunchKernelGGL((k_ccd_init_w<T>), dim3(Bi), dim3(ccd::BLOCK), 0, st, base->d_V.p, d2 * ld, (const T*)base->d_U.p, k, ld,
@@ -513,8 +792,87 @@ struct CcdSolver final : pcr_solver {
         secs = 0.0;
         return PCR_OK;
     }
+    static int gram_parts(int64_t d) { return (int)std::max<int64_t>(1, std::min<int64_t>(ccd::GRAM_PART_MAX, (d + ccd::GRAM_ROWS - 1) / ccd::GRAM_ROWS)); }
+    void gramcol(int live, const T* F, int64_t d, int P, const double* x, int xcol, double* part) {
+        hipLaunchKernelGGL((k_ccd_gramcol<T>), dim3(P, cdiv(k, kw)), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, live, F, d, k, ld, kw, x, xcol, part);
+    }
+    // s = F^T x and sum x^2 of the current work vector x, for the sweep of the other side: two launches
+    void gram_vector(const T* F, int64_t d, int P, const double* x, double* part, double* s) {
+        ProfScope ps(&prof, "ccd/gramcol", st);
+        gramcol(1, F, d, P, x, 0, part);
+        hipLaunchKernelGGL(k_ccd_gramred, dim3(1), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, 1, (const double*)part, P, k, s, (double*)nullptr, 0);
+    }
+    // rank t under implicit feedback: 7 maxinneriter + 5 launches, no host round trip
+    int enqueue_rank_implicit(int oi, int t) {
+        const int T_in = cp.maxinneriter;
+        {
+            ProfScope ps(&prof, "ccd/begin", st);
+            const int g = std::max(1, std::min(4096, cdiv(std::max(d1, d2), ccd::BLOCK)));
+            hipLaunchKernelGGL((k_ccd_begin<T>), dim3(g), dim3(ccd::BLOCK), 0, st, d_ctl.p, (const T*)base->d_U.p, (const T*)base->d_V.p, ld, t, oi, d1, d2,
+                               d_u.p, d_oldu.p, d_v.p, d_oldv.p);
+        }
+        const T* U = (const T*)base->d_U.p;
+        const T* V = (const T*)base->d_V.p;
+        for (int iter = 1; iter <= T_in; ++iter) {
+            const int addback = (iter == 1 && oi > 1) ? 1 : 0;
+            gram_vector(U, d1, Pu, (const double*)d_u.p, d_gpu.p, d_su.p);                  // s = U^T u, sum u^2: from the CURRENT u
+            {
+                ProfScope ps(&prof, "ccd/vsweep.i", st);
+                if (weighted)
+                    hipLaunchKernelGGL((k_ccd_sweep_iw<T, RT>), dim3(nvb), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, (const int64_t*)d_cptr.p,
+                                       (const int32_t*)d_row_c.p, d_res_c.p, (const double*)d_pd_c.p, (const RT*)d_w_c.p, (const double*)d_Wiv.p, V, ld, k, t,
+                                       (const double*)d_su.p, alpha, (const double*)d_u.p, (const double*)d_oldu.p, (const double*)d_oldv.p, d_v.p,
+                                       (const int32_t*)d_ilong.p, nilong, (const int32_t*)d_ishort.p, nishort, prm.lambda, cp.do_nmf, addback, d_vpart.p);
+                else
+                    hipLaunchKernelGGL((k_ccd_sweep_i<T, RT>), dim3(nvb), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, (const int64_t*)d_cptr.p,
+                                       (const int32_t*)d_row_c.p, d_res_c.p, (const double*)d_pd_c.p, (const double*)d_Wiv.p, V, ld, k, t,
+                                       (const double*)d_su.p, alpha, (const double*)d_u.p, (const double*)d_oldu.p, (const double*)d_oldv.p, d_v.p,
+                                       (const int32_t*)d_ilong.p, nilong, (const int32_t*)d_ishort.p, nishort, prm.lambda, cp.do_nmf, addback, d_vpart.p);
+            }
+            gram_vector(V, d2, Pv, (const double*)d_v.p, d_gpv.p, d_sv.p);                  // s = V^T v from the v just written
+            {
+                ProfScope ps(&prof, "ccd/usweep.i", st);
+                if (weighted)
+                    hipLaunchKernelGGL((k_ccd_sweep_iw<T, RT>), dim3(nub), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, (const int64_t*)base->d_uptr.p,
+                                       (const int32_t*)base->d_item.p, d_res_r.p, (const double*)d_pd_r.p, (const RT*)d_w_r.p, (const double*)d_Wiu.p, U, ld, k,
+                                       t, (const double*)d_sv.p, alpha, (const double*)d_v.p, (const double*)d_oldv.p, (const double*)d_oldu.p, d_u.p,
+                                       (const int32_t*)d_ulong.p, nulong, (const int32_t*)d_ushort.p, nushort, prm.lambda, cp.do_nmf, addback, d_upart.p);
+                else
+                    hipLaunchKernelGGL((k_ccd_sweep_i<T, RT>), dim3(nub), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, (const int64_t*)base->d_uptr.p,
+                                       (const int32_t*)base->d_item.p, d_res_r.p, (const double*)d_pd_r.p, (const double*)d_Wiu.p, U, ld, k, t,
+                                       (const double*)d_sv.p, alpha, (const double*)d_v.p, (const double*)d_oldv.p, (const double*)d_oldu.p, d_u.p,
+                                       (const int32_t*)d_ulong.p, nulong, (const int32_t*)d_ushort.p, nushort, prm.lambda, cp.do_nmf, addback, d_upart.p);
+            }
+            {
+                ProfScope ps(&prof, "ccd/decide", st);
+                hipLaunchKernelGGL(k_ccd_decide, dim3(1), dim3(ccd::BLOCK), 0, st, d_ctl.p, (const double*)d_vpart.p, nvb, (const double*)d_upart.p, nub,
+                                   cp.eps, oi, t, iter);
+            }
+        }
+        {
+            ProfScope ps(&prof, "ccd/resid.i", st);
+            hipLaunchKernelGGL((k_ccd_resid_i<T, RT>), dim3(2 * B + Bu + Bv + Bt), dim3(ccd::BLOCK), 0, st, (const CcdCtl*)d_ctl.p, B, Bu, Bv, Bt, nnz,
+                               d1, d2, tn, d_res_r.p, (const int32_t*)d_row_r.p, (const int32_t*)base->d_item.p, d_res_c.p, (const int32_t*)d_row_c.p,
+                               (const int32_t*)d_col_c.p, d_pd_r.p, d_pd_c.p, weighted ? (const RT*)d_w_r.p : (const RT*)nullptr, alpha,
+                               (const double*)d_Wiu.p, (const double*)d_Wiv.p, (const double*)d_u.p, (const double*)d_oldu.p, (const double*)d_v.p,
+                               (const double*)d_oldv.p, base->d_U.p, base->d_V.p, ld, t, (const int32_t*)d_tu.p, (const int32_t*)d_ti.p, d_tres.p,
+                               d_ploss.p, d_pregu.p, d_pregv.p, d_prmse.p, (T_in < 1 && oi > 1) ? 1 : 0);
+        }
+        {
+            // row t of both Gram matrices from the STORED column t, then the record
+            ProfScope ps(&prof, "ccd/final.i", st);
+            gramcol(0, U, d1, Pu, nullptr, t, d_gpu.p);
+            gramcol(0, V, d2, Pv, nullptr, t, d_gpv.p);
+            hipLaunchKernelGGL(k_ccd_final_i, dim3(1), dim3(ccd::BLOCK), 0, st, d_ctl.p, (const double*)d_ploss.p, B, (const double*)d_pregu.p, Bu,
+                               (const double*)d_pregv.p, Bv, (const double*)d_prmse.p, Bt, tn, prm.lambda, alpha, (const double*)d_gpu.p, Pu,
+                               (const double*)d_gpv.p, Pv, d_GU.p, d_GV.p, k, t);
+        }
+        HIPCHK(hipGetLastError());
+        return PCR_OK;
+    }
     // rank t of outer iteration `oi` (ccd-r1.cpp:130-199): 3 maxinneriter + 3 launches, no host round trip
     int enqueue_rank(int oi, int t) {
+        if (alpha > 0.0) return enqueue_rank_implicit(oi, t);
         const int T_in = cp.maxinneriter;
         {
             ProfScope ps(&prof, "ccd/begin", st);
@@ -669,7 +1027,11 @@ struct CcdSolver final : pcr_solver {
     // the unweighted kernels.  Nothing is changed before every weight has passed.  Ends a running training, like set_factors.
     int set_rating_weights(const double* w) override {
         HIPCHK(hipStreamSynchronize(st));
-        if (!w) { weighted = false; begun = false; return PCR_OK; }
+        if (!w) {
+            weighted = false; begun = false;
+            h_Wu.clear(); h_Wv.clear();
+            return alpha > 0.0 ? total_weights(alpha) : PCR_OK;
+        }
         std::vector<RT> w_r((size_t)nnz), w_c((size_t)nnz);
         for (int64_t z = 0; z < nnz; ++z) {
             const bool in_range = w[z] > 0.0 && w[z] <= (double)std::numeric_limits<RT>::max();     // (NaN fails both)
@@ -698,9 +1060,51 @@ struct CcdSolver final : pcr_solver {
         RC(d_w_r.upload(w_r, st)); RC(d_w_c.upload(w_c, st)); RC(d_Wu.upload(Wu, st)); RC(d_Wv.upload(Wv, st));
         weighted = true;
         begun = false;
-        return PCR_OK;
+        h_Wu.swap(Wu); h_Wv.swap(Wv);
+        return alpha > 0.0 ? total_weights(alpha) : PCR_OK;
     }
     int rating_weights_set(double* value) override { *value = weighted ? 1.0 : 0.0; return PCR_OK; }
+    // W = Wobs + a (d - n) per user and per item (Wobs = the sum of c_z, the count without weights): the row's total weight, the
+    // unrated cells included
+    int total_weights(double a) {
+        std::vector<double> Wu((size_t)d1), Wv((size_t)d2);
+        for (int64_t u = 0; u < d1; ++u) {
+            const int64_t n = h_uptr[(size_t)u + 1] - h_uptr[(size_t)u];
+            Wu[(size_t)u] = (weighted ? h_Wu[(size_t)u] : (double)n) + a * (double)(d2 - n);
+        }
+        for (int64_t j = 0; j < d2; ++j) {
+            const int64_t n = h_cptr[(size_t)j + 1] - h_cptr[(size_t)j];
+            Wv[(size_t)j] = (weighted ? h_Wv[(size_t)j] : (double)n) + a * (double)(d1 - n);
+        }
+        RC(d_Wiu.upload(Wu, st)); RC(d_Wiv.upload(Wv, st));
+        return PCR_OK;
+    }
+    // a: the weight of every unrated cell (target 0), finite and >= 0 as given, > 0 as stored (rounded to RT, as weights are) when
+    // > 0 as given; 0: the explicit kernels.  Nothing is changed before a has passed.  Ends a running training, like set_factors.
+    int set_implicit(double a) override {
+        const bool in_range = a >= 0.0 && a <= (double)std::numeric_limits<RT>::max();      // (NaN fails both)
+        const double as = in_range ? (double)(RT)a : -1.0;
+        if (!in_range || (a > 0.0 && !(as > 0.0))) {
+            pcr_set_error("pcr_solver_set_implicit: alpha must be a finite number >= 0, and > 0 in the solver's precision when it is > 0");
+            return PCR_ERR_ARG;
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        if (as > 0.0) {
+            if (!d_pd_r.p) {
+                Pu = gram_parts(d1); Pv = gram_parts(d2);
+                for (kw = 1; kw < k && kw < ccd::BLOCK; kw <<= 1) {}
+                RC(d_pd_r.alloc((size_t)nnz)); RC(d_pd_c.alloc((size_t)nnz));
+                RC(d_gpu.alloc((size_t)Pu * (size_t)(k + 1))); RC(d_gpv.alloc((size_t)Pv * (size_t)(k + 1)));
+                RC(d_su.alloc((size_t)k + 1)); RC(d_sv.alloc((size_t)k + 1));
+                RC(d_GU.alloc((size_t)k * (size_t)k)); RC(d_GV.alloc((size_t)k * (size_t)k));
+            }
+            RC(total_weights(as));
+        }
+        alpha = as;
+        begun = false;
+        return PCR_OK;
+    }
+    int implicit_alpha(double* value) override { *value = alpha; return PCR_OK; }
     int get_factors(double* U, double* V, bool local) override { return base->get_factors(U, V, local); }
     int evaluate(int which, int ndcg_k, double* err, double* ndcg) override { return base->evaluate(which, ndcg_k, err, ndcg); }
     double ridge_lambda() override { return prm.lambda; }

@@ -238,6 +238,13 @@ struct pcr_solver {
         return PCR_ERR_UNSUPPORTED;
     }
     virtual int rating_weights_set(double*) { pcr_set_error("pcr_solver_counter: 'ccd_rating_weights' exists on a CCDR1 solver only"); return PCR_ERR_STATE; }
+    // implicit feedback (alpha: the weight of every unrated cell; 0: off) and the "ccd_implicit" counter
+    virtual int set_implicit(double) {
+        pcr_set_error("pcr_solver_set_implicit: implicit feedback exists for CCDR1 (solver type 0) only; the ranking losses of PrimalCR / "
+                      "PrimalCR++ compare a user's rated items with each other and have no term for an unrated cell");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    virtual int implicit_alpha(double*) { pcr_set_error("pcr_solver_counter: 'ccd_implicit' exists on a CCDR1 solver only"); return PCR_ERR_STATE; }
     // the serving layer (pcr_serve.hip, pcr_fold.hip): the view of this solver's factors and shard, the exchange behind ServeView::sum (sync()
     // is ServeView::wait), the tables it keeps between calls
     virtual void serve_view(ServeView* v) = 0;

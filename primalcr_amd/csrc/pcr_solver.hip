@@ -2118,6 +2118,7 @@ int pcr_solver_counter(pcr_solver* s, const char* name, double* value) {
     if (!strncmp(name, "ustep_row_gathers/", 18)) return s->class_rows(name + 18, value);
     if (!strcmp(name, "ccd_residual_mismatch")) PCR_ABI("pcr_solver_counter", s->residual_mismatch(value));
     if (!strcmp(name, "ccd_rating_weights")) return s->rating_weights_set(value);
+    if (!strcmp(name, "ccd_implicit")) return s->implicit_alpha(value);
     pcr_set_error(std::string("pcr_solver_counter: unknown counter '") + name + "'");
     return PCR_ERR_ARG;
 }
@@ -2143,6 +2144,7 @@ int pcr_solver_get_factors_local(pcr_solver* s, double* U_local, double* V) { S_
 int pcr_solver_set_user_weights(pcr_solver* s, const double* w) { S_OR_ARG; PCR_ABI("pcr_solver_set_user_weights", s->set_user_weights(w, false)); }
 int pcr_solver_set_user_weights_local(pcr_solver* s, const double* w_local) { S_OR_ARG; PCR_ABI("pcr_solver_set_user_weights_local", s->set_user_weights(w_local, true)); }
 int pcr_solver_set_rating_weights(pcr_solver* s, const double* w) { S_OR_ARG; PCR_ABI("pcr_solver_set_rating_weights", s->set_rating_weights(w)); }
+int pcr_solver_set_implicit(pcr_solver* s, double alpha) { S_OR_ARG; PCR_ABI("pcr_solver_set_implicit", s->set_implicit(alpha)); }
 int pcr_comp_m(pcr_solver* s, double* m_out) { S_OR_ARG; PCR_ABI("pcr_comp_m", s->comp_m(m_out)); }
 int pcr_objective(pcr_solver* s, double* obj) { S_OR_ARG; PCR_ABI("pcr_objective", s->objective(obj)); }
 int pcr_obtain_g(pcr_solver* s, double* g) { S_OR_ARG; PCR_ABI("pcr_obtain_g", s->obtain_g(g)); }

@@ -45,6 +45,7 @@ NO_SOLVER(pcr_solver_set_factors_local, pcr_solver*, const double*, const double
 NO_SOLVER(pcr_solver_set_user_weights, pcr_solver*, const double*)
 NO_SOLVER(pcr_solver_set_user_weights_local, pcr_solver*, const double*)
 NO_SOLVER(pcr_solver_set_rating_weights, pcr_solver*, const double*)
+NO_SOLVER(pcr_solver_set_implicit, pcr_solver*, double)
 NO_SOLVER(pcr_solver_get_factors_local, pcr_solver*, double*, double*)
 NO_SOLVER(pcr_comp_m, pcr_solver*, double*)
 NO_SOLVER(pcr_objective, pcr_solver*, double*)
