@@ -253,8 +253,9 @@ int pcr_partition_users(const int64_t *index, int64_t d1, int nparts, int64_t *b
  *                   staged once per user) whenever one wave's image fits a workgroup's 160 KiB; both forms implement the same
  *                   contract, the tests hold them to each other; read at every call
  *   ridge_form      "cg" = pcr_fold_in_ridge / pcr_fold_in_ridge_model take the CG form for every user (the A/B arm of the direct
- *                   forms, and a test hook); "auto" (default) = the form rule; read when the call's plan is made
- *   nnls_form       "cg" = pcr_fold_in_nnls / pcr_fold_in_nnls_model take the CG form at every rank (the A/B arm of the direct
+ *                   forms, and a test hook); "auto" (default) = the form rule; read when the call's plan is made.  pcr_fold_in_conf /
+ *                   pcr_fold_in_conf_model read the same knob
+ *   nnls_form      "cg" = pcr_fold_in_nnls / pcr_fold_in_nnls_model take the CG form at every rank (the A/B arm of the direct
  *                   form, and a test hook); "auto" (default) = the form rule; read when the call's plan is made
  *   itemfold_table_bytes  test hook: the cap of pcr_fold_in_items' rater table (scores + levels) in bytes; a call whose unique
  *                   raters exceed it runs in batches of items (results do not depend on it); default 2^30; read at every call
@@ -1034,6 +1035,53 @@ int pcr_fold_in_ridge_model(const double *F, int64_t rows, int64_t k, double lam
  * is local: nothing is exchanged and any rank may call it alone.  Nothing of the solver is written.  Profile slot: foldin/ridge. */
 int pcr_fold_in_ridge(pcr_solver *s, int weighted, int64_t n, const int64_t *index, const int32_t *item, const double *val,
                       double *U_out, pcr_ridge_stats *stats, double *per_user);                     /* [device] */
+
+/* ------------------------------------------------------------------------- */
+/* confidence-weighted and implicit fold-in: the ridge fold-in of a model     */
+/* trained with rating weights (pcr_solver_set_rating_weights) and / or with  */
+/* implicit feedback (pcr_solver_set_implicit); no reference counterpart      */
+/* ------------------------------------------------------------------------- */
+/* The ridge fold-in's problem under the objective such a model was trained on.  For a user with ratings r_p on rows I of F (len of
+ * them), a_p = F[I_p], weights c_p > 0 (all 1 when weight is NULL), alpha >= 0 the weight of every unrated cell (a rating 0), d the
+ * rows of F and G = F^T F (k x k):
+ *     minimise sum_p c_p (r_p - a_p.u)^2 + alpha (u^T G u - sum_p (a_p.u)^2) + mu |u|^2,
+ *     mu = lambda W, W = sum_p c_p + alpha (d - len) (weighted != 0: the row's total weight, as in training) or mu = lambda,
+ *     <=>  M u = b,  M = alpha G + sum_p (c_p - alpha) a_p a_p^T + mu I,  b = sum_p c_p r_p a_p
+ * -- training's own column update written for a whole row: the sum over all d cells goes through G, computed once per call on
+ * v_mfma_f64_16x16x4_f64, and the rated cells are taken back out next to the ratings (an item rated twice is two ratings and two
+ * subtractions); the d x len unrated cells are never formed.  With weight NULL (or all 1) and alpha 0 this is the ridge fold-in,
+ * bit for bit.  weight and alpha are used in fp64 as given; only F and the returned row have the storage type.  F = U with the
+ * item-major ratings folds in new ITEMS.
+ *   Forms              a function of (len, k, alpha > 0) alone, never of the batch, the position or the grid:
+ *                        alpha == 0  the ridge entry's rule.  DUAL: (A A^T + mu C^-1) a = r, u = A^T a (C = diag c);
+ *                                    PRIMAL: (A^T C A + mu I) u = A^T C r; CG: Hp = A^T (c o (A p)) + mu p.
+ *                        alpha > 0   PRIMAL at every len >= 1 while roundup(k, 16) <= PCR_RIDGE_DIRECT_MAX (the alpha G term
+ *                                    makes the system k x k whatever the length); CG beyond, Hp = A^T ((c - alpha) o (A p)) +
+ *                                    alpha G p + mu p with G read from device memory, at most 2 k + 10 iterations.
+ *                      One wave (64 threads) up to PCR_RIDGE_WAVE_MAX ratings, except that an implicit primal system of more
+ *                      than 4 x 4 tiles (roundup(k, 16) > 64) always runs on 256 threads; 256 threads beyond and for the CG form.
+ *                      pcr_tune("ridge_form", "cg") forces the CG form, as for the ridge entry.
+ *   Statuses           the ridge entry's.  PCR_RIDGE_SINGULAR rows are zeros with loss = obj = sum_p c_p r_p^2.
+ *   Inputs             index / item / val as pcr_fold_in_ridge_model's; weight [index[n]] in the caller's order (the sorted copy
+ *                      of a row carries its weights through the same permutation), or NULL.  A user without ratings gets a zero
+ *                      row, status OK, loss = obj = 0, at any alpha.
+ *   Outputs            as the ridge entry's (pcr_ridge_stats, per_user [n][PCR_RIDGE_FIELDS]), with, at the returned (rounded) row,
+ *                      loss = sum_p c_p (r_p - a_p.u^)^2 + alpha (u^^T G u^ - sum_p (a_p.u^)^2) and obj = loss + mu |u^|^2.
+ *   Determinism        as the ridge entry's; G's row blocks are fixed by (rows, k) alone and added in block order, no atomics.
+ *                      Two identical calls are bitwise identical.
+ *   Errors             PCR_ERR_ARG before any device is looked for, the message naming the entry: everything the ridge entry
+ *                      refuses, a weight that is not finite or <= 0, an alpha that is negative or not finite.  Without a device:
+ *                      PCR_ERR_DEVICE.  Profile slots: foldin/conf, and foldin/conf.gram for G. */
+/* Standalone: F (rows x k) host fp64 in model-file layout. */
+int pcr_fold_in_conf_model(const double *F, int64_t rows, int64_t k, double lambda, int weighted, double alpha,
+                           int precision, int device, int64_t n, const int64_t *index, const int32_t *item,
+                           const double *val, const double *weight /* [index[n]] in the caller's order, or NULL = ones */,
+                           double *U_out, pcr_ridge_stats *stats, double *per_user);                /* [device] */
+/* On ANY live solver, as pcr_fold_in_ridge: its device V, storage type, stream and lambda; nothing of the solver is written.
+ * alpha is the caller's: the entry does not read the solver's pcr_solver_set_implicit setting. */
+int pcr_fold_in_conf(pcr_solver *s, int weighted, double alpha, int64_t n, const int64_t *index, const int32_t *item,
+                     const double *val, const double *weight, double *U_out, pcr_ridge_stats *stats,
+                     double *per_user);                                                             /* [device] */
 
 /* ------------------------------------------------------------------------- */
 /* non-negative fold-in: rows >= 0 for CCDR1 models trained with -N 1         */

@@ -280,6 +280,9 @@ def lib():
     if _LIB_OVERRIDE is None or hasattr(L, "pcr_fold_in_ridge"):
         L.pcr_fold_in_ridge_model.argtypes = [vp, i64, i64, cd, ci, ci, ci, i64, vp, vp, vp, vp, vp, vp]
         L.pcr_fold_in_ridge.argtypes = [vp, ci, i64, vp, vp, vp, vp, vp, vp]
+    if _LIB_OVERRIDE is None or hasattr(L, "pcr_fold_in_conf"):
+        L.pcr_fold_in_conf_model.argtypes = [vp, i64, i64, cd, ci, cd, ci, ci, i64, vp, vp, vp, vp, vp, vp, vp]
+        L.pcr_fold_in_conf.argtypes = [vp, ci, cd, i64, vp, vp, vp, vp, vp, vp, vp]
     if _LIB_OVERRIDE is None or hasattr(L, "pcr_fold_in_nnls"):
         L.pcr_fold_in_nnls_model.argtypes = [vp, i64, i64, cd, ci, ci, ci, i64, vp, vp, vp, vp, vp, vp]
         L.pcr_fold_in_nnls.argtypes = [vp, ci, i64, vp, vp, vp, vp, vp, vp]
@@ -1108,6 +1111,67 @@ def recommend_new_users_ridge(V, ratings, lam, topk, weighted=True, dtype=PCR_F6
     return items, scores, U_new, stats
 
 
+def conf_form(n, k, implicit=False):
+    """The form fold_in_conf() solves a user of n ratings in at rank k (include/primalcr.h), a function of (n, k, alpha > 0) alone:
+    ridge_form(n, k) for alpha == 0; for alpha > 0 (implicit) PCR_RIDGE_PRIMAL at every n while k padded to 16 is
+    <= PCR_RIDGE_DIRECT_MAX -- the alpha G term makes the system k x k whatever the length -- and PCR_RIDGE_CG beyond."""
+    if not implicit:
+        return ridge_form(n, k)
+    return PCR_RIDGE_PRIMAL if (k + 15) // 16 * 16 <= PCR_RIDGE_DIRECT_MAX else PCR_RIDGE_CG
+
+
+def conf_block(n, k, implicit=False):
+    """The workgroup width fold_in_conf() solves that user on: 256 threads for the CG form, beyond PCR_RIDGE_WAVE_MAX ratings and
+    for an implicit primal system of more than 4 x 4 tiles (k padded to 16 > 64), else one wave (64)."""
+    if conf_form(n, k, implicit) == PCR_RIDGE_CG or n > PCR_RIDGE_WAVE_MAX:
+        return 256
+    return 256 if implicit and (k + 15) // 16 * 16 > 64 else 64
+
+
+def conf_boundaries(k, implicit=False):
+    """The user lengths L at which fold_in_conf() changes its form or its workgroup width between L and L + 1 ratings at rank k."""
+    top = max(int(k), PCR_RIDGE_DIRECT_MAX) + 1
+    key = lambda n: (conf_form(n, k, implicit), conf_block(n, k, implicit))
+    return [L for L in range(top) if key(L) != key(L + 1)]
+
+
+def _conf_weights(weights, nnz):
+    if weights is None:
+        return None
+    w = np.ascontiguousarray(weights, np.float64)
+    if w.shape != (nnz,):
+        raise ValueError(f"weights must hold one weight per rating ({nnz})")
+    return w
+
+
+def fold_in_conf(F, ratings, lam, weights=None, alpha=0.0, weighted=True, dtype=PCR_F64, device=0, per_user=False):
+    """fold_in_ridge() under the objective of a model trained with rating weights (Solver.set_rating_weights) and / or implicit
+    feedback (Solver.set_implicit), on the GPU (pcr_fold_in_conf_model): with F [rows, k] fixed and G = F^T F, each row is the
+    exact minimiser of  sum_p c_p (r_p - F[I_p].u)^2 + alpha (u^T G u - sum_p (F[I_p].u)^2) + mu |u|^2  with mu = lam * (sum_p c_p
+    + alpha (rows - len)) (weighted) or mu = lam.  weights: one c_p > 0 per rating in the ratings' own order (None: ones); alpha
+    >= 0: the weight of every unrated cell, a rating 0.  weights=None and alpha=0 is fold_in_ridge(), bit for bit.  New ITEMS:
+    F = U and the item-major CSR.  Returns (rows float64 [n, k], stats dict[, per_user float64 [n, 6] of PCR_RIDGE_FIELDS]); loss
+    and obj are evaluated at the returned rows, which are rounded to `dtype`."""
+    F = np.ascontiguousarray(F, np.float64)
+    if F.ndim != 2:
+        raise ValueError("F must be [rows, k]")
+    index, item, val = _foldin_ratings(ratings)
+    n, k = index.shape[0] - 1, F.shape[1]
+    w = _conf_weights(weights, item.shape[0])
+    return _ridge_call(n, k, per_user, lambda uo, sp, pp: lib().pcr_fold_in_conf_model(
+        F.ctypes.data, F.shape[0], k, float(lam), 1 if weighted else 0, float(alpha), int(dtype), int(device), n, index.ctypes.data,
+        item.ctypes.data, val.ctypes.data, None if w is None else w.ctypes.data, uo, sp, pp))
+
+
+def recommend_new_users_conf(V, ratings, lam, topk, weights=None, alpha=0.0, weighted=True, dtype=PCR_F64, device=0):
+    """Top-K lists for users a weighted / implicit squared-loss model was not trained on: fold_in_conf(), then recommend(U_new, V,
+    topk, exclude=ratings).  Returns (items, scores, U_new, stats)."""
+    index, item, val = _foldin_ratings(ratings)
+    U_new, stats = fold_in_conf(V, (index, item, val), lam, weights=weights, alpha=alpha, weighted=weighted, dtype=dtype, device=device)
+    items, scores = recommend(U_new, V, topk, exclude=(index, item), dtype=dtype, device=device)
+    return items, scores, U_new, stats
+
+
 def nnls_form(k):
     """The form fold_in_nnls() takes at rank k (include/primalcr.h), a function of k alone: PCR_NNLS_DIRECT when k padded to 16 is
     <= PCR_RIDGE_DIRECT_MAX, PCR_NNLS_CG beyond."""
@@ -1671,6 +1735,22 @@ class Solver:
         n = index.shape[0] - 1
         return _ridge_call(n, self.k, per_user, lambda uo, sp, pp: lib().pcr_fold_in_ridge(
             self._h, 1 if weighted else 0, n, index.ctypes.data, item.ctypes.data, val.ctypes.data, uo, sp, pp))
+
+    def fold_in_conf(self, ratings, weights=None, alpha=None, weighted=True, per_user=False):
+        """fold_in_conf() for users this solver was not trained on, against its device V (pcr_fold_in_conf), in its storage type
+        and with its lambda; alpha=None takes the solver's own setting (set_implicit; counter "ccd_implicit"; 0 on a solver type
+        that has none).  Local to the rank; nothing of the solver is written."""
+        index, item, val = _foldin_ratings(ratings)
+        n = index.shape[0] - 1
+        w = _conf_weights(weights, item.shape[0])
+        if alpha is None:                                   # (the counter exists on a CCDR1 solver only: no setting, no alpha)
+            v = C.c_double()
+            a = v.value if lib().pcr_solver_counter(self._h, b"ccd_implicit", v) == 0 else 0.0
+        else:
+            a = float(alpha)
+        return _ridge_call(n, self.k, per_user, lambda uo, sp, pp: lib().pcr_fold_in_conf(
+            self._h, 1 if weighted else 0, a, n, index.ctypes.data, item.ctypes.data, val.ctypes.data, None if w is None else w.ctypes.data, uo,
+            sp, pp))
 
     def fold_in_nnls(self, ratings, weighted=True, per_user=False):
         """Non-negative factors for users this solver was not trained on, against its device V (pcr_fold_in_nnls), in its storage

@@ -45,6 +45,12 @@
 //                    --plain-reg, mu = lambda.  stdout gets one line "foldin_ridge users n dual n primal n cg n singular n cg_cap n
 //                    iters n loss x obj x" (%g); everything else as --fold-in, with the same exclusions of other modes; takes no -s
 //                    and no --steps
+//   omp-pmf-recommend --fold-in-ridge data_dir -l lambda [--rating-weights file] [--implicit alpha] ...
+//     --rating-weights file, --implicit alpha  --fold-in-ridge for a model trained with omp-pmf-train's options of the same names
+//                    (pcr_fold_in_conf_model): file holds 'user item weight' lines, one per rating of data_dir, matched with
+//                    pcr_dataset_match_weights; alpha is the weight of every unrated cell (finite, >= 0).  Malformed values are
+//                    refused before any device work.  The summary line starts with "foldin_conf".  Refused with --fold-in,
+//                    --fold-in-nnls and --fold-in-items.
 //   omp-pmf-recommend --fold-in-nnls data_dir -l lambda [--plain-reg] [-K topk] [--f32] [--scores] model_file output_file
 //   omp-pmf-recommend --fold-in-nnls data_dir -l lambda [--plain-reg] --eval data_dir [-c ...] [--threshold v] [--f32] model_file [output_file]
 //     --fold-in-nnls dir  --fold-in-ridge under u >= 0, for CCDR1 models trained with -N 1 (pcr_fold_in_nnls_model): each new user's
@@ -161,6 +167,11 @@ static const char* USAGE =
     "    --fold-in-ridge dir  --fold-in for squared-loss (CCDR1, -s 0) models: the exact ridge solution per new user; stdout gets a\n"
     "                   \"foldin_ridge users n dual n primal n cg n singular n cg_cap n iters n loss x obj x\" line; -l lambda is\n"
     "                   weighted by each user's rating count as in CCDR1 training; --plain-reg: the plain lambda |u|^2; no -s, --steps\n"
+    "       omp-pmf-recommend --fold-in-ridge data_dir -l lambda [--rating-weights file] [--implicit alpha] ...\n"
+    "    --rating-weights file, --implicit alpha  with --fold-in-ridge: the fold-in of a model trained with omp-pmf-train's options of\n"
+    "                   the same names: per-rating confidence weights ('user item weight' lines, one per rating of data_dir) and the\n"
+    "                   weight of every unrated cell (finite, >= 0); the summary line starts with foldin_conf; not with --fold-in,\n"
+    "                   --fold-in-nnls or --fold-in-items\n"
     "       omp-pmf-recommend --fold-in-nnls data_dir -l lambda [--plain-reg] [-K topk] [--f32] [--scores] model_file output_file\n"
     "       omp-pmf-recommend --fold-in-nnls data_dir -l lambda [--plain-reg] --eval data_dir [-c ...] [--threshold v] [--f32] model_file [output_file]\n"
     "    --fold-in-nnls dir  --fold-in-ridge under u >= 0, for CCDR1 models trained with -N 1: the exact non-negative minimiser per new\n"
@@ -490,7 +501,8 @@ static int run_tradeoff(const char* edir, const std::vector<double>& U, const st
 // (ridge: pcr_fold_in_ridge_model instead, mu = lambda x count unless plain_reg; its own summary line; nnls: pcr_fold_in_nnls_model,
 // likewise)
 static bool run_fold_in(const char* dir, const std::vector<double>& V, int64_t d2, int64_t k, double lambda, int solver, int steps, bool f32,
-                        bool ridge, bool nnls, bool plain_reg, int64_t* n_out, std::vector<int64_t>& index, std::vector<int32_t>& item, std::vector<double>& U_new) {
+                        bool ridge, bool nnls, bool plain_reg, int64_t* n_out, std::vector<int64_t>& index, std::vector<int32_t>& item, std::vector<double>& U_new,
+                        const char* wfile = nullptr, bool conf = false, double alpha = 0.0) {
     pcr_dataset* ds = nullptr;
     if (pcr_dataset_load_mt(dir, 0, &ds) != PCR_OK) { fprintf(stderr, "%s\n", pcr_last_error()); return false; }
     int64_t n, xd2, nnz, tnnz;
@@ -504,6 +516,18 @@ static bool run_fold_in(const char* dir, const std::vector<double>& V, int64_t d
     std::vector<int64_t> it64((size_t)nnz);
     std::vector<double> val((size_t)nnz);
     pcr_dataset_csr(ds, 0, index.data(), it64.data(), val.data());
+    std::vector<double> rw;                                        // --rating-weights: the weights in the CSR's order
+    if (wfile) {
+        auto fail = [&](const std::string& why) { fprintf(stderr, "--rating-weights: %s\n", why.c_str()); pcr_dataset_free(ds); return false; };
+        int64_t wn = 0, got = 0;
+        if (pcr_rating_file_count(wfile, &wn) != PCR_OK) return fail(pcr_last_error());
+        std::vector<int32_t> wu((size_t)wn), wi((size_t)wn);
+        std::vector<double> wv((size_t)wn);
+        if (pcr_rating_file_read(wfile, 0, wn, wu.data(), wi.data(), wv.data(), &got) != PCR_OK) return fail(pcr_last_error());
+        if (got != wn) return fail(std::string(wfile) + ": entry " + std::to_string(got + 1) + " is malformed");
+        rw.resize((size_t)nnz);
+        if (pcr_dataset_match_weights(ds, wn, wu.data(), wi.data(), wv.data(), rw.data()) != PCR_OK) return fail(pcr_last_error());
+    }
     pcr_dataset_free(ds);
     item.assign(it64.begin(), it64.end());
     pcr_params p;
@@ -519,6 +543,18 @@ static bool run_fold_in(const char* dir, const std::vector<double>& V, int64_t d
         }
         printf("foldin_nnls users %lld direct %lld cg %lld singular %lld cap %lld pivots %lld zeros %lld loss %g obj %g\n", (long long)ns.users,
                (long long)ns.direct, (long long)ns.cg, (long long)ns.singular, (long long)ns.cap, (long long)ns.pivots, (long long)ns.zeros, ns.loss, ns.obj);
+        *n_out = n;
+        return true;
+    }
+    if (conf) {                                                    // --fold-in-ridge with --rating-weights and / or --implicit
+        pcr_ridge_stats rs;
+        if (pcr_fold_in_conf_model(V.data(), d2, k, lambda, plain_reg ? 0 : 1, alpha, p.precision, 0, n, index.data(), item.data(), val.data(),
+                                   wfile ? rw.data() : nullptr, U_new.data(), &rs, nullptr) != PCR_OK) {
+            fprintf(stderr, "fold-in-ridge: %s\n", pcr_last_error());
+            return false;
+        }
+        printf("foldin_conf users %lld dual %lld primal %lld cg %lld singular %lld cg_cap %lld iters %lld loss %g obj %g\n", (long long)rs.users,
+               (long long)rs.dual, (long long)rs.primal, (long long)rs.cg, (long long)rs.singular, (long long)rs.cg_cap, (long long)rs.iters, rs.loss, rs.obj);
         *n_out = n;
         return true;
     }
@@ -704,6 +740,9 @@ int main(int argc, char** argv) {
     int max_per_group = 0;                                         // --max-per-group (0: not given)
     bool have_K = false;
     bool plain_reg = false;
+    const char* rwfile = nullptr;                                  // --rating-weights (with --fold-in-ridge)
+    bool have_implicit = false;                                    // --implicit alpha (with --fold-in-ridge)
+    double implicit_alpha = 0.0;
     double lambda = 0.0;
     bool have_lambda = false, have_s = false, have_steps = false;
     int solver = PCR_SOLVER_PCRPP, steps = 10;
@@ -746,6 +785,23 @@ int main(int argc, char** argv) {
             continue;
         }
         if (!strcmp(a, "--plain-reg")) { plain_reg = true; continue; }
+        if (!strcmp(a, "--rating-weights")) {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
+            rwfile = argv[++i];
+            continue;
+        }
+        if (!strcmp(a, "--implicit")) {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
+            const char* v = argv[++i];
+            char* end = nullptr;
+            implicit_alpha = strtod(v, &end);
+            if (end == v || *end != '\0' || !(implicit_alpha - implicit_alpha == 0.0) || implicit_alpha < 0.0) {
+                fprintf(stderr, "--implicit '%s' is not a finite number >= 0\n", v);
+                return 1;
+            }
+            have_implicit = true;
+            continue;
+        }
         if (!strcmp(a, "--fold-in") || !strcmp(a, "-l") || !strcmp(a, "-s") || !strcmp(a, "--steps")) {
             if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", a); return usage(); }
             const char* v = argv[++i];
@@ -894,6 +950,11 @@ int main(int argc, char** argv) {
         if (negatives >= 0 && ecfile) { fprintf(stderr, "--negatives does not go with --eval-candidates\n"); return 1; }
         if (have_seed && negatives < 0) { fprintf(stderr, "--seed goes with --negatives\n"); return 1; }
     }
+    if (rwfile || have_implicit) {                                 // (pcr_fold_in_conf_model: the ridge fold-in of a weighted / implicit model)
+        const char* mine = rwfile ? "--rating-weights" : "--implicit";
+        if (fdir || ndir || ifile) { fprintf(stderr, "%s does not go with --fold-in, --fold-in-nnls or --fold-in-items\n", mine); return 1; }
+        if (!rdir) { fprintf(stderr, "%s goes with --fold-in-ridge\n", mine); return 1; }
+    }
     if (ifile) {                                                   // (a mode of its own: it writes a model, no lists)
         if (fdir || rdir || ndir) { fprintf(stderr, "--fold-in-items does not go with --fold-in, --fold-in-ridge or --fold-in-nnls\n"); return 1; }
         if (edir || diversity || mmr || tradeoff || with_ranks || afile || cfile) {
@@ -979,7 +1040,8 @@ int main(int argc, char** argv) {
     if (gfile && !read_groups(gfile, d2, group)) return 1;
     if (fdir) {                                                    // the new users take the model's users' place: their factors, their ratings excluded
         std::vector<double> U_new;
-        if (!run_fold_in(fdir, V, d2, k, lambda, solver, steps, f32, ridge, nnls, plain_reg, &d1, xindex, xitem, U_new)) return 1;
+        if (!run_fold_in(fdir, V, d2, k, lambda, solver, steps, f32, ridge, nnls, plain_reg, &d1, xindex, xitem, U_new, rwfile, rwfile || have_implicit,
+                         implicit_alpha)) return 1;
         U.swap(U_new);
         users.resize((size_t)d1);
         for (int64_t u = 0; u < d1; ++u) users[(size_t)u] = (int32_t)u;

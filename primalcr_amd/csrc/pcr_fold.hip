@@ -3,6 +3,8 @@
 //   pcr_fold_in          new users of a ranking model     k_foldin (pcr_foldin.h)                    "foldin/newton"
 //   pcr_fold_in_ridge    squared loss                     k_ridge_direct, k_ridge_cg (pcr_ridge.h)   "foldin/ridge"
 //   pcr_fold_in_nnls     squared loss, row >= 0           k_nnls_direct, k_nnls_cg (pcr_nnls.h)      "foldin/nnls"
+//   pcr_fold_in_conf     squared loss, weights / implicit k_ridge_direct_conf, k_ridge_cg_conf,        "foldin/conf", "foldin/conf.gram"
+//                                                         k_ridge_catgram (pcr_ridge.h)
 //   pcr_fold_in_items    new items of a ranking model     k_rater_scores, k_itemfold (pcr_itemfold.h) "itemfold/scores", "itemfold/newton"
 // and, on fold-in's plan and forms, the explanation of listed items by a user's own ratings:
 //   pcr_explain          rows of a ranking model          k_explain (pcr_explain.h)                  "explain/contrib"
@@ -156,10 +158,27 @@ struct RidgeFamily {
     static size_t cg_bytes(int ld) { return ridge_cg_bytes(ld); }
     static size_t direct_bytes(int mp, int ld, int block) { return ridge_direct_bytes(mp, ld, block); }
     static bool tiles_ok(int mp, int, int block) { return mp >= 16 && mp <= (block == 64 ? 64 : PCR_RIDGE_DIRECT_MAX); }
-    template <typename T> static auto cg() { return k_ridge_cg<T>; }
+    template <typename T, class... A>
+    int cg(int64_t grid, size_t lds, hipStream_t st, A... args) const { return fold_launch(k_ridge_cg<T>, grid, 256, lds, st, args...); }
     template <typename T, int BLOCK, class... A>
-    static int direct(int64_t grid, size_t lds, hipStream_t st, int form, int mp, A... args) {
+    int direct(int64_t grid, size_t lds, hipStream_t st, int form, int mp, A... args) const {
         return fold_launch(k_ridge_direct<T, BLOCK>, grid, BLOCK, lds, st, args..., form == PCR_RIDGE_DUAL ? 1 : 0, mp);
+    }
+};
+// pcr_fold_in_conf*: the plain family under the conf entries' slot (no weights, alpha == 0: the ridge kernels themselves), and the
+// weighted / implicit instantiations with what they read besides (cf: device pointers of the run)
+struct ConfPlainFamily : RidgeFamily {
+    static constexpr const char *slot = "foldin/conf", *name = "conf";
+};
+struct ConfFamily : RidgeFamily {
+    static constexpr const char *slot = "foldin/conf", *name = "conf";
+    RidgeConf cf;
+    static size_t direct_bytes(int mp, int ld, int block) { return ridge_direct_conf_bytes(mp, ld, block); }
+    template <typename T, class... A>
+    int cg(int64_t grid, size_t lds, hipStream_t st, A... args) const { return fold_launch(k_ridge_cg_conf<T>, grid, 256, lds, st, args..., cf); }
+    template <typename T, int BLOCK, class... A>
+    int direct(int64_t grid, size_t lds, hipStream_t st, int form, int mp, A... args) const {
+        return fold_launch(k_ridge_direct_conf<T, BLOCK>, grid, BLOCK, lds, st, args..., form == PCR_RIDGE_DUAL ? 1 : 0, mp, cf);
     }
 };
 struct NnlsFamily {
@@ -170,18 +189,23 @@ struct NnlsFamily {
     static size_t cg_bytes(int ld) { return nnls_cg_bytes(ld); }
     static size_t direct_bytes(int mp, int ld, int block) { return nnls_direct_bytes(mp, ld, block); }
     static bool tiles_ok(int mp, int r, int block) { return mp >= 16 && mp >= r && mp <= (block == 64 ? 64 : PCR_RIDGE_DIRECT_MAX); }
-    template <typename T> static auto cg() { return k_nnls_cg<T>; }
+    template <typename T, class... A>
+    int cg(int64_t grid, size_t lds, hipStream_t st, A... args) const { return fold_launch(k_nnls_cg<T>, grid, 256, lds, st, args...); }
     template <typename T, int BLOCK, class... A>
-    static int direct(int64_t grid, size_t lds, hipStream_t st, int, int mp, A... args) {
+    int direct(int64_t grid, size_t lds, hipStream_t st, int, int mp, A... args) const {
         return fold_launch(k_nnls_direct<T, BLOCK>, grid, BLOCK, lds, st, args..., mp);
     }
 };
-template <class Fam, typename T>
-static int ridge_run(const ServeView& v, double lambda, int weighted, const PcrRidgePlan& P, double* U_out, typename Fam::Stats* stats, double* per_user) {
+// prepare(fam, st) (conf: the weights, W and the catalogue Gram to the device) runs before the family's slot opens.
+template <class Fam, typename T, class Prep>
+static int ridge_run(const ServeView& v, double lambda, int weighted, const PcrRidgePlan& P, double* U_out, typename Fam::Stats* stats, double* per_user,
+                     Prep&& prepare) {
     const int64_t n = P.X.d1;
     hipStream_t st = v.st;
     int cus = 0;
     RC(device_cus(&cus));
+    Fam fam;
+    RC(prepare(fam, st));
     DBuf<int64_t> uptr;
     DBuf<int32_t> item, order;
     DBuf<double> val;
@@ -200,8 +224,8 @@ static int ridge_run(const ServeView& v, double lambda, int weighted, const PcrR
             if (g.form == Fam::CG) {
                 const size_t lds = Fam::cg_bytes(v.ld);
                 if (lds > PCR_LDS_CU) { pcr_set_error(who + "rank " + std::to_string(v.r) + " is too large for the CG form's LDS"); return PCR_ERR_UNSUPPORTED; }
-                RC(fold_launch(Fam::template cg<T>(), fold_grid(g.count, cus, 8, lds), 256, lds, st, X, users, (int)g.count, F, v.r, v.ld, out.rows.p,
-                               out.per.p, lambda, weighted));
+                RC((fam.template cg<T>(fold_grid(g.count, cus, 8, lds), lds, st, X, users, (int)g.count, F, v.r, v.ld, out.rows.p, out.per.p, lambda,
+                                       weighted)));
                 continue;
             }
             const int mp = g.tiles * 16;
@@ -212,11 +236,40 @@ static int ridge_run(const ServeView& v, double lambda, int weighted, const PcrR
                 return PCR_ERR_UNSUPPORTED;
             }
             const int64_t grid = fold_grid(g.count, cus, fold_wg_cap(g.block), lds);
-            if (g.block == 64) RC((Fam::template direct<T, 64>(grid, lds, st, g.form, mp, X, users, (int)g.count, F, v.r, v.ld, out.rows.p, out.per.p, lambda, weighted)));
-            else RC((Fam::template direct<T, 256>(grid, lds, st, g.form, mp, X, users, (int)g.count, F, v.r, v.ld, out.rows.p, out.per.p, lambda, weighted)));
+            if (g.block == 64) RC((fam.template direct<T, 64>(grid, lds, st, g.form, mp, X, users, (int)g.count, F, v.r, v.ld, out.rows.p, out.per.p, lambda, weighted)));
+            else RC((fam.template direct<T, 256>(grid, lds, st, g.form, mp, X, users, (int)g.count, F, v.r, v.ld, out.rows.p, out.per.p, lambda, weighted)));
         }
     }
     return out.finish(v, U_out, per_user, [&](const double* hp) { if (stats) Fam::stats_from(hp, n, stats); });
+}
+template <class Fam, typename T>
+static int ridge_run(const ServeView& v, double lambda, int weighted, const PcrRidgePlan& P, double* U_out, typename Fam::Stats* stats, double* per_user) {
+    return ridge_run<Fam, T>(v, lambda, weighted, P, U_out, stats, per_user, [](Fam&, hipStream_t) { return PCR_OK; });
+}
+
+// Confidence-weighted / implicit fold-in (pcr_fold_in_conf*) of the plan's users against v's V.  Without
+// weights and alpha it IS the ridge run.  Else the weights and the per-user W go to the device and, for alpha > 0, the catalogue
+// Gram G = F^T F is built once ("foldin/conf.gram": k_ridge_catgram's partials per row block, then their sum in block order);
+// the ridge run then launches the family's weighted / implicit instantiations.
+template <typename T>
+static int conf_run(const ServeView& v, double lambda, int weighted, const PcrConfPlan& P, double* U_out, pcr_ridge_stats* stats, double* per_user) {
+    if (P.plain) return ridge_run<ConfPlainFamily, T>(v, lambda, weighted, P, U_out, stats, per_user);
+    DBuf<double> wt, W, G, part;
+    return ridge_run<ConfFamily, T>(v, lambda, weighted, P, U_out, stats, per_user, [&](ConfFamily& fam, hipStream_t st) -> int {
+        RC(wt.upload(P.wt, st)); RC(W.upload(P.W, st));
+        fam.cf.wt = wt.p; fam.cf.W = W.p; fam.cf.alpha = P.alpha;
+        if (P.alpha > 0.0) {
+            const int ldg = (v.r + 15) / 16 * 16, nb = ridge_catgram_blocks(v.d2, v.r), np = ridge_catgram_pairs(v.r);
+            RC(G.alloc((size_t)ldg * ldg)); RC(part.alloc((size_t)nb * np * 16 * 256));
+            ProfScope ps(v.prof, "foldin/conf.gram", st);
+            hipLaunchKernelGGL((k_ridge_catgram<T>), dim3((unsigned)nb, (unsigned)np), dim3(256), 0, st, serve_V<T>(v), v.d2, v.r, v.ld, nb, part.p);
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(k_ridge_catgram_sum, dim3((unsigned)np, 16), dim3(256), 0, st, (const double*)part.p, nb, v.r, ldg, G.p);
+            HIPCHK(hipGetLastError());
+            fam.cf.G = G.p; fam.cf.ldg = ldg;
+        }
+        return PCR_OK;
+    });
 }
 
 // Item fold-in (pcr_fold_in_items, pcr_fold_in_items_model; pcr_itemfold.h) of the plan's items against v's U: the slots and
@@ -595,6 +648,34 @@ int pcr_fold_in_ridge(pcr_solver* s, int weighted, int64_t n, const int64_t* ind
         RC(pcr_fold_in_ridge_check("pcr_fold_in_ridge", false, nullptr, v.d2, v.r, lambda, v.dtype, n, index, item, val, U_out, &P));
         return fold_serve(stats, n, v, on_solver, [&](auto zero) -> int {
             return ridge_run<RidgeFamily, decltype(zero)>(v, lambda, weighted != 0, P, U_out, stats, per_user);
+        });
+    });
+}
+
+int pcr_fold_in_conf_model(const double* F, int64_t rows, int64_t k, double lambda, int weighted, double alpha, int precision, int device, int64_t n,
+                           const int64_t* index, const int32_t* item, const double* val, const double* weight, double* U_out, pcr_ridge_stats* stats,
+                           double* per_user) {
+    return abi_guard("pcr_fold_in_conf_model", [&]() -> int {
+    PcrConfPlan P;
+    RC(pcr_fold_in_conf_check("pcr_fold_in_conf_model", true, F, rows, k, lambda, alpha, precision, n, index, item, val, weight, U_out, &P));
+    RC(model_device(device));
+    ServeView v; ModelDev M;
+    return fold_serve(stats, n, v, [&] { return M.open(nullptr, n, F, rows, k, nullptr, nullptr, true, precision, &v); }, [&](auto zero) -> int {
+        return conf_run<decltype(zero)>(v, lambda, weighted != 0, P, U_out, stats, per_user);
+    });
+    });
+}
+
+int pcr_fold_in_conf(pcr_solver* s, int weighted, double alpha, int64_t n, const int64_t* index, const int32_t* item, const double* val,
+                     const double* weight, double* U_out, pcr_ridge_stats* stats, double* per_user) {
+    S_OR_ARG;
+    return abi_guard("pcr_fold_in_conf", [&]() -> int {
+        const ServeView v = solver_view(s, 0);
+        const double lambda = s->ridge_lambda();
+        PcrConfPlan P;
+        RC(pcr_fold_in_conf_check("pcr_fold_in_conf", false, nullptr, v.d2, v.r, lambda, alpha, v.dtype, n, index, item, val, weight, U_out, &P));
+        return fold_serve(stats, n, v, on_solver, [&](auto zero) -> int {
+            return conf_run<decltype(zero)>(v, lambda, weighted != 0, P, U_out, stats, per_user);
         });
     });
 }

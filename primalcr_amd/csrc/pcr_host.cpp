@@ -2170,12 +2170,8 @@ static int fold_in_ls_args(const char* who, bool need_F, const double* F, int64_
     return PCR_OK;
 }
 
-int pcr_fold_in_ridge_check(const char* who, bool need_F, const double* F, int64_t rows, int64_t k, double lambda, int precision, int64_t n,
-                            const int64_t* index, const int32_t* item, const double* val, const double* U_out, PcrRidgePlan* plan) {
-    PcrRidgePlan local;
-    PcrRidgePlan& P = plan ? *plan : local;
-    const int rc = fold_in_ls_args(who, need_F, F, rows, k, lambda, precision, n, index, item, val, true, U_out, P.X);
-    if (rc != PCR_OK) return rc;
+// the launch ranges of a ridge / conf plan (implicit == 0: the ridge rule itself) from the user lengths
+static void ridge_plan_ranges(PcrRidgePlan& P, int64_t k, int64_t n, const int64_t* index, int implicit) {
     std::string knob;
     P.force_cg = pcr_tune_get("ridge_form", &knob) && knob == "cg";
     // a user's launch class: the CG form first, then primal and dual, 256 threads before one wave, more tiles before fewer; inside
@@ -2183,10 +2179,10 @@ int pcr_fold_in_ridge_check(const char* who, bool need_F, const double* F, int64
     auto len_of = [&](int32_t u) { return index[u + 1] - index[u]; };
     auto cls_of = [&](int32_t u, PcrRidgePlan::Range* r) {
         const int64_t len = len_of(u);
-        const int form = P.force_cg ? PCR_RIDGE_CG : pcr_ridge_form(len, k);
+        const int form = P.force_cg ? PCR_RIDGE_CG : pcr_conf_form(len, k, implicit);
         const int64_t m = form == PCR_RIDGE_DUAL ? std::max<int64_t>(len, 1) : k;
         r->form = form;
-        r->block = (form == PCR_RIDGE_CG || len > PCR_RIDGE_WAVE_MAX) ? 256 : 64;
+        r->block = form == PCR_RIDGE_CG ? 256 : pcr_conf_block(len, k, implicit);
         r->tiles = form == PCR_RIDGE_CG ? 0 : (int)((m + 15) / 16);
         return (int64_t)form * -1000 - (r->block == 256 ? 100 : 0) - r->tiles;
     };
@@ -2204,6 +2200,69 @@ int pcr_fold_in_ridge_check(const char* who, bool need_F, const double* F, int64
         if (P.ranges.empty() || key[(size_t)P.order[(size_t)i]] != key[(size_t)P.order[(size_t)(i - 1)]]) { r.first = i; r.count = 0; P.ranges.push_back(r); }
         P.ranges.back().count += 1;
     }
+}
+
+int pcr_fold_in_ridge_check(const char* who, bool need_F, const double* F, int64_t rows, int64_t k, double lambda, int precision, int64_t n,
+                            const int64_t* index, const int32_t* item, const double* val, const double* U_out, PcrRidgePlan* plan) {
+    PcrRidgePlan local;
+    PcrRidgePlan& P = plan ? *plan : local;
+    const int rc = fold_in_ls_args(who, need_F, F, rows, k, lambda, precision, n, index, item, val, true, U_out, P.X);
+    if (rc != PCR_OK) return rc;
+    ridge_plan_ranges(P, k, n, index, 0);
+    return PCR_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// confidence-weighted / implicit fold-in (include/primalcr.h): the form rule, argument checks and the host-side plan
+// ------------------------------------------------------------------------------------------
+int pcr_conf_form(int64_t len, int64_t k, int implicit) {
+    if (!implicit) return pcr_ridge_form(len, k);
+    return (k + 15) / 16 * 16 <= PCR_RIDGE_DIRECT_MAX ? PCR_RIDGE_PRIMAL : PCR_RIDGE_CG;
+}
+int pcr_conf_block(int64_t len, int64_t k, int implicit) {
+    if (pcr_conf_form(len, k, implicit) == PCR_RIDGE_CG || len > PCR_RIDGE_WAVE_MAX) return 256;
+    return implicit && (k + 15) / 16 * 16 > 64 ? 256 : 64;
+}
+
+int pcr_fold_in_conf_check(const char* who, bool need_F, const double* F, int64_t rows, int64_t k, double lambda, double alpha, int precision, int64_t n,
+                           const int64_t* index, const int32_t* item, const double* val, const double* weight, const double* U_out, PcrConfPlan* plan) {
+    PcrConfPlan local;
+    PcrConfPlan& P = plan ? *plan : local;
+    auto bad = [who](const std::string& why) { pcr_set_error(std::string(who) + ": " + why); return PCR_ERR_ARG; };
+    if (!std::isfinite(alpha) || alpha < 0.0) return bad("alpha must be finite and not negative");
+    const int rc = fold_in_ls_args(who, need_F, F, rows, k, lambda, precision, n, index, item, val, true, U_out, P.X);
+    if (rc != PCR_OK) return rc;
+    const int64_t nnz = index[n];
+    if (weight)
+        for (int64_t z = 0; z < nnz; ++z)
+            if (!std::isfinite(weight[z]) || weight[z] <= 0.0) return bad("a weight is not finite or not positive");
+    P.alpha = alpha;
+    P.plain = !weight && alpha == 0.0;
+    ridge_plan_ranges(P, k, n, index, alpha > 0.0 ? 1 : 0);
+    if (P.plain) return PCR_OK;
+    // the weights through the permutation of pcr_csr_sorted_copy: ascending items, equal items in the caller's order
+    P.wt.assign((size_t)nnz, 1.0);
+    P.W.assign((size_t)n, 0.0);
+    pcr_parallel_ranges(n, pcr_host_threads(), [&](int, int64_t lo, int64_t hi) {
+        std::vector<int64_t> perm;
+        for (int64_t u = lo; u < hi; ++u) {
+            const int64_t a = index[u], len = index[u + 1] - a;
+            if (weight) {
+                bool asc = true;
+                for (int64_t q = 1; q < len; ++q) asc = asc && item[a + q] >= item[a + q - 1];
+                if (asc) std::copy(weight + a, weight + a + len, P.wt.begin() + a);
+                else {
+                    perm.resize((size_t)len);
+                    for (int64_t q = 0; q < len; ++q) perm[(size_t)q] = a + q;
+                    std::stable_sort(perm.begin(), perm.end(), [&](int64_t x, int64_t y) { return item[x] < item[y]; });
+                    for (int64_t q = 0; q < len; ++q) P.wt[(size_t)(a + q)] = weight[perm[(size_t)q]];
+                }
+            }
+            double w = 0.0;
+            for (int64_t q = 0; q < len; ++q) w += P.wt[(size_t)(a + q)];
+            P.W[(size_t)u] = w + alpha * (double)(rows - len);
+        }
+    });
     return PCR_OK;
 }
 

@@ -292,6 +292,26 @@ int pcr_fold_in_ridge_check(const char* who, bool need_F, const double* F, int64
 // stats from the per-user table [n][PCR_RIDGE_FIELDS]: the counts, and loss / obj added in user order
 void pcr_ridge_stats_from(const double* per_user, int64_t n, pcr_ridge_stats* stats);
 
+// Confidence-weighted / implicit fold-in (include/primalcr.h, "confidence-weighted and implicit fold-in").  The form of a user of
+// len ratings at rank k, a function of (len, k, alpha > 0) alone: the ridge rule for implicit == 0; else PRIMAL at every len while
+// roundup(k, 16) <= PCR_RIDGE_DIRECT_MAX (the alpha G term makes the system k x k whatever the length), CG beyond.
+// pcr_conf_block: the workgroup width of that user -- 256 threads for the CG form, for more than PCR_RIDGE_WAVE_MAX ratings and
+// for an implicit primal system of more than 4 x 4 tiles (one wave carries at most 4 x 4), else 64.
+int pcr_conf_form(int64_t len, int64_t k, int implicit);
+int pcr_conf_block(int64_t len, int64_t k, int implicit);
+// The ridge plan (ranges by pcr_conf_form / pcr_conf_block) and what the conf kernels read besides: wt = the weights in X's order
+// (carried through the sorted copy's permutation; ones when the caller gave none), W[u] = sum of the user's weights in that order
+// + alpha (rows - len).  plain: no weights and alpha == 0 -- the plan is pcr_fold_in_ridge_check's and the ridge kernels run it.
+struct PcrConfPlan : PcrRidgePlan {
+    std::vector<double> wt, W;
+    double alpha = 0.0;
+    bool plain = false;
+};
+// pcr_fold_in_ridge_check's checks, then: every weight finite and > 0 (weight may be NULL), alpha finite and >= 0; errors are
+// PCR_ERR_ARG prefixed with `who`.  plan (may be NULL) receives the plan.
+int pcr_fold_in_conf_check(const char* who, bool need_F, const double* F, int64_t rows, int64_t k, double lambda, double alpha, int precision, int64_t n,
+                           const int64_t* index, const int32_t* item, const double* val, const double* weight, const double* U_out, PcrConfPlan* plan);
+
 // Non-negative fold-in (include/primalcr.h, "non-negative fold-in").  The form at rank k (PCR_NNLS_DIRECT / CG), a function of k alone.
 int pcr_nnls_form(int64_t k);
 // The ridge entries' argument checks under the nnls entry's name (one shared routine), and the plan for k_nnls_direct / k_nnls_cg

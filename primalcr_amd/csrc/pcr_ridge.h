@@ -19,6 +19,11 @@
 // would cap an fp32 model's CG at fp32 residuals, so the passes here are their fp64 counterparts); the row is rounded to T on store
 // and loss = |r - A u^|^2, obj = loss + mu |u^|^2 are taken at the ROUNDED row in one more pass.  Every sum has a fixed order that
 // depends on (n, k) alone, nothing is exchanged between workgroups, no atomics, every loop has a static bound.
+//
+// The confidence-weighted / implicit fold-in (pcr_fold_in_conf, pcr_fold_in_conf_model) runs the same
+// stages on RidgeConf's problem below: the CF = true instantiations of every function here (k_ridge_direct_conf,
+// k_ridge_cg_conf; the CF = false kernels keep their symbols and code) and, for alpha > 0, the catalogue Gram of
+// k_ridge_catgram / k_ridge_catgram_sum at the end of this file.
 #pragma once
 #include "pcr_host.h"
 #include "pcr_prims.h"
@@ -46,16 +51,30 @@ struct RidgeCsr {
     const int32_t* item;
     const double* val;
 };
+// What the confidence-weighted / implicit forms (CF, pcr_fold_in_conf*) read besides: per rating the weight
+// c_p > 0 in X's order, per user W = sum_p c_p + alpha (rows of F - len), and for alpha > 0 the catalogue Gram G = F^T F
+// (k_ridge_catgram below): [ldg][ldg] fp64, both triangles, zeros beyond the rank.  Per user the problem is
+//     minimise sum_p c_p (r_p - a_p.u)^2 + alpha (u^T G u - sum_p (a_p.u)^2) + mu |u|^2,    mu = lambda W (weighted) or lambda
+//     <=>  (alpha G + sum_p (c_p - alpha) a_p a_p^T + mu I) u = sum_p c_p r_p a_p
+// and, for alpha == 0, its dual (A A^T + mu C^-1) a = r, u = A^T a.  Inside a user's functions wt points at the user's weights.
+struct RidgeConf {
+    const double* wt = nullptr;
+    const double* W = nullptr;
+    const double* G = nullptr;
+    int ldg = 0;
+    double alpha = 0.0;
+};
 
 // sum over the user's ratings of (val - F[item] . uq)^2 (all: the residual; !resid: val is ignored, the scores' squares), uq: LDS,
 // fp64.  16-lane groups take the ratings round robin; a group's sum runs in rating order, the groups are added in group order.
-// part: LDS, BLOCK / 16 doubles.  Every thread gets the total.
-template <typename T, int BLOCK>
+// part: LDS, BLOCK / 16 doubles.  Every thread gets the total.  CF: the terms are c_p (val - score)^2 and *dd receives the
+// sum of the scores' squares, in the same order.
+template <typename T, int BLOCK, bool CF = false>
 __device__ __forceinline__ double ridge_loss(const T* __restrict__ F, const int32_t* __restrict__ item, const double* __restrict__ val, int n,
-                                             const double* uq, int r, int ld, double* part) {
+                                             const double* uq, int r, int ld, double* part, RidgeConf cf = RidgeConf(), double* dd = nullptr) {
     constexpr int NG = BLOCK / 16;
     const int g = threadIdx.x & 15, gi = threadIdx.x >> 4;
-    double acc = 0.0;
+    double acc = 0.0, acc2 = 0.0;
     for (int base = 0; base < n; base += NG) {
         const int p = base + gi;
         const bool live = p < n;
@@ -65,7 +84,11 @@ __device__ __forceinline__ double ridge_loss(const T* __restrict__ F, const int3
             for (int t = g; t < r; t += 16) d += (double)row[t] * uq[t];
         }
         d = ridge_sum16(d);
-        if (live) { const double e = val[p] - d; acc += e * e; }
+        if (live) {
+            const double e = val[p] - d;
+            if (CF) { acc += (cf.wt[p] * e) * e; acc2 += d * d; }
+            else acc += e * e;
+        }
     }
     __syncthreads();
     if (g == 0) part[gi] = acc;
@@ -74,16 +97,26 @@ __device__ __forceinline__ double ridge_loss(const T* __restrict__ F, const int3
 #pragma unroll
     for (int q = 0; q < NG; ++q) tot += part[q];
     __syncthreads();
+    if (CF) {
+        if (g == 0) part[gi] = acc2;
+        __syncthreads();
+        double t2 = 0.0;
+#pragma unroll
+        for (int q = 0; q < NG; ++q) t2 += part[q];
+        __syncthreads();
+        *dd = t2;
+    }
     return tot;
 }
 
 // the end of a user, every form: the row rounded to T and stored (pad columns zero), loss and obj at the rounded row, the table
 // line.  uvec: the solution in LDS (r entries; status != OK: ignored, the row is zeros and loss = |r|^2); uq: LDS scratch of r
-// doubles (may be uvec itself).
-template <typename T, int BLOCK>
+// doubles (may be uvec itself).  CF: loss = sum_p c_p (r_p - a_p.u^)^2 + alpha (u^^T G u^ - sum_p (a_p.u^)^2); u^^T G u^ by one
+// thread per column of G, the columns added by block_sum.
+template <typename T, int BLOCK, bool CF = false>
 __device__ __forceinline__ void ridge_finish(const T* __restrict__ F, const int32_t* __restrict__ item, const double* __restrict__ val, int n,
                                              double* uvec, int r, int ld, double mu, int form, int iters, int status, T* __restrict__ urow,
-                                             double* __restrict__ o, double* part, double* red) {
+                                             double* __restrict__ o, double* part, double* red, RidgeConf cf = RidgeConf()) {
     const int tid = threadIdx.x;
     const bool zero = status == PCR_RIDGE_SINGULAR;
     double nn = 0.0;
@@ -96,7 +129,18 @@ __device__ __forceinline__ void ridge_finish(const T* __restrict__ F, const int3
     for (int t = tid; t < r; t += BLOCK) uvec[t] = zero ? 0.0 : (double)(T)uvec[t];
     __syncthreads();
     nn = block_sum<BLOCK>(nn, red);
-    const double loss = ridge_loss<T, BLOCK>(F, item, val, n, uvec, r, ld, part);
+    double dd = 0.0;
+    double loss = ridge_loss<T, BLOCK, CF>(F, item, val, n, uvec, r, ld, part, cf, &dd);
+    if (CF && cf.alpha > 0.0) {                                          // (uniform)
+        double q = 0.0;
+        for (int t = tid; t < r; t += BLOCK) {
+            double s = 0.0;
+            for (int j = 0; j < r; ++j) s += cf.G[(size_t)j * cf.ldg + t] * uvec[j];
+            q += s * uvec[t];
+        }
+        const double ugu = block_sum<BLOCK>(q, red);
+        loss += cf.alpha * (ugu - dd);
+    }
     if (tid == 0) {
         o[0] = (double)n; o[1] = (double)form; o[2] = (double)iters; o[3] = loss; o[4] = loss + mu * nn; o[5] = (double)status;
     }
@@ -119,9 +163,13 @@ static inline size_t ridge_direct_bytes(int mp, int ld, int block) {
 //    the user's items in LDS); else M = A^T A + mu I (m = r) and the return value is b[tid] = (A^T r)[tid] for tid < mp.  Zc: the
 //    staging chunk [16][mp + 1], over which the tiles are written at the end (the caller's barrier makes them visible); rch: 16
 //    doubles.  Rows / columns beyond m are zeros with a unit diagonal, which the factorisation passes through unchanged.
-template <typename T, int BLOCK>
+//    CF (rch: 32 doubles; cw: the user's weights in LDS, mp of them, ones beyond n): the dual diagonal is mu / c_p; the primal
+//    accumulators start from alpha G's tiles (alpha > 0; mp == cf.ldg), the A operand of each staged rating is scaled by
+//    c_p - alpha (rch[16..31]) and b takes c_p r_p (rch[0..15]).
+template <typename T, int BLOCK, bool CF = false>
 __device__ __forceinline__ double ridge_gram(const T* __restrict__ F, const int32_t* __restrict__ uit, const double* __restrict__ uval, int n, int r, int ld,
-                                             int m, int mp, int dual, double mu, const int32_t* itm, double* rch, double* Zc) {
+                                             int m, int mp, int dual, double mu, const int32_t* itm, double* rch, double* Zc,
+                                             RidgeConf cf = RidgeConf(), const double* cw = nullptr) {
     constexpr int NW = BLOCK / PCR_WAVE, MAXM = BLOCK == 64 ? 64 : 112, MAXT = MAXM / 16;
     constexpr int MAXP = (MAXT * (MAXT + 1) / 2 + NW - 1) / NW;          // tile pairs per wave: 10 (one wave, 4 x 4 tiles) or 7 (four waves, 7 x 7)
     constexpr int RPP = BLOCK / 16, NREG = 16 * MAXM / BLOCK;            // staging: rows per pass, values per thread (16 or 7)
@@ -143,9 +191,13 @@ __device__ __forceinline__ double ridge_gram(const T* __restrict__ F, const int3
         int I = 0, rem = pr < npairs ? pr : 0;                       // pr -> (I, J), J <= I, row-major over the lower triangle
         while (rem > I) { rem -= I + 1; ++I; }
         offA[q] = I * 16 + row; offB[q] = rem * 16 + row;
+        if (CF && !dual && cf.alpha > 0.0 && pr < npairs) {              // (uniform) alpha G's tile (I, rem), in the accumulator's layout
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[q][e] = cf.alpha * cf.G[(size_t)(I * 16 + kh + 4 * e) * cf.ldg + rem * 16 + row];
+        }
     }
     T xr[NREG];
-    double rreg = 0.0;
+    double rreg = 0.0, wreg = 0.0;
     // issue(): the next chunk's values into registers; consume(): into the (idle) staging chunk as fp64.
     //   primal: thread (pp, t16) holds ratings c0 + pp + RPP j (j < 16 / RPP) x columns t16 + 16 k  -> Zc[rating][column]
     //   dual:   thread (pp, t16) holds column c0 + t16 of the user's rows pp + RPP j (j < NREG)      -> Zc[column][rating]
@@ -170,7 +222,13 @@ __device__ __forceinline__ double ridge_gram(const T* __restrict__ F, const int3
                     for (int k = 0; k < NCK; ++k) { const int c = t16 + 16 * k; if (c < r) xr[j * NCK + k] = frow[c]; }
                 }
             }
-            if (tid < 16) rreg = c0 + tid < n ? uval[c0 + tid] : 0.0;
+            if (CF) {
+                if (tid < 16) {
+                    const double c = c0 + tid < n ? cf.wt[c0 + tid] : 0.0;
+                    rreg = c0 + tid < n ? c * uval[c0 + tid] : 0.0;
+                    wreg = c0 + tid < n ? c - cf.alpha : 0.0;
+                }
+            } else if (tid < 16) rreg = c0 + tid < n ? uval[c0 + tid] : 0.0;
         }
     };
     auto consume = [&]() {
@@ -183,7 +241,7 @@ __device__ __forceinline__ double ridge_gram(const T* __restrict__ F, const int3
             for (int j = 0; j < 16 / RPP; ++j)
 #pragma unroll
                 for (int k = 0; k < NCK; ++k) { const int c = t16 + 16 * k; if (c < mp) Zc[(pp + RPP * j) * mps + c] = (double)xr[j * NCK + k]; }
-            if (tid < 16) rch[tid] = rreg;
+            if (tid < 16) { rch[tid] = rreg; if (CF) rch[16 + tid] = wreg; }
         }
     };
     double bacc = 0.0;                                               // primal: b[tid] = (A^T r)[tid]
@@ -196,9 +254,16 @@ __device__ __forceinline__ double ridge_gram(const T* __restrict__ F, const int3
 #pragma unroll 1
         for (int s4 = 0; s4 < 4; ++s4) {                             // (not unrolled: one k-step's operands in registers at a time)
             const int pb = (s4 * 4 + kh) * mps;
+            if (CF) {
+                const double wk = dual ? 1.0 : rch[16 + s4 * 4 + kh];
 #pragma unroll
-            for (int q = 0; q < MAXP; ++q)
-                if (wid + q * NW < npairs) acc[q] = ridge_mma(Zc[pb + offA[q]], Zc[pb + offB[q]], acc[q]);      // (wave-uniform)
+                for (int q = 0; q < MAXP; ++q)
+                    if (wid + q * NW < npairs) acc[q] = ridge_mma(Zc[pb + offA[q]] * wk, Zc[pb + offB[q]], acc[q]);
+            } else {
+#pragma unroll
+                for (int q = 0; q < MAXP; ++q)
+                    if (wid + q * NW < npairs) acc[q] = ridge_mma(Zc[pb + offA[q]], Zc[pb + offB[q]], acc[q]);      // (wave-uniform)
+            }
         }
         if (!dual && tid < mp) {
 #pragma unroll
@@ -219,7 +284,7 @@ __device__ __forceinline__ double ridge_gram(const T* __restrict__ F, const int3
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int rl = (lane >> 4) + 4 * e, rw = I * 16 + rl;
-                double v = acc[q][e] + (rw == col ? mu : 0.0);
+                double v = acc[q][e] + (rw == col ? ((CF && dual) ? mu / cw[rw] : mu) : 0.0);
                 if (rw >= m || col >= m) v = rw == col ? 1.0 : 0.0;
                 tile[rl * RIDGE_TP + cl] = v;
             }
@@ -359,20 +424,22 @@ __device__ __forceinline__ void ridge_trisolve(const double* Tl, const double* d
 // dual != 0: M = A A^T + mu I (m = n); else M = A^T A + mu I (m = r).  mp: the launch's padded side (a multiple of 16, at least
 // every user's m; BLOCK = 64: at most 64, BLOCK = 256: at most 112).  A user's results do not depend on mp: rows / columns beyond
 // m are zeros with a unit diagonal, which the factorisation passes through unchanged.
-template <typename T, int BLOCK>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2))) void k_ridge_direct(RidgeCsr X, const int32_t* __restrict__ users, int nusers, const T* __restrict__ F, int r, int ld,
-                                                        T* __restrict__ Uout, double* __restrict__ per_user, double lambda, int weighted, int dual,
-                                                        int mp) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+// The body of both kernels below.  CF (k_ridge_direct_conf): the weighted / implicit problem of RidgeConf above -- the dual form
+// runs at alpha == 0 only (pcr_conf_form), the primal form's mp is cf.ldg.
+template <typename T, int BLOCK, bool CF>
+__device__ __forceinline__ void ridge_direct_body(char* smem, RidgeCsr X, const int32_t* __restrict__ users, int nusers, const T* __restrict__ F, int r, int ld,
+                                                  T* __restrict__ Uout, double* __restrict__ per_user, double lambda, int weighted, int dual, int mp,
+                                                  RidgeConf cf) {
     Carver cv(smem);
     double* red = cv.take<double>(8);
     double* part = cv.take<double>(BLOCK / 16);
-    double* rch = cv.take<double>(16);                                   // the staged chunk's ratings (primal)
+    double* rch = cv.take<double>(CF ? 32 : 16);                         // the staged chunk's ratings (primal; CF: c r, then c - alpha)
     double* gv = cv.take<double>(mp);                                    // right-hand side, then the solution
     double* dinv = cv.take<double>(mp);                                  // 1 / L[i][i]
     double* rv = cv.take<double>(mp);                                    // dual: the user's ratings
     double* uvec = cv.take<double>(mp > ld ? mp : ld);
     int32_t* itm = cv.take<int32_t>(mp);                                 // dual: the user's items
+    double* cw = CF ? cv.take<double>(mp) : nullptr;                     // CF, dual: the user's weights
     double* Zc = reinterpret_cast<double*>(cv.p);                        // staging chunk [16][mp + 1] ...
     double* Tl = Zc;                                                     // ... and the tiles of M over it
     const int tid = threadIdx.x, wid = tid >> 6;
@@ -383,21 +450,26 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2))) void
         const int64_t s0 = X.uptr[u];
         const int n = (int)(X.uptr[u + 1] - s0);
         const int m = dual ? n : r;
-        const double mu = weighted ? lambda * (double)n : lambda;
+        const double mu = weighted ? lambda * (CF ? cf.W[u] : (double)n) : lambda;
         const int32_t* uit = X.item + s0;
         const double* uval = X.val + s0;
         T* urow = Uout + (size_t)u * ld;
         double* o = per_user + (size_t)u * PCR_RIDGE_FIELDS;
         const int form = dual ? PCR_RIDGE_DUAL : PCR_RIDGE_PRIMAL;
+        RidgeConf cu = cf;
+        if (CF) cu.wt = cf.wt + s0;
         if (n == 0) {                                                    // (uniform) a zero row, loss = obj = 0
             for (int t = tid; t < ld; t += BLOCK) urow[t] = (T)0;
             if (tid == 0) { o[0] = 0.0; o[1] = (double)form; o[2] = 0.0; o[3] = 0.0; o[4] = 0.0; o[5] = (double)PCR_RIDGE_OK; }
             continue;
         }
         if (dual)
-            for (int p = tid; p < mp; p += BLOCK) { itm[p] = p < n ? uit[p] : 0; rv[p] = p < n ? uval[p] : 0.0; }
+            for (int p = tid; p < mp; p += BLOCK) {
+                itm[p] = p < n ? uit[p] : 0; rv[p] = p < n ? uval[p] : 0.0;
+                if (CF) cw[p] = p < n ? cu.wt[p] : 1.0;
+            }
         __syncthreads();
-        const double bacc = ridge_gram<T, BLOCK>(F, uit, uval, n, r, ld, m, mp, dual, mu, itm, rch, Zc);
+        const double bacc = ridge_gram<T, BLOCK, CF>(F, uit, uval, n, r, ld, m, mp, dual, mu, itm, rch, Zc, cu, cw);
         for (int t = tid; t < mp; t += BLOCK) gv[t] = dual ? rv[t] : (t < m ? bacc : 0.0);      // (primal: mp <= BLOCK, one pass)
         if (tid == 0) red[7] = 0.0;                                      // "not positive definite" flag
         __syncthreads();
@@ -418,9 +490,26 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2))) void
             }
         }
         __syncthreads();
-        ridge_finish<T, BLOCK>(F, uit, uval, n, uvec, r, ld, mu, form, 0, bad ? PCR_RIDGE_SINGULAR : PCR_RIDGE_OK, urow, o, part, red);
+        ridge_finish<T, BLOCK, CF>(F, uit, uval, n, uvec, r, ld, mu, form, 0, bad ? PCR_RIDGE_SINGULAR : PCR_RIDGE_OK, urow, o, part, red, cu);
     }
 }
+
+template <typename T, int BLOCK>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2))) void k_ridge_direct(RidgeCsr X, const int32_t* __restrict__ users, int nusers, const T* __restrict__ F, int r, int ld,
+                                                        T* __restrict__ Uout, double* __restrict__ per_user, double lambda, int weighted, int dual,
+                                                        int mp) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    ridge_direct_body<T, BLOCK, false>(smem, X, users, nusers, F, r, ld, Uout, per_user, lambda, weighted, dual, mp, RidgeConf());
+}
+// The weighted / implicit instantiation (pcr_fold_in_conf*): the same stages on RidgeConf's problem
+template <typename T, int BLOCK>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2))) void k_ridge_direct_conf(RidgeCsr X, const int32_t* __restrict__ users, int nusers, const T* __restrict__ F, int r,
+                                                        int ld, T* __restrict__ Uout, double* __restrict__ per_user, double lambda, int weighted,
+                                                        int dual, int mp, RidgeConf cf) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    ridge_direct_body<T, BLOCK, true>(smem, X, users, nusers, F, r, ld, Uout, per_user, lambda, weighted, dual, mp, cf);
+}
+static inline size_t ridge_direct_conf_bytes(int mp, int ld, int block) { return ridge_direct_bytes(mp, ld, block) + carve_bytes(16, 8) + carve_bytes(mp, 8); }
 
 static inline size_t ridge_cg_bytes(int ld) {
     return carve_bytes(8, 8) + carve_bytes(16, 8) + 4 * carve_bytes(ld, 8) + carve_bytes(RIDGE_CG_CHUNK, 8) + carve_bytes(RIDGE_CG_CHUNK, 4);
@@ -430,14 +519,15 @@ static inline size_t ridge_cg_bytes(int ld) {
 //
 // out[t] (+)= sum over the user's ratings of w_p F[item p][t], w = the ratings (vec NULL) or the scores F[item p] . vec; in chunks of
 // RIDGE_CG_CHUNK ratings (scores by 16-lane groups, then one thread per column).  sc, itc: LDS, one chunk each.
-template <typename T>
+// CF: w = c_p r_p (vec NULL) or (c_p - alpha) F[item p] . vec.
+template <typename T, bool CF = false>
 __device__ __forceinline__ void ridge_cg_apply(const T* __restrict__ F, const int32_t* __restrict__ uit, const double* __restrict__ uval, int n, int r, int ld,
-                                               const double* vec, double* out, double* sc, int32_t* itc) {
+                                               const double* vec, double* out, double* sc, int32_t* itc, RidgeConf cf = RidgeConf()) {
     constexpr int BLOCK = 256, CH = RIDGE_CG_CHUNK;
     const int tid = threadIdx.x, g = tid & 15, gi = tid >> 4;
     for (int c0 = 0; c0 < n; c0 += CH) {
         const int cn = n - c0 < CH ? n - c0 : CH;
-        if (tid < cn) { itc[tid] = uit[c0 + tid]; if (!vec) sc[tid] = uval[c0 + tid]; }
+        if (tid < cn) { itc[tid] = uit[c0 + tid]; if (!vec) sc[tid] = CF ? cf.wt[c0 + tid] * uval[c0 + tid] : uval[c0 + tid]; }
         __syncthreads();
         if (vec) {
             for (int base = 0; base < cn; base += 16) {
@@ -448,7 +538,7 @@ __device__ __forceinline__ void ridge_cg_apply(const T* __restrict__ F, const in
                     for (int t = g; t < r; t += 16) d += (double)row[t] * vec[t];
                 }
                 d = ridge_sum16(d);
-                if (p < cn && g == 0) sc[p] = d;
+                if (p < cn && g == 0) sc[p] = CF ? (cf.wt[c0 + p] - cf.alpha) * d : d;
             }
             __syncthreads();
         }
@@ -466,10 +556,11 @@ __device__ __forceinline__ void ridge_cg_apply(const T* __restrict__ F, const in
 // and res = b.  pas == NULL: the whole system, side = r.  Else the system restricted to the coordinates with pas[t] != 0 (side =
 // npas of them; the caller has zeroed res on the others): the search direction stays zero outside them and Hp is masked to
 // them, Hp = mask(A^T (A p) + mu p).  Returns the status (PCR_RIDGE_OK / SINGULAR / CG_CAP); *iters: the iterations.
-template <typename T>
+// CF: Hp = A^T ((c - alpha) o (A p)) + alpha G p + mu p, G p by one thread per column of G; alpha > 0: at most 2 side + 10 iterations.
+template <typename T, bool CF = false>
 __device__ __forceinline__ int ridge_cg_solve(const T* __restrict__ F, const int32_t* __restrict__ uit, const double* __restrict__ uval, int n, int r, int ld,
                                               double mu, const int32_t* pas, int npas, double* uvec, double* res, double* pv, double* Hp, double* sc,
-                                              int32_t* itc, double* red, int* iters_out) {
+                                              int32_t* itc, double* red, int* iters_out, RidgeConf cf = RidgeConf()) {
     constexpr int BLOCK = 256;
     const int tid = threadIdx.x;
     double a = 0.0;
@@ -477,13 +568,21 @@ __device__ __forceinline__ int ridge_cg_solve(const T* __restrict__ F, const int
     double rr = block_sum<BLOCK>(a, red);
     const double stop = 1e-24 * rr;
     const int side = pas ? npas : r;
-    const int cap = 2 * (n < side ? n : side) + 10;
+    const int cap = (CF && cf.alpha > 0.0) ? 2 * side + 10 : 2 * (n < side ? n : side) + 10;
     int iters = 0, status = rr <= stop ? PCR_RIDGE_OK : PCR_RIDGE_CG_CAP;          // (b = 0: u = 0 is the answer)
     __syncthreads();
     for (int it = 0; it < cap && status == PCR_RIDGE_CG_CAP; ++it) {
-        for (int t = tid; t < r; t += BLOCK) Hp[t] = mu * pv[t];
+        if (CF && cf.alpha > 0.0) {                                      // (uniform)
+            for (int t = tid; t < r; t += BLOCK) {
+                double s = 0.0;
+                for (int j = 0; j < r; ++j) s += cf.G[(size_t)j * cf.ldg + t] * pv[j];
+                Hp[t] = mu * pv[t] + cf.alpha * s;
+            }
+        } else {
+            for (int t = tid; t < r; t += BLOCK) Hp[t] = mu * pv[t];
+        }
         __syncthreads();
-        ridge_cg_apply<T>(F, uit, uval, n, r, ld, pv, Hp, sc, itc);
+        ridge_cg_apply<T, CF>(F, uit, uval, n, r, ld, pv, Hp, sc, itc, cf);
         if (pas)
             for (int t = tid; t < r; t += BLOCK) if (!pas[t]) Hp[t] = 0.0;       // (the thread that wrote Hp[t])
         a = 0.0;
@@ -511,12 +610,12 @@ __device__ __forceinline__ int ridge_cg_solve(const T* __restrict__ F, const int
     return status;
 }
 
-// Matrix-free CG on (A^T A + mu I) u = A^T r from u = 0; 256 threads per user, any n and k.
-template <typename T>
-__global__ __launch_bounds__(256) void k_ridge_cg(RidgeCsr X, const int32_t* __restrict__ users, int nusers, const T* __restrict__ F, int r, int ld,
-                                                  T* __restrict__ Uout, double* __restrict__ per_user, double lambda, int weighted) {
+// Matrix-free CG on (A^T A + mu I) u = A^T r from u = 0; 256 threads per user, any n and k.  The body of both kernels below; CF
+// (k_ridge_cg_conf): RidgeConf's system.
+template <typename T, bool CF>
+__device__ __forceinline__ void ridge_cg_body(char* smem, RidgeCsr X, const int32_t* __restrict__ users, int nusers, const T* __restrict__ F, int r, int ld,
+                                              T* __restrict__ Uout, double* __restrict__ per_user, double lambda, int weighted, RidgeConf cf) {
     constexpr int BLOCK = 256, CH = RIDGE_CG_CHUNK;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     Carver cv(smem);
     double* red = cv.take<double>(8);
     double* part = cv.take<double>(16);
@@ -532,16 +631,120 @@ __global__ __launch_bounds__(256) void k_ridge_cg(RidgeCsr X, const int32_t* __r
         const int u = users[ui];
         const int64_t s0 = X.uptr[u];
         const int n = (int)(X.uptr[u + 1] - s0);
-        const double mu = weighted ? lambda * (double)n : lambda;
+        const double mu = weighted ? lambda * (CF ? cf.W[u] : (double)n) : lambda;
         const int32_t* uit = X.item + s0;
         const double* uval = X.val + s0;
+        RidgeConf cu = cf;
+        if (CF) cu.wt = cf.wt + s0;
         for (int t = tid; t < r; t += BLOCK) { uvec[t] = 0.0; res[t] = 0.0; }
         __syncthreads();
-        ridge_cg_apply<T>(F, uit, uval, n, r, ld, nullptr, res, sc, itc);               // b = A^T r: the first residual and direction
+        ridge_cg_apply<T, CF>(F, uit, uval, n, r, ld, nullptr, res, sc, itc, cu);       // b = A^T r: the first residual and direction
         int iters = 0;
-        const int status = ridge_cg_solve<T>(F, uit, uval, n, r, ld, mu, nullptr, 0, uvec, res, pv, Hp, sc, itc, red, &iters);
-        ridge_finish<T, BLOCK>(F, uit, uval, n, uvec, r, ld, mu, PCR_RIDGE_CG, iters, status, Uout + (size_t)u * ld,
-                               per_user + (size_t)u * PCR_RIDGE_FIELDS, part, red);
+        const int status = ridge_cg_solve<T, CF>(F, uit, uval, n, r, ld, mu, nullptr, 0, uvec, res, pv, Hp, sc, itc, red, &iters, cu);
+        ridge_finish<T, BLOCK, CF>(F, uit, uval, n, uvec, r, ld, mu, PCR_RIDGE_CG, iters, status, Uout + (size_t)u * ld,
+                                   per_user + (size_t)u * PCR_RIDGE_FIELDS, part, red, cu);
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_ridge_cg(RidgeCsr X, const int32_t* __restrict__ users, int nusers, const T* __restrict__ F, int r, int ld,
+                                                  T* __restrict__ Uout, double* __restrict__ per_user, double lambda, int weighted) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    ridge_cg_body<T, false>(smem, X, users, nusers, F, r, ld, Uout, per_user, lambda, weighted, RidgeConf());
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_ridge_cg_conf(RidgeCsr X, const int32_t* __restrict__ users, int nusers, const T* __restrict__ F, int r, int ld,
+                                                       T* __restrict__ Uout, double* __restrict__ per_user, double lambda, int weighted, RidgeConf cf) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    ridge_cg_body<T, true>(smem, X, users, nusers, F, r, ld, Uout, per_user, lambda, weighted, cf);
+}
+
+// ---- the catalogue Gram G = F^T F of the implicit forms (alpha > 0), fp64, once per call, any rank.
+// The columns are cut into panels of RIDGE_CAT_PANEL (4 tiles of 16), the rows into nb row blocks -- ridge_catgram_blocks: a
+// function of (rows, k) alone, never of the device or the grid.  Workgroup (b, panel pair PI >= PJ) of k_ridge_catgram walks its
+// row block in slabs of 16 rows: the slab's two column panels are staged in LDS as fp64 (the next slab's loads in flight
+// meanwhile) and the 16 tile pairs (4 x 4; the lower triangle on a diagonal panel pair) are dealt to the four waves, 4 each, on
+// v_mfma_f64_16x16x4_f64.  It writes its PARTIAL tiles, in the accumulator's layout; k_ridge_catgram_sum adds the nb partials of
+// every entry in block order and writes both triangles of G [ldg][ldg], ldg = roundup(k, 16) (columns beyond the rank are read
+// as zeros, so G's pad rows and columns are zeros).  No atomics, no counters: the workgroups meet at the kernel boundary only.
+#define RIDGE_CAT_PANEL 64
+#define RIDGE_CAT_LDS (2 * RIDGE_CAT_PANEL + 1)
+static inline int ridge_catgram_pairs(int64_t k) { const int64_t np = (k + RIDGE_CAT_PANEL - 1) / RIDGE_CAT_PANEL; return (int)(np * (np + 1) / 2); }
+static inline int ridge_catgram_blocks(int64_t rows, int64_t k) {        // 1024 rows per block, at most 64 blocks and 256 MB of partials
+    const int64_t by_rows = std::min<int64_t>(64, (rows + 1023) / 1024), per_block = (int64_t)ridge_catgram_pairs(k) * 16 * 256 * 8;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(by_rows, ((int64_t)256 << 20) / per_block));
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_ridge_catgram(const T* __restrict__ F, int64_t rows, int r, int ld, int nb, double* __restrict__ part) {
+    __shared__ double Z[16 * RIDGE_CAT_LDS];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int row = lane & 15, kh = lane >> 4, pp = tid >> 4, t16 = tid & 15;
+    const int nt = (r + 15) / 16;
+    int PI = 0, PJ = (int)blockIdx.y;                                    // panel pair, row-major over the lower triangle
+    while (PJ > PI) { PJ -= PI + 1; ++PI; }
+    const int64_t per = ((rows + nb - 1) / nb + 15) / 16 * 16;           // rows per block, a multiple of the slab
+    const int64_t r0 = (int64_t)blockIdx.x * per, r1 = r0 + per < rows ? r0 + per : rows;
+    ridge_f64x4 acc[4];
+    bool live[4];
+    int offA[4], offB[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int t = wid + 4 * q, ti = t >> 2, tj = t & 3, gI = PI * 4 + ti, gJ = PJ * 4 + tj;
+        live[q] = gI < nt && gJ < nt && gI >= gJ;                        // (wave-uniform)
+        offA[q] = ti * 16 + row; offB[q] = RIDGE_CAT_PANEL + tj * 16 + row;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[q][e] = 0.0;
+    }
+    T xr[8];
+    auto issue = [&](int64_t p0) {                                       // row p0 + pp, columns t16 + 16 j of panel PI (j < 4) and PJ
+        const int64_t p = p0 + pp;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = (j < 4 ? PI : PJ) * RIDGE_CAT_PANEL + t16 + 16 * (j & 3);
+            xr[j] = (p < r1 && c < r) ? F[(size_t)p * ld + c] : (T)0;
+        }
+    };
+    auto consume = [&]() {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) Z[pp * RIDGE_CAT_LDS + 16 * j + t16] = (double)xr[j];
+    };
+    if (r0 < r1) { issue(r0); consume(); }
+    __syncthreads();
+    for (int64_t p0 = r0; p0 < r1; p0 += 16) {
+        const bool more = p0 + 16 < r1;
+        if (more) issue(p0 + 16);
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            const int pb = (s4 * 4 + kh) * RIDGE_CAT_LDS;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (live[q]) acc[q] = ridge_mma(Z[pb + offA[q]], Z[pb + offB[q]], acc[q]);
+        }
+        __syncthreads();
+        if (more) { consume(); __syncthreads(); }
+    }
+    double* out = part + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * (16 * 256);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        if (live[q]) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) out[(wid + 4 * q) * 256 + e * 64 + lane] = acc[q][e];
+        }
+}
+
+// G's tile t of panel pair blockIdx.x: the nb partials of each entry added in block order; both triangles are written
+__global__ __launch_bounds__(256) void k_ridge_catgram_sum(const double* __restrict__ part, int nb, int r, int ldg, double* __restrict__ G) {
+    const int tid = threadIdx.x, lane = tid & 63, e = tid >> 6;
+    const int nt = (r + 15) / 16, npair = (int)gridDim.x, t = (int)blockIdx.y;
+    int PI = 0, PJ = (int)blockIdx.x;
+    while (PJ > PI) { PJ -= PI + 1; ++PI; }
+    const int gI = PI * 4 + (t >> 2), gJ = PJ * 4 + (t & 3);
+    if (gI >= nt || gJ >= nt || gI < gJ) return;                         // (uniform) the tiles k_ridge_catgram left out
+    double s = 0.0;
+    for (int b = 0; b < nb; ++b) s += part[((size_t)b * npair + blockIdx.x) * (16 * 256) + t * 256 + e * 64 + lane];
+    const int i = gI * 16 + (lane >> 4) + 4 * e, j = gJ * 16 + (lane & 15);
+    G[(size_t)i * ldg + j] = s;
+    if (gI != gJ) G[(size_t)j * ldg + i] = s;
 }
 

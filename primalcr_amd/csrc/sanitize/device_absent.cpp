@@ -161,6 +161,13 @@ int pcr_fold_in_ridge_model(const double* F, int64_t rows, int64_t k, double lam
     return rc != PCR_OK ? rc : absent();
 }
 NO_SOLVER(pcr_fold_in_ridge, pcr_solver*, int, int64_t, const int64_t*, const int32_t*, const double*, double*, pcr_ridge_stats*, double*)
+int pcr_fold_in_conf_model(const double* F, int64_t rows, int64_t k, double lambda, int, double alpha, int precision, int, int64_t n, const int64_t* index,
+                           const int32_t* item, const double* val, const double* weight, double* U_out, pcr_ridge_stats*, double*) {
+    const int rc = pcr_fold_in_conf_check("pcr_fold_in_conf_model", true, F, rows, k, lambda, alpha, precision, n, index, item, val, weight, U_out, nullptr);
+    return rc != PCR_OK ? rc : absent();
+}
+NO_SOLVER(pcr_fold_in_conf, pcr_solver*, int, double, int64_t, const int64_t*, const int32_t*, const double*, const double*, double*, pcr_ridge_stats*,
+          double*)
 int pcr_fold_in_nnls_model(const double* F, int64_t rows, int64_t k, double lambda, int, int precision, int, int64_t n, const int64_t* index,
                            const int32_t* item, const double* val, double* U_out, pcr_nnls_stats*, double*) {
     const int rc = pcr_fold_in_nnls_check("pcr_fold_in_nnls_model", true, F, rows, k, lambda, precision, n, index, item, val, U_out, nullptr);
